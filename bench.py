@@ -13,8 +13,13 @@ Every instance is solved to the reference's IPOPT tolerance (tol 1e-8, max_iter 
 solves per second, whole job.  With N > 1 each rank solves its own B instances on its own GPU (weak scaling, instances
 are independent: no data-path collective) and ONE packed block per rank -- the result rows of the step with their status and
 iteration counts -- is all-gathered over RCCL, on RCCL's own stream while the next batch is being solved (`--gather overlap`, the
-default; the last gathers are waited for inside the timed region) or inside the step (`--gather sync`); the collective alone is timed
-too (`gather.gather_ms_alone`), and the statistics of the line are reduced over the ranks.
+default; the last gathers are waited for inside the timed region) or inside the step (`--gather sync`); with `--full` the collective
+alone is timed too (`gather.gather_ms_alone`), and the statistics of the line are reduced over the ranks.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` = wall time of the K steps / K, ...);
+`roofline`, `fixed20`, `cpu_baseline`, `configs` and `other_paths` are null there.  `--full` adds all of them (below).
+`--dump-outputs DIR` writes what the last timed step returned -- result rows `x`, `status`, `iters`, `kkt` of rank 0's instances
+(`result_rows` for `--workload mixed`) -- as DIR/<name>.npy in float64; the inputs depend on the arguments alone.
 
 `--gpus N` without a torch.distributed launcher (WORLD_SIZE unset) starts the N ranks itself and FAILS when fewer than N
 devices are visible; it never reports a smaller n_gpus than it was asked for.
@@ -24,7 +29,7 @@ problem families, one handle and one stream per family -- solved concurrently, c
 all-gather at the end).
 
 Prints ONE JSON line on rank 0 (contract of the build driver; compact: < 2000 characters, arrays where the long form has
-objects -- the long form goes to stderr as `[bench detail] {...}` and to `--detail FILE`) with extra objects:
+objects -- the long form goes to stderr as `[bench detail] {...}` and to `--detail FILE`) with extra objects under `--full`:
   roofline      the iteration loop of a solve = ONE launch of k_pipeline (tiles with many instances iterating) followed by ONE launch
                 of k_solve_wg (the stragglers, one wavefront per two instances): algorithmic bytes of the instance-iterations
                 each performed / its mean launch duration (HIP events on the solve stream, a second, profiled pass over the
@@ -59,6 +64,7 @@ N_HORIZON, NX, NU, BATCH = 30, 6, 2, 4096
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
 JSON_OUT = sys.stdout            # main() swaps it for a private copy of file descriptor 1
 HOST_CPUS = 1                    # main() counts the host cpus before the OpenMP runtime pins the main thread
+DUMP_LIMIT = 60 * 1000 * 1000   # --dump-outputs: bytes of array data in all (the files stay below 64 MB)
 PUBLISHED_CASADI = "25.1 steps/s (N=10, 1 instance, unknown CPU, graph rebuilt every step; BASELINE.md section 1: 36-41 ms per step)"
 
 
@@ -179,9 +185,14 @@ def casadi_probe(fam, x0, p, wl):
 
 
 def spawn_ranks(args):
-    """--gpus N without a launcher: become `torch.distributed.run` with N ranks -- or fail; never measure fewer GPUs than asked"""
-    import torch
-    have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    """--gpus N without a launcher: run `torch.distributed.run` with N ranks as a child and exit with its status -- or fail; never measure
+    fewer GPUs than asked.  This process never opens a device: the count comes from a short-lived child of its own."""
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                           capture_output=True, text=True)
+    try:
+        have = int(probe.stdout.strip().splitlines()[-1])
+    except (ValueError, IndexError):
+        have = 0
     if have < args.gpus:
         raise SystemExit("bench.py --gpus %d: only %d GPU(s) visible on this host -- refusing to report a %d-GPU figure from fewer devices"
                          % (args.gpus, have, args.gpus))
@@ -190,8 +201,9 @@ def spawn_ranks(args):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execv(sys.executable, cmd)
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def forces_setup(B, local_rank=0):
@@ -251,15 +263,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--workload", choices=("headline", "mixed"), default="headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC passes (roofline.traffic falls back to the committed figure)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the roofline passes (HIP events, copy bandwidth, rocprofv3 PMC traffic), the "
+                         "fixed-20 variant, the CPU baseline, configurations 2 - 5, the side paths and the collective on its own.  Without it a "
+                         "run sets up, warms up, times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's rows) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-traffic", action="store_true",
+                    help="with --full: skip the rocprofv3 PMC passes (roofline.traffic falls back to the committed figure)")
     ap.add_argument("--gather", choices=("overlap", "sync"), default="overlap",
                     help="multi-GPU: the all-gather of a step's result rows runs on RCCL's stream under the next solve (overlap, default) or "
                          "is waited for inside the step (sync) -- the fallback should the collective starve behind the persistent kernel")
     ap.add_argument("--detail", default=None, help="write the full (long) result object to this file; it goes to stderr anyway")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed converged-mode steps and their roofline pass (no fixed-20 variant, configurations 2 - 5, side paths): "
-                         "under `rocprofv3 --kernel-trace --stats` the averages of k_pipeline<6> / k_solve_wg<6> are then those of the bench line")
+                    help="with --full: only the timed converged-mode steps and their roofline pass (no fixed-20 variant, configurations 2 - 5, side "
+                         "paths); under `rocprofv3 --kernel-trace --stats` the averages of k_pipeline<6> / k_solve_wg<6> are then those of the "
+                         "bench line (as they are for a run without --full)")
     ap.add_argument("--pmc-child", nargs="?", const="mpc", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.pmc_child:
@@ -391,6 +411,8 @@ def main():
     value = world * B * args.steps / dt
     med = float(np.median(per))
     st, it, kkt = d_st.cpu().numpy(), d_it.cpu().numpy(), d_kkt.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(x=d_outs[(n_step[0] - 1) % len(d_outs)].cpu().numpy(), status=st, iters=it, kkt=kkt))
     # (over ALL ranks' rows; the roofline pass below stays this rank's own launch statistics)
     allst = sharding.solve_stats_over_ranks(st, it, device=dev) if world > 1 else dict(converged_frac=float((st == 1).mean()), mean_iters=float(it.mean()), max_iters=int(it.max()))
     converged, mean_it_all, max_it = allst["converged_frac"], allst["mean_iters"], allst["max_iters"]
@@ -398,7 +420,7 @@ def main():
     kkt_max = sharding.max_over_ranks(float(kkt.max()), device=dev) if world > 1 else float(kkt.max())
     # the collective on its own: K gathers with nothing else on the machine, and a check of what arrived
     gather_info = None
-    if gather:
+    if gather and args.full:
         drain()
         barrier()
         tg = time.perf_counter()
@@ -412,6 +434,24 @@ def main():
                            bytes_per_rank=B * PW * 8, own_rows_round_trip=ok,
                            pipeline_abandoned=bool(solver.get_option("pipe_aborts")),       # (a persistent launch starved by the collective's workgroups would show here)
                            wait_ms_in_step=(gather_wait[0] / gather_wait[1] * 1e3) if gather_wait[1] else None)
+
+    def result(**extra):
+        return dict(metric="MPC steps/sec (N=30, nx=6 nu=2) at batch=4096", value=value, unit="MPC steps/s", n_gpus=world,
+                    steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step, higher_is_better=True, scaling="weak",
+                    vs_baseline=None, dtype="f64", data="synthetic",
+                    config=dict(workload="N=30 nx=6 nu=2 kinematic-bicycle lane-following (ZAM_Over-1_1 LF weights, dummy "
+                                         "obstacle), batch=%d per GPU, solved to tol 1e-8 (max_iter 100)" % B,
+                                batch_per_gpu=B, horizon=fam.N, nx=fam.nx, nu=2, parallelism="independent instances x%d" % world,
+                                mode="converged", gpu=torch.cuda.get_device_name(dev)),
+                    ms_per_step_median=med * 1e3, value_median_batch=world * B / med if world == 1 else None,
+                    converged_frac=converged, mean_iters=mean_it_all, max_iters=max_it, kkt_max=kkt_max, gather=gather_info, **extra)
+
+    if not args.full:                                    # a plain run: the headline figure and nothing else
+        if rank == 0:
+            emit(result(fixed20=None, roofline=None, cpu_baseline=None, configs=None, other_paths=None), args)
+        if gather:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline: second pass over the same K steps with HIP events around every kernel launch
     ab = algorithmic_bytes(fam.N, fam.nx)
@@ -576,17 +616,7 @@ def main():
         other_paths = side_paths(torch, mpc_amd, fam, B, local_rank, traffic=not args.no_traffic)
 
     if rank == 0:
-        out = dict(metric="MPC steps/sec (N=30, nx=6 nu=2) at batch=4096", value=value, unit="MPC steps/s", n_gpus=world,
-                   steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step, higher_is_better=True, scaling="weak",
-                   vs_baseline=None, dtype="f64", data="synthetic",
-                   config=dict(workload="N=30 nx=6 nu=2 kinematic-bicycle lane-following (ZAM_Over-1_1 LF weights, dummy "
-                                        "obstacle), batch=%d per GPU, solved to tol 1e-8 (max_iter 100)" % B,
-                               batch_per_gpu=B, horizon=fam.N, nx=fam.nx, nu=2, parallelism="independent instances x%d" % world,
-                               mode="converged", gpu=torch.cuda.get_device_name(dev)),
-                   ms_per_step_median=med * 1e3, value_median_batch=world * B / med if world == 1 else None,
-                   converged_frac=converged, mean_iters=mean_it_all, max_iters=max_it, kkt_max=kkt_max, gather=gather_info,
-                   fixed20=fixed20, roofline=roofline, cpu_baseline=cpu_baseline, configs=configs, other_paths=other_paths)
-        emit(out, args)
+        emit(result(fixed20=fixed20, roofline=roofline, cpu_baseline=cpu_baseline, configs=configs, other_paths=other_paths), args)
     if gather:
         dist.destroy_process_group()
 
@@ -613,7 +643,7 @@ def compact_line(out):
                 roofline=dict(bound=r["bound"], kernel=r["kernel"], achieved=_g(r["achieved"]), peak=r["peak"], unit=r["unit"], frac=_g(r["frac"], 4),
                               traffic=_g(r["traffic"]), avg_launch_us=_g(r["avg_launch_us"]), bytes_per_launch=_g(r["algorithmic_bytes_per_launch"]),
                               copy_bw=_g(r.get("measured_copy_bw_gbs"), 4), whole_step=_g(r["whole_step"]["frac"], 4), limiter=r["limiter"],
-                              kernels={k: [_g(v["avg_us"], 4), _g(v["gbs"], 4), _g(v["frac"], 3)] for k, v in r["kernels"].items()}))
+                              kernels={k: [_g(v["avg_us"], 4), _g(v["gbs"], 4), _g(v["frac"], 3)] for k, v in r["kernels"].items()}) if r else None)
     if cb:
         line["cpu_baseline"] = dict(value=_g(cb["value"]), unit=cb["unit"], cores=cb["cores"], kind=cb["kind"], sample=cb["sample_short"],
                                     one_thread=_g(cb["single_thread_value"], 4), sweep={k: _g(v, 3) for k, v in cb["sweep_steps_per_s"].items()},
@@ -641,6 +671,20 @@ def compact_line(out):
     if out.get("gather"):
         line["gather"] = {k: _g(v, 4) for k, v in out["gather"].items()}
     return line
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs DIR: one DIR/<name>.npy (float64) per array the timed path returned in its last step.  The arrays share their first axis
+    (instance / row); should they exceed `limit` bytes together, the rows of a fixed seeded sample are written, their indices as rows.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    if n * row_bytes > limit:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=limit // (row_bytes + 8), replace=False))
+        arrays = dict({k: a[keep] for k, a in arrays.items()}, rows=keep.astype(np.float64))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
 
 
 def emit(out, args):
@@ -850,6 +894,9 @@ def run_mixed(args, torch, dist, mpc_amd, sharding, wl, world, rank, local_rank,
             sharding.gather_packed(d_res, gathered)
 
     dt, per = timed(step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        # (the rank's block as a caller receives it: result rows in global order padded to one width, then status and iterations)
+        dump_outputs(args.dump_outputs, dict(result_rows=d_res.cpu().numpy()))
     value = world * per_gpu * args.steps / dt
     fams = {}
     for q in parts:

@@ -951,7 +951,7 @@ def test_rccl_all_gather_of_the_packed_block_beside_the_pipeline():
         env = dict(os.environ, MPC_BENCH_FORCE_GATHER="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29610 + (mode == "sync")))
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
             env.pop(k, None)
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--headline-only", "--no-cpu-baseline", "--no-traffic", "--steps", "12",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--headline-only", "--no-cpu-baseline", "--no-traffic", "--steps", "12",
                             "--warmup", "2", "--gather", mode], env=env, capture_output=True, text=True, timeout=600, cwd=root)
         assert r.returncode == 0, r.stderr[-3000:]
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

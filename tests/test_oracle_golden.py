@@ -118,7 +118,7 @@ def test_forces_model_kat_dynamics(golden_dir):
     assert n > 40
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PATH), reason="oracle/_ref not built (needs /root/reference)")
+@pytest.mark.skipif(not os.path.exists(REF_PATH), reason="oracle/_ref not built: the reference's sources were absent when build() ran")
 def test_forces_model_ref_reproduces_fixture(golden_dir):
     kat = np.load(os.path.join(golden_dir, "forces_model_kat.npz"))
     ref = ForcesModelRef()

@@ -198,3 +198,33 @@ def test_bench_line_is_compact_and_carries_the_contract():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and isinstance(cb["sample"], str)
     assert [c[0] for c in line["configs"]] == ["2", "3", "4", "5"] and all(len(c) == 9 for c in line["configs"])
     assert len(line["fixed20"]) == 2 and "forces_sqp" in line["other_paths"]
+
+
+def test_plain_bench_line_and_output_dump(tmp_path):
+    """a run without --full: the same contract keys with the extra objects null; --dump-outputs writes float64 .npy files, and a fixed seeded
+    sample of the rows (with their indices) once the arrays exceed the limit"""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    long_form = json.load(open(os.path.join(ROOT, "tests", "golden", "bench_detail_sample.json")))
+    long_form.update(fixed20=None, roofline=None, cpu_baseline=None, configs=None, other_paths=None, gather=None)
+    line = bench.compact_line(long_form)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] == (long_form[k] if k not in ("value", "ms_per_step") else bench._g(long_form[k], 6 if k == "value" else 5)), k
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "configs" not in line
+    rng = np.random.default_rng(3)
+    arrays = dict(x=rng.normal(size=(100, 7)), status=np.ones(100, np.int32), kkt=rng.random(100))
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    assert not (tmp_path / "all" / "rows.npy").exists()
+    limit = 30 * (9 * 8 + 8)                                      # room for 30 of the 100 rows and their indices
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    rows = np.load(tmp_path / "s1" / "rows.npy")
+    assert len(rows) == 30 and np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy")) and np.all(np.diff(rows) > 0)
+    assert sum(np.load(tmp_path / "s1" / (k + ".npy")).nbytes for k in list(arrays) + ["rows"]) <= limit
+    assert np.array_equal(np.load(tmp_path / "s1" / "x.npy"), arrays["x"][rows.astype(int)])
