@@ -122,6 +122,35 @@ int mpc_last_rescued(const mpc_handle* h);
 int mpc_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst,
                         double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt, void* stream);
 
+/* The rest of what CasADi's `sol(...)` returns (`res['f']`, `res['g']`, `res['lam_g']`, `res['lam_x']`).
+ * n_g = 1 + nx(N+1) + 9(N+1) rows in the order of mpc_set_bounds: row 0 the friction row, then the x_0 pin (nx rows), then the
+ * defects x_{k+1} - x_k - dt f(x_k, u_k) (nx rows per k), then per stage k the three circle-pair distances, each three times in a row
+ * (optimizer.py:395-403; the solver weights the copies by obst_mult).
+ *
+ * mpc_eval_nlp_batch: objective f [B] and all rows g [B, n_g] of the reference's NLP at ANY x [B, n_w] with parameters p [B, n_w]
+ * and obstacle centres obst [B, 6] (NULL: the descriptor's).  g is the literal row: row 0 is sqrt((a_0^2 + v_0^2 tan(delta_0)/2.578)^2)
+ * whatever "friction_lb" says; f is the reference's cost sum_{k<N} |x_k - xref_{k+1}|_Q^2 + |u_k|_R^2 (its terminal term is dead code).
+ * Either output may be NULL.  Does not need mpc_set_bounds.                                                                         */
+int mpc_eval_nlp_batch(mpc_handle* h, int32_t B, const double* x, const double* p, const double* obst, double* f, double* g);
+int mpc_eval_nlp_batch_dev(mpc_handle* h, int32_t B, const double* d_x, const double* d_p, const double* d_obst,
+                           double* d_f, double* d_g, void* stream);
+
+/* mpc_solve_batch[_dev] plus f [B] and g [B, n_g] at the returned x, and the multipliers lam_g [B, n_g], lam_x [B, n_w] of the final
+ * iterate; any of the four may be NULL, and with all four NULL the call IS mpc_solve_batch[_dev] (same kernels, same bits).
+ * Multipliers follow CasADi: grad f + J_g' lam_g + lam_x = 0 at the solution; lam_x = z_U - z_L (an active lower bound negative, an
+ * active upper bound positive, exactly 0 where a variable has no finite bound); lam_g by the same sign rule per row, equality rows either
+ * sign; the three copies of a circle row carry equal multipliers that sum to that distance's multiplier.
+ * Rows with status != 1 get NaN in lam_g and lam_x (a row that failed may carry its first attempt's x, which the last iterate does not
+ * belong to); f and g are always evaluated at the returned x.  lam_g[0] is NaN where the friction row sits exactly on its kink
+ * a_0^2 + v_0^2 tan(delta_0)/2.578 = 0 (not differentiable there).  Asking for a multiplier with fixed_iters > 0 -> MPC_ERR_INVALID.
+ * The _dev form synchronises `stream` when any of the four is asked for.                                                            */
+int mpc_solve_batch_ex(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst,
+                       double* x_out, int32_t* status, int32_t* iters, double* kkt,
+                       double* f, double* g, double* lam_g, double* lam_x);
+int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst,
+                           double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt,
+                           double* d_f, double* d_g, double* d_lam_g, double* d_lam_x, void* stream);
+
 /* Batched plant step on the device path: x_next = x + dt f(x,u) (integrator 0 = forward Euler,
  * optimizer.py:649-650) or one RK4 step (integrator 1, optimizer.py:97-98).  x: [B, nx], u: [B, 2] host. */
 int mpc_plant_step(mpc_handle* h, int32_t B, int32_t integrator, const double* x, const double* u, double* x_next);

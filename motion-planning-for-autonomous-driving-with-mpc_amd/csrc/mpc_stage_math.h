@@ -2317,4 +2317,147 @@ MPC_HD void output_instance(const PRef& P, int b) {
     if (P.kkt_out) P.kkt_out[b] = MPC_U(P.SC, (uint32_t)SC_E0);
 }
 
+// =========================================================================================================
+// The NLP as the caller states it (mpc_eval_nlp_batch, the f / g outputs of mpc_solve_batch_ex) and the solver's multipliers mapped
+// onto its rows (lam_g / lam_x).  One call per (instance, stage); plain pointers, no workspace accessors: the same code runs in the
+// kernels k_eval_nlp / k_mult_out and in the CPU harness of the tests.
+// Rows of g (n_g = 1 + nx (N + 1) + 9 (N + 1), the rows of mpc_set_bounds): 0 friction | 1 .. nx the x_0 pin | nx per defect k -> k + 1 |
+// 9 per stage: circle pair j (j = 0, 1, 2) three times (optimizer.py:395-403).
+// =========================================================================================================
+MPC_HD int nlp_n_g(const Params& P) { return 1 + P.nx * (P.N + 1) + 9 * (P.N + 1); }
+
+// stage k of instance (w, pr: its rows of x and p, obst: its six circle centres): the g rows stage k owns (row 0 and the pin at k = 0,
+// the defect k-1 -> k at k >= 1, the circle rows of stage k) -> g (the instance's row, may be null); returns the stage's cost term
+template <int NX>
+MPC_HD double nlp_eval_stage(const Params& P, const double* w, const double* pr, const double* obst, const int k, double* g) {
+    const int N = P.N;
+    const double* x = w + 2 * N + NX * k;
+    double fk = 0.0;
+    if (k < N) {
+        const double* u = w + 2 * k;
+        const double* rn = pr + 2 * N + NX * (k + 1);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            const double e = x[i] - rn[i];
+            fk += P.Q[i] * e * e;
+        }
+        fk += P.R[0] * u[0] * u[0] + P.R[1] * u[1] * u[1];
+    }
+    if (g == nullptr) return fk;
+    if (k == 0) {
+        g[0] = friction_eval(P, w[1], x[2], x[3], nullptr, nullptr, false);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) g[1 + i] = x[i] - pr[2 * N + i];
+    } else {
+        const double* xp = w + 2 * N + NX * (k - 1);
+        const double* up = w + 2 * (k - 1);
+        double f[NX], s, c, td;
+        ode_eval<NX>(P, xp, up, f, s, c, td);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) g[1 + NX * k + i] = x[i] - (f[i] * P.dt + xp[i]);
+    }
+    double sps, cps;
+    mpc_sincos(x[4], sps, cps);
+    const int r0 = 1 + NX * (N + 1) + 9 * k;
+    for (int j = 0; j < 3; ++j) {
+        const double d = circle_eval(P, obst, j, x[0], x[1], sps, cps, nullptr, nullptr, false);
+        for (int q = 0; q < 3; ++q) g[r0 + 3 * j + q] = d;
+    }
+    return fk;
+}
+
+// Where the final iterate of an instance lies: the tile-major rows (MPC_K) or the instance-major mailbox (MPC_KI, k_solve_wg)
+MPC_HD size_t mult_tile_index(const Params& P, const int R, const int k, const int e, const int b) {
+    return ws_index(P, (const double*)nullptr, (uint32_t)(k * (int)MPC_EV(R) + e), (uint32_t)b);
+}
+MPC_HD size_t mult_mb_index(const Params& P, const int R, const int k, const int e, const int b) {
+    return (size_t)b * (size_t)(P.N + 1) * MPC_EV(R) + (size_t)(e >> 1) * (size_t)(P.N + 1) * 2 + (size_t)k * 2 + (size_t)(e & 1);
+}
+MPC_HD double mult_row(const Params& P, const double* tile, const double* mb, const bool in_mb, const int R, const int k, const int e, const int b) {
+    return in_mb ? mb[mult_mb_index(P, R, k, e, b)] : tile[mult_tile_index(P, R, k, e, b)];
+}
+
+// Multipliers of stage k of instance b in CasADi's convention, grad f + J_g' lam_g + lam_x = 0: the kernels' multipliers of the objective
+// scaled by df (SC_DF) are divided by it; lam_x = z_U - z_L, 0 where the variable has no finite bound; the kernels carry the copies of a
+// circle row once, with weight m = obst_mult and multiplier nu: each of the three copies of the NLP gets m nu / 3 (nu itself for the
+// reference's m = 3).  The stage-0 friction row:
+//   kept as a row (IS_FROW != 0; friction_lb = ipopt, or |a_0^2 + c| <= a_max is not one interval): lam_g[0] = nu_f / df
+//   presolved into bounds of a_0 (prestart_a0_of): a side of a_0 whose bound is tighter than the caller's lbx / ubx comes from the row,
+//     lam_g[0] = (z_U - z_L of those sides) / (d g_0 / d a_0), d g_0 / d a_0 = 2 a_0 sign(a_0^2 + c); the pin rows give back what the row
+//     gradient adds in (delta_0, v_0): lam_pin -= lam_g[0] d g_0 / d (delta_0, v_0)
+//   at the kink a_0^2 + c = 0 (the row is not differentiable there) lam_g[0] = NaN.
+// w: the instance's returned row of x (the friction row's gradient is taken there).  lam_g / lam_x: the instance's output rows.
+template <int NX>
+MPC_HD void mult_stage(const Params& P, const int b, const int k, const bool in_mb, const double* w, double* lam_g, double* lam_x) {
+    constexpr int NZ = NX + 2;
+    const int N = P.N;
+    const double wm = P.obst_mult / 3.0;
+    const double idf = 1.0 / P.SC[ws_index(P, P.SC, (uint32_t)SC_DF, (uint32_t)b)];
+    double zl[NZ], zu[NZ], lam[NX];
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+        zl[i] = mult_row(P, P.ZL, P.MZL, in_mb, NZ, k, i, b);
+        zu[i] = mult_row(P, P.ZU, P.MZU, in_mb, NZ, k, i, b);
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) lam[i] = mult_row(P, P.LAM, P.MLAM, in_mb, NX, k, i, b) * idf;
+    // bound multipliers
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) {
+        if (i < 2 && k == N) continue;
+        const double lb = P.LB[k * NZ + i], ub = P.UB[k * NZ + i];
+        double v = 0.0;
+        if (has_lo(lb)) v -= zl[i];
+        if (has_hi(ub)) v += zu[i];
+        if (k == 0 && i == 1) continue;              // a_0: below, with the friction row
+        lam_x[i < 2 ? 2 * k + i : 2 * N + NX * k + (i - 2)] = v * idf;
+    }
+    if (k == 0) {
+        const double a = w[1], dl = w[2 * N + 2], v0 = w[2 * N + 3];
+        double gr[3], h[4];
+        friction_eval(P, a, dl, v0, gr, h, true);
+        const bool kink = a * a + v0 * (tan(dl) * v0 / P.friction_div) == 0.0;        // (friction_eval's sign(0) = 0: a zero gradient)
+        const bool frow = P.ISC[ws_index(P, P.ISC, (uint32_t)IS_FROW, (uint32_t)b)] != 0;
+        const double a0lb = P.SC[ws_index(P, P.SC, (uint32_t)SC_A0LB, (uint32_t)b)], a0ub = P.SC[ws_index(P, P.SC, (uint32_t)SC_A0UB, (uint32_t)b)];
+        const double lb = P.LB[1], ub = P.UB[1];
+        double lg0, zx = 0.0;
+        if (frow) {
+            lg0 = P.SC[ws_index(P, P.SC, (uint32_t)SC_NUF, (uint32_t)b)] * idf;
+            if (has_lo(lb)) zx -= zl[1];
+            if (has_hi(ub)) zx += zu[1];
+        } else {
+            // sides of a_0 that the presolved row set (tighter than the caller's bound), and those that are the caller's own
+            double zr = 0.0;
+            if (has_lo(a0lb)) { if (a0lb > lb) zr -= zl[1]; else zx -= zl[1]; }
+            if (has_hi(a0ub)) { if (a0ub < ub) zr += zu[1]; else zx += zu[1]; }
+            lg0 = (gr[0] != 0.0) ? zr * idf / gr[0] : 0.0;
+            lam[2] -= lg0 * gr[1];
+            lam[3] -= lg0 * gr[2];
+        }
+        lam_x[1] = zx * idf;
+        lam_g[0] = kink ? NAN : lg0;
+#pragma unroll
+        for (int i = 0; i < NX; ++i) lam_g[1 + i] = lam[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) lam_g[1 + NX * k + i] = lam[i];
+    }
+    const int r0 = 1 + NX * (N + 1) + 9 * k;
+    for (int j = 0; j < 3; ++j) {
+        const double nu = mult_row(P, P.NUO, P.MNUO, in_mb, 3, k, j, b) * idf * wm;
+        for (int q = 0; q < 3; ++q) lam_g[r0 + 3 * j + q] = nu;
+    }
+}
+// the rows mult_stage writes for stage k, all set to v (NaN: the instance did not converge)
+template <int NX>
+MPC_HD void mult_stage_fill(const Params& P, const int k, const double v, double* lam_g, double* lam_x) {
+    const int N = P.N;
+    if (k < N) { lam_x[2 * k] = v; lam_x[2 * k + 1] = v; }
+    for (int i = 0; i < NX; ++i) lam_x[2 * N + NX * k + i] = v;
+    if (k == 0) lam_g[0] = v;
+    for (int i = 0; i < NX; ++i) lam_g[1 + NX * k + i] = v;
+    const int r0 = 1 + NX * (N + 1) + 9 * k;
+    for (int q = 0; q < 9; ++q) lam_g[r0 + q] = v;
+}
+
 }  // namespace mpc

@@ -2442,6 +2442,77 @@ __global__ void k_rescue_scatter(const int32_t* idx, int nw, const int32_t* st, 
         if (kkt_out) kkt_out[b] = kkt[j];
     }
 }
+// the multipliers of the last level beside it (mpc_solve_batch_ex): the same rows, the same rule
+__global__ void k_rescue_scatter_mult(const int32_t* idx, int nw, int ng, const int32_t* st, const double* lg, const double* lx, double* lam_g,
+                                      double* lam_x) {
+    const int j = blockIdx.x, b = idx[j];
+    if (st[j] != 1) return;
+    if (lam_g) for (int q = threadIdx.x; q < ng; q += blockDim.x) lam_g[(size_t)b * ng + q] = lg[(size_t)j * ng + q];
+    if (lam_x) for (int q = threadIdx.x; q < nw; q += blockDim.x) lam_x[(size_t)b * nw + q] = lx[(size_t)j * nw + q];
+}
+
+// ---- the NLP's objective / constraints and the solver's multipliers on its rows (mpc_eval_nlp_batch, mpc_solve_batch_ex) -----------------
+// One thread per (instance, stage), 256-thread blocks of 256 / (N + 1) instances; the math is nlp_eval_stage / mult_stage of
+// mpc_stage_math.h (the CPU harness of the tests runs the same functions).
+constexpr int NLP_OUT_THREADS = 256;
+template <int NX>
+__global__ void __launch_bounds__(NLP_OUT_THREADS) k_eval_nlp(const Params P, const double* x, const double* p, const double* obst, double* f, double* g) {
+    __shared__ double fpart[NLP_OUT_THREADS];
+    const int S = P.N + 1, ipb = NLP_OUT_THREADS / S, t = threadIdx.x, li = t / S, k = t - li * S;
+    const int b = blockIdx.x * ipb + li;
+    const bool valid = li < ipb && b < P.B;
+    const size_t nw = (size_t)2 * P.N + (size_t)NX * S, ng = (size_t)nlp_n_g(P);
+    double fk = 0.0;
+    if (valid) {
+        double ob[6];
+        for (int i = 0; i < 6; ++i) ob[i] = obst ? obst[(size_t)b * 6 + i] : P.obst[i];
+        fk = nlp_eval_stage<NX>(P, x + (size_t)b * nw, p + (size_t)b * nw, ob, k, g ? g + (size_t)b * ng : nullptr);
+    }
+    fpart[t] = fk;
+    __syncthreads();
+    if (valid && k == 0 && f) {
+        double s = 0.0;
+        for (int q = 0; q < S; ++q) s += fpart[li * S + q];
+        f[b] = s;
+    }
+}
+// The multipliers of the final iterate of every instance of a solve that just ran on this workspace.  Where that iterate lies is told by
+// the primal rows: the mailbox (MZ; the host filled it with NaN before the solve) when k_solve_wg served the instance, the tile-major Z
+// otherwise -- whichever equals the returned row of x_out bit for bit.  No match, or a status other than 1: NaN.
+template <int NX>
+__global__ void __launch_bounds__(NLP_OUT_THREADS) k_mult_out(const Params P, const int has_mb, const double* x_out, const int32_t* status, double* lam_g,
+                                                              double* lam_x) {
+    __shared__ int miss[2][NLP_OUT_THREADS];
+    constexpr int NZ = NX + 2;
+    const int N = P.N, S = N + 1, ipb = NLP_OUT_THREADS / S, t = threadIdx.x, li = t / S, k = t - li * S;
+    const int b = blockIdx.x * ipb + li;
+    const bool valid = li < ipb && b < P.B;
+    const size_t nw = (size_t)2 * N + (size_t)NX * S, ng = (size_t)nlp_n_g(P);
+    if (t < ipb) { miss[0][t] = has_mb ? 0 : 1; miss[1][t] = 0; }
+    __syncthreads();
+    if (valid) {
+        const double* w = x_out + (size_t)b * nw;
+        bool mm = false, mt = false;
+        for (int i = 0; i < NZ; ++i) {
+            if (i < 2 && k == N) continue;
+            const double xv = w[i < 2 ? 2 * k + i : 2 * N + NX * k + (i - 2)];
+            if (has_mb) mm |= P.MZ[mult_mb_index(P, NZ, k, i, b)] != xv;
+            mt |= P.Z[mult_tile_index(P, NZ, k, i, b)] != xv;
+        }
+        if (mm) atomicOr(&miss[0][li], 1);
+        if (mt) atomicOr(&miss[1][li], 1);
+    }
+    __syncthreads();
+    if (!valid) return;
+    double* lg = lam_g + (size_t)b * ng;
+    double* lx = lam_x + (size_t)b * nw;
+    const bool in_mb = miss[0][li] == 0, in_tile = miss[1][li] == 0;
+    if (status[b] != 1 || !(in_mb || in_tile)) {
+        mult_stage_fill<NX>(P, k, NAN, lg, lx);
+        return;
+    }
+    mult_stage<NX>(P, b, k, in_mb, x_out + (size_t)b * nw, lg, lx);
+}
 
 template <int NX>
 __global__ void k_plant_step(const Params Pk, const double* x, const double* u, double* xn, int B, int integrator) {
@@ -2546,7 +2617,10 @@ struct mpc_handle {
         uint32_t pipe_xcd_mask = 0;
     } knobs;
     // grow-only device scratch of the entry points around the solve (plant step, metrics, FORCES mode): slot -> buffer
-    static constexpr int N_SCRATCH = 40;
+    static constexpr int N_SCRATCH = 44;
+    // mpc_solve_batch[_dev]_ex: where the multipliers of the running solve go ([B, n_g] / [B, n_w] rows of the caller, or null = not asked for)
+    double* mo_lam_g = nullptr;
+    double* mo_lam_x = nullptr;
     void* scratch[N_SCRATCH] = {};
     size_t scratch_cap[N_SCRATCH] = {};
 };
@@ -3628,6 +3702,34 @@ static int solve_dev_any(mpc_handle* h, int32_t B, const double* d_x0, const dou
     return solve_dev_impl<6>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it);
 }
 
+// ---- multipliers of a solve (mpc_solve_batch_ex): read back from the workspace behind the solve, the loop kernels are not touched -------
+// Before a solve whose multipliers will be read: the workspace in place (what solve_dev_impl would allocate) and the mailbox copy of the
+// iterate NaN, so that k_mult_out tells by the primal rows which instances k_solve_wg served in THIS solve.
+static int mult_prepare(mpc_handle* h, int32_t B, hipStream_t stream) {
+    const mpc_problem_desc& d = h->hp.desc;
+    const size_t Bp = ((size_t)B + 63) / 64 * 64;
+    const int rc = ensure_ws(h, Bp);
+    if (rc) return rc;
+    if (h->ws_mailbox) {
+        const WsLayout w = ws_layout(d.N, d.nx, Bp, true);
+        HIP_TRY(h, hipMemsetAsync(h->d_ws + w.MZ, 0xFF, Bp * (size_t)(d.N + 1) * MPC_EV(d.nx + 2) * sizeof(double), stream));
+    }
+    return MPC_OK;
+}
+// after it: lam_g [B, n_g], lam_x [B, n_w] of the B instances the last solve on this workspace left (x_out, status: that solve's)
+static int mult_read(mpc_handle* h, int32_t B, const double* d_x_out, const int32_t* d_status, double* lam_g, double* lam_x, hipStream_t stream) {
+    const mpc_problem_desc& d = h->hp.desc;
+    const size_t Bp = ((size_t)B + 63) / 64 * 64;
+    Params P;
+    fill_params(P, h->hp, B, Bp, 1, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
+    const int ipb = NLP_OUT_THREADS / (d.N + 1);
+    const dim3 grid((B + ipb - 1) / ipb);
+    if (d.nx == 5) hipLaunchKernelGGL((k_mult_out<5>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, h->ws_mailbox ? 1 : 0, d_x_out, d_status, lam_g, lam_x);
+    else hipLaunchKernelGGL((k_mult_out<6>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, h->ws_mailbox ? 1 : 0, d_x_out, d_status, lam_g, lam_x);
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+
 // Second chance for the instances of a batch that did not converge, on the device and behind the C-ABI.  IPOPT hands a start
 // that is locally infeasible -- typically a guess that runs straight through the obstacle, where the linearised circle rows
 // cannot be met within the fraction-to-the-boundary rule -- to its feasibility-restoration phase, which is not restated here
@@ -3660,17 +3762,30 @@ static int rescue_dev(mpc_handle* h, int32_t B, const double* d_x0, const double
         hipLaunchKernelGGL(k_rescue_gather, dim3(n), dim3(128), 0, stream, idx, (int)nw, d_x0, d_p, d_obst, xs, ps, os, acc);
         const double* fr = pass == 0 ? pass1 : pass2;
         const int nfr = pass == 0 ? 2 : 5;
+        // (mpc_solve_batch_ex: the multipliers of the last level, the original problem, go back beside its rows)
+        const size_t ng = h->hp.n_g();
+        double* mlg = nullptr;
+        if (h->mo_lam_g) {
+            mlg = static_cast<double*>(scratch_get(h, 38, (size_t)n * (ng + nw) * 8));
+            if (!mlg) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
+        }
         for (int q = 0; q < nfr && rc == MPC_OK; ++q) {
             h->hp.ol = relax_lo(fr[q] * h->hp.ol_raw);
             h->hp.desc.tol = (q + 1 < nfr) ? std::max(tol_keep, 1e-4) : tol_keep;      // intermediate levels only produce warm starts
+            if (mlg && q + 1 == nfr) rc = mult_prepare(h, n, stream);
+            if (rc != MPC_OK) break;
             h->in_rescue = true;
             rc = solve_dev_any(h, n, xs, ps, d_obst ? os : nullptr, out, st, it, kk, stream, nullptr, 0, nullptr);
             h->in_rescue = false;
+            if (rc == MPC_OK && mlg && q + 1 == nfr) rc = mult_read(h, n, out, st, mlg, mlg + (size_t)n * ng, stream);
             if (rc == MPC_OK) hipLaunchKernelGGL(k_rescue_carry, dim3(n), dim3(128), 0, stream, (int)nw, st, it, out, xs, acc);
         }
         h->hp.ol = ol_keep;
         h->hp.desc.tol = tol_keep;
         if (rc == MPC_OK) hipLaunchKernelGGL(k_rescue_scatter, dim3(n), dim3(128), 0, stream, idx, (int)nw, st, out, kk, acc, d_x_out, d_status, d_iters, d_kkt);
+        if (rc == MPC_OK && mlg)
+            hipLaunchKernelGGL(k_rescue_scatter_mult, dim3(n), dim3(128), 0, stream, idx, (int)nw, (int)ng, st, mlg, mlg + (size_t)n * ng, h->mo_lam_g,
+                               h->mo_lam_x);
         if (pass == 0) h->rescued_last = n;
     }
     h->hp.ol = ol_keep;
@@ -3720,12 +3835,16 @@ static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double*
         const size_t max_b = max_rows_per_solve(h);
         if ((size_t)B > max_b && !trace && !h->async_loop) {
             const size_t nw = h->hp.n_w();
+            const size_t ng = h->hp.n_g();
+            double *mlg = h->mo_lam_g, *mlx = h->mo_lam_x;
             int rescued = 0;
             for (size_t off = 0; off < (size_t)B; off += max_b) {
                 const int32_t n = (int32_t)std::min(max_b, (size_t)B - off);
+                if (mlg) { h->mo_lam_g = mlg + off * ng; h->mo_lam_x = mlx + off * nw; }
                 const int rcc = solve_dev(h, n, d_x0 + off * nw, d_p + off * nw, d_obst ? d_obst + off * 6 : nullptr, d_x_out + off * nw,
                                           d_status ? d_status + off : nullptr, d_iters ? d_iters + off : nullptr, d_kkt ? d_kkt + off : nullptr, stream,
                                           nullptr, 0, nullptr);
+                h->mo_lam_g = mlg; h->mo_lam_x = mlx;
                 if (rcc) return rcc;
                 rescued += h->rescued_last;
             }
@@ -3734,7 +3853,12 @@ static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double*
         }
     }
     h->resc_in_kernel = h->resc_ran = false;
-    const int rc = solve_dev_any(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it);
+    if (h->mo_lam_g) {
+        const int rm = mult_prepare(h, B, stream);
+        if (rm) return rm;
+    }
+    int rc = solve_dev_any(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it);
+    if (rc == MPC_OK && h->mo_lam_g) rc = mult_read(h, B, d_x_out, d_status, h->mo_lam_g, h->mo_lam_x, stream);
     // (converged mode: the solve has synchronised the stream; a launch of k_solve_wg with the second chance inside has given every stalled
     //  instance its levels already)
     // (what the next solve of this handle does about stalled instances: see resc_cond)
@@ -3806,6 +3930,110 @@ int mpc_solve_batch(mpc_handle* h, int32_t B, const double* x0, const double* p,
 int mpc_solve_batch_trace(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out,
                           int32_t* status, int32_t* iters, double* kkt, double* trace, int32_t trace_rows, int32_t* n_it) {
     return solve_host(h, B, x0, p, obst, x_out, status, iters, kkt, trace, trace_rows, n_it);
+}
+
+// objective and constraint rows of the reference's NLP at B points (k_eval_nlp); f / g may be null
+int mpc_eval_nlp_batch_dev(mpc_handle* h, int32_t B, const double* d_x, const double* d_p, const double* d_obst, double* d_f, double* d_g,
+                           void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !d_x || !d_p) { h->err = "B > 0 and x, p are required"; return MPC_ERR_INVALID; }
+    if (!d_f && !d_g) return MPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const mpc_problem_desc& d = h->hp.desc;
+    Params P;
+    fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, nullptr, nullptr, h->d_LB, h->d_UB, false);
+    const int ipb = NLP_OUT_THREADS / (d.N + 1);
+    const dim3 grid((B + ipb - 1) / ipb);
+    hipStream_t s = (hipStream_t)stream_;
+    if (d.nx == 5) hipLaunchKernelGGL((k_eval_nlp<5>), grid, dim3(NLP_OUT_THREADS), 0, s, P, d_x, d_p, d_obst, d_f, d_g);
+    else hipLaunchKernelGGL((k_eval_nlp<6>), grid, dim3(NLP_OUT_THREADS), 0, s, P, d_x, d_p, d_obst, d_f, d_g);
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_eval_nlp_batch(mpc_handle* h, int32_t B, const double* x, const double* p, const double* obst, double* f, double* g) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !x || !p) { h->err = "B > 0 and x, p are required"; return MPC_ERR_INVALID; }
+    if (!f && !g) return MPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t nw = h->hp.n_w(), nB = (size_t)B;
+    const size_t ng = h->hp.n_g();
+    double* buf = static_cast<double*>(scratch_get(h, 39, nB * (2 * nw + 6 + 1 + ng) * 8));
+    if (!buf) { h->err = "eval: out of device memory"; return MPC_ERR_HIP; }
+    double *dx = buf, *dp = dx + nB * nw, *dob = dp + nB * nw, *df = dob + nB * 6, *dg = df + nB;
+    hipStream_t s = h->own_stream;
+    HIP_TRY(h, hipMemcpyAsync(dx, x, nB * nw * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(dp, p, nB * nw * 8, hipMemcpyHostToDevice, s));
+    if (obst) HIP_TRY(h, hipMemcpyAsync(dob, obst, nB * 6 * 8, hipMemcpyHostToDevice, s));
+    const int rc = mpc_eval_nlp_batch_dev(h, B, dx, dp, obst ? dob : nullptr, f ? df : nullptr, g ? dg : nullptr, (void*)s);
+    if (rc) return rc;
+    if (f) HIP_TRY(h, hipMemcpyAsync(f, df, nB * 8, hipMemcpyDeviceToHost, s));
+    if (g) HIP_TRY(h, hipMemcpyAsync(g, dg, nB * ng * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MPC_OK;
+}
+
+// mpc_solve_batch_dev plus the NLP's objective / rows at the returned x and the multipliers of the final iterate (all four optional; none
+// asked for: exactly mpc_solve_batch_dev)
+int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
+                           int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
+                           void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    const bool mult = d_lam_g || d_lam_x;
+    if (!mult && !d_f && !d_g) return solve_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, s, nullptr, 0, nullptr);
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !d_x0 || !d_p || !d_x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
+    if (mult && h->hp.desc.fixed_iters > 0) { h->err = "multipliers need a solve to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (mult) {
+        const size_t nw = h->hp.n_w(), nB = (size_t)B;
+        const size_t ng = h->hp.n_g();
+        if (!d_status) d_status = static_cast<int32_t*>(scratch_get(h, 40, nB * 4));
+        if (!d_lam_g) d_lam_g = static_cast<double*>(scratch_get(h, 41, nB * ng * 8));
+        if (!d_lam_x) d_lam_x = static_cast<double*>(scratch_get(h, 41, nB * nw * 8));
+        if (!d_status || !d_lam_g || !d_lam_x) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    }
+    h->mo_lam_g = mult ? d_lam_g : nullptr;
+    h->mo_lam_x = mult ? d_lam_x : nullptr;
+    int rc = solve_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, s, nullptr, 0, nullptr);
+    h->mo_lam_g = h->mo_lam_x = nullptr;
+    if (rc == MPC_OK && (d_f || d_g)) rc = mpc_eval_nlp_batch_dev(h, B, d_x_out, d_p, d_obst, d_f, d_g, (void*)s);
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MPC_OK;
+}
+
+int mpc_solve_batch_ex(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out, int32_t* status,
+                       int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x) {
+    if (!f && !g && !lam_g && !lam_x) return solve_host(h, B, x0, p, obst, x_out, status, iters, kkt, nullptr, 0, nullptr);
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !x0 || !p || !x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure_io(h, (size_t)B);
+    if (rc) return rc;
+    const size_t nw = h->hp.n_w(), nB = (size_t)B;
+    const size_t ng = h->hp.n_g();
+    double* buf = static_cast<double*>(scratch_get(h, 37, nB * (1 + 2 * ng + nw) * 8));
+    if (!buf) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    double *df = buf, *dg = df + nB, *dlg = dg + nB * ng, *dlx = dlg + nB * ng;
+    hipStream_t s = h->own_stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, nB * nw * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_p, p, nB * nw * sizeof(double), hipMemcpyHostToDevice, s));
+    if (obst) HIP_TRY(h, hipMemcpyAsync(h->d_obst, obst, nB * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    const bool mult = lam_g || lam_x;
+    rc = mpc_solve_batch_dev_ex(h, B, h->d_x0, h->d_p, obst ? h->d_obst : nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt, f ? df : nullptr,
+                                g ? dg : nullptr, mult ? dlg : nullptr, mult ? dlx : nullptr, (void*)s);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(x_out, h->d_xout, nB * nw * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(h, hipMemcpyAsync(status, h->d_status, nB * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (iters) HIP_TRY(h, hipMemcpyAsync(iters, h->d_iters, nB * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (kkt) HIP_TRY(h, hipMemcpyAsync(kkt, h->d_kkt, nB * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (f) HIP_TRY(h, hipMemcpyAsync(f, df, nB * 8, hipMemcpyDeviceToHost, s));
+    if (g) HIP_TRY(h, hipMemcpyAsync(g, dg, nB * ng * 8, hipMemcpyDeviceToHost, s));
+    if (lam_g) HIP_TRY(h, hipMemcpyAsync(lam_g, dlg, nB * ng * 8, hipMemcpyDeviceToHost, s));
+    if (lam_x) HIP_TRY(h, hipMemcpyAsync(lam_x, dlx, nB * nw * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MPC_OK;
 }
 
 int mpc_plant_step_dev(mpc_handle* h, int32_t B, int32_t integrator, const double* d_x, const double* d_u, double* d_x_next, void* stream_) {

@@ -112,7 +112,11 @@ class NlpSolution(dict):
 
 class NlpSolverHandle:
     """`ca.nlpsol('solver', 'ipopt', nlp_prob, opts)` look-alike (optimizer.py:558): callable with the same
-    keyword arguments as optimizer.py:607.  Accepts a single instance ((n_w,1) / (n_w,)) or a batch [B, n_w]."""
+    keyword arguments as optimizer.py:607.  Accepts a single instance ((n_w,1) / (n_w,)) or a batch [B, n_w].
+
+    The result has CasADi's keys: 'x' (n_w,1), 'f' (1,1), 'g' and 'lam_g' (n_g,1), 'lam_x' (n_w,1) -- rows [B, .] for a batch; lam_g /
+    lam_x are NaN for an instance whose status is not 1 (include/mpcgpu.h, mpc_solve_batch_ex).  'f', 'g', 'lam_*' come with a
+    BatchedMPCSolver backend only.  A dual warm start (lam_x0 / lam_g0) is not taken: those keywords are accepted and ignored."""
 
     # failed instances get a second chance by homotopy on the obstacle radius: on the device, behind the C-ABI
     # (mpc_solve_batch; include/mpcgpu.h).  A backend without that (the stand-in backends of the tests) gets the same
@@ -134,7 +138,8 @@ class NlpSolverHandle:
             pa = pa.reshape(1, -1)
         if lbg is not None or lbx is not None or ubg is not None or ubx is not None:
             be.set_bounds(lbx, ubx, lbg, ubg)
-        res = be.solve(x0a, pa)
+        full = isinstance(be, BatchedMPCSolver)
+        res = be.solve(x0a, pa, multipliers=True) if full else be.solve(x0a, pa)
         rescued = np.zeros(res.status.shape[0], dtype=bool)
         n_rescued = int(be.last_rescued()) if hasattr(be, "last_rescued") else 0      # the second chance behind the C-ABI (a count, not a mask)
         if (self.rescue and not isinstance(be, BatchedMPCSolver) and not np.all(res.status == 1) and lbg is not None and lbx is not None
@@ -145,6 +150,12 @@ class NlpSolverHandle:
                            return_status="Solve_Succeeded" if np.all(res.status == 1) else "Not_Converged")
         x = res.x if batched else res.x.reshape(-1, 1)
         out = NlpSolution(x=DMLike(x))
+        if full:
+            if batched:
+                out["f"], out["g"], out["lam_g"], out["lam_x"] = (DMLike(a) for a in (res.f, res.g, res.lam_g, res.lam_x))
+            else:
+                out["f"] = DMLike(res.f.reshape(1, 1))
+                out["g"], out["lam_g"], out["lam_x"] = (DMLike(a.reshape(-1, 1)) for a in (res.g, res.lam_g, res.lam_x))
         out["status"] = res.status
         return out
 

@@ -34,6 +34,11 @@ class SolveResult:
     status: np.ndarray     # [B] int32, 1 converged / 0 max-iter / -6 NaN / -7 no progress
     iters: np.ndarray      # [B] int32
     kkt: np.ndarray        # [B] scaled KKT error at exit
+    # solve(..., multipliers=True): what CasADi's `sol(...)` returns besides x (include/mpcgpu.h, mpc_solve_batch_ex)
+    f: np.ndarray | None = None        # [B] objective at x
+    g: np.ndarray | None = None        # [B, n_g] constraint rows at x (order of mpc_set_bounds)
+    lam_g: np.ndarray | None = None    # [B, n_g] multipliers of the rows, NaN where status != 1
+    lam_x: np.ndarray | None = None    # [B, n_w] multipliers of the bounds (z_U - z_L), NaN where status != 1
 
 
 class BatchedMPCSolver:
@@ -102,7 +107,27 @@ class BatchedMPCSolver:
         self._bounds_key = key
         self._bounds = tuple(a.copy() for a in arrs)            # (lbx, ubx, lbg, ubg), for rescue_failed()
 
-    def solve(self, x0, p, obst=None) -> SolveResult:
+    def eval_nlp(self, x, p, obst=None):
+        """objective f [B] and constraint rows g [B, n_g] of the reference's NLP at any x [B, n_w] (mpc_eval_nlp_batch)."""
+        x = _abi.f64(x)
+        p = _abi.f64(p)
+        if x.ndim == 1:
+            x = x[None]
+        if p.ndim == 1:
+            p = p[None]
+        B = x.shape[0]
+        if x.shape != (B, self.n_w) or p.shape != (B, self.n_w):
+            raise MpcError(_abi.MPC_ERR_INVALID, f"x/p must be [B, {self.n_w}]")
+        if obst is not None:
+            obst = _abi.f64(obst, (B, 6))
+        f = np.empty(B)
+        g = np.empty((B, self.n_g))
+        self._check(self._lib.mpc_eval_nlp_batch(self._h, B, _abi.as_dp(x), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(f), _abi.as_dp(g)))
+        return f, g
+
+    def solve(self, x0, p, obst=None, *, multipliers=False) -> SolveResult:
+        """B instances at once.  multipliers=True: also f, g at the returned x and the multipliers lam_g, lam_x (CasADi's convention:
+        grad f + J_g' lam_g + lam_x = 0) in the result (mpc_solve_batch_ex)."""
         x0 = _abi.f64(x0)
         p = _abi.f64(p)
         if x0.ndim == 1:
@@ -118,9 +143,15 @@ class BatchedMPCSolver:
         status = np.empty(B, np.int32)
         iters = np.empty(B, np.int32)
         kkt = np.empty(B, np.float64)
-        self._check(self._lib.mpc_solve_batch(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out),
-                                              _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt)))
-        return SolveResult(out, status, iters, kkt)
+        if not multipliers:
+            self._check(self._lib.mpc_solve_batch(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out),
+                                                  _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt)))
+            return SolveResult(out, status, iters, kkt)
+        f, g, lam_g, lam_x = np.empty(B), np.empty((B, self.n_g)), np.empty((B, self.n_g)), np.empty((B, self.n_w))
+        self._check(self._lib.mpc_solve_batch_ex(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out),
+                                                 _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt), _abi.as_dp(f), _abi.as_dp(g),
+                                                 _abi.as_dp(lam_g), _abi.as_dp(lam_x)))
+        return SolveResult(out, status, iters, kkt, f, g, lam_g, lam_x)
 
     def last_rescued(self):
         """instances of the last solve that took the second chance of the C-ABI (mpc_last_rescued)"""
@@ -157,11 +188,17 @@ class BatchedMPCSolver:
                                                     _abi.as_ip(n_it)))
         return SolveResult(out, status, iters, kkt), trace[: int(n_it[0]) + 1]
 
-    def solve_device(self, B, d_x0, d_p, d_x_out, d_status=0, d_iters=0, d_kkt=0, d_obst=0, stream=0):
-        """device pointers (ints, e.g. torch.Tensor.data_ptr()) and a hipStream_t handle (int, 0 = default)."""
+    def solve_device(self, B, d_x0, d_p, d_x_out, d_status=0, d_iters=0, d_kkt=0, d_obst=0, stream=0, d_f=0, d_g=0, d_lam_g=0, d_lam_x=0):
+        """device pointers (ints, e.g. torch.Tensor.data_ptr()) and a hipStream_t handle (int, 0 = default).  d_f [B], d_g / d_lam_g
+        [B, n_g], d_lam_x [B, n_w]: the extra outputs of mpc_solve_batch_dev_ex (0 = not asked for)."""
         vp = C.c_void_p
-        self._check(self._lib.mpc_solve_batch_dev(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out),
-                                                  vp(d_status or None), vp(d_iters or None), vp(d_kkt or None), vp(stream or None)))
+        if not (d_f or d_g or d_lam_g or d_lam_x):
+            self._check(self._lib.mpc_solve_batch_dev(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out),
+                                                      vp(d_status or None), vp(d_iters or None), vp(d_kkt or None), vp(stream or None)))
+            return
+        self._check(self._lib.mpc_solve_batch_dev_ex(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out), vp(d_status or None),
+                                                     vp(d_iters or None), vp(d_kkt or None), vp(d_f or None), vp(d_g or None), vp(d_lam_g or None),
+                                                     vp(d_lam_x or None), vp(stream or None)))
 
     def plant_step(self, x, u, integrator="euler"):
         x = _abi.f64(x)
