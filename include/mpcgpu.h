@@ -151,6 +151,28 @@ int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const d
                            double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt,
                            double* d_f, double* d_g, double* d_lam_g, double* d_lam_x, void* stream);
 
+/* Parametric sensitivities of the returned optimum (sIPOPT's step).  p = [U_ref (N nu) | X_ref ((N+1) nx)], n_p = n_w.
+ * mpc_solve_batch[_dev]_ex plus: lam_p [B, n_p] (NULL: not computed), CasADi's d/dp [f + lam_g' g + lam_x' x] at the returned x (X_ref column 0
+ * -lam_g[pin rows], column k+1 -2 Q (x_k - xref_{k+1}), U_ref 0); n_dir >= 0 forward seeds dp [B, n_dir, n_p] -> dw [B, n_dir, n_w] = (dw/dp) dp
+ * from the KKT matrix of the final barrier iterate, without regularisation.  Keeps the final iterates for mpc_sens_adjoint.  x_out .. lam_x are
+ * bit for bit those of mpc_solve_batch[_dev]_ex; with lam_p NULL and n_dir 0 nothing more is written.  Rows with status != 1 get NaN in lam_p
+ * and dw, and so do rows whose final KKT matrix has the wrong inertia (a Riccati pivot <= 0) or that sit on the friction kink (lam_g[0] NaN).
+ * fixed_iters > 0 -> MPC_ERR_INVALID.  Derivatives with respect to the obstacle centres, the bounds and x0 are not provided.
+ * The _dev form synchronises `stream`.                                                                                                     */
+int mpc_solve_batch_sens(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out,
+                         int32_t* status, int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x,
+                         double* lam_p, int32_t n_dir, const double* dp, double* dw);
+int mpc_solve_batch_sens_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
+                             int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
+                             double* d_lam_p, int32_t n_dir, const double* d_dp, double* d_dw, void* stream);
+/* Reverse mode on the last mpc_solve_batch_sens[_dev] of this handle: seed_w [B, n_w] -> grad_p [B, n_p] = (dw/dp)' seed_w (NaN rows as above).
+ * Any solve of the handle after it (plain, _ex, closed loop, FORCES), or a different B -> MPC_ERR_STATE.  The _dev form is enqueued on
+ * `stream` and does not synchronise it: it reads the handle's snapshot and writes the handle's factor storage when it runs, so until it has
+ * completed the caller must not start another mpc_solve_batch_sens[_dev] or mpc_sens_adjoint[_dev] of this handle on a different stream
+ * (on the same stream, stream order takes care of it; the handle is not for concurrent use from several streams, as for every entry).         */
+int mpc_sens_adjoint(mpc_handle* h, int32_t B, const double* seed_w, double* grad_p);
+int mpc_sens_adjoint_dev(mpc_handle* h, int32_t B, const double* d_seed_w, double* d_grad_p, void* stream);
+
 /* Batched plant step on the device path: x_next = x + dt f(x,u) (integrator 0 = forward Euler,
  * optimizer.py:649-650) or one RK4 step (integrator 1, optimizer.py:97-98).  x: [B, nx], u: [B, 2] host. */
 int mpc_plant_step(mpc_handle* h, int32_t B, int32_t integrator, const double* x, const double* u, double* x_next);

@@ -47,6 +47,7 @@ EXPORTS = [
     "mpc_abi_version", "mpc_closed_loop_batch", "mpc_closed_loop_batch_dev", "mpc_metrics_batch", "mpc_forces_stage_eval", "mpc_forces_solve_batch",
     "mpc_get_pipeline_profile", "mpc_get_resident_profile", "mpc_measure_copy_bandwidth", "mpc_get_option", "mpc_plant_step_dev", "mpc_metrics_batch_dev", "mpc_forces_solve_batch_dev", "mpc_set_option", "mpc_last_rescued", "mpc_closed_loop_batch_ex", "mpc_closed_loop_batch_dev_ex", "mpc_last_loop_replayed", "mpc_validity_batch", "mpc_validity_batch_dev", "mpc_forces_closed_loop_batch", "mpc_forces_closed_loop_batch_dev",
     "mpc_eval_nlp_batch", "mpc_eval_nlp_batch_dev", "mpc_solve_batch_ex", "mpc_solve_batch_dev_ex",
+    "mpc_solve_batch_sens", "mpc_solve_batch_sens_dev", "mpc_sens_adjoint", "mpc_sens_adjoint_dev",
 ]
 
 
@@ -154,6 +155,14 @@ def load_library(path: str | None = None):
     L.mpc_solve_batch_ex.restype = C.c_int
     L.mpc_solve_batch_dev_ex.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_solve_batch_dev_ex.restype = C.c_int
+    L.mpc_solve_batch_sens.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp]
+    L.mpc_solve_batch_sens.restype = C.c_int
+    L.mpc_solve_batch_sens_dev.argtypes = [vp, C.c_int32] + [vp] * 12 + [C.c_int32, vp, vp, vp]
+    L.mpc_solve_batch_sens_dev.restype = C.c_int
+    L.mpc_sens_adjoint.argtypes = [vp, C.c_int32, _dp, _dp]
+    L.mpc_sens_adjoint.restype = C.c_int
+    L.mpc_sens_adjoint_dev.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.mpc_sens_adjoint_dev.restype = C.c_int
     L.mpc_abi_version.argtypes = []
     L.mpc_abi_version.restype = C.c_int
     if path == LIB_PATH:

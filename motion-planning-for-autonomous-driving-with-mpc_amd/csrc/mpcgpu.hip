@@ -36,6 +36,7 @@
 #include "mpc_closed_loop.h"
 #include "mpc_forces_qp.h"
 #include "mpc_riccati_mfma.h"
+#include "mpc_sens.h"
 
 using namespace mpc;
 
@@ -2514,6 +2515,76 @@ __global__ void __launch_bounds__(NLP_OUT_THREADS) k_mult_out(const Params P, co
     mult_stage<NX>(P, b, k, in_mb, x_out + (size_t)b * nw, lg, lx);
 }
 
+// ---- parametric sensitivities (mpc_solve_batch_sens, mpc_sens_adjoint; DESIGN.md section 13, the math in mpc_sens.h) -----------------------
+// The final iterate of every instance of a solve that just ran on this workspace -> the instance-major snapshot rows of the handle, found by
+// k_mult_out's rule (the NaN-filled mailbox when k_solve_wg served the instance, the tile-major rows otherwise).  A row whose status is not 1,
+// or whose iterate is in neither place, is marked invalid.  idx (the second chance's sub-batch): row j goes to snapshot row idx[j], and only
+// where its status is 1 -- the first attempt's row stays otherwise.
+template <int NX>
+__global__ void __launch_bounds__(NLP_OUT_THREADS) k_sens_gather(const Params P, const int has_mb, const double* x_out, const int32_t* status,
+                                                                 const double* obst, const int32_t* idx, double* snap) {
+    __shared__ int miss[2][NLP_OUT_THREADS];
+    constexpr int NZ = NX + 2;
+    const int N = P.N, S = N + 1, ipb = NLP_OUT_THREADS / S, t = threadIdx.x, li = t / S, k = t - li * S;
+    const int b = blockIdx.x * ipb + li;
+    const bool valid = li < ipb && b < P.B;
+    const size_t nw = (size_t)2 * N + (size_t)NX * S;
+    if (t < ipb) { miss[0][t] = has_mb ? 0 : 1; miss[1][t] = 0; }
+    __syncthreads();
+    if (valid) {
+        const double* w = x_out + (size_t)b * nw;
+        bool mm = false, mt = false;
+        for (int i = 0; i < NZ; ++i) {
+            if (i < 2 && k == N) continue;
+            const double xv = w[i < 2 ? 2 * k + i : 2 * N + NX * k + (i - 2)];
+            if (has_mb) mm |= P.MZ[mult_mb_index(P, NZ, k, i, b)] != xv;
+            mt |= P.Z[mult_tile_index(P, NZ, k, i, b)] != xv;
+        }
+        if (mm) atomicOr(&miss[0][li], 1);
+        if (mt) atomicOr(&miss[1][li], 1);
+    }
+    __syncthreads();
+    if (!valid) return;
+    const bool conv = status[b] == 1;
+    if (idx && !conv) return;
+    const bool in_mb = miss[0][li] == 0, in_tile = miss[1][li] == 0;
+    double ob[6];
+    for (int i = 0; i < 6; ++i) ob[i] = obst ? obst[(size_t)b * 6 + i] : P.obst[i];
+    const size_t row = idx ? (size_t)idx[b] : (size_t)b;
+    sens_gather_stage<NX>(P, b, k, in_mb, ob, conv && (in_mb || in_tile), snap + row * Sens<NX>::len(N));
+}
+// CasADi's lam_p from the solve's own outputs: one thread per entry of [B, n_p]
+template <int NX>
+__global__ void k_sens_lam_p(const Params P, const double* x_out, const double* p, const int32_t* status, const double* lam_g, double* lam_p) {
+    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), ng = (size_t)nlp_n_g(P);
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)P.B * nw) return;
+    const size_t b = e / nw;
+    const int q = (int)(e - b * nw);
+    lam_p[e] = sens_lam_p_entry<NX>(P, q, status[b] == 1, x_out + b * nw, p + b * nw, lam_g + b * ng);
+}
+// Lane per instance: factor the final KKT matrix of the snapshot (F: [stage][entry][B] factor storage), then n_dir forward directions
+// dp [B, n_dir, n_p] -> dw [B, n_dir, n_w] and / or one adjoint seed [B, n_w] -> grad_p [B, n_p].  NaN where the factor failed.
+constexpr int SENS_THREADS = 64;
+template <int NX>
+__global__ void __launch_bounds__(SENS_THREADS) k_sens_factor_solve(const Params P, const double* snap, double* F, const int n_dir, const double* dp,
+                                                                   double* dw, const double* seed, double* grad_p) {
+    const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
+    if (b >= P.B) return;
+    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), Bs = (size_t)P.B;
+    const SensInst si = sens_factor<NX>(P, snap + (size_t)b * Sens<NX>::len(P.N), F, Bs, b);
+    for (int d = 0; d < n_dir; ++d) {
+        double* o = dw + ((size_t)b * n_dir + d) * nw;
+        if (si.ok) sens_forward<NX>(P, si, F, Bs, b, dp + ((size_t)b * n_dir + d) * nw, o);
+        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
+    }
+    if (grad_p) {
+        double* o = grad_p + (size_t)b * nw;
+        if (si.ok) sens_adjoint<NX>(P, si, F, Bs, b, seed + (size_t)b * nw, o);
+        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
+    }
+}
+
 template <int NX>
 __global__ void k_plant_step(const Params Pk, const double* x, const double* u, double* xn, int B, int integrator) {
     const PRef P(Pk);
@@ -2617,10 +2688,15 @@ struct mpc_handle {
         uint32_t pipe_xcd_mask = 0;
     } knobs;
     // grow-only device scratch of the entry points around the solve (plant step, metrics, FORCES mode): slot -> buffer
-    static constexpr int N_SCRATCH = 44;
+    static constexpr int N_SCRATCH = 50;
     // mpc_solve_batch[_dev]_ex: where the multipliers of the running solve go ([B, n_g] / [B, n_w] rows of the caller, or null = not asked for)
     double* mo_lam_g = nullptr;
     double* mo_lam_x = nullptr;
+    // mpc_solve_batch_sens[_dev]: where the running solve's final iterates go (snapshot rows, mpc_sens.h; null = not asked for), and whether
+    // the snapshot of the last such solve is still the handle's last solve (any later solve clears it) and of how many instances
+    double* so_snap = nullptr;
+    bool snap_ok = false;
+    int32_t snap_B = 0;
     void* scratch[N_SCRATCH] = {};
     size_t scratch_cap[N_SCRATCH] = {};
 };
@@ -3697,6 +3773,7 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
 
 static int solve_dev_any(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
                          int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream, double* trace, int32_t trace_rows, int32_t* n_it) {
+    h->snap_ok = false;                 // (every solve of the handle: the snapshot of mpc_solve_batch_sens is no longer the last solve's)
     if (h->hp.desc.nx == 5)
         return solve_dev_impl<5>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it);
     return solve_dev_impl<6>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it);
@@ -3726,6 +3803,22 @@ static int mult_read(mpc_handle* h, int32_t B, const double* d_x_out, const int3
     const dim3 grid((B + ipb - 1) / ipb);
     if (d.nx == 5) hipLaunchKernelGGL((k_mult_out<5>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, h->ws_mailbox ? 1 : 0, d_x_out, d_status, lam_g, lam_x);
     else hipLaunchKernelGGL((k_mult_out<6>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, h->ws_mailbox ? 1 : 0, d_x_out, d_status, lam_g, lam_x);
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+
+// after it, likewise: the final iterates -> snapshot rows (mpc_solve_batch_sens); idx: the rows of the second chance's sub-batch
+static int sens_read(mpc_handle* h, int32_t B, const double* d_x_out, const int32_t* d_status, const double* d_obst, const int32_t* idx, double* snap,
+                     hipStream_t stream) {
+    const mpc_problem_desc& d = h->hp.desc;
+    const size_t Bp = ((size_t)B + 63) / 64 * 64;
+    Params P;
+    fill_params(P, h->hp, B, Bp, 1, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
+    const int ipb = NLP_OUT_THREADS / (d.N + 1);
+    const dim3 grid((B + ipb - 1) / ipb);
+    const int mb = h->ws_mailbox ? 1 : 0;
+    if (d.nx == 5) hipLaunchKernelGGL((k_sens_gather<5>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, mb, d_x_out, d_status, d_obst, idx, snap);
+    else hipLaunchKernelGGL((k_sens_gather<6>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, mb, d_x_out, d_status, d_obst, idx, snap);
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
@@ -3772,12 +3865,13 @@ static int rescue_dev(mpc_handle* h, int32_t B, const double* d_x0, const double
         for (int q = 0; q < nfr && rc == MPC_OK; ++q) {
             h->hp.ol = relax_lo(fr[q] * h->hp.ol_raw);
             h->hp.desc.tol = (q + 1 < nfr) ? std::max(tol_keep, 1e-4) : tol_keep;      // intermediate levels only produce warm starts
-            if (mlg && q + 1 == nfr) rc = mult_prepare(h, n, stream);
+            if ((mlg || h->so_snap) && q + 1 == nfr) rc = mult_prepare(h, n, stream);
             if (rc != MPC_OK) break;
             h->in_rescue = true;
             rc = solve_dev_any(h, n, xs, ps, d_obst ? os : nullptr, out, st, it, kk, stream, nullptr, 0, nullptr);
             h->in_rescue = false;
             if (rc == MPC_OK && mlg && q + 1 == nfr) rc = mult_read(h, n, out, st, mlg, mlg + (size_t)n * ng, stream);
+            if (rc == MPC_OK && h->so_snap && q + 1 == nfr) rc = sens_read(h, n, out, st, d_obst ? os : nullptr, idx, h->so_snap, stream);
             if (rc == MPC_OK) hipLaunchKernelGGL(k_rescue_carry, dim3(n), dim3(128), 0, stream, (int)nw, st, it, out, xs, acc);
         }
         h->hp.ol = ol_keep;
@@ -3821,6 +3915,7 @@ static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double*
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !d_x0 || !d_p || !d_x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
     if (!h->hp.bounds_set) { h->err = "mpc_set_bounds has not been called"; return MPC_ERR_STATE; }
+    h->snap_ok = false;
     HIP_TRY(h, hipSetDevice(h->device));
     h->rescued_last = 0;
     // the second chance needs the per-instance status: an internal row when the caller did not ask for it
@@ -3836,15 +3931,17 @@ static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double*
         if ((size_t)B > max_b && !trace && !h->async_loop) {
             const size_t nw = h->hp.n_w();
             const size_t ng = h->hp.n_g();
-            double *mlg = h->mo_lam_g, *mlx = h->mo_lam_x;
+            double *mlg = h->mo_lam_g, *mlx = h->mo_lam_x, *snp = h->so_snap;
+            const size_t slen = h->hp.desc.nx == 5 ? Sens<5>::len(h->hp.desc.N) : Sens<6>::len(h->hp.desc.N);
             int rescued = 0;
             for (size_t off = 0; off < (size_t)B; off += max_b) {
                 const int32_t n = (int32_t)std::min(max_b, (size_t)B - off);
                 if (mlg) { h->mo_lam_g = mlg + off * ng; h->mo_lam_x = mlx + off * nw; }
+                if (snp) h->so_snap = snp + off * slen;
                 const int rcc = solve_dev(h, n, d_x0 + off * nw, d_p + off * nw, d_obst ? d_obst + off * 6 : nullptr, d_x_out + off * nw,
                                           d_status ? d_status + off : nullptr, d_iters ? d_iters + off : nullptr, d_kkt ? d_kkt + off : nullptr, stream,
                                           nullptr, 0, nullptr);
-                h->mo_lam_g = mlg; h->mo_lam_x = mlx;
+                h->mo_lam_g = mlg; h->mo_lam_x = mlx; h->so_snap = snp;
                 if (rcc) return rcc;
                 rescued += h->rescued_last;
             }
@@ -3853,12 +3950,13 @@ static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double*
         }
     }
     h->resc_in_kernel = h->resc_ran = false;
-    if (h->mo_lam_g) {
+    if (h->mo_lam_g || h->so_snap) {
         const int rm = mult_prepare(h, B, stream);
         if (rm) return rm;
     }
     int rc = solve_dev_any(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it);
     if (rc == MPC_OK && h->mo_lam_g) rc = mult_read(h, B, d_x_out, d_status, h->mo_lam_g, h->mo_lam_x, stream);
+    if (rc == MPC_OK && h->so_snap) rc = sens_read(h, B, d_x_out, d_status, d_obst, nullptr, h->so_snap, stream);
     // (converged mode: the solve has synchronised the stream; a launch of k_solve_wg with the second chance inside has given every stalled
     //  instance its levels already)
     // (what the next solve of this handle does about stalled instances: see resc_cond)
@@ -4032,6 +4130,132 @@ int mpc_solve_batch_ex(mpc_handle* h, int32_t B, const double* x0, const double*
     if (g) HIP_TRY(h, hipMemcpyAsync(g, dg, nB * ng * 8, hipMemcpyDeviceToHost, s));
     if (lam_g) HIP_TRY(h, hipMemcpyAsync(lam_g, dlg, nB * ng * 8, hipMemcpyDeviceToHost, s));
     if (lam_x) HIP_TRY(h, hipMemcpyAsync(lam_x, dlx, nB * nw * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MPC_OK;
+}
+
+// ---- parametric sensitivities -----------------------------------------------------------------------------------
+static size_t sens_len(const mpc_handle* h) { return h->hp.desc.nx == 5 ? Sens<5>::len(h->hp.desc.N) : Sens<6>::len(h->hp.desc.N); }
+static int sens_fs(const mpc_handle* h) { return h->hp.desc.nx == 5 ? Sens<5>::FS : Sens<6>::FS; }
+// factor the snapshot's KKT matrices and solve: n_dir forward directions and / or one adjoint seed (k_sens_factor_solve)
+static int sens_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dp, double* d_dw, const double* d_seed, double* d_grad, hipStream_t s) {
+    const mpc_problem_desc& d = h->hp.desc;
+    double* F = static_cast<double*>(scratch_get(h, 45, (size_t)B * (size_t)(d.N + 1) * (size_t)sens_fs(h) * 8));
+    if (!F) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
+    Params P;
+    fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, nullptr, nullptr, h->d_LB, h->d_UB, false);
+    const dim3 grid((B + SENS_THREADS - 1) / SENS_THREADS);
+    double* snap = static_cast<double*>(h->scratch[44]);
+    if (d.nx == 5) hipLaunchKernelGGL((k_sens_factor_solve<5>), grid, dim3(SENS_THREADS), 0, s, P, snap, F, n_dir, d_dp, d_dw, d_seed, d_grad);
+    else hipLaunchKernelGGL((k_sens_factor_solve<6>), grid, dim3(SENS_THREADS), 0, s, P, snap, F, n_dir, d_dp, d_dw, d_seed, d_grad);
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+
+// mpc_solve_batch_dev_ex plus the snapshot of the final iterates, CasADi's lam_p and n_dir forward sensitivities
+int mpc_solve_batch_sens_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
+                             int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
+                             double* d_lam_p, int32_t n_dir, const double* d_dp, double* d_dw, void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !d_x0 || !d_p || !d_x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
+    if (n_dir < 0 || (n_dir > 0 && (!d_dp || !d_dw))) { h->err = "n_dir >= 0, and dp, dw are required when n_dir > 0"; return MPC_ERR_INVALID; }
+    if (h->hp.desc.fixed_iters > 0) { h->err = "sensitivities need a solve to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
+    h->snap_ok = false;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream_;
+    const size_t nB = (size_t)B, ng = h->hp.n_g();
+    double* snap = static_cast<double*>(scratch_get(h, 44, nB * sens_len(h) * 8));
+    if (!d_status) d_status = static_cast<int32_t*>(scratch_get(h, 46, nB * 4));
+    if (d_lam_p && !d_lam_g) d_lam_g = static_cast<double*>(scratch_get(h, 47, nB * ng * 8));
+    if (!snap || !d_status || (d_lam_p && !d_lam_g)) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    h->so_snap = snap;
+    int rc = mpc_solve_batch_dev_ex(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_f, d_g, d_lam_g, d_lam_x, stream_);
+    h->so_snap = nullptr;
+    if (rc) return rc;
+    h->snap_ok = true;
+    h->snap_B = B;
+    if (d_lam_p) {
+        Params P;
+        fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, nullptr, nullptr, h->d_LB, h->d_UB, false);
+        const size_t n = nB * h->hp.n_w();
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (h->hp.desc.nx == 5) hipLaunchKernelGGL((k_sens_lam_p<5>), grid, dim3(256), 0, s, P, d_x_out, d_p, d_status, d_lam_g, d_lam_p);
+        else hipLaunchKernelGGL((k_sens_lam_p<6>), grid, dim3(256), 0, s, P, d_x_out, d_p, d_status, d_lam_g, d_lam_p);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (n_dir > 0) {
+        rc = sens_launch(h, B, n_dir, d_dp, d_dw, nullptr, nullptr, s);
+        if (rc) return rc;
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MPC_OK;
+}
+
+int mpc_solve_batch_sens(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out, int32_t* status,
+                         int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x, double* lam_p, int32_t n_dir,
+                         const double* dp, double* dw) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !x0 || !p || !x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
+    if (n_dir < 0 || (n_dir > 0 && (!dp || !dw))) { h->err = "n_dir >= 0, and dp, dw are required when n_dir > 0"; return MPC_ERR_INVALID; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure_io(h, (size_t)B);
+    if (rc) return rc;
+    const size_t nw = h->hp.n_w(), nB = (size_t)B, ng = h->hp.n_g(), nd = (size_t)n_dir;
+    // [f | g | lam_g | lam_x | lam_p | dp | dw]
+    double* buf = static_cast<double*>(scratch_get(h, 48, nB * (1 + 2 * ng + 2 * nw + 2 * nd * nw) * 8));
+    if (!buf) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    double *df = buf, *dg = df + nB, *dlg = dg + nB * ng, *dlx = dlg + nB * ng, *dlp = dlx + nB * nw, *ddp = dlp + nB * nw, *ddw = ddp + nB * nd * nw;
+    hipStream_t s = h->own_stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, nB * nw * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_p, p, nB * nw * sizeof(double), hipMemcpyHostToDevice, s));
+    if (obst) HIP_TRY(h, hipMemcpyAsync(h->d_obst, obst, nB * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (nd) HIP_TRY(h, hipMemcpyAsync(ddp, dp, nB * nd * nw * sizeof(double), hipMemcpyHostToDevice, s));
+    rc = mpc_solve_batch_sens_dev(h, B, h->d_x0, h->d_p, obst ? h->d_obst : nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt, f ? df : nullptr,
+                                  g ? dg : nullptr, lam_g ? dlg : nullptr, lam_x ? dlx : nullptr, lam_p ? dlp : nullptr, n_dir, nd ? ddp : nullptr,
+                                  nd ? ddw : nullptr, (void*)s);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(x_out, h->d_xout, nB * nw * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(h, hipMemcpyAsync(status, h->d_status, nB * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (iters) HIP_TRY(h, hipMemcpyAsync(iters, h->d_iters, nB * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (kkt) HIP_TRY(h, hipMemcpyAsync(kkt, h->d_kkt, nB * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (f) HIP_TRY(h, hipMemcpyAsync(f, df, nB * 8, hipMemcpyDeviceToHost, s));
+    if (g) HIP_TRY(h, hipMemcpyAsync(g, dg, nB * ng * 8, hipMemcpyDeviceToHost, s));
+    if (lam_g) HIP_TRY(h, hipMemcpyAsync(lam_g, dlg, nB * ng * 8, hipMemcpyDeviceToHost, s));
+    if (lam_x) HIP_TRY(h, hipMemcpyAsync(lam_x, dlx, nB * nw * 8, hipMemcpyDeviceToHost, s));
+    if (lam_p) HIP_TRY(h, hipMemcpyAsync(lam_p, dlp, nB * nw * 8, hipMemcpyDeviceToHost, s));
+    if (nd) HIP_TRY(h, hipMemcpyAsync(dw, ddw, nB * nd * nw * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MPC_OK;
+}
+
+// reverse mode on the snapshot of the handle's last solve, if that was mpc_solve_batch_sens[_dev] with the same B (enqueued on `stream`)
+int mpc_sens_adjoint_dev(mpc_handle* h, int32_t B, const double* d_seed_w, double* d_grad_p, void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !d_seed_w || !d_grad_p) { h->err = "B > 0 and seed_w, grad_p are required"; return MPC_ERR_INVALID; }
+    if (!h->snap_ok || B != h->snap_B) {
+        h->err = "mpc_sens_adjoint: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B";
+        return MPC_ERR_STATE;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    return sens_launch(h, B, 0, nullptr, nullptr, d_seed_w, d_grad_p, (hipStream_t)stream_);
+}
+
+int mpc_sens_adjoint(mpc_handle* h, int32_t B, const double* seed_w, double* grad_p) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !seed_w || !grad_p) { h->err = "B > 0 and seed_w, grad_p are required"; return MPC_ERR_INVALID; }
+    if (!h->snap_ok || B != h->snap_B) {
+        h->err = "mpc_sens_adjoint: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B";
+        return MPC_ERR_STATE;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t nw = h->hp.n_w(), nB = (size_t)B;
+    double* buf = static_cast<double*>(scratch_get(h, 49, nB * 2 * nw * 8));
+    if (!buf) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    hipStream_t s = h->own_stream;
+    HIP_TRY(h, hipMemcpyAsync(buf, seed_w, nB * nw * 8, hipMemcpyHostToDevice, s));
+    const int rc = sens_launch(h, B, 0, nullptr, nullptr, buf, buf + nB * nw, s);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(grad_p, buf + nB * nw, nB * nw * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     return MPC_OK;
 }
@@ -4315,6 +4539,7 @@ int mpc_forces_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, con
                                const double* lb, const double* ub, const double* hl, const double* hu, int32_t hessian_mode,
                                double* d_x_out, int32_t* d_exitflag, int32_t* d_it, double* d_res, void* stream_) {
     if (!h) return MPC_ERR_INVALID;
+    h->snap_ok = false;                 // (a solve: the snapshot of mpc_solve_batch_sens is no longer the last solve's)
     if (B <= 0 || !d_x0 || !d_xinit || !d_all_parameters || !lb || !ub || !hl || !hu || !d_x_out) { h->err = "forces solve: null or empty argument"; return MPC_ERR_INVALID; }
     const mpc_problem_desc& d = h->hp.desc;
     if (d.nx != 5) { h->err = "the FORCES formulation has 5 states (z = [deltaDot, aLong, x, y, delta, v, psi])"; return MPC_ERR_INVALID; }

@@ -114,9 +114,10 @@ class NlpSolverHandle:
     """`ca.nlpsol('solver', 'ipopt', nlp_prob, opts)` look-alike (optimizer.py:558): callable with the same
     keyword arguments as optimizer.py:607.  Accepts a single instance ((n_w,1) / (n_w,)) or a batch [B, n_w].
 
-    The result has CasADi's keys: 'x' (n_w,1), 'f' (1,1), 'g' and 'lam_g' (n_g,1), 'lam_x' (n_w,1) -- rows [B, .] for a batch; lam_g /
-    lam_x are NaN for an instance whose status is not 1 (include/mpcgpu.h, mpc_solve_batch_ex).  'f', 'g', 'lam_*' come with a
-    BatchedMPCSolver backend only.  A dual warm start (lam_x0 / lam_g0) is not taken: those keywords are accepted and ignored."""
+    The result has CasADi's keys: 'x' (n_w,1), 'f' (1,1), 'g' and 'lam_g' (n_g,1), 'lam_x' and 'lam_p' (n_w,1) -- rows [B, .] for a batch;
+    lam_g / lam_x / lam_p are NaN for an instance whose status is not 1 (include/mpcgpu.h, mpc_solve_batch_ex; lam_p = d/dp [f + lam_g' g +
+    lam_x' x], the closed form of BatchedMPCSolver.lam_p_of).  'f', 'g', 'lam_*' come with a BatchedMPCSolver backend only.  A dual warm start (lam_x0 / lam_g0) is not
+    taken: those keywords are accepted and ignored."""
 
     # failed instances get a second chance by homotopy on the obstacle radius: on the device, behind the C-ABI
     # (mpc_solve_batch; include/mpcgpu.h).  A backend without that (the stand-in backends of the tests) gets the same
@@ -151,11 +152,12 @@ class NlpSolverHandle:
         x = res.x if batched else res.x.reshape(-1, 1)
         out = NlpSolution(x=DMLike(x))
         if full:
+            res.lam_p = be.lam_p_of(res.x, pa, res.lam_g, res.status)
             if batched:
-                out["f"], out["g"], out["lam_g"], out["lam_x"] = (DMLike(a) for a in (res.f, res.g, res.lam_g, res.lam_x))
+                out["f"], out["g"], out["lam_g"], out["lam_x"], out["lam_p"] = (DMLike(a) for a in (res.f, res.g, res.lam_g, res.lam_x, res.lam_p))
             else:
                 out["f"] = DMLike(res.f.reshape(1, 1))
-                out["g"], out["lam_g"], out["lam_x"] = (DMLike(a.reshape(-1, 1)) for a in (res.g, res.lam_g, res.lam_x))
+                out["g"], out["lam_g"], out["lam_x"], out["lam_p"] = (DMLike(a.reshape(-1, 1)) for a in (res.g, res.lam_g, res.lam_x, res.lam_p))
         out["status"] = res.status
         return out
 

@@ -39,6 +39,9 @@ class SolveResult:
     g: np.ndarray | None = None        # [B, n_g] constraint rows at x (order of mpc_set_bounds)
     lam_g: np.ndarray | None = None    # [B, n_g] multipliers of the rows, NaN where status != 1
     lam_x: np.ndarray | None = None    # [B, n_w] multipliers of the bounds (z_U - z_L), NaN where status != 1
+    # solve(..., lam_p=True / dp=...): parametric sensitivities (include/mpcgpu.h, mpc_solve_batch_sens)
+    lam_p: np.ndarray | None = None    # [B, n_p] CasADi's lam_p = d/dp [f + lam_g' g + lam_x' x], NaN where status != 1
+    dw: np.ndarray | None = None       # [B, n_dir, n_w] (dw*/dp) dp for the seeds dp [B, n_dir, n_p], NaN where status != 1
 
 
 class BatchedMPCSolver:
@@ -68,6 +71,7 @@ class BatchedMPCSolver:
         self.n_w = 2 * self.N + self.nx * (self.N + 1)
         self.n_g = 1 + self.nx * (self.N + 1) + 9 * (self.N + 1)
         self._h = C.c_void_p()
+        self._sens_gen = 0          # solves that left a snapshot of their final iterates (mpc_solve_batch_sens): autograd.py checks it
         rc = self._lib.mpc_create(C.byref(self._h), C.byref(d))
         if rc != _abi.MPC_OK:
             raise MpcError(rc, self._lib.mpc_last_error(None).decode())
@@ -125,9 +129,11 @@ class BatchedMPCSolver:
         self._check(self._lib.mpc_eval_nlp_batch(self._h, B, _abi.as_dp(x), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(f), _abi.as_dp(g)))
         return f, g
 
-    def solve(self, x0, p, obst=None, *, multipliers=False) -> SolveResult:
+    def solve(self, x0, p, obst=None, *, multipliers=False, lam_p=False, dp=None) -> SolveResult:
         """B instances at once.  multipliers=True: also f, g at the returned x and the multipliers lam_g, lam_x (CasADi's convention:
-        grad f + J_g' lam_g + lam_x = 0) in the result (mpc_solve_batch_ex)."""
+        grad f + J_g' lam_g + lam_x = 0) in the result (mpc_solve_batch_ex).  lam_p=True: CasADi's lam_p; dp [B, n_dir, n_p] (or [B, n_p]):
+        forward sensitivities dw = (dw*/dp) dp of the optimum (mpc_solve_batch_sens, which also keeps the final iterates for sens_adjoint).
+        p = [U_ref | X_ref], n_p = n_w."""
         x0 = _abi.f64(x0)
         p = _abi.f64(p)
         if x0.ndim == 1:
@@ -143,6 +149,8 @@ class BatchedMPCSolver:
         status = np.empty(B, np.int32)
         iters = np.empty(B, np.int32)
         kkt = np.empty(B, np.float64)
+        if lam_p or dp is not None:
+            return self._solve_sens(x0, p, obst, out, status, iters, kkt, multipliers, lam_p, dp)
         if not multipliers:
             self._check(self._lib.mpc_solve_batch(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out),
                                                   _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt)))
@@ -152,6 +160,64 @@ class BatchedMPCSolver:
                                                  _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt), _abi.as_dp(f), _abi.as_dp(g),
                                                  _abi.as_dp(lam_g), _abi.as_dp(lam_x)))
         return SolveResult(out, status, iters, kkt, f, g, lam_g, lam_x)
+
+    def _solve_sens(self, x0, p, obst, out, status, iters, kkt, multipliers, want_lam_p, dp):
+        B = x0.shape[0]
+        f = g = lam_g = lam_x = lp = dw = None
+        if multipliers:
+            f, g, lam_g, lam_x = np.empty(B), np.empty((B, self.n_g)), np.empty((B, self.n_g)), np.empty((B, self.n_w))
+        if want_lam_p:
+            lp = np.empty((B, self.n_w))
+        n_dir = 0
+        if dp is not None:
+            dp = _abi.f64(dp)
+            if dp.ndim == 2:
+                dp = dp[:, None, :]
+            if dp.ndim != 3 or dp.shape[0] != B or dp.shape[2] != self.n_w:
+                raise MpcError(_abi.MPC_ERR_INVALID, f"dp must be [B, n_dir, {self.n_w}]")
+            dp = np.ascontiguousarray(dp)
+            n_dir = dp.shape[1]
+            dw = np.empty((B, n_dir, self.n_w))
+        self._sens_gen += 1
+        self._check(self._lib.mpc_solve_batch_sens(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out), _abi.as_ip(status),
+                                                   _abi.as_ip(iters), _abi.as_dp(kkt), _abi.as_dp(f), _abi.as_dp(g), _abi.as_dp(lam_g),
+                                                   _abi.as_dp(lam_x), _abi.as_dp(lp), n_dir, _abi.as_dp(dp), _abi.as_dp(dw)))
+        return SolveResult(out, status, iters, kkt, f, g, lam_g, lam_x, lp, dw)
+
+    def lam_p_of(self, x, p, lam_g, status):
+        """CasADi's lam_p from what a solve with multipliers returned (the closed form k_sens_lam_p evaluates, same operations, same bits):
+        X_ref column 0 -lam_g[pin rows], column k+1 -2 Q (x_k - xref_{k+1}), U_ref 0; NaN where status != 1.  Needs no snapshot."""
+        N, nx = self.N, self.nx
+        B = x.shape[0]
+        Q = np.array([self.desc.Q[i] for i in range(nx)])
+        out = np.zeros((B, self.n_w))
+        out[:, 2 * N: 2 * N + nx] = -lam_g[:, 1: 1 + nx]
+        xs = x[:, 2 * N: 2 * N + nx * N].reshape(B, N, nx)
+        xr = p[:, 2 * N + nx:].reshape(B, N, nx)
+        out[:, 2 * N + nx:] = (-2.0 * Q * (xs - xr)).reshape(B, N * nx)
+        out[status != 1] = np.nan
+        return out
+
+    def sens_adjoint(self, seed_w):
+        """reverse mode on the last solve(..., lam_p / dp) of this solver: seed_w [B, n_w] -> grad_p [B, n_p] = (dw*/dp)' seed_w
+        (mpc_sens_adjoint; any solve in between -> MpcError with code MPC_ERR_STATE)"""
+        seed = _abi.f64(seed_w)
+        if seed.ndim == 1:
+            seed = seed[None]
+        grad = np.empty_like(seed)
+        self._check(self._lib.mpc_sens_adjoint(self._h, seed.shape[0], _abi.as_dp(seed), _abi.as_dp(grad)))
+        return grad
+
+    def feedback_gain(self, x0, p, obst=None):
+        """du_0*/dxref_0 [B, nu, nx]: the linearised control law around the optimum (xref_0 is the measured state the plan starts from)"""
+        x0 = _abi.f64(x0)
+        B = x0.shape[0] if x0.ndim == 2 else 1
+        nx = self.nx
+        dp = np.zeros((B, nx, self.n_w))
+        for i in range(nx):
+            dp[:, i, 2 * self.N + i] = 1.0
+        r = self.solve(x0, p, obst, dp=dp)
+        return np.ascontiguousarray(r.dw[:, :, 0:2].transpose(0, 2, 1))
 
     def last_rescued(self):
         """instances of the last solve that took the second chance of the C-ABI (mpc_last_rescued)"""
@@ -188,10 +254,19 @@ class BatchedMPCSolver:
                                                     _abi.as_ip(n_it)))
         return SolveResult(out, status, iters, kkt), trace[: int(n_it[0]) + 1]
 
-    def solve_device(self, B, d_x0, d_p, d_x_out, d_status=0, d_iters=0, d_kkt=0, d_obst=0, stream=0, d_f=0, d_g=0, d_lam_g=0, d_lam_x=0):
+    def solve_device(self, B, d_x0, d_p, d_x_out, d_status=0, d_iters=0, d_kkt=0, d_obst=0, stream=0, d_f=0, d_g=0, d_lam_g=0, d_lam_x=0,
+                     d_lam_p=0, n_dir=0, d_dp=0, d_dw=0):
         """device pointers (ints, e.g. torch.Tensor.data_ptr()) and a hipStream_t handle (int, 0 = default).  d_f [B], d_g / d_lam_g
-        [B, n_g], d_lam_x [B, n_w]: the extra outputs of mpc_solve_batch_dev_ex (0 = not asked for)."""
+        [B, n_g], d_lam_x [B, n_w]: the extra outputs of mpc_solve_batch_dev_ex (0 = not asked for).  d_lam_p [B, n_p], n_dir > 0 with
+        d_dp [B, n_dir, n_p] -> d_dw [B, n_dir, n_w]: mpc_solve_batch_sens_dev (keeps the final iterates for sens_adjoint_device)."""
         vp = C.c_void_p
+        if d_lam_p or n_dir:
+            self._sens_gen += 1
+            self._check(self._lib.mpc_solve_batch_sens_dev(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out), vp(d_status or None),
+                                                           vp(d_iters or None), vp(d_kkt or None), vp(d_f or None), vp(d_g or None), vp(d_lam_g or None),
+                                                           vp(d_lam_x or None), vp(d_lam_p or None), int(n_dir), vp(d_dp or None), vp(d_dw or None),
+                                                           vp(stream or None)))
+            return
         if not (d_f or d_g or d_lam_g or d_lam_x):
             self._check(self._lib.mpc_solve_batch_dev(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out),
                                                       vp(d_status or None), vp(d_iters or None), vp(d_kkt or None), vp(stream or None)))
@@ -199,6 +274,21 @@ class BatchedMPCSolver:
         self._check(self._lib.mpc_solve_batch_dev_ex(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out), vp(d_status or None),
                                                      vp(d_iters or None), vp(d_kkt or None), vp(d_f or None), vp(d_g or None), vp(d_lam_g or None),
                                                      vp(d_lam_x or None), vp(stream or None)))
+
+    def solve_sens_device(self, B, d_x0, d_p, d_x_out, d_status=0, d_iters=0, d_kkt=0, d_obst=0, stream=0, d_lam_p=0, n_dir=0, d_dp=0, d_dw=0):
+        """mpc_solve_batch_sens_dev even with no sensitivity output asked for: the solve plus the snapshot of its final iterates
+        (what sens_adjoint_device differentiates)"""
+        vp = C.c_void_p
+        self._sens_gen += 1
+        self._check(self._lib.mpc_solve_batch_sens_dev(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out), vp(d_status or None),
+                                                       vp(d_iters or None), vp(d_kkt or None), None, None, None, None, vp(d_lam_p or None), int(n_dir),
+                                                       vp(d_dp or None), vp(d_dw or None), vp(stream or None)))
+        return self._sens_gen
+
+    def sens_adjoint_device(self, B, d_seed_w, d_grad_p, stream=0):
+        """device form of sens_adjoint (enqueued on `stream`, not synchronised)"""
+        vp = C.c_void_p
+        self._check(self._lib.mpc_sens_adjoint_dev(self._h, int(B), vp(d_seed_w), vp(d_grad_p), vp(stream or None)))
 
     def plant_step(self, x, u, integrator="euler"):
         x = _abi.f64(x)

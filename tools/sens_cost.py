@@ -1,0 +1,79 @@
+"""Cost of the parametric sensitivities (mpc_solve_batch_sens_dev, mpc_sens_adjoint_dev) against the plain device solve and _ex, same handle,
+same batch, alternating samples: plain | _ex (f, g, lam_g, lam_x) | _sens with lam_p only | _sens with n_dir = nx forward seeds | the
+adjoint alone (on the snapshot of the last _sens call).
+Usage (GPU box): python tools/sens_cost.py [B] [family] [reps]"""
+import os, sys, time
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+import numpy as np
+import torch
+from helpers import FAMILIES, make_solver, set_cfg_bounds
+from oracle.nlp_numpy import synthetic_batch
+
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+fam = sys.argv[2] if len(sys.argv) > 2 else "zamlf_n30_nx6"
+reps = int(sys.argv[3]) if len(sys.argv) > 3 else 30
+cfg, kw = FAMILIES[fam]
+x0, p = synthetic_batch(cfg, B, **kw)
+s = make_solver(cfg)
+set_cfg_bounds(s, cfg)
+dev = "cuda"
+nx, nw = cfg.nx, s.n_w
+tx0, tp = torch.from_numpy(x0).to(dev), torch.from_numpy(p).to(dev)
+out = torch.empty_like(tx0)
+st = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty_like(st); kk = torch.empty(B, dtype=torch.float64, device=dev)
+f = torch.empty(B, dtype=torch.float64, device=dev)
+g = torch.empty((B, s.n_g), dtype=torch.float64, device=dev); lg = torch.empty_like(g)
+lx = torch.empty((B, nw), dtype=torch.float64, device=dev); lp = torch.empty_like(lx)
+dp = torch.zeros((B, nx, nw), dtype=torch.float64, device=dev)
+for i in range(nx):
+    dp[:, i, 2 * cfg.N + i] = 1.0
+dw = torch.empty_like(dp)
+seed = torch.randn((B, nw), dtype=torch.float64, device=dev); gp = torch.empty_like(seed)
+ptrs = (tx0.data_ptr(), tp.data_ptr(), out.data_ptr(), st.data_ptr(), it.data_ptr(), kk.data_ptr())
+
+
+def plain():
+    s.solve_device(B, *ptrs)
+
+
+def ex():
+    s.solve_device(B, *ptrs, d_f=f.data_ptr(), d_g=g.data_ptr(), d_lam_g=lg.data_ptr(), d_lam_x=lx.data_ptr())
+
+
+def sens_lam_p():
+    s.solve_device(B, *ptrs, d_lam_p=lp.data_ptr())
+
+
+def sens_fwd():
+    s.solve_device(B, *ptrs, n_dir=nx, d_dp=dp.data_ptr(), d_dw=dw.data_ptr())
+
+
+def adjoint():
+    s.sens_adjoint_device(B, seed.data_ptr(), gp.data_ptr())
+
+
+def sample(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+fns = dict(plain=plain, ex=ex, sens_lam_p=sens_lam_p, sens_fwd_nx=sens_fwd, adjoint=adjoint)
+for _ in range(3):
+    for fn in fns.values():
+        fn()
+t = {k: [] for k in fns}
+for _ in range(reps):
+    for k, fn in fns.items():
+        if k == "adjoint":
+            sens_lam_p()                         # (the adjoint needs the snapshot of a _sens solve as the handle's last solve)
+        t[k].append(sample(fn))
+med = {k: float(np.median(v)) for k, v in t.items()}
+print(f"B={B} {fam} ({reps} samples each, median / min ms):")
+for k, v in t.items():
+    print(f"  {k:12s} {med[k]:8.4f} / {min(v):8.4f}")
+print(f"  cost over plain: _ex {1e3 * (med['ex'] - med['plain']):.1f} us, _sens lam_p {1e3 * (med['sens_lam_p'] - med['plain']):.1f} us, "
+      f"_sens n_dir = {nx} {1e3 * (med['sens_fwd_nx'] - med['plain']):.1f} us, adjoint alone {1e3 * med['adjoint']:.1f} us")
