@@ -281,7 +281,7 @@ int mpc_forces_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, con
                                const double* lb, const double* ub, const double* hl, const double* hu, int32_t hessian_mode,
                                double* d_x_out, int32_t* d_exitflag, int32_t* d_it, double* d_res, void* stream);
 
-/* Run-time switches of a handle (18).  They are read from the environment once, at mpc_create (MPCGPU_<NAME IN CAPITALS>), and changed afterwards
+/* Run-time switches of a handle (19).  They are read from the environment once, at mpc_create (MPCGPU_<NAME IN CAPITALS>), and changed afterwards
  * only through this call; value NULL restores the default.  Unknown name -> MPC_ERR_INVALID.
  *   what is solved
  *     "friction_lb"      the lower bound lbg[0] = 0 of the reference's stage-0 friction row sqrt((a_0^2 + v_0^2 tan(delta_0)/2.578)^2)

@@ -30,6 +30,9 @@ struct HostProblem {
     // recorded CasADi runs show at ZAM_Over-1_1 steps 4 and 13)
     int fric_literal = 0;
     int n_mult = 0, n_z = 0;
+    // bit i: variable i has a finite lower / upper bound in LB / UB at some stage; dense: ... at every stage where it exists (lower bits
+    // 0-7, upper bits 8-15) -- kept in step with LB / UB by set_bounds
+    uint32_t lo_mask = 0, hi_mask = 0, dense_mask = 0xFFFFu;
     bool bounds_set = false;
     int NZ() const { return desc.nx + 2; }
     size_t n_w() const { return (size_t)2 * desc.N + (size_t)desc.nx * (desc.N + 1); }
@@ -73,7 +76,7 @@ inline void default_bounds(const mpc_problem_desc& d, std::vector<double>& lbx, 
     for (int i = 0; i < 9 * (N + 1); ++i) { lbg.push_back(1.2000000000000002); ubg.push_back(INFINITY); }
 }
 
-inline int set_bounds(HostProblem& hp, const double* lbx, const double* ubx, const double* lbg, const double* ubg, std::string& err) {
+inline int set_bound_rows(HostProblem& hp, const double* lbx, const double* ubx, const double* lbg, const double* ubg, std::string& err) {
     const mpc_problem_desc& d = hp.desc;
     const int N = d.N, nx = d.nx, NZ = nx + 2;
     std::vector<double> dlbx, dubx, dlbg, dubg;
@@ -122,6 +125,21 @@ inline int set_bounds(HostProblem& hp, const double* lbx, const double* ubx, con
     hp.n_z = nb + 3 * m * (N + 1) * (hp.has_ol + hp.has_ou);
     hp.bounds_set = true;
     return MPC_OK;
+}
+inline int set_bounds(HostProblem& hp, const double* lbx, const double* ubx, const double* lbg, const double* ubg, std::string& err) {
+    const int rc = set_bound_rows(hp, lbx, ubx, lbg, ubg, err);
+    hp.lo_mask = hp.hi_mask = 0;                // (also after an error: LB / UB may have changed)
+    hp.dense_mask = 0xFFFFu;
+    for (size_t q = 0; q < hp.LB.size(); ++q) {
+        const int i = (int)(q % (size_t)hp.NZ()), k = (int)(q / (size_t)hp.NZ());
+        if (hp.LB[q] > -1e300) hp.lo_mask |= 1u << i;
+        if (hp.UB[q] < 1e300) hp.hi_mask |= 1u << i;
+        if (!(i < 2 && k == hp.desc.N)) {                            // (the inputs of the terminal stage do not exist)
+            if (!(hp.LB[q] > -1e300)) hp.dense_mask &= ~(1u << i);
+            if (!(hp.UB[q] < 1e300)) hp.dense_mask &= ~(0x100u << i);
+        }
+    }
+    return rc;
 }
 
 // ---- workspace: one allocation of doubles + one of int32, tile-major [tile of 64 instances][row][64 lanes] --------
@@ -197,17 +215,7 @@ inline void fill_params(Params& P, const HostProblem& hp, int B, size_t Bp, int 
     P.run_counter = nullptr;
     P.dec_s = 0;                      // set after the masks below
     P.tile_mask = nullptr;
-    P.lo_mask = P.hi_mask = 0;
-    P.dense_mask = 0xFFFFu;
-    for (size_t q = 0; q < hp.LB.size(); ++q) {
-        const int i = (int)(q % (size_t)hp.NZ()), k = (int)(q / (size_t)hp.NZ());
-        if (hp.LB[q] > -1e300) P.lo_mask |= 1u << i;
-        if (hp.UB[q] < 1e300) P.hi_mask |= 1u << i;
-        if (!(i < 2 && k == d.N)) {                                  // (the inputs of the terminal stage do not exist)
-            if (!(hp.LB[q] > -1e300)) P.dense_mask &= ~(1u << i);
-            if (!(hp.UB[q] < 1e300)) P.dense_mask &= ~(0x100u << i);
-        }
-    }
+    P.lo_mask = hp.lo_mask; P.hi_mask = hp.hi_mask; P.dense_mask = hp.dense_mask;
     P.dec_s = (d.nx == 6 && d.Q[5] == 0.0 && !((P.lo_mask | P.hi_mask) & (1u << 7))) ? 1 : 0;
     P.x0 = nullptr; P.p = nullptr; P.LB = dLB; P.UB = dUB;
     // every array pointer addresses its first row inside tile 0

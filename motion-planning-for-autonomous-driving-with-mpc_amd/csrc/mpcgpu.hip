@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "mpc_host_common.h"
+#include "mpc_solve_plan.h"
 #include "mpc_closed_loop.h"
 #include "mpc_forces_qp.h"
 #include "mpc_riccati_mfma.h"
@@ -42,10 +43,6 @@ using namespace mpc;
 
 // ============================================================================================== device
 namespace {
-
-// stage-kernel workgroups: 256 threads (one wave per SIMD, the full 512-entry register file, no scratch) when
-// bx * (N + 1) <= 256 with bx >= 4 instances (N <= 63), else 512 threads
-constexpr int STAGE_MAX_THREADS = 512;
 
 // Workgroup barrier WITHOUT the release fence of __syncthreads(): that fence is `s_waitcnt vmcnt(0)`, i.e. every barrier
 // would wait until all of the wave's outstanding global stores are acknowledged by memory (microseconds under load).
@@ -146,16 +143,8 @@ __device__ __forceinline__ void block_reduce(R& r, int bx, double* lds) {
 }
 
 // multiplier state that is not touched by the line search is parked in LDS while the search runs (registers of the
-// 256-thread variant are capped at 256 so that two workgroups share a CU): rows of STASH_ROWS x blockDim doubles
-// state that the line search does not touch is parked in LDS while the search runs (LDS is idle at one workgroup per
-// CU; the registers it frees are the difference between a spill-free search loop and scratch traffic)
+// 256-thread variant are capped at 256 so that two workgroups share a CU): Stash<NX>::rows (mpc_solve_plan.h) rows of blockDim doubles
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-#ifndef MPC_STAGE_STASH
-#define MPC_STAGE_STASH 1
-#endif
-template <int NX> struct Stash {
-    __host__ __device__ static constexpr int rows(bool has_ou) { return 4 * (NX + 2) + 2 * 3 + (has_ou ? 2 * 3 : 0) + 3 + 2 * NX; }
-};
 template <int NX, bool OUT, uint32_t VM = 0xFFu>
 __device__ __forceinline__ void stash_xfer(Ctx<NX>& c, double* st, int T, int t, bool has_ou) {
     int r = 0;
@@ -176,11 +165,7 @@ __device__ __forceinline__ void stash_xfer(Ctx<NX>& c, double* st, int T, int t,
 #undef MPC_ST
 }
 
-// the variables that carry bounds in the reference's NLP (optimizer.py:421-491: steering rate, acceleration, steering angle, speed):
-constexpr uint32_t REF_BOUND_VM = 0x33u;
-// variant 2 of k_pipeline / k_solve_wg: that mask, the bounds of its variables at every stage, circle rows with a lower bound only and
-// multiplicity 3, one obstacle per batch -- the structure of every NLP the reference builds
-constexpr uint32_t REF_DENSE_LO = 0x31u, REF_DENSE_HI = 0x33u;      // (no lower bound on the acceleration)
+// variant 2 of k_pipeline / k_solve_wg: the reference's bound structure (REF_BOUND_VM, REF_DENSE_LO / HI of mpc_solve_plan.h) compiled in
 #ifndef MPC_REF_FLAGS
 #define MPC_REF_FLAGS (VM_OSPEC | vm_dense(REF_DENSE_LO, REF_DENSE_HI))
 #endif
@@ -443,10 +428,6 @@ __global__ void __launch_bounds__(MAXT, (INIT && MAXT <= 256) ? 2 : 1) k_stage(c
 // 2x2 block the wave repeats the sweep with delta_w added for those lanes (flag through LDS keeps the loader in step).
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int32_t HO_IN_MB = 0x40000000;  // flag in an entry of the hand-over lists
-constexpr uint32_t HO_BUCKETS = 4;  // hand-over lists of the hybrid solve, by KKT error: >= 1e-3 | >= 1e-4 | >= 1e-5 | below (rank correlation with the iterations left: 0.9)
-constexpr int RIC_DEPTH = 4;        // backward ring (stage blocks, 17 KiB each at nx = 6)
-constexpr int RIC_DEPTH_F = 10;     // forward ring (gains + A + defect rows, 13 KiB each): stages are short, so look further ahead --
-                                    // fed by TWO loader waves (even / odd stages), each limited to 4 stages in flight by the 6-bit vmcnt
 
 template <int NCH>
 __device__ __forceinline__ void wait_dma_behind(int stages_behind) {
@@ -738,19 +719,12 @@ struct PipeArgs {
     int32_t* ho_list;       // ... and the stage workers put them onto the hand-over lists on their way out (nullptr: k_ho_lists does, or nobody)
     uint32_t flags;         // bit 1: raise the abort word at once (option pipe_test_abort: exercises the host's restart path)
 };
-constexpr uint32_t PIPE_X_STRIDE = 64;          // uint32 words per XCD record: arrive @0, head @16, tail @32, finished @48, hand-over ticket @56
-constexpr uint32_t PIPE_ABORT = 8 * PIPE_X_STRIDE;      // abort word; +1 rounds (max), +2.. statistics
-constexpr uint32_t PIPE_STATS = PIPE_ABORT + 2;         // [wait ticks riccati, wait ticks stage, busy ticks stage, items, workers stage, workers riccati]
-constexpr uint32_t PIPE_WG = PIPE_ABORT + 16;           // statistics of the k_solve_wg launch behind the pipeline (5 words: rounds max, rounds, sweeps, instance-rounds, rescued): zeroed and copied back with the block
-constexpr uint32_t PIPE_HO = PIPE_ABORT + 24;           // hand-over list: instances left by retiring tiles, per bucket of their KKT error (HO_BUCKETS words)
-constexpr uint32_t PIPE_HDR = PIPE_ABORT + 32;          // then: stage_done[ntiles] | pad to 2 words | slots[8][cap] (uint64)
+// (layout of the control block: PIPE_* and pipe_ctl_words in mpc_solve_plan.h)
 constexpr uint32_t PIPE_EXIT = 0xFFFFFFFFu;
 constexpr unsigned long long PIPE_SPIN_LIMIT = 5000000ull;      // 100 MHz wall-clock ticks = 50 ms
 #ifndef MPC_PIPE_SLEEP
 #define MPC_PIPE_SLEEP 8                                        // s_sleep argument between two polls of a hand-off flag (x 64 clocks)
 #endif
-__host__ __device__ inline uint32_t pipe_slots_off(uint32_t ntiles) { return (PIPE_HDR + ntiles + 1u) & ~1u; }
-__host__ __device__ inline size_t pipe_ctl_words(uint32_t ntiles, uint32_t cap) { return (size_t)pipe_slots_off(ntiles) + (size_t)16 * cap; }
 
 // acquire side of a hand-off: nothing for the hardware to do -- every workspace load of the kernel is an sc1 load (DevParams::xcu), served by the
 // XCD's L2, where the producer's rows are once its `s_waitcnt vmcnt(0)` has returned; this keeps the compiler from moving loads above the flag
@@ -1146,12 +1120,6 @@ constexpr int RESC_LEVELS = 8;          // index q of IS_RLEV: 0 = the first att
 __device__ __forceinline__ double resc_fraction(int q) { return q == 2 || q == 7 ? 1.0 : q == 4 ? 0.4 : q == 5 ? 0.7 : q == 6 ? 0.9 : 0.0; }
 __device__ __forceinline__ bool resc_last(int q) { return q == 2 || q == 7; }
 
-// LDS of k_solve_wg, in doubles: the pad record (also the dump area of the sweeps: one double per lane), the records, the bounds table
-template <int NX>
-struct WgLds {
-    static constexpr int PAD = Rec<NX>::SIZE > 64 ? Rec<NX>::SIZE : 64;
-    __host__ __device__ static constexpr size_t doubles(int S, int bxw) { return (size_t)PAD + (size_t)Rec<NX>::SIZE * S * bxw + (size_t)2 * S * (NX + 2) + (size_t)16 * bxw + (size_t)64 * NX + (size_t)WgScl::SIZE * bxw; }
-};
 // k_solve_wg: the caller's output pointers (and the pointers of its epilogue) are read from the kernel-argument segment WHERE THEY ARE USED -- behind
 // an opaque copy of the segment pointer, so that the compiler does not load them at the kernel's entry and carry ten scalar registers through the
 // rounds (the stage phases run at 450+ vector registers with ~400 scalar values spilled into lanes; with the pointers live the kernel went from 456
@@ -1536,7 +1504,6 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
 // so that the host reads it when the stream has drained: no copy command, no kernel of its own behind the loop.  fin_ctl[PIPE_FIN_TICKET] counts the
 // workgroups that have left.
 constexpr uint32_t PIPE_FIN_WORDS = 32, PIPE_FIN_TICKET = 22;
-constexpr int PIPE_MAX_TILES = 256;          // tiles of one persistent launch in converged mode (a Riccati worker owns up to 32: its `fin` mask)
 template <int NX, int VAR, bool RESC = false>
 __global__ void __launch_bounds__(256) k_solve_wg(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* stats, const uint32_t* skip_if,
                                                                    const WgRescue resc, unsigned long long* wtrace, const int32_t* list, const uint32_t* list_n) {
@@ -1570,8 +1537,7 @@ __global__ void __launch_bounds__(256) k_solve_wg(const Params Pk, const int n_m
 // parked in LDS.  Same arithmetic per element and the same left-to-right order of the defect sums as prestart_chain.
 // Src: where the raw guess z(k, i) (i < 2: input, else state i - 2 of stage k) and the reference of stage 0 come from -- the workspace rows, or
 // (k_start) the block's rows of the caller's buffers as they lie in LDS: then nothing here waits for the ingest's stores
-// LDS doubles of prestart_par_block: bounds table and its pushed limits [4][S][NZ], rollout / defects / increments [(3 NX + 2)][S][bx], 4 per instance
-__host__ __device__ constexpr size_t prestart_doubles(int NX, int S, int bx) { return (size_t)4 * S * (NX + 2) + (size_t)(3 * NX + 2) * S * bx + (size_t)4 * bx; }
+// (its LDS: prestart_doubles, mpc_solve_plan.h)
 template <int NX, class Src>
 __device__ __forceinline__ void prestart_par_block(const PRef& P, const uint32_t b0, double* sm, const Src src) {
     constexpr bool WS = std::is_same<Src, PrestartFromWs>::value;
@@ -2620,17 +2586,33 @@ __global__ void k_plant_step(const Params Pk, const double* x, const double* u, 
 }  // namespace
 
 // ============================================================================================== host
+// grow-only device scratch of a handle (scratch_get): one slot per owner
+enum Scratch : int {
+    SCR_STAGING,                        // stage_host: the device copies of a host-pointer call's buffers (the outermost call only)
+    SCR_METRICS_OBST,                   // mpc_metrics_batch_dev: the descriptor's obstacle row
+    SCR_SOLVE_STATUS,                   // solve_dev: the status rows the second chance reads when the caller did not ask for them
+    SCR_HO_LIST,                        // solve_dev_impl: hand-over lists of the hybrid solve
+    SCR_RESC_IDX, SCR_RESC_BUF,         // rescue_dev: open instances + their count; the sub-batch's rows
+    SCR_RESC_MULT,                      // rescue_dev: multipliers of the sub-batch's last level
+    SCR_EX_STATUS, SCR_EX_LAM,          // solve_ex_dev: status / the multiplier rows (lam_g or lam_x) the caller did not ask for
+    SCR_SENS_SNAP,                      // mpc_solve_batch_sens_dev: snapshot of the final iterates (read again by mpc_sens_adjoint_dev)
+    SCR_SENS_STATUS, SCR_SENS_LAM_G,    // mpc_solve_batch_sens_dev: status / lam_g the caller did not ask for
+    SCR_SENS_F,                         // sens_launch: the factors of the KKT matrices
+    SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
+    SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
+    N_SCRATCH
+};
+
 struct mpc_handle {
     HostProblem hp;
     std::string err;
     int device = 0;
     // device workspace
     size_t cap_Bp = 0;
-    bool ws_mailbox = false;            // the workspace carries the instance-major mailbox section (wants_mailbox at allocation time)
+    bool ws_mailbox = false;            // the workspace carries the instance-major mailbox section (SolvePlan::mailbox at allocation time)
     double* d_ws = nullptr;
     int32_t* d_iws = nullptr;
     double *d_LB = nullptr, *d_UB = nullptr;
-    static constexpr int MAX_POLL_IT = 1024;
     unsigned long long* d_tile_mask = nullptr;
     double* d_state = nullptr;         // [B,5] plant state of the closed-loop driver
     size_t cap_state = 0;
@@ -2648,14 +2630,13 @@ struct mpc_handle {
     int32_t* d_counter = nullptr;      // [MAX_GROUPS][MAX_POLL_IT] instances still running after iteration it
     int32_t* h_counter = nullptr;      // pinned, [MAX_GROUPS][2] (double-buffered per poll)
     hipEvent_t ev_poll[4][2] = {};
-    // staging buffers of the host entry point
+    // rows of the solves of the closed-loop driver
     size_t cap_io = 0;
-    double *d_x0 = nullptr, *d_p = nullptr, *d_xout = nullptr, *d_kkt = nullptr, *d_obst = nullptr;
+    double *d_x0 = nullptr, *d_p = nullptr, *d_xout = nullptr, *d_kkt = nullptr;
     int32_t *d_status = nullptr, *d_iters = nullptr;
     hipStream_t own_stream = nullptr;
     // sub-batch pipelining: up to MAX_GROUPS tile groups iterate on their own streams so that the latency-bound
     // Riccati sweep of one group overlaps the stage kernels of the others
-    static constexpr int MAX_GROUPS = 4;
     hipStream_t sub_stream[MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[MAX_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
     // profiling
@@ -2673,108 +2654,25 @@ struct mpc_handle {
     uint32_t* h_fail = nullptr;         // pinned copy
     int loop_replayed = 0;              // the last closed loop had to be replayed with host synchronisation per step
     int rescued_last = 0;               // instances the last solve handed to the second chance (rescue_dev)
-    bool in_rescue = false;             // rescue_dev is solving its levels: they get no second chance of their own
     bool resc_in_kernel = false;        // the last solve ran k_solve_wg with the second chance inside (RESC) over EVERY instance of the batch: rescue_dev has nothing to add
     bool resc_ran = false;              // ... or at least over the instances the pipeline handed over (what stalled inside the pipeline is rescue_dev's)
     bool resc_hint = false;             // the last solve of this handle had stalled instances: the next one runs k_solve_wg<.., RESC> (option rescue_wg = 1, the default)
     bool attr_set_fq = false;
     bool attr_set = false;              // dynamic-LDS limits of the kernels raised on this handle's device
-    // run-time switches: read from the environment ONCE, at mpc_create (MPCGPU_<NAME>), changed afterwards only through
-    // mpc_set_option -- no getenv on the solve path
-    struct Knobs {
-        int pipeline = 1, hybrid = 1, hybrid_bx = 0, hybrid_live = -1, pipe_help = -1, pipe_test_abort = 0;
-        int rescue = 1, rescue_wg = 1, rescue_alone = 0, loop_async = 1, sync_spin = 1, max_batch = 0, friction_lb = 0, bound_mask = 1, big_wg = 0, groups = 0, poison = 0;
-        int timing = 0;                 // profiling aids, a sum of TIMING_* (below): shader-clock stamps printed to stderr; each synchronises
-        uint32_t pipe_xcd_mask = 0;
-    } knobs;
-    // grow-only device scratch of the entry points around the solve (plant step, metrics, FORCES mode): slot -> buffer
-    static constexpr int N_SCRATCH = 50;
-    // mpc_solve_batch[_dev]_ex: where the multipliers of the running solve go ([B, n_g] / [B, n_w] rows of the caller, or null = not asked for)
-    double* mo_lam_g = nullptr;
-    double* mo_lam_x = nullptr;
-    // mpc_solve_batch_sens[_dev]: where the running solve's final iterates go (snapshot rows, mpc_sens.h; null = not asked for), and whether
-    // the snapshot of the last such solve is still the handle's last solve (any later solve clears it) and of how many instances
-    double* so_snap = nullptr;
+    Knobs knobs;                        // run-time switches (mpc_solve_plan.h)
+    // mpc_solve_batch_sens[_dev]: whether the snapshot of the last such solve is still the handle's last solve (any later solve clears it) and of
+    // how many instances
     bool snap_ok = false;
     int32_t snap_B = 0;
     void* scratch[N_SCRATCH] = {};
     size_t scratch_cap[N_SCRATCH] = {};
 };
 
-// option timing: which kernels stamp their phases with the shader clock (printed to stderr after the solve)
-constexpr int TIMING_STAGE = 1,     // k_stage / k_riccati of the third / fourth iteration (forces one launch per kernel)
-              TIMING_PIPE = 2,      // k_pipeline: sixth work item / pass of every worker
-              TIMING_WG = 4,        // k_solve_wg: third round of every workgroup
-              TIMING_START = 8,     // k_start: every workgroup
-              TIMING_WG_TRACE = 16; // k_solve_wg: start, end and rounds of every workgroup (100 MHz wall clock)
-
 // error text of the last failed mpc_create on this thread (a handle does not exist yet to carry it)
 static thread_local std::string g_create_error;
 
-static int set_knob(mpc_handle::Knobs& k, const char* name, const char* value) {
-    const std::string n(name ? name : "");
-    const char* v = value ? value : "";
-    const long iv = strtol(v, nullptr, 0);
-    const int on = (value == nullptr) ? 0 : ((v[0] == '\0') ? 1 : (int)iv);   // "" (variable set, no value) counts as on
-    const int on1 = value == nullptr ? 1 : (v[0] != '0');                     // (switches that default to on: unset = on)
-    if (n == "pipeline") k.pipeline = on1;
-    else if (n == "hybrid") k.hybrid = value == nullptr ? 1 : (int)iv;
-    else if (n == "hybrid_bx") k.hybrid_bx = value == nullptr ? 0 : (int)iv;
-    else if (n == "hybrid_live") k.hybrid_live = value == nullptr ? -1 : (int)iv;
-    else if (n == "pipe_help") k.pipe_help = value == nullptr ? -1 : (int)iv;
-    else if (n == "pipe_test_abort") k.pipe_test_abort = on != 0;
-    else if (n == "pipe_xcd_mask") k.pipe_xcd_mask = value == nullptr ? 0u : (uint32_t)strtoul(v, nullptr, 0);
-    else if (n == "rescue") k.rescue = on1;
-    else if (n == "rescue_wg") k.rescue_wg = value == nullptr ? 1 : (int)iv;
-    else if (n == "rescue_alone") k.rescue_alone = on != 0;
-    else if (n == "loop_async") k.loop_async = on1;
-    else if (n == "sync_spin") k.sync_spin = on1;
-    else if (n == "max_batch") k.max_batch = value == nullptr ? 0 : (int)iv;
-    else if (n == "friction_lb") k.friction_lb = value == nullptr ? 0 : ((std::string(v) == "ipopt") ? 1 : (std::string(v) == "nlp") ? 0 : (int)iv);
-    else if (n == "bound_mask") k.bound_mask = value == nullptr ? 1 : (int)iv;
-    else if (n == "big_wg") k.big_wg = on != 0;
-    else if (n == "groups") k.groups = (int)iv;
-    else if (n == "poison") k.poison = on != 0;
-    else if (n == "timing") k.timing = value == nullptr ? 0 : (int)iv;
-    else return MPC_ERR_INVALID;
-    return MPC_OK;
-}
-static int get_knob(const mpc_handle::Knobs& k, const char* name, long* out) {
-    const std::string n(name ? name : "");
-    if (n == "pipeline") *out = k.pipeline;
-    else if (n == "hybrid") *out = k.hybrid;
-    else if (n == "hybrid_bx") *out = k.hybrid_bx;
-    else if (n == "hybrid_live") *out = k.hybrid_live;
-    else if (n == "pipe_help") *out = k.pipe_help;
-    else if (n == "pipe_test_abort") *out = k.pipe_test_abort;
-    else if (n == "pipe_xcd_mask") *out = (long)k.pipe_xcd_mask;
-    else if (n == "rescue") *out = k.rescue;
-    else if (n == "rescue_wg") *out = k.rescue_wg;
-    else if (n == "rescue_alone") *out = k.rescue_alone;
-    else if (n == "loop_async") *out = k.loop_async;
-    else if (n == "sync_spin") *out = k.sync_spin;
-    else if (n == "max_batch") *out = k.max_batch;
-    else if (n == "friction_lb") *out = k.friction_lb;
-    else if (n == "bound_mask") *out = k.bound_mask;
-    else if (n == "big_wg") *out = k.big_wg;
-    else if (n == "groups") *out = k.groups;
-    else if (n == "poison") *out = k.poison;
-    else if (n == "timing") *out = k.timing;
-    else return MPC_ERR_INVALID;
-    return MPC_OK;
-}
-static void knobs_from_env(mpc_handle::Knobs& k) {
-    static const char* names[] = {"pipeline", "hybrid", "hybrid_bx", "hybrid_live", "pipe_help", "pipe_test_abort", "pipe_xcd_mask", "rescue", "rescue_wg", "rescue_alone", "loop_async",
-                                  "sync_spin", "max_batch", "friction_lb", "bound_mask", "big_wg", "groups", "poison", "timing"};
-    for (const char* n : names) {
-        std::string env = "MPCGPU_";
-        for (const char* c = n; *c; ++c) env += (char)toupper(*c);
-        const char* v = getenv(env.c_str());
-        if (v) (void)set_knob(k, n, v);
-    }
-}
 // device scratch buffer `slot` of at least `bytes` (grow-only, owned by the handle)
-static void* scratch_get(mpc_handle* h, int slot, size_t bytes) {
+static void* scratch_get(mpc_handle* h, Scratch slot, size_t bytes) {
     if (bytes == 0) bytes = 8;
     if (h->scratch_cap[slot] < bytes) {
         if (h->scratch[slot]) (void)hipFree(h->scratch[slot]);
@@ -2802,15 +2700,40 @@ struct DevTmp {
         }                                                                                             \
     } while (0)
 
+// one buffer of a host-pointer call: the caller's pointer (null: not given -- the device twin sees null too), its size, copied in or out
+struct Stage { const void* host; size_t bytes; bool out; };
+// The host-pointer form of a call: the buffers laid out in the handle's staging slot, the inputs copied on the handle's stream, `dev` run with
+// the device pointers and that stream, the outputs copied back, one synchronisation.  The sizes are computed from arguments already checked.
+template <size_t N, class Dev>
+static int stage_host(mpc_handle* h, const Stage (&bufs)[N], Dev&& dev) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    size_t off[N], total = 0;
+    for (size_t i = 0; i < N; ++i) { off[i] = total; if (bufs[i].host) total += (bufs[i].bytes + 255) / 256 * 256; }
+    char* base = static_cast<char*>(scratch_get(h, SCR_STAGING, total));
+    if (!base) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    void* d[N];
+    const hipStream_t s = h->own_stream;
+    for (size_t i = 0; i < N; ++i) {
+        d[i] = bufs[i].host ? base + off[i] : nullptr;
+        if (d[i] && !bufs[i].out) HIP_TRY(h, hipMemcpyAsync(d[i], bufs[i].host, bufs[i].bytes, hipMemcpyHostToDevice, s));
+    }
+    const int rc = dev(d, s);
+    if (rc) return rc;
+    for (size_t i = 0; i < N; ++i)
+        if (d[i] && bufs[i].out) HIP_TRY(h, hipMemcpyAsync(const_cast<void*>(bufs[i].host), d[i], bufs[i].bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MPC_OK;
+}
+
 static void free_ws(mpc_handle* h) {
     if (h->d_ws) (void)hipFree(h->d_ws);
     if (h->d_iws) (void)hipFree(h->d_iws);
     h->d_ws = nullptr; h->d_iws = nullptr; h->cap_Bp = 0; h->ws_mailbox = false;
 }
 static void free_io(mpc_handle* h) {
-    void* ptrs[] = {h->d_x0, h->d_p, h->d_xout, h->d_kkt, h->d_obst, h->d_status, h->d_iters};
+    void* ptrs[] = {h->d_x0, h->d_p, h->d_xout, h->d_kkt, h->d_status, h->d_iters};
     for (void* p : ptrs) if (p) (void)hipFree(p);
-    h->d_x0 = h->d_p = h->d_xout = h->d_kkt = h->d_obst = nullptr;
+    h->d_x0 = h->d_p = h->d_xout = h->d_kkt = nullptr;
     h->d_status = h->d_iters = nullptr;
     h->cap_io = 0;
 }
@@ -2843,8 +2766,8 @@ int mpc_create(mpc_handle** out, const mpc_problem_desc* desc) {
     knobs_from_env(h->knobs);
     h->hp.fric_literal = h->knobs.friction_lb ? 1 : 0;
     if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&h->d_counter, sizeof(int32_t) * mpc_handle::MAX_GROUPS * mpc_handle::MAX_POLL_IT) != hipSuccess ||
-        hipHostMalloc(&h->h_counter, sizeof(int32_t) * mpc_handle::MAX_GROUPS * 2) != hipSuccess ||
+        hipMalloc(&h->d_counter, sizeof(int32_t) * MAX_GROUPS * MAX_POLL_IT) != hipSuccess ||
+        hipHostMalloc(&h->h_counter, sizeof(int32_t) * MAX_GROUPS * 2) != hipSuccess ||
         hipMalloc(&h->d_fail, 8 * sizeof(uint32_t)) != hipSuccess || hipHostMalloc(&h->h_fail, 8 * sizeof(uint32_t)) != hipSuccess) {
         g_create_error = "HIP stream/counter allocation failed";
         delete h;
@@ -2867,9 +2790,9 @@ int mpc_create(mpc_handle** out, const mpc_problem_desc* desc) {
         }
     }
     bool ok_streams = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
-    for (int g = 0; g < mpc_handle::MAX_GROUPS; ++g)
+    for (int g = 0; g < MAX_GROUPS; ++g)
         for (int q = 0; q < 2; ++q) ok_streams = ok_streams && hipEventCreateWithFlags(&h->ev_poll[g][q], hipEventDisableTiming) == hipSuccess;
-    for (int g = 0; g < mpc_handle::MAX_GROUPS && ok_streams; ++g)
+    for (int g = 0; g < MAX_GROUPS && ok_streams; ++g)
         ok_streams = hipStreamCreateWithFlags(&h->sub_stream[g], hipStreamNonBlocking) == hipSuccess &&
                      hipEventCreateWithFlags(&h->ev_join[g], hipEventDisableTiming) == hipSuccess;
     if (!ok_streams) { g_create_error = "HIP stream/event creation failed"; mpc_destroy(h); return MPC_ERR_HIP; }
@@ -2897,9 +2820,9 @@ int mpc_destroy(mpc_handle* h) {
     if (h->h_fail) (void)hipHostFree(h->h_fail);
     for (hipEvent_t ev : h->ev_pool) (void)hipEventDestroy(ev);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    for (int g = 0; g < mpc_handle::MAX_GROUPS; ++g)
+    for (int g = 0; g < MAX_GROUPS; ++g)
         for (int q = 0; q < 2; ++q) if (h->ev_poll[g][q]) (void)hipEventDestroy(h->ev_poll[g][q]);
-    for (int g = 0; g < mpc_handle::MAX_GROUPS; ++g) {
+    for (int g = 0; g < MAX_GROUPS; ++g) {
         if (h->ev_join[g]) (void)hipEventDestroy(h->ev_join[g]);
         if (h->sub_stream[g]) (void)hipStreamDestroy(h->sub_stream[g]);
     }
@@ -2997,21 +2920,22 @@ int mpc_get_profile(const mpc_handle* h, double out[6]) {
 
 }  // extern "C"
 
-// can this handle, as its options stand, ever launch k_solve_wg (the only user of the instance-major mailbox section of the workspace)?
-static bool wants_mailbox(const mpc_handle* h) {
-    const mpc_problem_desc& d = h->hp.desc;
-    const mpc_handle::Knobs& kn = h->knobs;
-    const bool small_wg = 4 * (d.N + 1) <= 256 && !kn.big_wg;
-    return small_wg && d.N + 1 <= 64 && kn.hybrid && d.fixed_iters <= 0 && kn.pipeline && !h->pipe_disabled;
+// what plan_solve reads of the device, the handle and the call
+static PlanState plan_state(const mpc_handle* h, int32_t B, bool per_inst_obst, bool trace, bool in_rescue) {
+    PlanState st;
+    st.n_cu = h->n_cu; st.xcd_mask = h->xcd_mask;
+    st.ws_mailbox = h->ws_mailbox; st.pipe_disabled = h->pipe_disabled; st.resc_hint = h->resc_hint;
+    st.B = B; st.per_inst_obst = per_inst_obst; st.trace = trace; st.in_rescue = in_rescue; st.async_loop = h->async_loop;
+    return st;
 }
-static int ensure_ws(mpc_handle* h, size_t Bp) {
-    const bool mb = wants_mailbox(h);
+// the workspace for Bp rows, with the mailbox section if `mb` (SolvePlan::mailbox)
+static int ensure_ws(mpc_handle* h, size_t Bp, bool mb) {
     if (Bp <= h->cap_Bp && (!mb || h->ws_mailbox)) return MPC_OK;
     const size_t Bp_req = Bp;
     Bp = std::max(Bp, h->cap_Bp);                      // (grow only: also when all that changes is the mailbox section)
     free_ws(h);
     WsLayout w = ws_layout(h->hp.desc.N, h->hp.desc.nx, Bp, mb);
-    // (a handle that grew close to the limit WITHOUT the mailbox section and now needs one: what was asked for fits -- max_rows_per_solve
+    // (a handle that grew close to the limit WITHOUT the mailbox section and now needs one: what was asked for fits -- SolvePlan::max_rows
     //  has chunked the batch for the layout with the mailbox -- the old capacity with the section added may not)
     if (w.total * sizeof(double) >= ((size_t)1 << 32) && Bp_req < Bp) { Bp = Bp_req; w = ws_layout(h->hp.desc.N, h->hp.desc.nx, Bp, mb); }
     if (w.total * sizeof(double) >= ((size_t)1 << 32)) {
@@ -3100,24 +3024,158 @@ static hipError_t wait_stream(mpc_handle* h, hipStream_t stream) {
     return hipStreamSynchronize(stream);
 }
 
+// ---- stamp reports of the profiling aids (option timing; tools/*_timing.py read this text) -----------------------------------------------
+// k_start: shader-clock stamps of every workgroup
+static void report_start_timing(hipStream_t stream, const unsigned long long* d_dbg, int nblk) {
+    std::vector<unsigned long long> hd((size_t)16 * nblk);
+    if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return;
+    const int order[16] = {11, 12, 13, 1, 2, 3, 4, 5, 6, 14, 15, 0, 7, 8, 9, 10};
+    static const char* names[15] = {"rows->LDS", "Z/REF stores", "bounds+a0", "defects", "scan1", "tan+scan2", "sincos+scan3", "ROLL+sums", "decide", "fence", "enter", "init point+exchange", "eval+assemble", "reduce", "finish"};
+    double acc[15] = {0};
+    unsigned long long t0 = ~0ull, t1 = 0ull;
+    for (int bq = 0; bq < nblk; ++bq) {
+        const unsigned long long* r = hd.data() + (size_t)bq * 16;
+        for (int j = 0; j < 15; ++j) acc[j] += (double)(long long)(r[order[j + 1]] - r[order[j]]);
+        t0 = std::min(t0, r[11]); t1 = std::max(t1, r[10]);
+    }
+    fprintf(stderr, "[mpcgpu k_start timing, shader-clock ticks, mean over %d workgroups]", nblk);
+    for (int j = 0; j < 15; ++j) fprintf(stderr, " %s=%.0f", names[j], acc[j] / nblk);
+    fprintf(stderr, "; first start to last end %.0f\n", (double)(t1 - t0));
+}
+// k_solve_wg (option wg_trace): every workgroup leaves its start, its end (100 MHz wall clock) and its rounds: when did the long ones start?
+static void report_wg_trace(const unsigned long long* d_wtrace, int n_wtrace) {
+    if (!d_wtrace) return;
+    std::vector<unsigned long long> hw((size_t)4 * n_wtrace);
+    if (hipMemcpy(hw.data(), d_wtrace, hw.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return;
+    unsigned long long t0 = ~0ull, t1 = 0ull;
+    std::vector<int> live;
+    for (int w = 0; w < n_wtrace; ++w) if (hw[4 * w + 2]) { t0 = std::min(t0, hw[4 * w]); t1 = std::max(t1, hw[4 * w + 1]); live.push_back(w); }
+    if (live.empty()) return;
+    std::sort(live.begin(), live.end(), [&](int a, int b) { return hw[4 * a + 1] > hw[4 * b + 1]; });
+    int late = 0;
+    double start_max = 0;
+    for (int w : live) { const double st = (double)(hw[4 * w] - t0) * 1e-2; if (st > 5.0) ++late; start_max = std::max(start_max, st); }
+    fprintf(stderr, "[mpcgpu wg_trace] %d workgroups with work of %d; span %.1f us; %d of them start more than 5 us after the first (latest start %.1f us); the last to finish:\n",
+            (int)live.size(), n_wtrace, (double)(t1 - t0) * 1e-2, late, start_max);
+    for (size_t i = 0; i < live.size() && i < 12; ++i) {
+        const int w = live[i];
+        const double st = (double)(hw[4 * w] - t0) * 1e-2, en = (double)(hw[4 * w + 1] - t0) * 1e-2;
+        const double tf = (double)((hw[4 * w + 3] >> 16) & 0xFFFFFFull) * 1e-2, tr1 = (double)((hw[4 * w + 3] >> 40) & 0xFFFFFFull) * 1e-2;
+        fprintf(stderr, "    workgroup %5d: start %6.1f us  end %6.1f us  rounds %2d  instance-rounds %2d  -> %.1f us per round; instances taken over after %.1f us, first round done after %.1f us, later rounds %.1f us each\n",
+                w, st, en, (int)hw[4 * w + 2], (int)(hw[4 * w + 3] & 0xFFFFu), (en - st) / (double)hw[4 * w + 2], tf, tr1, hw[4 * w + 2] > 1 ? (en - st - tr1) / (double)(hw[4 * w + 2] - 1) : 0.0);
+    }
+}
+// k_solve_wg alone: shader-clock stamps of every workgroup's third round
+static int report_wg_timing(mpc_handle* h, const unsigned long long* d_dbg, int nblk) {
+    std::vector<unsigned long long> hd((size_t)16 * nblk);
+    HIP_TRY(h, hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    double acc[16] = {0};
+    int cnt = 0;
+    // k_solve_wg: 12 round start, 13 records in LDS, 14 sweeps done, [0..10 stage_block's own stamps], 15 round end
+    const int order[16] = {12, 13, 14, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 15, 15};
+    for (int bq = 0; bq < nblk; ++bq) {
+        const unsigned long long* r = hd.data() + (size_t)bq * 16;
+        if (!r[15] || !r[10]) continue;
+        for (int q = 0; q < 14; ++q) acc[q] += (double)(long long)(r[order[q + 1]] - r[order[q]]);
+        ++cnt;
+    }
+    static const char* names[14] = {"records", "sweeps", "enter", "load+premath", "or", "P1", "reduce1+ls-begin", "linesearch", "P3-update", "exchange", "P4-eval", "reduce3", "P5", "drain"};
+    fprintf(stderr, "[mpcgpu k_solve_wg timing, shader-clock ticks, third round of %d workgroups]", cnt);
+    for (int q = 0; q < 14; ++q) fprintf(stderr, " %s=%.0f", names[q], cnt ? acc[q] / cnt : 0.0);
+    fprintf(stderr, "\n");
+    return MPC_OK;
+}
+// k_pipeline: shader-clock stamps of every worker's LAST work item / tile pass
+static int report_pipe_timing(mpc_handle* h, const unsigned long long* d_dbg) {
+    std::vector<unsigned long long> hd((size_t)16 * h->n_cu);
+    HIP_TRY(h, hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    double sa[16] = {0}, ra[9] = {0};
+    int ns = 0, nr = 0;
+    for (int bq = 0; bq < h->n_cu; ++bq) {
+        const unsigned long long* r = hd.data() + (size_t)bq * 16;
+        if (r[15] && r[10]) {
+            const int order[16] = {11, 12, 13, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 14, 15};
+            for (int q = 0; q + 1 < 16; ++q) sa[q] += (double)(long long)(r[order[q + 1]] - r[order[q]]);
+            ++ns;
+        } else if (r[13] && r[2]) {
+            ra[0] += (double)(long long)(r[12] - r[11]); ra[1] += (double)(long long)(r[1] - r[12]);
+            ra[2] += (double)(long long)(r[2] - r[1]); ra[3] += (double)(long long)(r[13] - r[2]);
+            ra[4] += (double)(long long)(r[4] - r[3]); ra[5] += (double)(long long)(r[5] - r[4]);
+            ra[6] += (double)(long long)(r[7] - r[6]); ra[7] += (double)(long long)(r[8] - r[7]);
+            ra[8] += (double)(long long)(r[9] - r[1]);
+            ++nr;
+        }
+    }
+    static const char* sn[15] = {"dequeue", "acquire+bcast", "enter", "issue-loads", "wait+barrier", "P1", "reduce1", "linesearch", "P3-update",
+                                 "exchange", "P4-eval", "reduce3", "P5", "drain", "signal"};
+    fprintf(stderr, "[mpcgpu pipeline timing, shader-clock ticks, last item of %d stage workers]", ns);
+    for (int q = 0; q < 15; ++q) fprintf(stderr, " %s=%.0f", sn[q], ns ? sa[q] / ns : 0.0);
+    fprintf(stderr, "\n[last pass of %d Riccati workers] wait=%.0f backward=%.0f forward=%.0f publish=%.0f; stage 15 of the backward sweep: barrier=%.0f step=%.0f, of the forward sweep: barrier=%.0f step=%.0f, its first stage starts %.0f ticks after the backward sweep\n",
+            nr, nr ? ra[0] / nr : 0.0, nr ? ra[1] / nr : 0.0, nr ? ra[2] / nr : 0.0, nr ? ra[3] / nr : 0.0, nr ? ra[4] / nr : 0.0, nr ? ra[5] / nr : 0.0,
+            nr ? ra[6] / nr : 0.0, nr ? ra[7] / nr : 0.0, nr ? ra[8] / nr : 0.0);
+    return MPC_OK;
+}
+// one launch per kernel: stamps of the stage kernel's third iteration (per block) and of the Riccati kernel's fourth (per tile)
+static int report_stage_timing(mpc_handle* h, hipStream_t stream, const unsigned long long* d_dbg, int nblk, int ntiles) {
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    std::vector<unsigned long long> hd((size_t)16 * nblk);
+    HIP_TRY(h, hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    double acc[10] = {0};
+    int cnt = 0;
+    for (int bq = 0; bq < nblk; ++bq) {
+        if (!hd[(size_t)bq * 16 + 10]) continue;
+        for (int q = 0; q < 10; ++q) acc[q] += (double)(hd[(size_t)bq * 16 + q + 1] - hd[(size_t)bq * 16 + q]);
+        ++cnt;
+    }
+    fprintf(stderr, "[mpcgpu stage timing, shader-clock ticks per block, mean over %d blocks]", cnt);
+    static const char* names[10] = {"issue-loads", "wait+barrier", "P1", "reduce1", "linesearch", "P3-update", "exchange", "P4-eval", "reduce3", "P5"};
+    for (int q = 0; q < 10; ++q) fprintf(stderr, " %s=%.0f", names[q], cnt ? acc[q] / cnt : 0.0);
+    fprintf(stderr, "\n");
+    double bw = 0, fw = 0;
+    int c2 = 0;
+    for (int tq = 0; tq < ntiles && (size_t)(8 * nblk + (tq + 1) * 16) <= hd.size(); ++tq) {
+        const unsigned long long* r = hd.data() + (size_t)8 * nblk + (size_t)tq * 16;
+        if (!r[2]) continue;
+        bw += (double)(r[1] - r[0]);
+        fw += (double)(r[2] - r[1]);
+        ++c2;
+        if (tq == 0) fprintf(stderr, "[riccati stage 15 of tile 0] bwd barrier-wait=%lld compute=%lld | fwd barrier-wait=%lld compute=%lld\n",
+                             (long long)(r[4] - r[3]), (long long)(r[5] - r[4]), (long long)(r[7] - r[6]), (long long)(r[8] - r[7]));
+    }
+    fprintf(stderr, "[mpcgpu riccati timing, ticks per workgroup, mean over %d] backward=%.0f forward=%.0f\n", c2, c2 ? bw / c2 : 0.0, c2 ? fw / c2 : 0.0);
+    return MPC_OK;
+}
+// an abandoned pipeline launch: the arrival counters of all tiles as it left them (a tile short of a multiple of its items lost an arrival, one
+// above received a foreign one)
+static void report_arrivals(const uint32_t* ctl, int ntiles, uint32_t items) {
+    std::vector<uint32_t> sd((size_t)ntiles);
+    if (hipMemcpy(sd.data(), ctl + PIPE_HDR, sd.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return;
+    fprintf(stderr, "[mpcgpu]   arrivals per tile (items per tile and round: %u):", items);
+    for (int q = 0; q < ntiles; ++q) fprintf(stderr, " %u%s", sd[q] & 0x7FFFFFFFu, (sd[q] >> 31) ? "r" : "");
+    fprintf(stderr, "\n");
+}
+
+// One solve of B <= SolvePlan::max_rows instances: the path is plan_solve's; what is decided here reacts to what the GPU returns (the
+// abort word of the pipeline, the convergence poll, the restart after an abandoned launch).
 template <int NX>
 static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst,
                           double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream,
-                          double* trace, int32_t trace_rows, int32_t* n_it_out) {
+                          double* trace, int32_t trace_rows, int32_t* n_it_out, bool in_rescue) {
     const mpc_problem_desc& d = h->hp.desc;
+    const Knobs& kn = h->knobs;
     const size_t Bp = ((size_t)B + 63) / 64 * 64;
+    PlanState ps = plan_state(h, B, d_obst != nullptr, trace != nullptr, in_rescue);
+    SolvePlan pl = plan_solve(h->hp, kn, ps);
     // tile-major layout: the rows of a tile do not depend on the batch size, so a smaller batch lives in the first tiles of
     // a larger allocation (grow-only; the rescue path alternates between the full batch and a failed subset)
-    int rc = ensure_ws(h, Bp);
+    int rc = ensure_ws(h, Bp, pl.mailbox);
     if (rc) return rc;
-    // 256-thread stage workgroups (one wave per SIMD, the whole register file, no scratch) hold 8 instances up to N = 31 and
-    // 4 up to N = 63 (N = 50, B = 4096: 2.49 ms against 3.25 ms with 512-thread workgroups, 1.99 ms in the pipeline)
-    const mpc_handle::Knobs& kn = h->knobs;
-    const bool small_wg = 4 * (d.N + 1) <= 256 && !kn.big_wg;
-    int bx = pick_bx(d.N, small_wg ? 256 : STAGE_MAX_THREADS);
+    if (ps.ws_mailbox != h->ws_mailbox) { ps.ws_mailbox = h->ws_mailbox; pl = plan_solve(h->hp, kn, ps); }
+    const int bx = pl.bx, threads = pl.threads, nblk = pl.nblk, ntiles = pl.ntiles, G = pl.G, stash_rows = pl.stash_rows;
+    const int hyb_bx = pl.hyb_bx, hand = pl.hand;
     Params P;
-    P.mbw_live = 0;
     fill_params(P, h->hp, B, Bp, bx, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
+    P.mbw_live = 0;
     P.x0 = d_x0; P.p = d_p; P.x_out = d_x_out; P.status_out = d_status; P.iters_out = d_iters; P.kkt_out = d_kkt;
     const WsLayout w = ws_layout(d.N, d.nx, Bp, h->ws_mailbox);
     Prof prof{h, stream};
@@ -3126,61 +3184,22 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         P.per_inst_obst = 1;
         hipLaunchKernelGGL(k_transpose_obst, dim3((B + 255) / 256), dim3(256), 0, stream, d_obst, h->d_ws + w.OBST * 64, B, (uint32_t)w.tile_elems);
     }
-    const int S = d.N + 1;
-    const int threads = ((S * bx + 63) / 64) * 64;
-    const bool stage_timing = (kn.timing & TIMING_STAGE) != 0;
-    const int nblk = (B + bx - 1) / bx;
-    const int nw = threads / 64;
-    // LDS: reductions | the larger of (stage exchange, multiplier stash of the 256-thread variant) | prefetch images
-    const bool has_ou = h->hp.has_ou != 0;
-    const size_t lds_max = 160 * 1024 - 1024;          // the kernels also hold a few hundred bytes of static LDS
-    const int stash_rows = small_wg && MPC_STAGE_STASH ? std::max(Stash<NX>::rows(has_ou), 2 * NX) : 2 * NX;
-    const size_t lds_bytes = ((size_t)nw * 10 * bx + (size_t)2 * S * (NX + 2) + (size_t)stash_rows * threads) * sizeof(double);
-    // the start-iterate kernel parks nothing in LDS (no line search): with the small footprint several of its workgroups share a CU
-    // and the 512 of a 4096-instance batch run at once instead of in two rounds
-    const size_t lds_init = ((size_t)nw * 10 * bx + (size_t)2 * S * (NX + 2) + (size_t)2 * NX * threads) * sizeof(double);
-    const int rblk = (int)(Bp / 64);
-    const size_t ric_lds = std::max(RIC_DEPTH * (size_t)((MPC_EV(Dim<NX>::NBLK) * 512 + 1023) / 1024) * 1024,
-                                    RIC_DEPTH_F * (size_t)((Dim<NX>::NKK * 512 + 1023) / 1024 + 6) * 1024) + 64;   // ring + flag
-    {
-        if (!h->attr_set) {        // per handle: the attribute belongs to the function object of the handle's device
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_riccati<NX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ric_lds));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_stage<NX, false, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_start<NX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prestart_par<NX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_stage<NX, true, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_stage<NX, false, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_stage<NX, true, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pipeline<NX, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_wg<NX, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_stage<NX, false, 256, REF_VM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_stage<NX, false, 512, REF_VM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pipeline<NX, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pipeline<NX, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_wg<NX, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_wg<NX, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_wg<NX, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            h->attr_set = true;
-        }
+    if (!h->attr_set) {        // per handle: the attribute belongs to the function object of the handle's device
+        const void* lds_max_kernels[] = {
+            reinterpret_cast<const void*>(&k_stage<NX, false, 256>), reinterpret_cast<const void*>(&k_start<NX>), reinterpret_cast<const void*>(&k_prestart_par<NX>),
+            reinterpret_cast<const void*>(&k_stage<NX, true, 256>), reinterpret_cast<const void*>(&k_stage<NX, false, 512>), reinterpret_cast<const void*>(&k_stage<NX, true, 512>),
+            reinterpret_cast<const void*>(&k_pipeline<NX, false>), reinterpret_cast<const void*>(&k_solve_wg<NX, false>),
+            reinterpret_cast<const void*>(&k_stage<NX, false, 256, REF_VM>), reinterpret_cast<const void*>(&k_stage<NX, false, 512, REF_VM>),
+            reinterpret_cast<const void*>(&k_pipeline<NX, 2>), reinterpret_cast<const void*>(&k_pipeline<NX, 2, true>), reinterpret_cast<const void*>(&k_solve_wg<NX, 2>),
+            reinterpret_cast<const void*>(&k_solve_wg<NX, 0, true>), reinterpret_cast<const void*>(&k_solve_wg<NX, 2, true>)};
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_riccati<NX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.ric_lds));
+        for (const void* kf : lds_max_kernels) HIP_TRY(h, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
+        h->attr_set = true;
     }
 
     // ---- tile groups (sub-batches).  Every group runs ingest -> init -> iterations -> egest on its own stream.
-    const int ntiles = (int)(Bp / 64);
-    int G = 1;
-    // (measured on MI355X at B = 4096: 4 groups gain 4 % in fixed-iteration mode and lose in converged mode, where
-    //  every group polls on its own; the workgroups of the two kernels cannot share a CU, so the overlap is small.
-    //  Kept as an opt-in: MPCGPU_GROUPS=2..4.)
-    if (!trace && !stage_timing && kn.groups > 0) {
-        G = kn.groups;
-        if (G > ntiles / 4) G = ntiles / 4;
-        if (G < 1) G = 1;
-        if (G > mpc_handle::MAX_GROUPS) G = mpc_handle::MAX_GROUPS;
-    }
-    const bool ref_vm_ok = ((P.lo_mask | P.hi_mask) & ~REF_BOUND_VM) == 0u;    // bounds on the reference's four variables only
-    // one thread per stage with the reference's bound structure compiled in (option bound_mask, default on): same arithmetic, same bits
-    const bool masked = kn.bound_mask != 0 && ref_vm_ok && (P.dense_mask & REF_DENSE_LO) == REF_DENSE_LO && ((P.dense_mask >> 8) & REF_DENSE_HI) == REF_DENSE_HI && P.has_ol && !P.has_ou && P.obst_mult == 3 && !P.per_inst_obst;
     struct Group { int tile0, ntl, blk0, nblk, b0, b1; hipStream_t st; bool running; };
-    Group grp[mpc_handle::MAX_GROUPS];
+    Group grp[MAX_GROUPS];
     for (int g = 0; g < G; ++g) {
         Group& q = grp[g];
         q.tile0 = (int)((long long)ntiles * g / G);
@@ -3198,23 +3217,19 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
     auto launch_stage = [&](const Group& q, bool init) {
         Params Pg = P;
         Pg.tile0 = q.tile0;
-        if (!init && stage_timing && P.DBG) Pg.DBG = P.DBG;
-        if (small_wg) {
-            if (init) hipLaunchKernelGGL((k_stage<NX, true, 256>), dim3(q.nblk), dim3(threads), lds_init, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else if (masked) hipLaunchKernelGGL((k_stage<NX, false, 256, REF_VM>), dim3(q.nblk), dim3(threads), lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else hipLaunchKernelGGL((k_stage<NX, false, 256>), dim3(q.nblk), dim3(threads), lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
+        if (!init && pl.stage_timing && P.DBG) Pg.DBG = P.DBG;
+        if (pl.small_wg) {
+            if (init) hipLaunchKernelGGL((k_stage<NX, true, 256>), dim3(q.nblk), dim3(threads), pl.lds_init, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
+            else if (pl.masked) hipLaunchKernelGGL((k_stage<NX, false, 256, REF_VM>), dim3(q.nblk), dim3(threads), pl.lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
+            else hipLaunchKernelGGL((k_stage<NX, false, 256>), dim3(q.nblk), dim3(threads), pl.lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
         } else {
-            if (init) hipLaunchKernelGGL((k_stage<NX, true, 512>), dim3(q.nblk), dim3(threads), lds_init, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else if (masked) hipLaunchKernelGGL((k_stage<NX, false, 512, REF_VM>), dim3(q.nblk), dim3(threads), lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else hipLaunchKernelGGL((k_stage<NX, false, 512>), dim3(q.nblk), dim3(threads), lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
+            if (init) hipLaunchKernelGGL((k_stage<NX, true, 512>), dim3(q.nblk), dim3(threads), pl.lds_init, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
+            else if (pl.masked) hipLaunchKernelGGL((k_stage<NX, false, 512, REF_VM>), dim3(q.nblk), dim3(threads), pl.lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
+            else hipLaunchKernelGGL((k_stage<NX, false, 512>), dim3(q.nblk), dim3(threads), pl.lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
         }
     };
-    if (kn.poison && !h->in_rescue) {           // (debugging aid: NaN into every row of every tile of the workspace before the solve)
-        const WsLayout wl = ws_layout(d.N, d.nx, Bp, h->ws_mailbox);
-        hipLaunchKernelGGL(k_poison, dim3(1024), dim3(256), 0, stream, h->d_ws, (uint32_t)wl.tile_elems, (uint32_t)wl.ntiles, 0u, (uint32_t)wl.rows * 64u);
-    }
-    const int cap = d.fixed_iters > 0 ? d.fixed_iters : d.max_iter;
-    const int chunk = d.fixed_iters > 0 ? cap : 4;
+    if (pl.poison)            // (debugging aid: NaN into every row of every tile of the workspace before the solve)
+        hipLaunchKernelGGL(k_poison, dim3(1024), dim3(256), 0, stream, h->d_ws, (uint32_t)w.tile_elems, (uint32_t)w.ntiles, 0u, (uint32_t)w.rows * 64u);
     DevTmp t_trace, t_dbg, t_pdbg;
     double* d_trace = nullptr;
     if (trace) { HIP_TRY(h, hipMalloc(&t_trace.p, sizeof(double) * 8 * (size_t)B)); d_trace = t_trace.as<double>(); }
@@ -3226,7 +3241,7 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         return MPC_OK;
     };
     unsigned long long* d_dbg = nullptr;
-    if (stage_timing) {
+    if (pl.stage_timing) {
         HIP_TRY(h, hipMalloc(&t_dbg.p, sizeof(unsigned long long) * 16 * (size_t)nblk));
         d_dbg = t_dbg.as<unsigned long long>();
         HIP_TRY(h, hipMemsetAsync(d_dbg, 0, sizeof(unsigned long long) * 16 * (size_t)nblk, stream));
@@ -3242,163 +3257,51 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         h->tile_mask_cap = (size_t)ntiles;
     }
     P.tile_mask = h->d_tile_mask;
-    const bool polled = d.fixed_iters <= 0 && !trace;
-    if (polled && cap > mpc_handle::MAX_POLL_IT) { h->err = "max_iter exceeds the poll table (1024)"; return MPC_ERR_INVALID; }
+    if (pl.polled && pl.cap > MAX_POLL_IT) { h->err = "max_iter exceeds the poll table (1024)"; return MPC_ERR_INVALID; }
     int it = 0, chunk_id = 0;
-    // ---- single-launch pipeline (k_pipeline): all iterations in one persistent grid, tiles cycling independently.
-    // Pays while the Riccati chain is latency bound (few tiles per CU); larger batches keep one launch per kernel.
     h->last_mode = 0;
     for (int i = 0; i < 8; ++i) { h->pipe_prof[i] = 0; h->res_prof[i] = 0; }
     bool piped = false;
-    // k_solve_wg with `bxw` instances per workgroup (1 or 2: one wavefront per workgroup, four workgroups per CU; bx: a whole CU)
-    // LDS of a k_solve_wg workgroup (ONE wavefront, bxw = 1 or 2 instances): records + bounds table; a restart of the second chance runs the
-    // start-point safeguard and the start iterate in the same memory
-    auto wg_lds = [&](int bxw) {
-        const size_t pre = prestart_doubles(NX, S, bxw) * sizeof(double);
-        const size_t init = ((size_t)10 * bxw + (size_t)2 * S * (NX + 2) + (size_t)2 * NX * 64) * sizeof(double);
-        return std::max(WgLds<NX>::doubles(S, bxw) * sizeof(double), bxw == 1 ? std::max(pre, init) : (size_t)0);
-    };
-    // the second chance inside the launch (k_solve_wg<.., RESC>): one instance per workgroup, the conditions of rescue_dev
-    // (option rescue_wg: 0 never; 2 always; 1, the default: when the handle's LAST solve had stalled instances -- the kernel with the second chance
-    //  inside carries its restart code at 512 registers and ~1 KB of scratch per thread, which costs a batch that never stalls 6 - 10 %: B = 256 lane
-    //  following 0.405 -> 0.366 ms, N = 50 1.24 -> 1.17 ms; the two give the same bits, so a handle may change between them from solve to solve)
-    const bool resc_cond = kn.rescue && (kn.rescue_wg >= 2 || kn.rescue_alone || (kn.rescue_wg == 1 && h->resc_hint)) && d.fixed_iters <= 0 && !trace && h->hp.has_ol && h->hp.ol_raw > 0.0 && !h->in_rescue;
-    auto wg_resc = [&](int bxw) { return resc_cond && bxw == 1; };
     DevTmp t_wtrace;
     unsigned long long* d_wtrace = nullptr;
     int n_wtrace = 0;
     const int32_t* wg_list = nullptr;                   // (behind the pipeline: the instances its retiring tiles left, see k_solve_wg)
     const uint32_t* wg_list_n = nullptr;
-    int wg_grid = 0;
-    auto launch_wg = [&](int bxw, const uint32_t* skip_if, uint32_t* stats, uint32_t* fin_ctl) {
-        if ((kn.timing & TIMING_WG_TRACE) && !h->async_loop && !h->in_rescue) {
-            n_wtrace = (B + bxw - 1) / bxw;
+    auto launch_wg = [&](const uint32_t* skip_if, uint32_t* stats, uint32_t* fin_ctl) {
+        if (pl.wg_trace) {
+            n_wtrace = (B + hyb_bx - 1) / hyb_bx;
             if (hipMalloc(&t_wtrace.p, sizeof(unsigned long long) * 4 * (size_t)n_wtrace) == hipSuccess) {
                 d_wtrace = t_wtrace.as<unsigned long long>();
                 (void)hipMemsetAsync(d_wtrace, 0, sizeof(unsigned long long) * 4 * (size_t)n_wtrace, stream);
             }
         }
         Params Pw = P;
-        Pw.bx = bxw;
+        Pw.bx = hyb_bx;
         Pw.fin_ctl = fin_ctl; Pw.fin_host = h->h_pipe;
         if (skip_if != nullptr) Pw.DBG = nullptr;         // (behind the pipeline: a stamp buffer of option pipe_timing is sized for the PIPELINE's workgroups)
         const int thr = 64;                        // (S * bxw <= 64: checked where the path is chosen)
         WgRescue rs{h->hp.ol_raw, BOUND_RELAX, 0};
-        const dim3 grid(wg_grid > 0 ? wg_grid : (B + bxw - 1) / bxw);
-        if (wg_resc(bxw)) {
+        const dim3 grid(pl.wg_grid);
+        if (pl.wg_resc) {
             rs.on = 1;
             h->resc_ran = true;
             // (behind the pipeline the launch sees the instances on the hand-over lists only: one that stalled INSIDE the pipeline is on none of
             //  them and keeps its status for rescue_dev)
             h->resc_in_kernel = wg_list == nullptr;
-            if (masked) hipLaunchKernelGGL((k_solve_wg<NX, 2, true>), grid, dim3(thr), wg_lds(bxw), stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
-            else hipLaunchKernelGGL((k_solve_wg<NX, 0, true>), grid, dim3(thr), wg_lds(bxw), stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
+            if (pl.masked) hipLaunchKernelGGL((k_solve_wg<NX, 2, true>), grid, dim3(thr), pl.wg_lds, stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
+            else hipLaunchKernelGGL((k_solve_wg<NX, 0, true>), grid, dim3(thr), pl.wg_lds, stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
         }
-        else if (masked) hipLaunchKernelGGL((k_solve_wg<NX, 2>), grid, dim3(thr), wg_lds(bxw), stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
-        else hipLaunchKernelGGL((k_solve_wg<NX, false>), grid, dim3(thr), wg_lds(bxw), stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
+        else if (pl.masked) hipLaunchKernelGGL((k_solve_wg<NX, 2>), grid, dim3(thr), pl.wg_lds, stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
+        else hipLaunchKernelGGL((k_solve_wg<NX, false>), grid, dim3(thr), pl.wg_lds, stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
     };
-    // option wg_trace: every workgroup of k_solve_wg leaves its start, its end (100 MHz wall clock) and its rounds: when did the long ones start?
-    auto report_wtrace = [&]() {
-        if (!d_wtrace) return;
-        std::vector<unsigned long long> hw((size_t)4 * n_wtrace);
-        if (hipMemcpy(hw.data(), d_wtrace, hw.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return;
-        unsigned long long t0 = ~0ull, t1 = 0ull;
-        std::vector<int> live;
-        for (int w = 0; w < n_wtrace; ++w) if (hw[4 * w + 2]) { t0 = std::min(t0, hw[4 * w]); t1 = std::max(t1, hw[4 * w + 1]); live.push_back(w); }
-        if (live.empty()) return;
-        std::sort(live.begin(), live.end(), [&](int a, int b) { return hw[4 * a + 1] > hw[4 * b + 1]; });
-        int late = 0;
-        double start_max = 0;
-        for (int w : live) { const double st = (double)(hw[4 * w] - t0) * 1e-2; if (st > 5.0) ++late; start_max = std::max(start_max, st); }
-        fprintf(stderr, "[mpcgpu wg_trace] %d workgroups with work of %d; span %.1f us; %d of them start more than 5 us after the first (latest start %.1f us); the last to finish:\n",
-                (int)live.size(), n_wtrace, (double)(t1 - t0) * 1e-2, late, start_max);
-        for (size_t i = 0; i < live.size() && i < 12; ++i) {
-            const int w = live[i];
-            const double st = (double)(hw[4 * w] - t0) * 1e-2, en = (double)(hw[4 * w + 1] - t0) * 1e-2;
-            const double tf = (double)((hw[4 * w + 3] >> 16) & 0xFFFFFFull) * 1e-2, tr1 = (double)((hw[4 * w + 3] >> 40) & 0xFFFFFFull) * 1e-2;
-            fprintf(stderr, "    workgroup %5d: start %6.1f us  end %6.1f us  rounds %2d  instance-rounds %2d  -> %.1f us per round; instances taken over after %.1f us, first round done after %.1f us, later rounds %.1f us each\n",
-                    w, st, en, (int)hw[4 * w + 2], (int)(hw[4 * w + 3] & 0xFFFFu), (en - st) / (double)hw[4 * w + 2], tf, tr1, hw[4 * w + 2] > 1 ? (en - st - tr1) / (double)(hw[4 * w + 2] - 1) : 0.0);
-        }
-    };
-    // hybrid solve (option hybrid): the pipeline runs a tile while it has many instances iterating, then k_solve_wg finishes the
-    // stragglers one wavefront per (hybrid_bx) instance -- `hand` = live instances per tile at which a tile changes over
-    // instances per wavefront of k_solve_wg: two fill the lanes (62 of 64 at N = 30) and halve the wavefronts a full machine needs; a batch
-    // that fits the machine one instance per wavefront (4 wavefront slots per CU) is faster that way -- a round of a wavefront with two live
-    // instances costs 47 us against 33 us (B = 256: 0.58 -> 0.54 ms).  hybrid_bx = 1 / 2 pins it, 0 chooses.
-    int hyb_bx = ((kn.hybrid_bx == 2 || (kn.hybrid_bx == 0 && B > 4 * h->n_cu)) && S * 2 <= 64) ? 2 : 1;
-    // (the levels of the second chance, rescue_dev: always the stragglers' kernel alone with one instance per wavefront -- the configuration the second
-    //  chance INSIDE a launch runs in, whatever the number of stalled instances: the pipeline's sweeps round differently from the matrix-pipe sweeps of
-    //  k_solve_wg, and which of the two paths gave an instance its second chance must not show in its bits)
-    // A handle whose last solve needed second chances: one instance per wavefront also somewhat beyond the machine's slots -- as far as the stragglers'
-    // kernel serves such a batch alone anyway, below -- so that the kernel with the second chance inside takes it (collision avoidance B = 1025
-    // 3.49 -> 2.83 ms, B = 2304 6.62 -> 4.81 ms; the same bits: an instance's arithmetic in k_solve_wg does not depend on its wavefront's company).
-    if (kn.hybrid_bx == 0 && resc_cond && hyb_bx == 2 && (size_t)ntiles * 64 * 8 <= (size_t)4 * h->n_cu * 18) hyb_bx = 1;
-    // Option rescue_alone (the caller knows the family stalls -- collision avoidance: a few instances per thousand, whose chains of 50 + 30 ... 60
-    // iterations are what the batch waits for): the stragglers' kernel ALONE, one instance per wavefront, with the second chance inside, up to 8192
-    // instances -- the bulk of the batch fits beside those chains, while the levels behind a launch cost a synchronised solve each: B = 3072 / 4096
-    // 8.3 -> 4.9 ms, 6144 9.2 -> 7.3, 8192 13.7 -> 12.4 ms.  An option and not the handle's history: it changes which sweeps serve an instance (last
-    // bits), and two consecutive calls of a handle give the same bits.
-    const bool resc_alone = kn.rescue_alone && kn.hybrid_bx == 0 && kn.hybrid_live < 0 && resc_cond && ntiles <= 128;
-    if (resc_alone) hyb_bx = 1;
-    if (h->in_rescue) hyb_bx = 1;
-    // (not with a fixed iteration count: no instance ever stops iterating, so no tile would ever change over)
-    const bool hyb_ok = kn.hybrid && h->ws_mailbox && d.fixed_iters <= 0 && kn.pipeline && !h->pipe_disabled && G == 1 && small_wg && S <= 64 && wg_lds(hyb_bx) <= lds_max / 4 && !trace && !stage_timing;
-    int hand = 0;
-    if (hyb_ok) {
-        // what the straggler launch holds at once, per tile (4 wavefront slots per CU x hyb_bx instances) ...
-        const int base = std::min(64, 4 * h->n_cu * hyb_bx / std::max(1, (int)(Bp / 64)));
-        // ... and half as much again when k_solve_wg deals its workgroups from the hand-over lists: the instances beyond the machine's slots are
-        // the ones closest to convergence and start when the first wavefronts free up, while the tiles leave the pipeline a round earlier --
-        // its rounds cost an instance 67 us, a straggler round 25 us (tools/hand_sweep.py: 3 - 5 % per batch on four instance sets at B = 4096,
-        // B = 3000 / 8192 and N = 50 likewise; above ~50 of 64 the pipeline no longer carries the bulk)
-        hand = base >= 64 ? base : std::max(base, std::min(50, base < 32 ? 7 * base / 4 : 3 * base / 2));
-        // ... and with ONE instance per wavefront there (horizons beyond 31 stages) at least 40: a round of the pipeline costs such a tile ~100 us, a
-        // straggler round 30, and the wavefronts beyond the machine's slots start as the first ones retire (tools/hand_sweep.py n50, four instance
-        // sets at B = 4096: 1.17 - 1.21 -> 1.14 - 1.17 ms; B = 5000 / 6000 / 8192: -6 / -10 / -10 %; B = 3000 unchanged)
-        if (hyb_bx == 1 && base < 64 && hand < 40) hand = 40;
-        // A batch somewhat larger than the stragglers' launch holds at once is still faster there alone than through the pipeline -- the wavefronts
-        // beyond the machine's slots start as the first ones retire --: up to 9/8 of the slots with two instances per wavefront (N = 30: B = 2049
-        // 0.75 -> 0.57 ms, 2304 0.74 -> 0.72, 2432 already 0.72 against 0.75), up to 9/4 with one, where a round of the pipeline costs three
-        // straggler rounds (N = 50: B = 1025 0.83 -> 0.54 ms, 1536 0.92 -> 0.77, 2304 0.98 -> 0.92, 2560 equal)
-        if ((size_t)ntiles * 64 * 8 <= (size_t)4 * h->n_cu * hyb_bx * (hyb_bx == 2 ? 9 : 18)) hand = 64;
-        if (resc_alone) hand = 64;
-        if (kn.hybrid_live >= 0) hand = std::min(64, kn.hybrid_live);
-    }
-    const bool wg_only = hyb_ok && (hand >= 64 || h->in_rescue);             // every tile would change over at once: no pipeline launch at all
-    // ---- which path serves the iteration loop (decided before anything is launched: the kernels of the loop write the caller's rows themselves)
-    uint32_t xcd_mask = h->xcd_mask;
-    if (kn.pipe_xcd_mask) {            // tests: pretend some XCDs away (a partitioned device); workgroups that land there leave
-        const uint32_t m = kn.pipe_xcd_mask & h->xcd_mask;
-        if (m) xcd_mask = m;
-    }
-    const int n_xcd = __builtin_popcount(xcd_mask);
-    const int tiles_x = (ntiles + n_xcd - 1) / n_xcd;
-    const int cu_x = std::max(2, h->n_cu / n_xcd);                     // a quarter of an XCD's CUs run Riccati sweeps (8 of 32)
-    // (nine to twelve tiles per XCD -- batches just above 4096 instances --: every tile its own Riccati worker still; with eight, one worker would own
-    //  two tiles and every round of the XCD would wait for its two passes -- as long as the stage workers that remain are not the scarcer kind:
-    //  at most five stage items per round for each of them.  tools/size_sweep.py, N = 30: B = 4160 ... 6144 -10 ... -4 %; N = 50, sixteen items per
-    //  tile, loses 2 - 11 % with it and keeps eight.)
-    const int n_ric_base = std::max(1, cu_x / 4);
-    // (... and the sweep of a tile is long against its stage items: at N = 10 a worker's second pass hides behind the first tile's stage work,
-    //  and B = 6144 loses 9 % to the four stage workers it gives up)
-    const bool ric_per_tile = tiles_x > n_ric_base && tiles_x <= 3 * cu_x / 8 && (64 / bx) * tiles_x <= 5 * (cu_x - tiles_x) && S >= 24;
-    const int n_ric = std::min(ric_per_tile ? tiles_x : n_ric_base, tiles_x);
-    // (threads >= 192: a stage item then covers at least six stages per wavefront and instance column -- the shapes the hand-off timing was measured on)
-    const bool eligible = G == 1 && !trace && !stage_timing && small_wg && threads >= 192 && threads <= 256 &&
-                          ntiles <= (d.fixed_iters > 0 ? 64 : PIPE_MAX_TILES) && (tiles_x + n_ric - 1) / n_ric <= 32 &&
-                          std::max(lds_bytes, ric_lds) <= lds_max;
-    const bool res_path = wg_only;         // k_solve_wg alone
-    const bool pipe_path = !res_path && eligible && !h->pipe_disabled && kn.pipeline;
-    // Both get a control block (abort word, round count, statistics of both loop kernels, count of instances that did not converge, hand-over
-    // lists' counters; the pipeline's queues behind them) -- one of two that alternate: the start kernel of a solve zeroes the other one for the
-    // next solve, the last workgroup of the loop copies the head of this one into the handle's pinned block.
+    // Both loop paths get a control block (abort word, round count, statistics of both loop kernels, count of instances that did not converge,
+    // hand-over lists' counters; the pipeline's queues behind them) -- one of two that alternate: the start kernel of a solve zeroes the other one
+    // for the next solve, the last workgroup of the loop copies the head of this one into the handle's pinned block.
     uint32_t *ctl = nullptr, *zero_next = nullptr;
     size_t ctl_words = 0;
     bool next_zeroed = false;
-    uint32_t pipe_cap = 1;
-    if (res_path || pipe_path) {
-        while (pipe_path && pipe_cap < 2u * (64u / (uint32_t)bx) * (uint32_t)tiles_x) pipe_cap <<= 1;
-        ctl_words = pipe_ctl_words((uint32_t)ntiles, pipe_cap);
+    if (pl.res_path || pl.pipe_path) {
+        ctl_words = pipe_ctl_words((uint32_t)ntiles, pl.pipe_cap);
         if (h->pipe_words < ctl_words) {
             if (h->d_pipe) (void)hipFree(h->d_pipe);
             h->d_pipe = nullptr; h->pipe_words = 0;
@@ -3423,44 +3326,20 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         Pg.tile0 = q.tile0;
         prof.begin(2, q.st);
         const int n_w = 2 * d.N + NX * (d.N + 1);
-        // start-point safeguard: stage-parallel form when its LDS footprint fits the default limit and the horizon has the two
-        // stage-threads the scans need (otherwise the two-chain kernel)
-        const size_t lds_pre = prestart_doubles(NX, S, bx) * sizeof(double);
-        const size_t lds_in = (size_t)bx * (2 * n_w - 2 * d.N) * sizeof(double);             // the block's rows of x0 and of the X_ref part of p
-        // (the fused kernel keeps the safeguard's LDS and the block's caller rows side by side; two of its workgroups share a CU)
-        const size_t lds_red = (size_t)(threads / 64) * 10 * bx * sizeof(double);            // (stage_block's reduction scratch, in front of the safeguard's region)
-        const bool fused = lds_red + lds_pre + 16 + lds_in <= 78 * 1024 && d.N >= 1 && small_wg;
-        if (!fused) hipLaunchKernelGGL((k_ingest<NX>), dim3(q.ntl, (n_w + 63) / 64 + (n_w - 2 * d.N + 63) / 64), dim3(256), 0, q.st, Pg);
-        if (fused) {
+        if (!pl.fused) hipLaunchKernelGGL((k_ingest<NX>), dim3(q.ntl, (n_w + 63) / 64 + (n_w - 2 * d.N + 63) / 64), dim3(256), 0, q.st, Pg);
+        if (pl.fused) {
             // (one launch for ingest, safeguard and start iterate: same blocks, same threads)
             DevTmp t_sdbg;
-            if ((kn.timing & TIMING_START) && !h->async_loop && G == 1 && hipMalloc(&t_sdbg.p, sizeof(unsigned long long) * 16 * (size_t)q.nblk) == hipSuccess) {
+            if (pl.start_timing && hipMalloc(&t_sdbg.p, sizeof(unsigned long long) * 16 * (size_t)q.nblk) == hipSuccess) {
                 (void)hipMemsetAsync(t_sdbg.p, 0, sizeof(unsigned long long) * 16 * (size_t)q.nblk, q.st);
                 Pg.DBG = t_sdbg.as<unsigned long long>();
             }
-            hipLaunchKernelGGL((k_start<NX>), dim3(q.nblk), dim3(threads), std::max(lds_red + lds_pre + 16 + lds_in, lds_init), q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows,
+            hipLaunchKernelGGL((k_start<NX>), dim3(q.nblk), dim3(threads), pl.lds_start, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows,
                                g == 0 ? zero_next : (uint32_t*)nullptr, (uint32_t)ctl_words);
             if (g == 0 && zero_next != nullptr) next_zeroed = true;
-            if (Pg.DBG) {          // (option start_timing: shader-clock stamps of every workgroup of k_start; synchronises)
-                std::vector<unsigned long long> hd((size_t)16 * q.nblk);
-                if (hipStreamSynchronize(q.st) == hipSuccess && hipMemcpy(hd.data(), Pg.DBG, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
-                    const int order[16] = {11, 12, 13, 1, 2, 3, 4, 5, 6, 14, 15, 0, 7, 8, 9, 10};
-                    static const char* names[15] = {"rows->LDS", "Z/REF stores", "bounds+a0", "defects", "scan1", "tan+scan2", "sincos+scan3", "ROLL+sums", "decide", "fence", "enter", "init point+exchange", "eval+assemble", "reduce", "finish"};
-                    double acc[15] = {0};
-                    unsigned long long t0 = ~0ull, t1 = 0ull;
-                    for (int bq = 0; bq < q.nblk; ++bq) {
-                        const unsigned long long* r = hd.data() + (size_t)bq * 16;
-                        for (int j = 0; j < 15; ++j) acc[j] += (double)(long long)(r[order[j + 1]] - r[order[j]]);
-                        t0 = std::min(t0, r[11]); t1 = std::max(t1, r[10]);
-                    }
-                    fprintf(stderr, "[mpcgpu k_start timing, shader-clock ticks, mean over %d workgroups]", q.nblk);
-                    for (int j = 0; j < 15; ++j) fprintf(stderr, " %s=%.0f", names[j], acc[j] / q.nblk);
-                    fprintf(stderr, "; first start to last end %.0f\n", (double)(t1 - t0));
-                }
-                Pg.DBG = nullptr;
-            }
+            if (Pg.DBG) report_start_timing(q.st, Pg.DBG, q.nblk);          // (synchronises)
         } else {
-            hipLaunchKernelGGL((k_prestart_par<NX>), dim3(q.nblk), dim3(threads), lds_pre, q.st, Pg);       // (N = 127, bx = 4: 112 KB of LDS)
+            hipLaunchKernelGGL((k_prestart_par<NX>), dim3(q.nblk), dim3(threads), pl.lds_pre, q.st, Pg);       // (N = 127, bx = 4: 112 KB of LDS)
             launch_stage(q, true);
         }
         if (G > 1) prof.end(q.st);          // (one stream: the span stays open, the first kernel of the loop starts where it ends)
@@ -3470,17 +3349,16 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         h->pipe_clean[h->pipe_flip ^ 1] = next_zeroed ? ctl_words : 0;
         h->pipe_flip ^= 1;
     }
-    if (res_path) {
+    if (pl.res_path) {
         // ---- workgroup-resident solve alone: ALL iterations of every instance in one launch of k_solve_wg
-        const int nblk_dbg = (B + hyb_bx - 1) / hyb_bx;
         DevTmp t_rdbg;
-        if ((kn.timing & TIMING_WG) && !h->async_loop) {
-            HIP_TRY(h, hipMalloc(&t_rdbg.p, sizeof(unsigned long long) * 16 * (size_t)nblk_dbg));
-            HIP_TRY(h, hipMemsetAsync(t_rdbg.p, 0, sizeof(unsigned long long) * 16 * (size_t)nblk_dbg, stream));
+        if (pl.wg_timing) {
+            HIP_TRY(h, hipMalloc(&t_rdbg.p, sizeof(unsigned long long) * 16 * (size_t)pl.wg_grid));
+            HIP_TRY(h, hipMemsetAsync(t_rdbg.p, 0, sizeof(unsigned long long) * 16 * (size_t)pl.wg_grid, stream));
             P.DBG = t_rdbg.as<unsigned long long>();
         }
         prof.next(5, stream);
-        launch_wg(hyb_bx, nullptr, ctl + PIPE_WG, h->async_loop ? nullptr : ctl + PIPE_ABORT);
+        launch_wg(nullptr, ctl + PIPE_WG, h->async_loop ? nullptr : ctl + PIPE_ABORT);
         prof.end(stream);
         h->last_mode = 2;
         if (h->async_loop) {             // closed-loop driver: nothing comes back to the host per step (this path has no abort word)
@@ -3491,176 +3369,113 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         HIP_TRY(h, wait_stream(h, stream));          // (the last workgroup to leave has put the block's head into h_pipe)
         h->h_fail[0] = h->h_pipe[14];
         for (int q = 0; q < 4; ++q) h->h_fail[2 + q] = h->h_pipe[16 + q];
-        if (h->resc_ran && !h->in_rescue) h->rescued_last = (int)h->h_pipe[20];
-        report_wtrace();
-        if (P.DBG) {          // shader-clock stamps of every workgroup's third round
-            std::vector<unsigned long long> hd((size_t)16 * nblk_dbg);
-            HIP_TRY(h, hipMemcpy(hd.data(), P.DBG, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            double acc[16] = {0};
-            int cnt = 0;
-            {
-                // k_solve_wg: 12 round start, 13 records in LDS, 14 sweeps done, [0..10 stage_block's own stamps], 15 round end
-                const int order[16] = {12, 13, 14, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 15, 15};
-                for (int bq = 0; bq < nblk_dbg; ++bq) {
-                    const unsigned long long* r = hd.data() + (size_t)bq * 16;
-                    if (!r[15] || !r[10]) continue;
-                    for (int q = 0; q < 14; ++q) acc[q] += (double)(long long)(r[order[q + 1]] - r[order[q]]);
-                    ++cnt;
-                }
-                static const char* names[14] = {"records", "sweeps", "enter", "load+premath", "or", "P1", "reduce1+ls-begin", "linesearch", "P3-update", "exchange", "P4-eval", "reduce3", "P5", "drain"};
-                fprintf(stderr, "[mpcgpu k_solve_wg timing, shader-clock ticks, third round of %d workgroups]", cnt);
-                for (int q = 0; q < 14; ++q) fprintf(stderr, " %s=%.0f", names[q], cnt ? acc[q] / cnt : 0.0);
-            }
-            fprintf(stderr, "\n");
+        if (h->resc_ran && !in_rescue) h->rescued_last = (int)h->h_pipe[20];
+        report_wg_trace(d_wtrace, n_wtrace);
+        if (P.DBG) {
+            rc = report_wg_timing(h, P.DBG, pl.wg_grid);
+            if (rc) return rc;
             P.DBG = nullptr;
         }
         piped = true;
         it = (int)h->h_fail[2];
-        h->res_prof[1] = 1; h->res_prof[2] = it; h->res_prof[3] = nblk_dbg; h->res_prof[4] = h->h_fail[3]; h->res_prof[5] = h->h_fail[4]; h->res_prof[6] = h->h_fail[5];
-    } else {
-        // (measured: 7-11 % faster than one launch per kernel at B = 64 ... 1024, 31 % at B = 4096; at B = 8192 the early
-        //  finishers of converged mode still gain 15 %, a fixed iteration count loses 8 % -- with two tiles per Riccati
-        //  worker both roles are throughput bound and the split of the CUs only costs)
-        if (pipe_path) {
-            PipeArgs A;
-            A.ntiles = (uint32_t)ntiles;
-            A.n_ric = (uint32_t)n_ric;
-            A.xcd_mask = xcd_mask;
-            A.items = 64u / (uint32_t)bx;
-            A.cap = pipe_cap;
-            A.flags = kn.pipe_test_abort ? 2u : 0u;
-            // the Riccati workers help with the stage items (k_pipeline<.., HELP>) where those are the bottleneck: more than three per stage worker and round
-            const bool pipe_help = (kn.pipe_help < 0 ? (int)A.items * tiles_x > 3 * (cu_x - n_ric) : kn.pipe_help != 0);
-            A.handover = (uint32_t)hand;
-            int32_t* ho_list = nullptr;
-            A.ho_list = nullptr;
-            if (hand > 0) {
-                ho_list = static_cast<int32_t*>(scratch_get(h, 36, (size_t)HO_BUCKETS * Bp * sizeof(int32_t)));
-                if (!ho_list) { h->err = "out of device memory"; return MPC_ERR_HIP; }
-                A.ho_list = ho_list;
-            }
-            A.ctl = ctl;
-            unsigned long long* d_pdbg = nullptr;
-            if (kn.timing & TIMING_PIPE) {
-                HIP_TRY(h, hipMalloc(&t_pdbg.p, sizeof(unsigned long long) * 16 * (size_t)h->n_cu));
-                d_pdbg = t_pdbg.as<unsigned long long>();
-                HIP_TRY(h, hipMemsetAsync(d_pdbg, 0, sizeof(unsigned long long) * 16 * (size_t)h->n_cu, stream));
-                P.DBG = d_pdbg;
-            }
-            prof.next(3, stream);
-            // tiles about to leave the pipeline (at most hand + 16 instances left; never a full tile) write the mailbox arrays in their stage items
-            P.mbw_live = hand > 0 ? std::min(63, hand + 16) : 0;
-            // (helping Riccati workers only in the variant with the reference's bound structure compiled in: the general one is at 512 registers with them)
-            if (pipe_help && masked) hipLaunchKernelGGL((k_pipeline<NX, 2, true>), dim3(h->n_cu), dim3(threads), std::max(lds_bytes, ric_lds), stream, P, A, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else if (masked) hipLaunchKernelGGL((k_pipeline<NX, 2>), dim3(h->n_cu), dim3(threads), std::max(lds_bytes, ric_lds), stream, P, A, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else hipLaunchKernelGGL((k_pipeline<NX, false>), dim3(h->n_cu), dim3(threads), std::max(lds_bytes, ric_lds), stream, P, A, h->hp.n_mult, h->hp.n_z, stash_rows);
-            if (hand <= 0) prof.end(stream);
-            if (hand > 0) {        // (its statistics words are part of the control block: no fill, no copy of their own)
-                if (!h->prof_span) prof.next(5, stream);          // (span mode: the pipeline's span stays open over k_solve_wg)
-                if (ho_list) {
-                    // (the counters: words of the control block, zero at the start of every solve)
-                    wg_list = ho_list; wg_list_n = ctl + PIPE_HO;
-                    // as many workgroups as the machine holds at once (four single-wavefront workgroups per CU), each with up to hyb_bx instances
-                    wg_grid = std::min((B + hyb_bx - 1) / hyb_bx, std::max(4 * h->n_cu, (int)((size_t)hand * ntiles + hyb_bx - 1) / hyb_bx));
-                }
-                // (the last kernel of the solve: its last workgroup copies the head of the control block into the pinned host block)
-                launch_wg(hyb_bx, (const uint32_t*)(ctl + PIPE_ABORT), ctl + PIPE_WG, h->async_loop ? nullptr : ctl + PIPE_ABORT);
-            }
-            prof.end(stream);
-            if (h->async_loop) {
-                // closed-loop driver: nothing comes back to the host per step -- a launch that had to be abandoned leaves its mark
-                // in the loop's sticky abort word, the bookkeeping kernels behind it then do nothing and the host replays the loop
-                hipLaunchKernelGGL(k_loop_sticky, dim3(1), dim3(1), 0, stream, (const uint32_t*)(ctl + PIPE_ABORT), h->d_fail + 1);
-                HIP_TRY(h, hipGetLastError());
-                h->async_ok = true;
-                h->last_mode = 1;
-                return MPC_OK;
-            }
-            // (no kernel behind the loop: the rows are out -- Params::emit -- and k_solve_wg has left the block's head in h_pipe; a pipeline that
-            //  runs its tiles to the end, option hybrid = 0, has no such epilogue: a copy command)
-            if (hand <= 0) HIP_TRY(h, hipMemcpyAsync(h->h_pipe, ctl + PIPE_ABORT, PIPE_FIN_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(h, wait_stream(h, stream));
-            h->h_fail[0] = h->h_pipe[14];
-            report_wtrace();
-            for (int q = 0; q < 4; ++q) h->h_fail[2 + q] = h->h_pipe[16 + q];
-            if (h->resc_ran && !h->in_rescue) h->rescued_last = (int)h->h_pipe[20];       // (fifth word: instances that took the second chance inside the launch)
-            if (hand > 0) {        // the stragglers' kernel: rounds of its slowest workgroup, workgroups, workgroup-rounds, sweeps, instance-iterations
-                h->res_prof[1] = 1; h->res_prof[2] = h->h_fail[2]; h->res_prof[3] = wg_grid > 0 ? wg_grid : (B + hyb_bx - 1) / hyb_bx;      // (workgroups launched: what the machine holds when they are dealt from the hand-over lists)
-                h->res_prof[4] = h->h_fail[3]; h->res_prof[5] = h->h_fail[4]; h->res_prof[6] = h->h_fail[5];
-            }
-            if (h->h_pipe[0] != 0u) {
-                // a bounded wait ran out (e.g. the dispatcher left an XCD without stage workers): the workspace is part-way
-                // through an iteration, so start over with one launch per kernel.  Once may be a transient of the machine's other tenants (the
-                // workgroups of a collective spinning on a slow peer, another handle's persistent launch); the handle stays on that path when it
-                // has happened PIPE_ABORTS_MAX times
-                h->pipe_disabled = true;
-                h->resc_in_kernel = h->resc_ran = false;         // (the k_solve_wg behind the abandoned launch returned at once: no instance has had its second chance)
-                // (abort word: 1 option pipe_test_abort, 2 a Riccati worker waited for its tile's stage items [tile << 16 | round; arrivals], 3 a helping
-                //  Riccati worker / 4 a stage worker waited for its queue slot [ticket; queue tail]; words 28 - 31 of the block's head)
-                fprintf(stderr, "[mpcgpu] single-launch pipeline abandoned (bounded wait expired: code %u, %u / %u, a millisecond later %u, waited %u ticks); re-running with one launch per kernel\n",
-                        h->h_pipe[0], h->h_pipe[28], h->h_pipe[29], h->h_pipe[30], h->h_pipe[31]);
-                {   // (the arrival counters of all tiles as the launch left them: a tile short of a multiple of its items lost an arrival, one above received a foreign one)
-                    std::vector<uint32_t> sd((size_t)ntiles);
-                    if (hipMemcpy(sd.data(), ctl + PIPE_HDR, sd.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess) {
-                        fprintf(stderr, "[mpcgpu]   arrivals per tile (items per tile and round: %u):", A.items);
-                        for (int q = 0; q < ntiles; ++q) fprintf(stderr, " %u%s", sd[q] & 0x7FFFFFFFu, (sd[q] >> 31) ? "r" : "");
-                        fprintf(stderr, "\n");
-                    }
-                }
-                const int rc_again = solve_dev_impl<NX>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it_out);
-                if (++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;
-                return rc_again;
-            }
-            P.DBG = nullptr;
-            if (d_pdbg) {       // shader-clock stamps of every worker's LAST work item / tile pass
-                std::vector<unsigned long long> hd((size_t)16 * h->n_cu);
-                HIP_TRY(h, hipMemcpy(hd.data(), d_pdbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                double sa[16] = {0}, ra[9] = {0};
-                int ns = 0, nr = 0;
-                for (int bq = 0; bq < h->n_cu; ++bq) {
-                    const unsigned long long* r = hd.data() + (size_t)bq * 16;
-                    if (r[15] && r[10]) {
-                        const int order[16] = {11, 12, 13, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 14, 15};
-                        for (int q = 0; q + 1 < 16; ++q) sa[q] += (double)(long long)(r[order[q + 1]] - r[order[q]]);
-                        ++ns;
-                    } else if (r[13] && r[2]) {
-                        ra[0] += (double)(long long)(r[12] - r[11]); ra[1] += (double)(long long)(r[1] - r[12]);
-                        ra[2] += (double)(long long)(r[2] - r[1]); ra[3] += (double)(long long)(r[13] - r[2]);
-                        ra[4] += (double)(long long)(r[4] - r[3]); ra[5] += (double)(long long)(r[5] - r[4]);
-                        ra[6] += (double)(long long)(r[7] - r[6]); ra[7] += (double)(long long)(r[8] - r[7]);
-                        ra[8] += (double)(long long)(r[9] - r[1]);
-                        ++nr;
-                    }
-                }
-                static const char* sn[15] = {"dequeue", "acquire+bcast", "enter", "issue-loads", "wait+barrier", "P1", "reduce1", "linesearch", "P3-update",
-                                             "exchange", "P4-eval", "reduce3", "P5", "drain", "signal"};
-                fprintf(stderr, "[mpcgpu pipeline timing, shader-clock ticks, last item of %d stage workers]", ns);
-                for (int q = 0; q < 15; ++q) fprintf(stderr, " %s=%.0f", sn[q], ns ? sa[q] / ns : 0.0);
-                fprintf(stderr, "\n[last pass of %d Riccati workers] wait=%.0f backward=%.0f forward=%.0f publish=%.0f; stage 15 of the backward sweep: barrier=%.0f step=%.0f, of the forward sweep: barrier=%.0f step=%.0f, its first stage starts %.0f ticks after the backward sweep\n",
-                        nr, nr ? ra[0] / nr : 0.0, nr ? ra[1] / nr : 0.0, nr ? ra[2] / nr : 0.0, nr ? ra[3] / nr : 0.0, nr ? ra[4] / nr : 0.0, nr ? ra[5] / nr : 0.0,
-                        nr ? ra[6] / nr : 0.0, nr ? ra[7] / nr : 0.0, nr ? ra[8] / nr : 0.0);
-            }
-            piped = true;
-            h->last_mode = 1;
-            it = (int)h->h_pipe[1];
-            const unsigned long long* st64 = reinterpret_cast<const unsigned long long*>(h->h_pipe + 2);
-            h->pipe_prof[1] = 1; h->pipe_prof[2] = it;
-            h->pipe_prof[3] = (double)st64[0] * 1e-5; h->pipe_prof[4] = (double)st64[1] * 1e-5; h->pipe_prof[5] = (double)st64[2] * 1e-5;   // 100 MHz ticks -> ms
-            h->pipe_prof[6] = (double)st64[3]; h->pipe_prof[7] = (double)h->h_pipe[12] + 1e-3 * (double)h->h_pipe[13];
+        h->res_prof[1] = 1; h->res_prof[2] = it; h->res_prof[3] = pl.wg_grid; h->res_prof[4] = h->h_fail[3]; h->res_prof[5] = h->h_fail[4]; h->res_prof[6] = h->h_fail[5];
+    } else if (pl.pipe_path) {
+        // ---- single-launch pipeline (k_pipeline): all iterations in one persistent grid, tiles cycling independently
+        PipeArgs A;
+        A.ntiles = (uint32_t)ntiles;
+        A.n_ric = (uint32_t)pl.n_ric;
+        A.xcd_mask = pl.xcd_mask;
+        A.items = 64u / (uint32_t)bx;
+        A.cap = pl.pipe_cap;
+        A.flags = kn.pipe_test_abort ? 2u : 0u;
+        A.handover = (uint32_t)hand;
+        A.ho_list = nullptr;
+        if (hand > 0) {
+            A.ho_list = static_cast<int32_t*>(scratch_get(h, SCR_HO_LIST, (size_t)HO_BUCKETS * Bp * sizeof(int32_t)));
+            if (!A.ho_list) { h->err = "out of device memory"; return MPC_ERR_HIP; }
         }
+        A.ctl = ctl;
+        unsigned long long* d_pdbg = nullptr;
+        if (pl.pipe_timing) {
+            HIP_TRY(h, hipMalloc(&t_pdbg.p, sizeof(unsigned long long) * 16 * (size_t)h->n_cu));
+            d_pdbg = t_pdbg.as<unsigned long long>();
+            HIP_TRY(h, hipMemsetAsync(d_pdbg, 0, sizeof(unsigned long long) * 16 * (size_t)h->n_cu, stream));
+            P.DBG = d_pdbg;
+        }
+        prof.next(3, stream);
+        P.mbw_live = pl.mbw_live;
+        const size_t lds_pipe = std::max(pl.lds_bytes, pl.ric_lds);
+        if (pl.pipe_help) hipLaunchKernelGGL((k_pipeline<NX, 2, true>), dim3(h->n_cu), dim3(threads), lds_pipe, stream, P, A, h->hp.n_mult, h->hp.n_z, stash_rows);
+        else if (pl.masked) hipLaunchKernelGGL((k_pipeline<NX, 2>), dim3(h->n_cu), dim3(threads), lds_pipe, stream, P, A, h->hp.n_mult, h->hp.n_z, stash_rows);
+        else hipLaunchKernelGGL((k_pipeline<NX, false>), dim3(h->n_cu), dim3(threads), lds_pipe, stream, P, A, h->hp.n_mult, h->hp.n_z, stash_rows);
+        if (hand <= 0) prof.end(stream);
+        if (hand > 0) {        // (its statistics words are part of the control block: no fill, no copy of their own)
+            if (!h->prof_span) prof.next(5, stream);          // (span mode: the pipeline's span stays open over k_solve_wg)
+            // (the counters: words of the control block, zero at the start of every solve)
+            wg_list = A.ho_list; wg_list_n = ctl + PIPE_HO;
+            // (the last kernel of the solve: its last workgroup copies the head of the control block into the pinned host block)
+            launch_wg((const uint32_t*)(ctl + PIPE_ABORT), ctl + PIPE_WG, h->async_loop ? nullptr : ctl + PIPE_ABORT);
+        }
+        prof.end(stream);
+        if (h->async_loop) {
+            // closed-loop driver: nothing comes back to the host per step -- a launch that had to be abandoned leaves its mark
+            // in the loop's sticky abort word, the bookkeeping kernels behind it then do nothing and the host replays the loop
+            hipLaunchKernelGGL(k_loop_sticky, dim3(1), dim3(1), 0, stream, (const uint32_t*)(ctl + PIPE_ABORT), h->d_fail + 1);
+            HIP_TRY(h, hipGetLastError());
+            h->async_ok = true;
+            h->last_mode = 1;
+            return MPC_OK;
+        }
+        // (no kernel behind the loop: the rows are out -- Params::emit -- and k_solve_wg has left the block's head in h_pipe; a pipeline that
+        //  runs its tiles to the end, option hybrid = 0, has no such epilogue: a copy command)
+        if (hand <= 0) HIP_TRY(h, hipMemcpyAsync(h->h_pipe, ctl + PIPE_ABORT, PIPE_FIN_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(h, wait_stream(h, stream));
+        h->h_fail[0] = h->h_pipe[14];
+        report_wg_trace(d_wtrace, n_wtrace);
+        for (int q = 0; q < 4; ++q) h->h_fail[2 + q] = h->h_pipe[16 + q];
+        if (h->resc_ran && !in_rescue) h->rescued_last = (int)h->h_pipe[20];       // (fifth word: instances that took the second chance inside the launch)
+        if (hand > 0) {        // the stragglers' kernel: rounds of its slowest workgroup, workgroups, workgroup-rounds, sweeps, instance-iterations
+            h->res_prof[1] = 1; h->res_prof[2] = h->h_fail[2]; h->res_prof[3] = pl.wg_grid;      // (workgroups launched: what the machine holds when they are dealt from the hand-over lists)
+            h->res_prof[4] = h->h_fail[3]; h->res_prof[5] = h->h_fail[4]; h->res_prof[6] = h->h_fail[5];
+        }
+        if (h->h_pipe[0] != 0u) {
+            // a bounded wait ran out (e.g. the dispatcher left an XCD without stage workers): the workspace is part-way
+            // through an iteration, so start over with one launch per kernel.  Once may be a transient of the machine's other tenants (the
+            // workgroups of a collective spinning on a slow peer, another handle's persistent launch); the handle stays on that path when it
+            // has happened PIPE_ABORTS_MAX times
+            h->pipe_disabled = true;
+            h->resc_in_kernel = h->resc_ran = false;         // (the k_solve_wg behind the abandoned launch returned at once: no instance has had its second chance)
+            // (abort word: 1 option pipe_test_abort, 2 a Riccati worker waited for its tile's stage items [tile << 16 | round; arrivals], 3 a helping
+            //  Riccati worker / 4 a stage worker waited for its queue slot [ticket; queue tail]; words 28 - 31 of the block's head)
+            fprintf(stderr, "[mpcgpu] single-launch pipeline abandoned (bounded wait expired: code %u, %u / %u, a millisecond later %u, waited %u ticks); re-running with one launch per kernel\n",
+                    h->h_pipe[0], h->h_pipe[28], h->h_pipe[29], h->h_pipe[30], h->h_pipe[31]);
+            report_arrivals(ctl, ntiles, A.items);
+            const int rc_again = solve_dev_impl<NX>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it_out, in_rescue);
+            if (++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;
+            return rc_again;
+        }
+        P.DBG = nullptr;
+        if (d_pdbg) { rc = report_pipe_timing(h, d_pdbg); if (rc) return rc; }
+        piped = true;
+        h->last_mode = 1;
+        it = (int)h->h_pipe[1];
+        const unsigned long long* st64 = reinterpret_cast<const unsigned long long*>(h->h_pipe + 2);
+        h->pipe_prof[1] = 1; h->pipe_prof[2] = it;
+        h->pipe_prof[3] = (double)st64[0] * 1e-5; h->pipe_prof[4] = (double)st64[1] * 1e-5; h->pipe_prof[5] = (double)st64[2] * 1e-5;   // 100 MHz ticks -> ms
+        h->pipe_prof[6] = (double)st64[3]; h->pipe_prof[7] = (double)h->h_pipe[12] + 1e-3 * (double)h->h_pipe[13];
     }
     if (!piped) {
         // one launch per kernel: the poll table of this solve and (unless an asynchronous closed loop accumulates over its steps) the
         // count of instances that do not converge start from zero -- the pipeline path keeps both in its control block
         if (!h->async_loop) HIP_TRY(h, hipMemsetAsync(h->d_fail, 0, sizeof(uint32_t), stream));
-        if (polled) HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int32_t) * mpc_handle::MAX_GROUPS * mpc_handle::MAX_POLL_IT, stream));
+        if (pl.polled) HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int32_t) * MAX_GROUPS * MAX_POLL_IT, stream));
         if (G > 1) {     // the sub-streams were forked before these memsets were enqueued
             HIP_TRY(h, hipEventRecord(h->ev_fork, stream));
             for (int g = 0; g < G; ++g) HIP_TRY(h, hipStreamWaitEvent(h->sub_stream[g], h->ev_fork, 0));
         }
     }
-    while (!piped && it < cap) {
-        const int n = std::min(trace ? 1 : chunk, cap - it);
+    while (!piped && it < pl.cap) {
+        const int n = std::min(trace ? 1 : pl.chunk, pl.cap - it);
         bool any = false;
         for (int j = 0; j < n; ++j) {
             for (int g = 0; g < G; ++g) {                 // interleave the groups launch by launch
@@ -3670,13 +3485,13 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
                 Params Pg = P;
                 Pg.tile0 = q.tile0;
                 prof.begin(0, q.st);
-                if (stage_timing && it + j == 3) Pg.DBG = d_dbg + (size_t)8 * nblk;   // Riccati stamps of the 4th iteration
-                hipLaunchKernelGGL((k_riccati<NX>), dim3(q.ntl), dim3(192), ric_lds, q.st, Pg);
+                if (pl.stage_timing && it + j == 3) Pg.DBG = d_dbg + (size_t)8 * nblk;   // Riccati stamps of the 4th iteration
+                hipLaunchKernelGGL((k_riccati<NX>), dim3(q.ntl), dim3(192), pl.ric_lds, q.st, Pg);
                 Pg.DBG = nullptr;
                 prof.end(q.st);
                 prof.begin(1, q.st);
-                P.DBG = (stage_timing && it + j == 2) ? d_dbg : nullptr;      // stamp the third iteration
-                P.run_counter = polled ? h->d_counter + (size_t)g * mpc_handle::MAX_POLL_IT + (it + j) : nullptr;
+                P.DBG = (pl.stage_timing && it + j == 2) ? d_dbg : nullptr;      // stamp the third iteration
+                P.run_counter = pl.polled ? h->d_counter + (size_t)g * MAX_POLL_IT + (it + j) : nullptr;
                 launch_stage(q, false);
                 P.run_counter = nullptr;
                 prof.end(q.st);
@@ -3685,7 +3500,7 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         }
         it += n;
         if (!any) break;
-        if (!polled) {
+        if (!pl.polled) {
             if (trace) {                                  // trace mode: exact stop, one synchronous count per iteration
                 HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int32_t), stream));
                 hipLaunchKernelGGL(k_count_running, dim3((B + 255) / 256), dim3(256), 0, stream, h->d_iws, (uint32_t)w.itile_elems, 0, B, h->d_counter);
@@ -3699,7 +3514,7 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         for (int g = 0; g < G; ++g) {
             const Group& q = grp[g];
             if (!q.running) continue;
-            HIP_TRY(h, hipMemcpyAsync(h->h_counter + 2 * g + slot, h->d_counter + (size_t)g * mpc_handle::MAX_POLL_IT + (it - 1), sizeof(int32_t),
+            HIP_TRY(h, hipMemcpyAsync(h->h_counter + 2 * g + slot, h->d_counter + (size_t)g * MAX_POLL_IT + (it - 1), sizeof(int32_t),
                                       hipMemcpyDeviceToHost, q.st));
             HIP_TRY(h, hipEventRecord(h->ev_poll[g][slot], q.st));
         }
@@ -3717,36 +3532,7 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
     }
     P.DBG = nullptr;
     if (trace) { rc = record_trace(it); if (rc) return rc; }
-    if (stage_timing) {
-        HIP_TRY(h, hipStreamSynchronize(stream));
-        std::vector<unsigned long long> hd((size_t)16 * nblk);
-        HIP_TRY(h, hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        double acc[10] = {0};
-        int cnt = 0;
-        for (int bq = 0; bq < nblk; ++bq) {
-            if (!hd[(size_t)bq * 16 + 10]) continue;
-            for (int q = 0; q < 10; ++q) acc[q] += (double)(hd[(size_t)bq * 16 + q + 1] - hd[(size_t)bq * 16 + q]);
-            ++cnt;
-        }
-        fprintf(stderr, "[mpcgpu stage timing, shader-clock ticks per block, mean over %d blocks]", cnt);
-        static const char* names[10] = {"issue-loads", "wait+barrier", "P1", "reduce1", "linesearch", "P3-update", "exchange", "P4-eval", "reduce3", "P5"};
-        for (int q = 0; q < 10; ++q) fprintf(stderr, " %s=%.0f", names[q], cnt ? acc[q] / cnt : 0.0);
-        fprintf(stderr, "\n");
-        {
-            double bw = 0, fw = 0;
-            int c2 = 0;
-            for (int tq = 0; tq < ntiles && (size_t)(8 * nblk + (tq + 1) * 16) <= hd.size(); ++tq) {
-                const unsigned long long* r = hd.data() + (size_t)8 * nblk + (size_t)tq * 16;
-                if (!r[2]) continue;
-                bw += (double)(r[1] - r[0]);
-                fw += (double)(r[2] - r[1]);
-                ++c2;
-                if (tq == 0) fprintf(stderr, "[riccati stage 15 of tile 0] bwd barrier-wait=%lld compute=%lld | fwd barrier-wait=%lld compute=%lld\n",
-                                     (long long)(r[4] - r[3]), (long long)(r[5] - r[4]), (long long)(r[7] - r[6]), (long long)(r[8] - r[7]));
-            }
-            fprintf(stderr, "[mpcgpu riccati timing, ticks per workgroup, mean over %d] backward=%.0f forward=%.0f\n", c2, c2 ? bw / c2 : 0.0, c2 ? fw / c2 : 0.0);
-        }
-    }
+    if (pl.stage_timing) { rc = report_stage_timing(h, stream, d_dbg, nblk, ntiles); if (rc) return rc; }
     if (n_it_out) *n_it_out = it;
     for (int g = 0; g < G; ++g) {
         const Group& q = grp[g];
@@ -3771,12 +3557,20 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
     return MPC_OK;
 }
 
+// what a solve writes besides its rows: multipliers ([B, n_g] / [B, n_w] device rows of the caller, mpc_solve_batch[_dev]_ex) and the snapshot
+// of its final iterates (mpc_solve_batch_sens[_dev], mpc_sens.h) -- null: not asked for
+struct SolveExtra {
+    double* lam_g = nullptr;
+    double* lam_x = nullptr;
+    double* snap = nullptr;
+};
 static int solve_dev_any(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
-                         int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream, double* trace, int32_t trace_rows, int32_t* n_it) {
+                         int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream, double* trace, int32_t trace_rows, int32_t* n_it,
+                         bool in_rescue) {
     h->snap_ok = false;                 // (every solve of the handle: the snapshot of mpc_solve_batch_sens is no longer the last solve's)
     if (h->hp.desc.nx == 5)
-        return solve_dev_impl<5>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it);
-    return solve_dev_impl<6>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it);
+        return solve_dev_impl<5>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it, in_rescue);
+    return solve_dev_impl<6>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it, in_rescue);
 }
 
 // ---- multipliers of a solve (mpc_solve_batch_ex): read back from the workspace behind the solve, the loop kernels are not touched -------
@@ -3785,7 +3579,7 @@ static int solve_dev_any(mpc_handle* h, int32_t B, const double* d_x0, const dou
 static int mult_prepare(mpc_handle* h, int32_t B, hipStream_t stream) {
     const mpc_problem_desc& d = h->hp.desc;
     const size_t Bp = ((size_t)B + 63) / 64 * 64;
-    const int rc = ensure_ws(h, Bp);
+    const int rc = ensure_ws(h, Bp, plan_solve(h->hp, h->knobs, plan_state(h, B, false, false, false)).mailbox);
     if (rc) return rc;
     if (h->ws_mailbox) {
         const WsLayout w = ws_layout(d.N, d.nx, Bp, true);
@@ -3832,9 +3626,9 @@ static int sens_read(mpc_handle* h, int32_t B, const double* d_x_out, const int3
 // original tolerance -- or nothing (the original failure stays).  Two passes: levels {0, 1}, then {0, 0.4, 0.7, 0.9, 1} for
 // what is still open.  Everything stays in device memory; the only host traffic is the count of open instances.
 static int rescue_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
-                      int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream) {
+                      int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream, const SolveExtra& ex) {
     const size_t nw = h->hp.n_w(), nB = (size_t)B;
-    int32_t* idx = static_cast<int32_t*>(scratch_get(h, 14, (nB + 1) * 4));
+    int32_t* idx = static_cast<int32_t*>(scratch_get(h, SCR_RESC_IDX, (nB + 1) * 4));
     if (!idx) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
     int32_t* cnt = idx + nB;
     static const double pass1[] = {0.0, 1.0}, pass2[] = {0.0, 0.4, 0.7, 0.9, 1.0};
@@ -3848,7 +3642,7 @@ static int rescue_dev(mpc_handle* h, int32_t B, const double* d_x0, const double
         HIP_TRY(h, hipStreamSynchronize(stream));
         if (n <= 0) break;
         // sub-batch buffers: [xs | ps | out] rows, obstacle rows, status / iterations / kkt of a level, accumulated iterations
-        double* buf = static_cast<double*>(scratch_get(h, 15, ((size_t)n * (3 * nw + 6 + 1)) * 8 + (size_t)n * 3 * 4 + 64));
+        double* buf = static_cast<double*>(scratch_get(h, SCR_RESC_BUF, ((size_t)n * (3 * nw + 6 + 1)) * 8 + (size_t)n * 3 * 4 + 64));
         if (!buf) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
         double *xs = buf, *ps = xs + (size_t)n * nw, *out = ps + (size_t)n * nw, *os = out + (size_t)n * nw, *kk = os + (size_t)n * 6;
         int32_t *st = reinterpret_cast<int32_t*>(kk + n), *it = st + n, *acc = it + n;
@@ -3858,28 +3652,25 @@ static int rescue_dev(mpc_handle* h, int32_t B, const double* d_x0, const double
         // (mpc_solve_batch_ex: the multipliers of the last level, the original problem, go back beside its rows)
         const size_t ng = h->hp.n_g();
         double* mlg = nullptr;
-        if (h->mo_lam_g) {
-            mlg = static_cast<double*>(scratch_get(h, 38, (size_t)n * (ng + nw) * 8));
+        if (ex.lam_g) {
+            mlg = static_cast<double*>(scratch_get(h, SCR_RESC_MULT, (size_t)n * (ng + nw) * 8));
             if (!mlg) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
         }
         for (int q = 0; q < nfr && rc == MPC_OK; ++q) {
             h->hp.ol = relax_lo(fr[q] * h->hp.ol_raw);
             h->hp.desc.tol = (q + 1 < nfr) ? std::max(tol_keep, 1e-4) : tol_keep;      // intermediate levels only produce warm starts
-            if ((mlg || h->so_snap) && q + 1 == nfr) rc = mult_prepare(h, n, stream);
+            if ((mlg || ex.snap) && q + 1 == nfr) rc = mult_prepare(h, n, stream);
             if (rc != MPC_OK) break;
-            h->in_rescue = true;
-            rc = solve_dev_any(h, n, xs, ps, d_obst ? os : nullptr, out, st, it, kk, stream, nullptr, 0, nullptr);
-            h->in_rescue = false;
+            rc = solve_dev_any(h, n, xs, ps, d_obst ? os : nullptr, out, st, it, kk, stream, nullptr, 0, nullptr, true);
             if (rc == MPC_OK && mlg && q + 1 == nfr) rc = mult_read(h, n, out, st, mlg, mlg + (size_t)n * ng, stream);
-            if (rc == MPC_OK && h->so_snap && q + 1 == nfr) rc = sens_read(h, n, out, st, d_obst ? os : nullptr, idx, h->so_snap, stream);
+            if (rc == MPC_OK && ex.snap && q + 1 == nfr) rc = sens_read(h, n, out, st, d_obst ? os : nullptr, idx, ex.snap, stream);
             if (rc == MPC_OK) hipLaunchKernelGGL(k_rescue_carry, dim3(n), dim3(128), 0, stream, (int)nw, st, it, out, xs, acc);
         }
         h->hp.ol = ol_keep;
         h->hp.desc.tol = tol_keep;
         if (rc == MPC_OK) hipLaunchKernelGGL(k_rescue_scatter, dim3(n), dim3(128), 0, stream, idx, (int)nw, st, out, kk, acc, d_x_out, d_status, d_iters, d_kkt);
         if (rc == MPC_OK && mlg)
-            hipLaunchKernelGGL(k_rescue_scatter_mult, dim3(n), dim3(128), 0, stream, idx, (int)nw, (int)ng, st, mlg, mlg + (size_t)n * ng, h->mo_lam_g,
-                               h->mo_lam_x);
+            hipLaunchKernelGGL(k_rescue_scatter_mult, dim3(n), dim3(128), 0, stream, idx, (int)nw, (int)ng, st, mlg, mlg + (size_t)n * ng, ex.lam_g, ex.lam_x);
         if (pass == 0) h->rescued_last = n;
     }
     h->hp.ol = ol_keep;
@@ -3888,86 +3679,61 @@ static int rescue_dev(mpc_handle* h, int32_t B, const double* d_x0, const double
     return rc;
 }
 
-// instances one solve can take: the workspace (tile-major section + mailbox arrays, both linear in the number of tiles) is addressed
-// with 32-bit buffer offsets
-// can a batch of this handle run in the persistent launch at all -- the conditions of solve_dev_impl that do not depend on the batch size
-static bool pipeline_shape(const mpc_handle* h) {
-    const mpc_problem_desc& d = h->hp.desc;
-    const mpc_handle::Knobs& kn = h->knobs;
-    if (4 * (d.N + 1) > 256 || kn.big_wg || !kn.pipeline || h->pipe_disabled || kn.groups > 0 || (kn.timing & TIMING_STAGE) || d.fixed_iters > 0) return false;
-    const int threads = (((d.N + 1) * pick_bx(d.N, 256) + 63) / 64) * 64;
-    return threads >= 192 && threads <= 256;
-}
-static size_t max_rows_per_solve(const mpc_handle* h) {
-    const WsLayout w1 = ws_layout(h->hp.desc.N, h->hp.desc.nx, 64, wants_mailbox(h));
-    size_t max_b = (((size_t)1 << 32) - 1) / (w1.total * sizeof(double)) * 64;
-    // (the persistent launch takes PIPE_MAX_TILES tiles -- 128 until the end of round 6, when a batch beyond them fell back to one launch per kernel
-    //  and iteration: 43 % more time per instance at B = 8193 than at 8192; now 256, four tiles per Riccati worker, and chunks of that size beyond:
-    //  B = 8193 2.33 -> 1.37 ms, 12288 3.06 -> 1.96 ms, 16384 2.63 ms; N = 10: 16384 1.0 ms = 16 M instances/s)
-    if (pipeline_shape(h)) max_b = std::min(max_b, (size_t)PIPE_MAX_TILES * 64);
-    if (h->knobs.max_batch > 0) max_b = std::min(max_b, (size_t)(h->knobs.max_batch + 63) / 64 * 64);
-    return max_b;
-}
 
 static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
                      int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream, double* trace, int32_t trace_rows,
-                     int32_t* n_it) {
+                     int32_t* n_it, const SolveExtra& ex = SolveExtra{}) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !d_x0 || !d_p || !d_x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
     if (!h->hp.bounds_set) { h->err = "mpc_set_bounds has not been called"; return MPC_ERR_STATE; }
     h->snap_ok = false;
     HIP_TRY(h, hipSetDevice(h->device));
     h->rescued_last = 0;
+    const SolvePlan pl = plan_solve(h->hp, h->knobs, plan_state(h, B, d_obst != nullptr, trace != nullptr, false));
     // the second chance needs the per-instance status: an internal row when the caller did not ask for it
-    const bool rescue = h->knobs.rescue && h->hp.desc.fixed_iters <= 0 && !trace && h->hp.has_ol && h->hp.ol_raw > 0.0;
-    if (rescue && !d_status) {
-        d_status = static_cast<int32_t*>(scratch_get(h, 11, (size_t)B * 4));
+    if (pl.rescue && !d_status) {
+        d_status = static_cast<int32_t*>(scratch_get(h, SCR_SOLVE_STATUS, (size_t)B * 4));
         if (!d_status) { h->err = "out of device memory"; return MPC_ERR_HIP; }
     }
     // The workspace is addressed with 32-bit buffer offsets (< 4 GiB): a batch beyond that is solved in chunks of whole tiles, one after
     // the other on the same stream (instances are independent; the rows of a chunk are a contiguous slice of every caller buffer).
-    {
-        const size_t max_b = max_rows_per_solve(h);
-        if ((size_t)B > max_b && !trace && !h->async_loop) {
-            const size_t nw = h->hp.n_w();
-            const size_t ng = h->hp.n_g();
-            double *mlg = h->mo_lam_g, *mlx = h->mo_lam_x, *snp = h->so_snap;
-            const size_t slen = h->hp.desc.nx == 5 ? Sens<5>::len(h->hp.desc.N) : Sens<6>::len(h->hp.desc.N);
-            int rescued = 0;
-            for (size_t off = 0; off < (size_t)B; off += max_b) {
-                const int32_t n = (int32_t)std::min(max_b, (size_t)B - off);
-                if (mlg) { h->mo_lam_g = mlg + off * ng; h->mo_lam_x = mlx + off * nw; }
-                if (snp) h->so_snap = snp + off * slen;
-                const int rcc = solve_dev(h, n, d_x0 + off * nw, d_p + off * nw, d_obst ? d_obst + off * 6 : nullptr, d_x_out + off * nw,
-                                          d_status ? d_status + off : nullptr, d_iters ? d_iters + off : nullptr, d_kkt ? d_kkt + off : nullptr, stream,
-                                          nullptr, 0, nullptr);
-                h->mo_lam_g = mlg; h->mo_lam_x = mlx; h->so_snap = snp;
-                if (rcc) return rcc;
-                rescued += h->rescued_last;
-            }
-            h->rescued_last = rescued;
-            return MPC_OK;
+    if ((size_t)B > pl.max_rows && !trace && !h->async_loop) {
+        const size_t max_b = pl.max_rows, nw = h->hp.n_w(), ng = h->hp.n_g();
+        const size_t slen = h->hp.desc.nx == 5 ? Sens<5>::len(h->hp.desc.N) : Sens<6>::len(h->hp.desc.N);
+        int rescued = 0;
+        for (size_t off = 0; off < (size_t)B; off += max_b) {
+            const int32_t n = (int32_t)std::min(max_b, (size_t)B - off);
+            SolveExtra exc = ex;
+            if (ex.lam_g) { exc.lam_g = ex.lam_g + off * ng; exc.lam_x = ex.lam_x + off * nw; }
+            if (ex.snap) exc.snap = ex.snap + off * slen;
+            const int rcc = solve_dev(h, n, d_x0 + off * nw, d_p + off * nw, d_obst ? d_obst + off * 6 : nullptr, d_x_out + off * nw,
+                                      d_status ? d_status + off : nullptr, d_iters ? d_iters + off : nullptr, d_kkt ? d_kkt + off : nullptr, stream,
+                                      nullptr, 0, nullptr, exc);
+            if (rcc) return rcc;
+            rescued += h->rescued_last;
         }
+        h->rescued_last = rescued;
+        return MPC_OK;
     }
     h->resc_in_kernel = h->resc_ran = false;
-    if (h->mo_lam_g || h->so_snap) {
+    if (ex.lam_g || ex.snap) {
         const int rm = mult_prepare(h, B, stream);
         if (rm) return rm;
     }
-    int rc = solve_dev_any(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it);
-    if (rc == MPC_OK && h->mo_lam_g) rc = mult_read(h, B, d_x_out, d_status, h->mo_lam_g, h->mo_lam_x, stream);
-    if (rc == MPC_OK && h->so_snap) rc = sens_read(h, B, d_x_out, d_status, d_obst, nullptr, h->so_snap, stream);
+    int rc = solve_dev_any(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it, false);
+    if (rc == MPC_OK && ex.lam_g) rc = mult_read(h, B, d_x_out, d_status, ex.lam_g, ex.lam_x, stream);
+    if (rc == MPC_OK && ex.snap) rc = sens_read(h, B, d_x_out, d_status, d_obst, nullptr, ex.snap, stream);
     // (converged mode: the solve has synchronised the stream; a launch of k_solve_wg with the second chance inside has given every stalled
     //  instance its levels already)
-    // (what the next solve of this handle does about stalled instances: see resc_cond)
-    if (rc == MPC_OK && rescue && !h->async_ok) h->resc_hint = h->h_fail[0] != 0u || h->rescued_last > 0;
-    if (rc != MPC_OK || !rescue || h->h_fail[0] == 0u || h->resc_in_kernel) return rc;
+    // (what the next solve of this handle does about stalled instances: see resc_cond in plan_solve)
+    if (rc == MPC_OK && pl.rescue && !h->async_ok) h->resc_hint = h->h_fail[0] != 0u || h->rescued_last > 0;
+    if (rc != MPC_OK || !pl.rescue || h->h_fail[0] == 0u || h->resc_in_kernel) return rc;
     double prof_keep[6], pipe_keep[8];
     const int mode_keep = h->last_mode;
     memcpy(prof_keep, h->prof, sizeof prof_keep);
     memcpy(pipe_keep, h->pipe_prof, sizeof pipe_keep);
     const int in_kernel = h->rescued_last;                  // (instances that had their second chance inside k_solve_wg already)
-    const int rr = rescue_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream);
+    const int rr = rescue_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, ex);
     h->rescued_last += in_kernel;
     memcpy(h->prof, prof_keep, sizeof prof_keep);          // the measurement helpers describe the main solve
     memcpy(h->pipe_prof, pipe_keep, sizeof pipe_keep);
@@ -3983,7 +3749,6 @@ static int ensure_io(mpc_handle* h, size_t B) {
     HIP_TRY(h, hipMalloc(&h->d_p, B * nw * sizeof(double)));
     HIP_TRY(h, hipMalloc(&h->d_xout, B * nw * sizeof(double)));
     HIP_TRY(h, hipMalloc(&h->d_kkt, B * sizeof(double)));
-    HIP_TRY(h, hipMalloc(&h->d_obst, B * 6 * sizeof(double)));
     HIP_TRY(h, hipMalloc(&h->d_status, B * sizeof(int32_t)));
     HIP_TRY(h, hipMalloc(&h->d_iters, B * sizeof(int32_t)));
     h->cap_io = B;
@@ -3994,23 +3759,11 @@ static int solve_host(mpc_handle* h, int32_t B, const double* x0, const double* 
                       int32_t* status, int32_t* iters, double* kkt, double* trace, int32_t trace_rows, int32_t* n_it) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !x0 || !p || !x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_io(h, (size_t)B);
-    if (rc) return rc;
-    const size_t nw = h->hp.n_w();
-    hipStream_t s = h->own_stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * nw * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_p, p, B * nw * sizeof(double), hipMemcpyHostToDevice, s));
-    if (obst) HIP_TRY(h, hipMemcpyAsync(h->d_obst, obst, (size_t)B * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-    rc = solve_dev(h, B, h->d_x0, h->d_p, obst ? h->d_obst : nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt, s, trace,
-                   trace_rows, n_it);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(x_out, h->d_xout, B * nw * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(h, hipMemcpyAsync(status, h->d_status, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (iters) HIP_TRY(h, hipMemcpyAsync(iters, h->d_iters, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (kkt) HIP_TRY(h, hipMemcpyAsync(kkt, h->d_kkt, B * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    const size_t nB = (size_t)B, nw = h->hp.n_w();
+    return stage_host(h, {{x0, nB * nw * 8, false}, {p, nB * nw * 8, false}, {obst, nB * 6 * 8, false}, {x_out, nB * nw * 8, true},
+                          {status, nB * 4, true}, {iters, nB * 4, true}, {kkt, nB * 8, true}}, [&](void** d, hipStream_t s) {
+        return solve_dev(h, B, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (int32_t*)d[4], (int32_t*)d[5], (double*)d[6], s, trace, trace_rows, n_it);
+    });
 }
 
 extern "C" {
@@ -4053,32 +3806,18 @@ int mpc_eval_nlp_batch(mpc_handle* h, int32_t B, const double* x, const double* 
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !x || !p) { h->err = "B > 0 and x, p are required"; return MPC_ERR_INVALID; }
     if (!f && !g) return MPC_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t nw = h->hp.n_w(), nB = (size_t)B;
-    const size_t ng = h->hp.n_g();
-    double* buf = static_cast<double*>(scratch_get(h, 39, nB * (2 * nw + 6 + 1 + ng) * 8));
-    if (!buf) { h->err = "eval: out of device memory"; return MPC_ERR_HIP; }
-    double *dx = buf, *dp = dx + nB * nw, *dob = dp + nB * nw, *df = dob + nB * 6, *dg = df + nB;
-    hipStream_t s = h->own_stream;
-    HIP_TRY(h, hipMemcpyAsync(dx, x, nB * nw * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dp, p, nB * nw * 8, hipMemcpyHostToDevice, s));
-    if (obst) HIP_TRY(h, hipMemcpyAsync(dob, obst, nB * 6 * 8, hipMemcpyHostToDevice, s));
-    const int rc = mpc_eval_nlp_batch_dev(h, B, dx, dp, obst ? dob : nullptr, f ? df : nullptr, g ? dg : nullptr, (void*)s);
-    if (rc) return rc;
-    if (f) HIP_TRY(h, hipMemcpyAsync(f, df, nB * 8, hipMemcpyDeviceToHost, s));
-    if (g) HIP_TRY(h, hipMemcpyAsync(g, dg, nB * ng * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    const size_t nw = h->hp.n_w(), nB = (size_t)B, ng = h->hp.n_g();
+    return stage_host(h, {{x, nB * nw * 8, false}, {p, nB * nw * 8, false}, {obst, nB * 6 * 8, false}, {f, nB * 8, true}, {g, nB * ng * 8, true}},
+                      [&](void** d, hipStream_t s) { return mpc_eval_nlp_batch_dev(h, B, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], s); });
 }
 
 // mpc_solve_batch_dev plus the NLP's objective / rows at the returned x and the multipliers of the final iterate (all four optional; none
 // asked for: exactly mpc_solve_batch_dev)
-int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
-                           int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
-                           void* stream_) {
-    hipStream_t s = (hipStream_t)stream_;
+static int solve_ex_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
+                        int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
+                        double* d_snap, hipStream_t s) {
     const bool mult = d_lam_g || d_lam_x;
-    if (!mult && !d_f && !d_g) return solve_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, s, nullptr, 0, nullptr);
+    if (!mult && !d_f && !d_g) return solve_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, s, nullptr, 0, nullptr, SolveExtra{nullptr, nullptr, d_snap});
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !d_x0 || !d_p || !d_x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
     if (mult && h->hp.desc.fixed_iters > 0) { h->err = "multipliers need a solve to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
@@ -4086,52 +3825,36 @@ int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const d
     if (mult) {
         const size_t nw = h->hp.n_w(), nB = (size_t)B;
         const size_t ng = h->hp.n_g();
-        if (!d_status) d_status = static_cast<int32_t*>(scratch_get(h, 40, nB * 4));
-        if (!d_lam_g) d_lam_g = static_cast<double*>(scratch_get(h, 41, nB * ng * 8));
-        if (!d_lam_x) d_lam_x = static_cast<double*>(scratch_get(h, 41, nB * nw * 8));
+        if (!d_status) d_status = static_cast<int32_t*>(scratch_get(h, SCR_EX_STATUS, nB * 4));
+        if (!d_lam_g) d_lam_g = static_cast<double*>(scratch_get(h, SCR_EX_LAM, nB * ng * 8));
+        if (!d_lam_x) d_lam_x = static_cast<double*>(scratch_get(h, SCR_EX_LAM, nB * nw * 8));       // (one of the two at most)
         if (!d_status || !d_lam_g || !d_lam_x) { h->err = "out of device memory"; return MPC_ERR_HIP; }
     }
-    h->mo_lam_g = mult ? d_lam_g : nullptr;
-    h->mo_lam_x = mult ? d_lam_x : nullptr;
-    int rc = solve_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, s, nullptr, 0, nullptr);
-    h->mo_lam_g = h->mo_lam_x = nullptr;
+    int rc = solve_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, s, nullptr, 0, nullptr,
+                       SolveExtra{mult ? d_lam_g : nullptr, mult ? d_lam_x : nullptr, d_snap});
     if (rc == MPC_OK && (d_f || d_g)) rc = mpc_eval_nlp_batch_dev(h, B, d_x_out, d_p, d_obst, d_f, d_g, (void*)s);
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));
     return MPC_OK;
 }
 
+int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
+                           int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
+                           void* stream_) {
+    return solve_ex_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_f, d_g, d_lam_g, d_lam_x, nullptr, (hipStream_t)stream_);
+}
+
 int mpc_solve_batch_ex(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out, int32_t* status,
                        int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x) {
-    if (!f && !g && !lam_g && !lam_x) return solve_host(h, B, x0, p, obst, x_out, status, iters, kkt, nullptr, 0, nullptr);
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !x0 || !p || !x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_io(h, (size_t)B);
-    if (rc) return rc;
-    const size_t nw = h->hp.n_w(), nB = (size_t)B;
-    const size_t ng = h->hp.n_g();
-    double* buf = static_cast<double*>(scratch_get(h, 37, nB * (1 + 2 * ng + nw) * 8));
-    if (!buf) { h->err = "out of device memory"; return MPC_ERR_HIP; }
-    double *df = buf, *dg = df + nB, *dlg = dg + nB * ng, *dlx = dlg + nB * ng;
-    hipStream_t s = h->own_stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, nB * nw * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_p, p, nB * nw * sizeof(double), hipMemcpyHostToDevice, s));
-    if (obst) HIP_TRY(h, hipMemcpyAsync(h->d_obst, obst, nB * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-    const bool mult = lam_g || lam_x;
-    rc = mpc_solve_batch_dev_ex(h, B, h->d_x0, h->d_p, obst ? h->d_obst : nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt, f ? df : nullptr,
-                                g ? dg : nullptr, mult ? dlg : nullptr, mult ? dlx : nullptr, (void*)s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(x_out, h->d_xout, nB * nw * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(h, hipMemcpyAsync(status, h->d_status, nB * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (iters) HIP_TRY(h, hipMemcpyAsync(iters, h->d_iters, nB * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (kkt) HIP_TRY(h, hipMemcpyAsync(kkt, h->d_kkt, nB * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (f) HIP_TRY(h, hipMemcpyAsync(f, df, nB * 8, hipMemcpyDeviceToHost, s));
-    if (g) HIP_TRY(h, hipMemcpyAsync(g, dg, nB * ng * 8, hipMemcpyDeviceToHost, s));
-    if (lam_g) HIP_TRY(h, hipMemcpyAsync(lam_g, dlg, nB * ng * 8, hipMemcpyDeviceToHost, s));
-    if (lam_x) HIP_TRY(h, hipMemcpyAsync(lam_x, dlx, nB * nw * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    const size_t nw = h->hp.n_w(), nB = (size_t)B, ng = h->hp.n_g();
+    return stage_host(h, {{x0, nB * nw * 8, false}, {p, nB * nw * 8, false}, {obst, nB * 6 * 8, false}, {x_out, nB * nw * 8, true}, {status, nB * 4, true},
+                          {iters, nB * 4, true}, {kkt, nB * 8, true}, {f, nB * 8, true}, {g, nB * ng * 8, true}, {lam_g, nB * ng * 8, true},
+                          {lam_x, nB * nw * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_solve_batch_dev_ex(h, B, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (int32_t*)d[4], (int32_t*)d[5], (double*)d[6],
+                                      (double*)d[7], (double*)d[8], (double*)d[9], (double*)d[10], s);
+    });
 }
 
 // ---- parametric sensitivities -----------------------------------------------------------------------------------
@@ -4140,12 +3863,12 @@ static int sens_fs(const mpc_handle* h) { return h->hp.desc.nx == 5 ? Sens<5>::F
 // factor the snapshot's KKT matrices and solve: n_dir forward directions and / or one adjoint seed (k_sens_factor_solve)
 static int sens_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dp, double* d_dw, const double* d_seed, double* d_grad, hipStream_t s) {
     const mpc_problem_desc& d = h->hp.desc;
-    double* F = static_cast<double*>(scratch_get(h, 45, (size_t)B * (size_t)(d.N + 1) * (size_t)sens_fs(h) * 8));
+    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(d.N + 1) * (size_t)sens_fs(h) * 8));
     if (!F) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
     Params P;
     fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, nullptr, nullptr, h->d_LB, h->d_UB, false);
     const dim3 grid((B + SENS_THREADS - 1) / SENS_THREADS);
-    double* snap = static_cast<double*>(h->scratch[44]);
+    double* snap = static_cast<double*>(h->scratch[SCR_SENS_SNAP]);
     if (d.nx == 5) hipLaunchKernelGGL((k_sens_factor_solve<5>), grid, dim3(SENS_THREADS), 0, s, P, snap, F, n_dir, d_dp, d_dw, d_seed, d_grad);
     else hipLaunchKernelGGL((k_sens_factor_solve<6>), grid, dim3(SENS_THREADS), 0, s, P, snap, F, n_dir, d_dp, d_dw, d_seed, d_grad);
     HIP_TRY(h, hipGetLastError());
@@ -4164,13 +3887,11 @@ int mpc_solve_batch_sens_dev(mpc_handle* h, int32_t B, const double* d_x0, const
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream_;
     const size_t nB = (size_t)B, ng = h->hp.n_g();
-    double* snap = static_cast<double*>(scratch_get(h, 44, nB * sens_len(h) * 8));
-    if (!d_status) d_status = static_cast<int32_t*>(scratch_get(h, 46, nB * 4));
-    if (d_lam_p && !d_lam_g) d_lam_g = static_cast<double*>(scratch_get(h, 47, nB * ng * 8));
+    double* snap = static_cast<double*>(scratch_get(h, SCR_SENS_SNAP, nB * sens_len(h) * 8));
+    if (!d_status) d_status = static_cast<int32_t*>(scratch_get(h, SCR_SENS_STATUS, nB * 4));
+    if (d_lam_p && !d_lam_g) d_lam_g = static_cast<double*>(scratch_get(h, SCR_SENS_LAM_G, nB * ng * 8));
     if (!snap || !d_status || (d_lam_p && !d_lam_g)) { h->err = "out of device memory"; return MPC_ERR_HIP; }
-    h->so_snap = snap;
-    int rc = mpc_solve_batch_dev_ex(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_f, d_g, d_lam_g, d_lam_x, stream_);
-    h->so_snap = nullptr;
+    int rc = solve_ex_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_f, d_g, d_lam_g, d_lam_x, snap, s);
     if (rc) return rc;
     h->snap_ok = true;
     h->snap_B = B;
@@ -4197,35 +3918,14 @@ int mpc_solve_batch_sens(mpc_handle* h, int32_t B, const double* x0, const doubl
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !x0 || !p || !x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
     if (n_dir < 0 || (n_dir > 0 && (!dp || !dw))) { h->err = "n_dir >= 0, and dp, dw are required when n_dir > 0"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_io(h, (size_t)B);
-    if (rc) return rc;
     const size_t nw = h->hp.n_w(), nB = (size_t)B, ng = h->hp.n_g(), nd = (size_t)n_dir;
-    // [f | g | lam_g | lam_x | lam_p | dp | dw]
-    double* buf = static_cast<double*>(scratch_get(h, 48, nB * (1 + 2 * ng + 2 * nw + 2 * nd * nw) * 8));
-    if (!buf) { h->err = "out of device memory"; return MPC_ERR_HIP; }
-    double *df = buf, *dg = df + nB, *dlg = dg + nB * ng, *dlx = dlg + nB * ng, *dlp = dlx + nB * nw, *ddp = dlp + nB * nw, *ddw = ddp + nB * nd * nw;
-    hipStream_t s = h->own_stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, nB * nw * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_p, p, nB * nw * sizeof(double), hipMemcpyHostToDevice, s));
-    if (obst) HIP_TRY(h, hipMemcpyAsync(h->d_obst, obst, nB * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (nd) HIP_TRY(h, hipMemcpyAsync(ddp, dp, nB * nd * nw * sizeof(double), hipMemcpyHostToDevice, s));
-    rc = mpc_solve_batch_sens_dev(h, B, h->d_x0, h->d_p, obst ? h->d_obst : nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt, f ? df : nullptr,
-                                  g ? dg : nullptr, lam_g ? dlg : nullptr, lam_x ? dlx : nullptr, lam_p ? dlp : nullptr, n_dir, nd ? ddp : nullptr,
-                                  nd ? ddw : nullptr, (void*)s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(x_out, h->d_xout, nB * nw * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(h, hipMemcpyAsync(status, h->d_status, nB * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (iters) HIP_TRY(h, hipMemcpyAsync(iters, h->d_iters, nB * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (kkt) HIP_TRY(h, hipMemcpyAsync(kkt, h->d_kkt, nB * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (f) HIP_TRY(h, hipMemcpyAsync(f, df, nB * 8, hipMemcpyDeviceToHost, s));
-    if (g) HIP_TRY(h, hipMemcpyAsync(g, dg, nB * ng * 8, hipMemcpyDeviceToHost, s));
-    if (lam_g) HIP_TRY(h, hipMemcpyAsync(lam_g, dlg, nB * ng * 8, hipMemcpyDeviceToHost, s));
-    if (lam_x) HIP_TRY(h, hipMemcpyAsync(lam_x, dlx, nB * nw * 8, hipMemcpyDeviceToHost, s));
-    if (lam_p) HIP_TRY(h, hipMemcpyAsync(lam_p, dlp, nB * nw * 8, hipMemcpyDeviceToHost, s));
-    if (nd) HIP_TRY(h, hipMemcpyAsync(dw, ddw, nB * nd * nw * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    return stage_host(h, {{x0, nB * nw * 8, false}, {p, nB * nw * 8, false}, {obst, nB * 6 * 8, false}, {nd ? dp : nullptr, nB * nd * nw * 8, false},
+                          {x_out, nB * nw * 8, true}, {status, nB * 4, true}, {iters, nB * 4, true}, {kkt, nB * 8, true}, {f, nB * 8, true},
+                          {g, nB * ng * 8, true}, {lam_g, nB * ng * 8, true}, {lam_x, nB * nw * 8, true}, {lam_p, nB * nw * 8, true},
+                          {nd ? dw : nullptr, nB * nd * nw * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_solve_batch_sens_dev(h, B, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[4], (int32_t*)d[5], (int32_t*)d[6], (double*)d[7],
+                                        (double*)d[8], (double*)d[9], (double*)d[10], (double*)d[11], (double*)d[12], n_dir, (double*)d[3], (double*)d[13], s);
+    });
 }
 
 // reverse mode on the snapshot of the handle's last solve, if that was mpc_solve_batch_sens[_dev] with the same B (enqueued on `stream`)
@@ -4243,21 +3943,9 @@ int mpc_sens_adjoint_dev(mpc_handle* h, int32_t B, const double* d_seed_w, doubl
 int mpc_sens_adjoint(mpc_handle* h, int32_t B, const double* seed_w, double* grad_p) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !seed_w || !grad_p) { h->err = "B > 0 and seed_w, grad_p are required"; return MPC_ERR_INVALID; }
-    if (!h->snap_ok || B != h->snap_B) {
-        h->err = "mpc_sens_adjoint: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B";
-        return MPC_ERR_STATE;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
     const size_t nw = h->hp.n_w(), nB = (size_t)B;
-    double* buf = static_cast<double*>(scratch_get(h, 49, nB * 2 * nw * 8));
-    if (!buf) { h->err = "out of device memory"; return MPC_ERR_HIP; }
-    hipStream_t s = h->own_stream;
-    HIP_TRY(h, hipMemcpyAsync(buf, seed_w, nB * nw * 8, hipMemcpyHostToDevice, s));
-    const int rc = sens_launch(h, B, 0, nullptr, nullptr, buf, buf + nB * nw, s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(grad_p, buf + nB * nw, nB * nw * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    return stage_host(h, {{seed_w, nB * nw * 8, false}, {grad_p, nB * nw * 8, true}},
+                      [&](void** d, hipStream_t s) { return mpc_sens_adjoint_dev(h, B, (double*)d[0], (double*)d[1], s); });
 }
 
 int mpc_plant_step_dev(mpc_handle* h, int32_t B, int32_t integrator, const double* d_x, const double* d_u, double* d_x_next, void* stream_) {
@@ -4277,20 +3965,9 @@ int mpc_plant_step_dev(mpc_handle* h, int32_t B, int32_t integrator, const doubl
 int mpc_plant_step(mpc_handle* h, int32_t B, int32_t integrator, const double* x, const double* u, double* x_next) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !x || !u || !x_next || integrator < 0 || integrator > 1) { h->err = "bad plant-step arguments"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
     const size_t nx = (size_t)h->hp.desc.nx, nB = (size_t)B;
-    double* dx = static_cast<double*>(scratch_get(h, 0, nB * nx * 8));       // buffers stay with the handle: optimize() calls this every step
-    double* du = static_cast<double*>(scratch_get(h, 1, nB * 2 * 8));
-    double* dn = static_cast<double*>(scratch_get(h, 2, nB * nx * 8));
-    if (!dx || !du || !dn) { h->err = "plant step: out of device memory"; return MPC_ERR_HIP; }
-    hipStream_t s = h->own_stream;
-    HIP_TRY(h, hipMemcpyAsync(dx, x, nB * nx * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(du, u, nB * 2 * 8, hipMemcpyHostToDevice, s));
-    const int rc = mpc_plant_step_dev(h, B, integrator, dx, du, dn, (void*)s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(x_next, dn, nB * nx * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    return stage_host(h, {{x, nB * nx * 8, false}, {u, nB * 2 * 8, false}, {x_next, nB * nx * 8, true}},
+                      [&](void** d, hipStream_t s) { return mpc_plant_step_dev(h, B, integrator, (double*)d[0], (double*)d[1], (double*)d[2], s); });
 }
 
 int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
@@ -4328,15 +4005,14 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
     // that needs the second chance -- is recorded on the device and looked at ONCE, at the end; then the loop is replayed
     // step by step with the host in between (the per-kernel path polls for convergence, the second chance needs the count).
     bool replay = true, loop_abandoned = false;
-    // (a batch beyond the workspace limit is solved in chunks, which the step-by-step form below does)
-    if (d.fixed_iters <= 0 && h->knobs.pipeline && !h->pipe_disabled && h->knobs.loop_async && (size_t)B <= max_rows_per_solve(h)) {
+    if (plan_solve(h->hp, h->knobs, plan_state(h, B, false, false, false)).loop_async) {
         HIP_TRY(h, hipMemsetAsync(h->d_fail, 0, 2 * sizeof(uint32_t), stream));
         A.abort_flag = h->d_fail + 1;
         hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
         h->async_loop = true;
         bool all_async = true;
         for (int i = 0; i < L && all_async; ++i) {
-            rc = solve_dev_any(h, B, h->d_x0, h->d_p, nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt, stream, nullptr, 0, nullptr);
+            rc = solve_dev_any(h, B, h->d_x0, h->d_p, nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt, stream, nullptr, 0, nullptr, false);
             if (rc) { h->async_loop = false; return rc; }
             all_async = h->async_ok;             // (a batch shape the pipeline does not take: the solve has run synchronously -- start over)
             if (all_async) hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
@@ -4379,36 +4055,12 @@ int mpc_closed_loop_batch_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, co
                              double* ctrl, int32_t* step_status) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    // staging buffers of the host-buffer form: owned by the handle, grow-only (no allocation per call once they have their size)
     const size_t nB = (size_t)B;
-    double* di = static_cast<double*>(scratch_get(h, 29, nB * 5 * 8));
-    double* dp = static_cast<double*>(scratch_get(h, 30, nB * Lp * 2 * 8));
-    double* dor = static_cast<double*>(scratch_get(h, 31, nB * Lp * 8));
-    double* dv = static_cast<double*>(scratch_get(h, 32, nB * 8));
-    double* dt_ = static_cast<double*>(scratch_get(h, 33, nB * L * 5 * 8));
-    double* dc = static_cast<double*>(scratch_get(h, 34, nB * L * 2 * 8));
-    int32_t* ds = static_cast<int32_t*>(scratch_get(h, 35, nB * L * 4));
-    if (!di || !dp || !dor || !dv || !dt_ || !dc || !ds) {
-        h->err = "closed loop: out of device memory";
-        return MPC_ERR_HIP;
-    }
-    hipStream_t s = h->own_stream;
-    int rc = MPC_OK;
-    if (hipMemcpyAsync(di, init_state, nB * 5 * 8, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(dp, path, nB * Lp * 2 * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(dor, orient, nB * Lp * 8, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(dv, vdes, nB * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
-        h->err = "closed loop: host to device copy failed";
-        rc = MPC_ERR_HIP;
-    }
-    if (!rc) rc = mpc_closed_loop_batch_dev_ex(h, B, L, Lp, di, dp, dor, dv, noise_mode, sigma, seed, dt_, dc, ds, (void*)s);
-    if (!rc) {
-        if (hipMemcpyAsync(traj, dt_, nB * L * 5 * 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(ctrl, dc, nB * L * 2 * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            (step_status && hipMemcpyAsync(step_status, ds, nB * L * 4, hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess) {
-            h->err = "closed loop: device to host copy failed";
-            rc = MPC_ERR_HIP;
-        }
-    }
-    return rc;
+    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
+                          {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true}, {step_status, nB * L * 4, true}}, [&](void** d, hipStream_t s) {
+        return mpc_closed_loop_batch_dev_ex(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], noise_mode, sigma, seed, (double*)d[4],
+                                            (double*)d[5], (int32_t*)d[6], s);
+    });
 }
 
 int mpc_closed_loop_batch(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
@@ -4424,7 +4076,7 @@ int mpc_metrics_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lo, const
     if (d_rmsd && !d_ref_path) { h->err = "metrics: rmsd needs ref_path"; return MPC_ERR_INVALID; }
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream_;
-    double* dob = static_cast<double*>(scratch_get(h, 3, 6 * 8));
+    double* dob = static_cast<double*>(scratch_get(h, SCR_METRICS_OBST, 6 * 8));
     if (!dob) { h->err = "metrics: out of device memory"; return MPC_ERR_HIP; }
     HIP_TRY(h, hipMemcpyAsync(dob, h->hp.desc.obstacle, 6 * 8, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_metrics, dim3(B), dim3(256), 0, s, L, Lo, d_traj, d_ref_path, d_origin_path, dob, h->hp.desc.ego_offset, r_sum, (int)all_pairs,
@@ -4438,26 +4090,11 @@ int mpc_metrics_batch(mpc_handle* h, int32_t B, int32_t L, int32_t Lo, const dou
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || L < 2 || !traj || (deviation && (!origin_path || Lo <= 0))) { h->err = "metrics: B > 0, L >= 2, traj (and origin_path with deviation) are required"; return MPC_ERR_INVALID; }
     if (rmsd && !ref_path) { h->err = "metrics: rmsd needs ref_path"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
     const size_t nB = (size_t)B;
-    hipStream_t s = h->own_stream;
-    double* dt_ = static_cast<double*>(scratch_get(h, 4, nB * L * 5 * 8));
-    double* dr = rmsd ? static_cast<double*>(scratch_get(h, 5, nB * L * 2 * 8)) : nullptr;
-    double* drm = rmsd ? static_cast<double*>(scratch_get(h, 6, nB * 2 * 8)) : nullptr;
-    double* dorig = deviation ? static_cast<double*>(scratch_get(h, 7, nB * Lo * 2 * 8)) : nullptr;
-    double* ddev = deviation ? static_cast<double*>(scratch_get(h, 8, nB * L * 8)) : nullptr;
-    double* dcl = clearance ? static_cast<double*>(scratch_get(h, 9, nB * 8)) : nullptr;
-    if (!dt_ || (rmsd && (!dr || !drm)) || (deviation && (!dorig || !ddev)) || (clearance && !dcl)) { h->err = "metrics: out of device memory"; return MPC_ERR_HIP; }
-    HIP_TRY(h, hipMemcpyAsync(dt_, traj, nB * L * 5 * 8, hipMemcpyHostToDevice, s));
-    if (rmsd) HIP_TRY(h, hipMemcpyAsync(dr, ref_path, nB * L * 2 * 8, hipMemcpyHostToDevice, s));
-    if (deviation) HIP_TRY(h, hipMemcpyAsync(dorig, origin_path, nB * Lo * 2 * 8, hipMemcpyHostToDevice, s));
-    const int rc = mpc_metrics_batch_dev(h, B, L, Lo, dt_, dr, dorig, r_sum, all_pairs, ddev, drm, dcl, (void*)s);
-    if (rc) return rc;
-    if (deviation) HIP_TRY(h, hipMemcpyAsync(deviation, ddev, nB * L * 8, hipMemcpyDeviceToHost, s));
-    if (rmsd) HIP_TRY(h, hipMemcpyAsync(rmsd, drm, nB * 2 * 8, hipMemcpyDeviceToHost, s));
-    if (clearance) HIP_TRY(h, hipMemcpyAsync(clearance, dcl, nB * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    return stage_host(h, {{traj, nB * L * 5 * 8, false}, {rmsd ? ref_path : nullptr, nB * L * 2 * 8, false}, {deviation ? origin_path : nullptr, nB * Lo * 2 * 8, false},
+                          {deviation, nB * L * 8, true}, {rmsd, nB * 2 * 8, true}, {clearance, nB * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_metrics_batch_dev(h, B, L, Lo, (double*)d[0], (double*)d[1], (double*)d[2], r_sum, all_pairs, (double*)d[3], (double*)d[4], (double*)d[5], s);
+    });
 }
 
 int mpc_validity_batch_dev(mpc_handle* h, int32_t B, int32_t L, const double* d_traj, double ego_length, double ego_width, int32_t n_obst,
@@ -4481,58 +4118,33 @@ int mpc_validity_batch(mpc_handle* h, int32_t B, int32_t L, const double* traj, 
                        int32_t* first_collision, int32_t* first_off_road) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || L <= 0 || !traj || !first_collision || !first_off_road) { h->err = "validity: B, L > 0, traj and both outputs are required"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = h->own_stream;
     const size_t nB = (size_t)B;
-    double* dt_ = static_cast<double*>(scratch_get(h, 4, nB * L * 5 * 8));
-    double* dob = n_obst > 0 ? static_cast<double*>(scratch_get(h, 5, (size_t)n_obst * L * 5 * 8)) : nullptr;
-    double* dl = n_left > 0 ? static_cast<double*>(scratch_get(h, 6, (size_t)n_left * 2 * 8)) : nullptr;
-    double* dr = n_right > 0 ? static_cast<double*>(scratch_get(h, 7, (size_t)n_right * 2 * 8)) : nullptr;
-    int32_t* dc = static_cast<int32_t*>(scratch_get(h, 11, nB * 4));
-    int32_t* dor = static_cast<int32_t*>(scratch_get(h, 12, nB * 4));
-    if (!dt_ || (n_obst > 0 && !dob) || (n_left > 0 && !dl) || (n_right > 0 && !dr) || !dc || !dor) { h->err = "validity: out of device memory"; return MPC_ERR_HIP; }
-    HIP_TRY(h, hipMemcpyAsync(dt_, traj, nB * L * 5 * 8, hipMemcpyHostToDevice, s));
-    if (n_obst > 0) HIP_TRY(h, hipMemcpyAsync(dob, obst, (size_t)n_obst * L * 5 * 8, hipMemcpyHostToDevice, s));
-    if (n_left > 0) HIP_TRY(h, hipMemcpyAsync(dl, left, (size_t)n_left * 2 * 8, hipMemcpyHostToDevice, s));
-    if (n_right > 0) HIP_TRY(h, hipMemcpyAsync(dr, right, (size_t)n_right * 2 * 8, hipMemcpyHostToDevice, s));
-    const int rc = mpc_validity_batch_dev(h, B, L, dt_, ego_length, ego_width, n_obst, dob, n_left, dl, n_right, dr, dc, dor, (void*)s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(first_collision, dc, nB * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(first_off_road, dor, nB * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    return stage_host(h, {{traj, nB * L * 5 * 8, false}, {n_obst > 0 ? obst : nullptr, (size_t)std::max(n_obst, 0) * L * 5 * 8, false},
+                          {n_left > 0 ? left : nullptr, (size_t)std::max(n_left, 0) * 2 * 8, false}, {n_right > 0 ? right : nullptr, (size_t)std::max(n_right, 0) * 2 * 8, false},
+                          {first_collision, nB * 4, true}, {first_off_road, nB * 4, true}}, [&](void** d, hipStream_t s) {
+        return mpc_validity_batch_dev(h, B, L, (double*)d[0], ego_length, ego_width, n_obst, (double*)d[1], n_left, (double*)d[2], n_right, (double*)d[3],
+                                      (int32_t*)d[4], (int32_t*)d[5], s);
+    });
 }
 
 int mpc_forces_stage_eval(mpc_handle* h, int32_t B, int32_t terminal, const double* z, const double* p, double* f, double* grad_f,
                           double* c, double* jac_c, double* hval, double* jac_h) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !z || !p) { h->err = "forces stage eval: B > 0, z and p are required"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
     const mpc_problem_desc& d = h->hp.desc;
     const size_t nB = (size_t)B;
-    const size_t sz[8] = {nB * 7, nB * 10, nB, nB * 7, nB * 5, nB * 35, nB * 10, nB * 70};
-    double* host[8] = {const_cast<double*>(z), const_cast<double*>(p), f, grad_f, terminal ? nullptr : c, terminal ? nullptr : jac_c, hval, jac_h};
-    double* dev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipStream_t s = h->own_stream;
-    bool ok = true;
-    for (int i = 0; i < 8 && ok; ++i)
-        if (host[i]) ok = hipMalloc(&dev[i], sz[i] * sizeof(double)) == hipSuccess;
-    for (int i = 0; i < 2 && ok; ++i) ok = hipMemcpyAsync(dev[i], host[i], sz[i] * sizeof(double), hipMemcpyHostToDevice, s) == hipSuccess;
-    if (ok) {
+    return stage_host(h, {{z, nB * 7 * 8, false}, {p, nB * 10 * 8, false}, {f, nB * 8, true}, {grad_f, nB * 7 * 8, true}, {terminal ? nullptr : c, nB * 5 * 8, true},
+                          {terminal ? nullptr : jac_c, nB * 35 * 8, true}, {hval, nB * 10 * 8, true}, {jac_h, nB * 70 * 8, true}}, [&](void** dv, hipStream_t s) {
         ForcesArgs A{};
         A.B = B; A.terminal = terminal ? 1 : 0;
         A.dt = d.dt; A.l = d.wheelbase; A.wb = d.friction_div; A.rho = d.ego_offset;
         for (int i = 0; i < 5; ++i) { A.Q[i] = d.Q[i]; A.Pt[i] = d.P[i]; }
         A.R[0] = d.R[0]; A.R[1] = d.R[1];
-        A.z = dev[0]; A.p = dev[1]; A.f = dev[2]; A.grad_f = dev[3]; A.c = dev[4]; A.jac_c = dev[5]; A.h = dev[6]; A.jac_h = dev[7];
+        A.z = (double*)dv[0]; A.p = (double*)dv[1]; A.f = (double*)dv[2]; A.grad_f = (double*)dv[3]; A.c = (double*)dv[4]; A.jac_c = (double*)dv[5];
+        A.h = (double*)dv[6]; A.jac_h = (double*)dv[7];
         hipLaunchKernelGGL(k_forces_stage, dim3((B + 127) / 128), dim3(128), 0, s, A);
-        for (int i = 2; i < 8 && ok; ++i)
-            if (host[i]) ok = hipMemcpyAsync(host[i], dev[i], sz[i] * sizeof(double), hipMemcpyDeviceToHost, s) == hipSuccess;
-        ok = ok && hipStreamSynchronize(s) == hipSuccess;
-    }
-    for (int i = 0; i < 8; ++i) (void)hipFree(dev[i]);
-    if (!ok) { h->err = "forces stage eval: HIP allocation, copy or launch failed"; return MPC_ERR_HIP; }
-    return MPC_OK;
+        return MPC_OK;
+    });
 }
 
 int mpc_forces_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_xinit, const double* d_all_parameters,
@@ -4550,10 +4162,10 @@ int mpc_forces_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, con
     const size_t nB = (size_t)B, Bp = (nB + 63) / 64 * 64;
     hipStream_t s = (hipStream_t)stream_;
     if ((size_t)FQ_ROWS * N * Bp * 8 >= ((size_t)1 << 32)) { h->err = "forces solve: batch too large for one call (workspace of 4 GiB)"; return MPC_ERR_INVALID; }
-    double* dws = static_cast<double*>(scratch_get(h, 10, (size_t)FQ_ROWS * N * Bp * 8));
-    int32_t* dflag = d_exitflag ? d_exitflag : static_cast<int32_t*>(scratch_get(h, 11, nB * 4));
-    int32_t* dit = d_it ? d_it : static_cast<int32_t*>(scratch_get(h, 12, nB * 4));
-    double* dres = d_res ? d_res : static_cast<double*>(scratch_get(h, 13, nB * 8));
+    double* dws = static_cast<double*>(scratch_get(h, SCR_FQ_WS, (size_t)FQ_ROWS * N * Bp * 8));
+    int32_t* dflag = d_exitflag ? d_exitflag : static_cast<int32_t*>(scratch_get(h, SCR_FQ_FLAG, nB * 4));
+    int32_t* dit = d_it ? d_it : static_cast<int32_t*>(scratch_get(h, SCR_FQ_IT, nB * 4));
+    double* dres = d_res ? d_res : static_cast<double*>(scratch_get(h, SCR_FQ_RES, nB * 8));
     if (!dws || !dflag || !dit || !dres) { h->err = "forces solve: out of device memory"; return MPC_ERR_HIP; }
     ForcesQpArgs A{};
     A.B = B; A.Bp = (int32_t)Bp; A.N = N; A.max_it = 60;
@@ -4586,28 +4198,12 @@ int mpc_forces_solve_batch(mpc_handle* h, int32_t B, const double* x0, const dou
                            double* x_out, int32_t* exitflag, int32_t* it, double* res) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !x0 || !xinit || !all_parameters || !lb || !ub || !hl || !hu || !x_out) { h->err = "forces solve: null or empty argument"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
     const size_t N = (size_t)h->hp.desc.N, nB = (size_t)B;
-    hipStream_t s = h->own_stream;
-    double* dz = static_cast<double*>(scratch_get(h, 4, nB * N * 7 * 8));
-    double* dxi = static_cast<double*>(scratch_get(h, 5, nB * 5 * 8));
-    double* dpar = static_cast<double*>(scratch_get(h, 6, nB * N * 10 * 8));
-    double* dout = static_cast<double*>(scratch_get(h, 7, nB * N * 7 * 8));
-    double* dres = static_cast<double*>(scratch_get(h, 13, nB * 8));
-    int32_t* dflag = static_cast<int32_t*>(scratch_get(h, 11, nB * 4));
-    int32_t* dit = static_cast<int32_t*>(scratch_get(h, 12, nB * 4));
-    if (!dz || !dxi || !dpar || !dout || !dres || !dflag || !dit) { h->err = "forces solve: out of device memory"; return MPC_ERR_HIP; }
-    HIP_TRY(h, hipMemcpyAsync(dz, x0, nB * N * 7 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dxi, xinit, nB * 5 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dpar, all_parameters, nB * N * 10 * 8, hipMemcpyHostToDevice, s));
-    const int rc = mpc_forces_solve_batch_dev(h, B, dz, dxi, dpar, lb, ub, hl, hu, hessian_mode, dout, dflag, dit, dres, (void*)s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(x_out, dout, nB * N * 7 * 8, hipMemcpyDeviceToHost, s));
-    if (exitflag) HIP_TRY(h, hipMemcpyAsync(exitflag, dflag, nB * 4, hipMemcpyDeviceToHost, s));
-    if (it) HIP_TRY(h, hipMemcpyAsync(it, dit, nB * 4, hipMemcpyDeviceToHost, s));
-    if (res) HIP_TRY(h, hipMemcpyAsync(res, dres, nB * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    return stage_host(h, {{x0, nB * N * 7 * 8, false}, {xinit, nB * 5 * 8, false}, {all_parameters, nB * N * 10 * 8, false}, {x_out, nB * N * 7 * 8, true},
+                          {exitflag, nB * 4, true}, {it, nB * 4, true}, {res, nB * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_forces_solve_batch_dev(h, B, (double*)d[0], (double*)d[1], (double*)d[2], lb, ub, hl, hu, hessian_mode, (double*)d[3], (int32_t*)d[4],
+                                          (int32_t*)d[5], (double*)d[6], s);
+    });
 }
 
 int mpc_forces_closed_loop_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_init_acc,
@@ -4624,11 +4220,11 @@ int mpc_forces_closed_loop_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_
     if (d.nx != 5) { h->err = "the FORCES formulation has 5 states"; return MPC_ERR_INVALID; }
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t nB = (size_t)B, N = (size_t)d.N;
-    double* st = static_cast<double*>(scratch_get(h, 16, nB * 5 * 8));
-    double* zb = static_cast<double*>(scratch_get(h, 17, nB * N * 7 * 8));
-    double* par = static_cast<double*>(scratch_get(h, 18, nB * N * 10 * 8));
-    double* zo = static_cast<double*>(scratch_get(h, 19, nB * N * 7 * 8));
-    int32_t* fl = static_cast<int32_t*>(scratch_get(h, 20, nB * 4));
+    double* st = static_cast<double*>(scratch_get(h, SCR_FL_STATE, nB * 5 * 8));
+    double* zb = static_cast<double*>(scratch_get(h, SCR_FL_ZBAR, nB * N * 7 * 8));
+    double* par = static_cast<double*>(scratch_get(h, SCR_FL_PARAMS, nB * N * 10 * 8));
+    double* zo = static_cast<double*>(scratch_get(h, SCR_FL_ZOUT, nB * N * 7 * 8));
+    int32_t* fl = static_cast<int32_t*>(scratch_get(h, SCR_FL_FLAG, nB * 4));
     if (!st || !zb || !par || !zo || !fl) { h->err = "forces closed loop: out of device memory"; return MPC_ERR_HIP; }
     hipStream_t s = (hipStream_t)stream_;
     ForcesLoopArgs A{};
@@ -4656,31 +4252,12 @@ int mpc_forces_closed_loop_batch(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
                                  int32_t hessian_mode, int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_flag) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "forces closed loop: null or empty argument"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
     const size_t nB = (size_t)B;
-    hipStream_t s = h->own_stream;
-    double* di = static_cast<double*>(scratch_get(h, 21, nB * 5 * 8));
-    double* da = static_cast<double*>(scratch_get(h, 22, nB * 8));
-    double* dp = static_cast<double*>(scratch_get(h, 23, nB * Lp * 2 * 8));
-    double* dor = static_cast<double*>(scratch_get(h, 24, nB * Lp * 8));
-    double* dv = static_cast<double*>(scratch_get(h, 25, nB * 8));
-    double* dt_ = static_cast<double*>(scratch_get(h, 26, nB * L * 5 * 8));
-    double* dc = static_cast<double*>(scratch_get(h, 27, nB * L * 2 * 8));
-    int32_t* df = static_cast<int32_t*>(scratch_get(h, 28, nB * L * 4));
-    if (!di || !da || !dp || !dor || !dv || !dt_ || !dc || !df) { h->err = "forces closed loop: out of device memory"; return MPC_ERR_HIP; }
-    HIP_TRY(h, hipMemcpyAsync(di, init_state, nB * 5 * 8, hipMemcpyHostToDevice, s));
-    if (init_acc) HIP_TRY(h, hipMemcpyAsync(da, init_acc, nB * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dp, path, nB * Lp * 2 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dor, orient, nB * Lp * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dv, vdes, nB * 8, hipMemcpyHostToDevice, s));
-    const int rc = mpc_forces_closed_loop_batch_dev(h, B, L, Lp, di, init_acc ? da : nullptr, dp, dor, dv, lb, ub, hl, hu, hessian_mode, noise_mode, sigma, seed,
-                                                    dt_, dc, step_flag ? df : nullptr, (void*)s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(traj, dt_, nB * L * 5 * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(ctrl, dc, nB * L * 2 * 8, hipMemcpyDeviceToHost, s));
-    if (step_flag) HIP_TRY(h, hipMemcpyAsync(step_flag, df, nB * L * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    return stage_host(h, {{init_state, nB * 5 * 8, false}, {init_acc, nB * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false},
+                          {vdes, nB * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true}, {step_flag, nB * L * 4, true}}, [&](void** d, hipStream_t s) {
+        return mpc_forces_closed_loop_batch_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], lb, ub, hl, hu,
+                                                hessian_mode, noise_mode, sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], s);
+    });
 }
 
 }  // extern "C"
