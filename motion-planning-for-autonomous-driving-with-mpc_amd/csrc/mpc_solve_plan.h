@@ -108,18 +108,45 @@ constexpr uint32_t REF_BOUND_VM = 0x33u;
 // multiplicity 3, one obstacle per batch -- the structure of every NLP the reference builds
 constexpr uint32_t REF_DENSE_LO = 0x31u, REF_DENSE_HI = 0x33u;      // (no lower bound on the acceleration)
 
-constexpr uint32_t HO_BUCKETS = 4;  // hand-over lists of the hybrid solve, by KKT error: >= 1e-3 | >= 1e-4 | >= 1e-5 | below (rank correlation with the iterations left: 0.9)
 constexpr int RIC_DEPTH = 4;        // backward ring (stage blocks, 17 KiB each at nx = 6)
 constexpr int RIC_DEPTH_F = 10;     // forward ring (gains + A + defect rows, 13 KiB each): stages are short, so look further ahead --
                                     // fed by TWO loader waves (even / odd stages), each limited to 4 stages in flight by the 6-bit vmcnt
 
-// control block of the single-launch pipeline (k_pipeline) and of k_solve_wg
-constexpr uint32_t PIPE_X_STRIDE = 64;          // uint32 words per XCD record: arrive @0, head @16, tail @32, finished @48, hand-over ticket @56
-constexpr uint32_t PIPE_ABORT = 8 * PIPE_X_STRIDE;      // abort word; +1 rounds (max), +2.. statistics
-constexpr uint32_t PIPE_STATS = PIPE_ABORT + 2;         // [wait ticks riccati, wait ticks stage, busy ticks stage, items, workers stage, workers riccati]
-constexpr uint32_t PIPE_WG = PIPE_ABORT + 16;           // statistics of the k_solve_wg launch behind the pipeline (5 words: rounds max, rounds, sweeps, instance-rounds, rescued): zeroed and copied back with the block
-constexpr uint32_t PIPE_HO = PIPE_ABORT + 24;           // hand-over list: instances left by retiring tiles, per bucket of their KKT error (HO_BUCKETS words)
-constexpr uint32_t PIPE_HDR = PIPE_ABORT + 32;          // then: stage_done[ntiles] | pad to 2 words | slots[8][cap] (uint64)
+// ---- control block of the single-launch pipeline (k_pipeline) and of k_solve_wg, in uint32 words:
+//      [8 XCD records | head | stage_done[ntiles] | pad to 2 words | slots[8][cap] (uint64)]
+// per-XCD record (k_pipeline): counters a cache line apart
+constexpr uint32_t PIPE_X_STRIDE = 64;
+// (arrivals on the XCD: their order gives the workgroups their role | ready queue: the next ticket a worker draws, the next one a Riccati worker
+//  publishes | tiles of the XCD that have stopped | tiles dealt to the stage workers that build the hand-over lists on their way out)
+enum PipeXcdWord : uint32_t { PX_ARRIVE = 0, PX_HEAD = 16, PX_TAIL = 32, PX_FINISHED = 48, PX_HO_TICKET = 56 };
+// the head: what the host reads back after a solve (the last workgroup of k_solve_wg copies it into the handle's pinned block, Params::fin_host)
+constexpr uint32_t PIPE_ABORT = 8 * PIPE_X_STRIDE;      // where it starts
+constexpr uint32_t HO_BUCKETS = 4;  // hand-over lists of the hybrid solve, by KKT error: >= 1e-3 | >= 1e-4 | >= 1e-5 | below (rank correlation with the iterations left: 0.9)
+enum PipeHeadWord : uint32_t {
+    PH_ABORT = 0, PH_ROUNDS = 1,    // k_pipeline: abort word (0: none; the codes: where the host reports them), rounds of its slowest tile
+    PH_STAT64 = 2,          // four uint64, 100 MHz ticks: Riccati workers waiting, stage workers waiting, stage workers busy; stage items served
+    PH_STAGE_WORKERS = 12, PH_RIC_WORKERS = 13, PH_FAIL = 14,      // ... its workers by role; instances that did not converge (Params::fail_count)
+    PH_WG = 16,             // k_solve_wg, WgStatWord
+    PH_HELPED = 21, PH_FIN_TICKET = 22,     // stage items served by helping Riccati workers; workgroups of the solve's last launch that have left
+    PH_HO = 24,             // HO_BUCKETS counters: instances left by retiring tiles, per bucket of their KKT error
+    PH_DETAIL = 28,         // four words of an abort's circumstances
+    PH_WORDS = 32 };
+enum PipeStat64 : uint32_t { P64_RIC_WAIT, P64_STAGE_WAIT, P64_STAGE_BUSY, P64_ITEMS };      // the uint64 at PH_STAT64
+enum WgStatWord : uint32_t { WGS_ROUNDS_MAX, WGS_ROUNDS, WGS_SWEEPS, WGS_INST_ROUNDS, WGS_RESCUED, WGS_WORDS };    // rounds of the slowest workgroup, workgroup-rounds, sweeps, instance-rounds, instances that took the second chance
+constexpr uint32_t PIPE_STATS = PIPE_ABORT + PH_STAT64, PIPE_WG = PIPE_ABORT + PH_WG, PIPE_HO = PIPE_ABORT + PH_HO, PIPE_HDR = PIPE_ABORT + PH_WORDS;
+struct CtlField { uint32_t at, words, align; };
+template <size_t N> constexpr bool ctl_fields_ok(const CtlField (&f)[N], uint32_t size) {
+    for (size_t i = 0; i < N; ++i) {
+        if (f[i].at % f[i].align || f[i].at + f[i].words > size) return false;
+        for (size_t j = 0; j < i; ++j) if (f[i].at < f[j].at + f[j].words && f[j].at < f[i].at + f[i].words) return false;
+    }
+    return true;
+}
+constexpr CtlField PIPE_HEAD_FIELDS[] = {{PH_ABORT, 1, 1}, {PH_ROUNDS, 1, 1}, {PH_STAT64, 8, 2}, {PH_STAGE_WORKERS, 1, 1}, {PH_RIC_WORKERS, 1, 1}, {PH_FAIL, 1, 1},
+                                         {PH_WG, WGS_WORDS, 1}, {PH_HELPED, 1, 1}, {PH_FIN_TICKET, 1, 1}, {PH_HO, HO_BUCKETS, 1}, {PH_DETAIL, 4, 1}};
+constexpr CtlField PIPE_XCD_FIELDS[] = {{PX_ARRIVE, 1, 1}, {PX_HEAD, 1, 1}, {PX_TAIL, 1, 1}, {PX_FINISHED, 1, 1}, {PX_HO_TICKET, 1, 1}};
+static_assert(ctl_fields_ok(PIPE_HEAD_FIELDS, PH_WORDS) && PIPE_ABORT % 2 == 0 && PH_HO + HO_BUCKETS <= PH_DETAIL, "the head's fields are disjoint, inside it, the uint64 ones 8-byte aligned; the hand-over counters end in front of the abort details");
+static_assert(ctl_fields_ok(PIPE_XCD_FIELDS, PIPE_X_STRIDE), "the fields of an XCD record are disjoint and inside it");
 constexpr uint32_t pipe_slots_off(uint32_t ntiles) { return (PIPE_HDR + ntiles + 1u) & ~1u; }
 constexpr size_t pipe_ctl_words(uint32_t ntiles, uint32_t cap) { return (size_t)pipe_slots_off(ntiles) + (size_t)16 * cap; }
 constexpr int PIPE_MAX_TILES = 256;          // tiles of one persistent launch in converged mode (a Riccati worker owns up to 32: its `fin` mask)

@@ -34,6 +34,7 @@
 
 #include "mpc_host_common.h"
 #include "mpc_solve_plan.h"
+#include "mpc_stamps.h"
 #include "mpc_closed_loop.h"
 #include "mpc_forces_qp.h"
 #include "mpc_riccati_mfma.h"
@@ -83,18 +84,6 @@ __device__ __forceinline__ double lds_uniform(const double v) {
     const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
     const unsigned long long r = ((unsigned long long)lds_uniform((uint32_t)(u >> 32)) << 32) | lds_uniform((uint32_t)u);
     return __builtin_bit_cast(double, r);
-}
-
-// workgroup-wide OR of a predicate with one such barrier (slots double-buffered by call parity)
-__device__ __forceinline__ int block_or(int pred, int (*slots)[8], int& parity) {
-    const int any = __any(pred) ? 1 : 0;
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) slots[parity][wave] = any;
-    lds_barrier();
-    int r = 0;
-    for (int w = 0; w < nw; ++w) r |= slots[parity][w];
-    parity ^= 1;
-    return r;
 }
 
 template <typename R>
@@ -175,9 +164,8 @@ constexpr uint32_t REF_VM = REF_BOUND_VM | MPC_REF_FLAGS;
 // leaves before touching HBM.  Called once per launch by k_stage and once per work item by k_pipeline.
 template <int NX, bool INIT, int MAXT, uint32_t VM = 0xFFu>
 __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, const int n_z, const int stash_rows, const uint32_t b0,
-                                            const unsigned long long tile_bits, double* lds, int (*or_slots)[8], const bool stamp = true,
+                                            const unsigned long long tile_bits, double* lds, const bool stamp = true,
                                             uint32_t* live_out = nullptr, const bool bounds_in_lds = false) {
-    int or_parity = 0;
     Ctx<NX> c;
     constexpr bool STASH = MAXT <= 256 && MPC_STAGE_STASH;
     const bool has_ou = (VM & VM_OSPEC) ? false : (P.has_ou != 0);     // (what the stash parks)
@@ -192,8 +180,7 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
     // (hybrid solve: a tile with few instances left is about to go to k_solve_wg -- its items write the mailbox arrays as well, so that the workgroups
     //  there find their instances in the layout they work on; a property of the tile's mask, the same for every item of the round)
     c.mbw = !INIT && P.mbw_live > 0 && __popcll(tile_bits) <= P.mbw_live;
-#define MPC_STAMP(i) do { if (P.DBG && t == 0 && stamp) P.DBG[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-    MPC_STAMP(0);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_ENTER, t == 0 && stamp);
     if (!INIT) {
         const unsigned long long m = tile_bits >> (b0 & 63u);
         if ((m & ((bx >= 64) ? ~0ull : ((1ull << bx) - 1ull))) == 0ull) return;
@@ -219,7 +206,7 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
         PreTmp<NX> tmp;
         phase_preload<NX, false, VM>(P, c, tmp);           // every array load of the kernel is in flight before the first wait
         phase_premath<NX>(P, c, tmp);
-        MPC_STAMP(1);
+        MPC_STAMP(P.DBG, blockIdx.x, SB_ISSUED, t == 0 && stamp);
         // (launches that write the caller's rows themselves: an instance the Riccati sweep has just given up leaves here -- its iterate is in c.z)
         if (P.emit && c.valid && c.status == ST_SWEEP_FAILED) {
             emit_result<NX>(P, c, -7, c.iters, c.k == 0 ? (double)MPC_S(P.SC, SC_E0) : 0.0);
@@ -233,13 +220,13 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
         // stage threads of an instance hold the same flags (they come out of the block-wide reductions bit for bit) -- so the vote of one
         // wavefront is the vote of the block.  Three barriers + LDS round trips less per work item.
         if (!__any(c.active ? 1 : 0)) return;
-        MPC_STAMP(2);
+        MPC_STAMP(P.DBG, blockIdx.x, SB_LOADED, t == 0 && stamp);
         Red1 r1;
         phase_step_candidates<NX, VM>(P, c, r1);
-        MPC_STAMP(3);
+        MPC_STAMP(P.DBG, blockIdx.x, SB_P1, t == 0 && stamp);
         block_reduce(r1, bx, lds);
         phase_linesearch_begin<NX>(P, c, r1);
-        MPC_STAMP(4);
+        MPC_STAMP(P.DBG, blockIdx.x, SB_RED1, t == 0 && stamp);
         double* stash = lds_x;                                 // shares the exchange region (each thread touches its own column only)
         if (STASH) stash_xfer<NX, true, VM>(c, stash, blockDim.x, t, has_ou);
         while (__any((c.active && c.searching) ? 1 : 0)) {
@@ -249,9 +236,9 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
             phase_linesearch_decide<NX>(P, c, r2);
         }
         if (STASH) stash_xfer<NX, false, VM>(c, stash, blockDim.x, t, has_ou);
-        MPC_STAMP(5);
+        MPC_STAMP(P.DBG, blockIdx.x, SB_LS, t == 0 && stamp);
         phase_apply_update<NX, false, VM>(P, c);
-        MPC_STAMP(6);
+        MPC_STAMP(P.DBG, blockIdx.x, SB_UPDATE, t == 0 && stamp);
     }
     // neighbour-stage exchange through LDS: thread (k, bl) needs x_{k+1} and lambda_{k+1} of the new iterate
     {
@@ -266,14 +253,14 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
             for (int i = 0; i < NX; ++i) { c.xn[i] = ex[i * T + tn]; c.lamn[i] = ex[(NX + i) * T + tn]; }
         }
     }
-    MPC_STAMP(7);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_XCHG, t == 0 && stamp);
     Red3 r3;
     phase_eval_assemble<NX, !INIT, false, VM>(P, c, r3);
-    MPC_STAMP(8);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_EVAL, t == 0 && stamp);
     block_reduce(r3, bx, lds);
-    MPC_STAMP(9);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_RED3, t == 0 && stamp);
     phase_finish<NX, false>(P, c, r3, n_mult, n_z);
-    MPC_STAMP(10);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_END, t == 0 && stamp);
     // convergence poll without an extra kernel: the stage-0 threads (all in wave 0) count the instances still iterating
     if (live_out != nullptr && t < 64) {
         const unsigned long long m = __ballot((c.valid && c.k == 0 && c.active && c.status == ST_RUNNING) ? 1 : 0);
@@ -283,7 +270,6 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
         const int cnt = __popcll(__ballot((c.valid && c.k == 0 && c.active && c.status == ST_RUNNING) ? 1 : 0));
         if (t == 0 && cnt) atomicAdd(P.run_counter, cnt);
     }
-#undef MPC_STAMP
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -338,29 +324,28 @@ __device__ __forceinline__ void wg_stage(const PRef& P, const int ib0, const int
         for (int i = 0; i < NX; ++i) { io.rn[t * NX + i] = c.rn[i]; if (c.k == 0 && c.valid) io.r0[c.bl * 8 + i] = c.r0[i]; }
         io.fric = __ballot((c.valid && c.k == 0 && c.fric_row) ? 1 : 0) != 0ull;
     }
-#define MPC_STAMP(i) do { if (P.DBG && t == 0 && stamp) P.DBG[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-    MPC_STAMP(0);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_ENTER, t == 0 && stamp);
     if (((io.fail >> (t & (bx - 1))) & 1u) && c.valid) { c.status = -7; c.active = false; }      // (what the sweep has written to the status row)
     phase_preload_rec<NX>(P, c, tmp);
     phase_premath<NX>(P, c, tmp);
-    MPC_STAMP(1);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_ISSUED, t == 0 && stamp);
     if (!__any(c.active ? 1 : 0)) return;
-    MPC_STAMP(2);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_LOADED, t == 0 && stamp);
     Red1 r1;
     phase_step_candidates<NX, VM>(P, c, r1);
-    MPC_STAMP(3);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_P1, t == 0 && stamp);
     block_reduce(r1, bx, nullptr);
     phase_linesearch_begin<NX>(P, c, r1);
-    MPC_STAMP(4);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_RED1, t == 0 && stamp);
     while (__any((c.active && c.searching) ? 1 : 0)) {
         Red2 r2;
         phase_trial_eval<NX, VM>(P, c, r2);
         block_reduce(r2, bx, nullptr);
         phase_linesearch_decide<NX, true>(P, c, r2);
     }
-    MPC_STAMP(5);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_LS, t == 0 && stamp);
     phase_apply_update<NX, true, VM>(P, c);
-    MPC_STAMP(6);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_UPDATE, t == 0 && stamp);
     {
         // neighbour-stage exchange: thread (k, bl) needs x_{k+1} and lambda_{k+1} of the new iterate -- lane t + bx of this wavefront
         const int tn = t + bx;
@@ -370,7 +355,7 @@ __device__ __forceinline__ void wg_stage(const PRef& P, const int ib0, const int
             if (tn < 64) { c.xn[i] = xs; c.lamn[i] = ls; }
         }
     }
-    MPC_STAMP(7);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_XCHG, t == 0 && stamp);
     Red3 r3;
     phase_eval_assemble<NX, true, true, VM>(P, c, r3);
     {
@@ -384,17 +369,16 @@ __device__ __forceinline__ void wg_stage(const PRef& P, const int ib0, const int
             for (int i = 0; i < NX; ++i) io.c0[(t & (bx - 1)) * 8 + i] = c.z[2 + i] - c.r0[i];
         }
     }
-    MPC_STAMP(8);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_EVAL, t == 0 && stamp);
     block_reduce(r3, bx, nullptr);
-    MPC_STAMP(9);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_RED3, t == 0 && stamp);
     phase_finish<NX, true>(P, c, r3, n_mult, n_z);
-    MPC_STAMP(10);
+    MPC_STAMP(P.DBG, blockIdx.x, SB_END, t == 0 && stamp);
     // (the ballot IS the activity mask of the next round -- bit l: instance b0 + l goes on; no status row is re-read)
     {
         const unsigned long long m = __ballot((c.valid && c.k == 0 && c.active && c.status == ST_RUNNING) ? 1 : 0);
         if (t == 0) *live_out = (uint32_t)m;
     }
-#undef MPC_STAMP
 }
 
 // VM: bound structure compiled into the phases (0xFF: looked up at run time; REF_VM: the reference's -- every path of a handle uses the
@@ -403,7 +387,6 @@ template <int NX, bool INIT, int MAXT, uint32_t VM = 0xFFu>
 __global__ void __launch_bounds__(MAXT, (INIT && MAXT <= 256) ? 2 : 1) k_stage(const Params Pk, const int n_mult, const int n_z, const int stash_rows) {
     const PRef P(Pk);
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ int or_slots[2][8];
     // workgroups are dealt round-robin to the 8 XCDs: renumber so that each XCD gets a contiguous run of instance
     // columns -- the 64/bx workgroups that share every 128-byte line of a tile then share one L2
     uint32_t blk = blockIdx.x;
@@ -411,7 +394,7 @@ __global__ void __launch_bounds__(MAXT, (INIT && MAXT <= 256) ? 2 : 1) k_stage(c
     const uint32_t b0 = (blk + (uint32_t)P.tile0 * (64u / (uint32_t)P.bx)) * (uint32_t)P.bx;
     // scalar load, uniform branch: finished workgroups leave without any vector memory traffic
     const unsigned long long bits = (!INIT && P.tile_mask != nullptr) ? P.tile_mask[b0 >> 6] : ~0ull;
-    stage_block<NX, INIT, MAXT, VM>(P, n_mult, n_z, stash_rows, b0, bits, lds, or_slots);
+    stage_block<NX, INIT, MAXT, VM>(P, n_mult, n_z, stash_rows, b0, bits, lds);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -495,8 +478,7 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
     //  once when it holds no more than the count, and its instances would do all their iterations behind the pipeline)
     //  (rounded up: a tile of one to four instances still leaves at once -- it would otherwise keep the whole launch going for its last instance)
     if (__popcll(act_mask) * 64 < handover_live * min(64, P.B - (int)(tile * 64u)) + 64) return 0ull;
-#define RIC_STAMP(i) do { if (P.DBG && threadIdx.x == 0 && stamp) P.DBG[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-    RIC_STAMP(0);
+    MPC_STAMP(P.DBG, blockIdx.x, RT_BEGIN, threadIdx.x == 0 && stamp);
     const __amdgpu_buffer_rsrc_t rsrc = P.rws;
     const uint32_t tile_off = tile * P.tile_elems * 8u;
     const uint32_t blk_base = (uint32_t)(uintptr_t)P.BLK - (uint32_t)(uintptr_t)P.WS + tile_off;
@@ -561,9 +543,9 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
                 double Ps[NS], pv[NX];
                 for (int t = 0; t <= N; ++t) {
                     const int k = N - t;
-                    if (t == 15) RIC_STAMP(3);
+                    if (t == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_B15_WAIT, threadIdx.x == 0 && stamp);
                     lds_barrier();
-                    if (t == 15) RIC_STAMP(4);
+                    if (t == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_B15_GO, threadIdx.x == 0 && stamp);
                     RicStage<NX> s;
                     read_stage((uint32_t)(t % RIC_DEPTH) * SLOT, s);
                     if (t == 0) {
@@ -582,7 +564,7 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
                     } else if (ok) {
                         ok = riccati_backward_step<NX, NE, SYM>(P, bb, k, s, delta, hux0, hux1, Ps, pv, SYM && sym);
                     }
-                    if (t == 15) RIC_STAMP(5);
+                    if (t == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_B15_END, threadIdx.x == 0 && stamp);
                 }
             };
             // (six states with a costless, unbounded progress state -- flagged by the host -- and no inertia correction anywhere in the wavefront:
@@ -605,7 +587,7 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
         lds_barrier();
         if (!again) break;
     }
-    RIC_STAMP(1);
+    MPC_STAMP(P.DBG, blockIdx.x, RT_BWD_END, threadIdx.x == 0 && stamp);
     // ================================================================ forward sweep
     const bool go = (wave == 0) && active && !failed;
     if (wave >= 3) {
@@ -641,10 +623,10 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
         for (int i = 0; i < NX; ++i) dx[i] = go ? -(double)MPC_U(P.SC, (uint32_t)(SC_C0 + i)) : 0.0;
         for (int k = 0; k < N; ++k) {
             const uint32_t slot = (uint32_t)(k % RIC_DEPTH_F) * FSLOT;
-            if (k == 15) RIC_STAMP(6);
+            if (k == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_F15_WAIT, threadIdx.x == 0 && stamp);
             lds_barrier();
-            if (k == 15) RIC_STAMP(7);
-            if (k == 0) RIC_STAMP(9);
+            if (k == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_F15_GO, threadIdx.x == 0 && stamp);
+            if (k == 0) MPC_STAMP(P.DBG, blockIdx.x, RT_F0, threadIdx.x == 0 && stamp);
             FwdStage<NX> f;
 #pragma unroll
             for (int j = 0; j < NX; ++j) {
@@ -659,7 +641,7 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
             // executed by every lane (finished / padding instances just write an unused step): keeping the stores out of
             // a divergent branch spares a waterfall loop around each of them
             riccati_forward_step<NX>(P, bb, k, f, dx);
-            if (k == 15) RIC_STAMP(8);
+            if (k == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_F15_END, threadIdx.x == 0 && stamp);
         }
         if (go) {
             double dz[D::NZ];
@@ -670,8 +652,7 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
             ws_store_rows<D::NZ>(MPC_ROWS(MPC_UK(P.DZ, D::NZ, N, e)), dz);
         }
     }
-    RIC_STAMP(2);
-#undef RIC_STAMP
+    MPC_STAMP(P.DBG, blockIdx.x, RT_FWD_END, threadIdx.x == 0 && stamp);
     return act_mask;
 #else
     return 0ull;
@@ -776,7 +757,6 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
     const PRef P = mpc_pref(Pk, true);  // (xcu: rows travel between the CUs of an XCD inside this launch -- every workspace load is an sc1 load)
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ int or_slots[2][8];
     __shared__ uint32_t sh_word[4];
     const int t = threadIdx.x;
     // the XCD this workgroup runs on, as an index among the XCDs the device was seen to have (k_xcd_census at handle
@@ -791,7 +771,7 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
     const uint32_t n_tiles_x = A.ntiles > xcd ? (A.ntiles - xcd + n_xcd - 1u) / n_xcd : 0u;   // tiles xcd, xcd + n_xcd, ...
     if (n_tiles_x == 0u) return;
     if ((A.flags & 2u) && t == 0) pipe_st(abort_w, 1u);
-    if (t == 0) sh_word[0] = pipe_add(X + 0, 1u);
+    if (t == 0) sh_word[0] = pipe_add(X + PX_ARRIVE, 1u);
     lds_barrier();
     const uint32_t slot = lds_uniform(sh_word[0]);
     const uint32_t n_ric = A.n_ric < n_tiles_x ? A.n_ric : n_tiles_x;
@@ -799,7 +779,6 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
     unsigned long long waited = 0;
     // (profiling aid: stamps of the worker's 6th pass / item only -- later ones would overwrite them)
     uint32_t n_pass = 0;
-#define PIPE_STAMP(i) do { if (P.DBG && t == 0 && n_pass == 5u) P.DBG[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
     if (slot < n_ric) {
         // ============================================================ Riccati worker: local tiles slot, slot + n_ric, ...
         // (option pipe_help: a Riccati worker whose tile has just gone to the stage workers takes ONE stage item of the queue itself instead of
@@ -815,7 +794,7 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
                 if ((fin >> j) & 1u) continue;
                 all_done = false;
                 const uint32_t tile = (slot + j * n_ric) * n_xcd + xcd;
-                PIPE_STAMP(11);
+                MPC_STAMP(P.DBG, blockIdx.x, PR_WAIT, t == 0 && n_pass == 5u);
                 if (t == 0) {
                     uint32_t ok = 1u;
                     const uint32_t need = A.items * round;
@@ -824,10 +803,10 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
                         if (pipe_ld(abort_w)) { ok = 0u; break; }
                         if (wall_clock64() - t0 > PIPE_SPIN_LIMIT) {
                             // (diagnostics of the abort message: which tile and round, the arrivals seen, the arrivals a millisecond later, the ticks waited)
-                            pipe_st(abort_w + 28, (tile << 16) | (round & 0xFFFFu)); pipe_st(abort_w + 29, pipe_ld(stage_done + tile)); pipe_st(abort_w + 31, (uint32_t)(wall_clock64() - t0));
+                            pipe_st(abort_w + PH_DETAIL, (tile << 16) | (round & 0xFFFFu)); pipe_st(abort_w + PH_DETAIL + 1, pipe_ld(stage_done + tile)); pipe_st(abort_w + PH_DETAIL + 3, (uint32_t)(wall_clock64() - t0));
                             const unsigned long long t1 = wall_clock64();
                             while (wall_clock64() - t1 < 100000ull) __builtin_amdgcn_s_sleep(8);
-                            pipe_st(abort_w + 30, pipe_ld(stage_done + tile));
+                            pipe_st(abort_w + PH_DETAIL + 2, pipe_ld(stage_done + tile));
                             pipe_st(abort_w, 2u); ok = 0u; break;
                         }
                         __builtin_amdgcn_s_sleep(MPC_PIPE_SLEEP);
@@ -839,7 +818,7 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
                 }
                 lds_barrier();
                 if (lds_uniform(sh_word[1]) == 0u) return;
-                PIPE_STAMP(12);
+                MPC_STAMP(P.DBG, blockIdx.x, PR_SWEEP, t == 0 && n_pass == 5u);
                 const unsigned long long mask = riccati_tile<NX>(P, tile, reinterpret_cast<char*>(lds), n_pass == 5u, (int)A.handover);
                 if (mask == 0ull) {
                     fin |= 1u << j;
@@ -849,8 +828,8 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
                         {   __hip_atomic_fetch_or(stage_done + tile, 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (performed before this worker counts its tile as finished: the stage workers read it on their way out)
                         }
-                        atomicMax(A.ctl + PIPE_ABORT + 1, round);
-                        pipe_add(X + 48, 1u);
+                        atomicMax(abort_w + PH_ROUNDS, round);
+                        pipe_add(X + PX_FINISHED, 1u);
                     }
                 } else if (t < 64) {
                     // (the tile's mask goes out with the sweep's last stores: ONE wait covers both -- it is read by a stage worker only after it has seen
@@ -858,13 +837,13 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
                     if (t == 0) __hip_atomic_store(P.tile_mask + tile, mask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // gains, cost-to-go and the step are in the L2
                     if (t == 0) {
-                        const uint32_t tk = pipe_add(X + 32, A.items);
+                        const uint32_t tk = pipe_add(X + PX_TAIL, A.items);
                         for (uint32_t q = 0; q < A.items; ++q)
                             __hip_atomic_store(slots + ((tk + q) & (A.cap - 1u)), ((unsigned long long)(tk + q + 1u) << 32) | (unsigned long long)((tile << 8) | q),
                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
                 }
-                PIPE_STAMP(13);
+                MPC_STAMP(P.DBG, blockIdx.x, PR_PUBLISHED, t == 0 && n_pass == 5u);
                 ++n_pass;
                 lds_barrier();                     // the rings are free again
                 if constexpr (helper) if (mask != 0ull) {
@@ -877,11 +856,11 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
                         const uint32_t tile_n = (slot + jn * n_ric) * n_xcd + xcd;
                         if (pipe_ld(stage_done + tile_n) < A.items * rn) {
                             // a ticket only for an item that has been published (the stage workers draw theirs blindly and wait; this worker must not)
-                            uint32_t hd = pipe_ld(X + 16);
+                            uint32_t hd = pipe_ld(X + PX_HEAD);
                             bool got = false;
-                            while ((int32_t)(pipe_ld(X + 32) - hd) > 0) {
+                            while ((int32_t)(pipe_ld(X + PX_TAIL) - hd) > 0) {
                                 uint32_t seen = hd;
-                                if (__hip_atomic_compare_exchange_strong(X + 16, &seen, hd + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { got = true; break; }
+                                if (__hip_atomic_compare_exchange_strong(X + PX_HEAD, &seen, hd + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { got = true; break; }
                                 hd = seen;
                             }
                             if (got) {
@@ -891,7 +870,7 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
                                     const unsigned long long v = __hip_atomic_load(sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                     if ((uint32_t)(v >> 32) == hd + 1u) { item = (uint32_t)v; break; }
                                     if (pipe_ld(abort_w)) break;
-                                    if (wall_clock64() - t0 > PIPE_SPIN_LIMIT) { pipe_st(abort_w + 28, hd); pipe_st(abort_w + 29, pipe_ld(X + 32)); pipe_st(abort_w + 31, (uint32_t)(wall_clock64() - t0)); pipe_st(abort_w, 3u); break; }
+                                    if (wall_clock64() - t0 > PIPE_SPIN_LIMIT) { pipe_st(abort_w + PH_DETAIL, hd); pipe_st(abort_w + PH_DETAIL + 1, pipe_ld(X + PX_TAIL)); pipe_st(abort_w + PH_DETAIL + 3, (uint32_t)(wall_clock64() - t0)); pipe_st(abort_w, 3u); break; }
                                     __builtin_amdgcn_s_sleep(1);
                                 }
                                 if (item != PIPE_EXIT) {
@@ -909,7 +888,7 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
                     const uint32_t item = lds_uniform(sh_word[1]);
                     const unsigned long long bits = ((unsigned long long)lds_uniform(sh_word[3]) << 32) | lds_uniform(sh_word[2]);
                     if (item != PIPE_EXIT) {
-                        stage_block<NX, false, 256, VAR == 2 ? REF_VM : 0xFFu>(P, n_mult, n_z, stash_rows, (item >> 8) * 64u + (item & 255u) * (uint32_t)P.bx, bits, lds, or_slots, false, nullptr, false);
+                        stage_block<NX, false, 256, VAR == 2 ? REF_VM : 0xFFu>(P, n_mult, n_z, stash_rows, (item >> 8) * 64u + (item & 255u) * (uint32_t)P.bx, bits, lds, false, nullptr, false);
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         lds_barrier();
                         if (t == 0) {
@@ -922,7 +901,7 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
             }
             if (all_done) break;
         }
-        if (t == 0) { atomicAdd(reinterpret_cast<unsigned long long*>(A.ctl + PIPE_STATS) + 0, waited); pipe_add(A.ctl + PIPE_STATS + 11, 1u); if (n_help) pipe_add(A.ctl + PIPE_ABORT + 21, n_help); }   // (word 21: stage items served by helping Riccati workers; word 14 is the fail count of k_egest)
+        if (t == 0) { atomicAdd(reinterpret_cast<unsigned long long*>(A.ctl + PIPE_STATS) + P64_RIC_WAIT, waited); pipe_add(abort_w + PH_RIC_WORKERS, 1u); if (n_help) pipe_add(abort_w + PH_HELPED, n_help); }
         return;
     }
     // ================================================================ stage worker: pulls (tile, sub-block) items of its XCD
@@ -930,21 +909,21 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
     uint32_t n_items = 0;
     bool have_bounds = false;
     for (;;) {
-        PIPE_STAMP(11);
+        MPC_STAMP(P.DBG, blockIdx.x, PW_TAKE, t == 0 && n_pass == 5u);
         if (t == 0) {
-            const uint32_t tk = pipe_add(X + 16, 1u);
+            const uint32_t tk = pipe_add(X + PX_HEAD, 1u);
             const unsigned long long* sl = slots + (tk & (A.cap - 1u));
             uint32_t item = PIPE_EXIT;
             const unsigned long long t0 = wall_clock64();
             for (;;) {
                 const unsigned long long v = __hip_atomic_load(sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if ((uint32_t)(v >> 32) == tk + 1u) { item = (uint32_t)v; break; }
-                if (pipe_ld(X + 48) >= n_tiles_x || pipe_ld(abort_w)) break;             // every tile of this XCD is finished: nothing can arrive
-                if (wall_clock64() - t0 > PIPE_SPIN_LIMIT) { pipe_st(abort_w + 28, tk); pipe_st(abort_w + 29, pipe_ld(X + 32)); pipe_st(abort_w + 31, (uint32_t)(wall_clock64() - t0)); pipe_st(abort_w, 4u); break; }
+                if (pipe_ld(X + PX_FINISHED) >= n_tiles_x || pipe_ld(abort_w)) break;             // every tile of this XCD is finished: nothing can arrive
+                if (wall_clock64() - t0 > PIPE_SPIN_LIMIT) { pipe_st(abort_w + PH_DETAIL, tk); pipe_st(abort_w + PH_DETAIL + 1, pipe_ld(X + PX_TAIL)); pipe_st(abort_w + PH_DETAIL + 3, (uint32_t)(wall_clock64() - t0)); pipe_st(abort_w, 4u); break; }
                 __builtin_amdgcn_s_sleep(MPC_PIPE_SLEEP);
             }
             const unsigned long long t1 = wall_clock64();
-            PIPE_STAMP(12);
+            MPC_STAMP(P.DBG, blockIdx.x, PW_GOT, t == 0 && n_pass == 5u);
             waited += t1 - t0;
             busy -= t1;
             unsigned long long bits = 0ull;
@@ -961,23 +940,22 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
         const uint32_t item = lds_uniform(sh_word[1]);
         const unsigned long long bits = ((unsigned long long)lds_uniform(sh_word[3]) << 32) | lds_uniform(sh_word[2]);
         if (item == PIPE_EXIT) break;
-        PIPE_STAMP(13);
+        MPC_STAMP(P.DBG, blockIdx.x, PW_BCAST, t == 0 && n_pass == 5u);
         const uint32_t tile = item >> 8;
-        stage_block<NX, false, 256, VAR == 2 ? REF_VM : 0xFFu>(P, n_mult, n_z, stash_rows, tile * 64u + (item & 255u) * (uint32_t)P.bx, bits, lds, or_slots, n_pass == 5u, nullptr, have_bounds);
+        stage_block<NX, false, 256, VAR == 2 ? REF_VM : 0xFFu>(P, n_mult, n_z, stash_rows, tile * 64u + (item & 255u) * (uint32_t)P.bx, bits, lds, n_pass == 5u, nullptr, have_bounds);
         // (an item whose instance columns have all finished leaves stage_block before the copy)
         have_bounds = have_bounds || ((bits >> (((item & 255u) * (uint32_t)P.bx) & 63u)) & ((P.bx >= 64) ? ~0ull : ((1ull << P.bx) - 1ull))) != 0ull;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                               // this wave's rows are in the L2
         lds_barrier();
-        PIPE_STAMP(14);
+        MPC_STAMP(P.DBG, blockIdx.x, PW_DONE, t == 0 && n_pass == 5u);
         if (t == 0) {
             pipe_add(stage_done + tile, 1u);
             busy += wall_clock64();
             ++n_items;
         }
-        PIPE_STAMP(15);
+        MPC_STAMP(P.DBG, blockIdx.x, PW_SIGNALLED, t == 0 && n_pass == 5u);
         ++n_pass;
     }
-#undef PIPE_STAMP
     // ---- hybrid solve: the stage workers of an XCD leave when every tile of the XCD has stopped -- on their way out they put the instances the
     //      tiles left onto the hand-over lists (ho_lists; tiles dealt by ticket).  A launch of its own for this costs 5.5 us between the two kernels.
     if (A.ho_list != nullptr && t < 64 && pipe_ld(abort_w) == 0u) {
@@ -985,7 +963,7 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         for (;;) {
             uint32_t j = 0u;
-            if (t == 0) j = pipe_add(X + 56, 1u);
+            if (t == 0) j = pipe_add(X + PX_HO_TICKET, 1u);
             j = (uint32_t)__builtin_amdgcn_readfirstlane((int)j);
             if (j >= n_tiles_x) break;
             ho_lists(P, (j * n_xcd + xcd) * 64u + (uint32_t)t, A.ho_list, A.ctl + PIPE_HO, stage_done);
@@ -993,10 +971,10 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
     }
     if (t == 0) {
         unsigned long long* st = reinterpret_cast<unsigned long long*>(A.ctl + PIPE_STATS);
-        atomicAdd(st + 1, waited);
-        atomicAdd(st + 2, busy + wall_clock64());
-        atomicAdd(st + 3, (unsigned long long)n_items);
-        pipe_add(A.ctl + PIPE_STATS + 10, 1u);
+        atomicAdd(st + P64_STAGE_WAIT, waited);
+        atomicAdd(st + P64_STAGE_BUSY, busy + wall_clock64());
+        atomicAdd(st + P64_ITEMS, (unsigned long long)n_items);
+        pipe_add(abort_w + PH_STAGE_WORKERS, 1u);
     }
 #endif
 }
@@ -1023,7 +1001,7 @@ template <int NX, class Src = PrestartFromWs> __device__ __forceinline__ void pr
 // safeguard, start iterate (what k_start does for a block) -- see k_solve_wg<.., RESC>
 template <int NX>
 __device__ __attribute__((noinline)) void wg_restart(const PRef& Pin, const int n_mult, const int n_z, const int stash_rows, const uint32_t b0, double* lds,
-                                                     int (*or_slots)[8], uint32_t* live_out, const bool carry, const bool from_xs, const bool keep_first, const bool first_tiled) {
+                                                     uint32_t* live_out, const bool carry, const bool from_xs, const bool keep_first, const bool first_tiled) {
     const PRef P = mpc_pref(static_cast<const Params&>(Pin), false);      // (a copy in registers, its cache policy a literal again: the reference points into the caller's stack)
     using D = Dim<NX>;
     const int t = threadIdx.x, N = P.N, bx = P.bx;
@@ -1072,7 +1050,7 @@ __device__ __attribute__((noinline)) void wg_restart(const PRef& Pin, const int 
     lds_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stage_block<NX, true, 256>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, or_slots, false, live_out);
+    stage_block<NX, true, 256>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, false, live_out);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1148,7 +1126,6 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
     const bool emit_exit = RESC && resc.on && Pk.emit != 0;
     if (RESC && emit_exit) P.emit = 0;
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ int or_slots[2][8];
     __shared__ uint32_t sh_mask;
     __shared__ int sh_next[2];
     if (skip_if != nullptr && *skip_if != 0u) return;          // the pipeline launch in front of this one was abandoned: the host starts over
@@ -1210,7 +1187,6 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
     double dl0 = 0.0, dl1 = 0.0;
     WgIo io{0u, 0u, lds_c0, lds_rn, lds_r0, lds_scl, true, false};
     const MfmaWords lane_words = mfma_lane_load<NX>(lane);
-#define WG_STAMP(i) do { if (P.DBG && t == 0 && rounds == 3u) P.DBG[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
     uint32_t rounds = 0, sweeps = 0, inst_rounds = 0, prev_mask = 0u;
     const unsigned long long t_begin = wtrace ? wall_clock64() : 0ull;        // (option wg_trace: when did this workgroup start, how long did it run, how many rounds)
     unsigned long long t_fresh = 0ull, t_round1 = 0ull;                        // (... when were its instances taken over, when was its first round done)
@@ -1255,7 +1231,7 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
                     int has_xs = (lev >> 8) & 1, first = lev & ~0x1FF;                  // (first: status and iteration count of the first attempt)
                     int acc = (q == 0 ? 0 : (int32_t)MPC_UB(P.ISC, (uint32_t)IS_ITACC, bb)) + it;
                     if (q == 0) {
-                        if (st == 0 || st == -7) { next = 1; first = (st == -7 ? 0x200 : 0) | (it << 16); if (stats != nullptr) atomicAdd(stats + 4, 1u); }
+                        if (st == 0 || st == -7) { next = 1; first = (st == -7 ? 0x200 : 0) | (it << 16); if (stats != nullptr) atomicAdd(stats + WGS_RESCUED, 1u); }
                     } else {
                         if (st == 1) { carry = 1; has_xs = 1; }
                         if (!resc_last(q)) next = q + 1;
@@ -1295,7 +1271,7 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
                 // (out of line, on a copy of the parameters: the start-point safeguard and the start iterate inlined here put the hot loop at 512
                 //  registers with scratch -- B = 256 lane following paid 1.7 % for a path it never takes)
                 const PRef Pc = P;
-                wg_restart<NX>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, or_slots, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
+                wg_restart<NX>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
             }
             fresh = true;
             bounds_ok = false;
@@ -1304,7 +1280,7 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
         }
         ++rounds;
         inst_rounds += (uint32_t)__popc(mask);
-        WG_STAMP(12);
+        MPC_STAMP(P.DBG, blockIdx.x, WG_ROUND, t == 0 && rounds == 3u);
         // ---- taking the instances over: the iterate, its multipliers and the reference move from the tile-major arrays (where the
         //      pipeline / the start-iterate kernel left them) into the instance-major mailbox arrays the rounds below work on -- one
         //      wavefront reads all stages of its one or two instances, and only there are the pieces of a thread contiguous
@@ -1394,7 +1370,7 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
         lds_barrier();
         if (wtrace != nullptr && fresh && t_fresh == 0ull) t_fresh = wall_clock64() - t_begin;
         fresh = false;
-        WG_STAMP(13);
+        MPC_STAMP(P.DBG, blockIdx.x, WG_RECORDS, t == 0 && rounds == 3u);
         // (per-lane operand offsets of the sweeps: unpacked every round from the lane's four table words -- opaque to the compiler here, so
         //  that the twenty unpacked values are not hoisted out of the loop and kept in registers across stage_block)
         MfmaWords lw = lane_words;
@@ -1456,7 +1432,7 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
                 finish(g0, ok[0], delta[0]);
                 if (two) finish(g1, ok[1], delta[1]);
                 lds_barrier();                                       // (step and cost-to-go are in the records; nothing of the sweeps' went to memory that this round reads)
-                WG_STAMP(14);
+                MPC_STAMP(P.DBG, blockIdx.x, WG_SWEPT, t == 0 && rounds == 3u);
             });
             io.have = true;
         }
@@ -1464,10 +1440,9 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
         lds_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        WG_STAMP(15);
+        MPC_STAMP(P.DBG, blockIdx.x, WG_ROUND_END, t == 0 && rounds == 3u);
         if (wtrace != nullptr && rounds == 1u) t_round1 = wall_clock64() - t_begin;
     }
-#undef WG_STAMP
     // the iterate goes back to the tile-major rows k_egest reads (a workgroup that found nothing to do never moved it) -- unless the launch writes
     // the caller's rows itself (Params::emit: the phases have, at the moment the status became final)
     if (rounds > 0u && valid && !Pk.emit) {
@@ -1492,18 +1467,17 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
         wtrace[blockIdx.x * 4 + 3] = (unsigned long long)(inst_rounds & 0xFFFFu) | ((t_fresh & 0xFFFFFFull) << 16) | ((t_round1 & 0xFFFFFFull) << 40);
     }
     if (stats != nullptr && t == 0) {
-        atomicMax(stats + 0, rounds);
-        atomicAdd(stats + 1, rounds);
-        atomicAdd(stats + 2, sweeps);
-        atomicAdd(stats + 3, inst_rounds);
+        atomicMax(stats + WGS_ROUNDS_MAX, rounds);
+        atomicAdd(stats + WGS_ROUNDS, rounds);
+        atomicAdd(stats + WGS_SWEEPS, sweeps);
+        atomicAdd(stats + WGS_INST_ROUNDS, inst_rounds);
     }
 #endif
 }
 // Params::fin_ctl: the launch is the last of its solve -- the workgroup that leaves LAST copies the solve's statistics block (abort word, rounds,
-// counters of both loop kernels, instances that did not converge: PIPE_FIN_WORDS words at fin_ctl) into the handle's pinned host block (fin_host),
-// so that the host reads it when the stream has drained: no copy command, no kernel of its own behind the loop.  fin_ctl[PIPE_FIN_TICKET] counts the
+// counters of both loop kernels, instances that did not converge: the PH_WORDS words at fin_ctl) into the handle's pinned host block (fin_host),
+// so that the host reads it when the stream has drained: no copy command, no kernel of its own behind the loop.  fin_ctl[PH_FIN_TICKET] counts the
 // workgroups that have left.
-constexpr uint32_t PIPE_FIN_WORDS = 32, PIPE_FIN_TICKET = 22;
 template <int NX, int VAR, bool RESC = false>
 __global__ void __launch_bounds__(256) k_solve_wg(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* stats, const uint32_t* skip_if,
                                                                    const WgRescue resc, unsigned long long* wtrace, const int32_t* list, const uint32_t* list_n) {
@@ -1518,10 +1492,10 @@ __global__ void __launch_bounds__(256) k_solve_wg(const Params Pk, const int n_m
             // (this workgroup's counters are agent-scope atomics: performed once acknowledged -- no cache write-back needed for the last workgroup to
             //  read them with agent-scope loads; the caller's rows become visible with the end of the kernel)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            tk = __hip_atomic_fetch_add(ctl + PIPE_FIN_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // counted as gone
+            tk = __hip_atomic_fetch_add(ctl + PH_FIN_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // counted as gone
         }
         tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk);
-        if (tk == gridDim.x - 1u && threadIdx.x < PIPE_FIN_WORDS) {
+        if (tk == gridDim.x - 1u && threadIdx.x < PH_WORDS) {
             const uint32_t v = __hip_atomic_load(ctl + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(kp->fin_host + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
@@ -1558,7 +1532,6 @@ __device__ __forceinline__ void prestart_par_block(const PRef& P, const uint32_t
     c.b = (int)b0 + bl;
     const bool valid = c.k <= N && c.b < P.B;
     const uint32_t bb = (uint32_t)c.b;
-#define PS_STAMP(i) do { if (P.DBG && threadIdx.x == 0) P.DBG[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
     // the bounds table and, next to it, the bounds pushed inwards the way push_in does it (push_limits) -- every clip below is then fmax / fmin
     for (int q0 = 0; q0 < nb; q0 += 2 * (int)blockDim.x) {
         double lo[2], hi[2];
@@ -1579,7 +1552,7 @@ __device__ __forceinline__ void prestart_par_block(const PRef& P, const uint32_t
         A0[bx + bl] = a0ub;
     }
     __syncthreads();
-    PS_STAMP(1);
+    MPC_STAMP(P.DBG, blockIdx.x, PP_BOUNDS, threadIdx.x == 0);
     const double dt = P.dt;
 #define PP_AT(arr, i, k) (arr)[((i) * S + (k)) * bx + bl]
     if (valid) {
@@ -1616,7 +1589,7 @@ __device__ __forceinline__ void prestart_par_block(const PRef& P, const uint32_t
         }
     }
     __syncthreads();
-    PS_STAMP(2);
+    MPC_STAMP(P.DBG, blockIdx.x, PP_DEFECTS, threadIdx.x == 0);
     // the sum of the guess's defects (its rows are complete): by the first stage-thread of the SECOND wavefront, which has nothing to do in the scans
     // -- off the critical path; the same order of additions as ever (stage-major)
     auto defect_sum = [&](const double* D, double th, const int ka, const int kb) {         // stages ka ... kb - 1 added to th
@@ -1693,7 +1666,7 @@ __device__ __forceinline__ void prestart_par_block(const PRef& P, const uint32_t
         }
     };
     scan(2, 3, 2);                                            // delta, v from the controls
-    PS_STAMP(3);
+    MPC_STAMP(P.DBG, blockIdx.x, PP_SCAN1, threadIdx.x == 0);
     if (valid && c.k < N) {
         const double dl = PP_AT(XR, 2, c.k), v = PP_AT(XR, 3, c.k);
         PP_AT(IN, 0, c.k) = v / P.wheelbase * mpc_tan(dl);            // (the functions of ode_eval: same bits as the two-chain kernel)
@@ -1701,7 +1674,7 @@ __device__ __forceinline__ void prestart_par_block(const PRef& P, const uint32_t
     }
     __syncthreads();
     scan(4, 5, NX == 6 ? 2 : 1);                              // psi (and the progress state)
-    PS_STAMP(4);
+    MPC_STAMP(P.DBG, blockIdx.x, PP_SCAN2, threadIdx.x == 0);
     if (valid && c.k < N) {
         double sp, cp;
         mpc_sincos(PP_AT(XR, 4, c.k), sp, cp);
@@ -1711,14 +1684,14 @@ __device__ __forceinline__ void prestart_par_block(const PRef& P, const uint32_t
     }
     __syncthreads();
     scan(0, 1, 2);                                            // x, y
-    PS_STAMP(5);
+    MPC_STAMP(P.DBG, blockIdx.x, PP_SCAN3, threadIdx.x == 0);
     if (valid) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) MPC_K(P.ROLL, NX, 0, i) = PP_AT(XR, i, c.k);
         if (clipped) A0[3 * bx + bl] = 1.0;
     }
     __syncthreads();
-    PS_STAMP(6);
+    MPC_STAMP(P.DBG, blockIdx.x, PP_SUMS, threadIdx.x == 0);
     if (valid && c.k == 0) {
         // the rollout's defects: |x_0 - r_0| and what the clipping took -- zeros unless some stage thread said otherwise (adding them changes nothing)
         double th = 0.0;
@@ -1730,7 +1703,6 @@ __device__ __forceinline__ void prestart_par_block(const PRef& P, const uint32_t
         prestart_decide<NX>(P, c.b, frow, a0lb, a0ub, A0[2 * bx + bl], th);
     }
 #undef PP_AT
-#undef PS_STAMP
 }
 template <int NX>
 __global__ void __launch_bounds__(1024) k_prestart_par(const Params Pk) {
@@ -1740,9 +1712,6 @@ __global__ void __launch_bounds__(1024) k_prestart_par(const Params Pk) {
 }
 // ingest + start-point safeguard + start iterate of a block of bx instances in ONE launch (the three have the same thread mapping; what one
 // leaves in the workspace -- rollout, per-instance bounds of a_0, the verdict -- comes back from this CU's own write-through L1 / the L2)
-#ifndef MPC_KSTART_STOP
-#define MPC_KSTART_STOP 0
-#endif
 #ifndef MPC_KSTART_OCC
 #define MPC_KSTART_OCC 2
 #endif
@@ -1752,14 +1721,12 @@ template <int NX>
 __global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* zero_p, const uint32_t zero_n) {
     const PRef P(Pk);
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ int or_slots[2][8];
     if (zero_p != nullptr && blockIdx.x == 0)
         for (uint32_t q = threadIdx.x; q < zero_n; q += blockDim.x) zero_p[q] = 0u;
     uint32_t blk = blockIdx.x;
     if ((gridDim.x & 7u) == 0u) blk = (blk & 7u) * (gridDim.x >> 3) + (blk >> 3);
     const uint32_t b0 = (blk + (uint32_t)P.tile0 * (64u / (uint32_t)P.bx)) * (uint32_t)P.bx;
-#define KS_STAMP(i) do { if (P.DBG && threadIdx.x == 0) P.DBG[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-    KS_STAMP(11);
+    MPC_STAMP(P.DBG, blockIdx.x, KS_BEGIN, threadIdx.x == 0);
     {
         // ---- the caller's rows of this block (x0, the X_ref part of p: row-major [B][n_w]) -> LDS -> the tile-major Z / REF rows of the
         //      workspace: what k_ingest does for a whole batch, here for the block's own bx instances (consecutive rows: coalesced reads)
@@ -1788,10 +1755,7 @@ __global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start(const Params Pk, 
             }
         }
         __syncthreads();
-        KS_STAMP(12);
-#if MPC_KSTART_STOP == 3
-        return;
-#endif
+        MPC_STAMP(P.DBG, blockIdx.x, KS_ROWS, threadIdx.x == 0);
         struct { int b, k; } c;
         c.k = t / bx;
         const int bl = t & (bx - 1);
@@ -1812,26 +1776,16 @@ __global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start(const Params Pk, 
             __device__ __forceinline__ double z(int bl, int k, int i) const { return i < 2 ? (k < N ? rx[bl * nw + 2 * k + i] : 0.0) : rx[bl * nw + 2 * N + NX * k + (i - 2)]; }
             __device__ __forceinline__ double ref0(int bl, int i) const { return rp[bl * npx + i]; }
         } src{rx, rp, nw, npx, N};
-        KS_STAMP(13);
-#if MPC_KSTART_STOP == 4
-        return;
-#endif
+        MPC_STAMP(P.DBG, blockIdx.x, KS_STORED, threadIdx.x == 0);
         prestart_par_block<NX, FromLds>(P, b0, pre, src);
     }
-    KS_STAMP(14);
-#if MPC_KSTART_STOP == 1
-    return;
-#endif
+    MPC_STAMP(P.DBG, blockIdx.x, KS_SAFE, threadIdx.x == 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    KS_STAMP(15);
-#undef KS_STAMP
-#if MPC_KSTART_STOP == 2
-    return;
-#endif
-    stage_block<NX, true, 256>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, or_slots, true, nullptr, true);
+    MPC_STAMP(P.DBG, blockIdx.x, KS_FENCED, threadIdx.x == 0);
+    stage_block<NX, true, 256>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, true, nullptr, true);
 }
 
 
@@ -2603,6 +2557,7 @@ enum Scratch : int {
     N_SCRATCH
 };
 
+enum FailWord { FAIL_COUNT, FAIL_LOOP_ABORT, FAIL_WORDS };  // d_fail / h_fail: instances of the last solve that did not converge (counted by k_egest); sticky abort word of an asynchronous closed loop
 struct mpc_handle {
     HostProblem hp;
     std::string err;
@@ -2622,7 +2577,7 @@ struct mpc_handle {
     int pipe_flip = 0;
     size_t pipe_clean[2] = {0, 0};     // leading words of each half known to be zero
     size_t pipe_words = 0;
-    uint32_t* h_pipe = nullptr;        // pinned copy of its abort word, round count and statistics (24 words)
+    uint32_t* h_pipe = nullptr;        // pinned copy of a block's head (mpc_solve_plan.h: PipeHeadWord)
     bool pipe_disabled = false;        // the handle stays on one launch per kernel: three pipeline launches had to be abandoned (see k_pipeline), or the XCD census failed
     int pipe_aborts = 0;               // pipeline launches of this handle abandoned so far (a solve whose launch is abandoned starts over with one launch per kernel)
     static constexpr int PIPE_ABORTS_MAX = 3;
@@ -2648,10 +2603,10 @@ struct mpc_handle {
     int n_cu = 256;
     uint32_t xcd_mask = 0xFFu;          // XCDs seen by k_xcd_census
     std::vector<hipEvent_t> ev_pool;
-    uint32_t* d_fail = nullptr;         // [0] instances of the last solve that did not converge (counted by k_egest); [1] sticky abort word of an asynchronous closed loop; [2..5] k_solve_wg: rounds of the slowest workgroup, workgroup-rounds, Riccati sweeps, instance-iterations
+    uint32_t* d_fail = nullptr;         // FailWord (the loop kernels count into PH_FAIL of their control block instead: solve_front)
     bool async_loop = false;            // solves are being enqueued by the closed-loop driver without host synchronisation
     bool async_ok = false;              // ... and the last one really went out that way
-    uint32_t* h_fail = nullptr;         // pinned copy
+    uint32_t* h_fail = nullptr;         // pinned copy (FAIL_COUNT: of every path, read_head)
     int loop_replayed = 0;              // the last closed loop had to be replayed with host synchronisation per step
     int rescued_last = 0;               // instances the last solve handed to the second chance (rescue_dev)
     bool resc_in_kernel = false;        // the last solve ran k_solve_wg with the second chance inside (RESC) over EVERY instance of the batch: rescue_dev has nothing to add
@@ -2768,7 +2723,7 @@ int mpc_create(mpc_handle** out, const mpc_problem_desc* desc) {
     if (hipSetDevice(h->device) != hipSuccess || hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc(&h->d_counter, sizeof(int32_t) * MAX_GROUPS * MAX_POLL_IT) != hipSuccess ||
         hipHostMalloc(&h->h_counter, sizeof(int32_t) * MAX_GROUPS * 2) != hipSuccess ||
-        hipMalloc(&h->d_fail, 8 * sizeof(uint32_t)) != hipSuccess || hipHostMalloc(&h->h_fail, 8 * sizeof(uint32_t)) != hipSuccess) {
+        hipMalloc(&h->d_fail, FAIL_WORDS * sizeof(uint32_t)) != hipSuccess || hipHostMalloc(&h->h_fail, FAIL_WORDS * sizeof(uint32_t)) != hipSuccess) {
         g_create_error = "HIP stream/counter allocation failed";
         delete h;
         return MPC_ERR_HIP;
@@ -2965,11 +2920,13 @@ struct Prof {
         }
         return h->ev_pool[used++];
     }
-    void begin(int kind, hipStream_t st = nullptr) {
+    // a span starts; one left open ends where this one starts, with ONE event (a marker between two kernels costs the stream a microsecond or two:
+    // the kernels of the iteration loop are measured back to back with a single marker between them)
+    void next(int kind, hipStream_t st = nullptr) {
         if (!h->profiling) return;
-        if (open) { next(kind, st); return; }          // (a span left open on purpose: its end is this one's start)
-        kinds.push_back(kind);
         (void)hipEventRecord(get(), st ? st : s);
+        if (open) spans.back().second = used - 1;
+        kinds.push_back(kind);
         spans.push_back({used - 1, 0});
         open = true;
     }
@@ -2978,22 +2935,6 @@ struct Prof {
         (void)hipEventRecord(get(), st ? st : s);
         spans.back().second = used - 1;
         open = false;
-    }
-    // end of one span = start of the next, ONE event (a marker between two kernels costs the stream a microsecond or two: the kernels of the
-    // iteration loop are measured back to back with a single marker between them)
-    void next(int kind, hipStream_t st = nullptr) {
-        if (!h->profiling) return;
-        if (!open) {
-            kinds.push_back(kind);
-            (void)hipEventRecord(get(), st ? st : s);
-            spans.push_back({used - 1, 0});
-            open = true;
-            return;
-        }
-        (void)hipEventRecord(get(), st ? st : s);
-        spans.back().second = used - 1;
-        kinds.push_back(kind);
-        spans.push_back({used - 1, 0});
     }
     void collect() {
         for (int i = 0; i < 6; ++i) h->prof[i] = 0;
@@ -3024,126 +2965,88 @@ static hipError_t wait_stream(mpc_handle* h, hipStream_t stream) {
     return hipStreamSynchronize(stream);
 }
 
-// ---- stamp reports of the profiling aids (option timing; tools/*_timing.py read this text) -----------------------------------------------
-// k_start: shader-clock stamps of every workgroup
-static void report_start_timing(hipStream_t stream, const unsigned long long* d_dbg, int nblk) {
-    std::vector<unsigned long long> hd((size_t)16 * nblk);
-    if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return;
-    const int order[16] = {11, 12, 13, 1, 2, 3, 4, 5, 6, 14, 15, 0, 7, 8, 9, 10};
-    static const char* names[15] = {"rows->LDS", "Z/REF stores", "bounds+a0", "defects", "scan1", "tan+scan2", "sincos+scan3", "ROLL+sums", "decide", "fence", "enter", "init point+exchange", "eval+assemble", "reduce", "finish"};
-    double acc[15] = {0};
-    unsigned long long t0 = ~0ull, t1 = 0ull;
-    for (int bq = 0; bq < nblk; ++bq) {
-        const unsigned long long* r = hd.data() + (size_t)bq * 16;
-        for (int j = 0; j < 15; ++j) acc[j] += (double)(long long)(r[order[j + 1]] - r[order[j]]);
-        t0 = std::min(t0, r[11]); t1 = std::max(t1, r[10]);
-    }
-    fprintf(stderr, "[mpcgpu k_start timing, shader-clock ticks, mean over %d workgroups]", nblk);
-    for (int j = 0; j < 15; ++j) fprintf(stderr, " %s=%.0f", names[j], acc[j] / nblk);
-    fprintf(stderr, "; first start to last end %.0f\n", (double)(t1 - t0));
+// ---- one solve of B <= SolvePlan::max_rows instances, part by part: the path is plan_solve's; what is decided here reacts to what the GPU
+//      returns (the abort word of the pipeline, the convergence poll, the restart after an abandoned launch)
+// the kernel instantiation of a launch, picked in one place per family; set_lds_limits enumerates the same functions' arguments
+// (masked / VAR 2: the reference's bound structure compiled in, else looked up at run time)
+template <int NX> static auto stage_kernel(bool small_wg, bool init, bool masked) {
+    if (small_wg) return init ? &k_stage<NX, true, 256> : masked ? &k_stage<NX, false, 256, REF_VM> : &k_stage<NX, false, 256>;
+    return init ? &k_stage<NX, true, 512> : masked ? &k_stage<NX, false, 512, REF_VM> : &k_stage<NX, false, 512>;
 }
-// k_solve_wg (option wg_trace): every workgroup leaves its start, its end (100 MHz wall clock) and its rounds: when did the long ones start?
-static void report_wg_trace(const unsigned long long* d_wtrace, int n_wtrace) {
-    if (!d_wtrace) return;
-    std::vector<unsigned long long> hw((size_t)4 * n_wtrace);
-    if (hipMemcpy(hw.data(), d_wtrace, hw.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return;
-    unsigned long long t0 = ~0ull, t1 = 0ull;
-    std::vector<int> live;
-    for (int w = 0; w < n_wtrace; ++w) if (hw[4 * w + 2]) { t0 = std::min(t0, hw[4 * w]); t1 = std::max(t1, hw[4 * w + 1]); live.push_back(w); }
-    if (live.empty()) return;
-    std::sort(live.begin(), live.end(), [&](int a, int b) { return hw[4 * a + 1] > hw[4 * b + 1]; });
-    int late = 0;
-    double start_max = 0;
-    for (int w : live) { const double st = (double)(hw[4 * w] - t0) * 1e-2; if (st > 5.0) ++late; start_max = std::max(start_max, st); }
-    fprintf(stderr, "[mpcgpu wg_trace] %d workgroups with work of %d; span %.1f us; %d of them start more than 5 us after the first (latest start %.1f us); the last to finish:\n",
-            (int)live.size(), n_wtrace, (double)(t1 - t0) * 1e-2, late, start_max);
-    for (size_t i = 0; i < live.size() && i < 12; ++i) {
-        const int w = live[i];
-        const double st = (double)(hw[4 * w] - t0) * 1e-2, en = (double)(hw[4 * w + 1] - t0) * 1e-2;
-        const double tf = (double)((hw[4 * w + 3] >> 16) & 0xFFFFFFull) * 1e-2, tr1 = (double)((hw[4 * w + 3] >> 40) & 0xFFFFFFull) * 1e-2;
-        fprintf(stderr, "    workgroup %5d: start %6.1f us  end %6.1f us  rounds %2d  instance-rounds %2d  -> %.1f us per round; instances taken over after %.1f us, first round done after %.1f us, later rounds %.1f us each\n",
-                w, st, en, (int)hw[4 * w + 2], (int)(hw[4 * w + 3] & 0xFFFFu), (en - st) / (double)hw[4 * w + 2], tf, tr1, hw[4 * w + 2] > 1 ? (en - st - tr1) / (double)(hw[4 * w + 2] - 1) : 0.0);
-    }
+template <int NX> static auto wg_kernel(bool masked, bool resc) {
+    if (resc) return masked ? &k_solve_wg<NX, 2, true> : &k_solve_wg<NX, 0, true>;
+    return masked ? &k_solve_wg<NX, 2> : &k_solve_wg<NX, 0>;
 }
-// k_solve_wg alone: shader-clock stamps of every workgroup's third round
-static int report_wg_timing(mpc_handle* h, const unsigned long long* d_dbg, int nblk) {
-    std::vector<unsigned long long> hd((size_t)16 * nblk);
-    HIP_TRY(h, hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double acc[16] = {0};
-    int cnt = 0;
-    // k_solve_wg: 12 round start, 13 records in LDS, 14 sweeps done, [0..10 stage_block's own stamps], 15 round end
-    const int order[16] = {12, 13, 14, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 15, 15};
-    for (int bq = 0; bq < nblk; ++bq) {
-        const unsigned long long* r = hd.data() + (size_t)bq * 16;
-        if (!r[15] || !r[10]) continue;
-        for (int q = 0; q < 14; ++q) acc[q] += (double)(long long)(r[order[q + 1]] - r[order[q]]);
-        ++cnt;
-    }
-    static const char* names[14] = {"records", "sweeps", "enter", "load+premath", "or", "P1", "reduce1+ls-begin", "linesearch", "P3-update", "exchange", "P4-eval", "reduce3", "P5", "drain"};
-    fprintf(stderr, "[mpcgpu k_solve_wg timing, shader-clock ticks, third round of %d workgroups]", cnt);
-    for (int q = 0; q < 14; ++q) fprintf(stderr, " %s=%.0f", names[q], cnt ? acc[q] / cnt : 0.0);
-    fprintf(stderr, "\n");
-    return MPC_OK;
+template <int NX> static auto pipeline_kernel(bool help, bool masked) {      // (helping Riccati workers: in the masked variant only, SolvePlan::pipe_help)
+    return help ? &k_pipeline<NX, 2, true> : masked ? &k_pipeline<NX, 2> : &k_pipeline<NX, 0>;
 }
-// k_pipeline: shader-clock stamps of every worker's LAST work item / tile pass
-static int report_pipe_timing(mpc_handle* h, const unsigned long long* d_dbg) {
-    std::vector<unsigned long long> hd((size_t)16 * h->n_cu);
-    HIP_TRY(h, hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double sa[16] = {0}, ra[9] = {0};
-    int ns = 0, nr = 0;
-    for (int bq = 0; bq < h->n_cu; ++bq) {
-        const unsigned long long* r = hd.data() + (size_t)bq * 16;
-        if (r[15] && r[10]) {
-            const int order[16] = {11, 12, 13, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 14, 15};
-            for (int q = 0; q + 1 < 16; ++q) sa[q] += (double)(long long)(r[order[q + 1]] - r[order[q]]);
-            ++ns;
-        } else if (r[13] && r[2]) {
-            ra[0] += (double)(long long)(r[12] - r[11]); ra[1] += (double)(long long)(r[1] - r[12]);
-            ra[2] += (double)(long long)(r[2] - r[1]); ra[3] += (double)(long long)(r[13] - r[2]);
-            ra[4] += (double)(long long)(r[4] - r[3]); ra[5] += (double)(long long)(r[5] - r[4]);
-            ra[6] += (double)(long long)(r[7] - r[6]); ra[7] += (double)(long long)(r[8] - r[7]);
-            ra[8] += (double)(long long)(r[9] - r[1]);
-            ++nr;
+// per handle: the dynamic-LDS limit belongs to the function object of the handle's device
+template <int NX> static int set_lds_limits(mpc_handle* h, size_t ric_lds) {
+    std::vector<const void*> fs = {reinterpret_cast<const void*>(&k_start<NX>), reinterpret_cast<const void*>(&k_prestart_par<NX>)};
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+            for (int c = 0; c < 2; ++c) fs.push_back(reinterpret_cast<const void*>(stage_kernel<NX>(a, b, c)));
+            fs.push_back(reinterpret_cast<const void*>(wg_kernel<NX>(a, b)));
+            fs.push_back(reinterpret_cast<const void*>(pipeline_kernel<NX>(a, b)));
         }
-    }
-    static const char* sn[15] = {"dequeue", "acquire+bcast", "enter", "issue-loads", "wait+barrier", "P1", "reduce1", "linesearch", "P3-update",
-                                 "exchange", "P4-eval", "reduce3", "P5", "drain", "signal"};
-    fprintf(stderr, "[mpcgpu pipeline timing, shader-clock ticks, last item of %d stage workers]", ns);
-    for (int q = 0; q < 15; ++q) fprintf(stderr, " %s=%.0f", sn[q], ns ? sa[q] / ns : 0.0);
-    fprintf(stderr, "\n[last pass of %d Riccati workers] wait=%.0f backward=%.0f forward=%.0f publish=%.0f; stage 15 of the backward sweep: barrier=%.0f step=%.0f, of the forward sweep: barrier=%.0f step=%.0f, its first stage starts %.0f ticks after the backward sweep\n",
-            nr, nr ? ra[0] / nr : 0.0, nr ? ra[1] / nr : 0.0, nr ? ra[2] / nr : 0.0, nr ? ra[3] / nr : 0.0, nr ? ra[4] / nr : 0.0, nr ? ra[5] / nr : 0.0,
-            nr ? ra[6] / nr : 0.0, nr ? ra[7] / nr : 0.0, nr ? ra[8] / nr : 0.0);
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_riccati<NX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ric_lds));
+    for (const void* kf : fs) HIP_TRY(h, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
+    h->attr_set = true;
     return MPC_OK;
 }
-// one launch per kernel: stamps of the stage kernel's third iteration (per block) and of the Riccati kernel's fourth (per tile)
-static int report_stage_timing(mpc_handle* h, hipStream_t stream, const unsigned long long* d_dbg, int nblk, int ntiles) {
-    HIP_TRY(h, hipStreamSynchronize(stream));
-    std::vector<unsigned long long> hd((size_t)16 * nblk);
-    HIP_TRY(h, hipMemcpy(hd.data(), d_dbg, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double acc[10] = {0};
-    int cnt = 0;
-    for (int bq = 0; bq < nblk; ++bq) {
-        if (!hd[(size_t)bq * 16 + 10]) continue;
-        for (int q = 0; q < 10; ++q) acc[q] += (double)(hd[(size_t)bq * 16 + q + 1] - hd[(size_t)bq * 16 + q]);
-        ++cnt;
+
+// tile groups (sub-batches, option groups): every group runs ingest -> init -> iterations -> egest on its own stream
+struct Group { int tile0, ntl, nblk, b0, b1; hipStream_t st; bool running; };
+// what the parts of a solve share, built once by solve_front
+struct Solve {
+    mpc_handle* h; hipStream_t stream; int32_t B; bool in_rescue;      // the call
+    SolvePlan pl; Params P; WsLayout w; Prof prof; Group grp[MAX_GROUPS];
+    // the control block of the loop kernels (mpc_solve_plan.h) -- one of the handle's two, which alternate: the start kernel of a solve zeroes the other
+    uint32_t* ctl = nullptr;            // one for the next solve, the last workgroup of the loop copies the head of this one into the pinned block
+    DevTmp t_wtrace;                    // option wg_trace: n_wtrace rows of four words
+    int n_wtrace = 0;
+    int it = 0;                         // iterations done (rounds of the slowest tile / workgroup)
+};
+
+// a zeroed stamp buffer of `n_rows` rows for one call, and its report: the rows come back here, mpc_stamps.h words them
+static hipError_t stamp_rows(DevTmp& t, size_t n_rows, hipStream_t st, size_t words = STAMP_SLOTS) {
+    const hipError_t e = hipMalloc(&t.p, sizeof(unsigned long long) * words * n_rows);
+    return e != hipSuccess ? e : hipMemsetAsync(t.p, 0, sizeof(unsigned long long) * words * n_rows, st);
+}
+template <class F> static hipError_t report_stamps(const unsigned long long* d_rows, size_t n, F format, hipStream_t sync = nullptr) {
+    std::vector<unsigned long long> hd(n);
+    hipError_t e = sync ? hipStreamSynchronize(sync) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy(hd.data(), d_rows, n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) fputs(format(hd.data()).c_str(), stderr);
+    return e;
+}
+template <int NX> static void launch_stage(const Solve& s, const Group& q, bool init) {
+    Params Pg = s.P;
+    Pg.tile0 = q.tile0;
+    const auto kf = stage_kernel<NX>(s.pl.small_wg, init, s.pl.masked);
+    hipLaunchKernelGGL(kf, dim3(q.nblk), dim3(s.pl.threads), init ? s.pl.lds_init : s.pl.lds_bytes, q.st, Pg, s.h->hp.n_mult, s.h->hp.n_z, s.pl.stash_rows);
+}
+// k_solve_wg: alone over every instance, or behind the pipeline (skip_if: its abort word) over the instances on the hand-over lists (list, list_n)
+template <int NX> static void launch_wg(Solve& s, const uint32_t* skip_if, const int32_t* list) {
+    mpc_handle* h = s.h; const SolvePlan& pl = s.pl;
+    if (pl.wg_trace) (void)stamp_rows(s.t_wtrace, s.n_wtrace = (s.B + pl.hyb_bx - 1) / pl.hyb_bx, s.stream, 4);
+    Params Pw = s.P;
+    Pw.bx = pl.hyb_bx;
+    // (the last kernel of the solve: its last workgroup copies the head of the control block into the pinned host block)
+    Pw.fin_ctl = h->async_loop ? nullptr : s.ctl + PIPE_ABORT; Pw.fin_host = h->h_pipe;
+    if (skip_if != nullptr) Pw.DBG = nullptr;         // (behind the pipeline: a stamp buffer of option pipe_timing is sized for the PIPELINE's workgroups)
+    WgRescue rs{h->hp.ol_raw, BOUND_RELAX, 0};
+    if (pl.wg_resc) {
+        rs.on = 1;
+        h->resc_ran = true;
+        // (behind the pipeline the launch sees the instances on the hand-over lists only: one that stalled INSIDE the pipeline is on none of
+        //  them and keeps its status for rescue_dev)
+        h->resc_in_kernel = list == nullptr;
     }
-    fprintf(stderr, "[mpcgpu stage timing, shader-clock ticks per block, mean over %d blocks]", cnt);
-    static const char* names[10] = {"issue-loads", "wait+barrier", "P1", "reduce1", "linesearch", "P3-update", "exchange", "P4-eval", "reduce3", "P5"};
-    for (int q = 0; q < 10; ++q) fprintf(stderr, " %s=%.0f", names[q], cnt ? acc[q] / cnt : 0.0);
-    fprintf(stderr, "\n");
-    double bw = 0, fw = 0;
-    int c2 = 0;
-    for (int tq = 0; tq < ntiles && (size_t)(8 * nblk + (tq + 1) * 16) <= hd.size(); ++tq) {
-        const unsigned long long* r = hd.data() + (size_t)8 * nblk + (size_t)tq * 16;
-        if (!r[2]) continue;
-        bw += (double)(r[1] - r[0]);
-        fw += (double)(r[2] - r[1]);
-        ++c2;
-        if (tq == 0) fprintf(stderr, "[riccati stage 15 of tile 0] bwd barrier-wait=%lld compute=%lld | fwd barrier-wait=%lld compute=%lld\n",
-                             (long long)(r[4] - r[3]), (long long)(r[5] - r[4]), (long long)(r[7] - r[6]), (long long)(r[8] - r[7]));
-    }
-    fprintf(stderr, "[mpcgpu riccati timing, ticks per workgroup, mean over %d] backward=%.0f forward=%.0f\n", c2, c2 ? bw / c2 : 0.0, c2 ? fw / c2 : 0.0);
-    return MPC_OK;
+    // (one wavefront per workgroup -- S * hyb_bx <= 64: checked where the path is chosen; its statistics and the lists' counters: words of the control block)
+    const auto kf = wg_kernel<NX>(pl.masked, pl.wg_resc);
+    hipLaunchKernelGGL(kf, dim3(pl.wg_grid), dim3(64), pl.wg_lds, s.stream, Pw, h->hp.n_mult, h->hp.n_z, pl.stash_rows, s.ctl + PIPE_WG, skip_if, rs, s.t_wtrace.as<unsigned long long>(), list,
+                       list != nullptr ? (const uint32_t*)(s.ctl + PIPE_HO) : nullptr);
 }
 // an abandoned pipeline launch: the arrival counters of all tiles as it left them (a tile short of a multiple of its items lost an arrival, one
 // above received a foreign one)
@@ -3154,59 +3057,52 @@ static void report_arrivals(const uint32_t* ctl, int ntiles, uint32_t items) {
     for (int q = 0; q < ntiles; ++q) fprintf(stderr, " %u%s", sd[q] & 0x7FFFFFFFu, (sd[q] >> 31) ? "r" : "");
     fprintf(stderr, "\n");
 }
+// the head of the control block as the loop kernels left it (h_pipe; PipeHeadWord): instances that did not converge, second chances taken inside
+// the launch, the profiles of the kernels that ran
+static void read_head(Solve& s) {
+    mpc_handle* h = s.h; const uint32_t* hd = h->h_pipe;
+    h->h_fail[FAIL_COUNT] = hd[PH_FAIL];
+    if (h->resc_ran && !s.in_rescue) h->rescued_last = (int)hd[PH_WG + WGS_RESCUED];
+    if (s.pl.res_path || s.pl.hand > 0) {          // k_solve_wg (behind the pipeline: the workgroups launched are what the machine holds, dealt from the hand-over lists)
+        h->res_prof[1] = 1; h->res_prof[2] = hd[PH_WG + WGS_ROUNDS_MAX]; h->res_prof[3] = s.pl.wg_grid;
+        h->res_prof[4] = hd[PH_WG + WGS_ROUNDS]; h->res_prof[5] = hd[PH_WG + WGS_SWEEPS]; h->res_prof[6] = hd[PH_WG + WGS_INST_ROUNDS];
+    }
+    s.it = (int)hd[s.pl.pipe_path ? PH_ROUNDS : PH_WG + WGS_ROUNDS_MAX];
+    if (s.pl.pipe_path) {
+        const unsigned long long* st64 = reinterpret_cast<const unsigned long long*>(hd + PH_STAT64);
+        h->pipe_prof[1] = 1; h->pipe_prof[2] = s.it;
+        h->pipe_prof[3] = (double)st64[P64_RIC_WAIT] * 1e-5; h->pipe_prof[4] = (double)st64[P64_STAGE_WAIT] * 1e-5; h->pipe_prof[5] = (double)st64[P64_STAGE_BUSY] * 1e-5;   // 100 MHz ticks -> ms
+        h->pipe_prof[6] = (double)st64[P64_ITEMS]; h->pipe_prof[7] = (double)hd[PH_STAGE_WORKERS] + 1e-3 * (double)hd[PH_RIC_WORKERS];
+    }
+}
 
-// One solve of B <= SolvePlan::max_rows instances: the path is plan_solve's; what is decided here reacts to what the GPU returns (the
-// abort word of the pipeline, the convergence poll, the restart after an abandoned launch).
+// the front: parameters, tile groups, buffers of the aids, control block; then caller's rows -> workspace, start-point safeguard, start iterate
 template <int NX>
-static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst,
-                          double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream,
-                          double* trace, int32_t trace_rows, int32_t* n_it_out, bool in_rescue) {
+static int solve_front(Solve& s, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt) {
+    mpc_handle* h = s.h;
     const mpc_problem_desc& d = h->hp.desc;
-    const Knobs& kn = h->knobs;
-    const size_t Bp = ((size_t)B + 63) / 64 * 64;
-    PlanState ps = plan_state(h, B, d_obst != nullptr, trace != nullptr, in_rescue);
-    SolvePlan pl = plan_solve(h->hp, kn, ps);
-    // tile-major layout: the rows of a tile do not depend on the batch size, so a smaller batch lives in the first tiles of
-    // a larger allocation (grow-only; the rescue path alternates between the full batch and a failed subset)
-    int rc = ensure_ws(h, Bp, pl.mailbox);
-    if (rc) return rc;
-    if (ps.ws_mailbox != h->ws_mailbox) { ps.ws_mailbox = h->ws_mailbox; pl = plan_solve(h->hp, kn, ps); }
-    const int bx = pl.bx, threads = pl.threads, nblk = pl.nblk, ntiles = pl.ntiles, G = pl.G, stash_rows = pl.stash_rows;
-    const int hyb_bx = pl.hyb_bx, hand = pl.hand;
-    Params P;
-    fill_params(P, h->hp, B, Bp, bx, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
+    const SolvePlan& pl = s.pl;
+    const int B = s.B, ntiles = pl.ntiles, G = pl.G;
+    const size_t Bp = (size_t)ntiles * 64;
+    hipStream_t stream = s.stream; Params& P = s.P;
+    fill_params(P, h->hp, B, Bp, pl.bx, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
     P.mbw_live = 0;
     P.x0 = d_x0; P.p = d_p; P.x_out = d_x_out; P.status_out = d_status; P.iters_out = d_iters; P.kkt_out = d_kkt;
-    const WsLayout w = ws_layout(d.N, d.nx, Bp, h->ws_mailbox);
-    Prof prof{h, stream};
+    s.w = ws_layout(d.N, d.nx, Bp, h->ws_mailbox);
+    const WsLayout& w = s.w;
     h->async_ok = false;
     if (d_obst) {
         P.per_inst_obst = 1;
         hipLaunchKernelGGL(k_transpose_obst, dim3((B + 255) / 256), dim3(256), 0, stream, d_obst, h->d_ws + w.OBST * 64, B, (uint32_t)w.tile_elems);
     }
-    if (!h->attr_set) {        // per handle: the attribute belongs to the function object of the handle's device
-        const void* lds_max_kernels[] = {
-            reinterpret_cast<const void*>(&k_stage<NX, false, 256>), reinterpret_cast<const void*>(&k_start<NX>), reinterpret_cast<const void*>(&k_prestart_par<NX>),
-            reinterpret_cast<const void*>(&k_stage<NX, true, 256>), reinterpret_cast<const void*>(&k_stage<NX, false, 512>), reinterpret_cast<const void*>(&k_stage<NX, true, 512>),
-            reinterpret_cast<const void*>(&k_pipeline<NX, false>), reinterpret_cast<const void*>(&k_solve_wg<NX, false>),
-            reinterpret_cast<const void*>(&k_stage<NX, false, 256, REF_VM>), reinterpret_cast<const void*>(&k_stage<NX, false, 512, REF_VM>),
-            reinterpret_cast<const void*>(&k_pipeline<NX, 2>), reinterpret_cast<const void*>(&k_pipeline<NX, 2, true>), reinterpret_cast<const void*>(&k_solve_wg<NX, 2>),
-            reinterpret_cast<const void*>(&k_solve_wg<NX, 0, true>), reinterpret_cast<const void*>(&k_solve_wg<NX, 2, true>)};
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_riccati<NX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.ric_lds));
-        for (const void* kf : lds_max_kernels) HIP_TRY(h, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-        h->attr_set = true;
-    }
-
-    // ---- tile groups (sub-batches).  Every group runs ingest -> init -> iterations -> egest on its own stream.
-    struct Group { int tile0, ntl, blk0, nblk, b0, b1; hipStream_t st; bool running; };
-    Group grp[MAX_GROUPS];
+    if (!h->attr_set) { const int rc = set_lds_limits<NX>(h, pl.ric_lds); if (rc) return rc; }
     for (int g = 0; g < G; ++g) {
-        Group& q = grp[g];
+        Group& q = s.grp[g];
         q.tile0 = (int)((long long)ntiles * g / G);
         q.ntl = (int)((long long)ntiles * (g + 1) / G) - q.tile0;
         q.b0 = q.tile0 * 64;
         q.b1 = std::min(B, (q.tile0 + q.ntl) * 64);
-        q.nblk = (q.b1 - q.b0 + bx - 1) / bx;
+        q.nblk = (q.b1 - q.b0 + pl.bx - 1) / pl.bx;
         q.st = (G == 1) ? stream : h->sub_stream[g];
         q.running = q.b1 > q.b0;
     }
@@ -3214,42 +3110,8 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         HIP_TRY(h, hipEventRecord(h->ev_fork, stream));
         for (int g = 0; g < G; ++g) HIP_TRY(h, hipStreamWaitEvent(h->sub_stream[g], h->ev_fork, 0));
     }
-    auto launch_stage = [&](const Group& q, bool init) {
-        Params Pg = P;
-        Pg.tile0 = q.tile0;
-        if (!init && pl.stage_timing && P.DBG) Pg.DBG = P.DBG;
-        if (pl.small_wg) {
-            if (init) hipLaunchKernelGGL((k_stage<NX, true, 256>), dim3(q.nblk), dim3(threads), pl.lds_init, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else if (pl.masked) hipLaunchKernelGGL((k_stage<NX, false, 256, REF_VM>), dim3(q.nblk), dim3(threads), pl.lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else hipLaunchKernelGGL((k_stage<NX, false, 256>), dim3(q.nblk), dim3(threads), pl.lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-        } else {
-            if (init) hipLaunchKernelGGL((k_stage<NX, true, 512>), dim3(q.nblk), dim3(threads), pl.lds_init, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else if (pl.masked) hipLaunchKernelGGL((k_stage<NX, false, 512, REF_VM>), dim3(q.nblk), dim3(threads), pl.lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-            else hipLaunchKernelGGL((k_stage<NX, false, 512>), dim3(q.nblk), dim3(threads), pl.lds_bytes, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows);
-        }
-    };
     if (pl.poison)            // (debugging aid: NaN into every row of every tile of the workspace before the solve)
         hipLaunchKernelGGL(k_poison, dim3(1024), dim3(256), 0, stream, h->d_ws, (uint32_t)w.tile_elems, (uint32_t)w.ntiles, 0u, (uint32_t)w.rows * 64u);
-    DevTmp t_trace, t_dbg, t_pdbg;
-    double* d_trace = nullptr;
-    if (trace) { HIP_TRY(h, hipMalloc(&t_trace.p, sizeof(double) * 8 * (size_t)B)); d_trace = t_trace.as<double>(); }
-    auto record_trace = [&](int it) -> int {
-        if (!trace || it >= trace_rows) return MPC_OK;
-        hipLaunchKernelGGL(k_gather_trace, dim3((B + 255) / 256), dim3(256), 0, stream, h->d_ws + w.SC * 64, (uint32_t)w.tile_elems, B, d_trace);
-        HIP_TRY(h, hipStreamSynchronize(stream));
-        HIP_TRY(h, hipMemcpy(trace + (size_t)it * 8 * B, d_trace, sizeof(double) * 8 * (size_t)B, hipMemcpyDeviceToHost));
-        return MPC_OK;
-    };
-    unsigned long long* d_dbg = nullptr;
-    if (pl.stage_timing) {
-        HIP_TRY(h, hipMalloc(&t_dbg.p, sizeof(unsigned long long) * 16 * (size_t)nblk));
-        d_dbg = t_dbg.as<unsigned long long>();
-        HIP_TRY(h, hipMemsetAsync(d_dbg, 0, sizeof(unsigned long long) * 16 * (size_t)nblk, stream));
-    }
-    // Convergence polling: every stage launch adds the number of instances it leaves running to its own device counter;
-    // after each chunk the last counter is copied to pinned memory.  The host looks at the poll of chunk c-1 only after
-    // chunk c is enqueued, so the GPU never idles on a host round trip; the price is one chunk of early-exit launches
-    // (a few microseconds each) at the very end.
     if (h->tile_mask_cap < (size_t)ntiles) {
         if (h->d_tile_mask) (void)hipFree(h->d_tile_mask);
         h->d_tile_mask = nullptr;
@@ -3258,46 +3120,9 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
     }
     P.tile_mask = h->d_tile_mask;
     if (pl.polled && pl.cap > MAX_POLL_IT) { h->err = "max_iter exceeds the poll table (1024)"; return MPC_ERR_INVALID; }
-    int it = 0, chunk_id = 0;
     h->last_mode = 0;
     for (int i = 0; i < 8; ++i) { h->pipe_prof[i] = 0; h->res_prof[i] = 0; }
-    bool piped = false;
-    DevTmp t_wtrace;
-    unsigned long long* d_wtrace = nullptr;
-    int n_wtrace = 0;
-    const int32_t* wg_list = nullptr;                   // (behind the pipeline: the instances its retiring tiles left, see k_solve_wg)
-    const uint32_t* wg_list_n = nullptr;
-    auto launch_wg = [&](const uint32_t* skip_if, uint32_t* stats, uint32_t* fin_ctl) {
-        if (pl.wg_trace) {
-            n_wtrace = (B + hyb_bx - 1) / hyb_bx;
-            if (hipMalloc(&t_wtrace.p, sizeof(unsigned long long) * 4 * (size_t)n_wtrace) == hipSuccess) {
-                d_wtrace = t_wtrace.as<unsigned long long>();
-                (void)hipMemsetAsync(d_wtrace, 0, sizeof(unsigned long long) * 4 * (size_t)n_wtrace, stream);
-            }
-        }
-        Params Pw = P;
-        Pw.bx = hyb_bx;
-        Pw.fin_ctl = fin_ctl; Pw.fin_host = h->h_pipe;
-        if (skip_if != nullptr) Pw.DBG = nullptr;         // (behind the pipeline: a stamp buffer of option pipe_timing is sized for the PIPELINE's workgroups)
-        const int thr = 64;                        // (S * bxw <= 64: checked where the path is chosen)
-        WgRescue rs{h->hp.ol_raw, BOUND_RELAX, 0};
-        const dim3 grid(pl.wg_grid);
-        if (pl.wg_resc) {
-            rs.on = 1;
-            h->resc_ran = true;
-            // (behind the pipeline the launch sees the instances on the hand-over lists only: one that stalled INSIDE the pipeline is on none of
-            //  them and keeps its status for rescue_dev)
-            h->resc_in_kernel = wg_list == nullptr;
-            if (pl.masked) hipLaunchKernelGGL((k_solve_wg<NX, 2, true>), grid, dim3(thr), pl.wg_lds, stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
-            else hipLaunchKernelGGL((k_solve_wg<NX, 0, true>), grid, dim3(thr), pl.wg_lds, stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
-        }
-        else if (pl.masked) hipLaunchKernelGGL((k_solve_wg<NX, 2>), grid, dim3(thr), pl.wg_lds, stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
-        else hipLaunchKernelGGL((k_solve_wg<NX, false>), grid, dim3(thr), pl.wg_lds, stream, Pw, h->hp.n_mult, h->hp.n_z, stash_rows, stats, skip_if, rs, d_wtrace, wg_list, wg_list_n);
-    };
-    // Both loop paths get a control block (abort word, round count, statistics of both loop kernels, count of instances that did not converge,
-    // hand-over lists' counters; the pipeline's queues behind them) -- one of two that alternate: the start kernel of a solve zeroes the other one
-    // for the next solve, the last workgroup of the loop copies the head of this one into the handle's pinned block.
-    uint32_t *ctl = nullptr, *zero_next = nullptr;
+    uint32_t* zero_next = nullptr;
     size_t ctl_words = 0;
     bool next_zeroed = false;
     if (pl.res_path || pl.pipe_path) {
@@ -3309,201 +3134,186 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
             h->pipe_words = ctl_words;
             h->pipe_clean[0] = h->pipe_clean[1] = 0;
         }
-        if (!h->h_pipe) HIP_TRY(h, hipHostMalloc(&h->h_pipe, PIPE_FIN_WORDS * sizeof(uint32_t)));
-        ctl = h->d_pipe + (size_t)h->pipe_flip * h->pipe_words;
+        if (!h->h_pipe) HIP_TRY(h, hipHostMalloc(&h->h_pipe, PH_WORDS * sizeof(uint32_t)));
+        s.ctl = h->d_pipe + (size_t)h->pipe_flip * h->pipe_words;
         zero_next = h->d_pipe + (size_t)(h->pipe_flip ^ 1) * h->pipe_words;
-        if (h->pipe_clean[h->pipe_flip] < ctl_words) HIP_TRY(h, hipMemsetAsync(ctl, 0, ctl_words * sizeof(uint32_t), stream));      // (first use, or a larger batch than the last)
+        if (h->pipe_clean[h->pipe_flip] < ctl_words) HIP_TRY(h, hipMemsetAsync(s.ctl, 0, ctl_words * sizeof(uint32_t), stream));      // (first use, or a larger batch than the last)
         h->pipe_clean[h->pipe_flip] = 0;
         P.emit = 1;
-        // (instances that did not converge are counted into word 14 of the block; an asynchronous closed loop accumulates them over its steps in d_fail instead)
-        P.fail_count = h->async_loop ? h->d_fail : ctl + PIPE_ABORT + 14;
+        // (an asynchronous closed loop accumulates the instances that did not converge over its steps in d_fail instead)
+        P.fail_count = h->async_loop ? h->d_fail + FAIL_COUNT : s.ctl + PIPE_ABORT + PH_FAIL;
     }
-    // ---- the front of the solve: caller's rows -> workspace, start-point safeguard, start iterate
     for (int g = 0; g < G; ++g) {
-        const Group& q = grp[g];
+        const Group& q = s.grp[g];
         if (!q.running) continue;
         Params Pg = P;
         Pg.tile0 = q.tile0;
-        prof.begin(2, q.st);
+        s.prof.next(2, q.st);
         const int n_w = 2 * d.N + NX * (d.N + 1);
-        if (!pl.fused) hipLaunchKernelGGL((k_ingest<NX>), dim3(q.ntl, (n_w + 63) / 64 + (n_w - 2 * d.N + 63) / 64), dim3(256), 0, q.st, Pg);
         if (pl.fused) {
             // (one launch for ingest, safeguard and start iterate: same blocks, same threads)
             DevTmp t_sdbg;
-            if (pl.start_timing && hipMalloc(&t_sdbg.p, sizeof(unsigned long long) * 16 * (size_t)q.nblk) == hipSuccess) {
-                (void)hipMemsetAsync(t_sdbg.p, 0, sizeof(unsigned long long) * 16 * (size_t)q.nblk, q.st);
-                Pg.DBG = t_sdbg.as<unsigned long long>();
-            }
-            hipLaunchKernelGGL((k_start<NX>), dim3(q.nblk), dim3(threads), pl.lds_start, q.st, Pg, h->hp.n_mult, h->hp.n_z, stash_rows,
+            if (pl.start_timing && stamp_rows(t_sdbg, q.nblk, q.st) == hipSuccess) Pg.DBG = t_sdbg.as<unsigned long long>();
+            hipLaunchKernelGGL((k_start<NX>), dim3(q.nblk), dim3(pl.threads), pl.lds_start, q.st, Pg, h->hp.n_mult, h->hp.n_z, pl.stash_rows,
                                g == 0 ? zero_next : (uint32_t*)nullptr, (uint32_t)ctl_words);
             if (g == 0 && zero_next != nullptr) next_zeroed = true;
-            if (Pg.DBG) report_start_timing(q.st, Pg.DBG, q.nblk);          // (synchronises)
+            if (Pg.DBG) (void)report_stamps(Pg.DBG, (size_t)STAMP_SLOTS * q.nblk, [&](const unsigned long long* r) { return format_start_timing(r, q.nblk); }, q.st);
         } else {
-            hipLaunchKernelGGL((k_prestart_par<NX>), dim3(q.nblk), dim3(threads), pl.lds_pre, q.st, Pg);       // (N = 127, bx = 4: 112 KB of LDS)
-            launch_stage(q, true);
+            hipLaunchKernelGGL((k_ingest<NX>), dim3(q.ntl, (n_w + 63) / 64 + (n_w - 2 * d.N + 63) / 64), dim3(256), 0, q.st, Pg);
+            hipLaunchKernelGGL((k_prestart_par<NX>), dim3(q.nblk), dim3(pl.threads), pl.lds_pre, q.st, Pg);       // (N = 127, bx = 4: 112 KB of LDS)
+            launch_stage<NX>(s, q, true);
         }
-        if (G > 1) prof.end(q.st);          // (one stream: the span stays open, the first kernel of the loop starts where it ends)
+        if (G > 1) s.prof.end(q.st);          // (one stream: the span stays open, the first kernel of the loop starts where it ends)
     }
-
-    if (ctl != nullptr) {
+    if (s.ctl != nullptr) {
         h->pipe_clean[h->pipe_flip ^ 1] = next_zeroed ? ctl_words : 0;
         h->pipe_flip ^= 1;
     }
-    if (pl.res_path) {
-        // ---- workgroup-resident solve alone: ALL iterations of every instance in one launch of k_solve_wg
-        DevTmp t_rdbg;
-        if (pl.wg_timing) {
-            HIP_TRY(h, hipMalloc(&t_rdbg.p, sizeof(unsigned long long) * 16 * (size_t)pl.wg_grid));
-            HIP_TRY(h, hipMemsetAsync(t_rdbg.p, 0, sizeof(unsigned long long) * 16 * (size_t)pl.wg_grid, stream));
-            P.DBG = t_rdbg.as<unsigned long long>();
-        }
-        prof.next(5, stream);
-        launch_wg(nullptr, ctl + PIPE_WG, h->async_loop ? nullptr : ctl + PIPE_ABORT);
-        prof.end(stream);
-        h->last_mode = 2;
-        if (h->async_loop) {             // closed-loop driver: nothing comes back to the host per step (this path has no abort word)
-            HIP_TRY(h, hipGetLastError());
-            h->async_ok = true;
-            return MPC_OK;
-        }
-        HIP_TRY(h, wait_stream(h, stream));          // (the last workgroup to leave has put the block's head into h_pipe)
-        h->h_fail[0] = h->h_pipe[14];
-        for (int q = 0; q < 4; ++q) h->h_fail[2 + q] = h->h_pipe[16 + q];
-        if (h->resc_ran && !in_rescue) h->rescued_last = (int)h->h_pipe[20];
-        report_wg_trace(d_wtrace, n_wtrace);
-        if (P.DBG) {
-            rc = report_wg_timing(h, P.DBG, pl.wg_grid);
-            if (rc) return rc;
-            P.DBG = nullptr;
-        }
-        piped = true;
-        it = (int)h->h_fail[2];
-        h->res_prof[1] = 1; h->res_prof[2] = it; h->res_prof[3] = pl.wg_grid; h->res_prof[4] = h->h_fail[3]; h->res_prof[5] = h->h_fail[4]; h->res_prof[6] = h->h_fail[5];
-    } else if (pl.pipe_path) {
-        // ---- single-launch pipeline (k_pipeline): all iterations in one persistent grid, tiles cycling independently
-        PipeArgs A;
-        A.ntiles = (uint32_t)ntiles;
-        A.n_ric = (uint32_t)pl.n_ric;
-        A.xcd_mask = pl.xcd_mask;
-        A.items = 64u / (uint32_t)bx;
-        A.cap = pl.pipe_cap;
-        A.flags = kn.pipe_test_abort ? 2u : 0u;
-        A.handover = (uint32_t)hand;
-        A.ho_list = nullptr;
-        if (hand > 0) {
-            A.ho_list = static_cast<int32_t*>(scratch_get(h, SCR_HO_LIST, (size_t)HO_BUCKETS * Bp * sizeof(int32_t)));
-            if (!A.ho_list) { h->err = "out of device memory"; return MPC_ERR_HIP; }
-        }
-        A.ctl = ctl;
-        unsigned long long* d_pdbg = nullptr;
-        if (pl.pipe_timing) {
-            HIP_TRY(h, hipMalloc(&t_pdbg.p, sizeof(unsigned long long) * 16 * (size_t)h->n_cu));
-            d_pdbg = t_pdbg.as<unsigned long long>();
-            HIP_TRY(h, hipMemsetAsync(d_pdbg, 0, sizeof(unsigned long long) * 16 * (size_t)h->n_cu, stream));
-            P.DBG = d_pdbg;
-        }
-        prof.next(3, stream);
-        P.mbw_live = pl.mbw_live;
-        const size_t lds_pipe = std::max(pl.lds_bytes, pl.ric_lds);
-        if (pl.pipe_help) hipLaunchKernelGGL((k_pipeline<NX, 2, true>), dim3(h->n_cu), dim3(threads), lds_pipe, stream, P, A, h->hp.n_mult, h->hp.n_z, stash_rows);
-        else if (pl.masked) hipLaunchKernelGGL((k_pipeline<NX, 2>), dim3(h->n_cu), dim3(threads), lds_pipe, stream, P, A, h->hp.n_mult, h->hp.n_z, stash_rows);
-        else hipLaunchKernelGGL((k_pipeline<NX, false>), dim3(h->n_cu), dim3(threads), lds_pipe, stream, P, A, h->hp.n_mult, h->hp.n_z, stash_rows);
-        if (hand <= 0) prof.end(stream);
-        if (hand > 0) {        // (its statistics words are part of the control block: no fill, no copy of their own)
-            if (!h->prof_span) prof.next(5, stream);          // (span mode: the pipeline's span stays open over k_solve_wg)
-            // (the counters: words of the control block, zero at the start of every solve)
-            wg_list = A.ho_list; wg_list_n = ctl + PIPE_HO;
-            // (the last kernel of the solve: its last workgroup copies the head of the control block into the pinned host block)
-            launch_wg((const uint32_t*)(ctl + PIPE_ABORT), ctl + PIPE_WG, h->async_loop ? nullptr : ctl + PIPE_ABORT);
-        }
-        prof.end(stream);
-        if (h->async_loop) {
-            // closed-loop driver: nothing comes back to the host per step -- a launch that had to be abandoned leaves its mark
-            // in the loop's sticky abort word, the bookkeeping kernels behind it then do nothing and the host replays the loop
-            hipLaunchKernelGGL(k_loop_sticky, dim3(1), dim3(1), 0, stream, (const uint32_t*)(ctl + PIPE_ABORT), h->d_fail + 1);
-            HIP_TRY(h, hipGetLastError());
-            h->async_ok = true;
-            h->last_mode = 1;
-            return MPC_OK;
-        }
-        // (no kernel behind the loop: the rows are out -- Params::emit -- and k_solve_wg has left the block's head in h_pipe; a pipeline that
-        //  runs its tiles to the end, option hybrid = 0, has no such epilogue: a copy command)
-        if (hand <= 0) HIP_TRY(h, hipMemcpyAsync(h->h_pipe, ctl + PIPE_ABORT, PIPE_FIN_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(h, wait_stream(h, stream));
-        h->h_fail[0] = h->h_pipe[14];
-        report_wg_trace(d_wtrace, n_wtrace);
-        for (int q = 0; q < 4; ++q) h->h_fail[2 + q] = h->h_pipe[16 + q];
-        if (h->resc_ran && !in_rescue) h->rescued_last = (int)h->h_pipe[20];       // (fifth word: instances that took the second chance inside the launch)
-        if (hand > 0) {        // the stragglers' kernel: rounds of its slowest workgroup, workgroups, workgroup-rounds, sweeps, instance-iterations
-            h->res_prof[1] = 1; h->res_prof[2] = h->h_fail[2]; h->res_prof[3] = pl.wg_grid;      // (workgroups launched: what the machine holds when they are dealt from the hand-over lists)
-            h->res_prof[4] = h->h_fail[3]; h->res_prof[5] = h->h_fail[4]; h->res_prof[6] = h->h_fail[5];
-        }
-        if (h->h_pipe[0] != 0u) {
-            // a bounded wait ran out (e.g. the dispatcher left an XCD without stage workers): the workspace is part-way
-            // through an iteration, so start over with one launch per kernel.  Once may be a transient of the machine's other tenants (the
-            // workgroups of a collective spinning on a slow peer, another handle's persistent launch); the handle stays on that path when it
-            // has happened PIPE_ABORTS_MAX times
-            h->pipe_disabled = true;
-            h->resc_in_kernel = h->resc_ran = false;         // (the k_solve_wg behind the abandoned launch returned at once: no instance has had its second chance)
-            // (abort word: 1 option pipe_test_abort, 2 a Riccati worker waited for its tile's stage items [tile << 16 | round; arrivals], 3 a helping
-            //  Riccati worker / 4 a stage worker waited for its queue slot [ticket; queue tail]; words 28 - 31 of the block's head)
-            fprintf(stderr, "[mpcgpu] single-launch pipeline abandoned (bounded wait expired: code %u, %u / %u, a millisecond later %u, waited %u ticks); re-running with one launch per kernel\n",
-                    h->h_pipe[0], h->h_pipe[28], h->h_pipe[29], h->h_pipe[30], h->h_pipe[31]);
-            report_arrivals(ctl, ntiles, A.items);
-            const int rc_again = solve_dev_impl<NX>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it_out, in_rescue);
-            if (++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;
-            return rc_again;
-        }
-        P.DBG = nullptr;
-        if (d_pdbg) { rc = report_pipe_timing(h, d_pdbg); if (rc) return rc; }
-        piped = true;
+    return MPC_OK;
+}
+
+// the workgroup-resident solve alone: ALL iterations of every instance in one launch of k_solve_wg
+template <int NX> static int solve_wg_alone(Solve& s) {
+    mpc_handle* h = s.h; const SolvePlan& pl = s.pl;
+    DevTmp t_rdbg;
+    if (pl.wg_timing) HIP_TRY(h, stamp_rows(t_rdbg, pl.wg_grid, s.stream));
+    s.P.DBG = t_rdbg.as<unsigned long long>();
+    s.prof.next(5, s.stream);
+    launch_wg<NX>(s, nullptr, nullptr);
+    s.prof.end(s.stream);
+    h->last_mode = 2;
+    if (h->async_loop) {             // closed-loop driver: nothing comes back to the host per step (this path has no abort word)
+        HIP_TRY(h, hipGetLastError());
+        h->async_ok = true;
+        return MPC_OK;
+    }
+    HIP_TRY(h, wait_stream(h, s.stream));          // (the last workgroup to leave has put the block's head into h_pipe)
+    read_head(s);
+    if (s.t_wtrace.p) (void)report_stamps(s.t_wtrace.as<unsigned long long>(), (size_t)4 * s.n_wtrace, [&](const unsigned long long* r) { return format_wg_trace(r, s.n_wtrace); });
+    if (s.P.DBG) HIP_TRY(h, report_stamps(s.P.DBG, (size_t)STAMP_SLOTS * pl.wg_grid, [&](const unsigned long long* r) { return format_wg_timing(r, pl.wg_grid); }));
+    s.P.DBG = nullptr;
+    return MPC_OK;
+}
+
+// the single-launch pipeline (k_pipeline): all iterations in one persistent grid, tiles cycling independently; with a hand-over threshold,
+// k_solve_wg behind it
+constexpr int PIPE_ABANDONED = -1000;      // a bounded wait of the launch ran out: the solve has to start over
+template <int NX> static int solve_pipeline(Solve& s) {
+    mpc_handle* h = s.h; const SolvePlan& pl = s.pl;
+    hipStream_t stream = s.stream; Params& P = s.P;
+    int32_t* ho_list = pl.hand > 0 ? static_cast<int32_t*>(scratch_get(h, SCR_HO_LIST, (size_t)HO_BUCKETS * pl.ntiles * 64 * sizeof(int32_t))) : nullptr;
+    if (pl.hand > 0 && !ho_list) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    const PipeArgs A{s.ctl, (uint32_t)pl.ntiles, pl.xcd_mask, (uint32_t)pl.n_ric, pl.pipe_cap, 64u / (uint32_t)pl.bx, (uint32_t)pl.hand, ho_list, h->knobs.pipe_test_abort ? 2u : 0u};
+    DevTmp t_pdbg;
+    if (pl.pipe_timing) HIP_TRY(h, stamp_rows(t_pdbg, h->n_cu, stream));
+    P.DBG = t_pdbg.as<unsigned long long>();
+    s.prof.next(3, stream);
+    P.mbw_live = pl.mbw_live;
+    const auto kf = pipeline_kernel<NX>(pl.pipe_help, pl.masked);
+    hipLaunchKernelGGL(kf, dim3(h->n_cu), dim3(pl.threads), std::max(pl.lds_bytes, pl.ric_lds), stream, P, A, h->hp.n_mult, h->hp.n_z, pl.stash_rows);
+    if (pl.hand > 0) {
+        if (!h->prof_span) s.prof.next(5, stream);          // (span mode: the pipeline's span stays open over k_solve_wg)
+        launch_wg<NX>(s, (const uint32_t*)(s.ctl + PIPE_ABORT), A.ho_list);
+    }
+    s.prof.end(stream);
+    if (h->async_loop) {
+        // closed-loop driver: nothing comes back to the host per step -- a launch that had to be abandoned leaves its mark
+        // in the loop's sticky abort word, the bookkeeping kernels behind it then do nothing and the host replays the loop
+        hipLaunchKernelGGL(k_loop_sticky, dim3(1), dim3(1), 0, stream, (const uint32_t*)(s.ctl + PIPE_ABORT), h->d_fail + FAIL_LOOP_ABORT);
+        HIP_TRY(h, hipGetLastError());
+        h->async_ok = true;
         h->last_mode = 1;
-        it = (int)h->h_pipe[1];
-        const unsigned long long* st64 = reinterpret_cast<const unsigned long long*>(h->h_pipe + 2);
-        h->pipe_prof[1] = 1; h->pipe_prof[2] = it;
-        h->pipe_prof[3] = (double)st64[0] * 1e-5; h->pipe_prof[4] = (double)st64[1] * 1e-5; h->pipe_prof[5] = (double)st64[2] * 1e-5;   // 100 MHz ticks -> ms
-        h->pipe_prof[6] = (double)st64[3]; h->pipe_prof[7] = (double)h->h_pipe[12] + 1e-3 * (double)h->h_pipe[13];
+        return MPC_OK;
     }
-    if (!piped) {
-        // one launch per kernel: the poll table of this solve and (unless an asynchronous closed loop accumulates over its steps) the
-        // count of instances that do not converge start from zero -- the pipeline path keeps both in its control block
-        if (!h->async_loop) HIP_TRY(h, hipMemsetAsync(h->d_fail, 0, sizeof(uint32_t), stream));
-        if (pl.polled) HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int32_t) * MAX_GROUPS * MAX_POLL_IT, stream));
-        if (G > 1) {     // the sub-streams were forked before these memsets were enqueued
-            HIP_TRY(h, hipEventRecord(h->ev_fork, stream));
-            for (int g = 0; g < G; ++g) HIP_TRY(h, hipStreamWaitEvent(h->sub_stream[g], h->ev_fork, 0));
-        }
+    // (no kernel behind the loop: the rows are out -- Params::emit -- and k_solve_wg has left the block's head in h_pipe; a pipeline that
+    //  runs its tiles to the end, option hybrid = 0, has no such epilogue: a copy command)
+    if (pl.hand <= 0) HIP_TRY(h, hipMemcpyAsync(h->h_pipe, s.ctl + PIPE_ABORT, PH_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, wait_stream(h, stream));
+    if (s.t_wtrace.p) (void)report_stamps(s.t_wtrace.as<unsigned long long>(), (size_t)4 * s.n_wtrace, [&](const unsigned long long* r) { return format_wg_trace(r, s.n_wtrace); });
+    read_head(s);
+    const uint32_t* hd = h->h_pipe;
+    if (hd[PH_ABORT] != 0u) {
+        // a bounded wait ran out (e.g. the dispatcher left an XCD without stage workers): the workspace is part-way
+        // through an iteration, so start over with one launch per kernel.  Once may be a transient of the machine's other tenants (the
+        // workgroups of a collective spinning on a slow peer, another handle's persistent launch); the handle stays on that path when it
+        // has happened PIPE_ABORTS_MAX times
+        h->pipe_disabled = true;
+        h->resc_in_kernel = h->resc_ran = false;         // (the k_solve_wg behind the abandoned launch returned at once: no instance has had its second chance)
+        // (abort word: 1 option pipe_test_abort, 2 a Riccati worker waited for its tile's stage items [tile << 16 | round; arrivals], 3 a helping
+        //  Riccati worker / 4 a stage worker waited for its queue slot [ticket; queue tail]; then the PH_DETAIL words)
+        fprintf(stderr, "[mpcgpu] single-launch pipeline abandoned (bounded wait expired: code %u, %u / %u, a millisecond later %u, waited %u ticks); re-running with one launch per kernel\n",
+                hd[PH_ABORT], hd[PH_DETAIL], hd[PH_DETAIL + 1], hd[PH_DETAIL + 2], hd[PH_DETAIL + 3]);
+        report_arrivals(s.ctl, pl.ntiles, A.items);
+        return PIPE_ABANDONED;
     }
-    while (!piped && it < pl.cap) {
+    P.DBG = nullptr;
+    if (t_pdbg.p) HIP_TRY(h, report_stamps(t_pdbg.as<unsigned long long>(), (size_t)STAMP_SLOTS * h->n_cu, [&](const unsigned long long* r) { return format_pipe_timing(r, h->n_cu); }));
+    h->last_mode = 1;
+    return MPC_OK;
+}
+
+// row `row` of the caller's per-iteration trace (mpc_solve_batch_trace; null: none) through its device copy
+static int record_trace(const Solve& s, double* trace, int32_t trace_rows, int row, double* d_trace) {
+    if (!trace || row >= trace_rows) return MPC_OK;
+    hipLaunchKernelGGL(k_gather_trace, dim3((s.B + 255) / 256), dim3(256), 0, s.stream, s.h->d_ws + s.w.SC * 64, (uint32_t)s.w.tile_elems, s.B, d_trace);
+    HIP_TRY(s.h, hipStreamSynchronize(s.stream));
+    HIP_TRY(s.h, hipMemcpy(trace + (size_t)row * 8 * s.B, d_trace, sizeof(double) * 8 * (size_t)s.B, hipMemcpyDeviceToHost));
+    return MPC_OK;
+}
+// one launch per kernel and iteration, then k_egest.
+// Convergence polling: every stage launch adds the number of instances it leaves running to its own device counter;
+// after each chunk the last counter is copied to pinned memory.  The host looks at the poll of chunk c-1 only after
+// chunk c is enqueued, so the GPU never idles on a host round trip; the price is one chunk of early-exit launches
+// (a few microseconds each) at the very end.
+template <int NX> static int solve_per_kernel(Solve& s, double* trace, int32_t trace_rows) {
+    mpc_handle* h = s.h;
+    const mpc_problem_desc& d = h->hp.desc;
+    const SolvePlan& pl = s.pl;
+    const int B = s.B, G = pl.G, nblk = pl.nblk;
+    hipStream_t stream = s.stream; Params& P = s.P;
+    int& it = s.it;
+    DevTmp t_trace, t_dbg;               // the trace's device copy; stamps of option timing = 1 (third / fourth iteration)
+    if (trace) HIP_TRY(h, hipMalloc(&t_trace.p, sizeof(double) * 8 * (size_t)B));
+    if (pl.stage_timing) HIP_TRY(h, stamp_rows(t_dbg, nblk, stream));
+    unsigned long long* const d_dbg = t_dbg.as<unsigned long long>();
+    // the poll table of this solve and (unless an asynchronous closed loop accumulates over its steps) the count of instances that do not
+    // converge start from zero -- the other paths keep both in their control block
+    if (!h->async_loop) HIP_TRY(h, hipMemsetAsync(h->d_fail + FAIL_COUNT, 0, sizeof(uint32_t), stream));
+    if (pl.polled) HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int32_t) * MAX_GROUPS * MAX_POLL_IT, stream));
+    if (G > 1) {     // the sub-streams were forked before these memsets were enqueued
+        HIP_TRY(h, hipEventRecord(h->ev_fork, stream));
+        for (int g = 0; g < G; ++g) HIP_TRY(h, hipStreamWaitEvent(h->sub_stream[g], h->ev_fork, 0));
+    }
+    int chunk_id = 0, rc;
+    while (it < pl.cap) {
         const int n = std::min(trace ? 1 : pl.chunk, pl.cap - it);
         bool any = false;
         for (int j = 0; j < n; ++j) {
             for (int g = 0; g < G; ++g) {                 // interleave the groups launch by launch
-                const Group& q = grp[g];
+                const Group& q = s.grp[g];
                 if (!q.running) continue;
                 any = true;
                 Params Pg = P;
                 Pg.tile0 = q.tile0;
-                prof.begin(0, q.st);
+                s.prof.next(0, q.st);
                 if (pl.stage_timing && it + j == 3) Pg.DBG = d_dbg + (size_t)8 * nblk;   // Riccati stamps of the 4th iteration
                 hipLaunchKernelGGL((k_riccati<NX>), dim3(q.ntl), dim3(192), pl.ric_lds, q.st, Pg);
-                Pg.DBG = nullptr;
-                prof.end(q.st);
-                prof.begin(1, q.st);
+                s.prof.end(q.st);
+                s.prof.next(1, q.st);
                 P.DBG = (pl.stage_timing && it + j == 2) ? d_dbg : nullptr;      // stamp the third iteration
                 P.run_counter = pl.polled ? h->d_counter + (size_t)g * MAX_POLL_IT + (it + j) : nullptr;
-                launch_stage(q, false);
+                launch_stage<NX>(s, q, false);
                 P.run_counter = nullptr;
-                prof.end(q.st);
+                s.prof.end(q.st);
             }
-            if (trace) { rc = record_trace(it + j); if (rc) return rc; }
+            if ((rc = record_trace(s, trace, trace_rows, it + j, t_trace.as<double>()))) return rc;
         }
         it += n;
         if (!any) break;
         if (!pl.polled) {
             if (trace) {                                  // trace mode: exact stop, one synchronous count per iteration
                 HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int32_t), stream));
-                hipLaunchKernelGGL(k_count_running, dim3((B + 255) / 256), dim3(256), 0, stream, h->d_iws, (uint32_t)w.itile_elems, 0, B, h->d_counter);
+                hipLaunchKernelGGL(k_count_running, dim3((B + 255) / 256), dim3(256), 0, stream, h->d_iws, (uint32_t)s.w.itile_elems, 0, B, h->d_counter);
                 HIP_TRY(h, hipMemcpyAsync(h->h_counter, h->d_counter, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
                 HIP_TRY(h, hipStreamSynchronize(stream));
                 if (h->h_counter[0] == 0) break;
@@ -3512,7 +3322,7 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         }
         const int slot = chunk_id & 1;
         for (int g = 0; g < G; ++g) {
-            const Group& q = grp[g];
+            const Group& q = s.grp[g];
             if (!q.running) continue;
             HIP_TRY(h, hipMemcpyAsync(h->h_counter + 2 * g + slot, h->d_counter + (size_t)g * MAX_POLL_IT + (it - 1), sizeof(int32_t),
                                       hipMemcpyDeviceToHost, q.st));
@@ -3521,7 +3331,7 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         if (chunk_id >= 1) {                              // look at the PREVIOUS chunk's poll (this chunk is already in the queue)
             bool still = false;
             for (int g = 0; g < G; ++g) {
-                Group& q = grp[g];
+                Group& q = s.grp[g];
                 if (!q.running) continue;
                 HIP_TRY(h, hipEventSynchronize(h->ev_poll[g][slot ^ 1]));
                 if (h->h_counter[2 * g + (slot ^ 1)] == 0) q.running = false; else still = true;
@@ -3531,29 +3341,51 @@ static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const do
         ++chunk_id;
     }
     P.DBG = nullptr;
-    if (trace) { rc = record_trace(it); if (rc) return rc; }
-    if (pl.stage_timing) { rc = report_stage_timing(h, stream, d_dbg, nblk, ntiles); if (rc) return rc; }
-    if (n_it_out) *n_it_out = it;
+    if ((rc = record_trace(s, trace, trace_rows, it, t_trace.as<double>()))) return rc;
+    if (pl.stage_timing)
+        HIP_TRY(h, report_stamps(d_dbg, (size_t)STAMP_SLOTS * nblk, [&](const unsigned long long* r) { return format_stage_timing(r, nblk, pl.ntiles); }, stream));
     for (int g = 0; g < G; ++g) {
-        const Group& q = grp[g];
-        if (q.b1 <= q.b0 || piped) continue;          // (pipeline: already enqueued behind the launch)
+        const Group& q = s.grp[g];
+        if (q.b1 <= q.b0) continue;
         Params Pg = P;
         Pg.tile0 = q.tile0;
-        prof.begin(2, q.st);
-        hipLaunchKernelGGL((k_egest<NX>), dim3(q.ntl, (2 * d.N + NX * (d.N + 1) + 63) / 64), dim3(256), 0, q.st, Pg, (const uint32_t*)nullptr, h->d_fail, (uint32_t*)nullptr, 0u);
-        prof.end(q.st);
+        s.prof.next(2, q.st);
+        hipLaunchKernelGGL((k_egest<NX>), dim3(q.ntl, (2 * d.N + NX * (d.N + 1) + 63) / 64), dim3(256), 0, q.st, Pg, (const uint32_t*)nullptr, h->d_fail + FAIL_COUNT, (uint32_t*)nullptr, 0u);
+        s.prof.end(q.st);
         if (G > 1) {
             HIP_TRY(h, hipEventRecord(h->ev_join[g], q.st));
             HIP_TRY(h, hipStreamWaitEvent(stream, h->ev_join[g], 0));
         }
     }
+    HIP_TRY(h, hipMemcpyAsync(h->h_fail, h->d_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    return MPC_OK;
+}
+
+template <int NX>
+static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst,
+                          double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream,
+                          double* trace, int32_t trace_rows, int32_t* n_it_out, bool in_rescue) {
+    Solve s{h, stream, B, in_rescue}; s.prof.h = h; s.prof.s = stream;
+    PlanState ps = plan_state(h, B, d_obst != nullptr, trace != nullptr, in_rescue);
+    s.pl = plan_solve(h->hp, h->knobs, ps);
+    // tile-major layout: the rows of a tile do not depend on the batch size, so a smaller batch lives in the first tiles of
+    // a larger allocation (grow-only; the rescue path alternates between the full batch and a failed subset)
+    int rc = ensure_ws(h, (size_t)s.pl.ntiles * 64, s.pl.mailbox); if (rc) return rc;
+    if (ps.ws_mailbox != h->ws_mailbox) { ps.ws_mailbox = h->ws_mailbox; s.pl = plan_solve(h->hp, h->knobs, ps); }
+    if ((rc = solve_front<NX>(s, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt))) return rc;
+    rc = s.pl.res_path ? solve_wg_alone<NX>(s) : s.pl.pipe_path ? solve_pipeline<NX>(s) : solve_per_kernel<NX>(s, trace, trace_rows);
+    if (rc == PIPE_ABANDONED) {          // (pipe_disabled: the second call plans one launch per kernel)
+        rc = solve_dev_impl<NX>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it_out, in_rescue);
+        if (++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;
+        return rc;
+    }
+    if (rc || h->async_ok) return rc;
+    // the back: iterations for the caller, the spans of the profile
+    if (n_it_out) *n_it_out = s.it;
     HIP_TRY(h, hipGetLastError());
-    h->prof[5] = it;
-    if (!piped) HIP_TRY(h, hipMemcpyAsync(h->h_fail, h->d_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (d.fixed_iters <= 0 || h->profiling) HIP_TRY(h, hipStreamSynchronize(stream));
-    const double its = it;
-    prof.collect();
-    h->prof[5] = its;
+    if (h->hp.desc.fixed_iters <= 0 || h->profiling) HIP_TRY(h, hipStreamSynchronize(stream));
+    s.prof.collect();
+    h->prof[5] = s.it;
     return MPC_OK;
 }
 
@@ -3726,8 +3558,8 @@ static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double*
     // (converged mode: the solve has synchronised the stream; a launch of k_solve_wg with the second chance inside has given every stalled
     //  instance its levels already)
     // (what the next solve of this handle does about stalled instances: see resc_cond in plan_solve)
-    if (rc == MPC_OK && pl.rescue && !h->async_ok) h->resc_hint = h->h_fail[0] != 0u || h->rescued_last > 0;
-    if (rc != MPC_OK || !pl.rescue || h->h_fail[0] == 0u || h->resc_in_kernel) return rc;
+    if (rc == MPC_OK && pl.rescue && !h->async_ok) h->resc_hint = h->h_fail[FAIL_COUNT] != 0u || h->rescued_last > 0;
+    if (rc != MPC_OK || !pl.rescue || h->h_fail[FAIL_COUNT] == 0u || h->resc_in_kernel) return rc;
     double prof_keep[6], pipe_keep[8];
     const int mode_keep = h->last_mode;
     memcpy(prof_keep, h->prof, sizeof prof_keep);
@@ -4006,8 +3838,8 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
     // step by step with the host in between (the per-kernel path polls for convergence, the second chance needs the count).
     bool replay = true, loop_abandoned = false;
     if (plan_solve(h->hp, h->knobs, plan_state(h, B, false, false, false)).loop_async) {
-        HIP_TRY(h, hipMemsetAsync(h->d_fail, 0, 2 * sizeof(uint32_t), stream));
-        A.abort_flag = h->d_fail + 1;
+        HIP_TRY(h, hipMemsetAsync(h->d_fail, 0, FAIL_WORDS * sizeof(uint32_t), stream));
+        A.abort_flag = h->d_fail + FAIL_LOOP_ABORT;
         hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
         h->async_loop = true;
         bool all_async = true;
@@ -4019,10 +3851,10 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
         }
         h->async_loop = false;
         if (all_async) {
-            HIP_TRY(h, hipMemcpyAsync(h->h_fail, h->d_fail, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(h, hipMemcpyAsync(h->h_fail, h->d_fail, FAIL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             HIP_TRY(h, hipStreamSynchronize(stream));
-            replay = h->h_fail[0] != 0u || h->h_fail[1] != 0u;
-            if (h->h_fail[1] != 0u) {
+            replay = h->h_fail[FAIL_COUNT] != 0u || h->h_fail[FAIL_LOOP_ABORT] != 0u;
+            if (h->h_fail[FAIL_LOOP_ABORT] != 0u) {
                 h->pipe_disabled = true;
                 loop_abandoned = true;
                 fprintf(stderr, "[mpcgpu] closed loop: a pipeline launch was abandoned (bounded wait expired); replaying the loop with one launch per kernel\n");

@@ -182,12 +182,14 @@ def gpu_workers(p, n_cu):
 @pytest.mark.parametrize("row", GPU_ROWS, ids=[r[0] for r in GPU_ROWS])
 def test_plan_is_what_the_library_runs(row):
     """one solve per row: the library's pipeline / resident profiles against emu_solve_plan for this device (collision avoidance with
-    option rescue = 0: the levels of the second chance behind the launch would overwrite the resident profile)"""
+    option rescue = 0: the levels of the second chance behind the launch would overwrite the resident profile).  Where k_solve_wg serves
+    the batch alone, its counters in the control block are the caller's iteration counts: instance-rounds their sum, the rounds of the
+    slowest workgroup their maximum"""
     import torch
     _, fam, B, opts, state, _ = row
     opts = dict(opts, **({"rescue": "0"} if fam == "ca" else {}))
     n_cu = torch.cuda.get_device_properties(0).multi_processor_count
-    p, _ = last_chunk(fam, B, opts, n_cu=n_cu, xcd_mask=0xFF, **state)
+    p, chunk = last_chunk(fam, B, opts, n_cu=n_cu, xcd_mask=0xFF, **state)
     cfg = CFGS[fam]
     kw = dict(fixed_iters=int(opts["fixed_iters"])) if "fixed_iters" in opts else {}
     s = make_solver(cfg, **kw)
@@ -205,3 +207,9 @@ def test_plan_is_what_the_library_runs(row):
     assert rp["ran"] == (p["path"] == "wg" or (p["path"] == "pipe" and p["hand"] > 0))
     if rp["ran"]:
         assert rp["workgroups"] == p["wg_grid"]
+    if p["path"] == "wg" and fam != "ca":
+        # k_solve_wg alone: its counters against the iteration counts the caller gets (of the call's last chunk: what the profile describes)
+        it = r.iters[(B - 1) // chunk * chunk:]
+        print(row[0], "iters sum", int(it.sum()), "max", int(it.max()))
+        assert rp["instance_iterations"] == int(it.sum())
+        assert rp["rounds"] == int(it.max())
