@@ -41,14 +41,57 @@ class MpcProblemDesc(C.Structure):
     ]
 
 
-EXPORTS = [
-    "mpc_default_desc", "mpc_create", "mpc_destroy", "mpc_last_error", "mpc_set_bounds", "mpc_solve_batch",
-    "mpc_solve_batch_dev", "mpc_plant_step", "mpc_set_profiling", "mpc_get_profile", "mpc_solve_batch_trace",
-    "mpc_abi_version", "mpc_closed_loop_batch", "mpc_closed_loop_batch_dev", "mpc_metrics_batch", "mpc_forces_stage_eval", "mpc_forces_solve_batch",
-    "mpc_get_pipeline_profile", "mpc_get_resident_profile", "mpc_measure_copy_bandwidth", "mpc_get_option", "mpc_plant_step_dev", "mpc_metrics_batch_dev", "mpc_forces_solve_batch_dev", "mpc_set_option", "mpc_last_rescued", "mpc_closed_loop_batch_ex", "mpc_closed_loop_batch_dev_ex", "mpc_last_loop_replayed", "mpc_validity_batch", "mpc_validity_batch_dev", "mpc_forces_closed_loop_batch", "mpc_forces_closed_loop_batch_dev",
-    "mpc_eval_nlp_batch", "mpc_eval_nlp_batch_dev", "mpc_solve_batch_ex", "mpc_solve_batch_dev_ex",
-    "mpc_solve_batch_sens", "mpc_solve_batch_sens_dev", "mpc_sens_adjoint", "mpc_sens_adjoint_dev",
-]
+_vp, _i32, _f64, _u64 = C.c_void_p, C.c_int32, C.c_double, C.c_uint64
+_desc_p = C.POINTER(MpcProblemDesc)
+_rows = [_dp, _dp, _dp, _dp, _ip, _ip, _dp]          # x0, p, obst, x_out, status, iters, kkt of a host-pointer solve
+_loop_tail = [_i32, _f64, _u64]                      # noise_mode, sigma, seed
+
+# the prototypes of include/mpcgpu.h: name -> argument types (device-pointer forms take void*; the last void* of a _dev form is the stream)
+PROTOTYPES = {
+    "mpc_default_desc": [_desc_p, _i32, _i32],
+    "mpc_create": [C.POINTER(_vp), _desc_p],
+    "mpc_destroy": [_vp],
+    "mpc_last_error": [_vp],
+    "mpc_abi_version": [],
+    "mpc_set_bounds": [_vp, _dp, _dp, _dp, _dp],
+    "mpc_set_profiling": [_vp, _i32],
+    "mpc_set_option": [_vp, C.c_char_p, C.c_char_p],
+    "mpc_get_option": [_vp, C.c_char_p, C.POINTER(C.c_int64)],
+    "mpc_get_profile": [_vp, _dp],
+    "mpc_get_pipeline_profile": [_vp, _dp],
+    "mpc_get_resident_profile": [_vp, _dp],
+    "mpc_measure_copy_bandwidth": [_vp, C.c_size_t, _i32, _dp],
+    "mpc_last_rescued": [_vp],
+    "mpc_last_loop_replayed": [_vp],
+    "mpc_solve_batch": [_vp, _i32] + _rows,
+    "mpc_solve_batch_dev": [_vp, _i32] + [_vp] * 8,
+    "mpc_solve_batch_trace": [_vp, _i32] + _rows + [_dp, _i32, _ip],
+    "mpc_eval_nlp_batch": [_vp, _i32] + [_dp] * 5,
+    "mpc_eval_nlp_batch_dev": [_vp, _i32] + [_vp] * 6,
+    "mpc_solve_batch_ex": [_vp, _i32] + _rows + [_dp] * 4,
+    "mpc_solve_batch_dev_ex": [_vp, _i32] + [_vp] * 12,
+    "mpc_solve_batch_sens": [_vp, _i32] + _rows + [_dp] * 5 + [_i32, _dp, _dp],
+    "mpc_solve_batch_sens_dev": [_vp, _i32] + [_vp] * 12 + [_i32, _vp, _vp, _vp],
+    "mpc_sens_adjoint": [_vp, _i32, _dp, _dp],
+    "mpc_sens_adjoint_dev": [_vp, _i32, _vp, _vp, _vp],
+    "mpc_plant_step": [_vp, _i32, _i32, _dp, _dp, _dp],
+    "mpc_plant_step_dev": [_vp, _i32, _i32] + [_vp] * 4,
+    "mpc_closed_loop_batch": [_vp, _i32, _i32, _i32] + [_dp] * 6 + [_ip],
+    "mpc_closed_loop_batch_dev": [_vp, _i32, _i32, _i32] + [_vp] * 8,
+    "mpc_closed_loop_batch_ex": [_vp, _i32, _i32, _i32] + [_dp] * 4 + _loop_tail + [_dp, _dp, _ip],
+    "mpc_closed_loop_batch_dev_ex": [_vp, _i32, _i32, _i32] + [_vp] * 4 + _loop_tail + [_vp] * 4,
+    "mpc_metrics_batch": [_vp, _i32, _i32, _i32, _dp, _dp, _dp, _f64, _i32, _dp, _dp, _dp],
+    "mpc_metrics_batch_dev": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _i32] + [_vp] * 4,
+    "mpc_validity_batch": [_vp, _i32, _i32, _dp, _f64, _f64, _i32, _dp, _i32, _dp, _i32, _dp, _ip, _ip],
+    "mpc_validity_batch_dev": [_vp, _i32, _i32, _vp, _f64, _f64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp],
+    "mpc_forces_stage_eval": [_vp, _i32, _i32] + [_dp] * 8,
+    "mpc_forces_solve_batch": [_vp, _i32] + [_dp] * 7 + [_i32, _dp, _ip, _ip, _dp],
+    "mpc_forces_solve_batch_dev": [_vp, _i32, _vp, _vp, _vp, _dp, _dp, _dp, _dp, _i32] + [_vp] * 5,
+    "mpc_forces_closed_loop_batch": [_vp, _i32, _i32, _i32] + [_dp] * 9 + [_i32] + _loop_tail + [_dp, _dp, _ip],
+    "mpc_forces_closed_loop_batch_dev": [_vp, _i32, _i32, _i32] + [_vp] * 5 + [_dp] * 4 + [_i32] + _loop_tail + [_vp] * 4,
+}
+RESTYPES = {"mpc_default_desc": None, "mpc_last_error": C.c_char_p, "mpc_abi_version": C.c_int}       # every other entry point returns an int code
+EXPORTS = list(PROTOTYPES)
 
 
 class MpcLibraryError(RuntimeError):
@@ -80,91 +123,9 @@ def load_library(path: str | None = None):
         L = C.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise MpcLibraryError(f"cannot load {path}: {e}") from e
-    vp = C.c_void_p
-    L.mpc_default_desc.argtypes = [C.POINTER(MpcProblemDesc), C.c_int32, C.c_int32]
-    L.mpc_default_desc.restype = None
-    L.mpc_create.argtypes = [C.POINTER(vp), C.POINTER(MpcProblemDesc)]
-    L.mpc_create.restype = C.c_int
-    L.mpc_destroy.argtypes = [vp]
-    L.mpc_destroy.restype = C.c_int
-    L.mpc_last_error.argtypes = [vp]
-    L.mpc_last_error.restype = C.c_char_p
-    L.mpc_set_bounds.argtypes = [vp, _dp, _dp, _dp, _dp]
-    L.mpc_set_bounds.restype = C.c_int
-    L.mpc_solve_batch.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip, _dp]
-    L.mpc_solve_batch.restype = C.c_int
-    L.mpc_solve_batch_dev.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_solve_batch_dev.restype = C.c_int
-    L.mpc_plant_step.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp, _dp]
-    L.mpc_plant_step.restype = C.c_int
-    L.mpc_set_profiling.argtypes = [vp, C.c_int32]
-    L.mpc_set_profiling.restype = C.c_int
-    L.mpc_get_profile.argtypes = [vp, _dp]
-    L.mpc_get_profile.restype = C.c_int
-    L.mpc_get_pipeline_profile.argtypes = [vp, _dp]
-    L.mpc_get_pipeline_profile.restype = C.c_int
-    L.mpc_get_resident_profile.argtypes = [vp, _dp]
-    L.mpc_get_resident_profile.restype = C.c_int
-    L.mpc_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
-    L.mpc_get_option.restype = C.c_int
-    L.mpc_measure_copy_bandwidth.argtypes = [vp, C.c_size_t, C.c_int32, _dp]
-    L.mpc_measure_copy_bandwidth.restype = C.c_int
-    L.mpc_solve_batch_trace.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, C.c_int32, _ip]
-    L.mpc_solve_batch_trace.restype = C.c_int
-    L.mpc_closed_loop_batch.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _ip]
-    L.mpc_closed_loop_batch.restype = C.c_int
-    L.mpc_closed_loop_batch_dev.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_closed_loop_batch_dev.restype = C.c_int
-    L.mpc_metrics_batch.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_int32, _dp, _dp, _dp]
-    L.mpc_metrics_batch.restype = C.c_int
-    L.mpc_forces_stage_eval.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
-    L.mpc_forces_stage_eval.restype = C.c_int
-    L.mpc_forces_solve_batch.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _ip, _ip, _dp]
-    L.mpc_forces_solve_batch.restype = C.c_int
-    L.mpc_plant_step_dev.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
-    L.mpc_plant_step_dev.restype = C.c_int
-    L.mpc_metrics_batch_dev.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_double, C.c_int32, vp, vp, vp, vp]
-    L.mpc_metrics_batch_dev.restype = C.c_int
-    L.mpc_forces_solve_batch_dev.argtypes = [vp, C.c_int32, vp, vp, vp, _dp, _dp, _dp, _dp, C.c_int32, vp, vp, vp, vp, vp]
-    L.mpc_forces_solve_batch_dev.restype = C.c_int
-    L.mpc_set_option.argtypes = [vp, C.c_char_p, C.c_char_p]
-    L.mpc_set_option.restype = C.c_int
-    L.mpc_closed_loop_batch_ex.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_int32, C.c_double, C.c_uint64, _dp, _dp, _ip]
-    L.mpc_closed_loop_batch_ex.restype = C.c_int
-    L.mpc_closed_loop_batch_dev_ex.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_double, C.c_uint64, vp, vp, vp, vp]
-    L.mpc_closed_loop_batch_dev_ex.restype = C.c_int
-    L.mpc_last_loop_replayed.argtypes = [vp]
-    L.mpc_last_loop_replayed.restype = C.c_int
-    L.mpc_validity_batch.argtypes = [vp, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp, _ip, _ip]
-    L.mpc_validity_batch.restype = C.c_int
-    L.mpc_validity_batch_dev.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_double, C.c_double, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
-    L.mpc_validity_batch_dev.restype = C.c_int
-    L.mpc_forces_closed_loop_batch.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32,
-                                               C.c_double, C.c_uint64, _dp, _dp, _ip]
-    L.mpc_forces_closed_loop_batch.restype = C.c_int
-    L.mpc_forces_closed_loop_batch_dev.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32,
-                                                   C.c_double, C.c_uint64, vp, vp, vp, vp]
-    L.mpc_forces_closed_loop_batch_dev.restype = C.c_int
-    L.mpc_last_rescued.argtypes = [vp]
-    L.mpc_last_rescued.restype = C.c_int
-    L.mpc_eval_nlp_batch.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _dp]
-    L.mpc_eval_nlp_batch.restype = C.c_int
-    L.mpc_eval_nlp_batch_dev.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp]
-    L.mpc_eval_nlp_batch_dev.restype = C.c_int
-    L.mpc_solve_batch_ex.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
-    L.mpc_solve_batch_ex.restype = C.c_int
-    L.mpc_solve_batch_dev_ex.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_solve_batch_dev_ex.restype = C.c_int
-    L.mpc_solve_batch_sens.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp]
-    L.mpc_solve_batch_sens.restype = C.c_int
-    L.mpc_solve_batch_sens_dev.argtypes = [vp, C.c_int32] + [vp] * 12 + [C.c_int32, vp, vp, vp]
-    L.mpc_solve_batch_sens_dev.restype = C.c_int
-    L.mpc_sens_adjoint.argtypes = [vp, C.c_int32, _dp, _dp]
-    L.mpc_sens_adjoint.restype = C.c_int
-    L.mpc_sens_adjoint_dev.argtypes = [vp, C.c_int32, vp, vp, vp]
-    L.mpc_sens_adjoint_dev.restype = C.c_int
-    L.mpc_abi_version.argtypes = []
-    L.mpc_abi_version.restype = C.c_int
+    for name, argtypes in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = argtypes, RESTYPES.get(name, C.c_int)
     if path == LIB_PATH:
         _lib = L
     return L

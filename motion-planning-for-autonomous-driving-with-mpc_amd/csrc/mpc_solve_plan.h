@@ -390,4 +390,30 @@ inline SolvePlan plan_solve(const HostProblem& hp, const Knobs& kn, const PlanSt
     return hp.desc.nx == 5 ? plan_solve_nx<5>(hp, kn, st) : plan_solve_nx<6>(hp, kn, st);
 }
 
+// ---- the rows of one batched solve of B instances as the host solve chain of mpcgpu.hip passes them on: device pointers inside the chain, host
+//      pointers at a host-pointer entry point; null: not given / not asked for.  A new per-solve buffer is a member here, its width in rows()
+//      and a line at the entry point that accepts it.
+struct SolveIo {
+    int32_t B = 0;
+    const double *x0 = nullptr, *p = nullptr, *obst = nullptr;      // start point, parameters [U_ref | X_ref], obstacle centres
+    double *x_out = nullptr, *kkt = nullptr;                        // written: the optimum, the KKT error at exit, how the solve ended, ...
+    int32_t *status = nullptr, *iters = nullptr;
+    double *lam_g = nullptr, *lam_x = nullptr;                      // ... the multipliers of the final iterate (mpc_solve_batch[_dev]_ex)
+    double* snap = nullptr;                                         // ... the snapshot of the final iterates (mpc_solve_batch_sens[_dev], mpc_sens.h)
+    size_t n_w = 0, n_g = 0, snap_len = 0;                          // HostProblem::n_w(), n_g(); Sens<NX>::len(N)
+    // mpc_solve_batch_trace: per-iteration rows [rows, 8, B] on the HOST, the iterations done (a trace call is never cut into chunks)
+    struct Trace { double* out = nullptr; int32_t rows = 0; int32_t* n_it = nullptr; } trace;
+    // Instances off .. off + n - 1.  THE table of the members' widths in elements per instance: staging sizes and the layout of the second
+    // chance's sub-batch are differences of the pointers this returns.
+    SolveIo rows(size_t off, int32_t n) const {
+        SolveIo r = *this;
+        r.B = n; r.trace = Trace{};
+        skip(r.x0, off * n_w); skip(r.p, off * n_w); skip(r.obst, off * 6);
+        skip(r.x_out, off * n_w); skip(r.status, off * 1); skip(r.iters, off * 1); skip(r.kkt, off * 1);
+        skip(r.lam_g, off * n_g); skip(r.lam_x, off * n_w); skip(r.snap, off * snap_len);
+        return r;
+    }
+    template <class T> static void skip(T*& q, size_t elems) { if (q) q += elems; }
+};
+
 }  // namespace mpc

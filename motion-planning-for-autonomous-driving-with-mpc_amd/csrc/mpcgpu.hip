@@ -2544,13 +2544,13 @@ __global__ void k_plant_step(const Params Pk, const double* x, const double* u, 
 enum Scratch : int {
     SCR_STAGING,                        // stage_host: the device copies of a host-pointer call's buffers (the outermost call only)
     SCR_METRICS_OBST,                   // mpc_metrics_batch_dev: the descriptor's obstacle row
-    SCR_SOLVE_STATUS,                   // solve_dev: the status rows the second chance reads when the caller did not ask for them
-    SCR_HO_LIST,                        // solve_dev_impl: hand-over lists of the hybrid solve
+    SCR_STATUS,                         // supply_status: the status rows of a solve whose caller did not ask for them (the outermost level that needs them)
+    SCR_HO_LIST,                        // solve_pipeline: hand-over lists of the hybrid solve
     SCR_RESC_IDX, SCR_RESC_BUF,         // rescue_dev: open instances + their count; the sub-batch's rows
     SCR_RESC_MULT,                      // rescue_dev: multipliers of the sub-batch's last level
-    SCR_EX_STATUS, SCR_EX_LAM,          // solve_ex_dev: status / the multiplier rows (lam_g or lam_x) the caller did not ask for
-    SCR_SENS_SNAP,                      // mpc_solve_batch_sens_dev: snapshot of the final iterates (read again by mpc_sens_adjoint_dev)
-    SCR_SENS_STATUS, SCR_SENS_LAM_G,    // mpc_solve_batch_sens_dev: status / lam_g the caller did not ask for
+    SCR_EX_LAM,                         // solve_ex_dev: the multiplier rows (lam_g or lam_x) the caller did not ask for
+    SCR_SENS_SNAP,                      // solve_sens_dev: snapshot of the final iterates (read again by mpc_sens_adjoint_dev)
+    SCR_SENS_LAM_G,                     // solve_sens_dev: lam_g for lam_p when the caller did not ask for it (live beside SCR_EX_LAM, then lam_x)
     SCR_SENS_F,                         // sens_launch: the factors of the KKT matrices
     SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
     SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
@@ -2655,6 +2655,49 @@ struct DevTmp {
         }                                                                                             \
     } while (0)
 
+// `...` once with NX = the handle's state dimension: a launch of a kernel template, a call of a host template
+#define FOR_NX(h, ...) \
+    do { if ((h)->hp.desc.nx == 5) { constexpr int NX = 5; __VA_ARGS__; } else { constexpr int NX = 6; __VA_ARGS__; } } while (0)
+
+// Params of a kernel that reads and writes caller rows of B instances, with the handle's workspace (what its last solve left) or without
+static Params rows_params(const mpc_handle* h, int32_t B, bool ws) {
+    Params P;
+    fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, ws ? h->d_ws : nullptr, ws ? h->d_iws : nullptr, h->d_LB, h->d_UB, ws && h->ws_mailbox);
+    return P;
+}
+// the grid of the kernels that run one thread per stage, NLP_OUT_THREADS / (N + 1) instances per workgroup
+static dim3 nlp_out_grid(const mpc_handle* h, int32_t B) { const int ipb = NLP_OUT_THREADS / (h->hp.desc.N + 1); return dim3((B + ipb - 1) / ipb); }
+static Params plant_params(const mpc_handle* h) { Params P{}; P.dt = h->hp.desc.dt; P.wheelbase = h->hp.desc.wheelbase; P.nx = h->hp.desc.nx; return P; }
+static size_t sens_len(const mpc_handle* h) { FOR_NX(h, return Sens<NX>::len(h->hp.desc.N)); }
+static int sens_fs(const mpc_handle* h) { FOR_NX(h, return Sens<NX>::FS); }
+
+// the rows of a solve of this handle: the caller's pointers go in at the entry point, the widths come from the handle
+static SolveIo solve_io(const mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out, int32_t* status,
+                        int32_t* iters, double* kkt, double* lam_g = nullptr, double* lam_x = nullptr) {
+    SolveIo io;
+    io.B = B; io.x0 = x0; io.p = p; io.obst = obst; io.x_out = x_out; io.status = status; io.iters = iters; io.kkt = kkt; io.lam_g = lam_g; io.lam_x = lam_x;
+    if (h) { io.n_w = h->hp.n_w(); io.n_g = h->hp.n_g(); io.snap_len = sens_len(h); }
+    return io;
+}
+// What every NLP solve starts with, once, at its entry point: the arguments, the handle's state (`refusal`: the entry point's own objection
+// to its other arguments), the device; from here on the snapshot of mpc_solve_batch_sens is no longer the last solve's.
+static int begin_solve(mpc_handle* h, const SolveIo& io, const char* refusal = nullptr, bool sens = false) {
+    if (!h) return MPC_ERR_INVALID;
+    if (io.B <= 0 || !io.x0 || !io.p || !io.x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
+    if (refusal) { h->err = refusal; return MPC_ERR_INVALID; }
+    if (sens && h->hp.desc.fixed_iters > 0) { h->err = "sensitivities need a solve to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
+    if ((io.lam_g || io.lam_x) && h->hp.desc.fixed_iters > 0) { h->err = "multipliers need a solve to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
+    if (!h->hp.bounds_set) { h->err = "mpc_set_bounds has not been called"; return MPC_ERR_STATE; }
+    h->snap_ok = false;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return MPC_OK;
+}
+// an internal status row for a level of the chain that reads the status when the caller gave none (every level below receives it)
+static int supply_status(mpc_handle* h, SolveIo& io) {
+    if (!io.status && !(io.status = static_cast<int32_t*>(scratch_get(h, SCR_STATUS, (size_t)io.B * 4)))) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    return MPC_OK;
+}
+
 // one buffer of a host-pointer call: the caller's pointer (null: not given -- the device twin sees null too), its size, copied in or out
 struct Stage { const void* host; size_t bytes; bool out; };
 // The host-pointer form of a call: the buffers laid out in the handle's staging slot, the inputs copied on the handle's stream, `dev` run with
@@ -2678,6 +2721,26 @@ static int stage_host(mpc_handle* h, const Stage (&bufs)[N], Dev&& dev) {
         if (d[i] && bufs[i].out) HIP_TRY(h, hipMemcpyAsync(const_cast<void*>(bufs[i].host), d[i], bufs[i].bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     return MPC_OK;
+}
+
+// The host-pointer form of a solve: the rows of `io` (sizes: what SolveIo::rows skips over B instances) and the buffers `more` staged, `dev` run
+// with the rows on the device, the device twins of `more` and the stream.
+#define IO_HOST_ROWS(X) X(x0, false) X(p, false) X(obst, false) X(x_out, true) X(status, true) X(iters, true) X(kkt, true) X(lam_g, true) X(lam_x, true)
+template <size_t M, class Dev>
+static int stage_solve(mpc_handle* h, const SolveIo& io, const Stage (&more)[M], Dev&& dev) {
+    const SolveIo end = io.rows((size_t)io.B, 0);
+    Stage st[9 + M], *q = st;
+#define X(m, out) *q++ = Stage{io.m, (size_t)((const char*)end.m - (const char*)io.m), out};
+    IO_HOST_ROWS(X)
+#undef X
+    std::copy(more, more + M, q);
+    return stage_host(h, st, [&](void** d, hipStream_t s) {
+        SolveIo dio = io;
+#define X(m, out) dio.m = static_cast<decltype(dio.m)>(*d++);
+        IO_HOST_ROWS(X)
+#undef X
+        return dev(dio, d, s);
+    });
 }
 
 static void free_ws(mpc_handle* h) {
@@ -2999,7 +3062,7 @@ template <int NX> static int set_lds_limits(mpc_handle* h, size_t ric_lds) {
 struct Group { int tile0, ntl, nblk, b0, b1; hipStream_t st; bool running; };
 // what the parts of a solve share, built once by solve_front
 struct Solve {
-    mpc_handle* h; hipStream_t stream; int32_t B; bool in_rescue;      // the call
+    mpc_handle* h; hipStream_t stream; SolveIo io; bool in_rescue;      // the call
     SolvePlan pl; Params P; WsLayout w; Prof prof; Group grp[MAX_GROUPS];
     // the control block of the loop kernels (mpc_solve_plan.h) -- one of the handle's two, which alternate: the start kernel of a solve zeroes the other
     uint32_t* ctl = nullptr;            // one for the next solve, the last workgroup of the loop copies the head of this one into the pinned block
@@ -3029,7 +3092,7 @@ template <int NX> static void launch_stage(const Solve& s, const Group& q, bool 
 // k_solve_wg: alone over every instance, or behind the pipeline (skip_if: its abort word) over the instances on the hand-over lists (list, list_n)
 template <int NX> static void launch_wg(Solve& s, const uint32_t* skip_if, const int32_t* list) {
     mpc_handle* h = s.h; const SolvePlan& pl = s.pl;
-    if (pl.wg_trace) (void)stamp_rows(s.t_wtrace, s.n_wtrace = (s.B + pl.hyb_bx - 1) / pl.hyb_bx, s.stream, 4);
+    if (pl.wg_trace) (void)stamp_rows(s.t_wtrace, s.n_wtrace = (s.io.B + pl.hyb_bx - 1) / pl.hyb_bx, s.stream, 4);
     Params Pw = s.P;
     Pw.bx = pl.hyb_bx;
     // (the last kernel of the solve: its last workgroup copies the head of the control block into the pinned host block)
@@ -3078,22 +3141,22 @@ static void read_head(Solve& s) {
 
 // the front: parameters, tile groups, buffers of the aids, control block; then caller's rows -> workspace, start-point safeguard, start iterate
 template <int NX>
-static int solve_front(Solve& s, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt) {
-    mpc_handle* h = s.h;
+static int solve_front(Solve& s) {
+    mpc_handle* h = s.h; const SolveIo& io = s.io;
     const mpc_problem_desc& d = h->hp.desc;
     const SolvePlan& pl = s.pl;
-    const int B = s.B, ntiles = pl.ntiles, G = pl.G;
+    const int B = s.io.B, ntiles = pl.ntiles, G = pl.G;
     const size_t Bp = (size_t)ntiles * 64;
     hipStream_t stream = s.stream; Params& P = s.P;
     fill_params(P, h->hp, B, Bp, pl.bx, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
     P.mbw_live = 0;
-    P.x0 = d_x0; P.p = d_p; P.x_out = d_x_out; P.status_out = d_status; P.iters_out = d_iters; P.kkt_out = d_kkt;
+    P.x0 = io.x0; P.p = io.p; P.x_out = io.x_out; P.status_out = io.status; P.iters_out = io.iters; P.kkt_out = io.kkt;
     s.w = ws_layout(d.N, d.nx, Bp, h->ws_mailbox);
     const WsLayout& w = s.w;
     h->async_ok = false;
-    if (d_obst) {
+    if (io.obst) {
         P.per_inst_obst = 1;
-        hipLaunchKernelGGL(k_transpose_obst, dim3((B + 255) / 256), dim3(256), 0, stream, d_obst, h->d_ws + w.OBST * 64, B, (uint32_t)w.tile_elems);
+        hipLaunchKernelGGL(k_transpose_obst, dim3((B + 255) / 256), dim3(256), 0, stream, io.obst, h->d_ws + w.OBST * 64, B, (uint32_t)w.tile_elems);
     }
     if (!h->attr_set) { const int rc = set_lds_limits<NX>(h, pl.ric_lds); if (rc) return rc; }
     for (int g = 0; g < G; ++g) {
@@ -3253,11 +3316,12 @@ template <int NX> static int solve_pipeline(Solve& s) {
 }
 
 // row `row` of the caller's per-iteration trace (mpc_solve_batch_trace; null: none) through its device copy
-static int record_trace(const Solve& s, double* trace, int32_t trace_rows, int row, double* d_trace) {
-    if (!trace || row >= trace_rows) return MPC_OK;
-    hipLaunchKernelGGL(k_gather_trace, dim3((s.B + 255) / 256), dim3(256), 0, s.stream, s.h->d_ws + s.w.SC * 64, (uint32_t)s.w.tile_elems, s.B, d_trace);
+static int record_trace(const Solve& s, int row, double* d_trace) {
+    double* const trace = s.io.trace.out;
+    if (!trace || row >= s.io.trace.rows) return MPC_OK;
+    hipLaunchKernelGGL(k_gather_trace, dim3((s.io.B + 255) / 256), dim3(256), 0, s.stream, s.h->d_ws + s.w.SC * 64, (uint32_t)s.w.tile_elems, s.io.B, d_trace);
     HIP_TRY(s.h, hipStreamSynchronize(s.stream));
-    HIP_TRY(s.h, hipMemcpy(trace + (size_t)row * 8 * s.B, d_trace, sizeof(double) * 8 * (size_t)s.B, hipMemcpyDeviceToHost));
+    HIP_TRY(s.h, hipMemcpy(trace + (size_t)row * 8 * s.io.B, d_trace, sizeof(double) * 8 * (size_t)s.io.B, hipMemcpyDeviceToHost));
     return MPC_OK;
 }
 // one launch per kernel and iteration, then k_egest.
@@ -3265,11 +3329,11 @@ static int record_trace(const Solve& s, double* trace, int32_t trace_rows, int r
 // after each chunk the last counter is copied to pinned memory.  The host looks at the poll of chunk c-1 only after
 // chunk c is enqueued, so the GPU never idles on a host round trip; the price is one chunk of early-exit launches
 // (a few microseconds each) at the very end.
-template <int NX> static int solve_per_kernel(Solve& s, double* trace, int32_t trace_rows) {
-    mpc_handle* h = s.h;
+template <int NX> static int solve_per_kernel(Solve& s) {
+    mpc_handle* h = s.h; const bool trace = s.io.trace.out != nullptr;
     const mpc_problem_desc& d = h->hp.desc;
     const SolvePlan& pl = s.pl;
-    const int B = s.B, G = pl.G, nblk = pl.nblk;
+    const int B = s.io.B, G = pl.G, nblk = pl.nblk;
     hipStream_t stream = s.stream; Params& P = s.P;
     int& it = s.it;
     DevTmp t_trace, t_dbg;               // the trace's device copy; stamps of option timing = 1 (third / fourth iteration)
@@ -3306,7 +3370,7 @@ template <int NX> static int solve_per_kernel(Solve& s, double* trace, int32_t t
                 P.run_counter = nullptr;
                 s.prof.end(q.st);
             }
-            if ((rc = record_trace(s, trace, trace_rows, it + j, t_trace.as<double>()))) return rc;
+            if ((rc = record_trace(s, it + j, t_trace.as<double>()))) return rc;
         }
         it += n;
         if (!any) break;
@@ -3341,7 +3405,7 @@ template <int NX> static int solve_per_kernel(Solve& s, double* trace, int32_t t
         ++chunk_id;
     }
     P.DBG = nullptr;
-    if ((rc = record_trace(s, trace, trace_rows, it, t_trace.as<double>()))) return rc;
+    if ((rc = record_trace(s, it, t_trace.as<double>()))) return rc;
     if (pl.stage_timing)
         HIP_TRY(h, report_stamps(d_dbg, (size_t)STAMP_SLOTS * nblk, [&](const unsigned long long* r) { return format_stage_timing(r, nblk, pl.ntiles); }, stream));
     for (int g = 0; g < G; ++g) {
@@ -3362,48 +3426,31 @@ template <int NX> static int solve_per_kernel(Solve& s, double* trace, int32_t t
 }
 
 template <int NX>
-static int solve_dev_impl(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst,
-                          double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream,
-                          double* trace, int32_t trace_rows, int32_t* n_it_out, bool in_rescue) {
-    Solve s{h, stream, B, in_rescue}; s.prof.h = h; s.prof.s = stream;
-    PlanState ps = plan_state(h, B, d_obst != nullptr, trace != nullptr, in_rescue);
+static int solve_dev_impl(mpc_handle* h, const SolveIo& io, hipStream_t stream, bool in_rescue) {
+    Solve s{h, stream, io, in_rescue}; s.prof.h = h; s.prof.s = stream;
+    PlanState ps = plan_state(h, io.B, io.obst != nullptr, io.trace.out != nullptr, in_rescue);
     s.pl = plan_solve(h->hp, h->knobs, ps);
     // tile-major layout: the rows of a tile do not depend on the batch size, so a smaller batch lives in the first tiles of
     // a larger allocation (grow-only; the rescue path alternates between the full batch and a failed subset)
     int rc = ensure_ws(h, (size_t)s.pl.ntiles * 64, s.pl.mailbox); if (rc) return rc;
     if (ps.ws_mailbox != h->ws_mailbox) { ps.ws_mailbox = h->ws_mailbox; s.pl = plan_solve(h->hp, h->knobs, ps); }
-    if ((rc = solve_front<NX>(s, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt))) return rc;
-    rc = s.pl.res_path ? solve_wg_alone<NX>(s) : s.pl.pipe_path ? solve_pipeline<NX>(s) : solve_per_kernel<NX>(s, trace, trace_rows);
+    if ((rc = solve_front<NX>(s))) return rc;
+    rc = s.pl.res_path ? solve_wg_alone<NX>(s) : s.pl.pipe_path ? solve_pipeline<NX>(s) : solve_per_kernel<NX>(s);
     if (rc == PIPE_ABANDONED) {          // (pipe_disabled: the second call plans one launch per kernel)
-        rc = solve_dev_impl<NX>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it_out, in_rescue);
+        rc = solve_dev_impl<NX>(h, io, stream, in_rescue);
         if (++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;
         return rc;
     }
     if (rc || h->async_ok) return rc;
     // the back: iterations for the caller, the spans of the profile
-    if (n_it_out) *n_it_out = s.it;
+    if (io.trace.n_it) *io.trace.n_it = s.it;
     HIP_TRY(h, hipGetLastError());
     if (h->hp.desc.fixed_iters <= 0 || h->profiling) HIP_TRY(h, hipStreamSynchronize(stream));
     s.prof.collect();
     h->prof[5] = s.it;
     return MPC_OK;
 }
-
-// what a solve writes besides its rows: multipliers ([B, n_g] / [B, n_w] device rows of the caller, mpc_solve_batch[_dev]_ex) and the snapshot
-// of its final iterates (mpc_solve_batch_sens[_dev], mpc_sens.h) -- null: not asked for
-struct SolveExtra {
-    double* lam_g = nullptr;
-    double* lam_x = nullptr;
-    double* snap = nullptr;
-};
-static int solve_dev_any(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
-                         int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream, double* trace, int32_t trace_rows, int32_t* n_it,
-                         bool in_rescue) {
-    h->snap_ok = false;                 // (every solve of the handle: the snapshot of mpc_solve_batch_sens is no longer the last solve's)
-    if (h->hp.desc.nx == 5)
-        return solve_dev_impl<5>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it, in_rescue);
-    return solve_dev_impl<6>(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it, in_rescue);
-}
+static int solve_dev_any(mpc_handle* h, const SolveIo& io, hipStream_t stream, bool in_rescue) { FOR_NX(h, return solve_dev_impl<NX>(h, io, stream, in_rescue)); }
 
 // ---- multipliers of a solve (mpc_solve_batch_ex): read back from the workspace behind the solve, the loop kernels are not touched -------
 // Before a solve whose multipliers will be read: the workspace in place (what solve_dev_impl would allocate) and the mailbox copy of the
@@ -3419,32 +3466,18 @@ static int mult_prepare(mpc_handle* h, int32_t B, hipStream_t stream) {
     }
     return MPC_OK;
 }
-// after it: lam_g [B, n_g], lam_x [B, n_w] of the B instances the last solve on this workspace left (x_out, status: that solve's)
-static int mult_read(mpc_handle* h, int32_t B, const double* d_x_out, const int32_t* d_status, double* lam_g, double* lam_x, hipStream_t stream) {
-    const mpc_problem_desc& d = h->hp.desc;
-    const size_t Bp = ((size_t)B + 63) / 64 * 64;
-    Params P;
-    fill_params(P, h->hp, B, Bp, 1, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
-    const int ipb = NLP_OUT_THREADS / (d.N + 1);
-    const dim3 grid((B + ipb - 1) / ipb);
-    if (d.nx == 5) hipLaunchKernelGGL((k_mult_out<5>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, h->ws_mailbox ? 1 : 0, d_x_out, d_status, lam_g, lam_x);
-    else hipLaunchKernelGGL((k_mult_out<6>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, h->ws_mailbox ? 1 : 0, d_x_out, d_status, lam_g, lam_x);
+// after it: io's lam_g [B, n_g], lam_x [B, n_w] of the B instances the last solve on this workspace left (x_out, status: that solve's)
+static int mult_read(mpc_handle* h, const SolveIo& io, hipStream_t stream) {
+    FOR_NX(h, hipLaunchKernelGGL((k_mult_out<NX>), nlp_out_grid(h, io.B), dim3(NLP_OUT_THREADS), 0, stream, rows_params(h, io.B, true), h->ws_mailbox ? 1 : 0,
+                                 io.x_out, io.status, io.lam_g, io.lam_x));
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
 
-// after it, likewise: the final iterates -> snapshot rows (mpc_solve_batch_sens); idx: the rows of the second chance's sub-batch
-static int sens_read(mpc_handle* h, int32_t B, const double* d_x_out, const int32_t* d_status, const double* d_obst, const int32_t* idx, double* snap,
-                     hipStream_t stream) {
-    const mpc_problem_desc& d = h->hp.desc;
-    const size_t Bp = ((size_t)B + 63) / 64 * 64;
-    Params P;
-    fill_params(P, h->hp, B, Bp, 1, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
-    const int ipb = NLP_OUT_THREADS / (d.N + 1);
-    const dim3 grid((B + ipb - 1) / ipb);
-    const int mb = h->ws_mailbox ? 1 : 0;
-    if (d.nx == 5) hipLaunchKernelGGL((k_sens_gather<5>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, mb, d_x_out, d_status, d_obst, idx, snap);
-    else hipLaunchKernelGGL((k_sens_gather<6>), grid, dim3(NLP_OUT_THREADS), 0, stream, P, mb, d_x_out, d_status, d_obst, idx, snap);
+// after it, likewise: the final iterates -> io's snapshot rows (mpc_solve_batch_sens); idx: the rows of the second chance's sub-batch
+static int sens_read(mpc_handle* h, const SolveIo& io, const int32_t* idx, hipStream_t stream) {
+    FOR_NX(h, hipLaunchKernelGGL((k_sens_gather<NX>), nlp_out_grid(h, io.B), dim3(NLP_OUT_THREADS), 0, stream, rows_params(h, io.B, true), h->ws_mailbox ? 1 : 0,
+                                 io.x_out, io.status, io.obst, idx, io.snap));
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
@@ -3457,90 +3490,79 @@ static int sens_read(mpc_handle* h, int32_t B, const double* d_x_out, const int3
 // one that converged; the last level is the ORIGINAL problem, so what is written back is a KKT point of the original NLP to the
 // original tolerance -- or nothing (the original failure stays).  Two passes: levels {0, 1}, then {0, 0.4, 0.7, 0.9, 1} for
 // what is still open.  Everything stays in device memory; the only host traffic is the count of open instances.
-static int rescue_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
-                      int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream, const SolveExtra& ex) {
-    const size_t nw = h->hp.n_w(), nB = (size_t)B;
-    int32_t* idx = static_cast<int32_t*>(scratch_get(h, SCR_RESC_IDX, (nB + 1) * 4));
+static int rescue_dev(mpc_handle* h, const SolveIo& io, hipStream_t stream) {
+    const int32_t B = io.B;
+    int32_t* idx = static_cast<int32_t*>(scratch_get(h, SCR_RESC_IDX, ((size_t)B + 1) * 4));
     if (!idx) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
-    int32_t* cnt = idx + nB;
+    int32_t* cnt = idx + B;
     static const double pass1[] = {0.0, 1.0}, pass2[] = {0.0, 0.4, 0.7, 0.9, 1.0};
     const double ol_keep = h->hp.ol, tol_keep = h->hp.desc.tol;
     h->rescued_last = 0;
     int rc = MPC_OK;
     for (int pass = 0; pass < 2 && rc == MPC_OK; ++pass) {
-        hipLaunchKernelGGL(k_rescue_select, dim3(1), dim3(1024), 0, stream, d_status, B, idx, cnt);
+        hipLaunchKernelGGL(k_rescue_select, dim3(1), dim3(1024), 0, stream, io.status, B, idx, cnt);
         int32_t n = 0;
         HIP_TRY(h, hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(h, hipStreamSynchronize(stream));
         if (n <= 0) break;
-        // sub-batch buffers: [xs | ps | out] rows, obstacle rows, status / iterations / kkt of a level, accumulated iterations
+        // the sub-batch, one allocation: [x0 | p | x_out | obst | kkt | status | iters] rows of a level, accumulated iterations -- every part
+        // starts where SolveIo::rows puts the end of the one before it
+        const size_t nw = io.n_w, ng = io.n_g;
         double* buf = static_cast<double*>(scratch_get(h, SCR_RESC_BUF, ((size_t)n * (3 * nw + 6 + 1)) * 8 + (size_t)n * 3 * 4 + 64));
         if (!buf) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
-        double *xs = buf, *ps = xs + (size_t)n * nw, *out = ps + (size_t)n * nw, *os = out + (size_t)n * nw, *kk = os + (size_t)n * 6;
-        int32_t *st = reinterpret_cast<int32_t*>(kk + n), *it = st + n, *acc = it + n;
-        hipLaunchKernelGGL(k_rescue_gather, dim3(n), dim3(128), 0, stream, idx, (int)nw, d_x0, d_p, d_obst, xs, ps, os, acc);
+        SolveIo sub = io.rows(0, n);
+        sub.lam_g = sub.lam_x = nullptr;
+        const auto end = [&] { return sub.rows((size_t)n, 0); };
+        double *const xs = buf, *ps, *os;
+        sub.x0 = xs; sub.p = ps = const_cast<double*>(end().x0); sub.x_out = const_cast<double*>(end().p); sub.obst = os = end().x_out;
+        sub.kkt = const_cast<double*>(end().obst); sub.status = reinterpret_cast<int32_t*>(end().kkt); sub.iters = end().status;
+        int32_t* const acc = end().iters;
+        hipLaunchKernelGGL(k_rescue_gather, dim3(n), dim3(128), 0, stream, idx, (int)nw, io.x0, io.p, io.obst, xs, ps, os, acc);
+        if (!io.obst) sub.obst = nullptr;
         const double* fr = pass == 0 ? pass1 : pass2;
         const int nfr = pass == 0 ? 2 : 5;
-        // (mpc_solve_batch_ex: the multipliers of the last level, the original problem, go back beside its rows)
-        const size_t ng = h->hp.n_g();
-        double* mlg = nullptr;
-        if (ex.lam_g) {
-            mlg = static_cast<double*>(scratch_get(h, SCR_RESC_MULT, (size_t)n * (ng + nw) * 8));
-            if (!mlg) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
+        // (the multipliers of the last level, the original problem, go back beside its rows; the snapshot rows are the batch's, filled through idx)
+        if (io.lam_g) {
+            sub.lam_g = static_cast<double*>(scratch_get(h, SCR_RESC_MULT, (size_t)n * (ng + nw) * 8));
+            if (!sub.lam_g) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
+            sub.lam_x = end().lam_g;
         }
         for (int q = 0; q < nfr && rc == MPC_OK; ++q) {
+            const bool last = q + 1 == nfr;             // (the original problem; the levels before it only produce warm starts)
             h->hp.ol = relax_lo(fr[q] * h->hp.ol_raw);
-            h->hp.desc.tol = (q + 1 < nfr) ? std::max(tol_keep, 1e-4) : tol_keep;      // intermediate levels only produce warm starts
-            if ((mlg || ex.snap) && q + 1 == nfr) rc = mult_prepare(h, n, stream);
+            h->hp.desc.tol = last ? tol_keep : std::max(tol_keep, 1e-4);
+            if ((sub.lam_g || sub.snap) && last) rc = mult_prepare(h, n, stream);
             if (rc != MPC_OK) break;
-            rc = solve_dev_any(h, n, xs, ps, d_obst ? os : nullptr, out, st, it, kk, stream, nullptr, 0, nullptr, true);
-            if (rc == MPC_OK && mlg && q + 1 == nfr) rc = mult_read(h, n, out, st, mlg, mlg + (size_t)n * ng, stream);
-            if (rc == MPC_OK && ex.snap && q + 1 == nfr) rc = sens_read(h, n, out, st, d_obst ? os : nullptr, idx, ex.snap, stream);
-            if (rc == MPC_OK) hipLaunchKernelGGL(k_rescue_carry, dim3(n), dim3(128), 0, stream, (int)nw, st, it, out, xs, acc);
+            rc = solve_dev_any(h, sub, stream, true);
+            if (rc == MPC_OK && sub.lam_g && last) rc = mult_read(h, sub, stream);
+            if (rc == MPC_OK && sub.snap && last) rc = sens_read(h, sub, idx, stream);
+            if (rc == MPC_OK) hipLaunchKernelGGL(k_rescue_carry, dim3(n), dim3(128), 0, stream, (int)nw, sub.status, sub.iters, sub.x_out, xs, acc);
         }
-        h->hp.ol = ol_keep;
-        h->hp.desc.tol = tol_keep;
-        if (rc == MPC_OK) hipLaunchKernelGGL(k_rescue_scatter, dim3(n), dim3(128), 0, stream, idx, (int)nw, st, out, kk, acc, d_x_out, d_status, d_iters, d_kkt);
-        if (rc == MPC_OK && mlg)
-            hipLaunchKernelGGL(k_rescue_scatter_mult, dim3(n), dim3(128), 0, stream, idx, (int)nw, (int)ng, st, mlg, mlg + (size_t)n * ng, ex.lam_g, ex.lam_x);
+        h->hp.ol = ol_keep; h->hp.desc.tol = tol_keep;
+        if (rc == MPC_OK)
+            hipLaunchKernelGGL(k_rescue_scatter, dim3(n), dim3(128), 0, stream, idx, (int)nw, sub.status, sub.x_out, sub.kkt, acc, io.x_out, io.status, io.iters, io.kkt);
+        if (rc == MPC_OK && sub.lam_g)
+            hipLaunchKernelGGL(k_rescue_scatter_mult, dim3(n), dim3(128), 0, stream, idx, (int)nw, (int)ng, sub.status, sub.lam_g, sub.lam_x, io.lam_g, io.lam_x);
         if (pass == 0) h->rescued_last = n;
     }
-    h->hp.ol = ol_keep;
-    h->hp.desc.tol = tol_keep;
+    h->hp.ol = ol_keep; h->hp.desc.tol = tol_keep;
     if (rc == MPC_OK) { HIP_TRY(h, hipGetLastError()); HIP_TRY(h, hipStreamSynchronize(stream)); }
     return rc;
 }
 
-
-static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
-                     int32_t* d_status, int32_t* d_iters, double* d_kkt, hipStream_t stream, double* trace, int32_t trace_rows,
-                     int32_t* n_it, const SolveExtra& ex = SolveExtra{}) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !d_x0 || !d_p || !d_x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
-    if (!h->hp.bounds_set) { h->err = "mpc_set_bounds has not been called"; return MPC_ERR_STATE; }
-    h->snap_ok = false;
-    HIP_TRY(h, hipSetDevice(h->device));
+// One solve behind an entry point that has begun it (begin_solve): chunks, the multipliers and the snapshot behind the launch, the second chance.
+static int solve_dev(mpc_handle* h, SolveIo io, hipStream_t stream) {
+    const int32_t B = io.B;
     h->rescued_last = 0;
-    const SolvePlan pl = plan_solve(h->hp, h->knobs, plan_state(h, B, d_obst != nullptr, trace != nullptr, false));
-    // the second chance needs the per-instance status: an internal row when the caller did not ask for it
-    if (pl.rescue && !d_status) {
-        d_status = static_cast<int32_t*>(scratch_get(h, SCR_SOLVE_STATUS, (size_t)B * 4));
-        if (!d_status) { h->err = "out of device memory"; return MPC_ERR_HIP; }
-    }
+    const SolvePlan pl = plan_solve(h->hp, h->knobs, plan_state(h, B, io.obst != nullptr, io.trace.out != nullptr, false));
+    // the second chance and the multipliers read the per-instance status
+    if (pl.rescue || io.lam_g) { const int rs = supply_status(h, io); if (rs) return rs; }
     // The workspace is addressed with 32-bit buffer offsets (< 4 GiB): a batch beyond that is solved in chunks of whole tiles, one after
     // the other on the same stream (instances are independent; the rows of a chunk are a contiguous slice of every caller buffer).
-    if ((size_t)B > pl.max_rows && !trace && !h->async_loop) {
-        const size_t max_b = pl.max_rows, nw = h->hp.n_w(), ng = h->hp.n_g();
-        const size_t slen = h->hp.desc.nx == 5 ? Sens<5>::len(h->hp.desc.N) : Sens<6>::len(h->hp.desc.N);
+    if ((size_t)B > pl.max_rows && !io.trace.out && !h->async_loop) {
         int rescued = 0;
-        for (size_t off = 0; off < (size_t)B; off += max_b) {
-            const int32_t n = (int32_t)std::min(max_b, (size_t)B - off);
-            SolveExtra exc = ex;
-            if (ex.lam_g) { exc.lam_g = ex.lam_g + off * ng; exc.lam_x = ex.lam_x + off * nw; }
-            if (ex.snap) exc.snap = ex.snap + off * slen;
-            const int rcc = solve_dev(h, n, d_x0 + off * nw, d_p + off * nw, d_obst ? d_obst + off * 6 : nullptr, d_x_out + off * nw,
-                                      d_status ? d_status + off : nullptr, d_iters ? d_iters + off : nullptr, d_kkt ? d_kkt + off : nullptr, stream,
-                                      nullptr, 0, nullptr, exc);
+        for (size_t off = 0; off < (size_t)B; off += pl.max_rows) {
+            const int rcc = solve_dev(h, io.rows(off, (int32_t)std::min(pl.max_rows, (size_t)B - off)), stream);
             if (rcc) return rcc;
             rescued += h->rescued_last;
         }
@@ -3548,13 +3570,10 @@ static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double*
         return MPC_OK;
     }
     h->resc_in_kernel = h->resc_ran = false;
-    if (ex.lam_g || ex.snap) {
-        const int rm = mult_prepare(h, B, stream);
-        if (rm) return rm;
-    }
-    int rc = solve_dev_any(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, trace, trace_rows, n_it, false);
-    if (rc == MPC_OK && ex.lam_g) rc = mult_read(h, B, d_x_out, d_status, ex.lam_g, ex.lam_x, stream);
-    if (rc == MPC_OK && ex.snap) rc = sens_read(h, B, d_x_out, d_status, d_obst, nullptr, ex.snap, stream);
+    if (io.lam_g || io.snap) { const int rm = mult_prepare(h, B, stream); if (rm) return rm; }
+    int rc = solve_dev_any(h, io, stream, false);
+    if (rc == MPC_OK && io.lam_g) rc = mult_read(h, io, stream);
+    if (rc == MPC_OK && io.snap) rc = sens_read(h, io, nullptr, stream);
     // (converged mode: the solve has synchronised the stream; a launch of k_solve_wg with the second chance inside has given every stalled
     //  instance its levels already)
     // (what the next solve of this handle does about stalled instances: see resc_cond in plan_solve)
@@ -3565,7 +3584,7 @@ static int solve_dev(mpc_handle* h, int32_t B, const double* d_x0, const double*
     memcpy(prof_keep, h->prof, sizeof prof_keep);
     memcpy(pipe_keep, h->pipe_prof, sizeof pipe_keep);
     const int in_kernel = h->rescued_last;                  // (instances that had their second chance inside k_solve_wg already)
-    const int rr = rescue_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, stream, ex);
+    const int rr = rescue_dev(h, io, stream);
     h->rescued_last += in_kernel;
     memcpy(h->prof, prof_keep, sizeof prof_keep);          // the measurement helpers describe the main solve
     memcpy(h->pipe_prof, pipe_keep, sizeof pipe_keep);
@@ -3587,32 +3606,76 @@ static int ensure_io(mpc_handle* h, size_t B) {
     return MPC_OK;
 }
 
-static int solve_host(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out,
-                      int32_t* status, int32_t* iters, double* kkt, double* trace, int32_t trace_rows, int32_t* n_it) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !x0 || !p || !x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
-    const size_t nB = (size_t)B, nw = h->hp.n_w();
-    return stage_host(h, {{x0, nB * nw * 8, false}, {p, nB * nw * 8, false}, {obst, nB * 6 * 8, false}, {x_out, nB * nw * 8, true},
-                          {status, nB * 4, true}, {iters, nB * 4, true}, {kkt, nB * 8, true}}, [&](void** d, hipStream_t s) {
-        return solve_dev(h, B, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (int32_t*)d[4], (int32_t*)d[5], (double*)d[6], s, trace, trace_rows, n_it);
-    });
+// solve_dev plus the NLP's objective / rows at the returned x and the multipliers of the final iterate (io.lam_g, io.lam_x; all four
+// optional; none asked for: exactly solve_dev, nothing synchronised here)
+static int solve_ex_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, hipStream_t s) {
+    const bool mult = io.lam_g || io.lam_x;
+    if (!mult && !d_f && !d_g) return solve_dev(h, io, s);
+    if (mult) {
+        const size_t nB = (size_t)io.B;
+        if (!io.lam_g) io.lam_g = static_cast<double*>(scratch_get(h, SCR_EX_LAM, nB * io.n_g * 8));
+        if (!io.lam_x) io.lam_x = static_cast<double*>(scratch_get(h, SCR_EX_LAM, nB * io.n_w * 8));       // (one of the two at most)
+        if (!io.lam_g || !io.lam_x) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    }
+    int rc = solve_dev(h, io, s);
+    if (rc == MPC_OK && (d_f || d_g)) rc = mpc_eval_nlp_batch_dev(h, io.B, io.x_out, io.p, io.obst, d_f, d_g, (void*)s);
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MPC_OK;
 }
+
+// ---- parametric sensitivities (DESIGN.md section 13) -----------------------------------------------------------------------------------
+// factor the snapshot's KKT matrices and solve: n_dir forward directions and / or one adjoint seed (k_sens_factor_solve)
+static int sens_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dp, double* d_dw, const double* d_seed, double* d_grad, hipStream_t s) {
+    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(h->hp.desc.N + 1) * (size_t)sens_fs(h) * 8));
+    if (!F) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
+    const double* snap = static_cast<const double*>(h->scratch[SCR_SENS_SNAP]);
+    FOR_NX(h, hipLaunchKernelGGL((k_sens_factor_solve<NX>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F,
+                                 n_dir, d_dp, d_dw, d_seed, d_grad));
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+
+// solve_ex_dev plus the snapshot of the final iterates, CasADi's lam_p and n_dir forward sensitivities
+static int solve_sens_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, double* d_lam_p, int32_t n_dir, const double* d_dp, double* d_dw, hipStream_t s) {
+    int rc = supply_status(h, io);
+    if (rc) return rc;
+    io.snap = static_cast<double*>(scratch_get(h, SCR_SENS_SNAP, (size_t)io.B * io.snap_len * 8));
+    if (d_lam_p && !io.lam_g) io.lam_g = static_cast<double*>(scratch_get(h, SCR_SENS_LAM_G, (size_t)io.B * io.n_g * 8));
+    if (!io.snap || (d_lam_p && !io.lam_g)) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    if ((rc = solve_ex_dev(h, io, d_f, d_g, s))) return rc;
+    h->snap_ok = true; h->snap_B = io.B;
+    if (d_lam_p) {
+        const dim3 grid((unsigned)(((size_t)io.B * io.n_w + 255) / 256));
+        FOR_NX(h, hipLaunchKernelGGL((k_sens_lam_p<NX>), grid, dim3(256), 0, s, rows_params(h, io.B, false), io.x_out, io.p, io.status, io.lam_g, d_lam_p));
+        HIP_TRY(h, hipGetLastError());
+    }
+    if (n_dir > 0 && (rc = sens_launch(h, io.B, n_dir, d_dp, d_dw, nullptr, nullptr, s))) return rc;
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MPC_OK;
+}
+static const char* bad_dirs(int32_t n_dir, const double* dp, const double* dw) { return n_dir < 0 || (n_dir > 0 && (!dp || !dw)) ? "n_dir >= 0, and dp, dw are required when n_dir > 0" : nullptr; }
 
 extern "C" {
 
 int mpc_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
                         int32_t* d_status, int32_t* d_iters, double* d_kkt, void* stream) {
-    return solve_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, (hipStream_t)stream, nullptr, 0, nullptr);
+    const SolveIo io = solve_io(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt);
+    const int rc = begin_solve(h, io);
+    return rc ? rc : solve_dev(h, io, (hipStream_t)stream);
 }
 
 int mpc_solve_batch(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out,
                     int32_t* status, int32_t* iters, double* kkt) {
-    return solve_host(h, B, x0, p, obst, x_out, status, iters, kkt, nullptr, 0, nullptr);
+    return mpc_solve_batch_trace(h, B, x0, p, obst, x_out, status, iters, kkt, nullptr, 0, nullptr);
 }
 
 int mpc_solve_batch_trace(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out,
                           int32_t* status, int32_t* iters, double* kkt, double* trace, int32_t trace_rows, int32_t* n_it) {
-    return solve_host(h, B, x0, p, obst, x_out, status, iters, kkt, trace, trace_rows, n_it);
+    SolveIo io = solve_io(h, B, x0, p, obst, x_out, status, iters, kkt);
+    io.trace = {trace, trace_rows, n_it};
+    const int rc = begin_solve(h, io);
+    return rc ? rc : stage_solve(h, io, {{nullptr, 0, false}}, [&](const SolveIo& dio, void**, hipStream_t s) { return solve_dev(h, dio, s); });
 }
 
 // objective and constraint rows of the reference's NLP at B points (k_eval_nlp); f / g may be null
@@ -3622,14 +3685,7 @@ int mpc_eval_nlp_batch_dev(mpc_handle* h, int32_t B, const double* d_x, const do
     if (B <= 0 || !d_x || !d_p) { h->err = "B > 0 and x, p are required"; return MPC_ERR_INVALID; }
     if (!d_f && !d_g) return MPC_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    const mpc_problem_desc& d = h->hp.desc;
-    Params P;
-    fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, nullptr, nullptr, h->d_LB, h->d_UB, false);
-    const int ipb = NLP_OUT_THREADS / (d.N + 1);
-    const dim3 grid((B + ipb - 1) / ipb);
-    hipStream_t s = (hipStream_t)stream_;
-    if (d.nx == 5) hipLaunchKernelGGL((k_eval_nlp<5>), grid, dim3(NLP_OUT_THREADS), 0, s, P, d_x, d_p, d_obst, d_f, d_g);
-    else hipLaunchKernelGGL((k_eval_nlp<6>), grid, dim3(NLP_OUT_THREADS), 0, s, P, d_x, d_p, d_obst, d_f, d_g);
+    FOR_NX(h, hipLaunchKernelGGL((k_eval_nlp<NX>), nlp_out_grid(h, B), dim3(NLP_OUT_THREADS), 0, (hipStream_t)stream_, rows_params(h, B, false), d_x, d_p, d_obst, d_f, d_g));
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
@@ -3643,120 +3699,41 @@ int mpc_eval_nlp_batch(mpc_handle* h, int32_t B, const double* x, const double* 
                       [&](void** d, hipStream_t s) { return mpc_eval_nlp_batch_dev(h, B, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], s); });
 }
 
-// mpc_solve_batch_dev plus the NLP's objective / rows at the returned x and the multipliers of the final iterate (all four optional; none
-// asked for: exactly mpc_solve_batch_dev)
-static int solve_ex_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
-                        int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
-                        double* d_snap, hipStream_t s) {
-    const bool mult = d_lam_g || d_lam_x;
-    if (!mult && !d_f && !d_g) return solve_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, s, nullptr, 0, nullptr, SolveExtra{nullptr, nullptr, d_snap});
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !d_x0 || !d_p || !d_x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
-    if (mult && h->hp.desc.fixed_iters > 0) { h->err = "multipliers need a solve to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (mult) {
-        const size_t nw = h->hp.n_w(), nB = (size_t)B;
-        const size_t ng = h->hp.n_g();
-        if (!d_status) d_status = static_cast<int32_t*>(scratch_get(h, SCR_EX_STATUS, nB * 4));
-        if (!d_lam_g) d_lam_g = static_cast<double*>(scratch_get(h, SCR_EX_LAM, nB * ng * 8));
-        if (!d_lam_x) d_lam_x = static_cast<double*>(scratch_get(h, SCR_EX_LAM, nB * nw * 8));       // (one of the two at most)
-        if (!d_status || !d_lam_g || !d_lam_x) { h->err = "out of device memory"; return MPC_ERR_HIP; }
-    }
-    int rc = solve_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, s, nullptr, 0, nullptr,
-                       SolveExtra{mult ? d_lam_g : nullptr, mult ? d_lam_x : nullptr, d_snap});
-    if (rc == MPC_OK && (d_f || d_g)) rc = mpc_eval_nlp_batch_dev(h, B, d_x_out, d_p, d_obst, d_f, d_g, (void*)s);
-    if (rc) return rc;
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
-}
-
 int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
                            int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
                            void* stream_) {
-    return solve_ex_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_f, d_g, d_lam_g, d_lam_x, nullptr, (hipStream_t)stream_);
+    const SolveIo io = solve_io(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_lam_g, d_lam_x);
+    const int rc = begin_solve(h, io);
+    return rc ? rc : solve_ex_dev(h, io, d_f, d_g, (hipStream_t)stream_);
 }
 
 int mpc_solve_batch_ex(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out, int32_t* status,
                        int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !x0 || !p || !x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
-    const size_t nw = h->hp.n_w(), nB = (size_t)B, ng = h->hp.n_g();
-    return stage_host(h, {{x0, nB * nw * 8, false}, {p, nB * nw * 8, false}, {obst, nB * 6 * 8, false}, {x_out, nB * nw * 8, true}, {status, nB * 4, true},
-                          {iters, nB * 4, true}, {kkt, nB * 8, true}, {f, nB * 8, true}, {g, nB * ng * 8, true}, {lam_g, nB * ng * 8, true},
-                          {lam_x, nB * nw * 8, true}}, [&](void** d, hipStream_t s) {
-        return mpc_solve_batch_dev_ex(h, B, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (int32_t*)d[4], (int32_t*)d[5], (double*)d[6],
-                                      (double*)d[7], (double*)d[8], (double*)d[9], (double*)d[10], s);
-    });
+    const SolveIo io = solve_io(h, B, x0, p, obst, x_out, status, iters, kkt, lam_g, lam_x);
+    const int rc = begin_solve(h, io);
+    if (rc) return rc;
+    return stage_solve(h, io, {{f, (size_t)B * 8, true}, {g, (size_t)B * io.n_g * 8, true}},
+                       [&](const SolveIo& dio, void** m, hipStream_t s) { return solve_ex_dev(h, dio, (double*)m[0], (double*)m[1], s); });
 }
 
-// ---- parametric sensitivities (DESIGN.md section 13) -----------------------------------------------------------------------------------
-static size_t sens_len(const mpc_handle* h) { return h->hp.desc.nx == 5 ? Sens<5>::len(h->hp.desc.N) : Sens<6>::len(h->hp.desc.N); }
-static int sens_fs(const mpc_handle* h) { return h->hp.desc.nx == 5 ? Sens<5>::FS : Sens<6>::FS; }
-// factor the snapshot's KKT matrices and solve: n_dir forward directions and / or one adjoint seed (k_sens_factor_solve)
-static int sens_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dp, double* d_dw, const double* d_seed, double* d_grad, hipStream_t s) {
-    const mpc_problem_desc& d = h->hp.desc;
-    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(d.N + 1) * (size_t)sens_fs(h) * 8));
-    if (!F) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
-    Params P;
-    fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, nullptr, nullptr, h->d_LB, h->d_UB, false);
-    const dim3 grid((B + SENS_THREADS - 1) / SENS_THREADS);
-    double* snap = static_cast<double*>(h->scratch[SCR_SENS_SNAP]);
-    if (d.nx == 5) hipLaunchKernelGGL((k_sens_factor_solve<5>), grid, dim3(SENS_THREADS), 0, s, P, snap, F, n_dir, d_dp, d_dw, d_seed, d_grad);
-    else hipLaunchKernelGGL((k_sens_factor_solve<6>), grid, dim3(SENS_THREADS), 0, s, P, snap, F, n_dir, d_dp, d_dw, d_seed, d_grad);
-    HIP_TRY(h, hipGetLastError());
-    return MPC_OK;
-}
-
-// mpc_solve_batch_dev_ex plus the snapshot of the final iterates, CasADi's lam_p and n_dir forward sensitivities
 int mpc_solve_batch_sens_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
                              int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
                              double* d_lam_p, int32_t n_dir, const double* d_dp, double* d_dw, void* stream_) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !d_x0 || !d_p || !d_x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
-    if (n_dir < 0 || (n_dir > 0 && (!d_dp || !d_dw))) { h->err = "n_dir >= 0, and dp, dw are required when n_dir > 0"; return MPC_ERR_INVALID; }
-    if (h->hp.desc.fixed_iters > 0) { h->err = "sensitivities need a solve to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
-    h->snap_ok = false;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream_;
-    const size_t nB = (size_t)B, ng = h->hp.n_g();
-    double* snap = static_cast<double*>(scratch_get(h, SCR_SENS_SNAP, nB * sens_len(h) * 8));
-    if (!d_status) d_status = static_cast<int32_t*>(scratch_get(h, SCR_SENS_STATUS, nB * 4));
-    if (d_lam_p && !d_lam_g) d_lam_g = static_cast<double*>(scratch_get(h, SCR_SENS_LAM_G, nB * ng * 8));
-    if (!snap || !d_status || (d_lam_p && !d_lam_g)) { h->err = "out of device memory"; return MPC_ERR_HIP; }
-    int rc = solve_ex_dev(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_f, d_g, d_lam_g, d_lam_x, snap, s);
-    if (rc) return rc;
-    h->snap_ok = true;
-    h->snap_B = B;
-    if (d_lam_p) {
-        Params P;
-        fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, nullptr, nullptr, h->d_LB, h->d_UB, false);
-        const size_t n = nB * h->hp.n_w();
-        const dim3 grid((unsigned)((n + 255) / 256));
-        if (h->hp.desc.nx == 5) hipLaunchKernelGGL((k_sens_lam_p<5>), grid, dim3(256), 0, s, P, d_x_out, d_p, d_status, d_lam_g, d_lam_p);
-        else hipLaunchKernelGGL((k_sens_lam_p<6>), grid, dim3(256), 0, s, P, d_x_out, d_p, d_status, d_lam_g, d_lam_p);
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (n_dir > 0) {
-        rc = sens_launch(h, B, n_dir, d_dp, d_dw, nullptr, nullptr, s);
-        if (rc) return rc;
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MPC_OK;
+    const SolveIo io = solve_io(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_lam_g, d_lam_x);
+    const int rc = begin_solve(h, io, bad_dirs(n_dir, d_dp, d_dw), true);
+    return rc ? rc : solve_sens_dev(h, io, d_f, d_g, d_lam_p, n_dir, d_dp, d_dw, (hipStream_t)stream_);
 }
 
 int mpc_solve_batch_sens(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out, int32_t* status,
                          int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x, double* lam_p, int32_t n_dir,
                          const double* dp, double* dw) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !x0 || !p || !x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
-    if (n_dir < 0 || (n_dir > 0 && (!dp || !dw))) { h->err = "n_dir >= 0, and dp, dw are required when n_dir > 0"; return MPC_ERR_INVALID; }
-    const size_t nw = h->hp.n_w(), nB = (size_t)B, ng = h->hp.n_g(), nd = (size_t)n_dir;
-    return stage_host(h, {{x0, nB * nw * 8, false}, {p, nB * nw * 8, false}, {obst, nB * 6 * 8, false}, {nd ? dp : nullptr, nB * nd * nw * 8, false},
-                          {x_out, nB * nw * 8, true}, {status, nB * 4, true}, {iters, nB * 4, true}, {kkt, nB * 8, true}, {f, nB * 8, true},
-                          {g, nB * ng * 8, true}, {lam_g, nB * ng * 8, true}, {lam_x, nB * nw * 8, true}, {lam_p, nB * nw * 8, true},
-                          {nd ? dw : nullptr, nB * nd * nw * 8, true}}, [&](void** d, hipStream_t s) {
-        return mpc_solve_batch_sens_dev(h, B, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[4], (int32_t*)d[5], (int32_t*)d[6], (double*)d[7],
-                                        (double*)d[8], (double*)d[9], (double*)d[10], (double*)d[11], (double*)d[12], n_dir, (double*)d[3], (double*)d[13], s);
+    const SolveIo io = solve_io(h, B, x0, p, obst, x_out, status, iters, kkt, lam_g, lam_x);
+    const int rc = begin_solve(h, io, bad_dirs(n_dir, dp, dw), true);
+    if (rc) return rc;
+    const size_t nB = (size_t)B, dirs = nB * (size_t)n_dir * io.n_w * 8;
+    return stage_solve(h, io, {{f, nB * 8, true}, {g, nB * io.n_g * 8, true}, {lam_p, nB * io.n_w * 8, true}, {n_dir ? dp : nullptr, dirs, false},
+                               {n_dir ? dw : nullptr, dirs, true}}, [&](const SolveIo& dio, void** m, hipStream_t s) {
+        return solve_sens_dev(h, dio, (double*)m[0], (double*)m[1], (double*)m[2], n_dir, (double*)m[3], (double*)m[4], s);
     });
 }
 
@@ -3784,12 +3761,7 @@ int mpc_plant_step_dev(mpc_handle* h, int32_t B, int32_t integrator, const doubl
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !d_x || !d_u || !d_x_next || integrator < 0 || integrator > 1) { h->err = "bad plant-step arguments"; return MPC_ERR_INVALID; }
     HIP_TRY(h, hipSetDevice(h->device));
-    const int nx = h->hp.desc.nx;
-    hipStream_t s = (hipStream_t)stream_;
-    Params P{};
-    P.dt = h->hp.desc.dt; P.wheelbase = h->hp.desc.wheelbase; P.nx = nx;
-    if (nx == 5) hipLaunchKernelGGL((k_plant_step<5>), dim3((B + 255) / 256), dim3(256), 0, s, P, d_x, d_u, d_x_next, B, integrator);
-    else hipLaunchKernelGGL((k_plant_step<6>), dim3((B + 255) / 256), dim3(256), 0, s, P, d_x, d_u, d_x_next, B, integrator);
+    FOR_NX(h, hipLaunchKernelGGL((k_plant_step<NX>), dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream_, plant_params(h), d_x, d_u, d_x_next, B, integrator));
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
@@ -3812,10 +3784,12 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
         return MPC_ERR_INVALID;
     }
     if (noise_mode < 0 || noise_mode > 2 || (noise_mode != 0 && !(sigma >= 0.0))) { h->err = "closed loop: noise_mode in {0, 1, 2}, sigma >= 0"; return MPC_ERR_INVALID; }
-    if (!h->hp.bounds_set) { h->err = "mpc_set_bounds has not been called"; return MPC_ERR_STATE; }
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_io(h, (size_t)B);
     if (rc) return rc;
+    // the rows of every solve of the loop: the handle's own (begin_solve: the bounds must be set)
+    const SolveIo io = solve_io(h, B, h->d_x0, h->d_p, nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt);
+    if ((rc = begin_solve(h, io))) return rc;
     if (h->cap_state < (size_t)B) {
         if (h->d_state) (void)hipFree(h->d_state);
         h->d_state = nullptr;
@@ -3829,8 +3803,7 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
     A.state = h->d_state; A.x0 = h->d_x0; A.p = h->d_p; A.x_out = h->d_xout; A.status = h->d_status;
     A.traj = d_traj; A.ctrl = d_ctrl; A.step_status = d_step_status;
     A.noise_mode = noise_mode; A.sigma = sigma; A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32);
-    Params P{};
-    P.dt = d.dt; P.wheelbase = d.wheelbase; P.nx = d.nx;
+    const Params P = plant_params(h);
     const dim3 grid((B + 127) / 128), block(128);
     // First attempt: the whole loop enqueued without a single host synchronisation (every solve in the persistent pipeline
     // launch, which needs no convergence poll).  What could go wrong on the way -- a pipeline launch abandoned, an instance
@@ -3844,7 +3817,7 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
         h->async_loop = true;
         bool all_async = true;
         for (int i = 0; i < L && all_async; ++i) {
-            rc = solve_dev_any(h, B, h->d_x0, h->d_p, nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt, stream, nullptr, 0, nullptr, false);
+            rc = solve_dev_any(h, io, stream, false);
             if (rc) { h->async_loop = false; return rc; }
             all_async = h->async_ok;             // (a batch shape the pipeline does not take: the solve has run synchronously -- start over)
             if (all_async) hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
@@ -3866,7 +3839,7 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
         A.abort_flag = nullptr;
         hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
         for (int i = 0; i < L; ++i) {
-            rc = solve_dev(h, B, h->d_x0, h->d_p, nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt, stream, nullptr, 0, nullptr);
+            rc = solve_dev(h, io, stream);
             if (rc) return rc;
             hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
         }

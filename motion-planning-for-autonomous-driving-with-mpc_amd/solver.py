@@ -22,6 +22,17 @@ from ._abi import MpcLibraryError, MpcProblemDesc
 RESCUE_FRACTIONS = (0.0, 0.4, 0.7, 0.9, 1.0)      # of the circle-distance lower bound, see rescue_failed()
 
 
+def _big(a, n):
+    """a bound list of the FORCES formulation as n doubles, +-inf as +-1e308"""
+    a = np.asarray(a, dtype=np.float64).reshape(n)
+    return _abi.f64(np.where(np.isfinite(a), a, np.sign(a) * 1e308))
+
+
+def _vp(d_ptr):
+    """a device pointer or stream handle given as an int (0: absent)"""
+    return C.c_void_p(d_ptr or None)
+
+
 class MpcError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"mpcgpu error {code}: {msg}")
@@ -111,21 +122,26 @@ class BatchedMPCSolver:
         self._bounds_key = key
         self._bounds = tuple(a.copy() for a in arrs)            # (lbx, ubx, lbg, ubg), for rescue_failed()
 
-    def eval_nlp(self, x, p, obst=None):
-        """objective f [B] and constraint rows g [B, n_g] of the reference's NLP at any x [B, n_w] (mpc_eval_nlp_batch)."""
-        x = _abi.f64(x)
-        p = _abi.f64(p)
+    def _rows_in(self, name, x, p, obst):
+        """(B, x [B, n_w], p [B, n_w], obst [B, 6] | None) as contiguous doubles; a single instance may come as vectors"""
+        x, p = _abi.f64(x), _abi.f64(p)
         if x.ndim == 1:
             x = x[None]
         if p.ndim == 1:
             p = p[None]
         B = x.shape[0]
         if x.shape != (B, self.n_w) or p.shape != (B, self.n_w):
-            raise MpcError(_abi.MPC_ERR_INVALID, f"x/p must be [B, {self.n_w}]")
-        if obst is not None:
-            obst = _abi.f64(obst, (B, 6))
-        f = np.empty(B)
-        g = np.empty((B, self.n_g))
+            raise MpcError(_abi.MPC_ERR_INVALID, f"{name}/p must be [B, {self.n_w}]")
+        return B, x, p, None if obst is None else _abi.f64(obst, (B, 6))
+
+    def _nlp_out(self, B):
+        """f [B], g [B, n_g], lam_g [B, n_g], lam_x [B, n_w] of a solve with multipliers"""
+        return np.empty(B), np.empty((B, self.n_g)), np.empty((B, self.n_g)), np.empty((B, self.n_w))
+
+    def eval_nlp(self, x, p, obst=None):
+        """objective f [B] and constraint rows g [B, n_g] of the reference's NLP at any x [B, n_w] (mpc_eval_nlp_batch)."""
+        B, x, p, obst = self._rows_in("x", x, p, obst)
+        f, g = np.empty(B), np.empty((B, self.n_g))
         self._check(self._lib.mpc_eval_nlp_batch(self._h, B, _abi.as_dp(x), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(f), _abi.as_dp(g)))
         return f, g
 
@@ -134,17 +150,7 @@ class BatchedMPCSolver:
         grad f + J_g' lam_g + lam_x = 0) in the result (mpc_solve_batch_ex).  lam_p=True: CasADi's lam_p; dp [B, n_dir, n_p] (or [B, n_p]):
         forward sensitivities dw = (dw*/dp) dp of the optimum (mpc_solve_batch_sens, which also keeps the final iterates for sens_adjoint).
         p = [U_ref | X_ref], n_p = n_w."""
-        x0 = _abi.f64(x0)
-        p = _abi.f64(p)
-        if x0.ndim == 1:
-            x0 = x0[None]
-        if p.ndim == 1:
-            p = p[None]
-        B = x0.shape[0]
-        if x0.shape != (B, self.n_w) or p.shape != (B, self.n_w):
-            raise MpcError(_abi.MPC_ERR_INVALID, f"x0/p must be [B, {self.n_w}]")
-        if obst is not None:
-            obst = _abi.f64(obst, (B, 6))
+        B, x0, p, obst = self._rows_in("x0", x0, p, obst)
         out = np.empty_like(x0)
         status = np.empty(B, np.int32)
         iters = np.empty(B, np.int32)
@@ -155,7 +161,7 @@ class BatchedMPCSolver:
             self._check(self._lib.mpc_solve_batch(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out),
                                                   _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt)))
             return SolveResult(out, status, iters, kkt)
-        f, g, lam_g, lam_x = np.empty(B), np.empty((B, self.n_g)), np.empty((B, self.n_g)), np.empty((B, self.n_w))
+        f, g, lam_g, lam_x = self._nlp_out(B)
         self._check(self._lib.mpc_solve_batch_ex(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out),
                                                  _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt), _abi.as_dp(f), _abi.as_dp(g),
                                                  _abi.as_dp(lam_g), _abi.as_dp(lam_x)))
@@ -165,7 +171,7 @@ class BatchedMPCSolver:
         B = x0.shape[0]
         f = g = lam_g = lam_x = lp = dw = None
         if multipliers:
-            f, g, lam_g, lam_x = np.empty(B), np.empty((B, self.n_g)), np.empty((B, self.n_g)), np.empty((B, self.n_w))
+            f, g, lam_g, lam_x = self._nlp_out(B)
         if want_lam_p:
             lp = np.empty((B, self.n_w))
         n_dir = 0
@@ -254,41 +260,36 @@ class BatchedMPCSolver:
                                                     _abi.as_ip(n_it)))
         return SolveResult(out, status, iters, kkt), trace[: int(n_it[0]) + 1]
 
+    def _dev_rows(self, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt):
+        """the leading arguments of every device-pointer solve"""
+        return [self._h, int(B), _vp(d_x0), _vp(d_p), _vp(d_obst), _vp(d_x_out), _vp(d_status), _vp(d_iters), _vp(d_kkt)]
+
     def solve_device(self, B, d_x0, d_p, d_x_out, d_status=0, d_iters=0, d_kkt=0, d_obst=0, stream=0, d_f=0, d_g=0, d_lam_g=0, d_lam_x=0,
                      d_lam_p=0, n_dir=0, d_dp=0, d_dw=0):
         """device pointers (ints, e.g. torch.Tensor.data_ptr()) and a hipStream_t handle (int, 0 = default).  d_f [B], d_g / d_lam_g
         [B, n_g], d_lam_x [B, n_w]: the extra outputs of mpc_solve_batch_dev_ex (0 = not asked for).  d_lam_p [B, n_p], n_dir > 0 with
         d_dp [B, n_dir, n_p] -> d_dw [B, n_dir, n_w]: mpc_solve_batch_sens_dev (keeps the final iterates for sens_adjoint_device)."""
-        vp = C.c_void_p
+        rows = self._dev_rows(B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt)
+        extra = [_vp(d_f), _vp(d_g), _vp(d_lam_g), _vp(d_lam_x)]
         if d_lam_p or n_dir:
             self._sens_gen += 1
-            self._check(self._lib.mpc_solve_batch_sens_dev(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out), vp(d_status or None),
-                                                           vp(d_iters or None), vp(d_kkt or None), vp(d_f or None), vp(d_g or None), vp(d_lam_g or None),
-                                                           vp(d_lam_x or None), vp(d_lam_p or None), int(n_dir), vp(d_dp or None), vp(d_dw or None),
-                                                           vp(stream or None)))
-            return
-        if not (d_f or d_g or d_lam_g or d_lam_x):
-            self._check(self._lib.mpc_solve_batch_dev(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out),
-                                                      vp(d_status or None), vp(d_iters or None), vp(d_kkt or None), vp(stream or None)))
-            return
-        self._check(self._lib.mpc_solve_batch_dev_ex(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out), vp(d_status or None),
-                                                     vp(d_iters or None), vp(d_kkt or None), vp(d_f or None), vp(d_g or None), vp(d_lam_g or None),
-                                                     vp(d_lam_x or None), vp(stream or None)))
+            self._check(self._lib.mpc_solve_batch_sens_dev(*rows, *extra, _vp(d_lam_p), int(n_dir), _vp(d_dp), _vp(d_dw), _vp(stream)))
+        elif d_f or d_g or d_lam_g or d_lam_x:
+            self._check(self._lib.mpc_solve_batch_dev_ex(*rows, *extra, _vp(stream)))
+        else:
+            self._check(self._lib.mpc_solve_batch_dev(*rows, _vp(stream)))
 
     def solve_sens_device(self, B, d_x0, d_p, d_x_out, d_status=0, d_iters=0, d_kkt=0, d_obst=0, stream=0, d_lam_p=0, n_dir=0, d_dp=0, d_dw=0):
         """mpc_solve_batch_sens_dev even with no sensitivity output asked for: the solve plus the snapshot of its final iterates
         (what sens_adjoint_device differentiates)"""
-        vp = C.c_void_p
         self._sens_gen += 1
-        self._check(self._lib.mpc_solve_batch_sens_dev(self._h, int(B), vp(d_x0), vp(d_p), vp(d_obst or None), vp(d_x_out), vp(d_status or None),
-                                                       vp(d_iters or None), vp(d_kkt or None), None, None, None, None, vp(d_lam_p or None), int(n_dir),
-                                                       vp(d_dp or None), vp(d_dw or None), vp(stream or None)))
+        self._check(self._lib.mpc_solve_batch_sens_dev(*self._dev_rows(B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt), None, None, None, None,
+                                                       _vp(d_lam_p), int(n_dir), _vp(d_dp), _vp(d_dw), _vp(stream)))
         return self._sens_gen
 
     def sens_adjoint_device(self, B, d_seed_w, d_grad_p, stream=0):
         """device form of sens_adjoint (enqueued on `stream`, not synchronised)"""
-        vp = C.c_void_p
-        self._check(self._lib.mpc_sens_adjoint_dev(self._h, int(B), vp(d_seed_w), vp(d_grad_p), vp(stream or None)))
+        self._check(self._lib.mpc_sens_adjoint_dev(self._h, int(B), _vp(d_seed_w), _vp(d_grad_p), _vp(stream)))
 
     def plant_step(self, x, u, integrator="euler"):
         x = _abi.f64(x)
@@ -326,10 +327,9 @@ class BatchedMPCSolver:
     def closed_loop_device(self, B, d_init_state, d_path, d_orient, d_vdes, steps, Lp, d_traj, d_ctrl, d_step_status=0, noise_mode=0, sigma=0.0,
                            seed=0, stream=0):
         """device-pointer form (ints): the whole loop is enqueued on `stream`; see mpc_closed_loop_batch_dev_ex"""
-        vp = C.c_void_p
-        self._check(self._lib.mpc_closed_loop_batch_dev_ex(self._h, int(B), int(steps), int(Lp), vp(d_init_state), vp(d_path), vp(d_orient), vp(d_vdes),
-                                                           int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), vp(d_traj), vp(d_ctrl),
-                                                           vp(d_step_status or None), vp(stream or None)))
+        self._check(self._lib.mpc_closed_loop_batch_dev_ex(self._h, int(B), int(steps), int(Lp), _vp(d_init_state), _vp(d_path), _vp(d_orient), _vp(d_vdes),
+                                                           int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl),
+                                                           _vp(d_step_status), _vp(stream)))
 
     def last_loop_replayed(self):
         return bool(self._lib.mpc_last_loop_replayed(self._h))
@@ -403,34 +403,24 @@ class BatchedMPCSolver:
         xinit = _abi.f64(xinit).reshape(B, 5)
         par = _abi.f64(all_parameters).reshape(B, N, 10)
 
-        def big(a, n):
-            a = np.asarray(a, dtype=np.float64).reshape(n)
-            return _abi.f64(np.where(np.isfinite(a), a, np.sign(a) * 1e308))
         out = np.empty_like(x0)
         flag, it, res = np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B)
-        self._check(self._lib.mpc_forces_solve_batch(self._h, B, _abi.as_dp(x0), _abi.as_dp(xinit), _abi.as_dp(par), _abi.as_dp(big(lb, 7)),
-                                                     _abi.as_dp(big(ub, 7)), _abi.as_dp(big(hl, 10)), _abi.as_dp(big(hu, 10)), int(hessian_mode), _abi.as_dp(out),
+        self._check(self._lib.mpc_forces_solve_batch(self._h, B, _abi.as_dp(x0), _abi.as_dp(xinit), _abi.as_dp(par), _abi.as_dp(_big(lb, 7)),
+                                                     _abi.as_dp(_big(ub, 7)), _abi.as_dp(_big(hl, 10)), _abi.as_dp(_big(hu, 10)), int(hessian_mode), _abi.as_dp(out),
                                                      _abi.as_ip(flag), _abi.as_ip(it), _abi.as_dp(res)))
         return out, flag, it, res
 
     def forces_solve_device(self, B, d_x0, d_xinit, d_par, lb, ub, hl, hu, d_x_out, d_flag=0, d_it=0, d_res=0, hessian_mode=0, stream=0):
         """mpc_forces_solve_batch_dev: device pointers (ints) for x0 [B,N,7], xinit [B,5], all_parameters [B,N,10] and the outputs;
         lb / ub / hl / hu are small host arrays.  Enqueues on `stream`; nothing is synchronised."""
-        def big(a, n):
-            a = np.asarray(a, dtype=np.float64).reshape(n)
-            return _abi.f64(np.where(np.isfinite(a), a, np.sign(a) * 1e308))
-        vp = C.c_void_p
-        self._check(self._lib.mpc_forces_solve_batch_dev(self._h, int(B), vp(d_x0), vp(d_xinit), vp(d_par), _abi.as_dp(big(lb, 7)), _abi.as_dp(big(ub, 7)),
-                                                         _abi.as_dp(big(hl, 10)), _abi.as_dp(big(hu, 10)), int(hessian_mode), vp(d_x_out), vp(d_flag or None),
-                                                         vp(d_it or None), vp(d_res or None), vp(stream or None)))
+        self._check(self._lib.mpc_forces_solve_batch_dev(self._h, int(B), _vp(d_x0), _vp(d_xinit), _vp(d_par), _abi.as_dp(_big(lb, 7)), _abi.as_dp(_big(ub, 7)),
+                                                         _abi.as_dp(_big(hl, 10)), _abi.as_dp(_big(hu, 10)), int(hessian_mode), _vp(d_x_out), _vp(d_flag),
+                                                         _vp(d_it), _vp(d_res), _vp(stream)))
 
     def forces_closed_loop(self, init_state, path, orient, vdes, steps, lb, ub, hl, hu, init_acc=None, hessian_mode=0, noise_mode=0, sigma=0.0, seed=0):
         """B egos through `steps` steps of ForcesproOptimizer.optimize (optimizer.py:246-366) on the device
         (mpc_forces_closed_loop_batch): init_state [B,5], path [B,Lp,2], orient [B,Lp], vdes [B] -> (traj [B,steps,5],
         ctrl [B,steps,2], exitflag [B,steps])."""
-        def big(a, n):
-            a = np.asarray(a, dtype=np.float64).reshape(n)
-            return _abi.f64(np.where(np.isfinite(a), a, np.sign(a) * 1e308))
         init_state = _abi.f64(init_state)
         if init_state.ndim == 1:
             init_state = init_state[None]
@@ -443,8 +433,8 @@ class BatchedMPCSolver:
         steps = int(steps)
         traj, ctrl, fl = np.empty((B, steps, 5)), np.empty((B, steps, 2)), np.empty((B, steps), np.int32)
         self._check(self._lib.mpc_forces_closed_loop_batch(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(acc), _abi.as_dp(path), _abi.as_dp(orient),
-                                                           _abi.as_dp(vdes), _abi.as_dp(big(lb, 7)), _abi.as_dp(big(ub, 7)), _abi.as_dp(big(hl, 10)),
-                                                           _abi.as_dp(big(hu, 10)), int(hessian_mode), int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1),
+                                                           _abi.as_dp(vdes), _abi.as_dp(_big(lb, 7)), _abi.as_dp(_big(ub, 7)), _abi.as_dp(_big(hl, 10)),
+                                                           _abi.as_dp(_big(hu, 10)), int(hessian_mode), int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1),
                                                            _abi.as_dp(traj), _abi.as_dp(ctrl), _abi.as_ip(fl)))
         return traj, ctrl, fl
 
@@ -456,9 +446,8 @@ class BatchedMPCSolver:
 
     def get_option(self, name):
         """current value of a run-time switch (include/mpcgpu.h: mpc_get_option)"""
-        import ctypes
-        v = ctypes.c_int64(0)
-        self._check(self._lib.mpc_get_option(self._h, str(name).encode(), ctypes.byref(v)))
+        v = C.c_int64(0)
+        self._check(self._lib.mpc_get_option(self._h, str(name).encode(), C.byref(v)))
         return int(v.value)
 
     def set_profiling(self, enable=True):

@@ -250,3 +250,23 @@ extern "C" int emu_stamp_report(int32_t which, const unsigned long long* rows, i
     memcpy(out, s.c_str(), s.size() + 1);
     return (int)s.size();
 }
+
+// SolveIo::rows (mpc_solve_plan.h) for a problem of N stages and nx states: the ten row members in declaration order (x0, p, obst, x_out, status,
+// iters, kkt, lam_g, lam_x, snap) point `at[i]` bytes into `base` (negative: null); out[0] = B of the slice, out[1 + i] = how many elements of
+// its own type member i moved (-1: it is null in the slice).  Nothing is dereferenced.
+extern "C" int emu_solve_io_rows(int32_t N, int32_t nx, int64_t snap_len, int32_t B, char* base, const int64_t* at, int64_t off, int32_t n, int64_t* out) {
+    HostProblem hp;
+    hp.desc.N = N; hp.desc.nx = nx;
+    SolveIo io;
+    io.B = B; io.n_w = hp.n_w(); io.n_g = hp.n_g(); io.snap_len = (size_t)snap_len;
+    const auto ptr = [&](int i) { return at[i] < 0 ? nullptr : base + at[i]; };
+    io.x0 = (const double*)ptr(0); io.p = (const double*)ptr(1); io.obst = (const double*)ptr(2); io.x_out = (double*)ptr(3);
+    io.status = (int32_t*)ptr(4); io.iters = (int32_t*)ptr(5); io.kkt = (double*)ptr(6); io.lam_g = (double*)ptr(7); io.lam_x = (double*)ptr(8);
+    io.snap = (double*)ptr(9);
+    const SolveIo r = io.rows((size_t)off, n);
+    out[0] = r.B;
+    out[1] = r.x0 ? r.x0 - io.x0 : -1; out[2] = r.p ? r.p - io.p : -1; out[3] = r.obst ? r.obst - io.obst : -1; out[4] = r.x_out ? r.x_out - io.x_out : -1;
+    out[5] = r.status ? r.status - io.status : -1; out[6] = r.iters ? r.iters - io.iters : -1; out[7] = r.kkt ? r.kkt - io.kkt : -1;
+    out[8] = r.lam_g ? r.lam_g - io.lam_g : -1; out[9] = r.lam_x ? r.lam_x - io.lam_x : -1; out[10] = r.snap ? r.snap - io.snap : -1;
+    return 0;
+}

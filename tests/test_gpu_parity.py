@@ -101,6 +101,51 @@ def test_batches_beyond_the_workspace_limit_are_solved_in_chunks():
     assert _same(partc, fullc) and sc.last_rescued() == n and np.all(partc.status == 1)
 
 
+# shift of the per-instance obstacle rows of the test below, in metres per row index: with it 17 of the 1024 instances stall without the
+# second chance (counted at the commit before the host solve chain took its rows as one struct)
+OBST_ROW_SHIFT = 1e-4
+
+
+def test_chunks_with_obstacle_rows_absent_outputs_multipliers_sensitivities_and_second_chance():
+    """every per-instance buffer of a solve through the chunk loop at once: obstacle rows (width 6) that differ from row to row, multipliers
+    (n_g, n_w), the snapshot behind lam_p / dw, a stalled instance in each of the three chunks (the second chance's sub-batch), and a device
+    call whose status / iters / kkt are absent.  A wrong row width, or a chunk that reads another chunk's rows, changes bits."""
+    import torch
+    cfg = CA_CFG
+    x0, p = ca_batch(cfg, 1024)
+    obst = np.tile(np.asarray(cfg.obstacle_centers, dtype=np.float64).ravel(), (1024, 1)) + OBST_ROW_SHIFT * np.arange(1024)[:, None]
+    s0 = make_solver(cfg)
+    set_cfg_bounds(s0, cfg)
+    s0.set_option("rescue", "0")
+    plain = s0.solve(x0, p, obst)
+    stalled, ok = np.nonzero(plain.status != 1)[0], np.nonzero(plain.status == 1)[0]
+    print("stalled without the second chance:", stalled.size, "of 1024")
+    rows = ok[:130].copy()
+    placed = [3, 70, 129][: min(3, stalled.size)]
+    rows[placed] = stalled[: len(placed)]
+    assert len(placed) > 0
+    x0, p, obst = (np.ascontiguousarray(a[rows]) for a in (x0, p, obst))
+    B = 130
+    seeds = np.zeros((B, 2, cfg.n_w))
+    seeds[:, 0, 2 * cfg.N] = 1.0                         # xref_0[0]
+    seeds[:, 1, 2 * cfg.N + 1] = 1.0                     # xref_0[1]
+    s = make_solver(cfg)
+    set_cfg_bounds(s, cfg)
+    a = s.solve(x0, p, obst, multipliers=True, lam_p=True, dp=seeds)
+    na = s.last_rescued()
+    s.set_option("max_batch", "64")                      # 64 + 64 + 2
+    b = s.solve(x0, p, obst, multipliers=True, lam_p=True, dp=seeds)
+    for name in ("x", "status", "iters", "kkt", "f", "g", "lam_g", "lam_x", "lam_p", "dw"):
+        assert np.array_equal(getattr(a, name), getattr(b, name), equal_nan=True), name
+    assert s.last_rescued() == na and na > 0
+    assert np.all(a.status[placed] == 1) and np.all(b.status[placed] == 1)
+    d = [torch.from_numpy(v).cuda() for v in (x0, p, obst)]
+    out = torch.empty_like(d[0])
+    s.solve_device(B, d[0].data_ptr(), d[1].data_ptr(), out.data_ptr(), d_obst=d[2].data_ptr())
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy(), a.x)
+
+
 @pytest.mark.parametrize("env", ["MPCGPU_BIG_WG", "MPCGPU_GROUPS"])
 def test_optional_kernel_variants_are_bit_identical(env, monkeypatch):
     """The opt-in variants (512-thread stage workgroups -- the kernel long horizons use --, sub-batch streams) run the
