@@ -205,6 +205,25 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
                                  const double* d_orient, const double* d_vdes, int32_t noise_mode, double sigma, uint64_t seed,
                                  double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream);
 int mpc_last_loop_replayed(const mpc_handle* h);
+/* The same loop past per-ego obstacles that move.  obst_track [B, Lt, 3] = (x, y, heading) of ego b's obstacle: Lt = 1, it stands still; Lt >= L,
+ * row i is its pose at loop step i (anything else, or a NULL track: MPC_ERR_INVALID with a message).  The solve of step i sees the obstacle where
+ * it is at step i, FROZEN over that solve's horizon -- the reference's NLP has one static obstacle per solve (optimizer.py:60-64, 395-403); this
+ * is that NLP, re-posed every step (its circle centres: the pose's centre, then +- obst_offset along the heading, compute_centers_of_
+ * approximation_circles, configuration.py:69-93 -- obst_offset = disc_distance / 4 of the obstacle rectangle).  The obstacle's SIZE stays the
+ * handle's: the radius sits in the lower bound of the circle rows given to mpc_set_bounds, one obstacle size per handle.
+ * A frozen obstacle gives no guarantee between steps: the plan of step i-1 kept its distance from the obstacle at step i-1.  A caller who needs a
+ * margin inflates the radius by the obstacle's travel per step.
+ * clearance [B, L] or NULL: clearance[b, i] = min over the three constrained circle pairs (ego circle j, obstacle circle j) of distance - r_sum for
+ * the state BEFORE step i (traj[b, i]) against the obstacle at step i; r_sum = the lower bound of the handle's circle rows.
+ * Noise modes, nx = 5 / 6, step_status, mpc_last_loop_replayed and option "loop_async" as in mpc_closed_loop_batch_ex.                     */
+int mpc_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
+                               const double* orient, const double* vdes, int32_t Lt, const double* obst_track, double obst_offset,
+                               int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_status,
+                               double* clearance);
+int mpc_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                   const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
+                                   int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status,
+                                   double* d_clearance, void* stream);
 /* FORCES-mode stage functions (scope row a11): what `FORCESNLPsolver_casadi2forces` evaluates per stage
  * (test/FORCESNLPsolver/FORCESNLPsolver_interface.c:41-198 -> casadi_f0..f9, FORCESNLPsolver_model.c:75-1756; the model
  * of ForcesproOptimizer, optimizer.py:91-245) for B independent (z, p) pairs.  z [B,7] = (deltaDot, aLong, x, y, delta, v,
@@ -269,6 +288,14 @@ int mpc_validity_batch(mpc_handle* h, int32_t B, int32_t L, const double* traj, 
 int mpc_validity_batch_dev(mpc_handle* h, int32_t B, int32_t L, const double* d_traj, double ego_length, double ego_width, int32_t n_obst,
                            const double* d_obst, int32_t n_left, const double* d_left, int32_t n_right, const double* d_right,
                            int32_t* d_first_collision, int32_t* d_first_off_road, void* stream);
+/* ... with obstacles of its own per trajectory: obst [B,n_obst,L,5], everything else as above (a sweep of egos that each had their own
+ * obstacle, mpc_closed_loop_batch_obst)                                                                                       */
+int mpc_validity_batch_ego(mpc_handle* h, int32_t B, int32_t L, const double* traj, double ego_length, double ego_width, int32_t n_obst,
+                           const double* obst, int32_t n_left, const double* left, int32_t n_right, const double* right,
+                           int32_t* first_collision, int32_t* first_off_road);
+int mpc_validity_batch_ego_dev(mpc_handle* h, int32_t B, int32_t L, const double* d_traj, double ego_length, double ego_width, int32_t n_obst,
+                               const double* d_obst, int32_t n_left, const double* d_left, int32_t n_right, const double* d_right,
+                               int32_t* d_first_collision, int32_t* d_first_off_road, void* stream);
 int mpc_closed_loop_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
                               const double* d_orient, const double* d_vdes, double* d_traj, double* d_ctrl,
                               int32_t* d_step_status, void* stream);

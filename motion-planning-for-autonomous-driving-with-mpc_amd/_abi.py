@@ -80,10 +80,14 @@ PROTOTYPES = {
     "mpc_closed_loop_batch_dev": [_vp, _i32, _i32, _i32] + [_vp] * 8,
     "mpc_closed_loop_batch_ex": [_vp, _i32, _i32, _i32] + [_dp] * 4 + _loop_tail + [_dp, _dp, _ip],
     "mpc_closed_loop_batch_dev_ex": [_vp, _i32, _i32, _i32] + [_vp] * 4 + _loop_tail + [_vp] * 4,
+    "mpc_closed_loop_batch_obst": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _dp, _f64] + _loop_tail + [_dp, _dp, _ip, _dp],
+    "mpc_closed_loop_batch_obst_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64] + _loop_tail + [_vp] * 5,
     "mpc_metrics_batch": [_vp, _i32, _i32, _i32, _dp, _dp, _dp, _f64, _i32, _dp, _dp, _dp],
     "mpc_metrics_batch_dev": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _i32] + [_vp] * 4,
     "mpc_validity_batch": [_vp, _i32, _i32, _dp, _f64, _f64, _i32, _dp, _i32, _dp, _i32, _dp, _ip, _ip],
     "mpc_validity_batch_dev": [_vp, _i32, _i32, _vp, _f64, _f64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp],
+    "mpc_validity_batch_ego": [_vp, _i32, _i32, _dp, _f64, _f64, _i32, _dp, _i32, _dp, _i32, _dp, _ip, _ip],
+    "mpc_validity_batch_ego_dev": [_vp, _i32, _i32, _vp, _f64, _f64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp],
     "mpc_forces_stage_eval": [_vp, _i32, _i32] + [_dp] * 8,
     "mpc_forces_solve_batch": [_vp, _i32] + [_dp] * 7 + [_i32, _dp, _ip, _ip, _dp],
     "mpc_forces_solve_batch_dev": [_vp, _i32, _vp, _vp, _vp, _dp, _dp, _dp, _dp, _i32] + [_vp] * 5,

@@ -135,6 +135,46 @@ MPC_HD void loop_advance_instance(const PRef& P, const LoopArgs& A, int b, int i
 }
 
 // =========================================================================================================================
+// Per-ego obstacles that move (mpc_closed_loop_batch_obst): the solve of loop step i sees ego b's obstacle where it is AT step i,
+// frozen over that solve's horizon -- the reference's NLP has one static obstacle per solve (optimizer.py:60-64, 395-403), so this
+// is that NLP, re-posed every step with other centres.  Before solve i the row of ego b in a [B, 6] buffer (the `obst` rows of
+// the solve) is written from its track; the solve kernels see nothing new.
+// =========================================================================================================================
+struct LoopObstArgs {
+    int32_t B, L, Lt, nx;            // instances, loop steps, poses per track (1: the obstacle stands still; >= L: pose i at step i), states per row of `state`
+    const double* track;             // [B,Lt,3] pose of ego b's obstacle: x, y, heading
+    double offset;                   // front / rear circle centres: +- offset along the heading (disc_distance / 4 of the obstacle rectangle)
+    double* obst;                    // [B,6]  circle centres of the next solve (order of mpc_problem_desc::obstacle)
+    const double* state;             // [B,nx] current plant state (LoopArgs::state)
+    double* clearance;               // [B,L]  loop_clearance of the state before step i against the obstacle at step i, or null
+    double r_sum;                    // sum of the two circle radii: the lower bound of the handle's circle rows
+    const uint32_t* abort_flag;      // as LoopArgs::abort_flag
+};
+// compute_centers_of_approximation_circles (configuration.py:69-93): the centre, then +- offset along the heading
+MPC_HD void loop_obstacle_centres(const double* row /* x, y, heading */, double offset, double* c6) {
+    const double cs = cos(row[2]), sn = sin(row[2]);
+    c6[0] = row[0];               c6[1] = row[1];
+    c6[2] = row[0] + offset * cs; c6[3] = row[1] + offset * sn;
+    c6[4] = row[0] - offset * cs; c6[5] = row[1] - offset * sn;
+}
+// minimum over the three constrained pairs (ego circle j against obstacle circle j, optimizer.py:395-403) of distance - r_sum; the ego
+// circles as the NLP builds them (circle_eval, P.ego_offset)
+MPC_HD double loop_clearance(const Params& P, const double* state5, const double* c6, double r_sum) {
+    const Trig tg = psi_trig(state5[4]);
+    double best = circle_eval(P, c6, 0, state5[0], state5[1], tg.sps, tg.cps, nullptr, nullptr, false);
+    for (int j = 1; j < 3; ++j) best = fmin(best, circle_eval(P, c6, j, state5[0], state5[1], tg.sps, tg.cps, nullptr, nullptr, false));
+    return best - r_sum;
+}
+// before solve i
+MPC_HD void loop_obst_instance(const Params& P, const LoopObstArgs& A, int b, int i) {
+    const int row = i < A.Lt - 1 ? i : A.Lt - 1;
+    double c6[6];
+    loop_obstacle_centres(A.track + ((size_t)b * A.Lt + row) * 3, A.offset, c6);
+    for (int q = 0; q < 6; ++q) A.obst[(size_t)b * 6 + q] = c6[q];
+    if (A.clearance) A.clearance[(size_t)b * A.L + i] = loop_clearance(P, A.state + (size_t)b * A.nx, c6, A.r_sum);
+}
+
+// =========================================================================================================================
 // The FORCES-mode loop (ForcesproOptimizer.optimize, MPC_Planner/optimizer.py:246-366) around `solver.solve(problem)`:
 //   * the guess problem["x0"] is the tiled initial point and is NEVER refreshed                              :264-274
 //   * run-time parameters of step k: the next N path points / orientations (replenished with the last one), the desired

@@ -1984,9 +1984,9 @@ __device__ __forceinline__ double seg_side(const double* poly, int n, double px,
     }
     return side;
 }
-__global__ void __launch_bounds__(128) k_validity(int L, const double* traj, double ego_l, double ego_w, int n_obst, const double* obst, int n_left,
-                                                  const double* left, int n_right, const double* right, int32_t* first_collision,
-                                                  int32_t* first_off_road) {
+__device__ __forceinline__ void validity_block(int L, const double* traj, double ego_l, double ego_w, int n_obst, const double* obst, int n_left,
+                                               const double* left, int n_right, const double* right, int32_t* first_collision,
+                                               int32_t* first_off_road) {
 #pragma clang fp contract(off)
     __shared__ int s_col, s_off;
     const int b = blockIdx.x, t = threadIdx.x;
@@ -2029,6 +2029,18 @@ __global__ void __launch_bounds__(128) k_validity(int L, const double* traj, dou
         first_collision[b] = s_col == 0x7fffffff ? -1 : s_col;
         first_off_road[b] = s_off == 0x7fffffff ? -1 : s_off;
     }
+}
+__global__ void __launch_bounds__(128) k_validity(int L, const double* traj, double ego_l, double ego_w, int n_obst, const double* obst, int n_left,
+                                                  const double* left, int n_right, const double* right, int32_t* first_collision,
+                                                  int32_t* first_off_road) {
+    validity_block(L, traj, ego_l, ego_w, n_obst, obst, n_left, left, n_right, right, first_collision, first_off_road);
+}
+// ... against obstacles of its own per trajectory: obst [B, n_obst, L, 5]
+__global__ void __launch_bounds__(128) k_validity_ego(int L, const double* traj, double ego_l, double ego_w, int n_obst, const double* obst, int n_left,
+                                                      const double* left, int n_right, const double* right, int32_t* first_collision,
+                                                      int32_t* first_off_road) {
+    validity_block(L, traj, ego_l, ego_w, n_obst, obst + (size_t)blockIdx.x * (size_t)n_obst * (size_t)L * 5, n_left, left, n_right, right, first_collision,
+                   first_off_road);
 }
 
 // FORCES-mode stage functions (row a11; FORCESNLPsolver_interface.c:41-198 / FORCESNLPsolver_model.c:75-1756, the model of
@@ -2299,6 +2311,13 @@ __global__ void __launch_bounds__(128) k_loop_advance(const Params Pk, const Loo
 __global__ void k_loop_sticky(const uint32_t* pipe_abort, uint32_t* loop_abort) {
     if (*pipe_abort != 0u) *loop_abort = 1u;
 }
+// before solve i of a loop with per-ego obstacles (mpc_closed_loop.h: LoopObstArgs): one ego per thread writes its row of the solve's
+// obstacle centres from its track, and the clearance of its current state if asked
+__global__ void __launch_bounds__(128) k_loop_obst(const Params Pk, const LoopObstArgs A, const int i) {
+    if (A.abort_flag != nullptr && *A.abort_flag != 0u) return;       // (as k_loop_advance)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < A.B) loop_obst_instance(Pk, A, b, i);
+}
 
 // FORCES-mode closed loop (mpc_closed_loop.h: ForcesLoopArgs), one instance per thread
 __global__ void k_floop_setup(const ForcesLoopArgs A) {
@@ -2554,6 +2573,7 @@ enum Scratch : int {
     SCR_SENS_F,                         // sens_launch: the factors of the KKT matrices
     SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
     SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
+    SCR_LOOP_OBST,                      // closed_loop_dev: the obstacle rows of a loop with per-ego obstacle tracks (k_loop_obst)
     N_SCRATCH
 };
 
@@ -3774,9 +3794,13 @@ int mpc_plant_step(mpc_handle* h, int32_t B, int32_t integrator, const double* x
                       [&](void** d, hipStream_t s) { return mpc_plant_step_dev(h, B, integrator, (double*)d[0], (double*)d[1], (double*)d[2], s); });
 }
 
-int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
-                                 const double* d_orient, const double* d_vdes, int32_t noise_mode, double sigma, uint64_t seed,
-                                 double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream_) {
+// per-ego obstacle tracks of a closed loop (mpc_closed_loop_batch_obst[_dev]); the plain loop has none
+struct LoopTrack { int32_t Lt; const double* d_track; double offset; double* d_clearance; };
+
+// the closed loop of every entry point, with `track` (k_loop_obst in front of every solve, whose rows then carry the obstacle centres) or without
+static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                           const double* d_orient, const double* d_vdes, const LoopTrack* track, int32_t noise_mode, double sigma, uint64_t seed,
+                           double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream_) {
     if (!h) return MPC_ERR_INVALID;
     const mpc_problem_desc& d = h->hp.desc;
     if (B <= 0 || L <= 0 || Lp < L || L < d.N || !d_init_state || !d_path || !d_orient || !d_vdes || !d_traj || !d_ctrl) {
@@ -3784,11 +3808,17 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
         return MPC_ERR_INVALID;
     }
     if (noise_mode < 0 || noise_mode > 2 || (noise_mode != 0 && !(sigma >= 0.0))) { h->err = "closed loop: noise_mode in {0, 1, 2}, sigma >= 0"; return MPC_ERR_INVALID; }
+    if (track && (!track->d_track || (track->Lt != 1 && track->Lt < L) || !std::isfinite(track->offset))) {
+        h->err = "closed loop: obst_track [B, Lt, 3] is required, with Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i), and a finite obst_offset";
+        return MPC_ERR_INVALID;
+    }
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_io(h, (size_t)B);
     if (rc) return rc;
+    double* d_obst = nullptr;
+    if (track && !(d_obst = static_cast<double*>(scratch_get(h, SCR_LOOP_OBST, (size_t)B * 6 * sizeof(double))))) { h->err = "out of device memory"; return MPC_ERR_HIP; }
     // the rows of every solve of the loop: the handle's own (begin_solve: the bounds must be set)
-    const SolveIo io = solve_io(h, B, h->d_x0, h->d_p, nullptr, h->d_xout, h->d_status, h->d_iters, h->d_kkt);
+    const SolveIo io = solve_io(h, B, h->d_x0, h->d_p, d_obst, h->d_xout, h->d_status, h->d_iters, h->d_kkt);
     if ((rc = begin_solve(h, io))) return rc;
     if (h->cap_state < (size_t)B) {
         if (h->d_state) (void)hipFree(h->d_state);
@@ -3805,18 +3835,30 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
     A.noise_mode = noise_mode; A.sigma = sigma; A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32);
     const Params P = plant_params(h);
     const dim3 grid((B + 127) / 128), block(128);
+    // before solve i, with a track: ego b's row of the solve's obstacle centres (stream order keeps it until solve i, its second chance and any
+    // restart have read it), and the clearance of its state
+    LoopObstArgs O{};
+    Params PO = P;
+    if (track) {
+        O.B = B; O.L = L; O.Lt = track->Lt; O.nx = d.nx;
+        O.track = track->d_track; O.offset = track->offset; O.obst = d_obst; O.state = h->d_state; O.clearance = track->d_clearance;
+        O.r_sum = h->hp.ol_raw;
+        PO.ego_offset = d.ego_offset;
+    }
+    const auto place_obstacles = [&](int i) { if (track) hipLaunchKernelGGL(k_loop_obst, grid, block, 0, stream, PO, O, i); };
     // First attempt: the whole loop enqueued without a single host synchronisation (every solve in the persistent pipeline
     // launch, which needs no convergence poll).  What could go wrong on the way -- a pipeline launch abandoned, an instance
     // that needs the second chance -- is recorded on the device and looked at ONCE, at the end; then the loop is replayed
     // step by step with the host in between (the per-kernel path polls for convergence, the second chance needs the count).
     bool replay = true, loop_abandoned = false;
-    if (plan_solve(h->hp, h->knobs, plan_state(h, B, false, false, false)).loop_async) {
+    if (plan_solve(h->hp, h->knobs, plan_state(h, B, track != nullptr, false, false)).loop_async) {
         HIP_TRY(h, hipMemsetAsync(h->d_fail, 0, FAIL_WORDS * sizeof(uint32_t), stream));
-        A.abort_flag = h->d_fail + FAIL_LOOP_ABORT;
+        A.abort_flag = O.abort_flag = h->d_fail + FAIL_LOOP_ABORT;
         hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
         h->async_loop = true;
         bool all_async = true;
         for (int i = 0; i < L && all_async; ++i) {
+            place_obstacles(i);
             rc = solve_dev_any(h, io, stream, false);
             if (rc) { h->async_loop = false; return rc; }
             all_async = h->async_ok;             // (a batch shape the pipeline does not take: the solve has run synchronously -- start over)
@@ -3836,9 +3878,10 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
     }
     h->loop_replayed = replay ? 1 : 0;
     if (replay) {
-        A.abort_flag = nullptr;
+        A.abort_flag = O.abort_flag = nullptr;
         hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
         for (int i = 0; i < L; ++i) {
+            place_obstacles(i);
             rc = solve_dev(h, io, stream);
             if (rc) return rc;
             hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
@@ -3847,6 +3890,38 @@ int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
     if (loop_abandoned && ++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;         // (see solve_dev_impl)
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
+}
+
+int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                 const double* d_orient, const double* d_vdes, int32_t noise_mode, double sigma, uint64_t seed,
+                                 double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream_) {
+    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, nullptr, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, stream_);
+}
+
+int mpc_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                   const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
+                                   int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status,
+                                   double* d_clearance, void* stream_) {
+    const LoopTrack track{Lt, d_obst_track, obst_offset, d_clearance};
+    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, &track, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, stream_);
+}
+
+int mpc_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                               const double* vdes, int32_t Lt, const double* obst_track, double obst_offset, int32_t noise_mode, double sigma,
+                               uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
+    if (!obst_track || (Lt != 1 && Lt < L)) {
+        h->err = "closed loop: obst_track [B, Lt, 3] is required, with Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i)";
+        return MPC_ERR_INVALID;
+    }
+    const size_t nB = (size_t)B;
+    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
+                          {obst_track, nB * Lt * 3 * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true}, {step_status, nB * L * 4, true},
+                          {clearance, nB * L * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_closed_loop_batch_obst_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], obst_offset, noise_mode,
+                                              sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], (double*)d[8], s);
+    });
 }
 
 int mpc_closed_loop_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
@@ -3902,9 +3977,10 @@ int mpc_metrics_batch(mpc_handle* h, int32_t B, int32_t L, int32_t Lo, const dou
     });
 }
 
-int mpc_validity_batch_dev(mpc_handle* h, int32_t B, int32_t L, const double* d_traj, double ego_length, double ego_width, int32_t n_obst,
-                           const double* d_obst, int32_t n_left, const double* d_left, int32_t n_right, const double* d_right,
-                           int32_t* d_first_collision, int32_t* d_first_off_road, void* stream_) {
+// the verdict of both entry-point pairs: obstacles shared by the batch [n_obst, L, 5] (k_validity) or per trajectory [B, n_obst, L, 5] (k_validity_ego)
+static int validity_dev(mpc_handle* h, bool per_ego, int32_t B, int32_t L, const double* d_traj, double ego_length, double ego_width, int32_t n_obst,
+                        const double* d_obst, int32_t n_left, const double* d_left, int32_t n_right, const double* d_right,
+                        int32_t* d_first_collision, int32_t* d_first_off_road, void* stream_) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || L <= 0 || !d_traj || !d_first_collision || !d_first_off_road || n_obst < 0 || (n_obst > 0 && !d_obst) ||
         (n_left > 0 && !d_left) || (n_right > 0 && !d_right) || !(ego_length > 0.0) || !(ego_width > 0.0)) {
@@ -3912,24 +3988,44 @@ int mpc_validity_batch_dev(mpc_handle* h, int32_t B, int32_t L, const double* d_
         return MPC_ERR_INVALID;
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_validity, dim3(B), dim3(128), 0, (hipStream_t)stream_, L, d_traj, ego_length, ego_width, n_obst, d_obst, n_left, d_left, n_right,
-                       d_right, d_first_collision, d_first_off_road);
+    hipLaunchKernelGGL(per_ego ? k_validity_ego : k_validity, dim3(B), dim3(128), 0, (hipStream_t)stream_, L, d_traj, ego_length, ego_width, n_obst, d_obst, n_left,
+                       d_left, n_right, d_right, d_first_collision, d_first_off_road);
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
-
-int mpc_validity_batch(mpc_handle* h, int32_t B, int32_t L, const double* traj, double ego_length, double ego_width, int32_t n_obst,
-                       const double* obst, int32_t n_left, const double* left, int32_t n_right, const double* right,
-                       int32_t* first_collision, int32_t* first_off_road) {
+static int validity_host(mpc_handle* h, bool per_ego, int32_t B, int32_t L, const double* traj, double ego_length, double ego_width, int32_t n_obst,
+                         const double* obst, int32_t n_left, const double* left, int32_t n_right, const double* right,
+                         int32_t* first_collision, int32_t* first_off_road) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || L <= 0 || !traj || !first_collision || !first_off_road) { h->err = "validity: B, L > 0, traj and both outputs are required"; return MPC_ERR_INVALID; }
     const size_t nB = (size_t)B;
-    return stage_host(h, {{traj, nB * L * 5 * 8, false}, {n_obst > 0 ? obst : nullptr, (size_t)std::max(n_obst, 0) * L * 5 * 8, false},
+    return stage_host(h, {{traj, nB * L * 5 * 8, false}, {n_obst > 0 ? obst : nullptr, (per_ego ? nB : 1) * (size_t)std::max(n_obst, 0) * L * 5 * 8, false},
                           {n_left > 0 ? left : nullptr, (size_t)std::max(n_left, 0) * 2 * 8, false}, {n_right > 0 ? right : nullptr, (size_t)std::max(n_right, 0) * 2 * 8, false},
                           {first_collision, nB * 4, true}, {first_off_road, nB * 4, true}}, [&](void** d, hipStream_t s) {
-        return mpc_validity_batch_dev(h, B, L, (double*)d[0], ego_length, ego_width, n_obst, (double*)d[1], n_left, (double*)d[2], n_right, (double*)d[3],
-                                      (int32_t*)d[4], (int32_t*)d[5], s);
+        return validity_dev(h, per_ego, B, L, (double*)d[0], ego_length, ego_width, n_obst, (double*)d[1], n_left, (double*)d[2], n_right, (double*)d[3],
+                            (int32_t*)d[4], (int32_t*)d[5], s);
     });
+}
+
+int mpc_validity_batch_dev(mpc_handle* h, int32_t B, int32_t L, const double* d_traj, double ego_length, double ego_width, int32_t n_obst,
+                           const double* d_obst, int32_t n_left, const double* d_left, int32_t n_right, const double* d_right,
+                           int32_t* d_first_collision, int32_t* d_first_off_road, void* stream_) {
+    return validity_dev(h, false, B, L, d_traj, ego_length, ego_width, n_obst, d_obst, n_left, d_left, n_right, d_right, d_first_collision, d_first_off_road, stream_);
+}
+int mpc_validity_batch_ego_dev(mpc_handle* h, int32_t B, int32_t L, const double* d_traj, double ego_length, double ego_width, int32_t n_obst,
+                               const double* d_obst, int32_t n_left, const double* d_left, int32_t n_right, const double* d_right,
+                               int32_t* d_first_collision, int32_t* d_first_off_road, void* stream_) {
+    return validity_dev(h, true, B, L, d_traj, ego_length, ego_width, n_obst, d_obst, n_left, d_left, n_right, d_right, d_first_collision, d_first_off_road, stream_);
+}
+int mpc_validity_batch(mpc_handle* h, int32_t B, int32_t L, const double* traj, double ego_length, double ego_width, int32_t n_obst,
+                       const double* obst, int32_t n_left, const double* left, int32_t n_right, const double* right,
+                       int32_t* first_collision, int32_t* first_off_road) {
+    return validity_host(h, false, B, L, traj, ego_length, ego_width, n_obst, obst, n_left, left, n_right, right, first_collision, first_off_road);
+}
+int mpc_validity_batch_ego(mpc_handle* h, int32_t B, int32_t L, const double* traj, double ego_length, double ego_width, int32_t n_obst,
+                           const double* obst, int32_t n_left, const double* left, int32_t n_right, const double* right,
+                           int32_t* first_collision, int32_t* first_off_road) {
+    return validity_host(h, true, B, L, traj, ego_length, ego_width, n_obst, obst, n_left, left, n_right, right, first_collision, first_off_road);
 }
 
 int mpc_forces_stage_eval(mpc_handle* h, int32_t B, int32_t terminal, const double* z, const double* p, double* f, double* grad_f,

@@ -117,7 +117,9 @@ class MPCPlanner(object):
         be = self._backend()
         deviation = deviation_euclidean_dis(be, x, conf.origin_reference_path)
         rmsd = compute_rmsd(be, x, conf.reference_path) if conf.use_case == "lane_following" else None
-        self.results = dict(states=x, controls=u, solve_time=solve_time, deviation=deviation, rmsd=rmsd)
+        # (clearance: distance - r_sum of every step against the tracked obstacle at that step, from the device loop of a configuration with
+        #  an obstacle_track; None otherwise)
+        self.results = dict(states=x, controls=u, solve_time=solve_time, deviation=deviation, rmsd=rmsd, clearance=getattr(self._optimizer, "clearance", None))
         if save_dir is not None:
             os.makedirs(save_dir, exist_ok=True)
             np.savetxt(os.path.join(save_dir, "deviation.txt"), deviation)
@@ -126,6 +128,8 @@ class MPCPlanner(object):
             np.savetxt(os.path.join(save_dir, "planned states.txt"), x)
             if rmsd is not None:
                 np.savetxt(os.path.join(save_dir, "RMSD.txt"), np.asarray(rmsd).reshape(2, 1))
+            if self.results["clearance"] is not None:
+                np.savetxt(os.path.join(save_dir, "clearance.txt"), self.results["clearance"])
         return trajectory, ego_vehicle
 
     def collision_check(self):

@@ -128,7 +128,8 @@ class NlpSolverHandle:
         self._backend = backend
         self._stats = {}
 
-    def __call__(self, x0=None, p=None, lbg=None, lbx=None, ubg=None, ubx=None, **_unused):
+    def __call__(self, x0=None, p=None, lbg=None, lbx=None, ubg=None, ubx=None, obst=None, **_unused):
+        """obst (not a CasADi keyword): circle centres [6] / [B, 6] of this solve's obstacle instead of the template's (BatchedMPCSolver.solve)"""
         be = self._backend
         x0a = np.asarray(x0.full() if hasattr(x0, "full") else x0, dtype=np.float64)
         pa = np.asarray(p.full() if hasattr(p, "full") else p, dtype=np.float64)
@@ -140,7 +141,8 @@ class NlpSolverHandle:
         if lbg is not None or lbx is not None or ubg is not None or ubx is not None:
             be.set_bounds(lbx, ubx, lbg, ubg)
         full = isinstance(be, BatchedMPCSolver)
-        res = be.solve(x0a, pa, multipliers=True) if full else be.solve(x0a, pa)
+        kw = {} if obst is None else dict(obst=np.asarray(obst, dtype=np.float64).reshape(x0a.shape[0], 6))
+        res = be.solve(x0a, pa, multipliers=True, **kw) if full else be.solve(x0a, pa, **kw)
         rescued = np.zeros(res.status.shape[0], dtype=bool)
         n_rescued = int(be.last_rescued()) if hasattr(be, "last_rescued") else 0      # the second chance behind the C-ABI (a count, not a mask)
         if (self.rescue and not isinstance(be, BatchedMPCSolver) and not np.all(res.status == 1) and lbg is not None and lbx is not None
@@ -191,6 +193,18 @@ class Optimizer(object):
             so["position_x"], so["position_y"], so["length"], so["width"], so["orientation"])
         self.radius_obstacle, _ = compute_approximating_circle_radius(so["length"], so["width"])
         self.radius_ego, _ = compute_approximating_circle_radius(configuration.p.l, configuration.p.w)
+        # optional (not in the reference): the obstacle's pose (x, y, heading) at every loop step, [L, 3]; its length and width stay static_obstacle's
+        track = getattr(configuration, "obstacle_track", None)
+        self.obstacle_track = None if track is None else np.asarray(track, dtype=np.float64).reshape(-1, 3)
+        _, disc_distance = compute_approximating_circle_radius(so["length"], so["width"])
+        self.obstacle_offset = (disc_distance / 2) / 2
+        self.clearance = None           # optimize() with a track, device loop: distance - r_sum of every step (include/mpcgpu.h, mpc_closed_loop_batch_obst)
+
+    def obstacle_centers_at(self, step):
+        """circle centres [6] of the tracked obstacle at loop step `step` (the last pose once the track ends)"""
+        x, y, th = self.obstacle_track[min(step, len(self.obstacle_track) - 1)]
+        so = self.configuration.static_obstacle
+        return np.array(compute_centers_of_approximation_circles(x, y, so["length"], so["width"], th), dtype=np.float64).ravel()
 
     def equal_constraints(self, *args, **kwargs):
         pass
@@ -277,9 +291,15 @@ class CasadiOptimizer(Optimizer):
             t_ = time.time()
             backend.set_bounds(lbx, ubx, lbg, ubg)
             init_state = np.array([self.init_position[0], self.init_position[1], 0.0, self.init_velocity, self.init_orientation])
-            traj, ctrl, st = backend.closed_loop(init_state, self.resampled_path_points, self.orientation, self.desired_velocity,
-                                                 self.iter_length, noise_mode=1 if noised else 0, sigma=sigma if noised else 0.0,
-                                                 seed=0 if seed is None else int(seed))
+            loop_kw = dict(noise_mode=1 if noised else 0, sigma=sigma if noised else 0.0, seed=0 if seed is None else int(seed))
+            if self.obstacle_track is None:
+                traj, ctrl, st = backend.closed_loop(init_state, self.resampled_path_points, self.orientation, self.desired_velocity, self.iter_length, **loop_kw)
+            else:
+                # every solve sees the obstacle where it is at its step, frozen over the horizon (mpc_closed_loop_batch_obst)
+                track = self.obstacle_track[np.minimum(np.arange(self.iter_length), len(self.obstacle_track) - 1)][None]
+                traj, ctrl, st, cl = backend.closed_loop(init_state, self.resampled_path_points, self.orientation, self.desired_velocity, self.iter_length,
+                                                         obst_track=track, obst_offset=self.obstacle_offset, clearance=True, **loop_kw)
+                self.clearance = cl[0]
             ok = bool(np.all(st == 1))
             sol._stats = dict(status=st[0].copy(), success=ok, return_status="Solve_Succeeded" if ok else "Not_Converged")
             return traj[0], ctrl[0], np.full(self.iter_length, (time.time() - t_) / self.iter_length)
@@ -295,7 +315,8 @@ class CasadiOptimizer(Optimizer):
             w0 = self.warm_start(plan_u, plan_x, first=(step == 0))
             tic = time.time()
             sol, f = self.solver()
-            w = sol(x0=w0, p=p_vec, lbg=lbg, lbx=lbx, ubg=ubg, ubx=ubx)["x"].full().ravel()
+            obst_kw = {} if self.obstacle_track is None else dict(obst=self.obstacle_centers_at(step))      # (the obstacle where it is at this step)
+            w = sol(x0=w0, p=p_vec, lbg=lbg, lbx=lbx, ubg=ubg, ubx=ubx, **obst_kw)["x"].full().ravel()
             seconds.append(time.time() - tic)
             plan_u = w[:num_controls * N].reshape(N, num_controls).T
             plan_x = w[num_controls * N:].reshape(N + 1, num_states).T

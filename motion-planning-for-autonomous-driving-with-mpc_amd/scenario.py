@@ -364,7 +364,14 @@ class Configuration(object):
         c.noised = self.settings["general_planning_settings"]["noised"]
         c.weights_setting = self.settings["weights_setting"]
         c.use_case = self.settings["scenario_settings"]["use_case"]
-        if c.use_case == "collision_avoidance":
+        # optional (not in the reference): scenario_settings.dynamic_obstacle_id names a moving obstacle of the scenario to plan around -- its pose at
+        # every loop step goes to the optimizer (the solve of a step sees it where it is at that step), its rectangle is the obstacle's size
+        dyn_id = self.settings["scenario_settings"].get("dynamic_obstacle_id")
+        if c.use_case == "collision_avoidance" and dyn_id is not None:
+            c.obstacle_track, length, width = obstacle_track(self.scenario, dyn_id, c.iter_length)
+            c.static_obstacle = {"position_x": c.obstacle_track[0, 0], "position_y": c.obstacle_track[0, 1], "length": length, "width": width,
+                                 "orientation": c.obstacle_track[0, 2]}
+        elif c.use_case == "collision_avoidance":
             o = self.scenario.obstacles[0]
             c.static_obstacle = {"position_x": o.position[0], "position_y": o.position[1], "length": o.length, "width": o.width,
                                  "orientation": o.orientation}
@@ -389,6 +396,23 @@ def obstacle_rectangles(scenario, steps):
                 r[i] = [o.states[i][0], o.states[i][1], o.length, o.width, o.states[i][2]]
         rows.append(r)
     return np.array(rows) if rows else np.zeros((0, steps, 5))
+
+
+def obstacle_track(scenario, obstacle_id, steps):
+    """([steps, 3] poses (x, y, orientation) of the moving obstacle `obstacle_id` at time steps 0 .. steps-1, its length, its width) -- the
+    obst_track of BatchedMPCSolver.closed_loop.  Before its first recorded state it stands at that state, after its last one it holds
+    the last pose; a time step missing in between holds the one before."""
+    for o in scenario.dynamic_obstacles:
+        if o.obstacle_id == int(obstacle_id):
+            break
+    else:
+        raise KeyError("no dynamic obstacle {} in the scenario".format(obstacle_id))
+    times = sorted(o.states)
+    track = np.empty((int(steps), 3))
+    for i in range(int(steps)):
+        known = [t for t in times if t <= i]
+        track[i] = o.states[known[-1] if known else times[0]]
+    return track, o.length, o.width
 
 
 def road_corridor(scenario, lanelet_ids, include_oncoming=True):
@@ -428,6 +452,6 @@ def init_values(scenario, planning_problem_id=None):
     return pp.initial_position, pp.initial_velocity, pp.initial_acceleration, pp.initial_orientation
 
 
-__all__ = ["read_scenario", "Configuration", "init_values", "plan_route", "obstacle_rectangles", "road_corridor", "clip_reference_path", "find_closest_point",
+__all__ = ["read_scenario", "Configuration", "init_values", "plan_route", "obstacle_rectangles", "obstacle_track", "road_corridor", "clip_reference_path", "find_closest_point",
            "chaikins_corner_cutting", "resample_polyline", "compute_polyline_length", "compute_orientation_from_polyline",
            "parameters_vehicle2"]

@@ -302,11 +302,14 @@ class BatchedMPCSolver:
                                              _abi.as_dp(out)))
         return out[0] if single else out
 
-    def closed_loop(self, init_state, path, orient, vdes, steps, noise_mode=0, sigma=0.0, seed=0):
+    def closed_loop(self, init_state, path, orient, vdes, steps, noise_mode=0, sigma=0.0, seed=0, obst_track=None, obst_offset=0.0, clearance=False):
         """B egos through `steps` receding-horizon steps on the device (include/mpcgpu.h: mpc_closed_loop_batch_ex; the loop
         body of CasadiOptimizer.optimize, optimizer.py:596-631).  init_state [B,5], path [B,Lp,2], orient [B,Lp],
         vdes [B] -> (traj [B,steps,5], ctrl [B,steps,2], step_status [B,steps]).  noise_mode / sigma / seed: the reference's
-        `noised: True` with a counter-based generator (noise.py holds the Python mirror of the samples)."""
+        `noised: True` with a counter-based generator (noise.py holds the Python mirror of the samples).
+        obst_track [B,Lt,3] (x, y, heading; Lt = 1: standing still, Lt >= steps: row i at step i; [B,3] = Lt 1): every ego past an obstacle of
+        its own, frozen over each solve's horizon (mpc_closed_loop_batch_obst); obst_offset: its front / rear circle centres along the heading.
+        clearance=True (with a track): a fourth return value [B,steps], see include/mpcgpu.h."""
         init_state = _abi.f64(init_state)
         if init_state.ndim == 1:
             init_state = init_state[None]
@@ -319,17 +322,35 @@ class BatchedMPCSolver:
         traj = np.empty((B, steps, 5))
         ctrl = np.empty((B, steps, 2))
         st = np.empty((B, steps), np.int32)
-        self._check(self._lib.mpc_closed_loop_batch_ex(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient),
-                                                       _abi.as_dp(vdes), int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), _abi.as_dp(traj),
-                                                       _abi.as_dp(ctrl), _abi.as_ip(st)))
-        return traj, ctrl, st
+        tail = (int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), _abi.as_dp(traj), _abi.as_dp(ctrl), _abi.as_ip(st))
+        if obst_track is None:
+            if clearance:
+                raise MpcError(_abi.MPC_ERR_INVALID, "clearance needs obst_track")
+            self._check(self._lib.mpc_closed_loop_batch_ex(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient),
+                                                           _abi.as_dp(vdes), *tail))
+            return traj, ctrl, st
+        track = _abi.f64(obst_track)
+        if track.ndim == 1:
+            track = track[None]
+        if track.ndim == 2:                                    # one ego: its poses; a batch: one standing pose per ego
+            track = track[None] if B == 1 else track[:, None, :]
+        if track.ndim != 3 or track.shape[0] != B or track.shape[2] != 3:
+            raise MpcError(_abi.MPC_ERR_INVALID, "obst_track must be [B, Lt, 3]")
+        cl = np.empty((B, steps)) if clearance else None
+        self._check(self._lib.mpc_closed_loop_batch_obst(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient),
+                                                         _abi.as_dp(vdes), track.shape[1], _abi.as_dp(track), float(obst_offset), *tail, _abi.as_dp(cl)))
+        return (traj, ctrl, st, cl) if clearance else (traj, ctrl, st)
 
     def closed_loop_device(self, B, d_init_state, d_path, d_orient, d_vdes, steps, Lp, d_traj, d_ctrl, d_step_status=0, noise_mode=0, sigma=0.0,
-                           seed=0, stream=0):
-        """device-pointer form (ints): the whole loop is enqueued on `stream`; see mpc_closed_loop_batch_dev_ex"""
-        self._check(self._lib.mpc_closed_loop_batch_dev_ex(self._h, int(B), int(steps), int(Lp), _vp(d_init_state), _vp(d_path), _vp(d_orient), _vp(d_vdes),
-                                                           int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl),
-                                                           _vp(d_step_status), _vp(stream)))
+                           seed=0, stream=0, d_obst_track=0, Lt=0, obst_offset=0.0, d_clearance=0):
+        """device-pointer form (ints): the whole loop is enqueued on `stream`; see mpc_closed_loop_batch_dev_ex, and with d_obst_track [B,Lt,3]
+        (d_clearance [B,steps] or 0) mpc_closed_loop_batch_obst_dev"""
+        head = (self._h, int(B), int(steps), int(Lp), _vp(d_init_state), _vp(d_path), _vp(d_orient), _vp(d_vdes))
+        tail = (int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl), _vp(d_step_status))
+        if d_obst_track or Lt:
+            self._check(self._lib.mpc_closed_loop_batch_obst_dev(*head, int(Lt), _vp(d_obst_track), float(obst_offset), *tail, _vp(d_clearance), _vp(stream)))
+        else:
+            self._check(self._lib.mpc_closed_loop_batch_dev_ex(*head, *tail, _vp(stream)))
 
     def last_loop_replayed(self):
         return bool(self._lib.mpc_last_loop_replayed(self._h))
@@ -357,11 +378,12 @@ class BatchedMPCSolver:
                                                 _abi.as_dp(cl)))
         return dict(deviation=dev, rmsd=rm, clearance=cl)
 
-    def validity(self, traj, obstacles=None, left=None, right=None, ego_length=4.3, ego_width=1.8):
+    def validity(self, traj, obstacles=None, left=None, right=None, ego_length=4.3, ego_width=1.8, per_ego=None):
         """collision / road verdict of B planned trajectories [B,L,5] on the device (mpc_validity_batch; the check of the
         reference's test, test/test_mpc_planner.py:37-47).  obstacles: [n,5] static rectangles (x, y, length, width, orientation)
         or [n,L,5] per time step; left / right: boundary polylines [m,2] of the drivable corridor in driving direction.
-        Returns dict(first_collision [B], first_off_road [B]) -- step index or -1."""
+        per_ego=True, or a 4-d array: obstacles [B,n,L,5] ([B,n,5] with per_ego=True: static), every trajectory against its own
+        (mpc_validity_batch_ego).  Returns dict(first_collision [B], first_off_road [B]) -- step index or -1."""
         traj = _abi.f64(traj)
         if traj.ndim == 2:
             traj = traj[None]
@@ -369,16 +391,27 @@ class BatchedMPCSolver:
         n_obst, ob = 0, None
         if obstacles is not None and len(obstacles):
             ob = np.asarray(obstacles, dtype=np.float64)
-            if ob.ndim == 2:
-                ob = np.repeat(ob[:, None, :], L, axis=1)
-            ob = _abi.f64(ob[:, :L])
-            n_obst = ob.shape[0]
+            if per_ego is None:
+                per_ego = ob.ndim == 4
+            if per_ego:
+                if ob.ndim == 3:
+                    ob = np.repeat(ob[:, :, None, :], L, axis=2)
+                if ob.ndim != 4 or ob.shape[0] != B or ob.shape[2] < L or ob.shape[3] != 5:
+                    raise MpcError(_abi.MPC_ERR_INVALID, f"per-ego obstacles must be [B = {B}, n, L >= {L}, 5]")
+                ob = _abi.f64(ob[:, :, :L])
+                n_obst = ob.shape[1]
+            else:
+                if ob.ndim == 2:
+                    ob = np.repeat(ob[:, None, :], L, axis=1)
+                ob = _abi.f64(ob[:, :L])
+                n_obst = ob.shape[0]
         lf = None if left is None else _abi.f64(left).reshape(-1, 2)
         rt = None if right is None else _abi.f64(right).reshape(-1, 2)
         fc, fo = np.empty(B, np.int32), np.empty(B, np.int32)
-        self._check(self._lib.mpc_validity_batch(self._h, B, L, _abi.as_dp(traj), float(ego_length), float(ego_width), n_obst, _abi.as_dp(ob),
-                                                 0 if lf is None else lf.shape[0], _abi.as_dp(lf), 0 if rt is None else rt.shape[0], _abi.as_dp(rt),
-                                                 _abi.as_ip(fc), _abi.as_ip(fo)))
+        fn = self._lib.mpc_validity_batch_ego if per_ego and n_obst else self._lib.mpc_validity_batch
+        self._check(fn(self._h, B, L, _abi.as_dp(traj), float(ego_length), float(ego_width), n_obst, _abi.as_dp(ob),
+                       0 if lf is None else lf.shape[0], _abi.as_dp(lf), 0 if rt is None else rt.shape[0], _abi.as_dp(rt),
+                       _abi.as_ip(fc), _abi.as_ip(fo)))
         return dict(first_collision=fc, first_off_road=fo)
 
     def forces_stage_eval(self, z, p, terminal=False):
