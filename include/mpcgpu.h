@@ -157,7 +157,8 @@ int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const d
  * from the KKT matrix of the final barrier iterate, without regularisation.  Keeps the final iterates for mpc_sens_adjoint.  x_out .. lam_x are
  * bit for bit those of mpc_solve_batch[_dev]_ex; with lam_p NULL and n_dir 0 nothing more is written.  Rows with status != 1 get NaN in lam_p
  * and dw, and so do rows whose final KKT matrix has the wrong inertia (a Riccati pivot <= 0) or that sit on the friction kink (lam_g[0] NaN).
- * fixed_iters > 0 -> MPC_ERR_INVALID.  Derivatives with respect to the obstacle centres, the bounds and x0 are not provided.
+ * fixed_iters > 0 -> MPC_ERR_INVALID.  The derivative with respect to the obstacle centres: mpc_sens_obst below.  Derivatives with respect to
+ * the bounds, the circle radius and x0 are not provided.
  * The _dev form synchronises `stream`.                                                                                                     */
 int mpc_solve_batch_sens(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out,
                          int32_t* status, int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x,
@@ -172,6 +173,18 @@ int mpc_solve_batch_sens_dev(mpc_handle* h, int32_t B, const double* d_x0, const
  * (on the same stream, stream order takes care of it; the handle is not for concurrent use from several streams, as for every entry).         */
 int mpc_sens_adjoint(mpc_handle* h, int32_t B, const double* seed_w, double* grad_p);
 int mpc_sens_adjoint_dev(mpc_handle* h, int32_t B, const double* d_seed_w, double* d_grad_p, void* stream);
+/* The derivative of the optimum with respect to the six obstacle circle centres o [B, 6] (the `obst` rows of the solve, or the descriptor's
+ * centres where it had none; order of mpc_problem_desc::obstacle), on the snapshot of the last mpc_solve_batch_sens[_dev] of this handle -- a
+ * solve with lam_p NULL and n_dir 0 is enough to take it.  Any part may be left out:
+ *   n_dir > 0 forward directions dobst [B, n_dir, 6] -> dw [B, n_dir, n_w] = (dw/do) dobst;
+ *   one adjoint seed seed_w [B, n_w] -> grad_obst [B, 6] = (dw/do)' seed_w (both or neither);
+ *   lam_obst [B, 6] = d/do [f + lam_g' g] at the returned x, which is the derivative of the optimal objective (envelope theorem).
+ * NaN rows, MPC_ERR_STATE and the stream rule of the _dev form are those of mpc_sens_adjoint; n_dir < 0, n_dir > 0 without dobst and dw, or
+ * only one of seed_w / grad_obst -> MPC_ERR_INVALID.  It shares the factor storage of mpc_sens_adjoint.                                    */
+int mpc_sens_obst(mpc_handle* h, int32_t B, int32_t n_dir, const double* dobst, double* dw, const double* seed_w, double* grad_obst,
+                  double* lam_obst);
+int mpc_sens_obst_dev(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dobst, double* d_dw, const double* d_seed_w, double* d_grad_obst,
+                      double* d_lam_obst, void* stream);
 
 /* Batched plant step on the device path: x_next = x + dt f(x,u) (integrator 0 = forward Euler,
  * optimizer.py:649-650) or one RK4 step (integrator 1, optimizer.py:97-98).  x: [B, nx], u: [B, 2] host. */

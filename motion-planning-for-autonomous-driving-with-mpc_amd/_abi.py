@@ -74,6 +74,8 @@ PROTOTYPES = {
     "mpc_solve_batch_sens_dev": [_vp, _i32] + [_vp] * 12 + [_i32, _vp, _vp, _vp],
     "mpc_sens_adjoint": [_vp, _i32, _dp, _dp],
     "mpc_sens_adjoint_dev": [_vp, _i32, _vp, _vp, _vp],
+    "mpc_sens_obst": [_vp, _i32, _i32, _dp, _dp, _dp, _dp, _dp],
+    "mpc_sens_obst_dev": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "mpc_plant_step": [_vp, _i32, _i32, _dp, _dp, _dp],
     "mpc_plant_step_dev": [_vp, _i32, _i32] + [_vp] * 4,
     "mpc_closed_loop_batch": [_vp, _i32, _i32, _i32] + [_dp] * 6 + [_ip],

@@ -1,15 +1,17 @@
-"""The batched solve as a differentiable layer: x*(p) with gradients to p through the parametric sensitivities of the optimum
-(include/mpcgpu.h: mpc_solve_batch_sens_dev, mpc_sens_adjoint_dev).
+"""The batched solve as a differentiable layer: x*(p, obst) with gradients to p and to the obstacle circle centres through the parametric
+sensitivities of the optimum (include/mpcgpu.h: mpc_solve_batch_sens_dev, mpc_sens_adjoint_dev, mpc_sens_obst_dev).
 
     from <package>.autograd import MPCSolve
     x, status = MPCSolve.apply(solver, x0, p)           # x0, p: float64 device tensors [B, n_w]; torch's current stream
     loss = f(x); loss.backward()                         # p.grad = (dx*/dp)' dloss/dx
 
-Gradients flow to p only (x0 is the initial guess: at an isolated optimum x* does not depend on it).  The obstacle centres are the solver's
-own (its descriptor's): per-instance obstacles (the `obst` argument of solve) are not taken by this layer, and no derivative with respect
-to them exists.  Rows whose status is not 1 get NaN
-gradients; failed="zero" masks them to 0 instead.  The backward pass differentiates the snapshot the forward solve left in the solver's
-handle: any later solve on the same solver makes it raise.
+    obst = obstacle_centres(pose, obst_offset)           # pose [B, 3] (x, y, heading) of every instance's obstacle -> [B, 6]
+    x, status = mpc_solve(solver, x0, p, obst=obst)      # the solve takes these centres; obst.grad / pose.grad = (dx*/do)' dloss/dx
+
+Gradients flow to p and, when it is given, to obst (x0 is the initial guess: at an isolated optimum x* does not depend on it).  Without
+obst the obstacle centres are the solver's own (its descriptor's) and the layer is what it was before obst existed, bit for bit.  Rows whose
+status is not 1 get NaN gradients; failed="zero" masks them to 0 instead.  The backward pass differentiates the snapshot the forward solve
+left in the solver's handle: any later solve on the same solver makes it raise.
 """
 from __future__ import annotations
 
@@ -18,9 +20,17 @@ import torch
 from .solver import BatchedMPCSolver
 
 
+def obstacle_centres(pose: torch.Tensor, obst_offset: float) -> torch.Tensor:
+    """pose [B, 3] (x, y, heading) -> the six circle centres [B, 6] of the obstacle: the centre, then +- obst_offset along the heading.  The
+    closed loop's loop_obstacle_centres (csrc/mpc_closed_loop.h) in torch, so that gradients reach the pose."""
+    x, y, th = pose[..., 0], pose[..., 1], pose[..., 2]
+    cs, sn = torch.cos(th), torch.sin(th)
+    return torch.stack([x, y, x + obst_offset * cs, y + obst_offset * sn, x - obst_offset * cs, y - obst_offset * sn], dim=-1)
+
+
 class MPCSolve(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, solver: BatchedMPCSolver, x0: torch.Tensor, p: torch.Tensor, failed: str = "nan"):
+    def forward(ctx, solver: BatchedMPCSolver, x0: torch.Tensor, p: torch.Tensor, failed: str = "nan", obst: torch.Tensor | None = None):
         if failed not in ("nan", "zero"):
             raise ValueError('failed must be "nan" or "zero"')
         for name, t in (("x0", x0), ("p", p)):
@@ -29,12 +39,16 @@ class MPCSolve(torch.autograd.Function):
         B = x0.shape[0]
         if p.shape[0] != B:
             raise ValueError("x0 and p must have the same number of rows")
+        if obst is not None and (obst.dtype != torch.float64 or not obst.is_cuda or tuple(obst.shape) != (B, 6)):
+            raise ValueError("obst must be a float64 device tensor [B, 6]")
         x0c, pc = x0.detach().contiguous(), p.detach().contiguous()
+        oc = None if obst is None else obst.detach().contiguous()
         x = torch.empty_like(x0c)
         status = torch.empty(B, dtype=torch.int32, device=x0.device)
         stream = torch.cuda.current_stream(x0.device).cuda_stream
-        ctx.gen = solver.solve_sens_device(B, x0c.data_ptr(), pc.data_ptr(), x.data_ptr(), d_status=status.data_ptr(), stream=stream)
-        ctx.solver, ctx.B, ctx.failed = solver, B, failed
+        ctx.gen = solver.solve_sens_device(B, x0c.data_ptr(), pc.data_ptr(), x.data_ptr(), d_status=status.data_ptr(),
+                                           d_obst=0 if oc is None else oc.data_ptr(), stream=stream)
+        ctx.solver, ctx.B, ctx.failed, ctx.has_obst = solver, B, failed, obst is not None
         ctx.save_for_backward(status)
         ctx.mark_non_differentiable(status)
         return x, status
@@ -46,14 +60,22 @@ class MPCSolve(torch.autograd.Function):
             raise RuntimeError("MPCSolve.backward: the solver has solved again since this forward pass; its snapshot of the final iterates is gone")
         (status,) = ctx.saved_tensors
         seed = grad_x.detach().to(torch.float64).contiguous()
-        grad_p = torch.empty_like(seed)
         stream = torch.cuda.current_stream(seed.device).cuda_stream
-        solver.sens_adjoint_device(ctx.B, seed.data_ptr(), grad_p.data_ptr(), stream=stream)      # MPC_ERR_STATE after any other solve
-        if ctx.failed == "zero":
-            grad_p = torch.where((status == 1)[:, None], grad_p, torch.zeros_like(grad_p))
-        return None, None, grad_p, None
+        grad_p = grad_obst = None
+        if not ctx.has_obst or ctx.needs_input_grad[2]:
+            grad_p = torch.empty_like(seed)
+            solver.sens_adjoint_device(ctx.B, seed.data_ptr(), grad_p.data_ptr(), stream=stream)      # MPC_ERR_STATE after any other solve
+            if ctx.failed == "zero":
+                grad_p = torch.where((status == 1)[:, None], grad_p, torch.zeros_like(grad_p))
+        if ctx.has_obst and ctx.needs_input_grad[4]:
+            grad_obst = torch.empty((ctx.B, 6), dtype=torch.float64, device=seed.device)
+            solver.sens_obst_device(ctx.B, d_seed_w=seed.data_ptr(), d_grad_obst=grad_obst.data_ptr(), stream=stream)
+            if ctx.failed == "zero":
+                grad_obst = torch.where((status == 1)[:, None], grad_obst, torch.zeros_like(grad_obst))
+        return None, None, grad_p, None, grad_obst
 
 
-def mpc_solve(solver: BatchedMPCSolver, x0: torch.Tensor, p: torch.Tensor, failed: str = "nan"):
-    """functional form of MPCSolve.apply: (x [B, n_w], status [B] int32)"""
-    return MPCSolve.apply(solver, x0, p, failed)
+def mpc_solve(solver: BatchedMPCSolver, x0: torch.Tensor, p: torch.Tensor, failed: str = "nan", obst: torch.Tensor | None = None):
+    """functional form of MPCSolve.apply: (x [B, n_w], status [B] int32).  obst [B, 6]: every instance's own obstacle circle centres (see
+    obstacle_centres); it may require grad"""
+    return MPCSolve.apply(solver, x0, p, failed, obst)

@@ -1,4 +1,4 @@
-// mpc_sens.h -- parametric sensitivities of a converged solve (mpc_solve_batch_sens, mpc_sens_adjoint).
+// mpc_sens.h -- parametric sensitivities of a converged solve (mpc_solve_batch_sens, mpc_sens_adjoint, mpc_sens_obst).
 //
 // The derivative of the returned optimum w*(p) with respect to the parameter row p = [U_ref | X_ref] is sIPOPT's step: the KKT matrix of
 // the final barrier iterate, with no inertia correction, solved against -d(KKT residual)/dp dp.  After the bound multipliers and the
@@ -14,8 +14,8 @@
 //                               ->  d ru_0[a] = sum over the sides the row set of z / gap * d bound / d (delta_0, v_0)
 // The objective scaling df multiplies the Hessian, the gradient and the multipliers alike and drops out of the primal step.
 //
-// Two layers, plain pointers only, so that the same code runs in the kernels (k_sens_gather, k_sens_factor_solve) and in the CPU harness of
-// the tests (tests/sensx/sensx.cpp):
+// Two layers, plain pointers only, so that the same code runs in the kernels (k_sens_gather, k_sens_factor_solve, k_sens_obst) and in the CPU harnesses
+// of the tests (tests/sensx/sensx.cpp, tests/sensobstx/sensobstx.cpp):
 //   snapshot  instance-major copy of the final iterate [(N + 1) stages of SS | a tail of T_COUNT], written by sens_gather_stage
 //   factor    per stage FS doubles, [stage][entry][Bs] (entry e of stage k of instance b at (k FS + e) Bs + b: lanes of a wave coalesce)
 #pragma once
@@ -165,8 +165,9 @@ MPC_HD void sens_dyn_hess(const Params& P, const double* x, const double* lamn, 
 }
 // Stage k of the condensed KKT matrix at the snapshot (what phase_ineq_assemble / phase_eval_model assemble at an iterate, without the
 // inertia correction): adds H_k into Hx, writes Ruu_k (ruu) and the coupling of a_0 with (delta_0, v_0) (hx, stage 0).
+// CIRCLE_SG = false leaves the slack weights sg J J' of the circle rows out (sens_solve_circ keeps those rows' multipliers as unknowns).
 // tail: the snapshot's tail; sn: stage k's snapshot, snn: stage k + 1's (k < N)
-template <int NX>
+template <int NX, bool CIRCLE_SG = true>
 MPC_HD void sens_stage_kkt(const Params& P, const int k, const double* tail, const double* sn, const double* snn, double* Hs, double* ruu,
                            double* hx) {
     using S = Sens<NX>;
@@ -208,8 +209,8 @@ MPC_HD void sens_stage_kkt(const Params& P, const int k, const double* tail, con
         circle_eval(P, tail + S::T_OBST, j, x[0], x[1], sps, cps, J, Ho, true);
         const double s = sn[S::SO + j], nu = sn[S::NUO + j];
         double sg = 0.0;
-        if (P.has_ol) sg += sn[S::ZLO + j] / (s - P.ol);
-        if (P.has_ou) sg += sn[S::ZUO + j] / (P.ou - s);
+        if (CIRCLE_SG && P.has_ol) sg += sn[S::ZLO + j] / (s - P.ol);
+        if (CIRCLE_SG && P.has_ou) sg += sn[S::ZUO + j] / (P.ou - s);
         int q = 0;
 #pragma unroll
         for (int r = 0; r < 3; ++r)
@@ -421,6 +422,301 @@ MPC_HD double sens_lam_p_entry(const Params& P, const int q, const bool conv, co
     const int k = (q - X0) / NX, i = (q - X0) - NX * k;
     if (k == 0) return -lg[1 + i];
     return -2.0 * P.Q[i] * (w[X0 + NX * (k - 1) + i] - pr[q]);
+}
+
+// ---- the obstacle centres (mpc_sens_obst, k_sens_obst) ----------------------------------------------------------------------------------
+// The same step against the same factor with another right-hand side.  The centre o_j (two numbers) of obstacle circle j enters circle row j
+// of every stage, dist_j(x_k, o_j) - s = 0, and nothing else.  With the row's slack eliminated (d nu = sg (J_x dx + J_o do), sg = sum z / gap,
+// as sens_stage_kkt does for the matrix) the stationarity rows of x_k at the state components oi = {0, 1, 4} change by
+//   m (nu Hxo + sg J_x J_o') do_j,     J_o = d dist / d o_j,  Hxo = d J_x / d o_j  (3 x 2),  m = obst_mult
+// and the right-hand side is minus that; the pin row and the friction term do not depend on the obstacle.  The multipliers of the snapshot
+// carry the objective scaling df, as the matrix does: it drops out of the primal step.
+//
+// circle_eval's distance and Jacobian J3 wrt (sx, sy, psi) with the derivatives wrt the centre of obstacle circle j:
+// Jo2 = d dist / d o_j = -(ex, ey), Hxo6 = d J3 / d o_j = -T' M, row-major [3][2] (T = [I | d centre / d psi], M = (I - e e') / dist)
+MPC_HD double circle_eval_centre(const Params& P, const double* obst, int j, double sx, double sy, double sps, double cps, double* J3, double* Jo2,
+                                 double* Hxo6) {
+    const double rho = P.ego_offset;
+    const double sg = (j == 0) ? 0.0 : (j == 1 ? 1.0 : -1.0);
+    const double cx = sx + sg * rho * cps - obst[2 * j];
+    const double cy = sy + sg * rho * sps - obst[2 * j + 1];
+    double r, ir;
+    mpc_sqrt_rcp(cx * cx + cy * cy, r, ir);
+    const double ex = cx * ir, ey = cy * ir;
+    const double tx = -sg * rho * sps, ty = sg * rho * cps;
+    J3[0] = ex;
+    J3[1] = ey;
+    J3[2] = ex * tx + ey * ty;
+    Jo2[0] = -ex;
+    Jo2[1] = -ey;
+    const double m00 = (1 - ex * ex) * ir, m01 = -ex * ey * ir, m11 = (1 - ey * ey) * ir;
+    Hxo6[0] = -m00; Hxo6[1] = -m01;
+    Hxo6[2] = -m01; Hxo6[3] = -m11;
+    Hxo6[4] = -(tx * m00 + ty * m01); Hxo6[5] = -(tx * m01 + ty * m11);
+    return r;
+}
+// one circle row of a stage: what circle_eval_centre returns, the row's weighted multiplier m nu and slack weight m sg (sg = sum z / gap)
+struct SensCirc { double J[3], Jo[2], Hxo[6], mnu, msg; };
+template <int NX>
+MPC_HD void sens_circ_row(const Params& P, const double* tail, const double* sn, const int j, const double sps, const double cps, SensCirc& C) {
+    using S = Sens<NX>;
+    const double* x = sn + S::Z + 2;
+    circle_eval_centre(P, tail + S::T_OBST, j, x[0], x[1], sps, cps, C.J, C.Jo, C.Hxo);
+    const double s = sn[S::SO + j];
+    double sg = 0.0;
+    if (P.has_ol) sg += sn[S::ZLO + j] / (s - P.ol);
+    if (P.has_ou) sg += sn[S::ZUO + j] / (P.ou - s);
+    C.mnu = P.obst_mult * sn[S::NUO + j];
+    C.msg = P.obst_mult * sg;
+}
+// What the solves against the obstacle centres need of every stage, computed once per instance (it does not depend on the right-hand side:
+// no trigonometry and no square root is left in the sweeps): the stage Hessian H0_k without the circle rows' slack weights sg J J', Ruu_k, the
+// coupling hx, and the three circle rows.  Per stage DS doubles, [stage][entry][Bs] as the factor.
+template <int NX>
+struct SensObst {
+    static constexpr int H = 0, RUU = Dim<NX>::NS, HX = RUU + 2, CIRC = HX + 2, CS = 13, DS = CIRC + 3 * CS;
+    MPC_HD static void load_row(const double* D, const size_t Bs, const int b, const int k, const int j, SensCirc& C) {
+        const double* d = D + ((size_t)k * DS + CIRC + CS * j) * Bs + b;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) C.J[r] = d[(size_t)r * Bs];
+        C.Jo[0] = d[3 * Bs]; C.Jo[1] = d[4 * Bs];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) C.Hxo[r] = d[(size_t)(5 + r) * Bs];
+        C.mnu = d[11 * Bs]; C.msg = d[12 * Bs];
+    }
+};
+template <int NX>
+MPC_HD void sens_obst_setup(const Params& P, const double* snap, double* D, const size_t Bs, const int b) {
+    using S = Sens<NX>;
+    using O = SensObst<NX>;
+    const int N = P.N;
+    const double* tail = snap + (size_t)(N + 1) * S::SS;
+    for (int k = 0; k <= N; ++k) {
+        const double* sn = snap + (size_t)k * S::SS;
+        double* d = D + (size_t)k * O::DS * Bs + b;
+        {
+            double Hs[Dim<NX>::NS], ruu[2], hx[2];
+#pragma unroll
+            for (int i = 0; i < Dim<NX>::NS; ++i) Hs[i] = 0.0;
+            sens_stage_kkt<NX, false>(P, k, tail, sn, k < N ? sn + S::SS : nullptr, Hs, ruu, hx);
+#pragma unroll
+            for (int i = 0; i < Dim<NX>::NS; ++i) d[(size_t)(O::H + i) * Bs] = Hs[i];
+            d[(size_t)O::RUU * Bs] = ruu[0]; d[(size_t)(O::RUU + 1) * Bs] = ruu[1];
+            d[(size_t)O::HX * Bs] = hx[0]; d[(size_t)(O::HX + 1) * Bs] = hx[1];
+        }
+        double sps, cps;
+        mpc_sincos(sn[S::Z + 2 + 4], sps, cps);
+#pragma unroll 1
+        for (int j = 0; j < 3; ++j) {
+            SensCirc C;
+            sens_circ_row<NX>(P, tail, sn, j, sps, cps, C);
+            double* c = d + (size_t)(O::CIRC + O::CS * j) * Bs;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) c[(size_t)r * Bs] = C.J[r];
+            c[3 * Bs] = C.Jo[0]; c[4 * Bs] = C.Jo[1];
+#pragma unroll
+            for (int r = 0; r < 6; ++r) c[(size_t)(5 + r) * Bs] = C.Hxo[r];
+            c[11 * Bs] = C.mnu; c[12 * Bs] = C.msg;
+        }
+    }
+}
+// a vector of one instance in memory: entry q at p[q st] (st = 1: a caller's row; st = the batch: scratch, lanes of a wave coalesce)
+struct SensVec {
+    double* p;
+    size_t st;
+    MPC_HD double& operator[](const size_t q) const { return p[q * st]; }
+};
+constexpr int SENS_OBST_REFINE = 2;
+
+// One right-hand side that carries circle-row terms, against the factor, to working precision.
+//   stationarity rows (gu_k, gx_k) and a shift t_kj of every circle row: the row reads J_kj dx_k - t_kj - ds = 0, so that with the slack
+//   eliminated its multiplier is n_kj = m sg_kj (J_kj dx_k - t_kj) and the condensed right-hand side of x_k is gx_k + sum_j m sg_kj J_kj t_kj.
+// On an active row sg ~ 1 / mu: the condensed right-hand side and the matrix hold terms of 1e10 that cancel to O(1), the solve of the condensed
+// system alone is good to ~1e-6 (measured: forward and adjoint disagree by up to 6e-5), and n_kj cannot be had from dx at all (J dx - t is
+// known to 1e-16, times sg).  So SENS_OBST_REFINE steps of iterative refinement on the system with the circle multipliers kept as unknowns,
+// whose residual is O(1) arithmetic throughout (one step leaves 6e-10 of that disagreement, two 1e-14):
+//   rho_x = gx - H0 dx - S'du - sum_j J_j n_j,  rho_u = gu - Ruu du - S dx     (H0: the stage Hessian without the sg J J' terms)
+//   r_nu_j = t_j - J_j dx + n_j / (m sg_j),     om_j = m sg_j r_nu_j
+// the dynamics rows hold exactly (dx is rolled out with the factor's A_k), so only the residual reduced onto the inputs matters:
+//   q_N = rho_x,N;  r_u,k = rho_u,k + B' q_{k+1},  q_k = rho_x,k + A_k' q_{k+1}
+// the correction solves the condensed system against (r_u, sum_j J_j om_j); n_j += m sg_j J_j d(dx) - om_j.
+// base(k, gx [NX], gu [2]) starts the right-hand side of stage k, row(k, j, C, gx) adds what circle row j (C) contributes and returns t_kj;
+// fin(k, j, C, x [NX], n) receives the result row by row.  sol (n_w, the layout of a row of w) receives the primal step; nrow, om
+// (3 (N + 1)) and work (n_w) are scratch.
+template <int NX, class BASE, class ROW, class FIN>
+MPC_HD void sens_solve_circ(const Params& P, double* F, const size_t Bs, const int b, const double* D, BASE base, ROW row, FIN fin,
+                            const SensVec sol, const SensVec nrow, const SensVec om, const SensVec work) {
+    using S = Sens<NX>;
+    using O = SensObst<NX>;
+    const int N = P.N, X0 = 2 * N;
+    const double dt = P.dt;
+    auto dd = [&](int k, int e) { return D[((size_t)k * O::DS + e) * Bs + b]; };
+    auto solve = [&](const SensVec v) {
+        sens_solve<NX>(P, F, Bs, b, nullptr,
+                       [&](int k, int i) { return v[2 * k + i]; },
+                       [&](int k, int i) { return v[X0 + NX * k + i]; },
+                       [&](int k, const double* u) { v[2 * k] = u[0]; v[2 * k + 1] = u[1]; },
+                       [&](int k, const double* x) {
+#pragma unroll
+                           for (int i = 0; i < NX; ++i) v[X0 + NX * k + i] = x[i];
+                       },
+                       nullptr);
+    };
+    // the condensed solve (its right-hand side staged in sol: sens_solve has read all of it before it writes the first step)
+    for (int k = 0; k <= N; ++k) {
+        double gx[NX], gu[2];
+        base(k, gx, gu);
+#pragma unroll 1
+        for (int j = 0; j < 3; ++j) {
+            SensCirc C;
+            O::load_row(D, Bs, b, k, j, C);
+            const double tt = C.msg * row(k, j, C, gx);
+            gx[0] += C.J[0] * tt; gx[1] += C.J[1] * tt; gx[4] += C.J[2] * tt;
+        }
+#pragma unroll
+        for (int i = 0; i < NX; ++i) sol[X0 + NX * k + i] = gx[i];
+        if (k < N) { sol[2 * k] = gu[0]; sol[2 * k + 1] = gu[1]; }
+    }
+    solve(sol);
+    for (int it = 0; it < SENS_OBST_REFINE; ++it) {
+        double q[NX];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) q[i] = 0.0;
+        for (int k = N; k >= 0; --k) {
+            double gx[NX], gu[2], dx[NX], du[2] = {0.0, 0.0};
+            base(k, gx, gu);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) dx[i] = sol[X0 + NX * k + i];
+            if (k < N) { du[0] = sol[2 * k]; du[1] = sol[2 * k + 1]; }
+            const double ruu[2] = {dd(k, O::RUU), dd(k, O::RUU + 1)}, hx[2] = {dd(k, O::HX), dd(k, O::HX + 1)};
+#pragma unroll
+            for (int i = 0; i < NX; ++i)
+#pragma unroll
+                for (int c = i; c < NX; ++c) {
+                    const double h = dd(k, O::H + Dim<NX>::sidx(i, c));
+                    gx[i] -= h * dx[c];
+                    if (c != i) gx[c] -= h * dx[i];
+                }
+            gx[2] -= hx[0] * du[1];
+            gx[3] -= hx[1] * du[1];
+            double wx[3] = {0.0, 0.0, 0.0};
+#pragma unroll 1
+            for (int j = 0; j < 3; ++j) {
+                SensCirc C;
+                O::load_row(D, Bs, b, k, j, C);
+                const double t = row(k, j, C, gx);
+                const double jd = C.J[0] * dx[0] + C.J[1] * dx[1] + C.J[2] * dx[4];
+                double n, w;
+                if (it == 0) { n = C.msg * (jd - t); w = 0.0; nrow[3 * k + j] = n; }
+                else { n = nrow[3 * k + j]; w = C.msg * (t - jd) + n; }
+                om[3 * k + j] = w;
+                gx[0] -= C.J[0] * n; gx[1] -= C.J[1] * n; gx[4] -= C.J[2] * n;
+                wx[0] += C.J[0] * w; wx[1] += C.J[1] * w; wx[2] += C.J[2] * w;
+            }
+            if (k < N) {
+                work[2 * k] = gu[0] - ruu[0] * du[0] + dt * q[2];
+                work[2 * k + 1] = gu[1] - ruu[1] * du[1] - (hx[0] * dx[2] + hx[1] * dx[3]) + dt * q[3];
+                double a[6];
+#pragma unroll
+                for (int e = 0; e < 6; ++e) a[e] = F[((size_t)k * S::FS + S::F_A + e) * Bs + b];
+                sens_At_vec<NX>(q, a, dt);
+            }
+#pragma unroll
+            for (int i = 0; i < NX; ++i) { q[i] += gx[i]; work[X0 + NX * k + i] = 0.0; }
+            work[X0 + NX * k] = wx[0]; work[X0 + NX * k + 1] = wx[1]; work[X0 + NX * k + 4] = wx[2];
+        }
+        solve(work);
+        for (int k = 0; k <= N; ++k) {
+            double x[NX], d0, d1, d4;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[i] = work[X0 + NX * k + i];
+            d0 = x[0]; d1 = x[1]; d4 = x[4];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) { x[i] += sol[X0 + NX * k + i]; sol[X0 + NX * k + i] = x[i]; }
+            if (k < N) { sol[2 * k] += work[2 * k]; sol[2 * k + 1] += work[2 * k + 1]; }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                SensCirc C;
+                O::load_row(D, Bs, b, k, j, C);
+                const double n = nrow[3 * k + j] + (C.msg * (C.J[0] * d0 + C.J[1] * d1 + C.J[2] * d4) - om[3 * k + j]);
+                nrow[3 * k + j] = n;
+                if (it == SENS_OBST_REFINE - 1) fin(k, j, C, x, n);
+            }
+        }
+    }
+}
+
+// forward direction: dobst [6] -> dw [n_w].  The centre o_j moves circle row j of every stage: gx_k = -m nu Hxo do_j at oi, t_kj = -J_o do_j.
+// D: the stage data of sens_obst_setup; nrow, om, work: scratch of sens_solve_circ
+template <int NX>
+MPC_HD void sens_forward_obst(const Params& P, double* F, const size_t Bs, const int b, const double* D, const double* dobst, double* dw,
+                              const SensVec nrow, const SensVec om, const SensVec work) {
+    sens_solve_circ<NX>(P, F, Bs, b, D,
+                        [&](int, double* gx, double* gu) {
+#pragma unroll
+                            for (int i = 0; i < NX; ++i) gx[i] = 0.0;
+                            gu[0] = gu[1] = 0.0;
+                        },
+                        [&](int, int j, const SensCirc& C, double* gx) {
+                            const double d0 = dobst[2 * j], d1 = dobst[2 * j + 1];
+                            gx[0] -= C.mnu * (C.Hxo[0] * d0 + C.Hxo[1] * d1);
+                            gx[1] -= C.mnu * (C.Hxo[2] * d0 + C.Hxo[3] * d1);
+                            gx[4] -= C.mnu * (C.Hxo[4] * d0 + C.Hxo[5] * d1);
+                            return -(C.Jo[0] * d0 + C.Jo[1] * d1);
+                        },
+                        [&](int, int, const SensCirc&, const double*, double) {}, SensVec{dw, 1}, nrow, om, work);
+}
+
+// reverse: seed_w [n_w] -> grad_o [6] = (dw/do)' seed_w.  The solve of the seed (t = 0) gives x_k and the circle multipliers n_kj; the
+// transposed right-hand side of the forward direction applied to them, summed over the stages: grad_o_j = -sum_k (m nu Hxo' x_k + J_o n_kj).
+// sol: scratch for the solve's primal step (n_w)
+template <int NX>
+MPC_HD void sens_adjoint_obst(const Params& P, double* F, const size_t Bs, const int b, const double* D, const double* seed, double* go,
+                              const SensVec sol, const SensVec nrow, const SensVec om, const SensVec work) {
+    const int N = P.N, X0 = 2 * N;
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    sens_solve_circ<NX>(P, F, Bs, b, D,
+                        [&](int k, double* gx, double* gu) {
+#pragma unroll
+                            for (int i = 0; i < NX; ++i) gx[i] = seed[X0 + NX * k + i];
+                            gu[0] = k < N ? seed[2 * k] : 0.0;
+                            gu[1] = k < N ? seed[2 * k + 1] : 0.0;
+                        },
+                        [&](int, int, const SensCirc&, double*) { return 0.0; },
+                        [&](int, int j, const SensCirc& C, const double* x, double n) {
+                            acc[2 * j] -= C.mnu * (C.Hxo[0] * x[0] + C.Hxo[2] * x[1] + C.Hxo[4] * x[4]) + C.Jo[0] * n;
+                            acc[2 * j + 1] -= C.mnu * (C.Hxo[1] * x[0] + C.Hxo[3] * x[1] + C.Hxo[5] * x[4]) + C.Jo[1] * n;
+                        },
+                        sol, nrow, om, work);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) go[i] = acc[i];
+}
+
+// lam_o [6] = d/do [f + lam_g' g] at the snapshot's iterate, in CasADi's sign and scale: per circle j the sum over the stages of the row's
+// multiplier -- the three copies of mult_stage summed, m nu / df -- times d dist_j / d o_j.  By the envelope theorem d f* / d o.
+template <int NX>
+MPC_HD void sens_lam_obst(const Params& P, const double* snap, double* lo) {
+    using S = Sens<NX>;
+    const int N = P.N;
+    const double* tail = snap + (size_t)(N + 1) * S::SS;
+    const double wm = P.obst_mult / 3.0, idf = 1.0 / tail[S::T_DF];
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k <= N; ++k) {
+        const double* sn = snap + (size_t)k * S::SS;
+        const double* x = sn + S::Z + 2;
+        double sps, cps;
+        mpc_sincos(x[4], sps, cps);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double J[3], Jo[2], Hxo[6];
+            circle_eval_centre(P, tail + S::T_OBST, j, x[0], x[1], sps, cps, J, Jo, Hxo);
+            const double lg = 3.0 * (sn[S::NUO + j] * idf * wm);
+            acc[2 * j] += lg * Jo[0];
+            acc[2 * j + 1] += lg * Jo[1];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) lo[i] = acc[i];
 }
 
 }  // namespace mpc

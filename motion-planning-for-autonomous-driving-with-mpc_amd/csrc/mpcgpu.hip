@@ -2524,6 +2524,43 @@ __global__ void __launch_bounds__(SENS_THREADS) k_sens_factor_solve(const Params
     }
 }
 
+// doubles per instance of k_sens_obst's scratch: the stage data of sens_obst_setup, then sol, work (n_w each) and nrow, om (3 (N + 1) each)
+template <int NX>
+MPC_HD size_t sens_obst_scratch_len(int N) { return (size_t)(N + 1) * SensObst<NX>::DS + (size_t)2 * ((size_t)2 * N + (size_t)NX * (N + 1)) + (size_t)6 * (N + 1); }
+// Lane per instance, the mapping of k_sens_factor_solve: the same factor of the snapshot, then the derivative with respect to the six obstacle
+// centres (mpc_sens_obst): n_dir forward directions dobst [B, n_dir, 6] -> dw [B, n_dir, n_w] and / or one adjoint seed [B, n_w] -> grad_o [B, 6],
+// and lam_o [B, 6] = d/do [f + lam_g' g].  NaN where the factor failed.  W: [sens_obst_scratch_len][B], the stage data of sens_obst_setup and
+// the vectors of sens_solve_circ.
+template <int NX>
+__global__ void __launch_bounds__(SENS_THREADS) k_sens_obst(const Params P, const double* snap, double* F, double* W, const int n_dir, const double* dobst,
+                                                           double* dw, const double* seed, double* grad_o, double* lam_o) {
+    const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
+    if (b >= P.B) return;
+    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), Bs = (size_t)P.B, nn = (size_t)3 * (P.N + 1);
+    const double* sb = snap + (size_t)b * Sens<NX>::len(P.N);
+    const SensInst si = sens_factor<NX>(P, sb, F, Bs, b);
+    if (si.ok && (n_dir > 0 || grad_o)) sens_obst_setup<NX>(P, sb, W, Bs, b);
+    double* V = W + (size_t)(P.N + 1) * SensObst<NX>::DS * Bs + b;
+    const SensVec sol{V, Bs}, work{V + nw * Bs, Bs}, nrow{V + 2 * nw * Bs, Bs}, om{V + (2 * nw + nn) * Bs, Bs};
+    for (int d = 0; d < n_dir; ++d) {
+        double* o = dw + ((size_t)b * n_dir + d) * nw;
+        if (si.ok) sens_forward_obst<NX>(P, F, Bs, b, W, dobst + ((size_t)b * n_dir + d) * 6, o, nrow, om, work);
+        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
+    }
+    if (grad_o) {
+        double go[6];
+        if (si.ok) sens_adjoint_obst<NX>(P, F, Bs, b, W, seed + (size_t)b * nw, go, sol, nrow, om, work);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) grad_o[(size_t)b * 6 + i] = si.ok ? go[i] : NAN;
+    }
+    if (lam_o) {
+        double lo[6];
+        if (si.ok) sens_lam_obst<NX>(P, sb, lo);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lam_o[(size_t)b * 6 + i] = si.ok ? lo[i] : NAN;
+    }
+}
+
 template <int NX>
 __global__ void k_plant_step(const Params Pk, const double* x, const double* u, double* xn, int B, int integrator) {
     const PRef P(Pk);
@@ -2570,7 +2607,8 @@ enum Scratch : int {
     SCR_EX_LAM,                         // solve_ex_dev: the multiplier rows (lam_g or lam_x) the caller did not ask for
     SCR_SENS_SNAP,                      // solve_sens_dev: snapshot of the final iterates (read again by mpc_sens_adjoint_dev)
     SCR_SENS_LAM_G,                     // solve_sens_dev: lam_g for lam_p when the caller did not ask for it (live beside SCR_EX_LAM, then lam_x)
-    SCR_SENS_F,                         // sens_launch: the factors of the KKT matrices
+    SCR_SENS_F,                         // sens_launch, sens_obst_launch: the factors of the KKT matrices
+    SCR_SENS_OBST,                      // sens_obst_launch: the stage data and the solves' vectors (sens_obst_setup, sens_solve_circ)
     SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
     SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
     SCR_LOOP_OBST,                      // closed_loop_dev: the obstacle rows of a loop with per-ego obstacle tracks (k_loop_obst)
@@ -3656,6 +3694,28 @@ static int sens_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_
     return MPC_OK;
 }
 
+// the same factor, solved against the obstacle centres' right-hand sides (k_sens_obst)
+static int sens_obst_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dobst, double* d_dw, const double* d_seed, double* d_grad, double* d_lam,
+                            hipStream_t s) {
+    const int N = h->hp.desc.N;
+    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(N + 1) * (size_t)sens_fs(h) * 8));
+    size_t wlen = 0;
+    FOR_NX(h, wlen = sens_obst_scratch_len<NX>(N));
+    double* W = static_cast<double*>(scratch_get(h, SCR_SENS_OBST, (size_t)B * wlen * 8));
+    if (!F || !W) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
+    const double* snap = static_cast<const double*>(h->scratch[SCR_SENS_SNAP]);
+    FOR_NX(h, hipLaunchKernelGGL((k_sens_obst<NX>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F, W,
+                                 n_dir, d_dobst, d_dw, d_seed, d_grad, d_lam));
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+static const char* bad_sens_obst(int32_t B, int32_t n_dir, const double* dobst, const double* dw, const double* seed_w, const double* grad_obst) {
+    if (B <= 0) return "B > 0 is required";
+    if (n_dir < 0 || (n_dir > 0 && (!dobst || !dw))) return "mpc_sens_obst: n_dir >= 0, and dobst, dw are required when n_dir > 0";
+    if ((seed_w != nullptr) != (grad_obst != nullptr)) return "mpc_sens_obst: seed_w and grad_obst go together";
+    return nullptr;
+}
+
 // solve_ex_dev plus the snapshot of the final iterates, CasADi's lam_p and n_dir forward sensitivities
 static int solve_sens_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, double* d_lam_p, int32_t n_dir, const double* d_dp, double* d_dw, hipStream_t s) {
     int rc = supply_status(h, io);
@@ -3775,6 +3835,30 @@ int mpc_sens_adjoint(mpc_handle* h, int32_t B, const double* seed_w, double* gra
     const size_t nw = h->hp.n_w(), nB = (size_t)B;
     return stage_host(h, {{seed_w, nB * nw * 8, false}, {grad_p, nB * nw * 8, true}},
                       [&](void** d, hipStream_t s) { return mpc_sens_adjoint_dev(h, B, (double*)d[0], (double*)d[1], s); });
+}
+
+// the derivative with respect to the obstacle centres on the same snapshot, under the same rule (enqueued on `stream`)
+int mpc_sens_obst_dev(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dobst, double* d_dw, const double* d_seed_w, double* d_grad_obst,
+                      double* d_lam_obst, void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    if (const char* bad = bad_sens_obst(B, n_dir, d_dobst, d_dw, d_seed_w, d_grad_obst)) { h->err = bad; return MPC_ERR_INVALID; }
+    if (!h->snap_ok || B != h->snap_B) {
+        h->err = "mpc_sens_obst: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B";
+        return MPC_ERR_STATE;
+    }
+    if (n_dir == 0 && !d_grad_obst && !d_lam_obst) return MPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return sens_obst_launch(h, B, n_dir, d_dobst, d_dw, d_seed_w, d_grad_obst, d_lam_obst, (hipStream_t)stream_);
+}
+
+int mpc_sens_obst(mpc_handle* h, int32_t B, int32_t n_dir, const double* dobst, double* dw, const double* seed_w, double* grad_obst, double* lam_obst) {
+    if (!h) return MPC_ERR_INVALID;
+    if (const char* bad = bad_sens_obst(B, n_dir, dobst, dw, seed_w, grad_obst)) { h->err = bad; return MPC_ERR_INVALID; }
+    const size_t nw = h->hp.n_w(), nB = (size_t)B, nd = (size_t)n_dir;
+    return stage_host(h, {{n_dir ? dobst : nullptr, nB * nd * 6 * 8, false}, {n_dir ? dw : nullptr, nB * nd * nw * 8, true}, {seed_w, nB * nw * 8, false},
+                          {grad_obst, nB * 6 * 8, true}, {lam_obst, nB * 6 * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_sens_obst_dev(h, B, n_dir, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], s);
+    });
 }
 
 int mpc_plant_step_dev(mpc_handle* h, int32_t B, int32_t integrator, const double* d_x, const double* d_u, double* d_x_next, void* stream_) {

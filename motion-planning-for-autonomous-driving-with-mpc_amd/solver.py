@@ -55,6 +55,14 @@ class SolveResult:
     dw: np.ndarray | None = None       # [B, n_dir, n_w] (dw*/dp) dp for the seeds dp [B, n_dir, n_p], NaN where status != 1
 
 
+@dataclass
+class ObstSens:
+    """sens_obst(): the derivative of the last solve's optimum with respect to the six obstacle circle centres o [B, 6] (mpc_sens_obst)"""
+    dw: np.ndarray | None = None         # [B, n_dir, n_w] (dw*/do) dobst, NaN where status != 1
+    grad_obst: np.ndarray | None = None  # [B, 6] (dw*/do)' seed_w
+    lam_obst: np.ndarray | None = None   # [B, 6] d/do [f + lam_g' g] = d f*/do
+
+
 class BatchedMPCSolver:
     def __init__(self, N, nx=5, *, dt=0.1, Q=None, R=None, P=None, obstacle_centers=None, wheelbase=2.5789128,
                  friction_div=2.578, ego_offset=0.75, max_iter=100, tol=1e-8, fixed_iters=0, obst_mult=3, device=0,
@@ -83,6 +91,7 @@ class BatchedMPCSolver:
         self.n_g = 1 + self.nx * (self.N + 1) + 9 * (self.N + 1)
         self._h = C.c_void_p()
         self._sens_gen = 0          # solves that left a snapshot of their final iterates (mpc_solve_batch_sens): autograd.py checks it
+        self._sens_B = 0            # ... and the batch size of the last of them
         rc = self._lib.mpc_create(C.byref(self._h), C.byref(d))
         if rc != _abi.MPC_OK:
             raise MpcError(rc, self._lib.mpc_last_error(None).decode())
@@ -185,6 +194,7 @@ class BatchedMPCSolver:
             n_dir = dp.shape[1]
             dw = np.empty((B, n_dir, self.n_w))
         self._sens_gen += 1
+        self._sens_B = B
         self._check(self._lib.mpc_solve_batch_sens(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out), _abi.as_ip(status),
                                                    _abi.as_ip(iters), _abi.as_dp(kkt), _abi.as_dp(f), _abi.as_dp(g), _abi.as_dp(lam_g),
                                                    _abi.as_dp(lam_x), _abi.as_dp(lp), n_dir, _abi.as_dp(dp), _abi.as_dp(dw)))
@@ -213,6 +223,31 @@ class BatchedMPCSolver:
         grad = np.empty_like(seed)
         self._check(self._lib.mpc_sens_adjoint(self._h, seed.shape[0], _abi.as_dp(seed), _abi.as_dp(grad)))
         return grad
+
+    def sens_obst(self, dobst=None, seed_w=None, lam=False) -> ObstSens:
+        """the derivative of the optimum of the last solve(..., lam_p / dp) of this solver with respect to its six obstacle circle centres
+        (the solve's obst rows, or the solver's own centres): dobst [B, n_dir, 6] (or [B, 6]) -> dw [B, n_dir, n_w]; seed_w [B, n_w] ->
+        grad_obst [B, 6]; lam=True: lam_obst [B, 6], the derivative of the optimal objective (mpc_sens_obst; any solve in between ->
+        MpcError with code MPC_ERR_STATE)"""
+        B = self._sens_B
+        dw = grad = lo = None
+        n_dir = 0
+        if dobst is not None:
+            dobst = _abi.f64(dobst)
+            if dobst.ndim == 2:
+                dobst = dobst[:, None, :]
+            if dobst.ndim != 3 or dobst.shape[0] != B or dobst.shape[2] != 6:
+                raise MpcError(_abi.MPC_ERR_INVALID, f"dobst must be [{B}, n_dir, 6]")
+            dobst = np.ascontiguousarray(dobst)
+            n_dir = dobst.shape[1]
+            dw = np.empty((B, n_dir, self.n_w))
+        if seed_w is not None:
+            seed_w = _abi.f64(seed_w, (B, self.n_w))
+            grad = np.empty((B, 6))
+        if lam:
+            lo = np.empty((B, 6))
+        self._check(self._lib.mpc_sens_obst(self._h, B, n_dir, _abi.as_dp(dobst), _abi.as_dp(dw), _abi.as_dp(seed_w), _abi.as_dp(grad), _abi.as_dp(lo)))
+        return ObstSens(dw, grad, lo)
 
     def feedback_gain(self, x0, p, obst=None):
         """du_0*/dxref_0 [B, nu, nx]: the linearised control law around the optimum (xref_0 is the measured state the plan starts from)"""
@@ -273,6 +308,7 @@ class BatchedMPCSolver:
         extra = [_vp(d_f), _vp(d_g), _vp(d_lam_g), _vp(d_lam_x)]
         if d_lam_p or n_dir:
             self._sens_gen += 1
+            self._sens_B = int(B)
             self._check(self._lib.mpc_solve_batch_sens_dev(*rows, *extra, _vp(d_lam_p), int(n_dir), _vp(d_dp), _vp(d_dw), _vp(stream)))
         elif d_f or d_g or d_lam_g or d_lam_x:
             self._check(self._lib.mpc_solve_batch_dev_ex(*rows, *extra, _vp(stream)))
@@ -283,6 +319,7 @@ class BatchedMPCSolver:
         """mpc_solve_batch_sens_dev even with no sensitivity output asked for: the solve plus the snapshot of its final iterates
         (what sens_adjoint_device differentiates)"""
         self._sens_gen += 1
+        self._sens_B = int(B)
         self._check(self._lib.mpc_solve_batch_sens_dev(*self._dev_rows(B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt), None, None, None, None,
                                                        _vp(d_lam_p), int(n_dir), _vp(d_dp), _vp(d_dw), _vp(stream)))
         return self._sens_gen
@@ -290,6 +327,12 @@ class BatchedMPCSolver:
     def sens_adjoint_device(self, B, d_seed_w, d_grad_p, stream=0):
         """device form of sens_adjoint (enqueued on `stream`, not synchronised)"""
         self._check(self._lib.mpc_sens_adjoint_dev(self._h, int(B), _vp(d_seed_w), _vp(d_grad_p), _vp(stream)))
+
+    def sens_obst_device(self, B, n_dir=0, d_dobst=0, d_dw=0, d_seed_w=0, d_grad_obst=0, d_lam_obst=0, stream=0):
+        """device form of sens_obst (enqueued on `stream`, not synchronised): d_dobst [B, n_dir, 6] -> d_dw [B, n_dir, n_w], d_seed_w [B, n_w] ->
+        d_grad_obst [B, 6], d_lam_obst [B, 6]; 0 = not asked for"""
+        self._check(self._lib.mpc_sens_obst_dev(self._h, int(B), int(n_dir), _vp(d_dobst), _vp(d_dw), _vp(d_seed_w), _vp(d_grad_obst), _vp(d_lam_obst),
+                                                _vp(stream)))
 
     def plant_step(self, x, u, integrator="euler"):
         x = _abi.f64(x)

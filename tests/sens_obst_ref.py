@@ -1,0 +1,90 @@
+"""numpy reference of the derivative of the NLP's optimum with respect to the six obstacle-circle centres (mpc_sens_obst; DESIGN.md
+section 13).
+
+The reduced KKT system of tests/sens_ref.py, K [dw; dnu] = G do, with another right-hand side: G = -d(KKT residual)/do.  The centres
+o = (o_0, o_1, o_2) enter the residual through the circle rows only -- the stationarity rows through J_g' lam_g, the rows of the active set
+through the distances themselves -- so G is the central difference (exact to ~H^2, the distances are smooth) of
+
+    [ J_A(o)' nu_A ;  g_A(o) ]        over the active circle rows A, nu_A their multipliers (the three copies of a row summed)
+
+evaluated by BicycleNLP with its `obst` attribute replaced.  Rows that are not active contribute nothing (their multiplier is 0 in the active-set
+derivative): where no circle row is active (lane following, the obstacle far away) the derivative is exactly 0.
+
+ObstCfg feeds other centres than the configuration's to everything that reads `cfg.obstacle_centers` (BicycleNLP, the C oracle's descriptor).
+"""
+import numpy as np
+
+from oracle.nlp_numpy import BicycleNLP
+import sens_ref
+
+H = 1e-6
+
+
+class ObstCfg:
+    """an NLPConfig whose `obstacle_centers` are the six numbers given (centre, front, rear circle: x, y each); everything else is cfg's"""
+
+    def __init__(self, cfg, centres):
+        self._cfg = cfg
+        self._centres = np.array(centres, dtype=np.float64).reshape(3, 2)
+
+    def __getattr__(self, name):
+        return getattr(self._cfg, name)
+
+    @property
+    def obstacle_centers(self):
+        return self._centres.copy()
+
+
+def circle_rows(nlp):
+    """first copy of every circle row: (row of g, stage k, pair j)"""
+    return [(nlp.row_obst(k) + 3 * j, k, j) for k in range(nlp.N + 1) for j in range(3)]
+
+
+def _circle_part(nlp, w, p, centres, rows, lam_sum):
+    """[J' nu ; g] of the circle rows `rows` (first copies) with multipliers lam_sum at the centres given"""
+    nlp.obst = np.asarray(centres, dtype=np.float64).reshape(3, 2)
+    J, g = nlp.jac(w, p), nlp.g(w, p)
+    return np.concatenate([J[rows].T @ lam_sum, g[rows]]) if rows else np.zeros(nlp.n_w)
+
+
+def kkt_matrix(cfg, centres, w, p, lam_g, lam_x, bounds=None):
+    """the reduced KKT matrix K of sens_ref at the centres given, the obstacle block G [n + m, 6] (K [dw; dnu] = G do) and the weak flag"""
+    oc = ObstCfg(cfg, centres)
+    nlp = BicycleNLP(oc)
+    bounds = nlp.bounds() if bounds is None else bounds
+    K, _, weak = sens_ref.kkt_matrix(oc, w, p, lam_g, lam_x, bounds)
+    rows, _, _ = sens_ref.active_sets(nlp, w, p, lam_g, lam_x, bounds)
+    n = nlp.n_w
+    first = {r for r, _, _ in circle_rows(nlp)}
+    act = [r for r in rows if r in first]
+    lam_sum = np.array([lam_g[r] + lam_g[r + 1] + lam_g[r + 2] for r in act])
+    G = np.zeros((K.shape[0], 6))
+    c0 = np.asarray(centres, dtype=np.float64).ravel()
+    for q in range(6):
+        e = np.zeros(6)
+        e[q] = H
+        d = (_circle_part(nlp, w, p, c0 + e, act, lam_sum) - _circle_part(nlp, w, p, c0 - e, act, lam_sum)) / (2 * H)
+        G[:n, q] = -d[:n]
+        for i, r in enumerate(act):
+            G[n + rows.index(r), q] = -d[n + i]
+    return K, G, weak
+
+
+def sensitivity_matrix(cfg, centres, w, p, lam_g, lam_x, bounds=None):
+    """dw/do [n_w, 6] of the optimum and the weak-activity flag"""
+    K, G, weak = kkt_matrix(cfg, centres, w, p, lam_g, lam_x, bounds)
+    if not G.any():
+        return np.zeros((cfg.n_w, 6)), weak
+    return np.linalg.solve(K, G)[:cfg.n_w], weak
+
+
+def lam_obst(cfg, centres, w, lam_g):
+    """d/do [f + lam_g' g] at w in closed form: sum over the stages of (the multiplier of circle row j, its three copies summed) times
+    d dist_j / d o_j = -(unit vector from the obstacle circle to the ego circle)"""
+    nlp = BicycleNLP(ObstCfg(cfg, centres))
+    _, X = nlp.split(w)
+    out = np.zeros(6)
+    for r, k, j in circle_rows(nlp):
+        _, J, _ = nlp.obstacle_rows(X[k])
+        out[2 * j: 2 * j + 2] -= (lam_g[r] + lam_g[r + 1] + lam_g[r + 2]) * J[j, :2]
+    return out
