@@ -102,6 +102,15 @@ const char* mpc_last_error(const mpc_handle* h);   /* h may be NULL: error of th
  * absolute value in the row and gets no barrier.  Passing NULL for all four installs the reference defaults. */
 int mpc_set_bounds(mpc_handle* h, const double* lbx, const double* ubx, const double* lbg, const double* ubg);
 
+/* Replaces the cost weights of a live handle: Q [5] -> desc.Q[0..4], R [2] -> desc.R[0..1]; NULL keeps the current ones.  Q[5] (the progress
+ * state's weight), P, the bounds and every option stay.  A non-finite value, a Q[i] < 0 or an R[j] <= 0 (R > 0 keeps the KKT matrix's input
+ * blocks positive definite) -> MPC_ERR_INVALID, and the handle is as it was.  Host bookkeeping only: no device work and no synchronisation.
+ * Every launch carries its weights by value, so work already enqueued keeps the weights it was enqueued with; every call from the next one on
+ * -- NLP solves, closed loops and the FORCES-mode entries, which read the same descriptor -- sees the new ones.  Like a solve, it ends the
+ * life of the sensitivity snapshot: mpc_sens_adjoint / mpc_sens_obst / mpc_sens_weights after it -> MPC_ERR_STATE (their factor reads the
+ * weights, which must be those of the solve).                                                                                               */
+int mpc_set_weights(mpc_handle* h, const double* Q, const double* R);
+
 /* Host-buffer entry point.  x0, p, x_out: [B, n_w] row-major.  obst: [B, 6] per-instance obstacle circle
  * centres or NULL (shared centres of the descriptor).  status/iters/kkt: [B], any may be NULL.            */
 int mpc_solve_batch(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst,
@@ -157,8 +166,8 @@ int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const d
  * from the KKT matrix of the final barrier iterate, without regularisation.  Keeps the final iterates for mpc_sens_adjoint.  x_out .. lam_x are
  * bit for bit those of mpc_solve_batch[_dev]_ex; with lam_p NULL and n_dir 0 nothing more is written.  Rows with status != 1 get NaN in lam_p
  * and dw, and so do rows whose final KKT matrix has the wrong inertia (a Riccati pivot <= 0) or that sit on the friction kink (lam_g[0] NaN).
- * fixed_iters > 0 -> MPC_ERR_INVALID.  The derivative with respect to the obstacle centres: mpc_sens_obst below.  Derivatives with respect to
- * the bounds, the circle radius and x0 are not provided.
+ * fixed_iters > 0 -> MPC_ERR_INVALID.  The derivative with respect to the obstacle centres: mpc_sens_obst below; with respect to the cost
+ * weights: mpc_sens_weights below.  Derivatives with respect to the bounds, the circle radius and x0 are not provided.
  * The _dev form synchronises `stream`.                                                                                                     */
 int mpc_solve_batch_sens(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out,
                          int32_t* status, int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x,
@@ -185,6 +194,22 @@ int mpc_sens_obst(mpc_handle* h, int32_t B, int32_t n_dir, const double* dobst, 
                   double* lam_obst);
 int mpc_sens_obst_dev(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dobst, double* d_dw, const double* d_seed_w, double* d_grad_obst,
                       double* d_lam_obst, void* stream);
+/* The derivative of the optimum with respect to the seven cost weights wt = [Q_0 .. Q_4 | R_0, R_1] (n_wt = 7 for nx 5 and 6 alike; the
+ * handle's current ones, see mpc_set_weights), on the snapshot of the last mpc_solve_batch_sens[_dev] of this handle -- a solve with lam_p NULL
+ * and n_dir 0 is enough to take it.  p [B, n_w]: the p rows of that solve; required, because the snapshot does not hold X_ref, and NOT checked
+ * against the solve (another p gives the derivative of nothing).  Any part may be left out:
+ *   n_dir > 0 forward directions dwt [B, n_dir, 7] -> dw [B, n_dir, n_w] = (dw/dwt) dwt;
+ *   one adjoint seed seed_w [B, n_w] -> grad_wt [B, 7] = (dw/dwt)' seed_w (both or neither);
+ *   lam_wt [B, 7] = d/dwt [f + lam_g' g] at the returned x = [sum_{k<N} (x_k - xref_{k+1})_i^2 | sum_{k<N} u_k[j]^2], which is the derivative
+ *   of the optimal objective (envelope theorem).
+ * The weights are shared by the batch; the rows of grad_wt / lam_wt are per instance, to be summed by the caller.  The objective scaling of
+ * the solve is held fixed.  NaN rows, MPC_ERR_STATE (also after mpc_set_weights) and the stream rule of the _dev form
+ * are those of mpc_sens_adjoint; p NULL, n_dir < 0, n_dir > 0 without dwt and dw, or only one of seed_w / grad_wt -> MPC_ERR_INVALID.  It
+ * shares the factor storage of mpc_sens_adjoint.                                                                                            */
+int mpc_sens_weights(mpc_handle* h, int32_t B, const double* p, int32_t n_dir, const double* dwt, double* dw, const double* seed_w, double* grad_wt,
+                     double* lam_wt);
+int mpc_sens_weights_dev(mpc_handle* h, int32_t B, const double* d_p, int32_t n_dir, const double* d_dwt, double* d_dw, const double* d_seed_w,
+                         double* d_grad_wt, double* d_lam_wt, void* stream);
 
 /* Batched plant step on the device path: x_next = x + dt f(x,u) (integrator 0 = forward Euler,
  * optimizer.py:649-650) or one RK4 step (integrator 1, optimizer.py:97-98).  x: [B, nx], u: [B, 2] host. */

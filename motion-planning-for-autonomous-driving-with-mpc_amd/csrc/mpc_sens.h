@@ -1,4 +1,5 @@
-// mpc_sens.h -- parametric sensitivities of a converged solve (mpc_solve_batch_sens, mpc_sens_adjoint, mpc_sens_obst).
+// mpc_sens.h -- parametric sensitivities of a converged solve (mpc_solve_batch_sens, mpc_sens_adjoint, mpc_sens_obst, mpc_sens_weights; DESIGN.md
+// section 13).
 //
 // The derivative of the returned optimum w*(p) with respect to the parameter row p = [U_ref | X_ref] is sIPOPT's step: the KKT matrix of
 // the final barrier iterate, with no inertia correction, solved against -d(KKT residual)/dp dp.  After the bound multipliers and the
@@ -13,9 +14,10 @@
 //   a presolved friction row:   the bounds -+ sqrt(fu - c(delta_0, v_0)) of a_0 (prestart_a0_of), with (delta_0, v_0) = xref_0
 //                               ->  d ru_0[a] = sum over the sides the row set of z / gap * d bound / d (delta_0, v_0)
 // The objective scaling df multiplies the Hessian, the gradient and the multipliers alike and drops out of the primal step.
+// The obstacle centres and the cost weights are further right-hand sides against the same factor: their sections below state them.
 //
-// Two layers, plain pointers only, so that the same code runs in the kernels (k_sens_gather, k_sens_factor_solve, k_sens_obst) and in the CPU harnesses
-// of the tests (tests/sensx/sensx.cpp, tests/sensobstx/sensobstx.cpp):
+// Two layers, plain pointers only, so that the same code runs in the kernels (k_sens_gather, k_sens_factor_solve, k_sens_obst, k_sens_weights)
+// and in the CPU harnesses of the tests (tests/sensx/sensx.cpp, tests/sensobstx/sensobstx.cpp, tests/sensweightx/sensweightx.cpp):
 //   snapshot  instance-major copy of the final iterate [(N + 1) stages of SS | a tail of T_COUNT], written by sens_gather_stage
 //   factor    per stage FS doubles, [stage][entry][Bs] (entry e of stage k of instance b at (k FS + e) Bs + b: lanes of a wave coalesce)
 #pragma once
@@ -542,8 +544,8 @@ constexpr int SENS_OBST_REFINE = 2;
 // the correction solves the condensed system against (r_u, sum_j J_j om_j); n_j += m sg_j J_j d(dx) - om_j.
 // base(k, gx [NX], gu [2]) starts the right-hand side of stage k, row(k, j, C, gx) adds what circle row j (C) contributes and returns t_kj;
 // fin(k, j, C, x [NX], n) receives the result row by row.  sol (n_w, the layout of a row of w) receives the primal step; nrow, om
-// (3 (N + 1)) and work (n_w) are scratch.
-template <int NX, class BASE, class ROW, class FIN>
+// (3 (N + 1)) and work (n_w) are scratch.  REFINE: the number of refinement steps (>= 1).
+template <int NX, int REFINE = SENS_OBST_REFINE, class BASE, class ROW, class FIN>
 MPC_HD void sens_solve_circ(const Params& P, double* F, const size_t Bs, const int b, const double* D, BASE base, ROW row, FIN fin,
                             const SensVec sol, const SensVec nrow, const SensVec om, const SensVec work) {
     using S = Sens<NX>;
@@ -578,7 +580,7 @@ MPC_HD void sens_solve_circ(const Params& P, double* F, const size_t Bs, const i
         if (k < N) { sol[2 * k] = gu[0]; sol[2 * k + 1] = gu[1]; }
     }
     solve(sol);
-    for (int it = 0; it < SENS_OBST_REFINE; ++it) {
+    for (int it = 0; it < REFINE; ++it) {
         double q[NX];
 #pragma unroll
         for (int i = 0; i < NX; ++i) q[i] = 0.0;
@@ -640,7 +642,7 @@ MPC_HD void sens_solve_circ(const Params& P, double* F, const size_t Bs, const i
                 O::load_row(D, Bs, b, k, j, C);
                 const double n = nrow[3 * k + j] + (C.msg * (C.J[0] * d0 + C.J[1] * d1 + C.J[2] * d4) - om[3 * k + j]);
                 nrow[3 * k + j] = n;
-                if (it == SENS_OBST_REFINE - 1) fin(k, j, C, x, n);
+                if (it == REFINE - 1) fin(k, j, C, x, n);
             }
         }
     }
@@ -717,6 +719,90 @@ MPC_HD void sens_lam_obst(const Params& P, const double* snap, double* lo) {
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) lo[i] = acc[i];
+}
+
+// ---- the cost weights (mpc_sens_weights, k_sens_weights) ---------------------------------------------------------------------------------
+// The same step against the same factor with a third right-hand side.  The weight vector is wt = [Q_0 .. Q_4 | R_0, R_1] (SENS_NWT numbers
+// for NX = 5 and 6 alike: Q_5, the progress state's weight, is not among them).  The weights enter the residual through the cost gradient only,
+//   of x_k:  df 2 Q_i e_k[i],  e_k = x_k - xref_{k+1}  (i < 5, k < N)         of u_k:  df 2 R_j u_k[j]  (k < N)
+// so the right-hand side of a direction dwt is
+//   rx_k[i] = -2 df e_k[i] dQ_i,   ru_k[j] = -2 df u_k[j] dR_j   (k < N);   stage N, the pin row and the friction term are 0
+// (a presolved friction bound depends on xref_0, not on the weights).  df drops out of dw as it does for p.  df is held FIXED: the
+// gradient-based scaling makes it a function of Q through the starting point, which moves the final barrier point at the order of mu only and
+// the optimum of the NLP not at all.
+// The right-hand side holds no sg = z / gap, but the MATRIX does: on an active circle row the factor carries terms of 1e10, and one sens_solve
+// against it, forward and adjoint, disagree by up to 2.4e-10 of sum |seed| max |dw| (measured on the collision-avoidance batch; the bound asked
+// of the adjoint identity is 1e-10).  So the solve is sens_solve_circ's, with every circle shift t = 0 and SENS_WT_REFINE step of refinement
+// (the obstacle right-hand side starts from 6e-5 and needs two): the identity then holds to 5e-16.
+// x_k, u_k: the snapshot's Z; xref: the instance's p row pr (the p of the solve; the snapshot does not hold it).
+constexpr int SENS_NWT = 7, SENS_NWQ = 5;
+constexpr int SENS_WT_REFINE = 1;
+
+// forward direction: dwt [7] -> dw [n_w].  D: the stage data of sens_obst_setup; nrow, om, work: scratch of sens_solve_circ
+template <int NX>
+MPC_HD void sens_forward_weights(const Params& P, const SensInst& si, double* F, const size_t Bs, const int b, const double* D, const double* snap,
+                                 const double* pr, const double* dwt, double* dw, const SensVec nrow, const SensVec om, const SensVec work) {
+    using S = Sens<NX>;
+    const int N = P.N, X0 = 2 * N;
+    const double m2df = -2.0 * si.df;
+    sens_solve_circ<NX, SENS_WT_REFINE>(P, F, Bs, b, D,
+                        [&](int k, double* gx, double* gu) {
+                            const double* z = snap + (size_t)k * S::SS + S::Z;
+#pragma unroll
+                            for (int i = 0; i < NX; ++i) gx[i] = (k < N && i < SENS_NWQ) ? m2df * (z[2 + i] - pr[X0 + NX * (k + 1) + i]) * dwt[i] : 0.0;
+                            gu[0] = k < N ? m2df * z[0] * dwt[SENS_NWQ] : 0.0;
+                            gu[1] = k < N ? m2df * z[1] * dwt[SENS_NWQ + 1] : 0.0;
+                        },
+                        [&](int, int, const SensCirc&, double*) { return 0.0; },
+                        [&](int, int, const SensCirc&, const double*, double) {}, SensVec{dw, 1}, nrow, om, work);
+}
+
+// reverse: seed_w [n_w] -> gwt [7] = (dw/dwt)' seed_w.  The solve of the seed gives (y_u,k, y_x,k) in sol; the transposed right-hand side of the
+// forward direction applied to them: grad_Q_i = sum_{k<N} -2 df e_k[i] y_x,k[i],  grad_R_j = sum_{k<N} -2 df u_k[j] y_u,k[j]
+template <int NX>
+MPC_HD void sens_adjoint_weights(const Params& P, const SensInst& si, double* F, const size_t Bs, const int b, const double* D, const double* snap,
+                                 const double* pr, const double* seed, double* gwt, const SensVec sol, const SensVec nrow, const SensVec om,
+                                 const SensVec work) {
+    using S = Sens<NX>;
+    const int N = P.N, X0 = 2 * N;
+    const double m2df = -2.0 * si.df;
+    sens_solve_circ<NX, SENS_WT_REFINE>(P, F, Bs, b, D,
+                        [&](int k, double* gx, double* gu) {
+#pragma unroll
+                            for (int i = 0; i < NX; ++i) gx[i] = seed[X0 + NX * k + i];
+                            gu[0] = k < N ? seed[2 * k] : 0.0;
+                            gu[1] = k < N ? seed[2 * k + 1] : 0.0;
+                        },
+                        [&](int, int, const SensCirc&, double*) { return 0.0; },
+                        [&](int, int, const SensCirc&, const double*, double) {}, sol, nrow, om, work);
+    double acc[SENS_NWT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < N; ++k) {
+        const double* z = snap + (size_t)k * S::SS + S::Z;
+#pragma unroll
+        for (int i = 0; i < SENS_NWQ; ++i) acc[i] += m2df * (z[2 + i] - pr[X0 + NX * (k + 1) + i]) * sol[X0 + NX * k + i];
+        acc[SENS_NWQ] += m2df * z[0] * sol[2 * k];
+        acc[SENS_NWQ + 1] += m2df * z[1] * sol[2 * k + 1];
+    }
+#pragma unroll
+    for (int i = 0; i < SENS_NWT; ++i) gwt[i] = acc[i];
+}
+
+// lam_wt [7] = d/dwt [f + lam_g' g] at the snapshot's iterate = [sum_{k<N} e_k[i]^2 | sum_{k<N} u_k[j]^2] (no constraint row holds a weight):
+// by the envelope theorem the derivative of the optimal objective, unscaled
+template <int NX>
+MPC_HD void sens_lam_weights(const Params& P, const double* snap, const double* pr, double* lwt) {
+    using S = Sens<NX>;
+    const int N = P.N, X0 = 2 * N;
+    double acc[SENS_NWT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < N; ++k) {
+        const double* z = snap + (size_t)k * S::SS + S::Z;
+#pragma unroll
+        for (int i = 0; i < SENS_NWQ; ++i) { const double e = z[2 + i] - pr[X0 + NX * (k + 1) + i]; acc[i] += e * e; }
+        acc[SENS_NWQ] += z[0] * z[0];
+        acc[SENS_NWQ + 1] += z[1] * z[1];
+    }
+#pragma unroll
+    for (int i = 0; i < SENS_NWT; ++i) lwt[i] = acc[i];
 }
 
 }  // namespace mpc

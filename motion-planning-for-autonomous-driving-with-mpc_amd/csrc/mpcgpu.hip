@@ -2561,6 +2561,41 @@ __global__ void __launch_bounds__(SENS_THREADS) k_sens_obst(const Params P, cons
     }
 }
 
+// Lane per instance, the mapping of k_sens_obst: the same factor of the snapshot, then the derivative with respect to the seven cost weights
+// wt = [Q_0 .. Q_4 | R_0, R_1] (mpc_sens_weights): n_dir forward directions dwt [B, n_dir, 7] -> dw [B, n_dir, n_w] and / or one adjoint seed
+// [B, n_w] -> grad_wt [B, 7], and lam_wt [B, 7] = d/dwt [f + lam_g' g].  p [B, n_w]: the p rows of the solve (xref).  NaN where the factor
+// failed.  W: [sens_obst_scratch_len][B], as k_sens_obst's (the solves are sens_solve_circ's: refined against the stage data of sens_obst_setup).
+template <int NX>
+__global__ void __launch_bounds__(SENS_THREADS) k_sens_weights(const Params P, const double* snap, double* F, double* W, const double* p, const int n_dir,
+                                                              const double* dwt, double* dw, const double* seed, double* grad_wt, double* lam_wt) {
+    const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
+    if (b >= P.B) return;
+    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), Bs = (size_t)P.B, nn = (size_t)3 * (P.N + 1);
+    const double* sb = snap + (size_t)b * Sens<NX>::len(P.N);
+    const double* pr = p + (size_t)b * nw;
+    const SensInst si = sens_factor<NX>(P, sb, F, Bs, b);
+    if (si.ok && (n_dir > 0 || grad_wt)) sens_obst_setup<NX>(P, sb, W, Bs, b);
+    double* V = W + (size_t)(P.N + 1) * SensObst<NX>::DS * Bs + b;
+    const SensVec sol{V, Bs}, work{V + nw * Bs, Bs}, nrow{V + 2 * nw * Bs, Bs}, om{V + (2 * nw + nn) * Bs, Bs};
+    for (int d = 0; d < n_dir; ++d) {
+        double* o = dw + ((size_t)b * n_dir + d) * nw;
+        if (si.ok) sens_forward_weights<NX>(P, si, F, Bs, b, W, sb, pr, dwt + ((size_t)b * n_dir + d) * SENS_NWT, o, nrow, om, work);
+        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
+    }
+    if (grad_wt) {
+        double gw[SENS_NWT];
+        if (si.ok) sens_adjoint_weights<NX>(P, si, F, Bs, b, W, sb, pr, seed + (size_t)b * nw, gw, sol, nrow, om, work);
+#pragma unroll
+        for (int i = 0; i < SENS_NWT; ++i) grad_wt[(size_t)b * SENS_NWT + i] = si.ok ? gw[i] : NAN;
+    }
+    if (lam_wt) {
+        double lw[SENS_NWT];
+        if (si.ok) sens_lam_weights<NX>(P, sb, pr, lw);
+#pragma unroll
+        for (int i = 0; i < SENS_NWT; ++i) lam_wt[(size_t)b * SENS_NWT + i] = si.ok ? lw[i] : NAN;
+    }
+}
+
 template <int NX>
 __global__ void k_plant_step(const Params Pk, const double* x, const double* u, double* xn, int B, int integrator) {
     const PRef P(Pk);
@@ -2607,8 +2642,8 @@ enum Scratch : int {
     SCR_EX_LAM,                         // solve_ex_dev: the multiplier rows (lam_g or lam_x) the caller did not ask for
     SCR_SENS_SNAP,                      // solve_sens_dev: snapshot of the final iterates (read again by mpc_sens_adjoint_dev)
     SCR_SENS_LAM_G,                     // solve_sens_dev: lam_g for lam_p when the caller did not ask for it (live beside SCR_EX_LAM, then lam_x)
-    SCR_SENS_F,                         // sens_launch, sens_obst_launch: the factors of the KKT matrices
-    SCR_SENS_OBST,                      // sens_obst_launch: the stage data and the solves' vectors (sens_obst_setup, sens_solve_circ)
+    SCR_SENS_F,                         // sens_launch, sens_obst_launch, sens_weights_launch: the factors of the KKT matrices
+    SCR_SENS_OBST,                      // sens_obst_launch, sens_weights_launch: the stage data and the solves' vectors (sens_obst_setup, sens_solve_circ)
     SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
     SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
     SCR_LOOP_OBST,                      // closed_loop_dev: the obstacle rows of a loop with per-ego obstacle tracks (k_loop_obst)
@@ -3716,6 +3751,29 @@ static const char* bad_sens_obst(int32_t B, int32_t n_dir, const double* dobst, 
     return nullptr;
 }
 
+// the same factor, solved against the cost weights' right-hand sides (k_sens_weights)
+static int sens_weights_launch(mpc_handle* h, int32_t B, const double* d_p, int32_t n_dir, const double* d_dwt, double* d_dw, const double* d_seed, double* d_grad,
+                               double* d_lam, hipStream_t s) {
+    const int N = h->hp.desc.N;
+    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(N + 1) * (size_t)sens_fs(h) * 8));
+    size_t wlen = 0;
+    FOR_NX(h, wlen = sens_obst_scratch_len<NX>(N));
+    double* W = static_cast<double*>(scratch_get(h, SCR_SENS_OBST, (size_t)B * wlen * 8));
+    if (!F || !W) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
+    const double* snap = static_cast<const double*>(h->scratch[SCR_SENS_SNAP]);
+    FOR_NX(h, hipLaunchKernelGGL((k_sens_weights<NX>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F, W, d_p,
+                                 n_dir, d_dwt, d_dw, d_seed, d_grad, d_lam));
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+static const char* bad_sens_weights(int32_t B, const double* p, int32_t n_dir, const double* dwt, const double* dw, const double* seed_w, const double* grad_wt) {
+    if (B <= 0) return "B > 0 is required";
+    if (!p) return "mpc_sens_weights: p (the p rows of the solve) is required";
+    if (n_dir < 0 || (n_dir > 0 && (!dwt || !dw))) return "mpc_sens_weights: n_dir >= 0, and dwt, dw are required when n_dir > 0";
+    if ((seed_w != nullptr) != (grad_wt != nullptr)) return "mpc_sens_weights: seed_w and grad_wt go together";
+    return nullptr;
+}
+
 // solve_ex_dev plus the snapshot of the final iterates, CasADi's lam_p and n_dir forward sensitivities
 static int solve_sens_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, double* d_lam_p, int32_t n_dir, const double* d_dp, double* d_dw, hipStream_t s) {
     int rc = supply_status(h, io);
@@ -3859,6 +3917,44 @@ int mpc_sens_obst(mpc_handle* h, int32_t B, int32_t n_dir, const double* dobst, 
                           {grad_obst, nB * 6 * 8, true}, {lam_obst, nB * 6 * 8, true}}, [&](void** d, hipStream_t s) {
         return mpc_sens_obst_dev(h, B, n_dir, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], s);
     });
+}
+
+// the derivative with respect to the cost weights on the same snapshot, under the same rule (enqueued on `stream`)
+int mpc_sens_weights_dev(mpc_handle* h, int32_t B, const double* d_p, int32_t n_dir, const double* d_dwt, double* d_dw, const double* d_seed_w,
+                         double* d_grad_wt, double* d_lam_wt, void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    if (const char* bad = bad_sens_weights(B, d_p, n_dir, d_dwt, d_dw, d_seed_w, d_grad_wt)) { h->err = bad; return MPC_ERR_INVALID; }
+    if (!h->snap_ok || B != h->snap_B) {
+        h->err = "mpc_sens_weights: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B, or mpc_set_weights came after it";
+        return MPC_ERR_STATE;
+    }
+    if (n_dir == 0 && !d_grad_wt && !d_lam_wt) return MPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return sens_weights_launch(h, B, d_p, n_dir, d_dwt, d_dw, d_seed_w, d_grad_wt, d_lam_wt, (hipStream_t)stream_);
+}
+
+int mpc_sens_weights(mpc_handle* h, int32_t B, const double* p, int32_t n_dir, const double* dwt, double* dw, const double* seed_w, double* grad_wt,
+                     double* lam_wt) {
+    if (!h) return MPC_ERR_INVALID;
+    if (const char* bad = bad_sens_weights(B, p, n_dir, dwt, dw, seed_w, grad_wt)) { h->err = bad; return MPC_ERR_INVALID; }
+    const size_t nw = h->hp.n_w(), nB = (size_t)B, nd = (size_t)n_dir;
+    return stage_host(h, {{p, nB * nw * 8, false}, {n_dir ? dwt : nullptr, nB * nd * SENS_NWT * 8, false}, {n_dir ? dw : nullptr, nB * nd * nw * 8, true},
+                          {seed_w, nB * nw * 8, false}, {grad_wt, nB * SENS_NWT * 8, true}, {lam_wt, nB * SENS_NWT * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_sens_weights_dev(h, B, (double*)d[0], n_dir, (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], (double*)d[5], s);
+    });
+}
+
+// Host bookkeeping only: every launch builds its Params from the descriptor (fill_params), so nothing on the device holds a weight.
+int mpc_set_weights(mpc_handle* h, const double* Q, const double* R) {
+    if (!h) return MPC_ERR_INVALID;
+    for (int i = 0; Q && i < 5; ++i)
+        if (!std::isfinite(Q[i]) || Q[i] < 0.0) { h->err = "mpc_set_weights: Q[0..4] must be finite and >= 0"; return MPC_ERR_INVALID; }
+    for (int j = 0; R && j < 2; ++j)
+        if (!std::isfinite(R[j]) || !(R[j] > 0.0)) { h->err = "mpc_set_weights: R[0..1] must be finite and > 0"; return MPC_ERR_INVALID; }
+    for (int i = 0; Q && i < 5; ++i) h->hp.desc.Q[i] = Q[i];
+    for (int j = 0; R && j < 2; ++j) h->hp.desc.R[j] = R[j];
+    h->snap_ok = false;                 // (the factor reads the weights: a snapshot taken under the old ones is no longer differentiable)
+    return MPC_OK;
 }
 
 int mpc_plant_step_dev(mpc_handle* h, int32_t B, int32_t integrator, const double* d_x, const double* d_u, double* d_x_next, void* stream_) {

@@ -63,6 +63,15 @@ class ObstSens:
     lam_obst: np.ndarray | None = None   # [B, 6] d/do [f + lam_g' g] = d f*/do
 
 
+@dataclass
+class WeightSens:
+    """sens_weights(): the derivative of the last solve's optimum with respect to the seven cost weights wt = [Q_0 .. Q_4 | R_0, R_1]
+    (mpc_sens_weights).  The weights are shared by the batch; the rows are per instance (sum them for the derivative of a batch loss)"""
+    dw: np.ndarray | None = None         # [B, n_dir, n_w] (dw*/dwt) dweights, NaN where status != 1
+    grad_wt: np.ndarray | None = None    # [B, 7] (dw*/dwt)' seed_w
+    lam_wt: np.ndarray | None = None     # [B, 7] d/dwt [f + lam_g' g] = d f*/dwt
+
+
 class BatchedMPCSolver:
     def __init__(self, N, nx=5, *, dt=0.1, Q=None, R=None, P=None, obstacle_centers=None, wheelbase=2.5789128,
                  friction_div=2.578, ego_offset=0.75, max_iter=100, tol=1e-8, fixed_iters=0, obst_mult=3, device=0,
@@ -130,6 +139,27 @@ class BatchedMPCSolver:
         self._check(self._lib.mpc_set_bounds(self._h, *[_abi.as_dp(a) for a in arrs]))
         self._bounds_key = key
         self._bounds = tuple(a.copy() for a in arrs)            # (lbx, ubx, lbg, ubg), for rescue_failed()
+
+    def set_weights(self, Q=None, R=None):
+        """replaces the cost weights Q[0..4] and / or R[0..1] of the live handle (mpc_set_weights): host bookkeeping only, no device work,
+        no synchronisation; every later call (FORCES-mode solves included) sees them.  Ends the life of the sensitivity snapshot, as a solve
+        does.  Invalid weights (non-finite, Q < 0, R <= 0) raise MpcError with code MPC_ERR_INVALID and change nothing."""
+        q = None if Q is None else _abi.f64(Q).ravel()[:5]
+        r = None if R is None else _abi.f64(R).ravel()
+        if (q is not None and q.size != 5) or (r is not None and r.size != 2):
+            raise MpcError(_abi.MPC_ERR_INVALID, "set_weights: Q must have 5 entries (a sixth is ignored) and R 2")
+        q = None if q is None else np.ascontiguousarray(q)
+        self._check(self._lib.mpc_set_weights(self._h, _abi.as_dp(q), _abi.as_dp(r)))
+        self._sens_gen += 1                                  # (a backward pass of autograd.py on the old snapshot raises)
+        for i in range(5 if q is not None else 0):
+            self.desc.Q[i] = q[i]
+        for j in range(2 if r is not None else 0):
+            self.desc.R[j] = r[j]
+
+    @property
+    def weights(self):
+        """the current seven cost weights [Q_0 .. Q_4 | R_0, R_1]"""
+        return np.array([self.desc.Q[i] for i in range(5)] + [self.desc.R[0], self.desc.R[1]])
 
     def _rows_in(self, name, x, p, obst):
         """(B, x [B, n_w], p [B, n_w], obst [B, 6] | None) as contiguous doubles; a single instance may come as vectors"""
@@ -249,6 +279,33 @@ class BatchedMPCSolver:
         self._check(self._lib.mpc_sens_obst(self._h, B, n_dir, _abi.as_dp(dobst), _abi.as_dp(dw), _abi.as_dp(seed_w), _abi.as_dp(grad), _abi.as_dp(lo)))
         return ObstSens(dw, grad, lo)
 
+    def sens_weights(self, p, dweights=None, seed_w=None, lam=False) -> WeightSens:
+        """the derivative of the optimum of the last solve(..., lam_p / dp) of this solver with respect to its seven cost weights
+        wt = [Q_0 .. Q_4 | R_0, R_1] (see `weights`).  p [B, n_w]: the p of that solve (not checked against it).  dweights [B, n_dir, 7] (or
+        [B, 7]) -> dw [B, n_dir, n_w]; seed_w [B, n_w] -> grad_wt [B, 7]; lam=True: lam_wt [B, 7], the derivative of the optimal objective
+        (mpc_sens_weights; any solve or set_weights in between -> MpcError with code MPC_ERR_STATE)"""
+        B = self._sens_B
+        p = _abi.f64(p, (B, self.n_w))
+        dw = grad = lw = None
+        n_dir = 0
+        if dweights is not None:
+            dweights = _abi.f64(dweights)
+            if dweights.ndim == 2:
+                dweights = dweights[:, None, :]
+            if dweights.ndim != 3 or dweights.shape[0] != B or dweights.shape[2] != 7:
+                raise MpcError(_abi.MPC_ERR_INVALID, f"dweights must be [{B}, n_dir, 7]")
+            dweights = np.ascontiguousarray(dweights)
+            n_dir = dweights.shape[1]
+            dw = np.empty((B, n_dir, self.n_w))
+        if seed_w is not None:
+            seed_w = _abi.f64(seed_w, (B, self.n_w))
+            grad = np.empty((B, 7))
+        if lam:
+            lw = np.empty((B, 7))
+        self._check(self._lib.mpc_sens_weights(self._h, B, _abi.as_dp(p), n_dir, _abi.as_dp(dweights), _abi.as_dp(dw), _abi.as_dp(seed_w), _abi.as_dp(grad),
+                                               _abi.as_dp(lw)))
+        return WeightSens(dw, grad, lw)
+
     def feedback_gain(self, x0, p, obst=None):
         """du_0*/dxref_0 [B, nu, nx]: the linearised control law around the optimum (xref_0 is the measured state the plan starts from)"""
         x0 = _abi.f64(x0)
@@ -333,6 +390,12 @@ class BatchedMPCSolver:
         d_grad_obst [B, 6], d_lam_obst [B, 6]; 0 = not asked for"""
         self._check(self._lib.mpc_sens_obst_dev(self._h, int(B), int(n_dir), _vp(d_dobst), _vp(d_dw), _vp(d_seed_w), _vp(d_grad_obst), _vp(d_lam_obst),
                                                 _vp(stream)))
+
+    def sens_weights_device(self, B, d_p, n_dir=0, d_dweights=0, d_dw=0, d_seed_w=0, d_grad_wt=0, d_lam_wt=0, stream=0):
+        """device form of sens_weights (enqueued on `stream`, not synchronised): d_p [B, n_w] the p of the solve; d_dweights [B, n_dir, 7] ->
+        d_dw [B, n_dir, n_w], d_seed_w [B, n_w] -> d_grad_wt [B, 7], d_lam_wt [B, 7]; 0 = not asked for"""
+        self._check(self._lib.mpc_sens_weights_dev(self._h, int(B), _vp(d_p), int(n_dir), _vp(d_dweights), _vp(d_dw), _vp(d_seed_w), _vp(d_grad_wt),
+                                                   _vp(d_lam_wt), _vp(stream)))
 
     def plant_step(self, x, u, integrator="euler"):
         x = _abi.f64(x)

@@ -1,7 +1,8 @@
 """Cost of the parametric sensitivities (mpc_solve_batch_sens_dev, mpc_sens_adjoint_dev) against the plain device solve and _ex, same handle,
 same batch, alternating samples: plain | _ex (f, g, lam_g, lam_x) | _sens with lam_p only | _sens with n_dir = nx forward seeds | the
 adjoint alone (on the snapshot of the last _sens call) | mpc_sens_obst_dev alone on the same snapshot: its adjoint with lam_obst, and six
-forward directions (the unit directions of the obstacle centres).
+forward directions (the unit directions of the obstacle centres) | mpc_sens_weights_dev alone on the same snapshot: its adjoint with
+lam_wt, and seven forward directions (the unit directions of the weights).
 Usage (GPU box): python tools/sens_cost.py [B] [family] [reps]"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
@@ -33,6 +34,8 @@ dw = torch.empty_like(dp)
 seed = torch.randn((B, nw), dtype=torch.float64, device=dev); gp = torch.empty_like(seed)
 dob = torch.eye(6, dtype=torch.float64, device=dev).repeat(B, 1, 1).contiguous(); dwo = torch.empty((B, 6, nw), dtype=torch.float64, device=dev)
 go = torch.empty((B, 6), dtype=torch.float64, device=dev); lo = torch.empty_like(go)
+dwt = torch.eye(7, dtype=torch.float64, device=dev).repeat(B, 1, 1).contiguous(); dww = torch.empty((B, 7, nw), dtype=torch.float64, device=dev)
+gw = torch.empty((B, 7), dtype=torch.float64, device=dev); lw = torch.empty_like(gw)
 ptrs = (tx0.data_ptr(), tp.data_ptr(), out.data_ptr(), st.data_ptr(), it.data_ptr(), kk.data_ptr())
 
 
@@ -64,6 +67,14 @@ def obst_fwd():
     s.sens_obst_device(B, 6, dob.data_ptr(), dwo.data_ptr())
 
 
+def wt_adjoint():
+    s.sens_weights_device(B, tp.data_ptr(), d_seed_w=seed.data_ptr(), d_grad_wt=gw.data_ptr(), d_lam_wt=lw.data_ptr())
+
+
+def wt_fwd():
+    s.sens_weights_device(B, tp.data_ptr(), 7, dwt.data_ptr(), dww.data_ptr())
+
+
 def sample(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -72,8 +83,9 @@ def sample(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
-fns = dict(plain=plain, ex=ex, sens_lam_p=sens_lam_p, sens_fwd_nx=sens_fwd, adjoint=adjoint, obst_adjoint=obst_adjoint, obst_fwd_6=obst_fwd)
-ON_SNAPSHOT = ("adjoint", "obst_adjoint", "obst_fwd_6")
+fns = dict(plain=plain, ex=ex, sens_lam_p=sens_lam_p, sens_fwd_nx=sens_fwd, adjoint=adjoint, obst_adjoint=obst_adjoint, obst_fwd_6=obst_fwd,
+           wt_adjoint=wt_adjoint, wt_fwd_7=wt_fwd)
+ON_SNAPSHOT = ("adjoint", "obst_adjoint", "obst_fwd_6", "wt_adjoint", "wt_fwd_7")
 for _ in range(3):
     for k, fn in fns.items():
         if k in ON_SNAPSHOT:
@@ -91,4 +103,5 @@ for k, v in t.items():
     print(f"  {k:12s} {med[k]:8.4f} / {min(v):8.4f}")
 print(f"  cost over plain: _ex {1e3 * (med['ex'] - med['plain']):.1f} us, _sens lam_p {1e3 * (med['sens_lam_p'] - med['plain']):.1f} us, "
       f"_sens n_dir = {nx} {1e3 * (med['sens_fwd_nx'] - med['plain']):.1f} us, adjoint alone {1e3 * med['adjoint']:.1f} us, "
-      f"obstacle adjoint + lam_obst alone {1e3 * med['obst_adjoint']:.1f} us, six obstacle directions alone {1e3 * med['obst_fwd_6']:.1f} us")
+      f"obstacle adjoint + lam_obst alone {1e3 * med['obst_adjoint']:.1f} us, six obstacle directions alone {1e3 * med['obst_fwd_6']:.1f} us, "
+      f"weights adjoint + lam_wt alone {1e3 * med['wt_adjoint']:.1f} us, seven weight directions alone {1e3 * med['wt_fwd_7']:.1f} us")
