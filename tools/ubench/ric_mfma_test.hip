@@ -2,17 +2,26 @@
 // recursion (ric_matrix_step / ric_vector_step / riccati_forward_step of csrc/mpc_stage_math.h, run on the host):
 // random stage blocks of NI instances, cost-to-go P_k / p_k, gains, Newton step compared entry by entry; shader-clock ticks per sweep.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o ric_mfma_test ric_mfma_test.hip ; run on the GPU box.
+//
+// ric_mfma_test <in> <out>: the case-file mode of the accuracy tests (tests/test_gpu_riccati_accuracy.py, formats in ric_cases.h).  Every case
+// of <in> goes through the one-instance-per-lane recursion on the device (k_lane: one case and code path per lane, the last wavefront partly
+// filled) and through the MFMA sweeps with one and with two instances per wavefront (neighbours in the file that share nx and N; a group
+// of odd size: the last one next to a copy of itself), delta_last and the symmetry mark taken from the case.  <out>: one block of results
+// per code path -- the three per-lane instantiations, MFMA x 1, MFMA x 2 -- each with every case in file order; the MFMA blocks carry the
+// sweeps of the WAVEFRONT where the others carry the case's own.  Nothing is judged here: the test compares with its reference.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
 #include <vector>
+#include "ric_cases.h"
 #include "../../motion-planning-for-autonomous-driving-with-mpc_amd/csrc/mpc_riccati_mfma.h"
 using namespace mpc;
 
 template <int NX, int NI>
 __global__ void __launch_bounds__(64) k_test(const Params Pk, const double* recs /*[NI][N+1][Rec::SIZE]*/, const double* c0 /*[NI][NX]*/, const double* hux /*[NI][2]*/,
-                                             const double* dlast, double* kout /*[NI][N][16]*/, unsigned long long* clk, int* okout, double* dout) {
+                                             const double* dlast, double* kout /*[NI][N][16]*/, unsigned long long* clk, int* okout, double* dout,
+                                             const double* symh /*[NI]: != 0: the symmetry mark*/, unsigned* swout /*[NI]: sweeps of the wavefront*/) {
     const PRef P(Pk);
 #if defined(__HIP_DEVICE_COMPILE__)
     using RC = Rec<NX>;
@@ -34,7 +43,7 @@ __global__ void __launch_bounds__(64) k_test(const Params Pk, const double* recs
         const int b = inst * NI + q;
         in[q].inst = (uint32_t)b;
         in[q].delta_last = dlast[b];
-        in[q].sym_hint = false;
+        in[q].sym_hint = symh[b] != 0.0;
         rec[q] = (mpc_lds_ptr)(lp)lrec + q * (N + 1) * stride;
         x0[q] = 0.0;
         if ((lane & 3) == 0) x0[q] = (m.Rb < NX) ? -c0[b * NX + m.Rb] : (m.Rb == 7 ? 1.0 : 0.0);
@@ -68,7 +77,7 @@ __global__ void __launch_bounds__(64) k_test(const Params Pk, const double* recs
         for (int k = 0; k < N; ++k)
             if (lane < 16) kout[((size_t)(inst * NI + q) * N + k) * 16 + lane] = lrec[(q * (N + 1) + k) * stride + RC::K0 + lane];
     if (lane == 0) {
-        for (int q = 0; q < NI; ++q) { clk[(inst * NI + q) * 2] = (t1 - t0) / NI; clk[(inst * NI + q) * 2 + 1] = (t2 - t1) / NI; okout[inst * NI + q] = ok[q] ? 1 : -1; dout[inst * NI + q] = delta[q]; }
+        for (int q = 0; q < NI; ++q) { clk[(inst * NI + q) * 2] = (t1 - t0) / NI; clk[(inst * NI + q) * 2 + 1] = (t2 - t1) / NI; okout[inst * NI + q] = ok[q] ? 1 : -1; dout[inst * NI + q] = delta[q]; swout[inst * NI + q] = sweeps; }
     }
 #endif
 }
@@ -116,9 +125,10 @@ static int run(int N, int NI, bool nonconvex) {
     (void)hipMalloc(&d_hux, hux.size() * 8); (void)hipMemcpy(d_hux, hux.data(), hux.size() * 8, hipMemcpyHostToDevice);
     (void)hipMalloc(&d_dl, NI * 8); (void)hipMemcpy(d_dl, dlast.data(), NI * 8, hipMemcpyHostToDevice);
     (void)hipMalloc(&d_k, (size_t)NI * N * 16 * 8); (void)hipMalloc(&d_clk, NI * 16); (void)hipMalloc(&d_ok, NI * 4); (void)hipMalloc(&d_do, NI * 8);
+    double* d_sym; unsigned* d_sw; (void)hipMalloc(&d_sym, NI * 8); (void)hipMemset(d_sym, 0, NI * 8); (void)hipMalloc(&d_sw, NI * 4);      // (no instance carries the mark)
     const size_t lds = ((size_t)NW * (N + 1) * RC::SIZE + RC::SIZE + 64) * 8;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_test<NX, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    for (int rep = 0; rep < 2; ++rep) { hipLaunchKernelGGL((k_test<NX, NW>), dim3(NI / NW), dim3(64), lds, 0, P, d_rec, d_c0, d_hux, d_dl, d_k, d_clk, d_ok, d_do); (void)hipDeviceSynchronize(); }
+    for (int rep = 0; rep < 2; ++rep) { hipLaunchKernelGGL((k_test<NX, NW>), dim3(NI / NW), dim3(64), lds, 0, P, d_rec, d_c0, d_hux, d_dl, d_k, d_clk, d_ok, d_do, d_sym, d_sw); (void)hipDeviceSynchronize(); }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { printf("launch failed: %s\n", hipGetErrorString(e)); return 1; }
     std::vector<double> ws(pk_el + dz_el), kk((size_t)NI * N * 16), dout(NI);
@@ -193,7 +203,190 @@ static int run(int N, int NI, bool nonconvex) {
     return (eP < 1e-10 && ep < 1e-10 && eK < 1e-10 && eD < 1e-9 && bad == 0) ? 0 : 1;
 }
 
-int main() {
+// ---- case-file mode -----------------------------------------------------------------------------------------------------------------------
+// the one-instance-per-lane recursion as the device compiler builds it: lane g runs case lane_case[g] in the instantiation lane_path[g]
+// (ric_cases.h: the loop riccati_tile runs around riccati_backward_step / riccati_forward_step); every lane of a launch has the same NX and N
+template <int NX>
+__global__ void __launch_bounds__(64) k_lane(const Params Pk, const double* cases, const unsigned* lane_case, const int* lane_path, const unsigned* lane_out, int nlanes, double* out) {
+    const PRef P(Pk);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= nlanes) return;
+    const double* cs = cases + lane_case[g];
+    double* o = out + lane_out[g];
+    ricx::lane_backward<NX>(P, cs, lane_path[g], o);
+    ricx::lane_forward<NX>(P, (uint32_t)g, P.N, cs, o);
+#endif
+}
+
+struct FileCase { int nx, N; size_t in_off, out_off; };
+#define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { printf("%s: %s\n", #call, hipGetErrorString(e_)); return 1; } } while (0)
+
+// the cases `idx` (same NX, N) on lanes: path p of the q-th case on lane p * count + q; results into blocks 0 .. N_PATHS - 1 of `out`
+template <int NX>
+static int lane_group(const std::vector<double>& in, const double* d_in, const std::vector<FileCase>& cases, const std::vector<int>& idx, size_t blk, double* d_out,
+                      std::vector<double>& out) {
+    const int nc = (int)idx.size(), nlanes = nc * ricx::N_PATHS, N = cases[idx[0]].N, ntiles = (nlanes + 63) / 64;
+    std::vector<unsigned> lane_case(nlanes), lane_out(nlanes);
+    std::vector<int> lane_path(nlanes);
+    for (int g = 0; g < nlanes; ++g) {
+        const FileCase& c = cases[idx[g % nc]];
+        lane_path[g] = g / nc;
+        lane_case[g] = (unsigned)c.in_off;
+        lane_out[g] = (unsigned)((size_t)lane_path[g] * blk + c.out_off);
+    }
+    const uint32_t tile = ricx::dz_tile_elems<NX>(N);
+    double* d_dz; unsigned *d_lc, *d_lo; int* d_lp;
+    HIP_OK(hipMalloc(&d_dz, (size_t)ntiles * tile * 8)); HIP_OK(hipMemset(d_dz, 0, (size_t)ntiles * tile * 8));
+    HIP_OK(hipMalloc(&d_lc, nlanes * 4)); HIP_OK(hipMalloc(&d_lo, nlanes * 4)); HIP_OK(hipMalloc(&d_lp, nlanes * 4));
+    HIP_OK(hipMemcpy(d_lc, lane_case.data(), nlanes * 4, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(d_lo, lane_out.data(), nlanes * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_lp, lane_path.data(), nlanes * 4, hipMemcpyHostToDevice));
+    Params P{};
+    P.N = N; P.dt = in[cases[idx[0]].in_off + ricx::C_DT]; P.B = nlanes; P.Bp = ntiles * 64; P.nx = NX;
+    P.WS = d_dz; P.ws_bytes = (uint32_t)((size_t)ntiles * tile * 8); P.DZ = d_dz; P.tile_elems = tile;
+    hipLaunchKernelGGL((k_lane<NX>), dim3(ntiles), dim3(64), 0, 0, P, d_in, d_lc, d_lp, d_lo, nlanes, d_out);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipGetLastError());
+    std::vector<double> dz((size_t)ntiles * tile);
+    HIP_OK(hipMemcpy(dz.data(), d_dz, dz.size() * 8, hipMemcpyDeviceToHost));
+    for (int g = 0; g < nlanes; ++g) {
+        double* o = &out[lane_out[g]];
+        HIP_OK(hipMemcpy(o, d_out + lane_out[g], ricx::out_doubles(N) * 8, hipMemcpyDeviceToHost));
+        ricx::copy_step<NX>(dz.data(), tile, (uint32_t)g, N, o);
+    }
+    (void)hipFree(d_dz); (void)hipFree(d_lc); (void)hipFree(d_lo); (void)hipFree(d_lp);
+    return 0;
+}
+
+// the same cases through the MFMA sweeps, NW per wavefront: neighbours in `idx` share one
+template <int NX, int NW>
+static int mfma_group(const std::vector<double>& in, const std::vector<FileCase>& cases, const std::vector<int>& idx_in, double* out /* the block of this code path */) {
+    using D = Dim<NX>;
+    using RC = Rec<NX>;
+    constexpr int NS = D::NS;
+    std::vector<int> idx(idx_in);
+    while (idx.size() % NW) idx.push_back(idx.back());
+    const int NI = (int)idx.size(), N = cases[idx[0]].N;
+    const double dt = in[cases[idx[0]].in_off + ricx::C_DT];
+    std::vector<double> recs((size_t)NI * (N + 1) * RC::SIZE, 0.0), c0(NI * NX), hux(NI * 2), dlast(NI), symh(NI);
+    for (int b = 0; b < NI; ++b) {
+        const double* cs = &in[cases[idx[b]].in_off];
+        for (int i = 0; i < NX; ++i) c0[b * NX + i] = cs[ricx::C_C0 + i];
+        hux[b * 2] = cs[ricx::C_HUX]; hux[b * 2 + 1] = cs[ricx::C_HUX + 1];
+        dlast[b] = cs[ricx::C_DLAST]; symh[b] = cs[ricx::C_SYM];
+        for (int k = 0; k <= N; ++k) {
+            const double* st = cs + ricx::CASE_HEAD + (size_t)k * ricx::CASE_STAGE;
+            double* r = &recs[((size_t)b * (N + 1) + k) * RC::SIZE];
+            for (int i = 0; i < 6; ++i) r[RC::A + i] = st[ricx::S_A + i];
+            r[RC::RUU] = st[ricx::S_RUU]; r[RC::RUU + 1] = st[ricx::S_RUU + 1]; r[RC::GU] = st[ricx::S_GU]; r[RC::GU + 1] = st[ricx::S_GU + 1];
+            for (int i = 0; i < NX; ++i) { r[RC::NCN + i] = -st[ricx::S_CN + i]; r[RC::GX + i] = st[ricx::S_GX + i]; }
+            for (int i = 0; i < NX; ++i) for (int j = i; j < NX; ++j) if (D::hrow(i, j) >= 0) r[RC::H + D::hrow(i, j)] = st[ricx::S_H + i * 6 + j];
+            r[RC::ZERO] = 0.0; r[RC::ONE] = 1.0; r[RC::DT] = dt;
+            r[RC::HX] = k == 0 ? hux[b * 2] : 0.0; r[RC::HX + 1] = k == 0 ? hux[b * 2 + 1] : 0.0;
+        }
+    }
+    const size_t pk_el = (size_t)(N + 1) * MPC_EV(D::NPK) * NI, dz_el = (size_t)(N + 1) * MPC_EV(D::NZ) * NI;
+    double* d_ws; HIP_OK(hipMalloc(&d_ws, (pk_el + dz_el + 128) * 8)); HIP_OK(hipMemset(d_ws, 0, (pk_el + dz_el + 128) * 8));
+    Params P{};
+    P.N = N; P.dt = dt; P.B = NI; P.Bp = 64; P.nx = NX;
+    P.WS = d_ws; P.ws_bytes = (uint32_t)((pk_el + dz_el + 128) * 8); P.MPK = d_ws; P.MDZ = d_ws + pk_el; P.KK = d_ws + pk_el + dz_el; P.tile_elems = (uint32_t)(pk_el + dz_el + 128);
+    double *d_rec, *d_c0, *d_hux, *d_dl, *d_k, *d_do, *d_sym; unsigned long long* d_clk; int* d_ok; unsigned* d_sw;
+    HIP_OK(hipMalloc(&d_rec, recs.size() * 8)); HIP_OK(hipMemcpy(d_rec, recs.data(), recs.size() * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMalloc(&d_c0, c0.size() * 8)); HIP_OK(hipMemcpy(d_c0, c0.data(), c0.size() * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMalloc(&d_hux, hux.size() * 8)); HIP_OK(hipMemcpy(d_hux, hux.data(), hux.size() * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMalloc(&d_dl, NI * 8)); HIP_OK(hipMemcpy(d_dl, dlast.data(), NI * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMalloc(&d_sym, NI * 8)); HIP_OK(hipMemcpy(d_sym, symh.data(), NI * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMalloc(&d_k, (size_t)NI * N * 16 * 8)); HIP_OK(hipMalloc(&d_clk, NI * 16)); HIP_OK(hipMalloc(&d_ok, NI * 4)); HIP_OK(hipMalloc(&d_do, NI * 8)); HIP_OK(hipMalloc(&d_sw, NI * 4));
+    const size_t lds = ((size_t)NW * (N + 1) * RC::SIZE + RC::SIZE + 64) * 8;
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_test<NX, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_test<NX, NW>), dim3(NI / NW), dim3(64), lds, 0, P, d_rec, d_c0, d_hux, d_dl, d_k, d_clk, d_ok, d_do, d_sym, d_sw);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipGetLastError());
+    std::vector<double> ws(pk_el + dz_el), kk((size_t)NI * N * 16), dout(NI);
+    std::vector<int> okv(NI); std::vector<unsigned> sw(NI);
+    HIP_OK(hipMemcpy(ws.data(), d_ws, ws.size() * 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(kk.data(), d_k, kk.size() * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(okv.data(), d_ok, NI * 4, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(dout.data(), d_do, NI * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(sw.data(), d_sw, NI * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < (int)idx_in.size(); ++b) {
+        double* o = out + cases[idx[b]].out_off;
+        o[0] = okv[b]; o[1] = dout[b]; o[2] = sw[b];
+        for (int k = 0; k <= N; ++k) {
+            double* os = o + ricx::OUT_HEAD + (size_t)k * ricx::OUT_STAGE;
+            const double* pk = &ws[((size_t)b * (N + 1) + k) * MPC_EV(D::NPK)];
+            const double* dz = &ws[pk_el + ((size_t)b * (N + 1) + k) * MPC_EV(D::NZ)];
+            for (int i = 0; i < NX; ++i) {
+                for (int j = i; j < NX; ++j) { os[ricx::O_P + i * 6 + j] = pk[D::sidx(i, j)]; os[ricx::O_P + j * 6 + i] = pk[D::sidx(i, j)]; }
+                os[ricx::O_PV + i] = pk[NS + i];
+            }
+            for (int e = 0; e < NX + 2; ++e) os[ricx::O_DU + e] = dz[e];
+            if (k < N) {
+                const double* g = &kk[((size_t)b * N + k) * 16];
+                for (int j = 0; j < NX; ++j) { os[ricx::O_K0 + j] = g[j]; os[ricx::O_K1 + j] = g[8 + j]; }
+                os[ricx::O_KFF] = g[7]; os[ricx::O_KFF + 1] = g[15];
+            }
+        }
+    }
+    (void)hipFree(d_ws); (void)hipFree(d_rec); (void)hipFree(d_c0); (void)hipFree(d_hux); (void)hipFree(d_dl); (void)hipFree(d_sym); (void)hipFree(d_k);
+    (void)hipFree(d_clk); (void)hipFree(d_ok); (void)hipFree(d_do); (void)hipFree(d_sw);
+    return 0;
+}
+
+template <int NX>
+static int file_group(const std::vector<double>& in, const double* d_in, const std::vector<FileCase>& cases, const std::vector<int>& idx, size_t blk, double* d_out,
+                      std::vector<double>& out) {
+    if (lane_group<NX>(in, d_in, cases, idx, blk, d_out, out)) return 1;
+    if (mfma_group<NX, 1>(in, cases, idx, out.data() + ricx::N_PATHS * blk)) return 1;
+    return mfma_group<NX, 2>(in, cases, idx, out.data() + (ricx::N_PATHS + 1) * blk);
+}
+
+static int run_file(const char* in_path, const char* out_path) {
+    std::vector<double> in;
+    {
+        FILE* f = fopen(in_path, "rb");
+        if (!f) { printf("cannot read %s\n", in_path); return 2; }
+        double buf[4096];
+        for (size_t n; (n = fread(buf, 8, 4096, f)) > 0;) in.insert(in.end(), buf, buf + n);
+        fclose(f);
+    }
+    if (in.empty()) { printf("empty case file\n"); return 2; }
+    const int n = (int)in[0];
+    std::vector<FileCase> cases;
+    size_t ci = 1, oi = 0;
+    for (int c = 0; c < n; ++c) {
+        if (ci + ricx::CASE_HEAD > in.size()) { printf("case %d: truncated file\n", c); return 2; }
+        const int nx = (int)in[ci + ricx::C_NX], N = (int)in[ci + ricx::C_N];
+        if ((nx != 5 && nx != 6) || N < 1 || N > 64 || ci + ricx::case_doubles(N) > in.size()) { printf("case %d: nx %d, N %d not handled or file truncated\n", c, nx, N); return 2; }
+        cases.push_back(FileCase{nx, N, ci, oi});
+        ci += ricx::case_doubles(N);
+        oi += ricx::out_doubles(N);
+    }
+    if (ci != in.size() || n < 1) { printf("malformed case file\n"); return 2; }
+    const size_t blk = oi;
+    constexpr int NBLK = ricx::N_PATHS + 2;
+    std::vector<double> out(blk * NBLK, 0.0);
+    double *d_in, *d_out;
+    HIP_OK(hipMalloc(&d_in, in.size() * 8)); HIP_OK(hipMemcpy(d_in, in.data(), in.size() * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMalloc(&d_out, blk * ricx::N_PATHS * 8)); HIP_OK(hipMemset(d_out, 0, blk * ricx::N_PATHS * 8));
+    std::vector<char> done(n, 0);
+    for (int c = 0; c < n; ++c) {
+        if (done[c]) continue;
+        std::vector<int> idx;
+        for (int q = c; q < n; ++q)
+            if (!done[q] && cases[q].nx == cases[c].nx && cases[q].N == cases[c].N && in[cases[q].in_off + ricx::C_DT] == in[cases[c].in_off + ricx::C_DT]) { idx.push_back(q); done[q] = 1; }
+        const int rc = cases[c].nx == 5 ? file_group<5>(in, d_in, cases, idx, blk, d_out, out) : file_group<6>(in, d_in, cases, idx, blk, d_out, out);
+        if (rc) return rc;
+        printf("nx %d N %d: %d cases\n", cases[c].nx, cases[c].N, (int)idx.size());
+    }
+    FILE* f = fopen(out_path, "wb");
+    if (!f || fwrite(out.data(), 8, out.size(), f) != out.size()) { printf("cannot write %s\n", out_path); return 2; }
+    fclose(f);
+    printf("OK\n");
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 3) return run_file(argv[1], argv[2]);
+    if (argc != 1) { printf("usage: ric_mfma_test [<cases in> <results out>]\n"); return 2; }
     int rc = 0;
     rc |= run<6, 1>(30, 8, false);
     rc |= run<6, 2>(30, 8, false);
