@@ -1957,8 +1957,14 @@ MPC_HD double sym(const double* Ps, int i, int j) { return Ps[(i <= j) ? Dim<NX>
 // One backward step of the recursion, in two halves that only meet through (P+, G, Lam^-1):
 //   ric_matrix_step  P+ -> P_k, gains K            (the critical chain: the next stage needs P_k)
 //   ric_vector_step  p+ -> p_k, feed-forward kff   (needs P+, G, Lam^-1 of the same stage; nothing waits for it)
-// riccati_backward_step below chains them (running them on two wavefronts, the vector half one stage behind, was measured
-// and rejected: DESIGN.md section 4).
+// riccati_backward_step below chains them on one thread (the emulation harness, k_solve_wg's scalar fallbacks, riccati_instance).
+// riccati_tile runs them on TWO wavefronts that both walk the matrix half: one stores what that half produces, the other -- a loader
+// wave that idles in the backward sweep -- adds the vector half and stores the rows with an entry of it (ric_store_matrix /
+// ric_store_vector below); nothing is handed over between them.  (Round 2 measured this form and dropped it: the sweep got shorter,
+// the batch did not, because the stage pool was the binding bound then, and the second wave's copy of the recursion rounded
+// differently.  Neither holds any more -- the pool has slack, and the contraction of every sum of products below is spelled out so
+// that a lane's bits do not depend on the instantiation: DESIGN.md section 4.  Handing G and Lam^-1 over through LDS, the vector
+// half one stage behind, stays rejected: ~18 ds_write per stage on the critical wave.)
 // With A = I + dtF (F has 7 nonzeros) the products are organised around W = P+ (dtF), which has only three nonzero
 // columns (delta, v, psi):   A'P+A = P+ + W + W' + (dtF)'W,   P+A = P+ + W,
 // so the 6x6 product P+A is never formed and P_k is accumulated onto P+ (18 + 12 + 12 temporaries instead of 36 + 21).
@@ -2143,6 +2149,47 @@ MPC_HD void ric_store_stage(const PRef& P, uint32_t bb, int k, const double* Ps,
     for (int i = 0; i < NX; ++i) pk[D::NS + i] = pv[i];
     ws_store_rows<D::NKK>(MPC_ROWS(MPC_UK(P.KK, D::NKK, k, e)), kk);
     ws_store_rows<D::NPK>(MPC_ROWS(MPC_UK(P.PK, D::NPK, k, e)), pk);
+}
+
+// The same rows as two disjoint sets of 16-byte row pairs, for the two compute waves of riccati_tile's backward sweep (each pair is
+// written whole by exactly one of them, so the order in which the two waves' stores land does not matter):
+//   ric_store_matrix  what the matrix half alone knows: the gain rows K0, K1 (pairs 0 .. NX-1 of KK) and the pairs of PK that hold only P_k
+//   ric_store_vector  everything with an entry of the vector half in it: the (kf0, kf1) pair of KK and the pairs of PK from the first one
+//                     that holds an entry of p_k -- the mixed pair (P_k[NS-1], p_k[0]) included, where NS is odd (NX = 5 and 6): the wave
+//                     that runs the vector half carries P_k as well -- to the end (NPK odd, NX = 6: the last row on its own)
+// Together they write the rows of ric_store_stage, each once.  PK_SPLIT: first row of PK that belongs to the vector set.
+template <int NX>
+struct RicSplit { static constexpr int PK_SPLIT = Dim<NX>::NS & ~1; };
+template <int NX>
+MPC_HD void ric_store_matrix_pk(const PRef& P, uint32_t bb, int k, const double* Ps) {
+    using D = Dim<NX>;
+    ws_store_rows<RicSplit<NX>::PK_SPLIT>(MPC_ROWS(MPC_UK(P.PK, D::NPK, k, e)), Ps);
+}
+template <int NX>
+MPC_HD void ric_store_vector_pk(const PRef& P, uint32_t bb, int k, const double* Ps, const double* pv) {
+    using D = Dim<NX>;
+    constexpr int S0 = RicSplit<NX>::PK_SPLIT, CNT = D::NPK - S0;
+    double pk[CNT];
+#pragma unroll
+    for (int i = S0; i < D::NS; ++i) pk[i - S0] = Ps[i];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) pk[D::NS - S0 + i] = pv[i];
+    ws_store_rows<CNT>(MPC_ROWS(MPC_UK(P.PK, D::NPK, k, S0 + e)), pk);
+}
+template <int NX>
+MPC_HD void ric_store_matrix(const PRef& P, uint32_t bb, int k, const double* Ps, const RicGain<NX>& g) {
+    using D = Dim<NX>;
+    double kk[2 * NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) { kk[j] = g.K0[j]; kk[NX + j] = g.K1[j]; }
+    ws_store_rows<2 * NX>(MPC_ROWS(MPC_UK(P.KK, D::NKK, k, e)), kk);
+    ric_store_matrix_pk<NX>(P, bb, k, Ps);
+}
+template <int NX>
+MPC_HD void ric_store_vector(const PRef& P, uint32_t bb, int k, const double* Ps, const double* pv, const RicGain<NX>& g) {
+    using D = Dim<NX>;
+    MPC_ST2(MPC_UK(P.KK, D::NKK, k, 2 * NX), g.kf0, g.kf1);
+    ric_store_vector_pk<NX>(P, bb, k, Ps, pv);
 }
 
 // both halves on one thread: consumes stage block `s`, updates (Ps, pv) IN PLACE, stores gains and cost-to-go

@@ -399,14 +399,17 @@ __global__ void __launch_bounds__(MAXT, (INIT && MAXT <= 256) ? 2 : 1) k_stage(c
 
 // ---------------------------------------------------------------------------------------------------------------
 // Riccati sweep (riccati_tile; k_riccati is the same as a kernel of its own): block-tridiagonal factor + solve.  One tile of
-// 64 instances = three wavefronts (the second loader, wave 2, only works in the forward sweep):
+// 64 instances = three wavefronts:
 //   wave 1 (loader)  streams the condensed stage blocks HBM -> LDS with asynchronous buffer->LDS DMA (1 KiB per wave
 //                    instruction, no VGPR round trip) RIC_DEPTH-1 stages ahead into a ring of RIC_DEPTH slots; its
 //                    vmcnt counter tracks nothing but those DMAs, so "stage k has landed" is an exact s_waitcnt.
 //   wave 0 (compute) one instance per lane: s_barrier -> ds_read of the stage block -> ~270 fp64 operations -> 16-byte
 //                    fire-and-forget stores of gains / cost-to-go; it never waits on HBM.
+//   wave 2           forward sweep: the second loader.  Backward sweep: a second compute wave on the same ring slots behind the same
+//                    barriers -- it repeats wave 0's matrix recursion and adds the vector half (p_k, kff), which nothing in the chain
+//                    waits for; wave 0 stores the gain rows and P_k, wave 2 the row pairs with an entry of p_k or kff.
 // The stage block of stage k is ONE contiguous chunk of the tile-major workspace (whole row pairs, 1 KiB each), so the LDS
-// image is [row pair][lane][2] and a lane reads both rows of a pair with one conflict-free ds_read_b128.  Arithmetic: riccati_backward_step / riccati_forward_step of
+// image is [row pair][lane][2] and a lane reads both rows of a pair with one conflict-free ds_read_b128.  Arithmetic: ric_matrix_step / ric_vector_step / riccati_forward_step of
 // mpc_stage_math.h (shared with the CPU emulation harness).  Inertia correction: if some lane finds an indefinite
 // 2x2 block the wave repeats the sweep with delta_w added for those lanes (flag through LDS keeps the loader in step).
 // ---------------------------------------------------------------------------------------------------------------
@@ -513,13 +516,13 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
     // ================================================================ backward sweep(s)
     double delta = 0.0, delta_last = 0.0, hux0 = 0.0, hux1 = 0.0;
     bool need = false, failed = false;
-    if (wave == 0) {
+    if (wave == 0 || wave == 2) {        // the two compute waves of the backward sweep: the same inputs, hence the same decisions
         need = active;
         if (active) { delta_last = MPC_U(P.SC, (uint32_t)SC_DLAST); hux0 = MPC_U(P.SC, (uint32_t)SC_HUX0); hux1 = MPC_U(P.SC, (uint32_t)SC_HUX1); }
     }
     for (;;) {
-        if (wave >= 2) {
-            for (int t = 0; t <= N; ++t) lds_barrier();             // second loader: idle in the backward sweep (a fourth wave -- k_pipeline's helping workers -- in both)
+        if (wave >= 3) {
+            for (int t = 0; t <= N; ++t) lds_barrier();             // a fourth wave (k_pipeline's helping workers): idle in both sweeps
         } else if (wave == 1) {
             // ---------------- loader: stages N, N-1, ... ; stage N-t lives in slot t % RIC_DEPTH
             for (int j = 0; j < RIC_DEPTH - 1 && j <= N; ++j) dma(blk_base + (uint32_t)(N - j) * BLK_BYTES, (uint32_t)j * SLOT, BLK_CHUNKS);
@@ -531,21 +534,27 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
                 if (kn >= 0) dma(blk_base + (uint32_t)kn * BLK_BYTES, (uint32_t)((t + RIC_DEPTH - 1) % RIC_DEPTH) * SLOT, BLK_CHUNKS);
             }
         } else {
-            // ---------------- compute
+            // ---------------- compute: wave 0 (MATRIX) and wave 2 (the second loader of the forward sweep, otherwise idle here: VECTOR)
+            // Both walk the matrix recursion P+ -> P_k from the same ring slot behind the same barrier -- the same instructions on the
+            // same data, so they hold the same P_k, the same verdicts `ok` and the same delta_w without exchanging a word.  Wave 0 stores
+            // what the next stage's chain produces anyway (gain rows, P_k); wave 2 adds the half nothing waits for (p_k, kff) and
+            // stores the row pairs with an entry of it (ric_store_matrix / ric_store_vector: no pair is written by both).
             bool ok = need;
             // symmetrised G'K for the instances that ever needed an inertia correction (mpc_stage_math.h, ric_matrix_step); a
             // wavefront without any runs the sweep instantiated without the term (decided per sweep, so that the loop of the
             // common case is the loop it always was)
             const bool sym = delta != 0.0 || delta_last != 0.0;
-            auto sweep = [&](auto sym_tag, auto ne_tag) {
+            auto sweep = [&](auto sym_tag, auto ne_tag, auto vec_tag) {
                 constexpr bool SYM = decltype(sym_tag)::value;
                 constexpr int NE = decltype(ne_tag)::value;
+                constexpr bool VEC = decltype(vec_tag)::value;
+                const bool lead = !VEC && threadIdx.x == 0 && stamp;
                 double Ps[NS], pv[NX];
                 for (int t = 0; t <= N; ++t) {
                     const int k = N - t;
-                    if (t == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_B15_WAIT, threadIdx.x == 0 && stamp);
+                    if (t == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_B15_WAIT, lead);
                     lds_barrier();
-                    if (t == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_B15_GO, threadIdx.x == 0 && stamp);
+                    if (t == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_B15_GO, lead);
                     RicStage<NX> s;
                     read_stage((uint32_t)(t % RIC_DEPTH) * SLOT, s);
                     if (t == 0) {
@@ -554,33 +563,49 @@ __device__ __forceinline__ unsigned long long riccati_tile(const PRef& P, const 
 #pragma unroll
                         for (int i = 0; i < NX; ++i) { Ps[D::sidx(i, i)] += delta; pv[i] = s.gx[i]; }
                         if (ok) {
-                            double pk[D::NPK];
-#pragma unroll
-                            for (int i = 0; i < NS; ++i) pk[i] = Ps[i];
-#pragma unroll
-                            for (int i = 0; i < NX; ++i) pk[NS + i] = pv[i];
-                            ws_store_rows<D::NPK>(MPC_ROWS(MPC_UK(P.PK, D::NPK, N, e)), pk);
+                            if (VEC) ric_store_vector_pk<NX>(P, bb, N, Ps, pv);
+                            else ric_store_matrix_pk<NX>(P, bb, N, Ps);
                         }
                     } else if (ok) {
-                        ok = riccati_backward_step<NX, NE, SYM>(P, bb, k, s, delta, hux0, hux1, Ps, pv, SYM && sym);
+                        RicGain<NX> g;
+                        if (VEC) {
+                            double Pn[NS];
+#pragma unroll
+                            for (int i = 0; i < NS; ++i) Pn[i] = Ps[i];
+                            ok = ric_matrix_step<NX, NE, SYM>(P, k, s, delta, hux0, hux1, Ps, g, SYM && sym);
+                            if (ok) {
+                                ric_vector_step<NX, NE, SYM>(P, s, Pn, g, pv);
+                                ric_store_vector<NX>(P, bb, k, Ps, pv, g);
+                            }
+                        } else {
+                            ok = ric_matrix_step<NX, NE, SYM>(P, k, s, delta, hux0, hux1, Ps, g, SYM && sym);
+                            if (ok) ric_store_matrix<NX>(P, bb, k, Ps, g);
+                        }
                     }
-                    if (t == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_B15_END, threadIdx.x == 0 && stamp);
+                    if (t == 15) MPC_STAMP(P.DBG, blockIdx.x, RT_B15_END, lead);
                 }
             };
             // (six states with a costless, unbounded progress state -- flagged by the host -- and no inertia correction anywhere in the wavefront:
             //  the recursion runs on five states, row and column of the sixth stay the zeros they are; same bits, a quarter fewer instructions)
-            if (__any(sym ? 1 : 0)) sweep(std::true_type{}, std::integral_constant<int, NX>{});
-            else if (NX == 6 && P.dec_s) sweep(std::false_type{}, std::integral_constant<int, (NX == 6 ? 5 : NX)>{});
-            else sweep(std::false_type{}, std::integral_constant<int, NX>{});
+            auto sweep_as = [&](auto vec_tag) {
+                if (__any(sym ? 1 : 0)) sweep(std::true_type{}, std::integral_constant<int, NX>{}, vec_tag);
+                else if (NX == 6 && P.dec_s) sweep(std::false_type{}, std::integral_constant<int, (NX == 6 ? 5 : NX)>{}, vec_tag);
+                else sweep(std::false_type{}, std::integral_constant<int, NX>{}, vec_tag);
+            };
+            if (wave == 0) sweep_as(std::false_type{});
+            else sweep_as(std::true_type{});
             if (need && ok) need = false;
             else if (need) {
                 if (delta == 0.0) delta = (delta_last == 0.0) ? DW_0 : fmax(DW_MIN, KW_MINUS * delta_last);
                 else delta *= (delta_last == 0.0) ? KW_PLUS_BAR : KW_PLUS;
                 if (delta > DW_MAX) { need = false; failed = true; }
             }
-            const int again = __any(need ? 1 : 0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                               // gains / cost-to-go are out
-            if (lane == 0) *flag = again;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                               // this wave's share of gains / cost-to-go is out
+            // (whether the sweep is repeated is wave 0's word alone: every wave, wave 2 included, takes it from the flag below)
+            if (wave == 0) {
+                const int again = __any(need ? 1 : 0);
+                if (lane == 0) *flag = again;
+            }
         }
         lds_barrier();
         const int again = lds_uniform(*flag);
