@@ -99,16 +99,22 @@ const char* mpc_last_error(const mpc_handle* h);   /* h may be NULL: error of th
 /* lbx/ubx: n_w entries (optimizer.py:470-491), +-inf = absent.  lbg/ubg: n_g = 1 + nx(N+1) + 9(N+1) entries
  * (optimizer.py:421-469): row 0 friction [lo, hi]; nx(N+1) equality rows (lbg == ubg); 9(N+1) obstacle rows,
  * all with the same [lo, hi].  Anything else -> MPC_ERR_BOUNDS.  A friction lower bound <= 0 is implied by the
- * absolute value in the row and gets no barrier.  Passing NULL for all four installs the reference defaults. */
+ * absolute value in the row and gets no barrier.  Passing NULL for all four installs the reference defaults.
+ * Like mpc_set_weights and like a solve, it ends the life of the sensitivity snapshot (the same bounds again included):
+ * mpc_sens_adjoint / mpc_sens_obst / mpc_sens_weights / mpc_sens_bounds after it -> MPC_ERR_STATE (their factor reads
+ * the bounds, which must be those of the solve).
+ * mpc_get_bounds: the bounds that are installed, as they were given (the defaults of an all-NULL call included), in the
+ * same layout; any argument may be NULL.  Before the first mpc_set_bounds -> MPC_ERR_STATE.                         */
 int mpc_set_bounds(mpc_handle* h, const double* lbx, const double* ubx, const double* lbg, const double* ubg);
+int mpc_get_bounds(const mpc_handle* h, double* lbx, double* ubx, double* lbg, double* ubg);
 
 /* Replaces the cost weights of a live handle: Q [5] -> desc.Q[0..4], R [2] -> desc.R[0..1]; NULL keeps the current ones.  Q[5] (the progress
  * state's weight), P, the bounds and every option stay.  A non-finite value, a Q[i] < 0 or an R[j] <= 0 (R > 0 keeps the KKT matrix's input
  * blocks positive definite) -> MPC_ERR_INVALID, and the handle is as it was.  Host bookkeeping only: no device work and no synchronisation.
  * Every launch carries its weights by value, so work already enqueued keeps the weights it was enqueued with; every call from the next one on
  * -- NLP solves, closed loops and the FORCES-mode entries, which read the same descriptor -- sees the new ones.  Like a solve, it ends the
- * life of the sensitivity snapshot: mpc_sens_adjoint / mpc_sens_obst / mpc_sens_weights after it -> MPC_ERR_STATE (their factor reads the
- * weights, which must be those of the solve).                                                                                               */
+ * life of the sensitivity snapshot: mpc_sens_adjoint / mpc_sens_obst / mpc_sens_weights / mpc_sens_bounds after it -> MPC_ERR_STATE (their
+ * factor reads the weights, which must be those of the solve).  mpc_set_bounds does the same.                                               */
 int mpc_set_weights(mpc_handle* h, const double* Q, const double* R);
 
 /* Host-buffer entry point.  x0, p, x_out: [B, n_w] row-major.  obst: [B, 6] per-instance obstacle circle
@@ -167,7 +173,8 @@ int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const d
  * bit for bit those of mpc_solve_batch[_dev]_ex; with lam_p NULL and n_dir 0 nothing more is written.  Rows with status != 1 get NaN in lam_p
  * and dw, and so do rows whose final KKT matrix has the wrong inertia (a Riccati pivot <= 0) or that sit on the friction kink (lam_g[0] NaN).
  * fixed_iters > 0 -> MPC_ERR_INVALID.  The derivative with respect to the obstacle centres: mpc_sens_obst below; with respect to the cost
- * weights: mpc_sens_weights below.  Derivatives with respect to the bounds, the circle radius and x0 are not provided.
+ * weights: mpc_sens_weights below; with respect to the bounds and the circle radius: mpc_sens_bounds below.  A derivative with respect to x0
+ * (the initial guess) is not provided: at an isolated optimum it is zero.
  * The _dev form synchronises `stream`.                                                                                                     */
 int mpc_solve_batch_sens(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out,
                          int32_t* status, int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x,
@@ -210,6 +217,24 @@ int mpc_sens_weights(mpc_handle* h, int32_t B, const double* p, int32_t n_dir, c
                      double* lam_wt);
 int mpc_sens_weights_dev(mpc_handle* h, int32_t B, const double* d_p, int32_t n_dir, const double* d_dwt, double* d_dw, const double* d_seed_w,
                          double* d_grad_wt, double* d_lam_wt, void* stream);
+/* The derivative of the optimum with respect to the bounds and the circle radius, on the snapshot of the last mpc_solve_batch_sens[_dev] of
+ * this handle -- a solve with lam_p NULL and n_dir 0 is enough to take it.  The bound vector is bv = [lbx (n_w) | ubx (n_w) | fl, fu, ol, ou],
+ * n_b = 2 n_w + 4: the arrays of mpc_set_bounds, then lbg[0], ubg[0] of the friction row and the pair [lo, hi] shared by the 9 (N + 1) circle
+ * rows -- ol is the radius sum.  The equality rows have no entry.  Any part may be left out:
+ *   n_dir > 0 forward directions dbv [B, n_dir, n_b] -> dw [B, n_dir, n_w] = (dw/dbv) dbv;
+ *   one adjoint seed seed_w [B, n_w] -> grad_bv [B, n_b] = (dw/dbv)' seed_w (both or neither);
+ *   lam_bv [B, n_b] = d f* / d bv, the derivative of the optimal objective (envelope theorem), in CasADi's sign and unscaled: entries of lbx, fl,
+ *   ol are >= 0, entries of ubx, fu, ou <= 0, and lam_bv[lbx_i] + lam_bv[ubx_i] = -lam_x[i], lam_bv[fl] + lam_bv[fu] = -lam_g[0],
+ *   lam_bv[ol] + lam_bv[ou] = -(sum of lam_g over the circle rows).
+ * The bounds are shared by the batch; the rows of grad_bv / lam_bv are per instance, to be summed by the caller.  An entry whose bound is absent
+ * (+-inf), or that the solve did not impose (fl under the default friction_lb = nlp; the caller's bound of a_0 on a side where the presolved
+ * friction row is tighter: that side moves with fu), has derivative 0 in all three outputs, and its dbv entry is not read.  NaN rows,
+ * MPC_ERR_STATE (also after mpc_set_bounds / mpc_set_weights) and the stream rule of the _dev form are those of mpc_sens_adjoint; n_dir < 0,
+ * n_dir > 0 without dbv and dw, or only one of seed_w / grad_bv -> MPC_ERR_INVALID; a call that asks for nothing returns MPC_OK at once.  It
+ * shares the factor storage of mpc_sens_adjoint.                                                                                            */
+int mpc_sens_bounds(mpc_handle* h, int32_t B, int32_t n_dir, const double* dbv, double* dw, const double* seed_w, double* grad_bv, double* lam_bv);
+int mpc_sens_bounds_dev(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dbv, double* d_dw, const double* d_seed_w, double* d_grad_bv,
+                        double* d_lam_bv, void* stream);
 
 /* Batched plant step on the device path: x_next = x + dt f(x,u) (integrator 0 = forward Euler,
  * optimizer.py:649-650) or one RK4 step (integrator 1, optimizer.py:97-98).  x: [B, nx], u: [B, 2] host. */

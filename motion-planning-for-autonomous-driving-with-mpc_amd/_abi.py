@@ -54,6 +54,7 @@ PROTOTYPES = {
     "mpc_last_error": [_vp],
     "mpc_abi_version": [],
     "mpc_set_bounds": [_vp, _dp, _dp, _dp, _dp],
+    "mpc_get_bounds": [_vp, _dp, _dp, _dp, _dp],
     "mpc_set_weights": [_vp, _dp, _dp],
     "mpc_set_profiling": [_vp, _i32],
     "mpc_set_option": [_vp, C.c_char_p, C.c_char_p],
@@ -79,6 +80,8 @@ PROTOTYPES = {
     "mpc_sens_obst_dev": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "mpc_sens_weights": [_vp, _i32, _dp, _i32, _dp, _dp, _dp, _dp, _dp],
     "mpc_sens_weights_dev": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mpc_sens_bounds": [_vp, _i32, _i32, _dp, _dp, _dp, _dp, _dp],
+    "mpc_sens_bounds_dev": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "mpc_plant_step": [_vp, _i32, _i32, _dp, _dp, _dp],
     "mpc_plant_step_dev": [_vp, _i32, _i32] + [_vp] * 4,
     "mpc_closed_loop_batch": [_vp, _i32, _i32, _i32] + [_dp] * 6 + [_ip],

@@ -1,6 +1,6 @@
-"""The batched solve as a differentiable layer: x*(p, obst, weights) with gradients to p, to the obstacle circle centres and to the cost
-weights through the parametric sensitivities of the optimum (include/mpcgpu.h: mpc_solve_batch_sens_dev, mpc_sens_adjoint_dev,
-mpc_sens_obst_dev, mpc_sens_weights_dev).
+"""The batched solve as a differentiable layer: x*(p, obst, weights, bounds) with gradients to p, to the obstacle circle centres, to the cost
+weights and to the bounds through the parametric sensitivities of the optimum (include/mpcgpu.h: mpc_solve_batch_sens_dev,
+mpc_sens_adjoint_dev, mpc_sens_obst_dev, mpc_sens_weights_dev, mpc_sens_bounds_dev).
 
     from <package>.autograd import MPCSolve
     x, status = MPCSolve.apply(solver, x0, p)           # x0, p: float64 device tensors [B, n_w]; torch's current stream
@@ -12,7 +12,10 @@ mpc_sens_obst_dev, mpc_sens_weights_dev).
     wt = torch.tensor(solver.weights, requires_grad=True)   # [7] float64 = [Q_0 .. Q_4 | R_0, R_1], on any device
     x, status = mpc_solve(solver, x0, p, weights=wt)     # sets the solver's weights, then solves; wt.grad = sum over the rows of (dx*/dwt)' dloss/dx
 
-Gradients flow to p and, when they are given, to obst and weights (x0 is the initial guess: at an isolated optimum x* does not depend on it).  Without
+    bv = torch.tensor(solver.bounds_vector(), requires_grad=True)   # [n_b] float64 = [lbx | ubx | fl, fu, ol, ou], on any device
+    x, status = mpc_solve(solver, x0, p, bounds=bv)      # sets the solver's bounds, then solves; bv.grad = sum over the rows of (dx*/dbv)' dloss/dx
+
+Gradients flow to p and, when they are given, to obst, weights and bounds (x0 is the initial guess: at an isolated optimum x* does not depend on it).  Without
 obst the obstacle centres are the solver's own (its descriptor's) and the layer is what it was before obst existed, bit for bit.  Rows whose
 status is not 1 get NaN gradients; failed="zero" masks them to 0 instead.  The backward pass differentiates the snapshot the forward solve
 left in the solver's handle: any later solve on the same solver makes it raise.
@@ -21,6 +24,11 @@ weights [7] is shared by the batch, as the handle's weights are: the forward pas
 weights afterwards -- and for a device tensor that is one copy of seven doubles to the host, hence a synchronisation of the device.  Its
 gradient is the sum over the rows of grad_wt [B, 7]: with failed="zero" rows whose status is not 1 contribute 0, with failed="nan" a single
 such row makes the whole sum NaN.  With weights=None the layer does not touch the solver's weights and is what it was before, bit for bit.
+
+bounds [n_b] (BatchedMPCSolver.bounds_vector: the circle radius is its entry ol) is shared by the batch in the same way: the forward pass calls
+solver.set_bounds(*solver.unpack_bounds(bounds)) -- the solver KEEPS these bounds afterwards -- which for a device tensor is one copy of n_b
+doubles to the host, hence a synchronisation.  Its gradient is the sum over the rows of grad_bv [B, n_b] under the same rule for failed rows;
+entries of absent bounds (+-inf) get 0.  With bounds=None the layer does not touch the solver's bounds and is what it was before, bit for bit.
 """
 from __future__ import annotations
 
@@ -40,7 +48,7 @@ def obstacle_centres(pose: torch.Tensor, obst_offset: float) -> torch.Tensor:
 class MPCSolve(torch.autograd.Function):
     @staticmethod
     def forward(ctx, solver: BatchedMPCSolver, x0: torch.Tensor, p: torch.Tensor, failed: str = "nan", obst: torch.Tensor | None = None,
-                weights: torch.Tensor | None = None):
+                weights: torch.Tensor | None = None, bounds: torch.Tensor | None = None):
         if failed not in ("nan", "zero"):
             raise ValueError('failed must be "nan" or "zero"')
         for name, t in (("x0", x0), ("p", p)):
@@ -56,6 +64,10 @@ class MPCSolve(torch.autograd.Function):
                 raise ValueError("weights must be a float64 tensor [7] = [Q_0 .. Q_4 | R_0, R_1]")
             wt = weights.detach().cpu().numpy()                 # (a device tensor: seven doubles to the host, a synchronisation)
             solver.set_weights(wt[:5], wt[5:])
+        if bounds is not None:
+            if bounds.dtype != torch.float64 or tuple(bounds.shape) != (solver.n_b,):
+                raise ValueError(f"bounds must be a float64 tensor [{solver.n_b}] = [lbx | ubx | fl, fu, ol, ou]")
+            solver.set_bounds(*solver.unpack_bounds(bounds.detach().cpu().numpy()))     # (a device tensor: a copy to the host, a synchronisation)
         x0c, pc = x0.detach().contiguous(), p.detach().contiguous()
         oc = None if obst is None else obst.detach().contiguous()
         x = torch.empty_like(x0c)
@@ -69,6 +81,9 @@ class MPCSolve(torch.autograd.Function):
         else:
             ctx.save_for_backward(status, pc)                   # (the weights' right-hand side reads X_ref: the p rows of the solve)
             ctx.wt_device = weights.device
+        ctx.has_bv = bounds is not None
+        if bounds is not None:
+            ctx.bv_device = bounds.device
         ctx.mark_non_differentiable(status)
         return x, status
 
@@ -80,8 +95,8 @@ class MPCSolve(torch.autograd.Function):
         status = ctx.saved_tensors[0]
         seed = grad_x.detach().to(torch.float64).contiguous()
         stream = torch.cuda.current_stream(seed.device).cuda_stream
-        grad_p = grad_obst = grad_wt = None
-        if not (ctx.has_obst or ctx.has_wt) or ctx.needs_input_grad[2]:
+        grad_p = grad_obst = grad_wt = grad_bv = None
+        if not (ctx.has_obst or ctx.has_wt or ctx.has_bv) or ctx.needs_input_grad[2]:
             grad_p = torch.empty_like(seed)
             solver.sens_adjoint_device(ctx.B, seed.data_ptr(), grad_p.data_ptr(), stream=stream)      # MPC_ERR_STATE after any other solve
             if ctx.failed == "zero":
@@ -97,12 +112,19 @@ class MPCSolve(torch.autograd.Function):
             if ctx.failed == "zero":
                 rows = torch.where((status == 1)[:, None], rows, torch.zeros_like(rows))
             grad_wt = rows.sum(dim=0).to(ctx.wt_device)
-        return None, None, grad_p, None, grad_obst, grad_wt
+        if ctx.has_bv and ctx.needs_input_grad[6]:
+            rows = torch.empty((ctx.B, solver.n_b), dtype=torch.float64, device=seed.device)
+            solver.sens_bounds_device(ctx.B, d_seed_w=seed.data_ptr(), d_grad_bv=rows.data_ptr(), stream=stream)
+            if ctx.failed == "zero":
+                rows = torch.where((status == 1)[:, None], rows, torch.zeros_like(rows))
+            grad_bv = rows.sum(dim=0).to(ctx.bv_device)
+        return None, None, grad_p, None, grad_obst, grad_wt, grad_bv
 
 
 def mpc_solve(solver: BatchedMPCSolver, x0: torch.Tensor, p: torch.Tensor, failed: str = "nan", obst: torch.Tensor | None = None,
-              weights: torch.Tensor | None = None):
+              weights: torch.Tensor | None = None, bounds: torch.Tensor | None = None):
     """functional form of MPCSolve.apply: (x [B, n_w], status [B] int32).  obst [B, 6]: every instance's own obstacle circle centres (see
     obstacle_centres); weights [7] float64 on any device: the cost weights [Q_0 .. Q_4 | R_0, R_1] the solver is set to before it solves;
-    both may require grad"""
-    return MPCSolve.apply(solver, x0, p, failed, obst, weights)
+    bounds [n_b] float64 on any device: the bound vector (BatchedMPCSolver.bounds_vector) the solver is set to before it solves; all three may
+    require grad"""
+    return MPCSolve.apply(solver, x0, p, failed, obst, weights, bounds)

@@ -1,5 +1,5 @@
-// mpc_sens.h -- parametric sensitivities of a converged solve (mpc_solve_batch_sens, mpc_sens_adjoint, mpc_sens_obst, mpc_sens_weights; DESIGN.md
-// section 13).
+// mpc_sens.h -- parametric sensitivities of a converged solve (mpc_solve_batch_sens, mpc_sens_adjoint, mpc_sens_obst, mpc_sens_weights,
+// mpc_sens_bounds).
 //
 // The derivative of the returned optimum w*(p) with respect to the parameter row p = [U_ref | X_ref] is sIPOPT's step: the KKT matrix of
 // the final barrier iterate, with no inertia correction, solved against -d(KKT residual)/dp dp.  After the bound multipliers and the
@@ -14,10 +14,11 @@
 //   a presolved friction row:   the bounds -+ sqrt(fu - c(delta_0, v_0)) of a_0 (prestart_a0_of), with (delta_0, v_0) = xref_0
 //                               ->  d ru_0[a] = sum over the sides the row set of z / gap * d bound / d (delta_0, v_0)
 // The objective scaling df multiplies the Hessian, the gradient and the multipliers alike and drops out of the primal step.
-// The obstacle centres and the cost weights are further right-hand sides against the same factor: their sections below state them.
+// The obstacle centres, the cost weights and the bounds are further right-hand sides against the same factor: their sections below state them.
 //
-// Two layers, plain pointers only, so that the same code runs in the kernels (k_sens_gather, k_sens_factor_solve, k_sens_obst, k_sens_weights)
-// and in the CPU harnesses of the tests (tests/sensx/sensx.cpp, tests/sensobstx/sensobstx.cpp, tests/sensweightx/sensweightx.cpp):
+// Two layers, plain pointers only, so that the same code runs in the kernels (k_sens_gather, k_sens_factor_solve, k_sens_obst, k_sens_weights,
+// k_sens_bounds) and in the CPU harnesses of the tests (tests/sensx/sensx.cpp, tests/sensobstx/sensobstx.cpp, tests/sensweightx/sensweightx.cpp,
+// tests/sensboundx/sensboundx.cpp):
 //   snapshot  instance-major copy of the final iterate [(N + 1) stages of SS | a tail of T_COUNT], written by sens_gather_stage
 //   factor    per stage FS doubles, [stage][entry][Bs] (entry e of stage k of instance b at (k FS + e) Bs + b: lanes of a wave coalesce)
 #pragma once
@@ -803,6 +804,214 @@ MPC_HD void sens_lam_weights(const Params& P, const double* snap, const double* 
     }
 #pragma unroll
     for (int i = 0; i < SENS_NWT; ++i) lwt[i] = acc[i];
+}
+
+// ---- the bounds and the circle radius (mpc_sens_bounds, k_sens_bounds) --------------------------------------------------------------------
+// The same step against the same factor with a fourth right-hand side.  The bound vector is bv = [lbx (n_w) | ubx (n_w) | fl, fu, ol, ou]: the
+// arrays of mpc_set_bounds, lbg[0] / ubg[0] of the friction row and the pair shared by the circle rows (ol is the radius sum); n_b = 2 n_w + 4.
+// With SL = z_L / gap_L and SU = z_U / gap_U of a side (what sens_stage_kkt adds to the diagonal; 0 where the side has no bound) a direction
+// dbv enters
+//   a variable bound of entry i of stage k:  z_L = mu / (x - lb), so d z_L = -SL (dx - dlb): the stationarity row gets  SL dlb + SU dub
+//   a_0 (stage 0, input 1): the bounds in force are the snapshot tail's.  A side the presolved friction row set (tighter than the caller's, the
+//     test of sens_factor: lb = -amax, ub = amax, amax = sqrt(fu - c)) moves with fu, d lb = dfu / (2 lb), d ub = dfu / (2 ub), and the
+//     caller's entry of that side has no effect
+//   a circle row:  J dx - t - ds = 0 with t = (SL dol + SU dou) / (SL + SU), the same for every stage and circle: sens_solve_circ's shift (the
+//     sides' shares SL / (SL + SU) are formed from the snapshot: the stage data keeps only their sum).  ou = inf: t = dol
+//   the friction row where it is kept as a row:  with tf = SL dfl + SU dfu the rows of (a_0, delta_0, v_0) get g tf, g the row's gradient
+// An entry whose side has no bound, or whose bound the solve did not impose (fl under friction_lb = nlp; the caller's side of a_0 behind a
+// presolved one), has SL = SU = 0: its derivative is 0 and its dbv entry is not read.  The entries are the caller's bounds; the solve relaxes
+// them by BOUND_RELAX (1e-8 relative), a factor 1 + 1e-8 at most on a derivative, which is left out.
+// An active side carries S ~ 1e10 in the right-hand side and in the matrix alike, as an active circle row does for the centres: the solve is
+// sens_solve_circ's with SENS_BV_REFINE step of refinement.  Measured with tests/sensboundx on the twelve collision-avoidance rows the tests
+// compare (N = 30, nx = 5; every row has active steering-rate bounds and circle rows), the worst |seed' dw - grad_bv' dbv| /
+// max(1, sum |seed| max |dw|) over ten directions: one step 1.1e-13, two 2.8e-17, three 2.9e-17; the bound asked of the identity is 1e-10, and
+// dw against the active-set reference is the same to every printed digit for one, two and three steps.  (The kernel with one step, over all 70
+// rows of that batch: 2.0e-12.)
+constexpr int SENS_BV_REFINE = 1;
+constexpr int SENS_BV_FL = 0, SENS_BV_FU = 1, SENS_BV_OL = 2, SENS_BV_OU = 3, SENS_BV_ROWS = 4;      // the four row bounds behind lbx | ubx
+
+// z / gap of the two sides of variable i of stage k (0: no bound on that side), and for a side of a_0 the presolved friction row set
+// d bound / d fu (cl, cu; 0: the side is the caller's own)
+template <int NX>
+MPC_HD void sens_var_sides(const Params& P, const double* tail, const double* sn, const int k, const int i, double& SL, double& SU, double& cl,
+                           double& cu) {
+    using S = Sens<NX>;
+    constexpr int NZ = NX + 2;
+    double lb = P.LB[k * NZ + i], ub = P.UB[k * NZ + i];
+    cl = cu = 0.0;
+    if (k == 0 && i == 1) {
+        const double a0lb = tail[S::T_A0LB], a0ub = tail[S::T_A0UB];
+        if (has_lo(a0lb) && a0lb > lb) cl = 1.0 / (2.0 * a0lb);
+        if (has_hi(a0ub) && a0ub < ub) cu = 1.0 / (2.0 * a0ub);
+        lb = a0lb; ub = a0ub;
+    }
+    const double z = sn[S::Z + i];
+    SL = has_lo(lb) ? sn[S::ZL + i] / (z - lb) : 0.0;
+    SU = has_hi(ub) ? sn[S::ZU + i] / (ub - z) : 0.0;
+}
+// the shares SL / (SL + SU), SU / (SL + SU) of the two sides of circle row j of a stage (0: no bound on that side)
+template <int NX>
+MPC_HD void sens_circ_shares(const Params& P, const double* sn, const int j, double& wl, double& wu) {
+    using S = Sens<NX>;
+    const double s = sn[S::SO + j];
+    const double SL = P.has_ol ? sn[S::ZLO + j] / (s - P.ol) : 0.0, SU = P.has_ou ? sn[S::ZUO + j] / (P.ou - s) : 0.0;
+    const double tot = SL + SU;
+    wl = tot > 0.0 ? SL / tot : 0.0;
+    wu = tot > 0.0 ? SU / tot : 0.0;
+}
+// the kept friction row: z / gap of its two sides and its gradient g wrt (a_0, delta_0, v_0); false where the row is presolved
+template <int NX>
+MPC_HD bool sens_fric_sides(const Params& P, const double* tail, const double* snap, double& SL, double& SU, double* g) {
+    using S = Sens<NX>;
+    if (tail[S::T_FROW] == 0.0) return false;
+    const double* z0 = snap + S::Z;
+    double h[4];
+    friction_eval(P, z0[1], z0[2 + 2], z0[2 + 3], g, h, true);
+    const double s = tail[S::T_SF];
+    SL = P.has_fl ? tail[S::T_ZLF] / (s - P.fl) : 0.0;
+    SU = P.has_fu ? tail[S::T_ZUF] / (P.fu - s) : 0.0;
+    return true;
+}
+
+// forward direction: dbv [n_b] -> dw [n_w].  D: the stage data of sens_obst_setup; nrow, om, work: scratch of sens_solve_circ
+template <int NX>
+MPC_HD void sens_forward_bounds(const Params& P, double* F, const size_t Bs, const int b, const double* D, const double* snap, const double* dbv,
+                                double* dw, const SensVec nrow, const SensVec om, const SensVec work) {
+    using S = Sens<NX>;
+    constexpr int NZ = NX + 2;
+    const int N = P.N, X0 = 2 * N, nw = X0 + NX * (N + 1);
+    const double* tail = snap + (size_t)(N + 1) * S::SS;
+    const double* dr = dbv + 2 * (size_t)nw;
+    sens_solve_circ<NX, SENS_BV_REFINE>(P, F, Bs, b, D,
+                        [&](int k, double* gx, double* gu) {
+                            const double* sn = snap + (size_t)k * S::SS;
+                            gu[0] = gu[1] = 0.0;
+#pragma unroll
+                            for (int i = 0; i < NZ; ++i) {
+                                if (i < 2 && k == N) continue;
+                                const int q = i < 2 ? 2 * k + i : X0 + NX * k + (i - 2);
+                                double SL, SU, cl, cu, g = 0.0;
+                                sens_var_sides<NX>(P, tail, sn, k, i, SL, SU, cl, cu);
+                                if (SL != 0.0) g += SL * (cl != 0.0 ? cl * dr[SENS_BV_FU] : dbv[q]);
+                                if (SU != 0.0) g += SU * (cu != 0.0 ? cu * dr[SENS_BV_FU] : dbv[nw + q]);
+                                if (i < 2) gu[i] = g;
+                                else gx[i - 2] = g;
+                            }
+                            double SL, SU, g[3];
+                            if (k == 0 && sens_fric_sides<NX>(P, tail, snap, SL, SU, g)) {
+                                double tf = 0.0;
+                                if (SL != 0.0) tf += SL * dr[SENS_BV_FL];
+                                if (SU != 0.0) tf += SU * dr[SENS_BV_FU];
+                                gu[1] += g[0] * tf; gx[2] += g[1] * tf; gx[3] += g[2] * tf;
+                            }
+                        },
+                        [&](int k, int j, const SensCirc&, double*) {
+                            double wl, wu, t = 0.0;
+                            sens_circ_shares<NX>(P, snap + (size_t)k * S::SS, j, wl, wu);
+                            if (wl != 0.0) t += wl * dr[SENS_BV_OL];
+                            if (wu != 0.0) t += wu * dr[SENS_BV_OU];
+                            return t;
+                        },
+                        [&](int, int, const SensCirc&, const double*, double) {}, SensVec{dw, 1}, nrow, om, work);
+}
+
+// reverse: seed_w [n_w] -> gbv [n_b] = (dw/dbv)' seed_w.  The solve of the seed (every shift t = 0) gives (y_u,k, y_x,k) in sol and the circle
+// multipliers n_kj; the transposed right-hand side of the forward direction applied to them: an entry of lbx / ubx gets S y of its variable,
+// fu the presolved sides of a_0 through d bound / d fu, fl / fu of a kept row S g' (y_a0, y_delta0, y_v0), ol / ou the sum of their shares of n_kj
+template <int NX>
+MPC_HD void sens_adjoint_bounds(const Params& P, double* F, const size_t Bs, const int b, const double* D, const double* snap, const double* seed,
+                                double* gbv, const SensVec sol, const SensVec nrow, const SensVec om, const SensVec work) {
+    using S = Sens<NX>;
+    constexpr int NZ = NX + 2;
+    const int N = P.N, X0 = 2 * N, nw = X0 + NX * (N + 1);
+    const double* tail = snap + (size_t)(N + 1) * S::SS;
+    double acc[SENS_BV_ROWS] = {0.0, 0.0, 0.0, 0.0};
+    sens_solve_circ<NX, SENS_BV_REFINE>(P, F, Bs, b, D,
+                        [&](int k, double* gx, double* gu) {
+#pragma unroll
+                            for (int i = 0; i < NX; ++i) gx[i] = seed[X0 + NX * k + i];
+                            gu[0] = k < N ? seed[2 * k] : 0.0;
+                            gu[1] = k < N ? seed[2 * k + 1] : 0.0;
+                        },
+                        [&](int, int, const SensCirc&, double*) { return 0.0; },
+                        [&](int k, int j, const SensCirc&, const double*, double n) {
+                            double wl, wu;
+                            sens_circ_shares<NX>(P, snap + (size_t)k * S::SS, j, wl, wu);
+                            acc[SENS_BV_OL] += wl * n;
+                            acc[SENS_BV_OU] += wu * n;
+                        },
+                        sol, nrow, om, work);
+    for (int k = 0; k <= N; ++k) {
+        const double* sn = snap + (size_t)k * S::SS;
+#pragma unroll
+        for (int i = 0; i < NZ; ++i) {
+            if (i < 2 && k == N) continue;
+            const int q = i < 2 ? 2 * k + i : X0 + NX * k + (i - 2);
+            double SL, SU, cl, cu;
+            sens_var_sides<NX>(P, tail, sn, k, i, SL, SU, cl, cu);
+            const double y = sol[q];
+            if (cl != 0.0) { acc[SENS_BV_FU] += SL * cl * y; SL = 0.0; }
+            if (cu != 0.0) { acc[SENS_BV_FU] += SU * cu * y; SU = 0.0; }
+            gbv[q] = SL * y;
+            gbv[nw + q] = SU * y;
+        }
+    }
+    double SL, SU, g[3];
+    if (sens_fric_sides<NX>(P, tail, snap, SL, SU, g)) {
+        const double gy = g[0] * sol[1] + g[1] * sol[X0 + 2] + g[2] * sol[X0 + 3];
+        acc[SENS_BV_FL] += SL * gy;
+        acc[SENS_BV_FU] += SU * gy;
+    }
+#pragma unroll
+    for (int i = 0; i < SENS_BV_ROWS; ++i) gbv[2 * (size_t)nw + i] = acc[i];
+}
+
+// lam_bv [n_b] = d f* / d bv (envelope theorem) at the snapshot's iterate, in CasADi's sign and unscaled: z_L / df of a lower side, -z_U / df
+// of an upper one, summed over the rows fl / fu / ol / ou bound (the circle rows weighted as sens_lam_obst weights them: the three copies of a
+// row together carry m z / df).  A presolved side of a_0 hands its multiplier on to fu through the friction row's gradient at a_0, the very
+// quotient mult_stage forms lam_g[0] from (2 a_0 against the 2 lb / 2 ub of the right-hand side: a difference of the order of mu), so that
+//   lam_bv[lbx_i] + lam_bv[ubx_i] = -lam_x[i],  lam_bv[fl] + lam_bv[fu] = -lam_g[0],  lam_bv[ol] + lam_bv[ou] = -(sum of lam_g over the circle rows)
+// hold to rounding and to what the final iterate leaves of nu = z_U - z_L of a row's slack.
+template <int NX>
+MPC_HD void sens_lam_bounds(const Params& P, const double* snap, double* lbv) {
+    using S = Sens<NX>;
+    constexpr int NZ = NX + 2;
+    const int N = P.N, X0 = 2 * N, nw = X0 + NX * (N + 1);
+    const double* tail = snap + (size_t)(N + 1) * S::SS;
+    const double idf = 1.0 / tail[S::T_DF], wm = P.obst_mult / 3.0;
+    double acc[SENS_BV_ROWS] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k <= N; ++k) {
+        const double* sn = snap + (size_t)k * S::SS;
+#pragma unroll
+        for (int i = 0; i < NZ; ++i) {
+            if (i < 2 && k == N) continue;
+            const int q = i < 2 ? 2 * k + i : X0 + NX * k + (i - 2);
+            const double lb = P.LB[k * NZ + i], ub = P.UB[k * NZ + i];
+            double zl = has_lo(lb) ? sn[S::ZL + i] : 0.0, zu = has_hi(ub) ? sn[S::ZU + i] : 0.0;
+            if (k == 0 && i == 1 && tail[S::T_FROW] == 0.0) {
+                const double a0lb = tail[S::T_A0LB], a0ub = tail[S::T_A0UB];
+                double zr = 0.0, g[3], h[4];
+                zl = zu = 0.0;
+                if (has_lo(a0lb)) { if (a0lb > lb) zr -= sn[S::ZL + 1]; else zl = sn[S::ZL + 1]; }
+                if (has_hi(a0ub)) { if (a0ub < ub) zr += sn[S::ZU + 1]; else zu = sn[S::ZU + 1]; }
+                friction_eval(P, sn[S::Z + 1], sn[S::Z + 2 + 2], sn[S::Z + 2 + 3], g, h, true);
+                if (g[0] != 0.0) acc[SENS_BV_FU] -= zr * idf / g[0];
+            }
+            lbv[q] = zl * idf;
+            lbv[nw + q] = -(zu * idf);
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            if (P.has_ol) acc[SENS_BV_OL] += 3.0 * (sn[S::ZLO + j] * idf * wm);
+            if (P.has_ou) acc[SENS_BV_OU] -= 3.0 * (sn[S::ZUO + j] * idf * wm);
+        }
+    }
+    if (tail[S::T_FROW] != 0.0) {
+        if (P.has_fl) acc[SENS_BV_FL] += tail[S::T_ZLF] * idf;
+        if (P.has_fu) acc[SENS_BV_FU] -= tail[S::T_ZUF] * idf;
+    }
+#pragma unroll
+    for (int i = 0; i < SENS_BV_ROWS; ++i) lbv[2 * (size_t)nw + i] = acc[i];
 }
 
 }  // namespace mpc

@@ -2621,6 +2621,38 @@ __global__ void __launch_bounds__(SENS_THREADS) k_sens_weights(const Params P, c
     }
 }
 
+// Lane per instance, the mapping of k_sens_obst: the same factor of the snapshot, then the derivative with respect to the bounds and the circle
+// radius bv = [lbx (n_w) | ubx (n_w) | fl, fu, ol, ou] (mpc_sens_bounds; n_b = 2 n_w + 4): n_dir forward directions dbv [B, n_dir, n_b] ->
+// dw [B, n_dir, n_w] and / or one adjoint seed [B, n_w] -> grad_bv [B, n_b], and lam_bv [B, n_b] = d f* / d bv.  NaN where the factor failed.
+// W: [sens_obst_scratch_len][B], as k_sens_obst's (the solves are sens_solve_circ's: refined against the stage data of sens_obst_setup).
+template <int NX>
+__global__ void __launch_bounds__(SENS_THREADS) k_sens_bounds(const Params P, const double* snap, double* F, double* W, const int n_dir, const double* dbv,
+                                                             double* dw, const double* seed, double* grad_bv, double* lam_bv) {
+    const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
+    if (b >= P.B) return;
+    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), Bs = (size_t)P.B, nn = (size_t)3 * (P.N + 1), nb = 2 * nw + SENS_BV_ROWS;
+    const double* sb = snap + (size_t)b * Sens<NX>::len(P.N);
+    const SensInst si = sens_factor<NX>(P, sb, F, Bs, b);
+    if (si.ok && (n_dir > 0 || grad_bv)) sens_obst_setup<NX>(P, sb, W, Bs, b);
+    double* V = W + (size_t)(P.N + 1) * SensObst<NX>::DS * Bs + b;
+    const SensVec sol{V, Bs}, work{V + nw * Bs, Bs}, nrow{V + 2 * nw * Bs, Bs}, om{V + (2 * nw + nn) * Bs, Bs};
+    for (int d = 0; d < n_dir; ++d) {
+        double* o = dw + ((size_t)b * n_dir + d) * nw;
+        if (si.ok) sens_forward_bounds<NX>(P, F, Bs, b, W, sb, dbv + ((size_t)b * n_dir + d) * nb, o, nrow, om, work);
+        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
+    }
+    if (grad_bv) {
+        double* o = grad_bv + (size_t)b * nb;
+        if (si.ok) sens_adjoint_bounds<NX>(P, F, Bs, b, W, sb, seed + (size_t)b * nw, o, sol, nrow, om, work);
+        else for (size_t q = 0; q < nb; ++q) o[q] = NAN;
+    }
+    if (lam_bv) {
+        double* o = lam_bv + (size_t)b * nb;
+        if (si.ok) sens_lam_bounds<NX>(P, sb, o);
+        else for (size_t q = 0; q < nb; ++q) o[q] = NAN;
+    }
+}
+
 template <int NX>
 __global__ void k_plant_step(const Params Pk, const double* x, const double* u, double* xn, int B, int integrator) {
     const PRef P(Pk);
@@ -2667,8 +2699,8 @@ enum Scratch : int {
     SCR_EX_LAM,                         // solve_ex_dev: the multiplier rows (lam_g or lam_x) the caller did not ask for
     SCR_SENS_SNAP,                      // solve_sens_dev: snapshot of the final iterates (read again by mpc_sens_adjoint_dev)
     SCR_SENS_LAM_G,                     // solve_sens_dev: lam_g for lam_p when the caller did not ask for it (live beside SCR_EX_LAM, then lam_x)
-    SCR_SENS_F,                         // sens_launch, sens_obst_launch, sens_weights_launch: the factors of the KKT matrices
-    SCR_SENS_OBST,                      // sens_obst_launch, sens_weights_launch: the stage data and the solves' vectors (sens_obst_setup, sens_solve_circ)
+    SCR_SENS_F,                         // sens_launch, sens_obst_launch, sens_weights_launch, sens_bounds_launch: the factors of the KKT matrices
+    SCR_SENS_OBST,                      // sens_obst_launch, sens_weights_launch, sens_bounds_launch: the stage data and the solves' vectors (sens_obst_setup, sens_solve_circ)
     SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
     SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
     SCR_LOOP_OBST,                      // closed_loop_dev: the obstacle rows of a loop with per-ego obstacle tracks (k_loop_obst)
@@ -2737,6 +2769,7 @@ struct mpc_handle {
     // how many instances
     bool snap_ok = false;
     int32_t snap_B = 0;
+    std::vector<double> raw_bounds[4];  // lbx, ubx, lbg, ubg as mpc_set_bounds was given them (mpc_get_bounds)
     void* scratch[N_SCRATCH] = {};
     size_t scratch_cap[N_SCRATCH] = {};
 };
@@ -2969,13 +3002,29 @@ int mpc_destroy(mpc_handle* h) {
 
 int mpc_set_bounds(mpc_handle* h, const double* lbx, const double* ubx, const double* lbg, const double* ubg) {
     if (!h) return MPC_ERR_INVALID;
+    h->snap_ok = false;                 // (the factor reads the bounds: a snapshot taken under the old ones is no longer differentiable)
     int rc = set_bounds(h->hp, lbx, ubx, lbg, ubg, h->err);
     if (rc) return rc;
+    // the bounds as they were given, for mpc_get_bounds (LB / UB hold them relaxed)
+    if (!lbx) default_bounds(h->hp.desc, h->raw_bounds[0], h->raw_bounds[1], h->raw_bounds[2], h->raw_bounds[3]);
+    else {
+        const double* src[4] = {lbx, ubx, lbg, ubg};
+        for (int q = 0; q < 4; ++q) h->raw_bounds[q].assign(src[q], src[q] + (q < 2 ? h->hp.n_w() : h->hp.n_g()));
+    }
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t n = h->hp.LB.size() * sizeof(double);
     if (!h->d_LB) { HIP_TRY(h, hipMalloc(&h->d_LB, n)); HIP_TRY(h, hipMalloc(&h->d_UB, n)); }
     HIP_TRY(h, hipMemcpy(h->d_LB, h->hp.LB.data(), n, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_UB, h->hp.UB.data(), n, hipMemcpyHostToDevice));
+    return MPC_OK;
+}
+
+int mpc_get_bounds(const mpc_handle* h, double* lbx, double* ubx, double* lbg, double* ubg) {
+    if (!h) return MPC_ERR_INVALID;
+    if (!h->hp.bounds_set || h->raw_bounds[0].empty()) return MPC_ERR_STATE;
+    double* dst[4] = {lbx, ubx, lbg, ubg};
+    for (int q = 0; q < 4; ++q)
+        if (dst[q]) std::copy(h->raw_bounds[q].begin(), h->raw_bounds[q].end(), dst[q]);
     return MPC_OK;
 }
 
@@ -3799,6 +3848,28 @@ static const char* bad_sens_weights(int32_t B, const double* p, int32_t n_dir, c
     return nullptr;
 }
 
+// the same factor, solved against the bounds' right-hand sides (k_sens_bounds)
+static int sens_bounds_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dbv, double* d_dw, const double* d_seed, double* d_grad, double* d_lam,
+                              hipStream_t s) {
+    const int N = h->hp.desc.N;
+    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(N + 1) * (size_t)sens_fs(h) * 8));
+    size_t wlen = 0;
+    FOR_NX(h, wlen = sens_obst_scratch_len<NX>(N));
+    double* W = static_cast<double*>(scratch_get(h, SCR_SENS_OBST, (size_t)B * wlen * 8));
+    if (!F || !W) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
+    const double* snap = static_cast<const double*>(h->scratch[SCR_SENS_SNAP]);
+    FOR_NX(h, hipLaunchKernelGGL((k_sens_bounds<NX>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F, W,
+                                 n_dir, d_dbv, d_dw, d_seed, d_grad, d_lam));
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+static const char* bad_sens_bounds(int32_t B, int32_t n_dir, const double* dbv, const double* dw, const double* seed_w, const double* grad_bv) {
+    if (B <= 0) return "B > 0 is required";
+    if (n_dir < 0 || (n_dir > 0 && (!dbv || !dw))) return "mpc_sens_bounds: n_dir >= 0, and dbv, dw are required when n_dir > 0";
+    if ((seed_w != nullptr) != (grad_bv != nullptr)) return "mpc_sens_bounds: seed_w and grad_bv go together";
+    return nullptr;
+}
+
 // solve_ex_dev plus the snapshot of the final iterates, CasADi's lam_p and n_dir forward sensitivities
 static int solve_sens_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, double* d_lam_p, int32_t n_dir, const double* d_dp, double* d_dw, hipStream_t s) {
     int rc = supply_status(h, io);
@@ -3966,6 +4037,30 @@ int mpc_sens_weights(mpc_handle* h, int32_t B, const double* p, int32_t n_dir, c
     return stage_host(h, {{p, nB * nw * 8, false}, {n_dir ? dwt : nullptr, nB * nd * SENS_NWT * 8, false}, {n_dir ? dw : nullptr, nB * nd * nw * 8, true},
                           {seed_w, nB * nw * 8, false}, {grad_wt, nB * SENS_NWT * 8, true}, {lam_wt, nB * SENS_NWT * 8, true}}, [&](void** d, hipStream_t s) {
         return mpc_sens_weights_dev(h, B, (double*)d[0], n_dir, (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], (double*)d[5], s);
+    });
+}
+
+// the derivative with respect to the bounds and the circle radius on the same snapshot, under the same rule (enqueued on `stream`)
+int mpc_sens_bounds_dev(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dbv, double* d_dw, const double* d_seed_w, double* d_grad_bv,
+                        double* d_lam_bv, void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    if (const char* bad = bad_sens_bounds(B, n_dir, d_dbv, d_dw, d_seed_w, d_grad_bv)) { h->err = bad; return MPC_ERR_INVALID; }
+    if (!h->snap_ok || B != h->snap_B) {
+        h->err = "mpc_sens_bounds: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B, or mpc_set_bounds / mpc_set_weights came after it";
+        return MPC_ERR_STATE;
+    }
+    if (n_dir == 0 && !d_grad_bv && !d_lam_bv) return MPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return sens_bounds_launch(h, B, n_dir, d_dbv, d_dw, d_seed_w, d_grad_bv, d_lam_bv, (hipStream_t)stream_);
+}
+
+int mpc_sens_bounds(mpc_handle* h, int32_t B, int32_t n_dir, const double* dbv, double* dw, const double* seed_w, double* grad_bv, double* lam_bv) {
+    if (!h) return MPC_ERR_INVALID;
+    if (const char* bad = bad_sens_bounds(B, n_dir, dbv, dw, seed_w, grad_bv)) { h->err = bad; return MPC_ERR_INVALID; }
+    const size_t nw = h->hp.n_w(), nB = (size_t)B, nd = (size_t)n_dir, nb = 2 * nw + SENS_BV_ROWS;
+    return stage_host(h, {{n_dir ? dbv : nullptr, nB * nd * nb * 8, false}, {n_dir ? dw : nullptr, nB * nd * nw * 8, true}, {seed_w, nB * nw * 8, false},
+                          {grad_bv, nB * nb * 8, true}, {lam_bv, nB * nb * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_sens_bounds_dev(h, B, n_dir, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], s);
     });
 }
 

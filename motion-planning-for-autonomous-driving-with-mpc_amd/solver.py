@@ -72,6 +72,16 @@ class WeightSens:
     lam_wt: np.ndarray | None = None     # [B, 7] d/dwt [f + lam_g' g] = d f*/dwt
 
 
+@dataclass
+class BoundSens:
+    """sens_bounds(): the derivative of the last solve's optimum with respect to the bound vector bv = [lbx (n_w) | ubx (n_w) | fl, fu, ol, ou]
+    (mpc_sens_bounds; n_b = 2 n_w + 4, see BatchedMPCSolver.bounds_vector).  The bounds are shared by the batch; the rows are per instance (sum
+    them for the derivative of a batch loss)"""
+    dw: np.ndarray | None = None         # [B, n_dir, n_w] (dw*/dbv) dbounds, NaN where status != 1
+    grad_bv: np.ndarray | None = None    # [B, n_b] (dw*/dbv)' seed_w
+    lam_bv: np.ndarray | None = None     # [B, n_b] d f*/dbv
+
+
 class BatchedMPCSolver:
     def __init__(self, N, nx=5, *, dt=0.1, Q=None, R=None, P=None, obstacle_centers=None, wheelbase=2.5789128,
                  friction_div=2.578, ego_offset=0.75, max_iter=100, tol=1e-8, fixed_iters=0, obst_mult=3, device=0,
@@ -98,6 +108,7 @@ class BatchedMPCSolver:
         self.N, self.nx = int(N), int(nx)
         self.n_w = 2 * self.N + self.nx * (self.N + 1)
         self.n_g = 1 + self.nx * (self.N + 1) + 9 * (self.N + 1)
+        self.n_b = 2 * self.n_w + 4
         self._h = C.c_void_p()
         self._sens_gen = 0          # solves that left a snapshot of their final iterates (mpc_solve_batch_sens): autograd.py checks it
         self._sens_B = 0            # ... and the batch size of the last of them
@@ -124,8 +135,10 @@ class BatchedMPCSolver:
 
     # ------------------------------------------------------------------------------------------------
     def set_bounds(self, lbx=None, ubx=None, lbg=None, ubg=None):
-        """the four lists of `inequal_constraints()` (optimizer.py:413-491); all None = reference defaults."""
+        """the four lists of `inequal_constraints()` (optimizer.py:413-491); all None = reference defaults.  The lists the solver already
+        holds are not installed again; anything else reaches mpc_set_bounds, which ends the life of the sensitivity snapshot, as a solve does."""
         if lbx is None and ubx is None and lbg is None and ubg is None:
+            self._sens_gen += 1                              # (a backward pass of autograd.py on the old snapshot raises)
             self._check(self._lib.mpc_set_bounds(self._h, None, None, None, None))
             self._bounds_key = None
             self._bounds = None
@@ -136,9 +149,34 @@ class BatchedMPCSolver:
         key = tuple(a.tobytes() for a in arrs)
         if key == self._bounds_key:
             return
+        self._sens_gen += 1
         self._check(self._lib.mpc_set_bounds(self._h, *[_abi.as_dp(a) for a in arrs]))
         self._bounds_key = key
         self._bounds = tuple(a.copy() for a in arrs)            # (lbx, ubx, lbg, ubg), for rescue_failed()
+
+    def get_bounds(self):
+        """(lbx [n_w], ubx [n_w], lbg [n_g], ubg [n_g]) as the handle holds them (mpc_get_bounds): what set_bounds installed, the reference
+        defaults of an all-None call included"""
+        out = np.empty(self.n_w), np.empty(self.n_w), np.empty(self.n_g), np.empty(self.n_g)
+        self._check(self._lib.mpc_get_bounds(self._h, *[_abi.as_dp(a) for a in out]))
+        return out
+
+    def bounds_vector(self):
+        """the bound vector bv [n_b] = [lbx (n_w) | ubx (n_w) | fl, fu, ol, ou] of get_bounds(): fl, fu are lbg[0], ubg[0] of the friction row,
+        ol, ou the pair shared by the 9 (N + 1) circle rows (ol is the radius sum); what sens_bounds differentiates with respect to"""
+        lbx, ubx, lbg, ubg = self.get_bounds()
+        return np.concatenate([lbx, ubx, [lbg[0], ubg[0], lbg[-1], ubg[-1]]])
+
+    def unpack_bounds(self, bv):
+        """(lbx, ubx, lbg, ubg) of a bound vector [n_b], the arguments of set_bounds: the equality rows 0, every circle row [ol, ou]"""
+        bv = _abi.f64(bv).ravel()
+        if bv.size != self.n_b:
+            raise MpcError(_abi.MPC_ERR_BOUNDS, f"expected a bound vector of {self.n_b} entries")
+        nw, ne, no = self.n_w, self.nx * (self.N + 1), 9 * (self.N + 1)
+        fl, fu, ol, ou = bv[2 * nw:]
+        lbg = np.concatenate([[fl], np.zeros(ne), np.full(no, ol)])
+        ubg = np.concatenate([[fu], np.zeros(ne), np.full(no, ou)])
+        return bv[:nw].copy(), bv[nw: 2 * nw].copy(), lbg, ubg
 
     def set_weights(self, Q=None, R=None):
         """replaces the cost weights Q[0..4] and / or R[0..1] of the live handle (mpc_set_weights): host bookkeeping only, no device work,
@@ -306,6 +344,32 @@ class BatchedMPCSolver:
                                                _abi.as_dp(lw)))
         return WeightSens(dw, grad, lw)
 
+    def sens_bounds(self, dbounds=None, seed_w=None, lam=False) -> BoundSens:
+        """the derivative of the optimum of the last solve(..., lam_p / dp) of this solver with respect to its bound vector bv (see
+        bounds_vector): dbounds [B, n_dir, n_b] (or [B, n_b]) -> dw [B, n_dir, n_w]; seed_w [B, n_w] -> grad_bv [B, n_b]; lam=True: lam_bv
+        [B, n_b], the derivative of the optimal objective.  Entries of absent bounds (+-inf) and of bounds the solve did not impose are 0 and
+        their dbounds entries are not read (mpc_sens_bounds; any solve, set_bounds or set_weights in between -> MpcError with code
+        MPC_ERR_STATE)"""
+        B = self._sens_B
+        dw = grad = lb = None
+        n_dir = 0
+        if dbounds is not None:
+            dbounds = _abi.f64(dbounds)
+            if dbounds.ndim == 2:
+                dbounds = dbounds[:, None, :]
+            if dbounds.ndim != 3 or dbounds.shape[0] != B or dbounds.shape[2] != self.n_b:
+                raise MpcError(_abi.MPC_ERR_INVALID, f"dbounds must be [{B}, n_dir, {self.n_b}]")
+            dbounds = np.ascontiguousarray(dbounds)
+            n_dir = dbounds.shape[1]
+            dw = np.empty((B, n_dir, self.n_w))
+        if seed_w is not None:
+            seed_w = _abi.f64(seed_w, (B, self.n_w))
+            grad = np.empty((B, self.n_b))
+        if lam:
+            lb = np.empty((B, self.n_b))
+        self._check(self._lib.mpc_sens_bounds(self._h, B, n_dir, _abi.as_dp(dbounds), _abi.as_dp(dw), _abi.as_dp(seed_w), _abi.as_dp(grad), _abi.as_dp(lb)))
+        return BoundSens(dw, grad, lb)
+
     def feedback_gain(self, x0, p, obst=None):
         """du_0*/dxref_0 [B, nu, nx]: the linearised control law around the optimum (xref_0 is the measured state the plan starts from)"""
         x0 = _abi.f64(x0)
@@ -396,6 +460,12 @@ class BatchedMPCSolver:
         d_dw [B, n_dir, n_w], d_seed_w [B, n_w] -> d_grad_wt [B, 7], d_lam_wt [B, 7]; 0 = not asked for"""
         self._check(self._lib.mpc_sens_weights_dev(self._h, int(B), _vp(d_p), int(n_dir), _vp(d_dweights), _vp(d_dw), _vp(d_seed_w), _vp(d_grad_wt),
                                                    _vp(d_lam_wt), _vp(stream)))
+
+    def sens_bounds_device(self, B, n_dir=0, d_dbounds=0, d_dw=0, d_seed_w=0, d_grad_bv=0, d_lam_bv=0, stream=0):
+        """device form of sens_bounds (enqueued on `stream`, not synchronised): d_dbounds [B, n_dir, n_b] -> d_dw [B, n_dir, n_w], d_seed_w
+        [B, n_w] -> d_grad_bv [B, n_b], d_lam_bv [B, n_b]; 0 = not asked for"""
+        self._check(self._lib.mpc_sens_bounds_dev(self._h, int(B), int(n_dir), _vp(d_dbounds), _vp(d_dw), _vp(d_seed_w), _vp(d_grad_bv), _vp(d_lam_bv),
+                                                  _vp(stream)))
 
     def plant_step(self, x, u, integrator="euler"):
         x = _abi.f64(x)

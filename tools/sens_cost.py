@@ -2,7 +2,8 @@
 same batch, alternating samples: plain | _ex (f, g, lam_g, lam_x) | _sens with lam_p only | _sens with n_dir = nx forward seeds | the
 adjoint alone (on the snapshot of the last _sens call) | mpc_sens_obst_dev alone on the same snapshot: its adjoint with lam_obst, and six
 forward directions (the unit directions of the obstacle centres) | mpc_sens_weights_dev alone on the same snapshot: its adjoint with
-lam_wt, and seven forward directions (the unit directions of the weights).
+lam_wt, and seven forward directions (the unit directions of the weights) | mpc_sens_bounds_dev alone on the same snapshot: its adjoint with
+lam_bv, and nine forward directions (the limits of the vehicle, the friction limit and the circle radius, each moved at every stage at once).
 Usage (GPU box): python tools/sens_cost.py [B] [family] [reps]"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
@@ -36,6 +37,16 @@ dob = torch.eye(6, dtype=torch.float64, device=dev).repeat(B, 1, 1).contiguous()
 go = torch.empty((B, 6), dtype=torch.float64, device=dev); lo = torch.empty_like(go)
 dwt = torch.eye(7, dtype=torch.float64, device=dev).repeat(B, 1, 1).contiguous(); dww = torch.empty((B, 7, nw), dtype=torch.float64, device=dev)
 gw = torch.empty((B, 7), dtype=torch.float64, device=dev); lw = torch.empty_like(gw)
+nb = s.n_b
+dbv = torch.zeros((B, 9, nb), dtype=torch.float64, device=dev)
+for k in range(cfg.N):
+    dbv[:, 0, 2 * k] = 1.0; dbv[:, 1, nw + 2 * k] = 1.0; dbv[:, 2, nw + 2 * k + 1] = 1.0                    # deltav_min, deltav_max, a_ub
+for k in range(cfg.N + 1):
+    for q, (side, i) in enumerate(((0, 2), (nw, 2), (0, 3), (nw, 3))):                                       # delta_min, delta_max, v_min, v_max
+        dbv[:, 3 + q, side + 2 * cfg.N + nx * k + i] = 1.0
+dbv[:, 7, 2 * nw + 1] = 1.0; dbv[:, 8, 2 * nw + 2] = 1.0                                                     # fu, ol
+dwb = torch.empty((B, 9, nw), dtype=torch.float64, device=dev)
+gb = torch.empty((B, nb), dtype=torch.float64, device=dev); lb = torch.empty_like(gb)
 ptrs = (tx0.data_ptr(), tp.data_ptr(), out.data_ptr(), st.data_ptr(), it.data_ptr(), kk.data_ptr())
 
 
@@ -75,6 +86,14 @@ def wt_fwd():
     s.sens_weights_device(B, tp.data_ptr(), 7, dwt.data_ptr(), dww.data_ptr())
 
 
+def bv_adjoint():
+    s.sens_bounds_device(B, d_seed_w=seed.data_ptr(), d_grad_bv=gb.data_ptr(), d_lam_bv=lb.data_ptr())
+
+
+def bv_fwd():
+    s.sens_bounds_device(B, 9, dbv.data_ptr(), dwb.data_ptr())
+
+
 def sample(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -84,8 +103,8 @@ def sample(fn):
 
 
 fns = dict(plain=plain, ex=ex, sens_lam_p=sens_lam_p, sens_fwd_nx=sens_fwd, adjoint=adjoint, obst_adjoint=obst_adjoint, obst_fwd_6=obst_fwd,
-           wt_adjoint=wt_adjoint, wt_fwd_7=wt_fwd)
-ON_SNAPSHOT = ("adjoint", "obst_adjoint", "obst_fwd_6", "wt_adjoint", "wt_fwd_7")
+           wt_adjoint=wt_adjoint, wt_fwd_7=wt_fwd, bv_adjoint=bv_adjoint, bv_fwd_9=bv_fwd)
+ON_SNAPSHOT = ("adjoint", "obst_adjoint", "obst_fwd_6", "wt_adjoint", "wt_fwd_7", "bv_adjoint", "bv_fwd_9")
 for _ in range(3):
     for k, fn in fns.items():
         if k in ON_SNAPSHOT:
@@ -104,4 +123,5 @@ for k, v in t.items():
 print(f"  cost over plain: _ex {1e3 * (med['ex'] - med['plain']):.1f} us, _sens lam_p {1e3 * (med['sens_lam_p'] - med['plain']):.1f} us, "
       f"_sens n_dir = {nx} {1e3 * (med['sens_fwd_nx'] - med['plain']):.1f} us, adjoint alone {1e3 * med['adjoint']:.1f} us, "
       f"obstacle adjoint + lam_obst alone {1e3 * med['obst_adjoint']:.1f} us, six obstacle directions alone {1e3 * med['obst_fwd_6']:.1f} us, "
-      f"weights adjoint + lam_wt alone {1e3 * med['wt_adjoint']:.1f} us, seven weight directions alone {1e3 * med['wt_fwd_7']:.1f} us")
+      f"weights adjoint + lam_wt alone {1e3 * med['wt_adjoint']:.1f} us, seven weight directions alone {1e3 * med['wt_fwd_7']:.1f} us, "
+      f"bounds adjoint + lam_bv alone {1e3 * med['bv_adjoint']:.1f} us, nine bound directions alone {1e3 * med['bv_fwd_9']:.1f} us")
