@@ -16,9 +16,8 @@
 // The objective scaling df multiplies the Hessian, the gradient and the multipliers alike and drops out of the primal step.
 // The obstacle centres, the cost weights and the bounds are further right-hand sides against the same factor: their sections below state them.
 //
-// Two layers, plain pointers only, so that the same code runs in the kernels (k_sens_gather, k_sens_factor_solve, k_sens_obst, k_sens_weights,
-// k_sens_bounds) and in the CPU harnesses of the tests (tests/sensx/sensx.cpp, tests/sensobstx/sensobstx.cpp, tests/sensweightx/sensweightx.cpp,
-// tests/sensboundx/sensboundx.cpp):
+// Two layers, plain pointers only, so that the same code runs in the kernels (k_sens_gather, k_sens<NX, Fam>) and in the CPU harness of the
+// tests (tests/sensx/sensx.cpp):
 //   snapshot  instance-major copy of the final iterate [(N + 1) stages of SS | a tail of T_COUNT], written by sens_gather_stage
 //   factor    per stage FS doubles, [stage][entry][Bs] (entry e of stage k of instance b at (k FS + e) Bs + b: lanes of a wave coalesce)
 #pragma once
@@ -204,7 +203,7 @@ MPC_HD void sens_stage_kkt(const Params& P, const int k, const double* tail, con
         if (i < 2) ruu[i] += sg;
         else sens_sym<NX>(Hs, i - 2, i - 2) += sg;
     }
-    // circle rows (obst_mult copies of one row each; the loop stays rolled: unrolled, k_sens_factor_solve<6> goes past 256 VGPRs)
+    // circle rows (obst_mult copies of one row each; the loop stays rolled: unrolled, k_sens<6, SensFamP<6>> goes past 256 VGPRs)
     const int oi[3] = {0, 1, 4};
 #pragma unroll 1
     for (int j = 0; j < 3; ++j) {
@@ -285,7 +284,7 @@ MPC_HD SensInst sens_factor(const Params& P, const double* snap, double* F, cons
         sens_congruence<NX>(Pm, a, dt, Nk[0], Nk[1]);                  // A'PA, rows 2 and 3 of PA
 #pragma unroll
         for (int j = 0; j < NX; ++j) { Nk[0][j] *= dt; Nk[1][j] *= dt; }
-        // (a compiler barrier: without it the stage's snapshot loads are hoisted above the congruence and k_sens_factor_solve<6> holds 248
+        // (a compiler barrier: without it the stage's snapshot loads are hoisted above the congruence and k_sens<6, SensFamP<6>> holds 248
         //  VGPRs, a few short of the 256 where this toolchain starts AGPR copies; with it, 220)
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" ::: "memory");
@@ -427,7 +426,7 @@ MPC_HD double sens_lam_p_entry(const Params& P, const int q, const bool conv, co
     return -2.0 * P.Q[i] * (w[X0 + NX * (k - 1) + i] - pr[q]);
 }
 
-// ---- the obstacle centres (mpc_sens_obst, k_sens_obst) ----------------------------------------------------------------------------------
+// ---- the obstacle centres (mpc_sens_obst, SensFamObst) ----------------------------------------------------------------------------------
 // The same step against the same factor with another right-hand side.  The centre o_j (two numbers) of obstacle circle j enters circle row j
 // of every stage, dist_j(x_k, o_j) - s = 0, and nothing else.  With the row's slack eliminated (d nu = sg (J_x dx + J_o do), sg = sum z / gap,
 // as sens_stage_kkt does for the matrix) the stationarity rows of x_k at the state components oi = {0, 1, 4} change by
@@ -649,6 +648,22 @@ MPC_HD void sens_solve_circ(const Params& P, double* F, const size_t Bs, const i
     }
 }
 
+// the pieces of a right-hand side that several families share: the seed of an adjoint as base, a circle row without shift, a result nobody reads
+template <int NX>
+struct SensSeedRhs {
+    const double* seed;
+    int N;
+    MPC_HD void operator()(const int k, double* gx, double* gu) const {
+        const int X0 = 2 * N;
+#pragma unroll
+        for (int i = 0; i < NX; ++i) gx[i] = seed[X0 + NX * k + i];
+        gu[0] = k < N ? seed[2 * k] : 0.0;
+        gu[1] = k < N ? seed[2 * k + 1] : 0.0;
+    }
+};
+struct SensNoShift { MPC_HD double operator()(int, int, const SensCirc&, double*) const { return 0.0; } };
+struct SensNoFin { MPC_HD void operator()(int, int, const SensCirc&, const double*, double) const {} };
+
 // forward direction: dobst [6] -> dw [n_w].  The centre o_j moves circle row j of every stage: gx_k = -m nu Hxo do_j at oi, t_kj = -J_o do_j.
 // D: the stage data of sens_obst_setup; nrow, om, work: scratch of sens_solve_circ
 template <int NX>
@@ -667,7 +682,7 @@ MPC_HD void sens_forward_obst(const Params& P, double* F, const size_t Bs, const
                             gx[4] -= C.mnu * (C.Hxo[4] * d0 + C.Hxo[5] * d1);
                             return -(C.Jo[0] * d0 + C.Jo[1] * d1);
                         },
-                        [&](int, int, const SensCirc&, const double*, double) {}, SensVec{dw, 1}, nrow, om, work);
+                        SensNoFin{}, SensVec{dw, 1}, nrow, om, work);
 }
 
 // reverse: seed_w [n_w] -> grad_o [6] = (dw/do)' seed_w.  The solve of the seed (t = 0) gives x_k and the circle multipliers n_kj; the
@@ -679,13 +694,8 @@ MPC_HD void sens_adjoint_obst(const Params& P, double* F, const size_t Bs, const
     const int N = P.N, X0 = 2 * N;
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     sens_solve_circ<NX>(P, F, Bs, b, D,
-                        [&](int k, double* gx, double* gu) {
-#pragma unroll
-                            for (int i = 0; i < NX; ++i) gx[i] = seed[X0 + NX * k + i];
-                            gu[0] = k < N ? seed[2 * k] : 0.0;
-                            gu[1] = k < N ? seed[2 * k + 1] : 0.0;
-                        },
-                        [&](int, int, const SensCirc&, double*) { return 0.0; },
+                        SensSeedRhs<NX>{seed, N},
+                        SensNoShift{},
                         [&](int, int j, const SensCirc& C, const double* x, double n) {
                             acc[2 * j] -= C.mnu * (C.Hxo[0] * x[0] + C.Hxo[2] * x[1] + C.Hxo[4] * x[4]) + C.Jo[0] * n;
                             acc[2 * j + 1] -= C.mnu * (C.Hxo[1] * x[0] + C.Hxo[3] * x[1] + C.Hxo[5] * x[4]) + C.Jo[1] * n;
@@ -722,7 +732,7 @@ MPC_HD void sens_lam_obst(const Params& P, const double* snap, double* lo) {
     for (int i = 0; i < 6; ++i) lo[i] = acc[i];
 }
 
-// ---- the cost weights (mpc_sens_weights, k_sens_weights) ---------------------------------------------------------------------------------
+// ---- the cost weights (mpc_sens_weights, SensFamWeights) ---------------------------------------------------------------------------------
 // The same step against the same factor with a third right-hand side.  The weight vector is wt = [Q_0 .. Q_4 | R_0, R_1] (SENS_NWT numbers
 // for NX = 5 and 6 alike: Q_5, the progress state's weight, is not among them).  The weights enter the residual through the cost gradient only,
 //   of x_k:  df 2 Q_i e_k[i],  e_k = x_k - xref_{k+1}  (i < 5, k < N)         of u_k:  df 2 R_j u_k[j]  (k < N)
@@ -754,8 +764,8 @@ MPC_HD void sens_forward_weights(const Params& P, const SensInst& si, double* F,
                             gu[0] = k < N ? m2df * z[0] * dwt[SENS_NWQ] : 0.0;
                             gu[1] = k < N ? m2df * z[1] * dwt[SENS_NWQ + 1] : 0.0;
                         },
-                        [&](int, int, const SensCirc&, double*) { return 0.0; },
-                        [&](int, int, const SensCirc&, const double*, double) {}, SensVec{dw, 1}, nrow, om, work);
+                        SensNoShift{},
+                        SensNoFin{}, SensVec{dw, 1}, nrow, om, work);
 }
 
 // reverse: seed_w [n_w] -> gwt [7] = (dw/dwt)' seed_w.  The solve of the seed gives (y_u,k, y_x,k) in sol; the transposed right-hand side of the
@@ -768,14 +778,9 @@ MPC_HD void sens_adjoint_weights(const Params& P, const SensInst& si, double* F,
     const int N = P.N, X0 = 2 * N;
     const double m2df = -2.0 * si.df;
     sens_solve_circ<NX, SENS_WT_REFINE>(P, F, Bs, b, D,
-                        [&](int k, double* gx, double* gu) {
-#pragma unroll
-                            for (int i = 0; i < NX; ++i) gx[i] = seed[X0 + NX * k + i];
-                            gu[0] = k < N ? seed[2 * k] : 0.0;
-                            gu[1] = k < N ? seed[2 * k + 1] : 0.0;
-                        },
-                        [&](int, int, const SensCirc&, double*) { return 0.0; },
-                        [&](int, int, const SensCirc&, const double*, double) {}, sol, nrow, om, work);
+                        SensSeedRhs<NX>{seed, N},
+                        SensNoShift{},
+                        SensNoFin{}, sol, nrow, om, work);
     double acc[SENS_NWT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < N; ++k) {
         const double* z = snap + (size_t)k * S::SS + S::Z;
@@ -806,7 +811,7 @@ MPC_HD void sens_lam_weights(const Params& P, const double* snap, const double* 
     for (int i = 0; i < SENS_NWT; ++i) lwt[i] = acc[i];
 }
 
-// ---- the bounds and the circle radius (mpc_sens_bounds, k_sens_bounds) --------------------------------------------------------------------
+// ---- the bounds and the circle radius (mpc_sens_bounds, SensFamBounds) --------------------------------------------------------------------
 // The same step against the same factor with a fourth right-hand side.  The bound vector is bv = [lbx (n_w) | ubx (n_w) | fl, fu, ol, ou]: the
 // arrays of mpc_set_bounds, lbg[0] / ubg[0] of the friction row and the pair shared by the circle rows (ol is the radius sum); n_b = 2 n_w + 4.
 // With SL = z_L / gap_L and SU = z_U / gap_U of a side (what sens_stage_kkt adds to the diagonal; 0 where the side has no bound) a direction
@@ -822,7 +827,7 @@ MPC_HD void sens_lam_weights(const Params& P, const double* snap, const double* 
 // presolved one), has SL = SU = 0: its derivative is 0 and its dbv entry is not read.  The entries are the caller's bounds; the solve relaxes
 // them by BOUND_RELAX (1e-8 relative), a factor 1 + 1e-8 at most on a derivative, which is left out.
 // An active side carries S ~ 1e10 in the right-hand side and in the matrix alike, as an active circle row does for the centres: the solve is
-// sens_solve_circ's with SENS_BV_REFINE step of refinement.  Measured with tests/sensboundx on the twelve collision-avoidance rows the tests
+// sens_solve_circ's with SENS_BV_REFINE step of refinement.  Measured with the harness (tests/sensx/sensx.cpp, sensboundx_solve) on the twelve collision-avoidance rows the tests
 // compare (N = 30, nx = 5; every row has active steering-rate bounds and circle rows), the worst |seed' dw - grad_bv' dbv| /
 // max(1, sum |seed| max |dw|) over ten directions: one step 1.1e-13, two 2.8e-17, three 2.9e-17; the bound asked of the identity is 1e-10, and
 // dw against the active-set reference is the same to every printed digit for one, two and three steps.  (The kernel with one step, over all 70
@@ -912,7 +917,7 @@ MPC_HD void sens_forward_bounds(const Params& P, double* F, const size_t Bs, con
                             if (wu != 0.0) t += wu * dr[SENS_BV_OU];
                             return t;
                         },
-                        [&](int, int, const SensCirc&, const double*, double) {}, SensVec{dw, 1}, nrow, om, work);
+                        SensNoFin{}, SensVec{dw, 1}, nrow, om, work);
 }
 
 // reverse: seed_w [n_w] -> gbv [n_b] = (dw/dbv)' seed_w.  The solve of the seed (every shift t = 0) gives (y_u,k, y_x,k) in sol and the circle
@@ -927,13 +932,8 @@ MPC_HD void sens_adjoint_bounds(const Params& P, double* F, const size_t Bs, con
     const double* tail = snap + (size_t)(N + 1) * S::SS;
     double acc[SENS_BV_ROWS] = {0.0, 0.0, 0.0, 0.0};
     sens_solve_circ<NX, SENS_BV_REFINE>(P, F, Bs, b, D,
-                        [&](int k, double* gx, double* gu) {
-#pragma unroll
-                            for (int i = 0; i < NX; ++i) gx[i] = seed[X0 + NX * k + i];
-                            gu[0] = k < N ? seed[2 * k] : 0.0;
-                            gu[1] = k < N ? seed[2 * k + 1] : 0.0;
-                        },
-                        [&](int, int, const SensCirc&, double*) { return 0.0; },
+                        SensSeedRhs<NX>{seed, N},
+                        SensNoShift{},
                         [&](int k, int j, const SensCirc&, const double*, double n) {
                             double wl, wu;
                             sens_circ_shares<NX>(P, snap + (size_t)k * S::SS, j, wl, wu);
@@ -1012,6 +1012,111 @@ MPC_HD void sens_lam_bounds(const Params& P, const double* snap, double* lbv) {
     }
 #pragma unroll
     for (int i = 0; i < SENS_BV_ROWS; ++i) lbv[2 * (size_t)nw + i] = acc[i];
+}
+
+// ---- parameter families ----------------------------------------------------------------------------------------------------------------
+// What the solves of one instance work on: the factor, the stage data D of sens_obst_setup and the scratch vectors of sens_solve_circ (null
+// for a family without CIRC), the instance's snapshot row and its row pr of the solve's p (null where the family does not read it).
+template <int NX>
+struct SensCtx {
+    const Params& P;
+    SensInst si;
+    double* F;
+    size_t Bs;
+    int b;
+    const double* D;
+    const double* snap;
+    const double* pr;
+    SensVec sol, work, nrow, om;
+};
+// A family of parameters is a type Fam<NX> with
+//   CIRC                    whether its solves are sens_solve_circ's (they need sens_obst_setup's stage data and the scratch vectors)
+//   LAM                     whether it has a lam (the p row's is k_sens_lam_p's: another thread mapping)
+//   row(N)                  the length of a direction, a gradient and a lam row
+//   forward(c, dir, dw)     dir [row] -> dw [n_w]
+//   adjoint(c, seed, grad)  seed_w [n_w] -> grad [row] = (dw/d parameter)' seed_w
+//   lam(c, out)             out [row] = d/d parameter [f + lam_g' g] at the snapshot's iterate
+// over the functions of the sections above.  Those keep their plain arguments: with the bodies taking the context and unpacking it, the same
+// arithmetic compiled to 85 more reloads of spilled SGPRs in the bounds' kernel and its directions ran 0.8 % slower.
+// sens_family runs a family: it is the body of k_sens<NX, Fam> and of the harness of the tests.
+template <int NX>
+struct SensFamP {               // the p row [U_ref | X_ref]: n_p = n_w
+    static constexpr bool CIRC = false, LAM = false;
+    MPC_HD static size_t row(const int N) { return (size_t)2 * N + (size_t)NX * (N + 1); }
+    MPC_HD static void forward(const SensCtx<NX>& c, const double* dp, double* dw) { sens_forward<NX>(c.P, c.si, c.F, c.Bs, c.b, dp, dw); }
+    MPC_HD static void adjoint(const SensCtx<NX>& c, const double* seed, double* gp) { sens_adjoint<NX>(c.P, c.si, c.F, c.Bs, c.b, seed, gp); }
+};
+template <int NX>
+struct SensFamObst {            // the six obstacle centres
+    static constexpr bool CIRC = true, LAM = true;
+    MPC_HD static size_t row(int) { return 6; }
+    MPC_HD static void forward(const SensCtx<NX>& c, const double* dobst, double* dw) { sens_forward_obst<NX>(c.P, c.F, c.Bs, c.b, c.D, dobst, dw, c.nrow, c.om, c.work); }
+    MPC_HD static void adjoint(const SensCtx<NX>& c, const double* seed, double* go) { sens_adjoint_obst<NX>(c.P, c.F, c.Bs, c.b, c.D, seed, go, c.sol, c.nrow, c.om, c.work); }
+    MPC_HD static void lam(const SensCtx<NX>& c, double* lo) { sens_lam_obst<NX>(c.P, c.snap, lo); }
+};
+template <int NX>
+struct SensFamWeights {         // the seven cost weights; reads the instance's p row
+    static constexpr bool CIRC = true, LAM = true;
+    MPC_HD static size_t row(int) { return SENS_NWT; }
+    MPC_HD static void forward(const SensCtx<NX>& c, const double* dwt, double* dw) {
+        sens_forward_weights<NX>(c.P, c.si, c.F, c.Bs, c.b, c.D, c.snap, c.pr, dwt, dw, c.nrow, c.om, c.work);
+    }
+    MPC_HD static void adjoint(const SensCtx<NX>& c, const double* seed, double* gwt) {
+        sens_adjoint_weights<NX>(c.P, c.si, c.F, c.Bs, c.b, c.D, c.snap, c.pr, seed, gwt, c.sol, c.nrow, c.om, c.work);
+    }
+    MPC_HD static void lam(const SensCtx<NX>& c, double* lwt) { sens_lam_weights<NX>(c.P, c.snap, c.pr, lwt); }
+};
+template <int NX>
+struct SensFamBounds {          // the bound vector bv: n_b = 2 n_w + 4
+    static constexpr bool CIRC = true, LAM = true;
+    MPC_HD static size_t row(const int N) { return (size_t)2 * ((size_t)2 * N + (size_t)NX * (N + 1)) + SENS_BV_ROWS; }
+    MPC_HD static void forward(const SensCtx<NX>& c, const double* dbv, double* dw) { sens_forward_bounds<NX>(c.P, c.F, c.Bs, c.b, c.D, c.snap, dbv, dw, c.nrow, c.om, c.work); }
+    MPC_HD static void adjoint(const SensCtx<NX>& c, const double* seed, double* gbv) {
+        sens_adjoint_bounds<NX>(c.P, c.F, c.Bs, c.b, c.D, c.snap, seed, gbv, c.sol, c.nrow, c.om, c.work);
+    }
+    MPC_HD static void lam(const SensCtx<NX>& c, double* lbv) { sens_lam_bounds<NX>(c.P, c.snap, lbv); }
+};
+
+// ---- one instance, one family ------------------------------------------------------------------------------------------------------------
+// doubles per instance of the scratch W of a CIRC family: the stage data of sens_obst_setup, then sol, work (n_w each) and nrow, om (3 (N + 1) each)
+template <int NX>
+MPC_HD size_t sens_obst_scratch_len(int N) { return (size_t)(N + 1) * SensObst<NX>::DS + (size_t)2 * ((size_t)2 * N + (size_t)NX * (N + 1)) + (size_t)6 * (N + 1); }
+
+// Instance b of P.B: factor the final KKT matrix of its snapshot row (F: [stage][entry][B] factor storage), the stage data where the family
+// needs it and a direction or a gradient is asked for (W: [sens_obst_scratch_len][B]; null otherwise), then n_dir forward directions
+// dir [B, n_dir, row] -> dw [B, n_dir, n_w], one adjoint seed [B, n_w] -> grad [B, row] and lam [B, row], each optional (n_dir = 0, null).
+// p [B, n_w]: the p rows of the solve, for a family that reads them.  NaN where the factor failed; returns whether it succeeded.
+template <int NX, class Fam>
+MPC_HD bool sens_family(const Params& P, const double* snap, double* F, double* W, const double* p, const int b, const int n_dir, const double* dir,
+                        double* dw, const double* seed, double* grad, double* lam) {
+    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), Bs = (size_t)P.B, nr = Fam::row(P.N);
+    const double* sb = snap + (size_t)b * Sens<NX>::len(P.N);
+    SensCtx<NX> c{P, sens_factor<NX>(P, sb, F, Bs, b), F, Bs, b, W, sb, p ? p + (size_t)b * nw : nullptr, {}, {}, {}, {}};
+    const bool ok = c.si.ok;
+    if constexpr (Fam::CIRC) {
+        const size_t nn = (size_t)3 * (P.N + 1);
+        if (ok && (n_dir > 0 || grad)) sens_obst_setup<NX>(P, sb, W, Bs, b);
+        double* V = W + (size_t)(P.N + 1) * SensObst<NX>::DS * Bs + b;
+        c.sol = {V, Bs}; c.work = {V + nw * Bs, Bs}; c.nrow = {V + 2 * nw * Bs, Bs}; c.om = {V + (2 * nw + nn) * Bs, Bs};
+    }
+    for (int d = 0; d < n_dir; ++d) {
+        double* o = dw + ((size_t)b * n_dir + d) * nw;
+        if (ok) Fam::forward(c, dir + ((size_t)b * n_dir + d) * nr, o);
+        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
+    }
+    if (grad) {
+        double* o = grad + (size_t)b * nr;
+        if (ok) Fam::adjoint(c, seed + (size_t)b * nw, o);
+        else for (size_t q = 0; q < nr; ++q) o[q] = NAN;
+    }
+    if constexpr (Fam::LAM) {
+        if (lam) {
+            double* o = lam + (size_t)b * nr;
+            if (ok) Fam::lam(c, o);
+            else for (size_t q = 0; q < nr; ++q) o[q] = NAN;
+        }
+    }
+    return ok;
 }
 
 }  // namespace mpc

@@ -2527,130 +2527,15 @@ __global__ void k_sens_lam_p(const Params P, const double* x_out, const double* 
     const int q = (int)(e - b * nw);
     lam_p[e] = sens_lam_p_entry<NX>(P, q, status[b] == 1, x_out + b * nw, p + b * nw, lam_g + b * ng);
 }
-// Lane per instance: factor the final KKT matrix of the snapshot (F: [stage][entry][B] factor storage), then n_dir forward directions
-// dp [B, n_dir, n_p] -> dw [B, n_dir, n_w] and / or one adjoint seed [B, n_w] -> grad_p [B, n_p].  NaN where the factor failed.
+// Lane per instance: sens_family (mpc_sens.h) of one parameter family Fam -- SensFamP (mpc_solve_batch_sens, mpc_sens_adjoint), SensFamObst
+// (mpc_sens_obst), SensFamWeights (mpc_sens_weights), SensFamBounds (mpc_sens_bounds).  Its arguments are sens_family's.
 constexpr int SENS_THREADS = 64;
-template <int NX>
-__global__ void __launch_bounds__(SENS_THREADS) k_sens_factor_solve(const Params P, const double* snap, double* F, const int n_dir, const double* dp,
-                                                                   double* dw, const double* seed, double* grad_p) {
+template <int NX, class Fam>
+__global__ void __launch_bounds__(SENS_THREADS) k_sens(const Params P, const double* snap, double* F, double* W, const double* p, const int n_dir,
+                                                      const double* dir, double* dw, const double* seed, double* grad, double* lam) {
     const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
     if (b >= P.B) return;
-    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), Bs = (size_t)P.B;
-    const SensInst si = sens_factor<NX>(P, snap + (size_t)b * Sens<NX>::len(P.N), F, Bs, b);
-    for (int d = 0; d < n_dir; ++d) {
-        double* o = dw + ((size_t)b * n_dir + d) * nw;
-        if (si.ok) sens_forward<NX>(P, si, F, Bs, b, dp + ((size_t)b * n_dir + d) * nw, o);
-        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
-    }
-    if (grad_p) {
-        double* o = grad_p + (size_t)b * nw;
-        if (si.ok) sens_adjoint<NX>(P, si, F, Bs, b, seed + (size_t)b * nw, o);
-        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
-    }
-}
-
-// doubles per instance of k_sens_obst's scratch: the stage data of sens_obst_setup, then sol, work (n_w each) and nrow, om (3 (N + 1) each)
-template <int NX>
-MPC_HD size_t sens_obst_scratch_len(int N) { return (size_t)(N + 1) * SensObst<NX>::DS + (size_t)2 * ((size_t)2 * N + (size_t)NX * (N + 1)) + (size_t)6 * (N + 1); }
-// Lane per instance, the mapping of k_sens_factor_solve: the same factor of the snapshot, then the derivative with respect to the six obstacle
-// centres (mpc_sens_obst): n_dir forward directions dobst [B, n_dir, 6] -> dw [B, n_dir, n_w] and / or one adjoint seed [B, n_w] -> grad_o [B, 6],
-// and lam_o [B, 6] = d/do [f + lam_g' g].  NaN where the factor failed.  W: [sens_obst_scratch_len][B], the stage data of sens_obst_setup and
-// the vectors of sens_solve_circ.
-template <int NX>
-__global__ void __launch_bounds__(SENS_THREADS) k_sens_obst(const Params P, const double* snap, double* F, double* W, const int n_dir, const double* dobst,
-                                                           double* dw, const double* seed, double* grad_o, double* lam_o) {
-    const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
-    if (b >= P.B) return;
-    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), Bs = (size_t)P.B, nn = (size_t)3 * (P.N + 1);
-    const double* sb = snap + (size_t)b * Sens<NX>::len(P.N);
-    const SensInst si = sens_factor<NX>(P, sb, F, Bs, b);
-    if (si.ok && (n_dir > 0 || grad_o)) sens_obst_setup<NX>(P, sb, W, Bs, b);
-    double* V = W + (size_t)(P.N + 1) * SensObst<NX>::DS * Bs + b;
-    const SensVec sol{V, Bs}, work{V + nw * Bs, Bs}, nrow{V + 2 * nw * Bs, Bs}, om{V + (2 * nw + nn) * Bs, Bs};
-    for (int d = 0; d < n_dir; ++d) {
-        double* o = dw + ((size_t)b * n_dir + d) * nw;
-        if (si.ok) sens_forward_obst<NX>(P, F, Bs, b, W, dobst + ((size_t)b * n_dir + d) * 6, o, nrow, om, work);
-        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
-    }
-    if (grad_o) {
-        double go[6];
-        if (si.ok) sens_adjoint_obst<NX>(P, F, Bs, b, W, seed + (size_t)b * nw, go, sol, nrow, om, work);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) grad_o[(size_t)b * 6 + i] = si.ok ? go[i] : NAN;
-    }
-    if (lam_o) {
-        double lo[6];
-        if (si.ok) sens_lam_obst<NX>(P, sb, lo);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) lam_o[(size_t)b * 6 + i] = si.ok ? lo[i] : NAN;
-    }
-}
-
-// Lane per instance, the mapping of k_sens_obst: the same factor of the snapshot, then the derivative with respect to the seven cost weights
-// wt = [Q_0 .. Q_4 | R_0, R_1] (mpc_sens_weights): n_dir forward directions dwt [B, n_dir, 7] -> dw [B, n_dir, n_w] and / or one adjoint seed
-// [B, n_w] -> grad_wt [B, 7], and lam_wt [B, 7] = d/dwt [f + lam_g' g].  p [B, n_w]: the p rows of the solve (xref).  NaN where the factor
-// failed.  W: [sens_obst_scratch_len][B], as k_sens_obst's (the solves are sens_solve_circ's: refined against the stage data of sens_obst_setup).
-template <int NX>
-__global__ void __launch_bounds__(SENS_THREADS) k_sens_weights(const Params P, const double* snap, double* F, double* W, const double* p, const int n_dir,
-                                                              const double* dwt, double* dw, const double* seed, double* grad_wt, double* lam_wt) {
-    const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
-    if (b >= P.B) return;
-    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), Bs = (size_t)P.B, nn = (size_t)3 * (P.N + 1);
-    const double* sb = snap + (size_t)b * Sens<NX>::len(P.N);
-    const double* pr = p + (size_t)b * nw;
-    const SensInst si = sens_factor<NX>(P, sb, F, Bs, b);
-    if (si.ok && (n_dir > 0 || grad_wt)) sens_obst_setup<NX>(P, sb, W, Bs, b);
-    double* V = W + (size_t)(P.N + 1) * SensObst<NX>::DS * Bs + b;
-    const SensVec sol{V, Bs}, work{V + nw * Bs, Bs}, nrow{V + 2 * nw * Bs, Bs}, om{V + (2 * nw + nn) * Bs, Bs};
-    for (int d = 0; d < n_dir; ++d) {
-        double* o = dw + ((size_t)b * n_dir + d) * nw;
-        if (si.ok) sens_forward_weights<NX>(P, si, F, Bs, b, W, sb, pr, dwt + ((size_t)b * n_dir + d) * SENS_NWT, o, nrow, om, work);
-        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
-    }
-    if (grad_wt) {
-        double gw[SENS_NWT];
-        if (si.ok) sens_adjoint_weights<NX>(P, si, F, Bs, b, W, sb, pr, seed + (size_t)b * nw, gw, sol, nrow, om, work);
-#pragma unroll
-        for (int i = 0; i < SENS_NWT; ++i) grad_wt[(size_t)b * SENS_NWT + i] = si.ok ? gw[i] : NAN;
-    }
-    if (lam_wt) {
-        double lw[SENS_NWT];
-        if (si.ok) sens_lam_weights<NX>(P, sb, pr, lw);
-#pragma unroll
-        for (int i = 0; i < SENS_NWT; ++i) lam_wt[(size_t)b * SENS_NWT + i] = si.ok ? lw[i] : NAN;
-    }
-}
-
-// Lane per instance, the mapping of k_sens_obst: the same factor of the snapshot, then the derivative with respect to the bounds and the circle
-// radius bv = [lbx (n_w) | ubx (n_w) | fl, fu, ol, ou] (mpc_sens_bounds; n_b = 2 n_w + 4): n_dir forward directions dbv [B, n_dir, n_b] ->
-// dw [B, n_dir, n_w] and / or one adjoint seed [B, n_w] -> grad_bv [B, n_b], and lam_bv [B, n_b] = d f* / d bv.  NaN where the factor failed.
-// W: [sens_obst_scratch_len][B], as k_sens_obst's (the solves are sens_solve_circ's: refined against the stage data of sens_obst_setup).
-template <int NX>
-__global__ void __launch_bounds__(SENS_THREADS) k_sens_bounds(const Params P, const double* snap, double* F, double* W, const int n_dir, const double* dbv,
-                                                             double* dw, const double* seed, double* grad_bv, double* lam_bv) {
-    const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
-    if (b >= P.B) return;
-    const size_t nw = (size_t)2 * P.N + (size_t)NX * (P.N + 1), Bs = (size_t)P.B, nn = (size_t)3 * (P.N + 1), nb = 2 * nw + SENS_BV_ROWS;
-    const double* sb = snap + (size_t)b * Sens<NX>::len(P.N);
-    const SensInst si = sens_factor<NX>(P, sb, F, Bs, b);
-    if (si.ok && (n_dir > 0 || grad_bv)) sens_obst_setup<NX>(P, sb, W, Bs, b);
-    double* V = W + (size_t)(P.N + 1) * SensObst<NX>::DS * Bs + b;
-    const SensVec sol{V, Bs}, work{V + nw * Bs, Bs}, nrow{V + 2 * nw * Bs, Bs}, om{V + (2 * nw + nn) * Bs, Bs};
-    for (int d = 0; d < n_dir; ++d) {
-        double* o = dw + ((size_t)b * n_dir + d) * nw;
-        if (si.ok) sens_forward_bounds<NX>(P, F, Bs, b, W, sb, dbv + ((size_t)b * n_dir + d) * nb, o, nrow, om, work);
-        else for (size_t q = 0; q < nw; ++q) o[q] = NAN;
-    }
-    if (grad_bv) {
-        double* o = grad_bv + (size_t)b * nb;
-        if (si.ok) sens_adjoint_bounds<NX>(P, F, Bs, b, W, sb, seed + (size_t)b * nw, o, sol, nrow, om, work);
-        else for (size_t q = 0; q < nb; ++q) o[q] = NAN;
-    }
-    if (lam_bv) {
-        double* o = lam_bv + (size_t)b * nb;
-        if (si.ok) sens_lam_bounds<NX>(P, sb, o);
-        else for (size_t q = 0; q < nb; ++q) o[q] = NAN;
-    }
+    sens_family<NX, Fam>(P, snap, F, W, p, b, n_dir, dir, dw, seed, grad, lam);
 }
 
 template <int NX>
@@ -2699,8 +2584,8 @@ enum Scratch : int {
     SCR_EX_LAM,                         // solve_ex_dev: the multiplier rows (lam_g or lam_x) the caller did not ask for
     SCR_SENS_SNAP,                      // solve_sens_dev: snapshot of the final iterates (read again by mpc_sens_adjoint_dev)
     SCR_SENS_LAM_G,                     // solve_sens_dev: lam_g for lam_p when the caller did not ask for it (live beside SCR_EX_LAM, then lam_x)
-    SCR_SENS_F,                         // sens_launch, sens_obst_launch, sens_weights_launch, sens_bounds_launch: the factors of the KKT matrices
-    SCR_SENS_OBST,                      // sens_obst_launch, sens_weights_launch, sens_bounds_launch: the stage data and the solves' vectors (sens_obst_setup, sens_solve_circ)
+    SCR_SENS_F,                         // sens_family_launch: the factors of the KKT matrices
+    SCR_SENS_OBST,                      // sens_family_launch: the stage data and the solves' vectors of a family with CIRC (sens_obst_setup, sens_solve_circ)
     SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
     SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
     SCR_LOOP_OBST,                      // closed_loop_dev: the obstacle rows of a loop with per-ego obstacle tracks (k_loop_obst)
@@ -3792,82 +3677,67 @@ static int solve_ex_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, hip
 }
 
 // ---- parametric sensitivities -----------------------------------------------------------------------------------
-// factor the snapshot's KKT matrices and solve: n_dir forward directions and / or one adjoint seed (k_sens_factor_solve)
-static int sens_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dp, double* d_dw, const double* d_seed, double* d_grad, hipStream_t s) {
-    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(h->hp.desc.N + 1) * (size_t)sens_fs(h) * 8));
-    if (!F) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
+// One parameter family (mpc_sens.h) on the snapshot: the factors of the KKT matrices, the family's scratch where it has any, k_sens<NX, Fam>
+template <template <int> class Fam>
+static int sens_family_launch(mpc_handle* h, int32_t B, const double* d_p, int32_t n_dir, const double* d_dir, double* d_dw, const double* d_seed, double* d_grad,
+                              double* d_lam, hipStream_t s) {
+    const int N = h->hp.desc.N;
+    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(N + 1) * (size_t)sens_fs(h) * 8));
+    double* W = nullptr;
+    if (Fam<5>::CIRC) {
+        size_t wlen = 0;
+        FOR_NX(h, wlen = sens_obst_scratch_len<NX>(N));
+        W = static_cast<double*>(scratch_get(h, SCR_SENS_OBST, (size_t)B * wlen * 8));
+    }
+    if (!F || (Fam<5>::CIRC && !W)) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
     const double* snap = static_cast<const double*>(h->scratch[SCR_SENS_SNAP]);
-    FOR_NX(h, hipLaunchKernelGGL((k_sens_factor_solve<NX>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F,
-                                 n_dir, d_dp, d_dw, d_seed, d_grad));
+    FOR_NX(h, hipLaunchKernelGGL((k_sens<NX, Fam<NX>>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F, W,
+                                 d_p, n_dir, d_dir, d_dw, d_seed, d_grad, d_lam));
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
 
-// the same factor, solved against the obstacle centres' right-hand sides (k_sens_obst)
-static int sens_obst_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dobst, double* d_dw, const double* d_seed, double* d_grad, double* d_lam,
-                            hipStream_t s) {
-    const int N = h->hp.desc.N;
-    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(N + 1) * (size_t)sens_fs(h) * 8));
-    size_t wlen = 0;
-    FOR_NX(h, wlen = sens_obst_scratch_len<NX>(N));
-    double* W = static_cast<double*>(scratch_get(h, SCR_SENS_OBST, (size_t)B * wlen * 8));
-    if (!F || !W) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
-    const double* snap = static_cast<const double*>(h->scratch[SCR_SENS_SNAP]);
-    FOR_NX(h, hipLaunchKernelGGL((k_sens_obst<NX>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F, W,
-                                 n_dir, d_dobst, d_dw, d_seed, d_grad, d_lam));
-    HIP_TRY(h, hipGetLastError());
-    return MPC_OK;
-}
-static const char* bad_sens_obst(int32_t B, int32_t n_dir, const double* dobst, const double* dw, const double* seed_w, const double* grad_obst) {
+// What an entry point says when it refuses: need_p (null: p is not an argument), dirs, pair for its arguments, state for the snapshot
+struct SensTexts { const char *need_p, *dirs, *pair, *state; };
+static const SensTexts SENS_OBST_TEXTS = {nullptr, "mpc_sens_obst: n_dir >= 0, and dobst, dw are required when n_dir > 0", "mpc_sens_obst: seed_w and grad_obst go together",
+                                          "mpc_sens_obst: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B"};
+static const SensTexts SENS_WEIGHTS_TEXTS = {"mpc_sens_weights: p (the p rows of the solve) is required", "mpc_sens_weights: n_dir >= 0, and dwt, dw are required when n_dir > 0",
+                                             "mpc_sens_weights: seed_w and grad_wt go together",
+                                             "mpc_sens_weights: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B, or mpc_set_weights came after it"};
+static const SensTexts SENS_BOUNDS_TEXTS = {nullptr, "mpc_sens_bounds: n_dir >= 0, and dbv, dw are required when n_dir > 0", "mpc_sens_bounds: seed_w and grad_bv go together",
+                                            "mpc_sens_bounds: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B, or mpc_set_bounds / mpc_set_weights came after it"};
+static const char* bad_sens_args(const SensTexts& t, int32_t B, const double* p, int32_t n_dir, const double* dir, const double* dw, const double* seed_w, const double* grad) {
     if (B <= 0) return "B > 0 is required";
-    if (n_dir < 0 || (n_dir > 0 && (!dobst || !dw))) return "mpc_sens_obst: n_dir >= 0, and dobst, dw are required when n_dir > 0";
-    if ((seed_w != nullptr) != (grad_obst != nullptr)) return "mpc_sens_obst: seed_w and grad_obst go together";
+    if (t.need_p && !p) return t.need_p;
+    if (n_dir < 0 || (n_dir > 0 && (!dir || !dw))) return t.dirs;
+    if ((seed_w != nullptr) != (grad != nullptr)) return t.pair;
     return nullptr;
 }
-
-// the same factor, solved against the cost weights' right-hand sides (k_sens_weights)
-static int sens_weights_launch(mpc_handle* h, int32_t B, const double* d_p, int32_t n_dir, const double* d_dwt, double* d_dw, const double* d_seed, double* d_grad,
-                               double* d_lam, hipStream_t s) {
-    const int N = h->hp.desc.N;
-    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(N + 1) * (size_t)sens_fs(h) * 8));
-    size_t wlen = 0;
-    FOR_NX(h, wlen = sens_obst_scratch_len<NX>(N));
-    double* W = static_cast<double*>(scratch_get(h, SCR_SENS_OBST, (size_t)B * wlen * 8));
-    if (!F || !W) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
-    const double* snap = static_cast<const double*>(h->scratch[SCR_SENS_SNAP]);
-    FOR_NX(h, hipLaunchKernelGGL((k_sens_weights<NX>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F, W, d_p,
-                                 n_dir, d_dwt, d_dw, d_seed, d_grad, d_lam));
-    HIP_TRY(h, hipGetLastError());
-    return MPC_OK;
+// The device form of a family's entry point: `bad` (what its argument check found) -> MPC_ERR_INVALID; the snapshot must be that of the handle's
+// last solve, mpc_solve_batch_sens[_dev] with the same B (MPC_ERR_STATE with `state`); nothing asked for -> MPC_OK; else enqueued on `s`.
+template <template <int> class Fam>
+static int sens_family_dev(mpc_handle* h, const char* bad, const char* state, int32_t B, const double* d_p, int32_t n_dir, const double* d_dir, double* d_dw,
+                           const double* d_seed, double* d_grad, double* d_lam, hipStream_t s) {
+    if (!h) return MPC_ERR_INVALID;
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    if (!h->snap_ok || B != h->snap_B) { h->err = state; return MPC_ERR_STATE; }
+    if (n_dir == 0 && !d_grad && !d_lam) return MPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return sens_family_launch<Fam>(h, B, d_p, n_dir, d_dir, d_dw, d_seed, d_grad, d_lam, s);
 }
-static const char* bad_sens_weights(int32_t B, const double* p, int32_t n_dir, const double* dwt, const double* dw, const double* seed_w, const double* grad_wt) {
-    if (B <= 0) return "B > 0 is required";
-    if (!p) return "mpc_sens_weights: p (the p rows of the solve) is required";
-    if (n_dir < 0 || (n_dir > 0 && (!dwt || !dw))) return "mpc_sens_weights: n_dir >= 0, and dwt, dw are required when n_dir > 0";
-    if ((seed_w != nullptr) != (grad_wt != nullptr)) return "mpc_sens_weights: seed_w and grad_wt go together";
-    return nullptr;
-}
-
-// the same factor, solved against the bounds' right-hand sides (k_sens_bounds)
-static int sens_bounds_launch(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dbv, double* d_dw, const double* d_seed, double* d_grad, double* d_lam,
-                              hipStream_t s) {
-    const int N = h->hp.desc.N;
-    double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, (size_t)B * (size_t)(N + 1) * (size_t)sens_fs(h) * 8));
-    size_t wlen = 0;
-    FOR_NX(h, wlen = sens_obst_scratch_len<NX>(N));
-    double* W = static_cast<double*>(scratch_get(h, SCR_SENS_OBST, (size_t)B * wlen * 8));
-    if (!F || !W) { h->err = "sensitivities: out of device memory"; return MPC_ERR_HIP; }
-    const double* snap = static_cast<const double*>(h->scratch[SCR_SENS_SNAP]);
-    FOR_NX(h, hipLaunchKernelGGL((k_sens_bounds<NX>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F, W,
-                                 n_dir, d_dbv, d_dw, d_seed, d_grad, d_lam));
-    HIP_TRY(h, hipGetLastError());
-    return MPC_OK;
-}
-static const char* bad_sens_bounds(int32_t B, int32_t n_dir, const double* dbv, const double* dw, const double* seed_w, const double* grad_bv) {
-    if (B <= 0) return "B > 0 is required";
-    if (n_dir < 0 || (n_dir > 0 && (!dbv || !dw))) return "mpc_sens_bounds: n_dir >= 0, and dbv, dw are required when n_dir > 0";
-    if ((seed_w != nullptr) != (grad_bv != nullptr)) return "mpc_sens_bounds: seed_w and grad_bv go together";
-    return nullptr;
+// The host-pointer form: the same check of the caller's arguments, the buffers staged by the family's row length, then the device form
+template <template <int> class Fam>
+static int sens_family_host(mpc_handle* h, const char* bad, const char* state, int32_t B, const double* p, int32_t n_dir, const double* dir, double* dw,
+                            const double* seed, double* grad, double* lam) {
+    if (!h) return MPC_ERR_INVALID;
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    size_t nr = 0;
+    FOR_NX(h, nr = Fam<NX>::row(h->hp.desc.N));
+    const size_t nw = h->hp.n_w(), nB = (size_t)B, nd = (size_t)n_dir;
+    return stage_host(h, {{p, nB * nw * 8, false}, {n_dir ? dir : nullptr, nB * nd * nr * 8, false}, {n_dir ? dw : nullptr, nB * nd * nw * 8, true},
+                          {seed, nB * nw * 8, false}, {grad, nB * nr * 8, true}, {lam, nB * nr * 8, true}}, [&](void** d, hipStream_t s) {
+        return sens_family_dev<Fam>(h, nullptr, state, B, (double*)d[0], n_dir, (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], (double*)d[5], s);
+    });
 }
 
 // solve_ex_dev plus the snapshot of the final iterates, CasADi's lam_p and n_dir forward sensitivities
@@ -3884,7 +3754,7 @@ static int solve_sens_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, d
         FOR_NX(h, hipLaunchKernelGGL((k_sens_lam_p<NX>), grid, dim3(256), 0, s, rows_params(h, io.B, false), io.x_out, io.p, io.status, io.lam_g, d_lam_p));
         HIP_TRY(h, hipGetLastError());
     }
-    if (n_dir > 0 && (rc = sens_launch(h, io.B, n_dir, d_dp, d_dw, nullptr, nullptr, s))) return rc;
+    if (n_dir > 0 && (rc = sens_family_launch<SensFamP>(h, io.B, nullptr, n_dir, d_dp, d_dw, nullptr, nullptr, nullptr, s))) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));
     return MPC_OK;
 }
@@ -3972,96 +3842,50 @@ int mpc_solve_batch_sens(mpc_handle* h, int32_t B, const double* x0, const doubl
 }
 
 // reverse mode on the snapshot of the handle's last solve, if that was mpc_solve_batch_sens[_dev] with the same B (enqueued on `stream`)
-int mpc_sens_adjoint_dev(mpc_handle* h, int32_t B, const double* d_seed_w, double* d_grad_p, void* stream_) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !d_seed_w || !d_grad_p) { h->err = "B > 0 and seed_w, grad_p are required"; return MPC_ERR_INVALID; }
-    if (!h->snap_ok || B != h->snap_B) {
-        h->err = "mpc_sens_adjoint: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B";
-        return MPC_ERR_STATE;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    return sens_launch(h, B, 0, nullptr, nullptr, d_seed_w, d_grad_p, (hipStream_t)stream_);
+static const char* bad_sens_adjoint(int32_t B, const double* seed_w, const double* grad_p) { return B <= 0 || !seed_w || !grad_p ? "B > 0 and seed_w, grad_p are required" : nullptr; }
+static const char* const SENS_ADJOINT_STATE = "mpc_sens_adjoint: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B";
+int mpc_sens_adjoint_dev(mpc_handle* h, int32_t B, const double* d_seed_w, double* d_grad_p, void* stream) {
+    return sens_family_dev<SensFamP>(h, bad_sens_adjoint(B, d_seed_w, d_grad_p), SENS_ADJOINT_STATE, B, nullptr, 0, nullptr, nullptr, d_seed_w, d_grad_p, nullptr, (hipStream_t)stream);
 }
-
 int mpc_sens_adjoint(mpc_handle* h, int32_t B, const double* seed_w, double* grad_p) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !seed_w || !grad_p) { h->err = "B > 0 and seed_w, grad_p are required"; return MPC_ERR_INVALID; }
-    const size_t nw = h->hp.n_w(), nB = (size_t)B;
-    return stage_host(h, {{seed_w, nB * nw * 8, false}, {grad_p, nB * nw * 8, true}},
-                      [&](void** d, hipStream_t s) { return mpc_sens_adjoint_dev(h, B, (double*)d[0], (double*)d[1], s); });
+    return sens_family_host<SensFamP>(h, bad_sens_adjoint(B, seed_w, grad_p), SENS_ADJOINT_STATE, B, nullptr, 0, nullptr, nullptr, seed_w, grad_p, nullptr);
 }
 
 // the derivative with respect to the obstacle centres on the same snapshot, under the same rule (enqueued on `stream`)
 int mpc_sens_obst_dev(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dobst, double* d_dw, const double* d_seed_w, double* d_grad_obst,
-                      double* d_lam_obst, void* stream_) {
-    if (!h) return MPC_ERR_INVALID;
-    if (const char* bad = bad_sens_obst(B, n_dir, d_dobst, d_dw, d_seed_w, d_grad_obst)) { h->err = bad; return MPC_ERR_INVALID; }
-    if (!h->snap_ok || B != h->snap_B) {
-        h->err = "mpc_sens_obst: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B";
-        return MPC_ERR_STATE;
-    }
-    if (n_dir == 0 && !d_grad_obst && !d_lam_obst) return MPC_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    return sens_obst_launch(h, B, n_dir, d_dobst, d_dw, d_seed_w, d_grad_obst, d_lam_obst, (hipStream_t)stream_);
+                      double* d_lam_obst, void* stream) {
+    const SensTexts& t = SENS_OBST_TEXTS;
+    return sens_family_dev<SensFamObst>(h, bad_sens_args(t, B, nullptr, n_dir, d_dobst, d_dw, d_seed_w, d_grad_obst), t.state, B, nullptr, n_dir, d_dobst, d_dw, d_seed_w,
+                                        d_grad_obst, d_lam_obst, (hipStream_t)stream);
 }
-
 int mpc_sens_obst(mpc_handle* h, int32_t B, int32_t n_dir, const double* dobst, double* dw, const double* seed_w, double* grad_obst, double* lam_obst) {
-    if (!h) return MPC_ERR_INVALID;
-    if (const char* bad = bad_sens_obst(B, n_dir, dobst, dw, seed_w, grad_obst)) { h->err = bad; return MPC_ERR_INVALID; }
-    const size_t nw = h->hp.n_w(), nB = (size_t)B, nd = (size_t)n_dir;
-    return stage_host(h, {{n_dir ? dobst : nullptr, nB * nd * 6 * 8, false}, {n_dir ? dw : nullptr, nB * nd * nw * 8, true}, {seed_w, nB * nw * 8, false},
-                          {grad_obst, nB * 6 * 8, true}, {lam_obst, nB * 6 * 8, true}}, [&](void** d, hipStream_t s) {
-        return mpc_sens_obst_dev(h, B, n_dir, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], s);
-    });
+    const SensTexts& t = SENS_OBST_TEXTS;
+    return sens_family_host<SensFamObst>(h, bad_sens_args(t, B, nullptr, n_dir, dobst, dw, seed_w, grad_obst), t.state, B, nullptr, n_dir, dobst, dw, seed_w, grad_obst, lam_obst);
 }
 
 // the derivative with respect to the cost weights on the same snapshot, under the same rule (enqueued on `stream`)
 int mpc_sens_weights_dev(mpc_handle* h, int32_t B, const double* d_p, int32_t n_dir, const double* d_dwt, double* d_dw, const double* d_seed_w,
-                         double* d_grad_wt, double* d_lam_wt, void* stream_) {
-    if (!h) return MPC_ERR_INVALID;
-    if (const char* bad = bad_sens_weights(B, d_p, n_dir, d_dwt, d_dw, d_seed_w, d_grad_wt)) { h->err = bad; return MPC_ERR_INVALID; }
-    if (!h->snap_ok || B != h->snap_B) {
-        h->err = "mpc_sens_weights: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B, or mpc_set_weights came after it";
-        return MPC_ERR_STATE;
-    }
-    if (n_dir == 0 && !d_grad_wt && !d_lam_wt) return MPC_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    return sens_weights_launch(h, B, d_p, n_dir, d_dwt, d_dw, d_seed_w, d_grad_wt, d_lam_wt, (hipStream_t)stream_);
+                         double* d_grad_wt, double* d_lam_wt, void* stream) {
+    const SensTexts& t = SENS_WEIGHTS_TEXTS;
+    return sens_family_dev<SensFamWeights>(h, bad_sens_args(t, B, d_p, n_dir, d_dwt, d_dw, d_seed_w, d_grad_wt), t.state, B, d_p, n_dir, d_dwt, d_dw, d_seed_w, d_grad_wt,
+                                           d_lam_wt, (hipStream_t)stream);
 }
-
 int mpc_sens_weights(mpc_handle* h, int32_t B, const double* p, int32_t n_dir, const double* dwt, double* dw, const double* seed_w, double* grad_wt,
                      double* lam_wt) {
-    if (!h) return MPC_ERR_INVALID;
-    if (const char* bad = bad_sens_weights(B, p, n_dir, dwt, dw, seed_w, grad_wt)) { h->err = bad; return MPC_ERR_INVALID; }
-    const size_t nw = h->hp.n_w(), nB = (size_t)B, nd = (size_t)n_dir;
-    return stage_host(h, {{p, nB * nw * 8, false}, {n_dir ? dwt : nullptr, nB * nd * SENS_NWT * 8, false}, {n_dir ? dw : nullptr, nB * nd * nw * 8, true},
-                          {seed_w, nB * nw * 8, false}, {grad_wt, nB * SENS_NWT * 8, true}, {lam_wt, nB * SENS_NWT * 8, true}}, [&](void** d, hipStream_t s) {
-        return mpc_sens_weights_dev(h, B, (double*)d[0], n_dir, (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], (double*)d[5], s);
-    });
+    const SensTexts& t = SENS_WEIGHTS_TEXTS;
+    return sens_family_host<SensFamWeights>(h, bad_sens_args(t, B, p, n_dir, dwt, dw, seed_w, grad_wt), t.state, B, p, n_dir, dwt, dw, seed_w, grad_wt, lam_wt);
 }
 
 // the derivative with respect to the bounds and the circle radius on the same snapshot, under the same rule (enqueued on `stream`)
 int mpc_sens_bounds_dev(mpc_handle* h, int32_t B, int32_t n_dir, const double* d_dbv, double* d_dw, const double* d_seed_w, double* d_grad_bv,
-                        double* d_lam_bv, void* stream_) {
-    if (!h) return MPC_ERR_INVALID;
-    if (const char* bad = bad_sens_bounds(B, n_dir, d_dbv, d_dw, d_seed_w, d_grad_bv)) { h->err = bad; return MPC_ERR_INVALID; }
-    if (!h->snap_ok || B != h->snap_B) {
-        h->err = "mpc_sens_bounds: the handle's last solve was not mpc_solve_batch_sens[_dev] with this B, or mpc_set_bounds / mpc_set_weights came after it";
-        return MPC_ERR_STATE;
-    }
-    if (n_dir == 0 && !d_grad_bv && !d_lam_bv) return MPC_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    return sens_bounds_launch(h, B, n_dir, d_dbv, d_dw, d_seed_w, d_grad_bv, d_lam_bv, (hipStream_t)stream_);
+                        double* d_lam_bv, void* stream) {
+    const SensTexts& t = SENS_BOUNDS_TEXTS;
+    return sens_family_dev<SensFamBounds>(h, bad_sens_args(t, B, nullptr, n_dir, d_dbv, d_dw, d_seed_w, d_grad_bv), t.state, B, nullptr, n_dir, d_dbv, d_dw, d_seed_w, d_grad_bv,
+                                          d_lam_bv, (hipStream_t)stream);
 }
-
 int mpc_sens_bounds(mpc_handle* h, int32_t B, int32_t n_dir, const double* dbv, double* dw, const double* seed_w, double* grad_bv, double* lam_bv) {
-    if (!h) return MPC_ERR_INVALID;
-    if (const char* bad = bad_sens_bounds(B, n_dir, dbv, dw, seed_w, grad_bv)) { h->err = bad; return MPC_ERR_INVALID; }
-    const size_t nw = h->hp.n_w(), nB = (size_t)B, nd = (size_t)n_dir, nb = 2 * nw + SENS_BV_ROWS;
-    return stage_host(h, {{n_dir ? dbv : nullptr, nB * nd * nb * 8, false}, {n_dir ? dw : nullptr, nB * nd * nw * 8, true}, {seed_w, nB * nw * 8, false},
-                          {grad_bv, nB * nb * 8, true}, {lam_bv, nB * nb * 8, true}}, [&](void** d, hipStream_t s) {
-        return mpc_sens_bounds_dev(h, B, n_dir, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], s);
-    });
+    const SensTexts& t = SENS_BOUNDS_TEXTS;
+    return sens_family_host<SensFamBounds>(h, bad_sens_args(t, B, nullptr, n_dir, dbv, dw, seed_w, grad_bv), t.state, B, nullptr, n_dir, dbv, dw, seed_w, grad_bv, lam_bv);
 }
 
 // Host bookkeeping only: every launch builds its Params from the descriptor (fill_params), so nothing on the device holds a weight.

@@ -7,6 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 SRC = os.path.join(HERE, "emu.cpp")
 LIB = os.path.join(HERE, "libmpc_emu.so")
 DEPS = [SRC,
+        os.path.join(HERE, "emu_solve.h"),
         os.path.join(ROOT, "motion-planning-for-autonomous-driving-with-mpc_amd", "csrc", "mpc_stage_math.h"),
         os.path.join(ROOT, "motion-planning-for-autonomous-driving-with-mpc_amd", "csrc", "mpc_host_common.h"),
         os.path.join(ROOT, "motion-planning-for-autonomous-driving-with-mpc_amd", "csrc", "mpc_solve_plan.h"),

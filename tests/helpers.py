@@ -1,8 +1,12 @@
 """shared test helpers: problem families, emulator binding, oracle-backed fake backend for host-logic tests."""
+import atexit
 import ctypes as C
 import importlib
 import os
+import shutil
+import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -55,6 +59,25 @@ def make_solver(cfg, **kw):
 def set_cfg_bounds(solver, cfg):
     lbg, ubg, lbx, ubx = BicycleNLP(cfg).bounds()
     solver.set_bounds(lbx, ubx, lbg, ubg)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the g++ harnesses of the CPU tests (tests/<name>/<name>.cpp)
+# ------------------------------------------------------------------------------------------------------------
+_harness = {}
+
+
+def harness_lib(name):
+    """Path of tests/<name>/<name>.cpp compiled by g++ into a shared library in a temporary directory; once per session, however many test
+    modules ask for it."""
+    if name not in _harness:
+        if not _harness:
+            _harness[None] = tempfile.mkdtemp(prefix="mpc_harness_")
+            atexit.register(shutil.rmtree, _harness[None], ignore_errors=True)
+        lib = os.path.join(_harness[None], f"lib{name}.so")
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, os.path.join(ROOT, "tests", name, name + ".cpp")])
+        _harness[name] = lib
+    return _harness[name]
 
 
 # ------------------------------------------------------------------------------------------------------------

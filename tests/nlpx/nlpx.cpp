@@ -1,120 +1,34 @@
 // tests/nlpx/nlpx.cpp -- CPU harness of the NLP evaluation and the multiplier mapping (TEST INFRASTRUCTURE, not shipped).
 //
-// Steps the kernels' phase functions of <package>/csrc/mpc_stage_math.h thread by thread on the CPU, the way tests/emu/emu.cpp does (one
-// launch per kernel and iteration: the iterate stays in the tile-major rows), then runs what k_eval_nlp and k_mult_out run on the GPU:
-// nlp_eval_stage and mult_stage.  Built by tests/test_multipliers_cpu.py with g++ into a temporary directory.
+// The emulated solve of tests/emu/emu_solve.h (one launch per kernel and iteration: the iterate stays in the tile-major rows), then what
+// k_eval_nlp and k_mult_out run on the GPU: nlp_eval_stage and mult_stage.  Built by tests/helpers.py (harness_lib) with g++ into a
+// temporary directory.
 #include <cmath>
 #include <string>
 #include <vector>
 
-#include "../../motion-planning-for-autonomous-driving-with-mpc_amd/csrc/mpc_host_common.h"
+#include "../emu/emu_solve.h"
 
 using namespace mpc;
 
-template <typename R>
-static void reduce_block(std::vector<R>& part, int bx, int S) {
-    for (int bl = 0; bl < bx; ++bl) {
-        R acc = part[bl];
-        for (int k = 1; k < S; ++k) red_combine(acc, part[(size_t)k * bx + bl]);
-        for (int k = 0; k < S; ++k) part[(size_t)k * bx + bl] = acc;
-    }
-}
-
 template <int NX>
-static int run(const HostProblem& hp, int B, const double* x0, const double* p, double* x_out, int32_t* status, double* lam_g, double* lam_x) {
-    const mpc_problem_desc& d = hp.desc;
-    const int N = d.N, S = N + 1;
-    const size_t Bp = ((size_t)B + 63) / 64 * 64;
-    const int bx = pick_bx(N, 512);
-    const WsLayout w = ws_layout(N, NX, Bp, false);
-    std::vector<double> ws(w.total, 0.0);
-    std::vector<int32_t> iws(w.itotal, 0);
-    std::vector<int32_t> iters(B);
-    std::vector<double> kkt(B);
-    Params P;
-    fill_params(P, hp, B, Bp, bx, ws.data(), iws.data(), hp.LB.data(), hp.UB.data(), false);
-    P.x0 = x0; P.p = p; P.x_out = x_out; P.status_out = status; P.iters_out = iters.data(); P.kkt_out = kkt.data();
-    const int nblocks = (B + bx - 1) / bx, nthreads = S * bx;
-    std::vector<Ctx<NX>> ctx(nthreads);
-    std::vector<Red0> r0(nthreads);
-    std::vector<Red1> r1(nthreads);
-    std::vector<Red2> r2(nthreads);
-    std::vector<Red3> r3(nthreads);
-    auto setup = [&](int blk) {
-        for (int t = 0; t < nthreads; ++t) {
-            Ctx<NX>& c = ctx[t];
-            c = Ctx<NX>{};
-            c.k = t / bx;
-            c.b = blk * bx + t % bx;
-            c.valid = c.b < B;
-            if (!c.valid) c.b = (int)Bp - 1;
-            c.active = false;
-        }
-    };
-    auto eval_finish = [&](bool reuse) {
-        for (int t = 0; t + bx < nthreads; ++t)
-            for (int i = 0; i < NX; ++i) { ctx[t].xn[i] = ctx[t + bx].z[2 + i]; ctx[t].lamn[i] = ctx[t + bx].lam[i]; }
-        for (int t = 0; t < nthreads; ++t) { if (reuse) phase_eval_assemble<NX, true>(P, ctx[t], r3[t]); else phase_eval_assemble<NX, false>(P, ctx[t], r3[t]); }
-        reduce_block(r3, bx, S);
-        for (int t = 0; t < nthreads; ++t) phase_finish<NX>(P, ctx[t], r3[t], hp.n_mult, hp.n_z);
-    };
-    for (int b = 0; b < B; ++b) ingest_instance<NX>(P, b);
-    for (int b = 0; b < B; ++b) prestart_instance<NX>(P, b);
-    for (int blk = 0; blk < nblocks; ++blk) {
-        setup(blk);
-        for (int t = 0; t < nthreads; ++t) phase_init_point<NX>(P, ctx[t], r0[t]);
-        reduce_block(r0, bx, S);
-        for (int t = 0; t < nthreads; ++t) phase_init_scalars<NX>(P, ctx[t], r0[t]);
-        eval_finish(false);
-    }
-    for (int it = 0; it < d.max_iter; ++it) {
-        int running = 0;
-        for (int b = 0; b < B; ++b) running += iws[w.ielem(IS_STATUS, b)] == ST_RUNNING;
-        if (!running) break;
-        for (int b = 0; b < B; ++b) riccati_instance<NX>(P, b);
-        for (int blk = 0; blk < nblocks; ++blk) {
-            setup(blk);
-            bool any = false;
-            for (int t = 0; t < nthreads; ++t) { PreTmp<NX> tmp; phase_load_scalars<NX>(P, ctx[t]); phase_preload<NX>(P, ctx[t], tmp); phase_premath<NX>(P, ctx[t], tmp); any |= ctx[t].active; }
-            if (!any) continue;
-            for (int t = 0; t < nthreads; ++t) phase_step_candidates<NX>(P, ctx[t], r1[t]);
-            reduce_block(r1, bx, S);
-            for (int t = 0; t < nthreads; ++t) phase_linesearch_begin<NX>(P, ctx[t], r1[t]);
-            for (;;) {
-                bool searching = false;
-                for (int t = 0; t < nthreads; ++t) searching |= (ctx[t].active && ctx[t].searching);
-                if (!searching) break;
-                for (int t = 0; t < nthreads; ++t) phase_trial_eval<NX>(P, ctx[t], r2[t]);
-                reduce_block(r2, bx, S);
-                for (int t = 0; t < nthreads; ++t) phase_linesearch_decide<NX>(P, ctx[t], r2[t]);
-            }
-            for (int t = 0; t < nthreads; ++t) phase_apply_update<NX>(P, ctx[t]);
-            eval_finish(true);
-        }
-    }
-    for (int b = 0; b < B; ++b) output_instance<NX>(P, b);
-    const size_t nw = hp.n_w(), ng = hp.n_g();
-    for (int b = 0; b < B; ++b)
-        for (int k = 0; k <= N; ++k) {
-            if (status[b] != 1) mult_stage_fill<NX>(P, k, NAN, lam_g + (size_t)b * ng, lam_x + (size_t)b * nw);
-            else mult_stage<NX>(P, b, k, false, x_out + (size_t)b * nw, lam_g + (size_t)b * ng, lam_x + (size_t)b * nw);
-        }
-    return MPC_OK;
+static void run(const HostProblem& hp, int B, const double* x0, const double* p, double* x_out, int32_t* status, double* lam_g, double* lam_x) {
+    EmuSolve<NX> e;
+    EmuOpts o;
+    o.mailbox = false;
+    e.run(hp, B, x0, p, x_out, status, nullptr, nullptr, o);
+    e.multipliers(hp, x_out, status, lam_g, lam_x);
 }
 
 extern "C" int nlpx_solve(const mpc_problem_desc* desc, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
                           int32_t friction_literal, int32_t B, const double* x0, const double* p, double* x_out, int32_t* status,
                           double* lam_g, double* lam_x) {
     HostProblem hp;
-    hp.desc = *desc;
-    std::string err;
-    int rc = validate_desc(hp.desc, err);
+    const int rc = emu_problem(hp, desc, lbx, ubx, lbg, ubg, friction_literal);
     if (rc) return rc;
-    hp.fric_literal = friction_literal ? 1 : 0;
-    rc = set_bounds(hp, lbx, ubx, lbg, ubg, err);
-    if (rc) return rc;
-    if (desc->nx == 5) return run<5>(hp, B, x0, p, x_out, status, lam_g, lam_x);
-    return run<6>(hp, B, x0, p, x_out, status, lam_g, lam_x);
+    if (desc->nx == 5) run<5>(hp, B, x0, p, x_out, status, lam_g, lam_x);
+    else run<6>(hp, B, x0, p, x_out, status, lam_g, lam_x);
+    return MPC_OK;
 }
 
 extern "C" int nlpx_eval(const mpc_problem_desc* desc, int32_t B, const double* x, const double* p, const double* obst, double* f, double* g) {

@@ -5,13 +5,12 @@ on the CPU; the oracle loop over the scenes of tests/loop_obst_ref.py is the ref
 tests presuppose about it is checked here."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import loop_obst_ref as ref
-from helpers import ROOT, abi, pkg
+from helpers import ROOT, abi, harness_lib, pkg
 from oracle.nlp_numpy import circle_centers
 
 scn = __import__("importlib").import_module(pkg.__name__ + ".scenario")
@@ -31,10 +30,8 @@ def test_new_entry_points_declared_and_exported():
 
 
 @pytest.fixture(scope="module")
-def loopx(tmp_path_factory):
-    lib = str(tmp_path_factory.mktemp("loopx") / "libloopx.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, os.path.join(ROOT, "tests", "loopx", "loopx.cpp")])
-    L = C.CDLL(lib)
+def loopx():
+    L = C.CDLL(harness_lib("loopx"))
     dp = C.POINTER(C.c_double)
     L.loopx_centres.argtypes = [C.c_int32, dp, C.c_double, dp]
     L.loopx_clearance.argtypes = [C.c_int32, C.c_double, dp, dp, C.c_double, dp]

@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import CA_CFG, FAMILIES, ROOT, BicycleNLP, abi, ca_batch, cfg_from_golden, emu_desc, synthetic_batch
+from helpers import CA_CFG, FAMILIES, ROOT, BicycleNLP, abi, ca_batch, cfg_from_golden, emu_desc, harness_lib, synthetic_batch
 from oracle.binding import OracleSolver as CORACLE
 from test_gpu_multipliers import kkt_violations
 
@@ -31,11 +31,8 @@ def test_new_entry_points_declared_and_exported():
 
 
 @pytest.fixture(scope="module")
-def nlpx(tmp_path_factory):
-    d = tmp_path_factory.mktemp("nlpx")
-    lib = str(d / "libnlpx.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, os.path.join(ROOT, "tests", "nlpx", "nlpx.cpp")])
-    L = C.CDLL(lib)
+def nlpx():
+    L = C.CDLL(harness_lib("nlpx"))
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     L.nlpx_solve.argtypes = [C.POINTER(abi.MpcProblemDesc), dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, dp, ip, dp, dp]
     L.nlpx_eval.argtypes = [C.POINTER(abi.MpcProblemDesc), C.c_int32, dp, dp, dp, dp, dp]

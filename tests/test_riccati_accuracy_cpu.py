@@ -18,16 +18,14 @@ that in long double (see ILL below for the figures) and are held to 1 % of the f
 """
 import collections
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import riccati_ref as R
+from helpers import harness_lib
 from riccati_ref import PATHS, check_counts, decoupled_zeros_exact, judge, plain_errors, family_key
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ---- the batch, its reference and its plain twin (shared with the GPU test through this module's helpers) ----------------------------------
 @pytest.fixture(scope="module")
 def batch():
@@ -174,11 +172,8 @@ def test_generator_rejects_few_draws_and_covers_the_schedule(batch):
 
 # ---- 2. the scalar recursion -------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def ricx(tmp_path_factory):
-    d = tmp_path_factory.mktemp("ricx")
-    lib = str(d / "libricx.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, os.path.join(ROOT, "tests", "ricx", "ricx.cpp")])
-    L = C.CDLL(lib)
+def ricx():
+    L = C.CDLL(harness_lib("ricx"))
     dp = C.POINTER(C.c_double)
     L.ricx_run.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_size_t]
     L.ricx_run.restype = C.c_int

@@ -7,27 +7,23 @@ emulation harness and k_solve_wg's scalar fallbacks keep running) only if
      and ric_matrix_step alone the same P_k and gains;
   2. ric_store_matrix and ric_store_vector together write exactly the rows ric_store_stage writes, the same bits, each row by one of them
      (a 16-byte row pair never by both -- the two waves' stores land in no defined order).
-Harness: tests/ricsplitx/ricsplitx.cpp, built here with g++.  Everything is compared as bit patterns; the workspace images start as a NaN with a
+Harness: tests/ricsplitx/ricsplitx.cpp, built with g++ (helpers.harness_lib).  Everything is compared as bit patterns; the workspace images start as a NaN with a
 payload no computation produces, so "written" is "no longer the sentinel".
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers import harness_lib
+
 SENTINEL = np.uint64(0x7FF8DEADBEEF1234)
 N_HORIZON = 6
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("ricsplitx")
-    path = str(d / "libricsplitx.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", path, os.path.join(ROOT, "tests", "ricsplitx", "ricsplitx.cpp")])
-    L = C.CDLL(path)
+def lib():
+    L = C.CDLL(harness_lib("ricsplitx"))
     dp = C.POINTER(C.c_double)
     L.ricsplit_image_doubles.restype = C.c_long
     L.ricsplit_row_index.restype = C.c_long

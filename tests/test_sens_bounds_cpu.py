@@ -2,8 +2,8 @@
 (DESIGN.md section 13).
 
 tests/sens_bounds_ref.py (the active-set reduced KKT of tests/sens_ref.py with the bounds' right-hand side) is checked against central
-differences of the C oracle's re-solves; tests/sensboundx/sensboundx.cpp steps the kernels' own phase functions on the CPU and then runs the
-functions k_sens_bounds runs on the GPU (csrc/mpc_sens.h), checked against that reference."""
+differences of the C oracle's re-solves; tests/sensx/sensx.cpp (sensboundx_solve) steps the kernels' own phase functions on the CPU and then runs the
+functions k_sens<NX, SensFamBounds> runs on the GPU (csrc/mpc_sens.h), checked against that reference."""
 import ctypes as C
 import os
 import re
@@ -12,7 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import CA_CFG, ROOT, WEIGHTS_ZAM_LF, BicycleNLP, NLPConfig, abi, ca_batch, emu_desc, synthetic_batch
+from helpers import CA_CFG, ROOT, WEIGHTS_ZAM_LF, BicycleNLP, NLPConfig, abi, ca_batch, emu_desc, harness_lib, synthetic_batch
 from oracle.binding import OracleSolver
 import sens_ref
 import sens_bounds_ref as bref
@@ -130,11 +130,8 @@ def test_reference_lam_bounds_is_the_gradient_of_the_optimal_objective(oracle_op
 
 # ---- the kernel's math on the CPU -----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def sensboundx(tmp_path_factory):
-    d = tmp_path_factory.mktemp("sensboundx")
-    lib = str(d / "libsensboundx.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, os.path.join(ROOT, "tests", "sensboundx", "sensboundx.cpp")])
-    L = C.CDLL(lib)
+def sensboundx():
+    L = C.CDLL(harness_lib("sensx"))
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     L.sensboundx_solve.argtypes = [C.POINTER(abi.MpcProblemDesc), dp, dp, dp, dp, C.c_int32, dp, dp, dp, ip, dp, dp, C.c_int32, dp, dp, dp, dp, dp, ip, ip]
     return L

@@ -1,8 +1,8 @@
 """CPU: the derivative of the optimum with respect to the obstacle centres behind mpc_sens_obst.
 
 tests/sens_obst_ref.py (the active-set reduced KKT of tests/sens_ref.py with the obstacle right-hand side) is checked against central
-differences of the C oracle's solves; tests/sensobstx/sensobstx.cpp steps the kernels' own phase functions on the CPU with per-instance
-obstacle rows and then runs the functions k_sens_obst runs on the GPU (csrc/mpc_sens.h), checked against that reference."""
+differences of the C oracle's solves; tests/sensx/sensx.cpp (sensobstx_solve) steps the kernels' own phase functions on the CPU with per-instance
+obstacle rows and then runs the functions k_sens<NX, SensFamObst> runs on the GPU (csrc/mpc_sens.h), checked against that reference."""
 import ctypes as C
 import os
 import re
@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import CA_CFG, FAMILIES, ROOT, BicycleNLP, abi, ca_batch, emu_desc, synthetic_batch
+from helpers import CA_CFG, FAMILIES, ROOT, BicycleNLP, abi, ca_batch, emu_desc, harness_lib, synthetic_batch
 from oracle.binding import OracleSolver
 import sens_obst_ref
 import sens_ref
@@ -94,11 +94,8 @@ def test_reference_lam_obst_is_the_gradient_of_the_optimal_objective(oracle_opti
 
 # ---- 3. the kernel's math on the CPU ----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def sensobstx(tmp_path_factory):
-    d = tmp_path_factory.mktemp("sensobstx")
-    lib = str(d / "libsensobstx.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, os.path.join(ROOT, "tests", "sensobstx", "sensobstx.cpp")])
-    L = C.CDLL(lib)
+def sensobstx():
+    L = C.CDLL(harness_lib("sensx"))
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     L.sensobstx_solve.argtypes = [C.POINTER(abi.MpcProblemDesc), dp, dp, dp, dp, C.c_int32, dp, dp, dp, dp, ip, dp, dp, C.c_int32, dp, dp, dp, dp,
                                   dp, ip, ip]

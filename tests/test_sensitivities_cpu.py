@@ -2,7 +2,7 @@
 
 tests/sens_ref.py (the active-set reduced KKT of the numpy NLP) is checked against central finite differences of the C oracle's solves at
 golden optima; tests/sensx/sensx.cpp steps the kernels' own phase functions on the CPU and then runs the functions k_sens_gather,
-k_sens_lam_p and k_sens_factor_solve run on the GPU (csrc/mpc_sens.h), checked against that reference."""
+k_sens_lam_p and k_sens<NX, SensFamP> run on the GPU (csrc/mpc_sens.h), checked against that reference."""
 import ctypes as C
 import os
 import re
@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import CA_CFG, FAMILIES, ROOT, BicycleNLP, abi, ca_batch, cfg_from_golden, emu_desc, synthetic_batch
+from helpers import CA_CFG, FAMILIES, ROOT, BicycleNLP, abi, ca_batch, cfg_from_golden, emu_desc, harness_lib, synthetic_batch
 from oracle.binding import OracleSolver
 import sens_ref
 
@@ -87,11 +87,8 @@ def test_reference_lam_p_is_the_parameter_gradient_of_the_lagrangian():
 
 # ---- 2. the kernels' math on the CPU ---------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def sensx(tmp_path_factory):
-    d = tmp_path_factory.mktemp("sensx")
-    lib = str(d / "libsensx.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", lib, os.path.join(ROOT, "tests", "sensx", "sensx.cpp")])
-    L = C.CDLL(lib)
+def sensx():
+    L = C.CDLL(harness_lib("sensx"))
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     L.sensx_solve.argtypes = [C.POINTER(abi.MpcProblemDesc), dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, dp, ip, dp, dp, dp, C.c_int32, dp, dp,
                               dp, dp, ip]

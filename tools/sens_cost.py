@@ -4,21 +4,26 @@ adjoint alone (on the snapshot of the last _sens call) | mpc_sens_obst_dev alone
 forward directions (the unit directions of the obstacle centres) | mpc_sens_weights_dev alone on the same snapshot: its adjoint with
 lam_wt, and seven forward directions (the unit directions of the weights) | mpc_sens_bounds_dev alone on the same snapshot: its adjoint with
 lam_bv, and nine forward directions (the limits of the vehicle, the friction limit and the circle radius, each moved at every stage at once).
-Usage (GPU box): python tools/sens_cost.py [B] [family] [reps]"""
+Usage (GPU box): python tools/sens_cost.py [B] [family] [reps] [libmpcgpu.so]     family: a key of helpers.FAMILIES, or `ca` (the collision-avoidance
+configuration of the tests); a library path measures that build instead of the package's own (a parent build, for an A/B of alternating runs)"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import numpy as np
 import torch
-from helpers import FAMILIES, make_solver, set_cfg_bounds
+from helpers import CA_CFG, FAMILIES, ca_batch, make_solver, set_cfg_bounds
 from oracle.nlp_numpy import synthetic_batch
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 fam = sys.argv[2] if len(sys.argv) > 2 else "zamlf_n30_nx6"
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 30
-cfg, kw = FAMILIES[fam]
-x0, p = synthetic_batch(cfg, B, **kw)
-s = make_solver(cfg)
+if fam == "ca":
+    cfg = CA_CFG
+    x0, p = ca_batch(cfg, B)
+else:
+    cfg, kw = FAMILIES[fam]
+    x0, p = synthetic_batch(cfg, B, **kw)
+s = make_solver(cfg, lib_path=sys.argv[4] if len(sys.argv) > 4 else None)
 set_cfg_bounds(s, cfg)
 dev = "cuda"
 nx, nw = cfg.nx, s.n_w
