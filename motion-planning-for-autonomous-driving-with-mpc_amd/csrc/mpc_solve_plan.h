@@ -390,6 +390,32 @@ inline SolvePlan plan_solve(const HostProblem& hp, const Knobs& kn, const PlanSt
     return hp.desc.nx == 5 ? plan_solve_nx<5>(hp, kn, st) : plan_solve_nx<6>(hp, kn, st);
 }
 
+// ---- after the launch: what one solve reports back, and what its caller (solve_dev of mpcgpu.hip) does about the instances that stalled -------
+// a level of the second chance (rescue_dev): the lower bound of the circle rows and the tolerance this solve runs with, in place of the problem's
+struct Level { double ol, tol; };
+struct SolveOutcome {
+    bool async_ok = false;              // the solve was enqueued without host synchronisation: nothing below but `mode` is known
+    int mode = 0;                       // 0: one launch per kernel and iteration, 1: single-launch pipeline (+ k_solve_wg behind it), 2: k_solve_wg alone
+    int iters = 0;                      // iterations done (rounds of the slowest tile / workgroup)
+    uint32_t failed = 0;                // instances that did not converge
+    bool resc_in_kernel = false;        // k_solve_wg ran with the second chance inside (RESC) over EVERY instance of the batch: rescue_dev has nothing to add
+    bool resc_ran = false;              // ... or at least over the instances the pipeline handed over (what stalled inside the pipeline is rescue_dev's)
+    int rescued_in_kernel = 0;          // instances that took the second chance there
+    double prof[6] = {}, res_prof[8] = {}, pipe_prof[8] = {};      // what mpc_get_profile / _resident_profile / _pipeline_profile return
+};
+struct AfterSolve {
+    bool run_rescue;                    // rescue_dev: the instances that are still open get their levels behind the launch
+    bool set_hint, hint;                // PlanState::resc_hint of the handle's next solve (left as it is unless set_hint)
+};
+inline AfterSolve after_solve(const SolvePlan& pl, const SolveOutcome& o) {
+    AfterSolve a{};
+    a.set_hint = pl.rescue;
+    a.hint = o.failed != 0u || o.rescued_in_kernel > 0;
+    // (a launch of k_solve_wg with the second chance inside over the whole batch has given every stalled instance its levels already)
+    a.run_rescue = pl.rescue && o.failed != 0u && !o.resc_in_kernel;
+    return a;
+}
+
 // ---- the rows of one batched solve of B instances as the host solve chain of mpcgpu.hip passes them on: device pointers inside the chain, host
 //      pointers at a host-pointer entry point; null: not given / not asked for.  A new per-solve buffer is a member here, its width in rows()
 //      and a line at the entry point that accepts it.

@@ -2592,7 +2592,8 @@ enum Scratch : int {
     N_SCRATCH
 };
 
-enum FailWord { FAIL_COUNT, FAIL_LOOP_ABORT, FAIL_WORDS };  // d_fail / h_fail: instances of the last solve that did not converge (counted by k_egest); sticky abort word of an asynchronous closed loop
+// d_fail / h_fail: instances that did not converge, counted by k_egest (one launch per kernel) or by every solve of an asynchronous closed loop over its steps (else: PH_FAIL); that loop's sticky abort word
+enum FailWord { FAIL_COUNT, FAIL_LOOP_ABORT, FAIL_WORDS };
 struct mpc_handle {
     HostProblem hp;
     std::string err;
@@ -2616,7 +2617,7 @@ struct mpc_handle {
     bool pipe_disabled = false;        // the handle stays on one launch per kernel: three pipeline launches had to be abandoned (see k_pipeline), or the XCD census failed
     int pipe_aborts = 0;               // pipeline launches of this handle abandoned so far (a solve whose launch is abandoned starts over with one launch per kernel)
     static constexpr int PIPE_ABORTS_MAX = 3;
-    int last_mode = 0;                 // 0: one launch per kernel and iteration, 1: single-launch pipeline (+ k_solve_wg behind it), 2: k_solve_wg alone
+    int last_mode = 0;                 // SolveOutcome::mode of the last solve (keep_outcome)
     int32_t* d_counter = nullptr;      // [MAX_GROUPS][MAX_POLL_IT] instances still running after iteration it
     int32_t* h_counter = nullptr;      // pinned, [MAX_GROUPS][2] (double-buffered per poll)
     hipEvent_t ev_poll[4][2] = {};
@@ -2632,6 +2633,7 @@ struct mpc_handle {
     // profiling
     bool profiling = false;
     bool prof_span = false;             // (mpc_set_profiling(h, 2): the iteration loop of the hybrid solve as ONE span -- no marker between its two kernels)
+    // (of the last solve's MAIN launch, keep_outcome -- but after a second chance behind the launch, solve_dev leaves rescue_dev's LAST LEVEL in res_prof: what mpc_get_resident_profile has always returned then)
     double prof[6] = {0, 0, 0, 0, 0, 0};
     double res_prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // k_solve_wg: ms (profiling only), ran, rounds of the slowest workgroup, workgroups, workgroup-rounds, Riccati sweeps, instance-iterations
     double pipe_prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // k_pipeline: ms (profiling only), launches, rounds, Riccati-wait / stage-wait / stage-busy ms summed over workers, items, stage workers + riccati workers / 1000
@@ -2639,13 +2641,9 @@ struct mpc_handle {
     uint32_t xcd_mask = 0xFFu;          // XCDs seen by k_xcd_census
     std::vector<hipEvent_t> ev_pool;
     uint32_t* d_fail = nullptr;         // FailWord (the loop kernels count into PH_FAIL of their control block instead: solve_front)
-    bool async_loop = false;            // solves are being enqueued by the closed-loop driver without host synchronisation
-    bool async_ok = false;              // ... and the last one really went out that way
-    uint32_t* h_fail = nullptr;         // pinned copy (FAIL_COUNT: of every path, read_head)
+    uint32_t* h_fail = nullptr;         // pinned copy (read by solve_dev_impl behind the one-launch-per-kernel path and by closed_loop_dev behind its asynchronous loop)
     int loop_replayed = 0;              // the last closed loop had to be replayed with host synchronisation per step
-    int rescued_last = 0;               // instances the last solve handed to the second chance (rescue_dev)
-    bool resc_in_kernel = false;        // the last solve ran k_solve_wg with the second chance inside (RESC) over EVERY instance of the batch: rescue_dev has nothing to add
-    bool resc_ran = false;              // ... or at least over the instances the pipeline handed over (what stalled inside the pipeline is rescue_dev's)
+    int rescued_last = 0;               // instances the last solve handed to the second chance, inside its launch and behind it (solve_dev)
     bool resc_hint = false;             // the last solve of this handle had stalled instances: the next one runs k_solve_wg<.., RESC> (option rescue_wg = 1, the default)
     bool attr_set_fq = false;
     bool attr_set = false;              // dynamic-LDS limits of the kernels raised on this handle's device
@@ -2990,13 +2988,19 @@ int mpc_get_profile(const mpc_handle* h, double out[6]) {
 
 }  // extern "C"
 
+// how one solve is called: its stream; a level of the second chance (null: the handle's problem as it is); enqueued by the closed loop without host synchronisation
+struct SolveCall { hipStream_t stream = nullptr; const Level* level = nullptr; bool async = false; };
 // what plan_solve reads of the device, the handle and the call
-static PlanState plan_state(const mpc_handle* h, int32_t B, bool per_inst_obst, bool trace, bool in_rescue) {
+static PlanState plan_state(const mpc_handle* h, int32_t B, bool per_inst_obst, bool trace, const SolveCall& call = {}) {
     PlanState st;
     st.n_cu = h->n_cu; st.xcd_mask = h->xcd_mask;
     st.ws_mailbox = h->ws_mailbox; st.pipe_disabled = h->pipe_disabled; st.resc_hint = h->resc_hint;
-    st.B = B; st.per_inst_obst = per_inst_obst; st.trace = trace; st.in_rescue = in_rescue; st.async_loop = h->async_loop;
+    st.B = B; st.per_inst_obst = per_inst_obst; st.trace = trace; st.in_rescue = call.level != nullptr; st.async_loop = call.async;
     return st;
+}
+// a pipeline launch was abandoned and its work done again with one launch per kernel (pipe_disabled): the next solve tries the pipeline again, PIPE_ABORTS_MAX times at most
+static void count_abandoned_launch(mpc_handle* h) {
+    if (++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;
 }
 // the workspace for Bp rows, with the mailbox section if `mb` (SolvePlan::mailbox)
 static int ensure_ws(mpc_handle* h, size_t Bp, bool mb) {
@@ -3051,18 +3055,17 @@ struct Prof {
         spans.back().second = used - 1;
         open = false;
     }
-    void collect() {
-        for (int i = 0; i < 6; ++i) h->prof[i] = 0;
+    void collect(SolveOutcome& o) {
         if (!h->profiling) return;
         (void)hipDeviceSynchronize();
         for (size_t i = 0; i < kinds.size(); ++i) {
             float ms = 0;
             (void)hipEventElapsedTime(&ms, h->ev_pool[spans[i].first], h->ev_pool[spans[i].second]);
-            if (kinds[i] == 0) { h->prof[0] += ms; h->prof[1] += 1; }
-            else if (kinds[i] == 1) { h->prof[2] += ms; h->prof[3] += 1; }
-            else if (kinds[i] == 3) h->pipe_prof[0] += ms;
-            else if (kinds[i] == 5) h->res_prof[0] += ms;
-            else h->prof[4] += ms;
+            if (kinds[i] == 0) { o.prof[0] += ms; o.prof[1] += 1; }
+            else if (kinds[i] == 1) { o.prof[2] += ms; o.prof[3] += 1; }
+            else if (kinds[i] == 3) o.pipe_prof[0] += ms;
+            else if (kinds[i] == 5) o.res_prof[0] += ms;
+            else o.prof[4] += ms;
         }
     }
 };
@@ -3114,13 +3117,12 @@ template <int NX> static int set_lds_limits(mpc_handle* h, size_t ric_lds) {
 struct Group { int tile0, ntl, nblk, b0, b1; hipStream_t st; bool running; };
 // what the parts of a solve share, built once by solve_front
 struct Solve {
-    mpc_handle* h; hipStream_t stream; SolveIo io; bool in_rescue;      // the call
+    mpc_handle* h; SolveCall call; hipStream_t stream; SolveIo io; SolveOutcome& out;      // the call (stream: call.stream); what it reports back (the path functions, read_head)
     SolvePlan pl; Params P; WsLayout w; Prof prof; Group grp[MAX_GROUPS];
     // the control block of the loop kernels (mpc_solve_plan.h) -- one of the handle's two, which alternate: the start kernel of a solve zeroes the other
     uint32_t* ctl = nullptr;            // one for the next solve, the last workgroup of the loop copies the head of this one into the pinned block
     DevTmp t_wtrace;                    // option wg_trace: n_wtrace rows of four words
     int n_wtrace = 0;
-    int it = 0;                         // iterations done (rounds of the slowest tile / workgroup)
 };
 
 // a zeroed stamp buffer of `n_rows` rows for one call, and its report: the rows come back here, mpc_stamps.h words them
@@ -3148,15 +3150,15 @@ template <int NX> static void launch_wg(Solve& s, const uint32_t* skip_if, const
     Params Pw = s.P;
     Pw.bx = pl.hyb_bx;
     // (the last kernel of the solve: its last workgroup copies the head of the control block into the pinned host block)
-    Pw.fin_ctl = h->async_loop ? nullptr : s.ctl + PIPE_ABORT; Pw.fin_host = h->h_pipe;
+    Pw.fin_ctl = s.call.async ? nullptr : s.ctl + PIPE_ABORT; Pw.fin_host = h->h_pipe;
     if (skip_if != nullptr) Pw.DBG = nullptr;         // (behind the pipeline: a stamp buffer of option pipe_timing is sized for the PIPELINE's workgroups)
     WgRescue rs{h->hp.ol_raw, BOUND_RELAX, 0};
     if (pl.wg_resc) {
         rs.on = 1;
-        h->resc_ran = true;
+        s.out.resc_ran = true;
         // (behind the pipeline the launch sees the instances on the hand-over lists only: one that stalled INSIDE the pipeline is on none of
         //  them and keeps its status for rescue_dev)
-        h->resc_in_kernel = list == nullptr;
+        s.out.resc_in_kernel = list == nullptr;
     }
     // (one wavefront per workgroup -- S * hyb_bx <= 64: checked where the path is chosen; its statistics and the lists' counters: words of the control block)
     const auto kf = wg_kernel<NX>(pl.masked, pl.wg_resc);
@@ -3175,19 +3177,19 @@ static void report_arrivals(const uint32_t* ctl, int ntiles, uint32_t items) {
 // the head of the control block as the loop kernels left it (h_pipe; PipeHeadWord): instances that did not converge, second chances taken inside
 // the launch, the profiles of the kernels that ran
 static void read_head(Solve& s) {
-    mpc_handle* h = s.h; const uint32_t* hd = h->h_pipe;
-    h->h_fail[FAIL_COUNT] = hd[PH_FAIL];
-    if (h->resc_ran && !s.in_rescue) h->rescued_last = (int)hd[PH_WG + WGS_RESCUED];
+    const uint32_t* hd = s.h->h_pipe; SolveOutcome& o = s.out;
+    o.failed = hd[PH_FAIL];
+    if (o.resc_ran) o.rescued_in_kernel = (int)hd[PH_WG + WGS_RESCUED];
     if (s.pl.res_path || s.pl.hand > 0) {          // k_solve_wg (behind the pipeline: the workgroups launched are what the machine holds, dealt from the hand-over lists)
-        h->res_prof[1] = 1; h->res_prof[2] = hd[PH_WG + WGS_ROUNDS_MAX]; h->res_prof[3] = s.pl.wg_grid;
-        h->res_prof[4] = hd[PH_WG + WGS_ROUNDS]; h->res_prof[5] = hd[PH_WG + WGS_SWEEPS]; h->res_prof[6] = hd[PH_WG + WGS_INST_ROUNDS];
+        o.res_prof[1] = 1; o.res_prof[2] = hd[PH_WG + WGS_ROUNDS_MAX]; o.res_prof[3] = s.pl.wg_grid;
+        o.res_prof[4] = hd[PH_WG + WGS_ROUNDS]; o.res_prof[5] = hd[PH_WG + WGS_SWEEPS]; o.res_prof[6] = hd[PH_WG + WGS_INST_ROUNDS];
     }
-    s.it = (int)hd[s.pl.pipe_path ? PH_ROUNDS : PH_WG + WGS_ROUNDS_MAX];
+    o.iters = (int)hd[s.pl.pipe_path ? PH_ROUNDS : PH_WG + WGS_ROUNDS_MAX];
     if (s.pl.pipe_path) {
         const unsigned long long* st64 = reinterpret_cast<const unsigned long long*>(hd + PH_STAT64);
-        h->pipe_prof[1] = 1; h->pipe_prof[2] = s.it;
-        h->pipe_prof[3] = (double)st64[P64_RIC_WAIT] * 1e-5; h->pipe_prof[4] = (double)st64[P64_STAGE_WAIT] * 1e-5; h->pipe_prof[5] = (double)st64[P64_STAGE_BUSY] * 1e-5;   // 100 MHz ticks -> ms
-        h->pipe_prof[6] = (double)st64[P64_ITEMS]; h->pipe_prof[7] = (double)hd[PH_STAGE_WORKERS] + 1e-3 * (double)hd[PH_RIC_WORKERS];
+        o.pipe_prof[1] = 1; o.pipe_prof[2] = o.iters;
+        o.pipe_prof[3] = (double)st64[P64_RIC_WAIT] * 1e-5; o.pipe_prof[4] = (double)st64[P64_STAGE_WAIT] * 1e-5; o.pipe_prof[5] = (double)st64[P64_STAGE_BUSY] * 1e-5;   // 100 MHz ticks -> ms
+        o.pipe_prof[6] = (double)st64[P64_ITEMS]; o.pipe_prof[7] = (double)hd[PH_STAGE_WORKERS] + 1e-3 * (double)hd[PH_RIC_WORKERS];
     }
 }
 
@@ -3201,11 +3203,11 @@ static int solve_front(Solve& s) {
     const size_t Bp = (size_t)ntiles * 64;
     hipStream_t stream = s.stream; Params& P = s.P;
     fill_params(P, h->hp, B, Bp, pl.bx, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
+    if (s.call.level) { P.ol = s.call.level->ol; P.tol = s.call.level->tol; }
     P.mbw_live = 0;
     P.x0 = io.x0; P.p = io.p; P.x_out = io.x_out; P.status_out = io.status; P.iters_out = io.iters; P.kkt_out = io.kkt;
     s.w = ws_layout(d.N, d.nx, Bp, h->ws_mailbox);
     const WsLayout& w = s.w;
-    h->async_ok = false;
     if (io.obst) {
         P.per_inst_obst = 1;
         hipLaunchKernelGGL(k_transpose_obst, dim3((B + 255) / 256), dim3(256), 0, stream, io.obst, h->d_ws + w.OBST * 64, B, (uint32_t)w.tile_elems);
@@ -3235,8 +3237,6 @@ static int solve_front(Solve& s) {
     }
     P.tile_mask = h->d_tile_mask;
     if (pl.polled && pl.cap > MAX_POLL_IT) { h->err = "max_iter exceeds the poll table (1024)"; return MPC_ERR_INVALID; }
-    h->last_mode = 0;
-    for (int i = 0; i < 8; ++i) { h->pipe_prof[i] = 0; h->res_prof[i] = 0; }
     uint32_t* zero_next = nullptr;
     size_t ctl_words = 0;
     bool next_zeroed = false;
@@ -3256,7 +3256,7 @@ static int solve_front(Solve& s) {
         h->pipe_clean[h->pipe_flip] = 0;
         P.emit = 1;
         // (an asynchronous closed loop accumulates the instances that did not converge over its steps in d_fail instead)
-        P.fail_count = h->async_loop ? h->d_fail + FAIL_COUNT : s.ctl + PIPE_ABORT + PH_FAIL;
+        P.fail_count = s.call.async ? h->d_fail + FAIL_COUNT : s.ctl + PIPE_ABORT + PH_FAIL;
     }
     for (int g = 0; g < G; ++g) {
         const Group& q = s.grp[g];
@@ -3296,10 +3296,10 @@ template <int NX> static int solve_wg_alone(Solve& s) {
     s.prof.next(5, s.stream);
     launch_wg<NX>(s, nullptr, nullptr);
     s.prof.end(s.stream);
-    h->last_mode = 2;
-    if (h->async_loop) {             // closed-loop driver: nothing comes back to the host per step (this path has no abort word)
+    s.out.mode = 2;
+    if (s.call.async) {              // closed-loop driver: nothing comes back to the host per step (this path has no abort word)
         HIP_TRY(h, hipGetLastError());
-        h->async_ok = true;
+        s.out.async_ok = true;
         return MPC_OK;
     }
     HIP_TRY(h, wait_stream(h, s.stream));          // (the last workgroup to leave has put the block's head into h_pipe)
@@ -3331,13 +3331,13 @@ template <int NX> static int solve_pipeline(Solve& s) {
         launch_wg<NX>(s, (const uint32_t*)(s.ctl + PIPE_ABORT), A.ho_list);
     }
     s.prof.end(stream);
-    if (h->async_loop) {
+    if (s.call.async) {
         // closed-loop driver: nothing comes back to the host per step -- a launch that had to be abandoned leaves its mark
         // in the loop's sticky abort word, the bookkeeping kernels behind it then do nothing and the host replays the loop
         hipLaunchKernelGGL(k_loop_sticky, dim3(1), dim3(1), 0, stream, (const uint32_t*)(s.ctl + PIPE_ABORT), h->d_fail + FAIL_LOOP_ABORT);
         HIP_TRY(h, hipGetLastError());
-        h->async_ok = true;
-        h->last_mode = 1;
+        s.out.async_ok = true;
+        s.out.mode = 1;
         return MPC_OK;
     }
     // (no kernel behind the loop: the rows are out -- Params::emit -- and k_solve_wg has left the block's head in h_pipe; a pipeline that
@@ -3352,8 +3352,7 @@ template <int NX> static int solve_pipeline(Solve& s) {
         // through an iteration, so start over with one launch per kernel.  Once may be a transient of the machine's other tenants (the
         // workgroups of a collective spinning on a slow peer, another handle's persistent launch); the handle stays on that path when it
         // has happened PIPE_ABORTS_MAX times
-        h->pipe_disabled = true;
-        h->resc_in_kernel = h->resc_ran = false;         // (the k_solve_wg behind the abandoned launch returned at once: no instance has had its second chance)
+        h->pipe_disabled = true;                        // (the outcome is dropped with the launch: the k_solve_wg behind it returned at once, no instance has had its second chance)
         // (abort word: 1 option pipe_test_abort, 2 a Riccati worker waited for its tile's stage items [tile << 16 | round; arrivals], 3 a helping
         //  Riccati worker / 4 a stage worker waited for its queue slot [ticket; queue tail]; then the PH_DETAIL words)
         fprintf(stderr, "[mpcgpu] single-launch pipeline abandoned (bounded wait expired: code %u, %u / %u, a millisecond later %u, waited %u ticks); re-running with one launch per kernel\n",
@@ -3363,7 +3362,7 @@ template <int NX> static int solve_pipeline(Solve& s) {
     }
     P.DBG = nullptr;
     if (t_pdbg.p) HIP_TRY(h, report_stamps(t_pdbg.as<unsigned long long>(), (size_t)STAMP_SLOTS * h->n_cu, [&](const unsigned long long* r) { return format_pipe_timing(r, h->n_cu); }));
-    h->last_mode = 1;
+    s.out.mode = 1;
     return MPC_OK;
 }
 
@@ -3387,14 +3386,14 @@ template <int NX> static int solve_per_kernel(Solve& s) {
     const SolvePlan& pl = s.pl;
     const int B = s.io.B, G = pl.G, nblk = pl.nblk;
     hipStream_t stream = s.stream; Params& P = s.P;
-    int& it = s.it;
+    int& it = s.out.iters;
     DevTmp t_trace, t_dbg;               // the trace's device copy; stamps of option timing = 1 (third / fourth iteration)
     if (trace) HIP_TRY(h, hipMalloc(&t_trace.p, sizeof(double) * 8 * (size_t)B));
     if (pl.stage_timing) HIP_TRY(h, stamp_rows(t_dbg, nblk, stream));
     unsigned long long* const d_dbg = t_dbg.as<unsigned long long>();
     // the poll table of this solve and (unless an asynchronous closed loop accumulates over its steps) the count of instances that do not
     // converge start from zero -- the other paths keep both in their control block
-    if (!h->async_loop) HIP_TRY(h, hipMemsetAsync(h->d_fail + FAIL_COUNT, 0, sizeof(uint32_t), stream));
+    if (!s.call.async) HIP_TRY(h, hipMemsetAsync(h->d_fail + FAIL_COUNT, 0, sizeof(uint32_t), stream));
     if (pl.polled) HIP_TRY(h, hipMemsetAsync(h->d_counter, 0, sizeof(int32_t) * MAX_GROUPS * MAX_POLL_IT, stream));
     if (G > 1) {     // the sub-streams were forked before these memsets were enqueued
         HIP_TRY(h, hipEventRecord(h->ev_fork, stream));
@@ -3478,9 +3477,10 @@ template <int NX> static int solve_per_kernel(Solve& s) {
 }
 
 template <int NX>
-static int solve_dev_impl(mpc_handle* h, const SolveIo& io, hipStream_t stream, bool in_rescue) {
-    Solve s{h, stream, io, in_rescue}; s.prof.h = h; s.prof.s = stream;
-    PlanState ps = plan_state(h, io.B, io.obst != nullptr, io.trace.out != nullptr, in_rescue);
+static int solve_dev_impl(mpc_handle* h, const SolveIo& io, const SolveCall& call, SolveOutcome& out) {
+    out = SolveOutcome{};
+    Solve s{h, call, call.stream, io, out}; s.prof.h = h; s.prof.s = call.stream;
+    PlanState ps = plan_state(h, io.B, io.obst != nullptr, io.trace.out != nullptr, call);
     s.pl = plan_solve(h->hp, h->knobs, ps);
     // tile-major layout: the rows of a tile do not depend on the batch size, so a smaller batch lives in the first tiles of
     // a larger allocation (grow-only; the rescue path alternates between the full batch and a failed subset)
@@ -3489,20 +3489,22 @@ static int solve_dev_impl(mpc_handle* h, const SolveIo& io, hipStream_t stream, 
     if ((rc = solve_front<NX>(s))) return rc;
     rc = s.pl.res_path ? solve_wg_alone<NX>(s) : s.pl.pipe_path ? solve_pipeline<NX>(s) : solve_per_kernel<NX>(s);
     if (rc == PIPE_ABANDONED) {          // (pipe_disabled: the second call plans one launch per kernel)
-        rc = solve_dev_impl<NX>(h, io, stream, in_rescue);
-        if (++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;
+        rc = solve_dev_impl<NX>(h, io, call, out);
+        count_abandoned_launch(h);
         return rc;
     }
-    if (rc || h->async_ok) return rc;
+    if (rc || out.async_ok) return rc;
     // the back: iterations for the caller, the spans of the profile
-    if (io.trace.n_it) *io.trace.n_it = s.it;
+    if (io.trace.n_it) *io.trace.n_it = out.iters;
     HIP_TRY(h, hipGetLastError());
-    if (h->hp.desc.fixed_iters <= 0 || h->profiling) HIP_TRY(h, hipStreamSynchronize(stream));
-    s.prof.collect();
-    h->prof[5] = s.it;
+    const bool synced = h->hp.desc.fixed_iters <= 0 || h->profiling;
+    if (synced) HIP_TRY(h, hipStreamSynchronize(call.stream));
+    if (synced && !s.pl.res_path && !s.pl.pipe_path) out.failed = h->h_fail[FAIL_COUNT];       // (one launch per kernel: k_egest's count has arrived only now; the loop kernels' came with the head)
+    s.prof.collect(out);
+    out.prof[5] = out.iters;
     return MPC_OK;
 }
-static int solve_dev_any(mpc_handle* h, const SolveIo& io, hipStream_t stream, bool in_rescue) { FOR_NX(h, return solve_dev_impl<NX>(h, io, stream, in_rescue)); }
+static int solve_dev_any(mpc_handle* h, const SolveIo& io, const SolveCall& call, SolveOutcome& out) { FOR_NX(h, return solve_dev_impl<NX>(h, io, call, out)); }
 
 // ---- multipliers of a solve (mpc_solve_batch_ex): read back from the workspace behind the solve, the loop kernels are not touched -------
 // Before a solve whose multipliers will be read: the workspace in place (what solve_dev_impl would allocate) and the mailbox copy of the
@@ -3510,7 +3512,7 @@ static int solve_dev_any(mpc_handle* h, const SolveIo& io, hipStream_t stream, b
 static int mult_prepare(mpc_handle* h, int32_t B, hipStream_t stream) {
     const mpc_problem_desc& d = h->hp.desc;
     const size_t Bp = ((size_t)B + 63) / 64 * 64;
-    const int rc = ensure_ws(h, Bp, plan_solve(h->hp, h->knobs, plan_state(h, B, false, false, false)).mailbox);
+    const int rc = ensure_ws(h, Bp, plan_solve(h->hp, h->knobs, plan_state(h, B, false, false)).mailbox);
     if (rc) return rc;
     if (h->ws_mailbox) {
         const WsLayout w = ws_layout(d.N, d.nx, Bp, true);
@@ -3542,14 +3544,13 @@ static int sens_read(mpc_handle* h, const SolveIo& io, const int32_t* idx, hipSt
 // one that converged; the last level is the ORIGINAL problem, so what is written back is a KKT point of the original NLP to the
 // original tolerance -- or nothing (the original failure stays).  Two passes: levels {0, 1}, then {0, 0.4, 0.7, 0.9, 1} for
 // what is still open.  Everything stays in device memory; the only host traffic is the count of open instances.
-static int rescue_dev(mpc_handle* h, const SolveIo& io, hipStream_t stream) {
+// n_first (0 as it comes in): the instances the first pass took; last_level: the outcome of the last level that ran (untouched while n_first is 0).
+static int rescue_dev(mpc_handle* h, const SolveIo& io, hipStream_t stream, int& n_first, SolveOutcome& last_level) {
     const int32_t B = io.B;
     int32_t* idx = static_cast<int32_t*>(scratch_get(h, SCR_RESC_IDX, ((size_t)B + 1) * 4));
     if (!idx) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
     int32_t* cnt = idx + B;
     static const double pass1[] = {0.0, 1.0}, pass2[] = {0.0, 0.4, 0.7, 0.9, 1.0};
-    const double ol_keep = h->hp.ol, tol_keep = h->hp.desc.tol;
-    h->rescued_last = 0;
     int rc = MPC_OK;
     for (int pass = 0; pass < 2 && rc == MPC_OK; ++pass) {
         hipLaunchKernelGGL(k_rescue_select, dim3(1), dim3(1024), 0, stream, io.status, B, idx, cnt);
@@ -3581,37 +3582,43 @@ static int rescue_dev(mpc_handle* h, const SolveIo& io, hipStream_t stream) {
         }
         for (int q = 0; q < nfr && rc == MPC_OK; ++q) {
             const bool last = q + 1 == nfr;             // (the original problem; the levels before it only produce warm starts)
-            h->hp.ol = relax_lo(fr[q] * h->hp.ol_raw);
-            h->hp.desc.tol = last ? tol_keep : std::max(tol_keep, 1e-4);
+            // (... as hp holds it: relax_lo(1.0 * ol_raw) is hp.ol by set_bound_rows, the tolerance hp.desc.tol -- so mult_prepare, mult_read and
+            //  sens_read, which build their Params from hp, read the last level's solve with the bound and the tolerance it ran with)
+            const Level level{relax_lo(fr[q] * h->hp.ol_raw), last ? h->hp.desc.tol : std::max(h->hp.desc.tol, 1e-4)};
             if ((sub.lam_g || sub.snap) && last) rc = mult_prepare(h, n, stream);
             if (rc != MPC_OK) break;
-            rc = solve_dev_any(h, sub, stream, true);
+            rc = solve_dev_any(h, sub, SolveCall{stream, &level, false}, last_level);
             if (rc == MPC_OK && sub.lam_g && last) rc = mult_read(h, sub, stream);
             if (rc == MPC_OK && sub.snap && last) rc = sens_read(h, sub, idx, stream);
             if (rc == MPC_OK) hipLaunchKernelGGL(k_rescue_carry, dim3(n), dim3(128), 0, stream, (int)nw, sub.status, sub.iters, sub.x_out, xs, acc);
         }
-        h->hp.ol = ol_keep; h->hp.desc.tol = tol_keep;
         if (rc == MPC_OK)
             hipLaunchKernelGGL(k_rescue_scatter, dim3(n), dim3(128), 0, stream, idx, (int)nw, sub.status, sub.x_out, sub.kkt, acc, io.x_out, io.status, io.iters, io.kkt);
         if (rc == MPC_OK && sub.lam_g)
             hipLaunchKernelGGL(k_rescue_scatter_mult, dim3(n), dim3(128), 0, stream, idx, (int)nw, (int)ng, sub.status, sub.lam_g, sub.lam_x, io.lam_g, io.lam_x);
-        if (pass == 0) h->rescued_last = n;
+        if (pass == 0) n_first = n;
     }
-    h->hp.ol = ol_keep; h->hp.desc.tol = tol_keep;
     if (rc == MPC_OK) { HIP_TRY(h, hipGetLastError()); HIP_TRY(h, hipStreamSynchronize(stream)); }
     return rc;
+}
+
+static void keep_outcome(mpc_handle* h, const SolveOutcome& o) {      // what the handle goes on telling about a solve after the call (mpc_get_profile & co.)
+    h->last_mode = o.mode;
+    memcpy(h->pipe_prof, o.pipe_prof, sizeof o.pipe_prof);
+    memcpy(h->res_prof, o.res_prof, sizeof o.res_prof);
+    if (!o.async_ok) memcpy(h->prof, o.prof, sizeof o.prof);         // (a solve that was only enqueued has measured nothing)
 }
 
 // One solve behind an entry point that has begun it (begin_solve): chunks, the multipliers and the snapshot behind the launch, the second chance.
 static int solve_dev(mpc_handle* h, SolveIo io, hipStream_t stream) {
     const int32_t B = io.B;
     h->rescued_last = 0;
-    const SolvePlan pl = plan_solve(h->hp, h->knobs, plan_state(h, B, io.obst != nullptr, io.trace.out != nullptr, false));
+    const SolvePlan pl = plan_solve(h->hp, h->knobs, plan_state(h, B, io.obst != nullptr, io.trace.out != nullptr));
     // the second chance and the multipliers read the per-instance status
     if (pl.rescue || io.lam_g) { const int rs = supply_status(h, io); if (rs) return rs; }
     // The workspace is addressed with 32-bit buffer offsets (< 4 GiB): a batch beyond that is solved in chunks of whole tiles, one after
     // the other on the same stream (instances are independent; the rows of a chunk are a contiguous slice of every caller buffer).
-    if ((size_t)B > pl.max_rows && !io.trace.out && !h->async_loop) {
+    if ((size_t)B > pl.max_rows && !io.trace.out) {
         int rescued = 0;
         for (size_t off = 0; off < (size_t)B; off += pl.max_rows) {
             const int rcc = solve_dev(h, io.rows(off, (int32_t)std::min(pl.max_rows, (size_t)B - off)), stream);
@@ -3621,27 +3628,22 @@ static int solve_dev(mpc_handle* h, SolveIo io, hipStream_t stream) {
         h->rescued_last = rescued;
         return MPC_OK;
     }
-    h->resc_in_kernel = h->resc_ran = false;
     if (io.lam_g || io.snap) { const int rm = mult_prepare(h, B, stream); if (rm) return rm; }
-    int rc = solve_dev_any(h, io, stream, false);
+    SolveOutcome out;
+    int rc = solve_dev_any(h, io, SolveCall{stream}, out);
+    keep_outcome(h, out);
+    h->rescued_last = out.rescued_in_kernel;
     if (rc == MPC_OK && io.lam_g) rc = mult_read(h, io, stream);
     if (rc == MPC_OK && io.snap) rc = sens_read(h, io, nullptr, stream);
-    // (converged mode: the solve has synchronised the stream; a launch of k_solve_wg with the second chance inside has given every stalled
-    //  instance its levels already)
-    // (what the next solve of this handle does about stalled instances: see resc_cond in plan_solve)
-    if (rc == MPC_OK && pl.rescue && !h->async_ok) h->resc_hint = h->h_fail[FAIL_COUNT] != 0u || h->rescued_last > 0;
-    if (rc != MPC_OK || !pl.rescue || h->h_fail[FAIL_COUNT] == 0u || h->resc_in_kernel) return rc;
-    double prof_keep[6], pipe_keep[8];
-    const int mode_keep = h->last_mode;
-    memcpy(prof_keep, h->prof, sizeof prof_keep);
-    memcpy(pipe_keep, h->pipe_prof, sizeof pipe_keep);
-    const int in_kernel = h->rescued_last;                  // (instances that had their second chance inside k_solve_wg already)
-    const int rr = rescue_dev(h, io, stream);
-    h->rescued_last += in_kernel;
-    memcpy(h->prof, prof_keep, sizeof prof_keep);          // the measurement helpers describe the main solve
-    memcpy(h->pipe_prof, pipe_keep, sizeof pipe_keep);
-    h->last_mode = mode_keep;
-    return rr;
+    if (rc != MPC_OK) return rc;
+    const AfterSolve after = after_solve(pl, out);      // (a solve that may need it runs in converged mode and has synchronised the stream)
+    if (after.set_hint) h->resc_hint = after.hint;      // (what the next solve of this handle does about stalled instances: see resc_cond in plan_solve)
+    if (!after.run_rescue) return MPC_OK;
+    int n_first = 0; SolveOutcome level;        // (the levels are solves of their own: the handle goes on describing the main one -- but see mpc_handle::res_prof)
+    rc = rescue_dev(h, io, stream, n_first, level);
+    h->rescued_last += n_first;
+    if (n_first > 0) memcpy(h->res_prof, level.res_prof, sizeof level.res_prof);
+    return rc;
 }
 
 static int ensure_io(mpc_handle* h, size_t B) {
@@ -3975,20 +3977,20 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
     // that needs the second chance -- is recorded on the device and looked at ONCE, at the end; then the loop is replayed
     // step by step with the host in between (the per-kernel path polls for convergence, the second chance needs the count).
     bool replay = true, loop_abandoned = false;
-    if (plan_solve(h->hp, h->knobs, plan_state(h, B, track != nullptr, false, false)).loop_async) {
+    if (plan_solve(h->hp, h->knobs, plan_state(h, B, track != nullptr, false)).loop_async) {
         HIP_TRY(h, hipMemsetAsync(h->d_fail, 0, FAIL_WORDS * sizeof(uint32_t), stream));
         A.abort_flag = O.abort_flag = h->d_fail + FAIL_LOOP_ABORT;
         hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
-        h->async_loop = true;
         bool all_async = true;
+        SolveOutcome out;
         for (int i = 0; i < L && all_async; ++i) {
             place_obstacles(i);
-            rc = solve_dev_any(h, io, stream, false);
-            if (rc) { h->async_loop = false; return rc; }
-            all_async = h->async_ok;             // (a batch shape the pipeline does not take: the solve has run synchronously -- start over)
+            rc = solve_dev_any(h, io, SolveCall{stream, nullptr, true}, out);
+            if (rc) return rc;
+            all_async = out.async_ok;            // (a batch shape the pipeline does not take: the solve has run synchronously -- start over)
             if (all_async) hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
         }
-        h->async_loop = false;
+        keep_outcome(h, out);
         if (all_async) {
             HIP_TRY(h, hipMemcpyAsync(h->h_fail, h->d_fail, FAIL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             HIP_TRY(h, hipStreamSynchronize(stream));
@@ -4011,7 +4013,7 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
             hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
         }
     }
-    if (loop_abandoned && ++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;         // (see solve_dev_impl)
+    if (loop_abandoned) count_abandoned_launch(h);
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }

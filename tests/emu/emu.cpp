@@ -66,6 +66,17 @@ extern "C" int emu_solve_plan(const mpc_problem_desc* desc, const double* lbx, c
     return MPC_OK;
 }
 
+// what solve_dev does behind a launch (mpc_solve_plan.h: after_solve): in = [pl.rescue, failed, resc_ran, resc_in_kernel, rescued_in_kernel];
+// out = [run_rescue, set_hint, hint]
+extern "C" void emu_after_solve(const int64_t* in, int64_t* out) {
+    SolvePlan pl{};
+    pl.rescue = in[0] != 0;
+    SolveOutcome o;
+    o.failed = (uint32_t)in[1]; o.resc_ran = in[2] != 0; o.resc_in_kernel = in[3] != 0; o.rescued_in_kernel = (int)in[4];
+    const AfterSolve a = after_solve(pl, o);
+    out[0] = a.run_rescue; out[1] = a.set_hint; out[2] = a.hint;
+}
+
 // closed-loop driver pieces (mpc_closed_loop.h) on host arrays: mode 0 = setup, 1 = advance after step i
 extern "C" int emu_closed_loop_piece(int32_t mode, int32_t i, double dt, double wheelbase, int32_t B, int32_t N, int32_t L, int32_t Lp,
                                      const double* init_state, const double* path, const double* orient, const double* vdes,

@@ -590,6 +590,29 @@ def test_second_chance_behind_the_pipeline_with_one_instance_per_wavefront():
         assert a.iters[i] > plain.iters[i]
 
 
+@pytest.mark.parametrize("B", [1024, 4096])
+def test_getters_describe_the_main_solve_after_a_second_chance(B):
+    """The levels of the host-side second chance (rescue_dev) are solves of their own; what the handle reports afterwards -- iterations, the
+    pipeline's profile -- is still the main solve's.  Collision avoidance on two fresh handles, one without the second chance: B = 1024 is
+    k_solve_wg alone, B = 4096 the pipeline with k_solve_wg behind it.  The rows of the instances that needed no second chance are the same
+    bits."""
+    x0, p = ca_batch(CA_CFG, B)
+    plain_s, s = make_solver(CA_CFG), make_solver(CA_CFG)
+    for h in (plain_s, s):
+        set_cfg_bounds(h, CA_CFG)
+    plain_s.set_option("rescue", "0")
+    plain = plain_s.solve(x0, p)
+    r = s.solve(x0, p)
+    pp0, pp = plain_s.get_pipeline_profile(), s.get_pipeline_profile()
+    print(B, "rescued", s.last_rescued(), plain_s.get_profile(), s.get_profile(), pp0, pp)
+    assert pp0["ran"] == (B == 4096)
+    assert plain_s.last_rescued() == 0 and s.last_rescued() > 0
+    assert s.get_profile()["iterations"] == plain_s.get_profile()["iterations"]
+    assert pp["ran"] == pp0["ran"] and pp["rounds"] == pp0["rounds"]
+    home = plain.status == 1
+    assert home.sum() < B and np.array_equal(r.x[home], plain.x[home]) and np.array_equal(r.iters[home], plain.iters[home])
+
+
 def test_fixed_iteration_mode_matches_converged():
     cfg, kw = FAMILIES["zamlf_n30_nx6"]
     x0, p = synthetic_batch(cfg, 512, **kw)

@@ -163,6 +163,38 @@ def test_plan_options_are_parsed_like_mpc_set_option():
         plan(LF30, 4096, {"no_such_option": "1"})
 
 
+# ---- behind the launch (after_solve): the second chance behind it, the hint for the handle's next solve --------------------------------
+# (id, pl.rescue, outcome: failed, resc_ran, resc_in_kernel, rescued_in_kernel; expected: run_rescue, set_hint, hint -- None: not written).
+# Read off solve_dev as it stood before the decision was extracted; a fix of ADVICE.md's findings about this region shows as a changed row.
+AFTER_ROWS = [
+    # every instance converged, none stalled on the way: nothing to do, the next solve needs no second chance inside its launch
+    ("clean", 1, (0, 0, 0, 0), (0, 1, 0)),
+    # instances left open and no second chance inside the launch: rescue_dev gives them their levels; the next solve takes the kernel that has it
+    ("failed", 1, (3, 0, 0, 0), (1, 1, 1)),
+    # k_solve_wg<.., RESC> alone over every instance: what is still open has had its levels -- rescue_dev would only repeat them
+    ("failed_in_kernel", 1, (3, 1, 1, 5), (0, 1, 1)),
+    # ... behind the pipeline it saw the handed-over instances only: one that stalled inside the pipeline is still rescue_dev's
+    ("failed_behind_pipeline", 1, (2, 1, 0, 4), (1, 1, 1)),
+    # all home, some through the second chance inside the launch: the family stalls, the hint stays
+    ("rescued_in_kernel", 1, (0, 1, 1, 7), (0, 1, 1)),
+    # no second chance for this solve (option rescue = 0, a fixed iteration count, a trace, no circle rows): the handle's hint is left alone
+    ("no_rescue", 0, (3, 0, 0, 0), (0, 0, None)),
+]
+
+
+@pytest.mark.parametrize("row", AFTER_ROWS, ids=[r[0] for r in AFTER_ROWS])
+def test_after_solve_table(row):
+    _, rescue, outcome, want = row
+    L = emu_lib()
+    L.emu_after_solve.argtypes = [C.POINTER(C.c_int64)] * 2
+    L.emu_after_solve.restype = None
+    inp, out = np.array((rescue,) + outcome, np.int64), np.zeros(3, np.int64)
+    L.emu_after_solve(inp.ctypes.data_as(C.POINTER(C.c_int64)), out.ctypes.data_as(C.POINTER(C.c_int64)))
+    got = (int(out[0]), int(out[1]), int(out[2]) if out[1] else None)
+    print(row[0], got)
+    assert got == want
+
+
 # ---- the GPU: what the library reports after one solve of each row on a fresh handle ----------------------------------------------------
 
 def gpu_workers(p, n_cu):
