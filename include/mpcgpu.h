@@ -66,7 +66,9 @@ extern "C" {
 typedef struct mpc_handle mpc_handle;
 
 typedef struct mpc_problem_desc {
-    int32_t N;             /* predict_horizon (optimizer.py:520); 1 <= N <= 127                          */
+    int32_t N;             /* predict_horizon (optimizer.py:520); 1 <= N <= 127 for the NLP entry points,
+                              <= 192 for the FORCES-mode solve; a handle of a longer horizon is refused
+                              (MPC_ERR_INVALID) by the entry points that cannot run it                    */
     int32_t nx;            /* 5 = reference state [x, y, delta, v, psi]; 6 appends a decoupled progress
                               state s (s' = v, no weight, unbounded) used by the synthetic benchmark      */
     int32_t nu;            /* must be 2: [deltaDot, aLong]                                                */
@@ -301,7 +303,7 @@ int mpc_forces_stage_eval(mpc_handle* h, int32_t B, int32_t terminal, const doub
  * (optimizer.py:326; C side FORCESNLPsolver_solve, test/FORCESNLPsolver/include/FORCESNLPsolver.h:117-219) for B independent
  * problems: ONE step of sequential quadratic programming from the guess x0, as the reference configures FORCESPRO
  * (sqp_nlp.maxqps = 1, BFGS initialised to 2.5 I, reg_hessian 5e-6; optimizer.py:225-240).  Horizon N = the descriptor's
- * N, weights Q / R / P of the descriptor.  x0 [B,N,7] = problem["x0"], xinit [B,5], all_parameters [B,N,10] (optimizer.py:
+ * N (at most 192), weights Q / R / P of the descriptor.  x0 [B,N,7] = problem["x0"], xinit [B,5], all_parameters [B,N,10] (optimizer.py:
  * 124-127, 313-318); lb/ub [7], hl/hu [10] = inequal_constraint() (optimizer.py:100-119; +-inf or |v| >= 1e300 = absent).
  * hessian_mode 0: QP Hessian = exact Hessian of the least-squares cost (Gauss-Newton SQP, default); 1: the literal
  * `bfgs_init = 2.5 I` (see csrc/mpc_forces_qp.h: forces_hessian_diag for why that is not the default).

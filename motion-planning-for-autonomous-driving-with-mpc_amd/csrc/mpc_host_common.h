@@ -47,9 +47,13 @@ inline void apply_fric_literal(HostProblem& hp, int literal) {
 inline double relax_lo(double lo) { return std::isfinite(lo) ? lo - BOUND_RELAX * std::fmax(1.0, std::fabs(lo)) : -INFINITY; }
 inline double relax_hi(double hi) { return std::isfinite(hi) ? hi + BOUND_RELAX * std::fmax(1.0, std::fabs(hi)) : INFINITY; }
 
-inline int validate_desc(const mpc_problem_desc& d, std::string& err) {
+// Horizons: the NLP solve and everything around it (one thread per stage in workgroups of at most 512 threads, bx = 4) go up to MAX_N_NLP; the
+// FORCES-mode solve has a limit of its own (mpc_forces_solve_batch_dev).  A HANDLE may be created for any horizon up to MAX_N_HANDLE -- every
+// entry point then refuses the horizons it cannot run, with its own message.
+constexpr int MAX_N_NLP = 127, MAX_N_HANDLE = 1024;
+inline int validate_desc(const mpc_problem_desc& d, std::string& err, int max_N = MAX_N_NLP) {
     char buf[256];
-    if (d.N < 1 || d.N > 127) { snprintf(buf, sizeof buf, "N=%d outside [1,127]", d.N); err = buf; return MPC_ERR_INVALID; }
+    if (d.N < 1 || d.N > max_N) { snprintf(buf, sizeof buf, "N=%d outside [1,%d]", d.N, max_N); err = buf; return MPC_ERR_INVALID; }
     if (d.nx != 5 && d.nx != 6) { snprintf(buf, sizeof buf, "nx=%d (supported: 5, 6)", d.nx); err = buf; return MPC_ERR_INVALID; }
     if (d.nu != 2) { err = "nu must be 2"; return MPC_ERR_INVALID; }
     if (d.formulation != MPC_FORM_CASADI_EULER) { err = "unsupported formulation"; return MPC_ERR_INVALID; }
@@ -195,7 +199,7 @@ inline WsLayout ws_layout(int N, int nx, size_t Bp, bool mailbox = true) {
 
 inline int pick_bx(int N, int max_threads) {
     int bx = 64;
-    while (bx > 4 && bx * (N + 1) > max_threads) bx >>= 1;      // N <= 127 (validate_desc): 4 * 128 = 512 threads at most
+    while (bx > 4 && bx * (N + 1) > max_threads) bx >>= 1;      // N <= MAX_N_NLP (begin_solve): 4 * 128 = 512 threads at most
     return bx;
 }
 

@@ -2713,10 +2713,19 @@ static SolveIo solve_io(const mpc_handle* h, int32_t B, const double* x0, const 
     if (h) { io.n_w = h->hp.n_w(); io.n_g = h->hp.n_g(); io.snap_len = sens_len(h); }
     return io;
 }
+// A handle exists for horizons that only the FORCES-mode solve runs (mpc_create); the kernels of the NLP are laid out for N <= MAX_N_NLP
+static bool nlp_horizon_ok(mpc_handle* h) {
+    if (h->hp.desc.N <= MAX_N_NLP) return true;
+    char buf[160];
+    snprintf(buf, sizeof buf, "N=%d: the NLP entry points take horizons up to %d (only the FORCES-mode solve goes further)", h->hp.desc.N, MAX_N_NLP);
+    h->err = buf;
+    return false;
+}
 // What every NLP solve starts with, once, at its entry point: the arguments, the handle's state (`refusal`: the entry point's own objection
 // to its other arguments), the device; from here on the snapshot of mpc_solve_batch_sens is no longer the last solve's.
 static int begin_solve(mpc_handle* h, const SolveIo& io, const char* refusal = nullptr, bool sens = false) {
     if (!h) return MPC_ERR_INVALID;
+    if (!nlp_horizon_ok(h)) return MPC_ERR_INVALID;
     if (io.B <= 0 || !io.x0 || !io.p || !io.x_out) { h->err = "B > 0 and x0, p, x_out are required"; return MPC_ERR_INVALID; }
     if (refusal) { h->err = refusal; return MPC_ERR_INVALID; }
     if (sens && h->hp.desc.fixed_iters > 0) { h->err = "sensitivities need a solve to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
@@ -2802,7 +2811,7 @@ int mpc_create(mpc_handle** out, const mpc_problem_desc* desc) {
     if (!out || !desc) { g_create_error = "null argument"; return MPC_ERR_INVALID; }
     *out = nullptr;
     std::string err;
-    int rc = validate_desc(*desc, err);
+    int rc = validate_desc(*desc, err, MAX_N_HANDLE);       // (the NLP entry points refuse N > MAX_N_NLP themselves: nlp_horizon_ok)
     if (rc) { g_create_error = err; return rc; }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -3789,6 +3798,7 @@ int mpc_eval_nlp_batch_dev(mpc_handle* h, int32_t B, const double* d_x, const do
                            void* stream_) {
     if (!h) return MPC_ERR_INVALID;
     if (B <= 0 || !d_x || !d_p) { h->err = "B > 0 and x, p are required"; return MPC_ERR_INVALID; }
+    if (!nlp_horizon_ok(h)) return MPC_ERR_INVALID;
     if (!d_f && !d_g) return MPC_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     FOR_NX(h, hipLaunchKernelGGL((k_eval_nlp<NX>), nlp_out_grid(h, B), dim3(NLP_OUT_THREADS), 0, (hipStream_t)stream_, rows_params(h, B, false), d_x, d_p, d_obst, d_f, d_g));

@@ -146,11 +146,14 @@ def solve_qp(st, zbar, xinit, Hd, max_it=IPM_MAX_IT, tol=IPM_TOL, tol_mu=IPM_TOL
 
         def step_len(v, dv):
             return min(1.0, step_max(v, dv))
-        dxa, dsa, dla, dpa = solve(s * lam)
-        a_aff = min(step_len(s, dsa), step_len(lam, dla))
-        mu_aff = float((s + a_aff * dsa) @ (lam + a_aff * dla)) / M
-        sigma = (mu_aff / mu) ** 3
-        dx, ds, dl, dp = solve(s * lam + dsa * dla - sigma * mu)
+        try:
+            dxa, dsa, dla, dpa = solve(s * lam)
+            a_aff = min(step_len(s, dsa), step_len(lam, dla))
+            mu_aff = float((s + a_aff * dsa) @ (lam + a_aff * dla)) / M
+            sigma = (mu_aff / mu) ** 3
+            dx, ds, dl, dp = solve(s * lam + dsa * dla - sigma * mu)
+        except np.linalg.LinAlgError:                         # an infeasible QP on its way to mu > 1e6: lam / s past what LAPACK factors
+            break
         a_p = min(1.0, 0.995 * step_max(s, ds))
         a_d = min(1.0, 0.995 * step_max(lam, dl))
         x = x + a_p * dx
