@@ -289,6 +289,47 @@ int mpc_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t 
                                    const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
                                    int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status,
                                    double* d_clearance, void* stream);
+/* The same loop as a chain of optima, linearised: besides traj / ctrl / step_status / clearance, the per-step feedback gains of the first
+ * control of every solve,
+ *   kgain [B,L,2,5] = d u*_0 / d s_i  (s_i = traj[b,i], the measured state)      wgain [B,L,2,7] = d u*_0 / d wt  (wt = [Q_0..Q_4 | R_0, R_1])
+ *   ogain [B,L,2,3] = d u*_0 / d pose of the obstacle at step i (x, y, heading; through the six circle centres)
+ * each two adjoint solves per step on the snapshot of that step's solve (mpc_solve_batch_sens' math).  Any gain may be NULL; with all three NULL
+ * the call is the loop it wraps.  Lt = 0 with a NULL obst_track: the plain loop without per-ego obstacles -- ogain and clearance must then be
+ * NULL (MPC_ERR_INVALID).  Otherwise the arguments of mpc_closed_loop_batch_obst.  With a gain asked for the loop runs step by step (every solve
+ * synchronises); traj, ctrl and step_status are bit for bit those of the step-by-step loop (option "loop_async" = "0") on the same handle.
+ * fixed_iters > 0 -> MPC_ERR_INVALID.  A step whose status is not 1, or whose factor fails (friction kink, wrong inertia: as
+ * mpc_solve_batch_sens), gets NaN gains.  Like every loop it ends the life of the sensitivity snapshot (mpc_sens_* after it -> MPC_ERR_STATE).
+ * The warm start, the reference window and the noise carry no derivative; vdes and the path are not differentiated.                      */
+int mpc_closed_loop_batch_lin(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
+                              const double* orient, const double* vdes, int32_t Lt, const double* obst_track, double obst_offset,
+                              int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_status,
+                              double* clearance, double* kgain, double* wgain, double* ogain);
+int mpc_closed_loop_batch_lin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                  const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
+                                  int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status,
+                                  double* d_clearance, double* d_kgain, double* d_wgain, double* d_ogain, void* stream);
+/* Forward sweep over a recorded loop, n_dir directions per ego, no solve:  ds_0 = dinit;  du_i = K_i ds_i + W_i dwt + O_i dtrack[min(i, Lt-1)];
+ * dtraj[i] = ds_i, dctrl[i] = du_i;  ds_{i+1} = ds_i + dt (F_x ds_i + F_u du_i), the plant Jacobians at traj[i] (the plant is linear in u: ctrl
+ * is accepted for symmetry and not read, it may be NULL).  dinit [B,n_dir,5], dwt [B,n_dir,7], dtrack [B,n_dir,Lt,3]: NULL = zero; dtrack needs
+ * ogain, dwt needs wgain (MPC_ERR_INVALID).  A NULL gain is zero.  dtraj [B,n_dir,L,5], dctrl [B,n_dir,L,2]: either may be NULL.  NaN gains of
+ * step i make dctrl NaN from row i on, dtraj in the steering angle and the velocity at row i+1 and in every state from row i+2 on.  Stateless: reads its arguments and the handle's dt and wheelbase, may follow
+ * any call; the _dev form enqueues on `stream` and does not synchronise.                                                                  */
+int mpc_loop_tangent(mpc_handle* h, int32_t B, int32_t L, int32_t n_dir, const double* traj, const double* ctrl, const double* kgain,
+                     const double* wgain, const double* ogain, int32_t Lt, const double* dinit, const double* dwt, const double* dtrack,
+                     double* dtraj, double* dctrl);
+int mpc_loop_tangent_dev(mpc_handle* h, int32_t B, int32_t L, int32_t n_dir, const double* d_traj, const double* d_ctrl, const double* d_kgain,
+                         const double* d_wgain, const double* d_ogain, int32_t Lt, const double* d_dinit, const double* d_dwt,
+                         const double* d_dtrack, double* d_dtraj, double* d_dctrl, void* stream);
+/* Reverse sweep, its transpose:  lam = 0;  for i = L-1 .. 0:  g_u = seed_ctrl[i] + dt F_u' lam;  grad_wt += W_i' g_u;  grad_track[min(i, Lt-1)] +=
+ * O_i' g_u;  lam <- seed_traj[i] + lam + dt F_x' lam + K_i' g_u;  grad_init = lam.  seed_traj [B,L,5], seed_ctrl [B,L,2]: NULL = zero.
+ * grad_init [B,5], grad_wt [B,7] (per ego: sum the rows for shared weights, as mpc_sens_weights), grad_track [B,Lt,3] (needs ogain): any may
+ * be NULL.  NaN gains of step i make grad_init, grad_wt and the rows of grad_track up to min(i, Lt-1) of that ego NaN.  Stateless as above.  */
+int mpc_loop_adjoint(mpc_handle* h, int32_t B, int32_t L, const double* traj, const double* ctrl, const double* kgain, const double* wgain,
+                     const double* ogain, int32_t Lt, const double* seed_traj, const double* seed_ctrl, double* grad_init, double* grad_wt,
+                     double* grad_track);
+int mpc_loop_adjoint_dev(mpc_handle* h, int32_t B, int32_t L, const double* d_traj, const double* d_ctrl, const double* d_kgain,
+                         const double* d_wgain, const double* d_ogain, int32_t Lt, const double* d_seed_traj, const double* d_seed_ctrl,
+                         double* d_grad_init, double* d_grad_wt, double* d_grad_track, void* stream);
 /* FORCES-mode stage functions (scope row a11): what `FORCESNLPsolver_casadi2forces` evaluates per stage
  * (test/FORCESNLPsolver/FORCESNLPsolver_interface.c:41-198 -> casadi_f0..f9, FORCESNLPsolver_model.c:75-1756; the model
  * of ForcesproOptimizer, optimizer.py:91-245) for B independent (z, p) pairs.  z [B,7] = (deltaDot, aLong, x, y, delta, v,

@@ -90,6 +90,12 @@ PROTOTYPES = {
     "mpc_closed_loop_batch_dev_ex": [_vp, _i32, _i32, _i32] + [_vp] * 4 + _loop_tail + [_vp] * 4,
     "mpc_closed_loop_batch_obst": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _dp, _f64] + _loop_tail + [_dp, _dp, _ip, _dp],
     "mpc_closed_loop_batch_obst_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64] + _loop_tail + [_vp] * 5,
+    "mpc_closed_loop_batch_lin": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _dp, _f64] + _loop_tail + [_dp, _dp, _ip, _dp] + [_dp] * 3,
+    "mpc_closed_loop_batch_lin_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64] + _loop_tail + [_vp] * 8,
+    "mpc_loop_tangent": [_vp, _i32, _i32, _i32] + [_dp] * 5 + [_i32] + [_dp] * 5,
+    "mpc_loop_tangent_dev": [_vp, _i32, _i32, _i32] + [_vp] * 5 + [_i32] + [_vp] * 6,
+    "mpc_loop_adjoint": [_vp, _i32, _i32] + [_dp] * 5 + [_i32] + [_dp] * 5,
+    "mpc_loop_adjoint_dev": [_vp, _i32, _i32] + [_vp] * 5 + [_i32] + [_vp] * 6,
     "mpc_metrics_batch": [_vp, _i32, _i32, _i32, _dp, _dp, _dp, _f64, _i32, _dp, _dp, _dp],
     "mpc_metrics_batch_dev": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _i32] + [_vp] * 4,
     "mpc_validity_batch": [_vp, _i32, _i32, _dp, _f64, _f64, _i32, _dp, _i32, _dp, _i32, _dp, _ip, _ip],

@@ -29,6 +29,18 @@ bounds [n_b] (BatchedMPCSolver.bounds_vector: the circle radius is its entry ol)
 solver.set_bounds(*solver.unpack_bounds(bounds)) -- the solver KEEPS these bounds afterwards -- which for a device tensor is one copy of n_b
 doubles to the host, hence a synchronisation.  Its gradient is the sum over the rows of grad_bv [B, n_b] under the same rule for failed rows;
 entries of absent bounds (+-inf) get 0.  With bounds=None the layer does not touch the solver's bounds and is what it was before, bit for bit.
+
+The closed loop as a layer, differentiated as a chain of optima (include/mpcgpu.h: mpc_closed_loop_batch_lin_dev, mpc_loop_adjoint_dev;
+DESIGN.md section 7):
+
+    wt = torch.tensor(solver.weights, requires_grad=True)
+    traj, ctrl = mpc_closed_loop(solver, init_state, wt, path, orient, vdes, steps, obst_track=track, obst_offset=off)
+    loss = g(traj, ctrl); loss.backward()                # init_state.grad [B, 5], wt.grad [7] (summed over the egos), track.grad [B, Lt, 3]
+
+The forward pass calls solver.set_weights(weights) -- the solver KEEPS them -- and runs the loop step by step with the per-step gains; the
+backward pass is one reverse sweep over the recorded gains and needs no solve, so later solves on the solver do not disturb it.  vdes and the
+path are not differentiated.  An ego with a step whose status is not 1 (NaN gains) gets NaN gradients, and with them wt.grad; failed="zero"
+gives such egos zero gradients instead.
 """
 from __future__ import annotations
 
@@ -128,3 +140,74 @@ def mpc_solve(solver: BatchedMPCSolver, x0: torch.Tensor, p: torch.Tensor, faile
     bounds [n_b] float64 on any device: the bound vector (BatchedMPCSolver.bounds_vector) the solver is set to before it solves; all three may
     require grad"""
     return MPCSolve.apply(solver, x0, p, failed, obst, weights, bounds)
+
+
+class MPCClosedLoop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver: BatchedMPCSolver, init_state: torch.Tensor, weights: torch.Tensor, path: torch.Tensor, orient: torch.Tensor, vdes: torch.Tensor,
+                steps: int, obst_track: torch.Tensor | None, obst_offset: float, noise_mode: int, sigma: float, seed: int, failed: str):
+        if failed not in ("nan", "zero"):
+            raise ValueError('failed must be "nan" or "zero"')
+        dev = init_state.device
+        if init_state.dtype != torch.float64 or not init_state.is_cuda or init_state.dim() != 2 or init_state.shape[1] != 5:
+            raise ValueError("init_state must be a float64 device tensor [B, 5]")
+        B, L = init_state.shape[0], int(steps)
+        if weights.dtype != torch.float64 or tuple(weights.shape) != (7,):
+            raise ValueError("weights must be a float64 tensor [7] = [Q_0 .. Q_4 | R_0, R_1]")
+        for name, t in (("path", path), ("orient", orient), ("vdes", vdes)):
+            if t.dtype != torch.float64 or t.device != dev:
+                raise ValueError(f"{name} must be a float64 tensor on init_state's device")
+        if path.dim() != 3 or path.shape[0] != B or path.shape[2] != 2 or tuple(orient.shape) != (B, path.shape[1]) or tuple(vdes.shape) != (B,):
+            raise ValueError("path must be [B, Lp, 2], orient [B, Lp], vdes [B]")
+        Lt = 0
+        if obst_track is not None:
+            if obst_track.dtype != torch.float64 or obst_track.device != dev or obst_track.dim() != 3 or obst_track.shape[0] != B or obst_track.shape[2] != 3:
+                raise ValueError("obst_track must be a float64 tensor [B, Lt, 3] on init_state's device")
+            Lt = obst_track.shape[1]
+        wt = weights.detach().cpu().numpy()                     # (a device tensor: seven doubles to the host, a synchronisation)
+        solver.set_weights(wt[:5], wt[5:])
+        ins = [t.detach().contiguous() for t in (init_state, path, orient, vdes)]
+        tr = None if obst_track is None else obst_track.detach().contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)       # noqa: E731
+        traj, ctrl, kg, wg = new(B, L, 5), new(B, L, 2), new(B, L, 2, 5), new(B, L, 2, 7)
+        og = new(B, L, 2, 3) if tr is not None else None
+        status = torch.empty((B, L), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        solver.closed_loop_lin_device(B, ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), ins[3].data_ptr(), L, path.shape[1], traj.data_ptr(),
+                                      ctrl.data_ptr(), d_step_status=status.data_ptr(), noise_mode=noise_mode, sigma=sigma, seed=seed, stream=stream,
+                                      d_obst_track=0 if tr is None else tr.data_ptr(), Lt=Lt, obst_offset=obst_offset, d_kgain=kg.data_ptr(),
+                                      d_wgain=wg.data_ptr(), d_ogain=0 if og is None else og.data_ptr())
+        ctx.solver, ctx.failed, ctx.Lt, ctx.wt_device = solver, failed, Lt, weights.device
+        ctx.save_for_backward(*([traj, ctrl, kg, wg] + ([og] if og is not None else [])))
+        return traj, ctrl
+
+    @staticmethod
+    def backward(ctx, grad_traj, grad_ctrl):
+        traj, ctrl, kg, wg = ctx.saved_tensors[:4]
+        og = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        B, L = traj.shape[:2]
+        dev = traj.device
+        st = grad_traj.detach().to(torch.float64).contiguous()
+        sc = grad_ctrl.detach().to(torch.float64).contiguous()
+        gi = torch.empty((B, 5), dtype=torch.float64, device=dev)
+        gw = torch.empty((B, 7), dtype=torch.float64, device=dev)
+        gt = torch.empty((B, ctx.Lt, 3), dtype=torch.float64, device=dev) if og is not None else None
+        ctx.solver.loop_adjoint_device(B, L, traj.data_ptr(), ctrl.data_ptr(), d_kgain=kg.data_ptr(), d_wgain=wg.data_ptr(), d_ogain=0 if og is None else og.data_ptr(),
+                                       Lt=ctx.Lt, d_seed_traj=st.data_ptr(), d_seed_ctrl=sc.data_ptr(), d_grad_init=gi.data_ptr(), d_grad_wt=gw.data_ptr(),
+                                       d_grad_track=0 if gt is None else gt.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        if ctx.failed == "zero":
+            good = ~torch.isnan(kg).reshape(B, -1).any(dim=1)
+            gi = torch.where(good[:, None], gi, torch.zeros_like(gi))
+            gw = torch.where(good[:, None], gw, torch.zeros_like(gw))
+            if gt is not None:
+                gt = torch.where(good[:, None, None], gt, torch.zeros_like(gt))
+        return None, gi, gw.sum(dim=0).to(ctx.wt_device), None, None, None, None, gt, None, None, None, None, None
+
+
+def mpc_closed_loop(solver: BatchedMPCSolver, init_state: torch.Tensor, weights: torch.Tensor, path: torch.Tensor, orient: torch.Tensor, vdes: torch.Tensor,
+                    steps: int, obst_track: torch.Tensor | None = None, obst_offset: float = 0.0, noise_mode: int = 0, sigma: float = 0.0, seed: int = 0,
+                    failed: str = "nan"):
+    """the closed loop of B egos as a differentiable layer: (traj [B, steps, 5], ctrl [B, steps, 2]).  init_state [B, 5], path [B, Lp, 2],
+    orient [B, Lp], vdes [B], obst_track [B, Lt, 3] | None: float64 device tensors; weights [7] float64 on any device, which the solver is set
+    to before the loop runs.  init_state, weights and obst_track may require grad."""
+    return MPCClosedLoop.apply(solver, init_state, weights, path, orient, vdes, steps, obst_track, obst_offset, noise_mode, sigma, seed, failed)

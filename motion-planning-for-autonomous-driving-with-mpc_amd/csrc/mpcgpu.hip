@@ -39,6 +39,7 @@
 #include "mpc_forces_qp.h"
 #include "mpc_riccati_mfma.h"
 #include "mpc_sens.h"
+#include "mpc_loop_lin.h"
 
 using namespace mpc;
 
@@ -2538,6 +2539,37 @@ __global__ void __launch_bounds__(SENS_THREADS) k_sens(const Params P, const dou
     sens_family<NX, Fam>(P, snap, F, W, p, b, n_dir, dir, dw, seed, grad, lam);
 }
 
+// ---- the closed loop's per-step gains and the sweeps over them (mpc_closed_loop_batch_lin, mpc_loop_tangent, mpc_loop_adjoint; mpc_loop_lin.h) ----
+// Lane per instance, between the solve of loop step A.i and k_loop_advance: loop_gain_family of one parameter family on the step's snapshot
+template <int NX, class Fam>
+__global__ void __launch_bounds__(SENS_THREADS) k_loop_gain(const Params P, const double* snap, double* F, double* W, const double* p, double* seed, double* grad,
+                                                           const LoopGainArgs A) {
+    const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
+    if (b >= P.B) return;
+    loop_gain_family<NX, Fam>(P, snap, F, W, p, seed, grad, A, b);
+}
+// (instantiated here, in front of the kernels that follow in this file: the code object keeps its order of kernels, and with it every
+//  existing kernel the bytes around it)
+#define LOOP_GAIN_KERNEL(NX, FAM) \
+    template __global__ void k_loop_gain<NX, FAM<NX>>(const Params, const double*, double*, double*, const double*, double*, double*, const LoopGainArgs);
+LOOP_GAIN_KERNEL(5, SensFamP) LOOP_GAIN_KERNEL(6, SensFamP) LOOP_GAIN_KERNEL(5, SensFamWeights) LOOP_GAIN_KERNEL(6, SensFamWeights)
+LOOP_GAIN_KERNEL(5, SensFamObst) LOOP_GAIN_KERNEL(6, SensFamObst)
+#undef LOOP_GAIN_KERNEL
+// lane per (ego, direction)
+__global__ void __launch_bounds__(SENS_THREADS) k_loop_tangent(const Params P, const LoopSweepArgs A, const double* dinit, const double* dwt, const double* dtrack,
+                                                              double* dtraj, double* dctrl) {
+    const size_t e = (size_t)blockIdx.x * SENS_THREADS + threadIdx.x;
+    if (e >= (size_t)A.B * A.n_dir) return;
+    loop_tangent_lane(P, A, (int)(e / A.n_dir), (int)(e % A.n_dir), dinit, dwt, dtrack, dtraj, dctrl);
+}
+// lane per ego
+__global__ void __launch_bounds__(SENS_THREADS) k_loop_adjoint(const Params P, const LoopSweepArgs A, const double* seed_traj, const double* seed_ctrl, double* grad_init,
+                                                              double* grad_wt, double* grad_track) {
+    const int b = blockIdx.x * SENS_THREADS + threadIdx.x;
+    if (b >= A.B) return;
+    loop_adjoint_lane(P, A, b, seed_traj, seed_ctrl, grad_init, grad_wt, grad_track);
+}
+
 template <int NX>
 __global__ void k_plant_step(const Params Pk, const double* x, const double* u, double* xn, int B, int integrator) {
     const PRef P(Pk);
@@ -2589,6 +2621,7 @@ enum Scratch : int {
     SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
     SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
     SCR_LOOP_OBST,                      // closed_loop_dev: the obstacle rows of a loop with per-ego obstacle tracks (k_loop_obst)
+    SCR_LOOP_SEED, SCR_LOOP_GRAD,       // closed_loop_dev with gains: the unit seeds and the gradient rows of k_loop_gain
     N_SCRATCH
 };
 
@@ -3769,6 +3802,16 @@ static int solve_sens_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, d
     HIP_TRY(h, hipStreamSynchronize(s));
     return MPC_OK;
 }
+// the per-step gains of mpc_closed_loop_batch_lin[_dev] (mpc_loop_lin.h), each [B, L, 2, .] or null; the plain loops have none
+struct LoopLin { double *kgain, *wgain, *ogain; };
+
+// one family's gains of loop step A.i, between the step's solve (which left the snapshot) and k_loop_advance: k_loop_gain<NX, Fam>
+template <template <int> class Fam>
+static void loop_gain_launch(mpc_handle* h, int32_t B, const double* snap, double* F, double* W, double* seed, double* grad, const LoopGainArgs& A, hipStream_t s) {
+    FOR_NX(h, hipLaunchKernelGGL((k_loop_gain<NX, Fam<NX>>), dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, s, rows_params(h, B, false), snap, F,
+                                 Fam<5>::CIRC ? W : nullptr, (const double*)h->d_p, seed, grad, A));
+}
+
 static const char* bad_dirs(int32_t n_dir, const double* dp, const double* dw) { return n_dir < 0 || (n_dir > 0 && (!dp || !dw)) ? "n_dir >= 0, and dp, dw are required when n_dir > 0" : nullptr; }
 
 extern "C" {
@@ -3933,10 +3976,12 @@ int mpc_plant_step(mpc_handle* h, int32_t B, int32_t integrator, const double* x
 // per-ego obstacle tracks of a closed loop (mpc_closed_loop_batch_obst[_dev]); the plain loop has none
 struct LoopTrack { int32_t Lt; const double* d_track; double offset; double* d_clearance; };
 
-// the closed loop of every entry point, with `track` (k_loop_obst in front of every solve, whose rows then carry the obstacle centres) or without
+// the closed loop of every entry point, with `track` (k_loop_obst in front of every solve, whose rows then carry the obstacle centres) or without;
+// with `lin` (mpc_closed_loop_batch_lin_dev has checked it) step by step, every solve leaving its snapshot and the gain kernels of the families asked for behind
+// it (null: exactly the loop without)
 static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
                            const double* d_orient, const double* d_vdes, const LoopTrack* track, int32_t noise_mode, double sigma, uint64_t seed,
-                           double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream_) {
+                           double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream_, const LoopLin* lin = nullptr) {
     if (!h) return MPC_ERR_INVALID;
     const mpc_problem_desc& d = h->hp.desc;
     if (B <= 0 || L <= 0 || Lp < L || L < d.N || !d_init_state || !d_path || !d_orient || !d_vdes || !d_traj || !d_ctrl) {
@@ -3982,6 +4027,34 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
         PO.ego_offset = d.ego_offset;
     }
     const auto place_obstacles = [&](int i) { if (track) hipLaunchKernelGGL(k_loop_obst, grid, block, 0, stream, PO, O, i); };
+    if (lin) {
+        // Step by step: the snapshot solve synchronises.  Its launch plan does not depend on the snapshot, so traj, ctrl and step_status are those
+        // of the step-by-step loop below, bit for bit.  The snapshot is never marked valid: the sens entry points refuse after this loop as after any.
+        const size_t nB = (size_t)B, nw = io.n_w;
+        size_t wlen = 0;
+        FOR_NX(h, wlen = sens_obst_scratch_len<NX>(d.N));
+        SolveIo sio = io;
+        sio.snap = static_cast<double*>(scratch_get(h, SCR_SENS_SNAP, nB * io.snap_len * 8));
+        double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, nB * (size_t)(d.N + 1) * (size_t)sens_fs(h) * 8));
+        double* W = (lin->wgain || lin->ogain) ? static_cast<double*>(scratch_get(h, SCR_SENS_OBST, nB * wlen * 8)) : nullptr;
+        double* sd = static_cast<double*>(scratch_get(h, SCR_LOOP_SEED, nB * nw * 8));
+        double* gr = static_cast<double*>(scratch_get(h, SCR_LOOP_GRAD, nB * nw * 8));          // (n_w: the longest row, the p family's)
+        if (!sio.snap || !F || ((lin->wgain || lin->ogain) && !W) || !sd || !gr) { h->err = "closed loop with gains: out of device memory"; return MPC_ERR_HIP; }
+        h->loop_replayed = 1;
+        hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
+        for (int i = 0; i < L; ++i) {
+            place_obstacles(i);
+            rc = solve_dev(h, sio, stream);
+            if (rc) return rc;
+            LoopGainArgs G{L, i, track ? track->Lt : 0, track ? track->d_track : nullptr, track ? track->offset : 0.0, nullptr};
+            if ((G.gain = lin->kgain)) loop_gain_launch<SensFamP>(h, B, sio.snap, F, W, sd, gr, G, stream);
+            if ((G.gain = lin->wgain)) loop_gain_launch<SensFamWeights>(h, B, sio.snap, F, W, sd, gr, G, stream);
+            if ((G.gain = lin->ogain)) loop_gain_launch<SensFamObst>(h, B, sio.snap, F, W, sd, gr, G, stream);
+            hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
+        }
+        HIP_TRY(h, hipGetLastError());
+        return MPC_OK;
+    }
     // First attempt: the whole loop enqueued without a single host synchronisation (every solve in the persistent pipeline
     // launch, which needs no convergence poll).  What could go wrong on the way -- a pipeline launch abandoned, an instance
     // that needs the second chance -- is recorded on the device and looked at ONCE, at the end; then the loop is replayed
@@ -4057,6 +4130,110 @@ int mpc_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, 
                           {clearance, nB * L * 8, true}}, [&](void** d, hipStream_t s) {
         return mpc_closed_loop_batch_obst_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], obst_offset, noise_mode,
                                               sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], (double*)d[8], s);
+    });
+}
+
+// the loop with per-step gains: Lt = 0 with a null track is the plain loop (ogain must then be null); no gain asked for: the loop it wraps
+int mpc_closed_loop_batch_lin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                  const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
+                                  int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status,
+                                  double* d_clearance, double* d_kgain, double* d_wgain, double* d_ogain, void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    if (h->hp.desc.fixed_iters > 0) { h->err = "closed loop with gains: the sensitivities need solves to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
+    const bool has_track = Lt != 0 || d_obst_track != nullptr;
+    if (!has_track && d_ogain) { h->err = "closed loop with gains: ogain needs obst_track"; return MPC_ERR_INVALID; }
+    if (!has_track && d_clearance) { h->err = "closed loop with gains: clearance needs obst_track"; return MPC_ERR_INVALID; }
+    const LoopTrack track{Lt, d_obst_track, obst_offset, d_clearance};
+    const LoopLin lin{d_kgain, d_wgain, d_ogain};
+    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, has_track ? &track : nullptr, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status,
+                           stream_, (d_kgain || d_wgain || d_ogain) ? &lin : nullptr);
+}
+
+int mpc_closed_loop_batch_lin(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                              const double* vdes, int32_t Lt, const double* obst_track, double obst_offset, int32_t noise_mode, double sigma,
+                              uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance, double* kgain, double* wgain,
+                              double* ogain) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
+    if ((Lt != 0 || obst_track) && (!obst_track || (Lt != 1 && Lt < L))) {
+        h->err = "closed loop: obst_track [B, Lt, 3] needs Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i); Lt = 0 with a null track: no obstacle tracks";
+        return MPC_ERR_INVALID;
+    }
+    const size_t nB = (size_t)B, nL = nB * (size_t)L;
+    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
+                          {obst_track, nB * (size_t)Lt * 3 * 8, false}, {traj, nL * 5 * 8, true}, {ctrl, nL * 2 * 8, true}, {step_status, nL * 4, true},
+                          {clearance, nL * 8, true}, {kgain, nL * 2 * LOOP_NS * 8, true}, {wgain, nL * 2 * SENS_NWT * 8, true}, {ogain, nL * 2 * LOOP_NPOSE * 8, true}},
+                      [&](void** d, hipStream_t s) {
+        return mpc_closed_loop_batch_lin_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], obst_offset, noise_mode,
+                                             sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], (double*)d[8], (double*)d[9], (double*)d[10], (double*)d[11], s);
+    });
+}
+
+// The sweeps over a recorded loop: stateless -- they read their arguments and the handle's dt and wheelbase, and may follow any call.
+static const char* bad_loop_sweep(int32_t B, int32_t L, int32_t Lt, const double* traj, const double* ogain, const double* dwt, const double* wgain, const void* track_arg) {
+    if (B <= 0 || L <= 0 || Lt < 0 || !traj) return "loop sweep: B > 0, L > 0, Lt >= 0 and traj are required";
+    if (ogain && Lt <= 0) return "loop sweep: ogain needs Lt >= 1";
+    if (track_arg && (!ogain || Lt <= 0)) return "loop sweep: dtrack / grad_track need ogain and Lt >= 1";
+    if (dwt && !wgain) return "loop sweep: dwt needs wgain";
+    return nullptr;
+}
+int mpc_loop_tangent_dev(mpc_handle* h, int32_t B, int32_t L, int32_t n_dir, const double* d_traj, const double* d_ctrl, const double* d_kgain,
+                         const double* d_wgain, const double* d_ogain, int32_t Lt, const double* d_dinit, const double* d_dwt, const double* d_dtrack,
+                         double* d_dtraj, double* d_dctrl, void* stream) {
+    if (!h) return MPC_ERR_INVALID;
+    (void)d_ctrl;               // (the plant is linear in u: its Jacobian does not read the controls)
+    const char* bad = n_dir < 0 ? "loop tangent: n_dir >= 0 is required" : bad_loop_sweep(B, L, Lt, d_traj, d_ogain, d_dwt, d_wgain, d_dtrack);
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    if (n_dir == 0 || (!d_dtraj && !d_dctrl)) return MPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const LoopSweepArgs A{B, L, Lt, n_dir, d_traj, d_kgain, d_wgain, d_ogain};
+    const size_t lanes = (size_t)B * (size_t)n_dir;
+    hipLaunchKernelGGL(k_loop_tangent, dim3((unsigned)((lanes + SENS_THREADS - 1) / SENS_THREADS)), dim3(SENS_THREADS), 0, (hipStream_t)stream, plant_params(h), A, d_dinit,
+                       d_dwt, d_dtrack, d_dtraj, d_dctrl);
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+int mpc_loop_tangent(mpc_handle* h, int32_t B, int32_t L, int32_t n_dir, const double* traj, const double* ctrl, const double* kgain, const double* wgain,
+                     const double* ogain, int32_t Lt, const double* dinit, const double* dwt, const double* dtrack, double* dtraj, double* dctrl) {
+    if (!h) return MPC_ERR_INVALID;
+    (void)ctrl;
+    const char* bad = n_dir < 0 ? "loop tangent: n_dir >= 0 is required" : bad_loop_sweep(B, L, Lt, traj, ogain, dwt, wgain, dtrack);
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    const size_t nL = (size_t)B * (size_t)L, nD = (size_t)B * (size_t)n_dir;
+    return stage_host(h, {{traj, nL * 5 * 8, false}, {kgain, nL * 2 * LOOP_NS * 8, false}, {wgain, nL * 2 * SENS_NWT * 8, false}, {ogain, nL * 2 * LOOP_NPOSE * 8, false},
+                          {dinit, nD * LOOP_NS * 8, false}, {dwt, nD * SENS_NWT * 8, false}, {dtrack, nD * (size_t)Lt * LOOP_NPOSE * 8, false},
+                          {dtraj, nD * L * LOOP_NS * 8, true}, {dctrl, nD * L * 2 * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_loop_tangent_dev(h, B, L, n_dir, (double*)d[0], nullptr, (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], (double*)d[5], (double*)d[6],
+                                    (double*)d[7], (double*)d[8], s);
+    });
+}
+int mpc_loop_adjoint_dev(mpc_handle* h, int32_t B, int32_t L, const double* d_traj, const double* d_ctrl, const double* d_kgain, const double* d_wgain,
+                         const double* d_ogain, int32_t Lt, const double* d_seed_traj, const double* d_seed_ctrl, double* d_grad_init, double* d_grad_wt,
+                         double* d_grad_track, void* stream) {
+    if (!h) return MPC_ERR_INVALID;
+    (void)d_ctrl;
+    const char* bad = bad_loop_sweep(B, L, Lt, d_traj, d_ogain, nullptr, nullptr, d_grad_track);
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    if (!d_grad_init && !d_grad_wt && !d_grad_track) return MPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const LoopSweepArgs A{B, L, Lt, 1, d_traj, d_kgain, d_wgain, d_ogain};
+    hipLaunchKernelGGL(k_loop_adjoint, dim3((B + SENS_THREADS - 1) / SENS_THREADS), dim3(SENS_THREADS), 0, (hipStream_t)stream, plant_params(h), A, d_seed_traj, d_seed_ctrl,
+                       d_grad_init, d_grad_wt, d_grad_track);
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+int mpc_loop_adjoint(mpc_handle* h, int32_t B, int32_t L, const double* traj, const double* ctrl, const double* kgain, const double* wgain, const double* ogain,
+                     int32_t Lt, const double* seed_traj, const double* seed_ctrl, double* grad_init, double* grad_wt, double* grad_track) {
+    if (!h) return MPC_ERR_INVALID;
+    (void)ctrl;
+    const char* bad = bad_loop_sweep(B, L, Lt, traj, ogain, nullptr, nullptr, grad_track);
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    const size_t nB = (size_t)B, nL = nB * (size_t)L;
+    return stage_host(h, {{traj, nL * 5 * 8, false}, {kgain, nL * 2 * LOOP_NS * 8, false}, {wgain, nL * 2 * SENS_NWT * 8, false}, {ogain, nL * 2 * LOOP_NPOSE * 8, false},
+                          {seed_traj, nL * LOOP_NS * 8, false}, {seed_ctrl, nL * 2 * 8, false}, {grad_init, nB * LOOP_NS * 8, true}, {grad_wt, nB * SENS_NWT * 8, true},
+                          {grad_track, nB * (size_t)Lt * LOOP_NPOSE * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_loop_adjoint_dev(h, B, L, (double*)d[0], nullptr, (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], (double*)d[5], (double*)d[6],
+                                    (double*)d[7], (double*)d[8], s);
     });
 }
 

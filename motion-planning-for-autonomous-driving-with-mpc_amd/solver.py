@@ -82,6 +82,20 @@ class BoundSens:
     lam_bv: np.ndarray | None = None     # [B, n_b] d f*/dbv
 
 
+@dataclass
+class LoopLin:
+    """closed_loop(..., linearize=True): the rollout and the per-step feedback gains of the first control of every solve
+    (mpc_closed_loop_batch_lin).  Rows of a step whose status is not 1, or whose factor failed, are NaN."""
+    traj: np.ndarray                      # [B, L, 5] state before step i
+    ctrl: np.ndarray                      # [B, L, 2] applied controls
+    status: np.ndarray                    # [B, L] int32
+    kgain: np.ndarray                     # [B, L, 2, 5] d u*_0 / d traj[b, i]
+    wgain: np.ndarray                     # [B, L, 2, 7] d u*_0 / d [Q_0 .. Q_4 | R_0, R_1]
+    ogain: np.ndarray | None = None       # [B, L, 2, 3] d u*_0 / d (x, y, heading) of the obstacle at step i (with obst_track)
+    clearance: np.ndarray | None = None   # [B, L] (with obst_track and clearance=True)
+    Lt: int = 0                           # poses per track (0: no obst_track)
+
+
 class BatchedMPCSolver:
     def __init__(self, N, nx=5, *, dt=0.1, Q=None, R=None, P=None, obstacle_centers=None, wheelbase=2.5789128,
                  friction_div=2.578, ego_offset=0.75, max_iter=100, tol=1e-8, fixed_iters=0, obst_mult=3, device=0,
@@ -478,14 +492,17 @@ class BatchedMPCSolver:
                                              _abi.as_dp(out)))
         return out[0] if single else out
 
-    def closed_loop(self, init_state, path, orient, vdes, steps, noise_mode=0, sigma=0.0, seed=0, obst_track=None, obst_offset=0.0, clearance=False):
+    def closed_loop(self, init_state, path, orient, vdes, steps, noise_mode=0, sigma=0.0, seed=0, obst_track=None, obst_offset=0.0, clearance=False,
+                    linearize=False):
         """B egos through `steps` receding-horizon steps on the device (include/mpcgpu.h: mpc_closed_loop_batch_ex; the loop
         body of CasadiOptimizer.optimize, optimizer.py:596-631).  init_state [B,5], path [B,Lp,2], orient [B,Lp],
         vdes [B] -> (traj [B,steps,5], ctrl [B,steps,2], step_status [B,steps]).  noise_mode / sigma / seed: the reference's
         `noised: True` with a counter-based generator (noise.py holds the Python mirror of the samples).
         obst_track [B,Lt,3] (x, y, heading; Lt = 1: standing still, Lt >= steps: row i at step i; [B,3] = Lt 1): every ego past an obstacle of
         its own, frozen over each solve's horizon (mpc_closed_loop_batch_obst); obst_offset: its front / rear circle centres along the heading.
-        clearance=True (with a track): a fourth return value [B,steps], see include/mpcgpu.h."""
+        clearance=True (with a track): a fourth return value [B,steps], see include/mpcgpu.h.
+        linearize=True: a LoopLin instead -- the same rollout, step by step, with the gains kgain, wgain and (with a track) ogain of every step
+        (mpc_closed_loop_batch_lin), what loop_tangent / loop_adjoint sweep over."""
         init_state = _abi.f64(init_state)
         if init_state.ndim == 1:
             init_state = init_state[None]
@@ -502,6 +519,11 @@ class BatchedMPCSolver:
         if obst_track is None:
             if clearance:
                 raise MpcError(_abi.MPC_ERR_INVALID, "clearance needs obst_track")
+            if linearize:
+                kg, wg = np.empty((B, steps, 2, 5)), np.empty((B, steps, 2, 7))
+                self._check(self._lib.mpc_closed_loop_batch_lin(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient),
+                                                                _abi.as_dp(vdes), 0, None, 0.0, *tail, None, _abi.as_dp(kg), _abi.as_dp(wg), None))
+                return LoopLin(traj, ctrl, st, kg, wg)
             self._check(self._lib.mpc_closed_loop_batch_ex(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient),
                                                            _abi.as_dp(vdes), *tail))
             return traj, ctrl, st
@@ -513,6 +535,12 @@ class BatchedMPCSolver:
         if track.ndim != 3 or track.shape[0] != B or track.shape[2] != 3:
             raise MpcError(_abi.MPC_ERR_INVALID, "obst_track must be [B, Lt, 3]")
         cl = np.empty((B, steps)) if clearance else None
+        if linearize:
+            kg, wg, og = np.empty((B, steps, 2, 5)), np.empty((B, steps, 2, 7)), np.empty((B, steps, 2, 3))
+            self._check(self._lib.mpc_closed_loop_batch_lin(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient),
+                                                            _abi.as_dp(vdes), track.shape[1], _abi.as_dp(track), float(obst_offset), *tail, _abi.as_dp(cl),
+                                                            _abi.as_dp(kg), _abi.as_dp(wg), _abi.as_dp(og)))
+            return LoopLin(traj, ctrl, st, kg, wg, og, cl, track.shape[1])
         self._check(self._lib.mpc_closed_loop_batch_obst(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient),
                                                          _abi.as_dp(vdes), track.shape[1], _abi.as_dp(track), float(obst_offset), *tail, _abi.as_dp(cl)))
         return (traj, ctrl, st, cl) if clearance else (traj, ctrl, st)
@@ -527,6 +555,72 @@ class BatchedMPCSolver:
             self._check(self._lib.mpc_closed_loop_batch_obst_dev(*head, int(Lt), _vp(d_obst_track), float(obst_offset), *tail, _vp(d_clearance), _vp(stream)))
         else:
             self._check(self._lib.mpc_closed_loop_batch_dev_ex(*head, *tail, _vp(stream)))
+
+    def closed_loop_lin_device(self, B, d_init_state, d_path, d_orient, d_vdes, steps, Lp, d_traj, d_ctrl, d_step_status=0, noise_mode=0, sigma=0.0,
+                               seed=0, stream=0, d_obst_track=0, Lt=0, obst_offset=0.0, d_clearance=0, d_kgain=0, d_wgain=0, d_ogain=0):
+        """device-pointer form of closed_loop(..., linearize=True) (mpc_closed_loop_batch_lin_dev): d_kgain [B,steps,2,5], d_wgain [B,steps,2,7],
+        d_ogain [B,steps,2,3] (needs d_obst_track), 0 = not asked for; runs step by step, every solve synchronises `stream`"""
+        self._check(self._lib.mpc_closed_loop_batch_lin_dev(self._h, int(B), int(steps), int(Lp), _vp(d_init_state), _vp(d_path), _vp(d_orient), _vp(d_vdes), int(Lt),
+                                                            _vp(d_obst_track), float(obst_offset), int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj),
+                                                            _vp(d_ctrl), _vp(d_step_status), _vp(d_clearance), _vp(d_kgain), _vp(d_wgain), _vp(d_ogain), _vp(stream)))
+
+    @staticmethod
+    def _loop_dirs(name, a, B, tail):
+        """an optional direction / seed array as contiguous doubles [B, ...tail] (None stays None)"""
+        if a is None:
+            return None
+        a = _abi.f64(a)
+        if a.shape != (B,) + tuple(tail):
+            raise MpcError(_abi.MPC_ERR_INVALID, f"{name} must be {[B] + list(tail)}")
+        return a
+
+    def loop_tangent(self, lin: LoopLin, dinit=None, dwt=None, dtrack=None):
+        """forward sweep over a linearised loop, no solve (mpc_loop_tangent): dinit [B,n_dir,5], dwt [B,n_dir,7], dtrack [B,n_dir,Lt,3] (needs
+        lin.ogain), any of them None (zero) but not all -> (dtraj [B,n_dir,L,5], dctrl [B,n_dir,L,2]), the derivatives of lin.traj / lin.ctrl
+        along every direction.  NaN from the first step with NaN gains on."""
+        B, L = lin.traj.shape[:2]
+        given = [a for a in (dinit, dwt, dtrack) if a is not None]
+        if not given:
+            raise MpcError(_abi.MPC_ERR_INVALID, "loop_tangent: one of dinit, dwt, dtrack is required")
+        n_dir = np.asarray(given[0]).shape[1] if np.asarray(given[0]).ndim >= 2 else -1
+        if n_dir < 0:
+            raise MpcError(_abi.MPC_ERR_INVALID, "loop_tangent: directions are [B, n_dir, ...]")
+        if dtrack is not None and lin.ogain is None:
+            raise MpcError(_abi.MPC_ERR_INVALID, "loop_tangent: dtrack needs a loop linearised with obst_track")
+        dinit = self._loop_dirs("dinit", dinit, B, (n_dir, 5))
+        dwt = self._loop_dirs("dwt", dwt, B, (n_dir, 7))
+        dtrack = self._loop_dirs("dtrack", dtrack, B, (n_dir, lin.Lt, 3))
+        dtraj, dctrl = np.empty((B, n_dir, L, 5)), np.empty((B, n_dir, L, 2))
+        self._check(self._lib.mpc_loop_tangent(self._h, B, L, n_dir, _abi.as_dp(_abi.f64(lin.traj)), _abi.as_dp(_abi.f64(lin.ctrl)), _abi.as_dp(_abi.f64(lin.kgain)),
+                                               _abi.as_dp(_abi.f64(lin.wgain)), None if lin.ogain is None else _abi.as_dp(_abi.f64(lin.ogain)), int(lin.Lt),
+                                               _abi.as_dp(dinit), _abi.as_dp(dwt), _abi.as_dp(dtrack), _abi.as_dp(dtraj), _abi.as_dp(dctrl)))
+        return dtraj, dctrl
+
+    def loop_adjoint(self, lin: LoopLin, seed_traj=None, seed_ctrl=None):
+        """reverse sweep, no solve (mpc_loop_adjoint): seed_traj [B,L,5], seed_ctrl [B,L,2] (None: zero) -> (grad_init [B,5], grad_wt [B,7],
+        grad_track [B,Lt,3] | None): the gradients of sum(seed_traj * traj) + sum(seed_ctrl * ctrl) with respect to init_state, the weights (per
+        ego: sum the rows) and the obstacle poses.  An ego with NaN gains at some step has NaN gradients."""
+        B, L = lin.traj.shape[:2]
+        seed_traj = self._loop_dirs("seed_traj", seed_traj, B, (L, 5))
+        seed_ctrl = self._loop_dirs("seed_ctrl", seed_ctrl, B, (L, 2))
+        gi, gw = np.empty((B, 5)), np.empty((B, 7))
+        gt = None if lin.ogain is None else np.empty((B, lin.Lt, 3))
+        self._check(self._lib.mpc_loop_adjoint(self._h, B, L, _abi.as_dp(_abi.f64(lin.traj)), _abi.as_dp(_abi.f64(lin.ctrl)), _abi.as_dp(_abi.f64(lin.kgain)),
+                                               _abi.as_dp(_abi.f64(lin.wgain)), None if lin.ogain is None else _abi.as_dp(_abi.f64(lin.ogain)), int(lin.Lt),
+                                               _abi.as_dp(seed_traj), _abi.as_dp(seed_ctrl), _abi.as_dp(gi), _abi.as_dp(gw), _abi.as_dp(gt)))
+        return gi, gw, gt
+
+    def loop_tangent_device(self, B, L, n_dir, d_traj, d_ctrl, d_kgain=0, d_wgain=0, d_ogain=0, Lt=0, d_dinit=0, d_dwt=0, d_dtrack=0, d_dtraj=0, d_dctrl=0,
+                            stream=0):
+        """device form of loop_tangent (enqueued on `stream`, not synchronised); 0 = absent"""
+        self._check(self._lib.mpc_loop_tangent_dev(self._h, int(B), int(L), int(n_dir), _vp(d_traj), _vp(d_ctrl), _vp(d_kgain), _vp(d_wgain), _vp(d_ogain), int(Lt),
+                                                   _vp(d_dinit), _vp(d_dwt), _vp(d_dtrack), _vp(d_dtraj), _vp(d_dctrl), _vp(stream)))
+
+    def loop_adjoint_device(self, B, L, d_traj, d_ctrl, d_kgain=0, d_wgain=0, d_ogain=0, Lt=0, d_seed_traj=0, d_seed_ctrl=0, d_grad_init=0, d_grad_wt=0,
+                            d_grad_track=0, stream=0):
+        """device form of loop_adjoint (enqueued on `stream`, not synchronised); 0 = absent"""
+        self._check(self._lib.mpc_loop_adjoint_dev(self._h, int(B), int(L), _vp(d_traj), _vp(d_ctrl), _vp(d_kgain), _vp(d_wgain), _vp(d_ogain), int(Lt),
+                                                   _vp(d_seed_traj), _vp(d_seed_ctrl), _vp(d_grad_init), _vp(d_grad_wt), _vp(d_grad_track), _vp(stream)))
 
     def last_loop_replayed(self):
         return bool(self._lib.mpc_last_loop_replayed(self._h))
@@ -736,4 +830,4 @@ def rescue_failed(backend, x0, p, result, bounds, fractions=RESCUE_FRACTIONS):
     return SolveResult(x, st, it, kkt), rescued
 
 
-__all__ = ["BatchedMPCSolver", "SolveResult", "MpcError", "MpcLibraryError", "rescue_failed", "RESCUE_FRACTIONS"]
+__all__ = ["BatchedMPCSolver", "SolveResult", "LoopLin", "MpcError", "MpcLibraryError", "rescue_failed", "RESCUE_FRACTIONS"]
