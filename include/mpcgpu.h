@@ -27,6 +27,7 @@
  *                                     FORCES-mode stage cost / RK4 dynamics / inequalities with their derivatives.
  *   mpc_forces_solve_batch .......... `output, exitflag, info = solver.solve(problem)` of ForcesproOptimizer (optimizer.py:326).
  *   mpc_forces_closed_loop_batch .... the loop of ForcesproOptimizer.optimize around it (optimizer.py:246-366).
+ *   mpc_forces_closed_loop_batch_obst  that loop past per-ego moving obstacles, predicted per stage, with a guess that follows the plan.
  *   mpc_metrics_batch ............... deviation.txt / RMSD.txt of MPCPlanner (mpc_planner.py:184-199, 279-292), circle clearance.
  *   mpc_validity_batch .............. the collision / road-boundary verdict of test/test_mpc_planner.py:37-47.
  *
@@ -370,6 +371,33 @@ int mpc_forces_closed_loop_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_
                                      const double* d_path, const double* d_orient, const double* d_vdes, const double* lb, const double* ub,
                                      const double* hl, const double* hu, int32_t hessian_mode, int32_t noise_mode, double sigma, uint64_t seed,
                                      double* d_traj, double* d_ctrl, int32_t* d_step_flag, void* stream);
+/* The same loop past per-ego obstacles that move, with a guess that may follow the plan (neither is in the reference).  Everything not named
+ * here keeps the meaning it has in mpc_forces_closed_loop_batch[_dev].
+ * guess_mode 0: the reference's guess, the tiled initial point, never refreshed.  1 (real-time iteration): after a solve with exitflag 1 the guess of
+ * the next solve is the solution shifted by one stage, zbar[j] = z_out[min(j + 1, N - 1)]; after any other exitflag the guess stays as it was.  Step 0
+ * uses the tiled initial point in both modes; the applied input is always z_out[0][0:2] (+ noise).
+ * obst_track [B, Lt, 3] = (x, y, heading) of ego b's obstacle at loop step i; its circle centres: the pose's centre, then +- obst_offset along the
+ * heading (as mpc_closed_loop_batch_obst).  Lt = 1: the obstacle stands still; Lt >= L: it moves; Lt = 0 with a NULL track: the descriptor's centres in
+ * every stage -- predict must then be 0 and clearance NULL; any other Lt: MPC_ERR_INVALID with a message.
+ * predict 0: every stage of step k sees pose row min(k, Lt - 1), frozen over the horizon as in the NLP loop.  1: stage j sees row min(k + j, Lt - 1) --
+ * stage j's state is the state at time k + j (stage 0 is pinned to xinit); rows past the track repeat its last pose.  The path index of stage j
+ * stays k + 1 + j, the reference's own choice (optimizer.py:292-318).
+ * clearance [B, L] or NULL: clearance[b, i] = min over ALL NINE circle pairs (the FORCES model constrains every ego circle against every obstacle
+ * circle) of distance - r_sum for the state before step i (traj[b, i]) against the pose at step i; ego circles: the descriptor's ego_offset.
+ * With guess_mode 0 and Lt 0 the outputs are bit for bit those of mpc_forces_closed_loop_batch[_dev] on the same handle.  The _dev form enqueues the
+ * whole loop on `stream` (one bookkeeping launch between two solves) and synchronises nothing.  nx != 5, L < N and a bad noise mode are refused as
+ * there.  Like every loop it ends the life of the sensitivity snapshot.                                                                            */
+int mpc_forces_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* init_acc,
+                                      const double* path, const double* orient, const double* vdes, const double* lb, const double* ub,
+                                      const double* hl, const double* hu, int32_t hessian_mode, int32_t guess_mode, int32_t Lt,
+                                      const double* obst_track, double obst_offset, int32_t predict, double r_sum, int32_t noise_mode, double sigma,
+                                      uint64_t seed, double* traj, double* ctrl, int32_t* step_flag, double* clearance);
+int mpc_forces_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_init_acc,
+                                          const double* d_path, const double* d_orient, const double* d_vdes, const double* lb, const double* ub,
+                                          const double* hl, const double* hu, int32_t hessian_mode, int32_t guess_mode, int32_t Lt,
+                                          const double* d_obst_track, double obst_offset, int32_t predict, double r_sum, int32_t noise_mode,
+                                          double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_flag, double* d_clearance,
+                                          void* stream);
 
 /* Post-hoc trajectory metrics (scope row f4) for B planned trajectories traj [B,L,5] (host buffers, any output may be NULL):
  *   deviation [B,L]  distance to the nearest point of origin_path [B,Lo,2]   (plot_deviation_euclidean_dis,

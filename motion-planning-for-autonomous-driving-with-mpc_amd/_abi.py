@@ -107,6 +107,8 @@ PROTOTYPES = {
     "mpc_forces_solve_batch_dev": [_vp, _i32, _vp, _vp, _vp, _dp, _dp, _dp, _dp, _i32] + [_vp] * 5,
     "mpc_forces_closed_loop_batch": [_vp, _i32, _i32, _i32] + [_dp] * 9 + [_i32] + _loop_tail + [_dp, _dp, _ip],
     "mpc_forces_closed_loop_batch_dev": [_vp, _i32, _i32, _i32] + [_vp] * 5 + [_dp] * 4 + [_i32] + _loop_tail + [_vp] * 4,
+    "mpc_forces_closed_loop_batch_obst": [_vp, _i32, _i32, _i32] + [_dp] * 9 + [_i32, _i32, _i32, _dp, _f64, _i32, _f64] + _loop_tail + [_dp, _dp, _ip, _dp],
+    "mpc_forces_closed_loop_batch_obst_dev": [_vp, _i32, _i32, _i32] + [_vp] * 5 + [_dp] * 4 + [_i32, _i32, _i32, _vp, _f64, _i32, _f64] + _loop_tail + [_vp] * 5,
 }
 RESTYPES = {"mpc_default_desc": None, "mpc_last_error": C.c_char_p, "mpc_abi_version": C.c_int}       # every other entry point returns an int code
 EXPORTS = list(PROTOTYPES)

@@ -260,4 +260,110 @@ MPC_HD void forces_loop_advance_instance(const ForcesLoopArgs& A, int b, int k) 
     for (int i = 0; i < 5; ++i) A.state[(size_t)b * 5 + i] = x[i] + h / 6.0 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
 }
 
+// =========================================================================================================================
+// The FORCES-mode loop past per-ego obstacles that move, with a guess that may follow the plan (mpc_forces_closed_loop_batch_obst).
+// Not in the reference, whose loop has one static obstacle and a guess it never refreshes; with guess_mode 0 and Lt 0 it is that loop.
+//   * guess_mode 1 (real-time iteration): after a solve with exitflag 1 the guess of the next solve is the solution shifted by one
+//     stage, zbar[j] = z_out[min(j + 1, N - 1)]; after any other exitflag the guess stays as it was
+//   * stage j of step k sees the obstacle at track row min(k, Lt - 1) (predict 0: frozen over the horizon, as the NLP loop has it) or
+//     min(k + j, Lt - 1) (predict 1: stage j's state is the state at time k + j -- stage 0 is pinned to xinit); the path index stays
+//     k + 1 + j, the reference's own choice
+// One thread per (instance, stage): row (b, j) of the parameters and of the guess is written by thread (b, j) alone, thread (b, 0)
+// also records the step and moves the plant.  z_out and zbar are distinct buffers and no thread reads what another one writes in the
+// same launch.
+// =========================================================================================================================
+struct ForcesTurnArgs {
+    ForcesLoopArgs F;                // the loop's rows; F.obstacle: the centres of every stage when there is no track (Lt = 0)
+    int32_t guess_mode;              // 0: the tiled initial point, never refreshed; 1: the shifted solution after exitflag 1
+    int32_t Lt, predict;             // poses per track (0: none, 1: the obstacle stands still, >= L: pose i at step i); 0 / 1 as above
+    const double* track;             // [B,Lt,3] pose of ego b's obstacle: x, y, heading
+    double offset;                   // front / rear circle centres: +- offset along the heading
+    double* clearance;               // [B,L] forces_loop_clearance of the state before step i against the obstacle at step i, or null
+    double r_sum, ego_offset;        // sum of the two circle radii; ego circle centres: +- ego_offset along the ego's heading
+};
+// desired velocity at path index idx: vdes for the first L - N indices, then linspace(vdes, 0, N); beyond the run: its last entry
+// (the rule of forces_loop_params_instance, expression for expression: the two loops agree bit for bit)
+MPC_HD double forces_loop_vdes(double vd, int idx, int L, int N) {
+    const int iv = idx < L ? idx : L - 1;
+    double v = vd;
+    if (iv >= L - N) {
+        const int r = iv - (L - N);
+        v = (N > 1) ? vd + (double)r * ((0.0 - vd) / (double)(N - 1)) : vd;          // numpy.linspace: start + i * step
+        if (r == N - 1 && N > 1) v = 0.0;                                             // ... with the end point exact
+    }
+    return v;
+}
+// track row that stage j of step k sees
+MPC_HD int forces_turn_pose_row(const ForcesTurnArgs& A, int k, int j) {
+    const int i = A.predict ? k + j : k;
+    return i < A.Lt - 1 ? i : A.Lt - 1;
+}
+// row (b, j) of all_parameters of step k
+MPC_HD void forces_turn_param_row(const ForcesTurnArgs& A, int b, int j, int k) {
+    const ForcesLoopArgs& F = A.F;
+    const int idx = k + 1 + j;
+    const int ip = idx < F.Lp ? idx : F.Lp - 1;                                       // replenished with the last point / orientation
+    double* p = F.params + ((size_t)b * F.N + j) * 10;
+    p[0] = F.path[((size_t)b * F.Lp + ip) * 2];
+    p[1] = F.path[((size_t)b * F.Lp + ip) * 2 + 1];
+    p[2] = forces_loop_vdes(F.vdes[b], idx, F.L, F.N);
+    p[3] = F.orient[(size_t)b * F.Lp + ip];
+    if (A.Lt > 0) loop_obstacle_centres(A.track + ((size_t)b * A.Lt + forces_turn_pose_row(A, k, j)) * 3, A.offset, p + 4);
+    else for (int q = 0; q < 6; ++q) p[4 + q] = F.obstacle[q];
+}
+// row (b, j) of the guess after a solve: the solution shifted by one stage, or left alone
+MPC_HD void forces_turn_guess_row(const ForcesTurnArgs& A, int b, int j) {
+    const ForcesLoopArgs& F = A.F;
+    if (A.guess_mode != 1 || F.exitflag[b] != 1) return;
+    const int src = j + 1 < F.N ? j + 1 : F.N - 1;
+    for (int i = 0; i < 7; ++i) F.zbar[((size_t)b * F.N + j) * 7 + i] = F.z_out[((size_t)b * F.N + src) * 7 + i];
+}
+// minimum over all nine circle pairs (the FORCES model constrains every ego circle against every obstacle circle) of distance - r_sum
+MPC_HD double forces_loop_clearance(double ego_offset, const double* state5, const double* c6, double r_sum) {
+    const double cs = cos(state5[4]), sn = sin(state5[4]);
+    double best = 0.0;
+    for (int e = 0; e < 3; ++e) {
+        const double sg = (e == 0) ? 0.0 : (e == 1 ? 1.0 : -1.0);
+        const double ex = state5[0] + sg * ego_offset * cs, ey = state5[1] + sg * ego_offset * sn;
+        for (int j = 0; j < 3; ++j) {
+            const double dx = ex - c6[2 * j], dy = ey - c6[2 * j + 1];
+            const double d = sqrt(dx * dx + dy * dy);
+            if ((e == 0 && j == 0) || d < best) best = d;
+        }
+    }
+    return best - r_sum;
+}
+// clearance[b, i]: the plant state (the state before step i) against the obstacle at step i
+MPC_HD void forces_turn_clearance(const ForcesTurnArgs& A, int b, int i) {
+    if (!A.clearance || A.Lt <= 0) return;
+    const int row = i < A.Lt - 1 ? i : A.Lt - 1;
+    double c6[6];
+    loop_obstacle_centres(A.track + ((size_t)b * A.Lt + row) * 3, A.offset, c6);
+    A.clearance[(size_t)b * A.F.L + i] = forces_loop_clearance(A.ego_offset, A.F.state + (size_t)b * 5, c6, A.r_sum);
+}
+// before the first solve, thread (b, j): row j of the tiled guess and of the parameters of step 0; thread (b, 0): the plant state, clearance[b, 0]
+MPC_HD void forces_turn_setup_row(const ForcesTurnArgs& A, int b, int j) {
+    const ForcesLoopArgs& F = A.F;
+    const double z0[7] = {0.0, F.init_acc ? F.init_acc[b] : 0.0, F.init_state[(size_t)b * 5 + 0], F.init_state[(size_t)b * 5 + 1], 0.0,
+                          F.init_state[(size_t)b * 5 + 3], F.init_state[(size_t)b * 5 + 4]};
+    for (int i = 0; i < 7; ++i) F.zbar[((size_t)b * F.N + j) * 7 + i] = z0[i];
+    forces_turn_param_row(A, b, j, 0);
+    if (j == 0) {
+        for (int q = 0; q < 5; ++q) F.state[(size_t)b * 5 + q] = (q == 2) ? 0.0 : F.init_state[(size_t)b * 5 + q];
+        forces_turn_clearance(A, b, 0);
+    }
+}
+// after solve k, thread (b, j): the guess and the parameters of step k + 1 (none after the last step); thread (b, 0): record step k, the applied
+// input (+ noise), one RK4 step of the plant, clearance[b, k + 1]
+MPC_HD void forces_turn_row(const ForcesTurnArgs& A, int b, int j, int k) {
+    if (k + 1 < A.F.L) {
+        forces_turn_guess_row(A, b, j);
+        forces_turn_param_row(A, b, j, k + 1);
+    }
+    if (j == 0) {
+        forces_loop_advance_instance(A.F, b, k);
+        if (k + 1 < A.F.L) forces_turn_clearance(A, b, k + 1);
+    }
+}
+
 }  // namespace mpc

@@ -2358,6 +2358,16 @@ __global__ void k_floop_advance(const ForcesLoopArgs A, const int k) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < A.B) forces_loop_advance_instance(A, b, k);
 }
+// FORCES-mode closed loop past per-ego obstacles (mpc_closed_loop.h: ForcesTurnArgs), one thread per (instance, stage): thread t has row t of the
+// [B * N, 10] parameters and of the [B * N, 7] guess, so consecutive lanes write consecutive rows.  k_floop_turn is the one launch between two solves.
+__global__ void __launch_bounds__(256) k_floop_turn_setup(const ForcesTurnArgs A) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < A.F.B * A.F.N) forces_turn_setup_row(A, t / A.F.N, t % A.F.N);
+}
+__global__ void __launch_bounds__(256) k_floop_turn(const ForcesTurnArgs A, const int k) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < A.F.B * A.F.N) forces_turn_row(A, t / A.F.N, t % A.F.N, k);
+}
 
 // ---- second chance for stalled instances (see rescue_dev on the host side) ---------------------------------------------
 // ordered list of the instances whose status is not "converged": one workgroup, ballot-based compaction
@@ -2620,6 +2630,7 @@ enum Scratch : int {
     SCR_SENS_OBST,                      // sens_family_launch: the stage data and the solves' vectors of a family with CIRC (sens_obst_setup, sens_solve_circ)
     SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
     SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
+    SCR_FT_STATE, SCR_FT_ZBAR, SCR_FT_PARAMS, SCR_FT_ZOUT, SCR_FT_FLAG,    // mpc_forces_closed_loop_batch_obst_dev: the rows of its solves
     SCR_LOOP_OBST,                      // closed_loop_dev: the obstacle rows of a loop with per-ego obstacle tracks (k_loop_obst)
     SCR_LOOP_SEED, SCR_LOOP_GRAD,       // closed_loop_dev with gains: the unit seeds and the gradient rows of k_loop_gain
     N_SCRATCH
@@ -4471,6 +4482,86 @@ int mpc_forces_closed_loop_batch(mpc_handle* h, int32_t B, int32_t L, int32_t Lp
                           {vdes, nB * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true}, {step_flag, nB * L * 4, true}}, [&](void** d, hipStream_t s) {
         return mpc_forces_closed_loop_batch_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], lb, ub, hl, hu,
                                                 hessian_mode, noise_mode, sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], s);
+    });
+}
+
+// what both forms of mpc_forces_closed_loop_batch_obst refuse about the guess and the track (null: nothing)
+static const char* forces_loop_obst_refusal(int32_t L, int32_t guess_mode, int32_t Lt, const double* track, double obst_offset, int32_t predict,
+                                            double r_sum, const double* clearance) {
+    if (!(guess_mode == 0 || guess_mode == 1) || !(predict == 0 || predict == 1)) return "forces closed loop: guess_mode 0 or 1, predict 0 or 1";
+    if (Lt == 0 && !track) {
+        if (predict) return "forces closed loop: predict needs obst_track (Lt = 0 with a null track: the descriptor's obstacle in every stage)";
+        if (clearance) return "forces closed loop: clearance needs obst_track (Lt = 0 with a null track: the descriptor's obstacle in every stage)";
+        return nullptr;
+    }
+    if (!track || (Lt != 1 && Lt < L) || !std::isfinite(obst_offset))
+        return "forces closed loop: obst_track [B, Lt, 3] needs Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i) and a finite "
+               "obst_offset; Lt = 0 with a null track: no obstacle tracks";
+    if (clearance && !std::isfinite(r_sum)) return "forces closed loop: clearance needs a finite r_sum";
+    return nullptr;
+}
+
+int mpc_forces_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_init_acc,
+                                          const double* d_path, const double* d_orient, const double* d_vdes, const double* lb, const double* ub,
+                                          const double* hl, const double* hu, int32_t hessian_mode, int32_t guess_mode, int32_t Lt,
+                                          const double* d_obst_track, double obst_offset, int32_t predict, double r_sum, int32_t noise_mode, double sigma,
+                                          uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_flag, double* d_clearance, void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    const mpc_problem_desc& d = h->hp.desc;
+    if (B <= 0 || L <= 0 || Lp <= 0 || L < d.N || !d_init_state || !d_path || !d_orient || !d_vdes || !d_traj || !d_ctrl || !lb || !ub || !hl || !hu) {
+        h->err = "forces closed loop: B, L, Lp > 0, L >= N and init_state, path, orient, vdes, traj, ctrl, lb, ub, hl, hu are required";
+        return MPC_ERR_INVALID;
+    }
+    if (!(noise_mode == 0 || noise_mode == 2) || (noise_mode && !(sigma >= 0.0))) { h->err = "forces closed loop: noise_mode 0 or 2, sigma >= 0"; return MPC_ERR_INVALID; }
+    if (d.nx != 5) { h->err = "the FORCES formulation has 5 states"; return MPC_ERR_INVALID; }
+    if (const char* why = forces_loop_obst_refusal(L, guess_mode, Lt, d_obst_track, obst_offset, predict, r_sum, d_clearance)) { h->err = why; return MPC_ERR_INVALID; }
+    const size_t nB = (size_t)B, N = (size_t)d.N;
+    if (nB * N >= ((size_t)1 << 27)) { h->err = "forces closed loop: batch too large for one call"; return MPC_ERR_INVALID; }      // (one thread per stage row, int indices)
+    HIP_TRY(h, hipSetDevice(h->device));
+    double* st = static_cast<double*>(scratch_get(h, SCR_FT_STATE, nB * 5 * 8));
+    double* zb = static_cast<double*>(scratch_get(h, SCR_FT_ZBAR, nB * N * 7 * 8));
+    double* par = static_cast<double*>(scratch_get(h, SCR_FT_PARAMS, nB * N * 10 * 8));
+    double* zo = static_cast<double*>(scratch_get(h, SCR_FT_ZOUT, nB * N * 7 * 8));
+    int32_t* fl = static_cast<int32_t*>(scratch_get(h, SCR_FT_FLAG, nB * 4));
+    if (!st || !zb || !par || !zo || !fl) { h->err = "forces closed loop: out of device memory"; return MPC_ERR_HIP; }
+    hipStream_t s = (hipStream_t)stream_;
+    ForcesTurnArgs A{};
+    ForcesLoopArgs& F = A.F;
+    F.B = B; F.N = d.N; F.L = L; F.Lp = Lp;
+    F.init_state = d_init_state; F.init_acc = d_init_acc; F.path = d_path; F.orient = d_orient; F.vdes = d_vdes;
+    for (int i = 0; i < 6; ++i) F.obstacle[i] = d.obstacle[i];
+    F.state = st; F.zbar = zb; F.params = par; F.z_out = zo; F.exitflag = fl;
+    F.traj = d_traj; F.ctrl = d_ctrl; F.step_flag = d_step_flag;
+    F.dt = d.dt; F.wheelbase = d.wheelbase;
+    F.noise_mode = noise_mode; F.sigma = sigma; F.seed_lo = (uint32_t)seed; F.seed_hi = (uint32_t)(seed >> 32);
+    A.guess_mode = guess_mode; A.Lt = Lt; A.predict = predict; A.track = d_obst_track; A.offset = obst_offset;
+    A.clearance = d_clearance; A.r_sum = r_sum; A.ego_offset = d.ego_offset;
+    const dim3 block(256), grid((unsigned)((nB * N + 255) / 256));
+    hipLaunchKernelGGL(k_floop_turn_setup, grid, block, 0, s, A);
+    for (int k = 0; k < L; ++k) {                       // nothing comes back to the host between the steps
+        const int rc = mpc_forces_solve_batch_dev(h, B, zb, st, par, lb, ub, hl, hu, hessian_mode, zo, fl, nullptr, nullptr, (void*)s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_floop_turn, grid, block, 0, s, A, k);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_forces_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* init_acc, const double* path,
+                                      const double* orient, const double* vdes, const double* lb, const double* ub, const double* hl, const double* hu,
+                                      int32_t hessian_mode, int32_t guess_mode, int32_t Lt, const double* obst_track, double obst_offset, int32_t predict,
+                                      double r_sum, int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_flag,
+                                      double* clearance) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "forces closed loop: null or empty argument"; return MPC_ERR_INVALID; }
+    if (const char* why = forces_loop_obst_refusal(L, guess_mode, Lt, obst_track, obst_offset, predict, r_sum, clearance)) { h->err = why; return MPC_ERR_INVALID; }
+    const size_t nB = (size_t)B;
+    return stage_host(h, {{init_state, nB * 5 * 8, false}, {init_acc, nB * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false},
+                          {vdes, nB * 8, false}, {obst_track, nB * (size_t)Lt * 3 * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true},
+                          {step_flag, nB * L * 4, true}, {clearance, nB * L * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_forces_closed_loop_batch_obst_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], lb, ub, hl, hu,
+                                                     hessian_mode, guess_mode, Lt, (double*)d[5], obst_offset, predict, r_sum, noise_mode, sigma, seed,
+                                                     (double*)d[6], (double*)d[7], (int32_t*)d[8], (double*)d[9], s);
     });
 }
 

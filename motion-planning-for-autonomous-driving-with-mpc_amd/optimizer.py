@@ -440,12 +440,28 @@ class ForcesproOptimizer(Optimizer):
     # 2.5 I; see csrc/mpc_forces_qp.h: forces_hessian_diag and INTEGRATION.md for why that is not the default)
     hessian_mode = 0
 
-    def __init__(self, configuration, init_values, predict_horizon, device=0, hessian_mode=None):
+    # not in the reference (include/mpcgpu.h, mpc_forces_closed_loop_batch_obst).  guess_mode 1, real-time iteration: after a solve with exitflag 1
+    # problem["x0"] of the next solve is the solution shifted by one stage; after any other exitflag it stays as it was.  obstacle_track [L, 3]: the
+    # obstacle's pose (x, y, heading) at every loop step (None: the configuration's `obstacle_track`, if it has one; without one the static obstacle);
+    # its circle centres lie +- disc_distance / 4 of the obstacle rectangle along the heading.  predict_obstacle: stage j of step k sees the pose of
+    # step k + j instead of step k.  With a track or guess_mode 1 the exitflags are not asserted: optimize() leaves them in `exitflags` [L].
+    guess_mode = 0
+    predict_obstacle = False
+
+    def __init__(self, configuration, init_values, predict_horizon, device=0, hessian_mode=None, guess_mode=None, obstacle_track=None,
+                 predict_obstacle=None):
         super(ForcesproOptimizer, self).__init__(configuration, init_values, predict_horizon)
         self._device = device
         self._pair = None
         if hessian_mode is not None:
             self.hessian_mode = int(hessian_mode)
+        if guess_mode is not None:
+            self.guess_mode = int(guess_mode)
+        if obstacle_track is not None:
+            self.obstacle_track = np.asarray(obstacle_track, dtype=np.float64).reshape(-1, 3)
+        if predict_obstacle is not None:
+            self.predict_obstacle = bool(predict_obstacle)
+        self.exitflags = None           # optimize(): the exitflag of every step
 
     def inequal_constraint(self):
         """optimizer.py:100-119."""
@@ -486,8 +502,12 @@ class ForcesproOptimizer(Optimizer):
             pts = np.hstack((pts, self.resampled_path_points[-1].reshape(2, -1)))
             ori = np.hstack((ori, self.orientation[-1]))
             v = np.hstack((v, v_all[-1]))
-        oc = np.array(self.obstacle_circles_centers_tuple, dtype=np.float64).reshape(6, 1)
-        return np.vstack((pts, v, ori, np.tile(oc, (1, N))))
+        if self.obstacle_track is None:
+            oc = np.tile(np.array(self.obstacle_circles_centers_tuple, dtype=np.float64).reshape(6, 1), (1, N))
+        else:
+            # per-stage centres: the pose of step k (frozen over the horizon) or of step k + j (predicted), the last pose once the track ends
+            oc = np.stack([self.obstacle_centers_at(k + j if self.predict_obstacle else k) for j in range(N)], axis=1)
+        return np.vstack((pts, v, ori, oc))
 
     use_device_loop = True      # the whole loop on the device (mpc_forces_closed_loop_batch); False: the step-by-step host loop below
 
@@ -498,19 +518,33 @@ class ForcesproOptimizer(Optimizer):
         noised = bool(self.configuration.noised)
         seed = getattr(self.configuration, "noise_seed", None)
         backend = getattr(solver, "_backend", None)
-        if self.use_device_loop and hasattr(backend, "forces_closed_loop") and (not noised or seed is not None):
+        plain = self.guess_mode == 0 and self.obstacle_track is None               # the reference's loop: every exitflag is asserted
+        if self.use_device_loop and hasattr(backend, "forces_closed_loop" if plain else "forces_closed_loop_obst") and (not noised or seed is not None):
             t_ = time.time()
             sigma = 0.1 if self.configuration.use_case == "lane_following" else 0.05
             init_state = np.array([self.init_position[0], self.init_position[1], 0.0, self.init_velocity, self.init_orientation])
-            traj, ctrl, flag = backend.forces_closed_loop(init_state, self.resampled_path_points, self.orientation, self.desired_velocity, L,
-                                                          model.lb, model.ub, model.hl, model.hu, init_acc=self.init_acceleration,
-                                                          hessian_mode=self.hessian_mode, noise_mode=2 if noised else 0,
-                                                          sigma=sigma if noised else 0.0, seed=0 if seed is None else int(seed))
-            assert np.all(flag == 1), "bad exitflag"                               # optimizer.py:330
+            loop_kw = dict(init_acc=self.init_acceleration, hessian_mode=self.hessian_mode, noise_mode=2 if noised else 0,
+                           sigma=sigma if noised else 0.0, seed=0 if seed is None else int(seed))
+            if plain:
+                traj, ctrl, flag = backend.forces_closed_loop(init_state, self.resampled_path_points, self.orientation, self.desired_velocity, L,
+                                                              model.lb, model.ub, model.hl, model.hu, **loop_kw)
+                assert np.all(flag == 1), "bad exitflag"                           # optimizer.py:330
+            else:
+                # (mpc_forces_closed_loop_batch_obst: the exitflags are returned, not asserted)
+                track = self.obstacle_track
+                if track is not None:                                              # (a track that ends before the run holds its last pose)
+                    track = track[np.minimum(np.arange(max(L, len(track))), len(track) - 1)][None]
+                traj, ctrl, flag, cl = backend.forces_closed_loop_obst(init_state, self.resampled_path_points, self.orientation, self.desired_velocity, L,
+                                                                       model.lb, model.ub, model.hl, model.hu, obst_track=track,
+                                                                       obst_offset=self.obstacle_offset, predict=self.predict_obstacle,
+                                                                       guess_mode=self.guess_mode, r_sum=self.radius_ego + self.radius_obstacle, **loop_kw)
+                self.clearance = None if cl is None else cl[0]
+            self.exitflags = flag[0].copy()
             return traj[0], ctrl[0], np.full(L, (time.time() - t_) / L)
         x = np.zeros((5, L + 1))
         u = np.zeros((2, L))
         solve_time = np.zeros(L)
+        flags = np.zeros(L, dtype=np.int32)
         x0i = np.array([0.0, self.init_acceleration, self.init_position[0], self.init_position[1], 0.0, self.init_velocity, self.init_orientation])
         x0 = np.transpose(np.tile(x0i, (1, model.N)))
         xinit = np.array([self.init_position[0], self.init_position[1], 0.0, self.init_velocity, self.init_orientation])
@@ -522,11 +556,15 @@ class ForcesproOptimizer(Optimizer):
             params = self.runtime_parameters(k, model.N)
             problem["all_parameters"] = np.reshape(np.transpose(params), (10 * model.N, 1))
             output, exitflag, info = solver.solve(problem)
-            assert exitflag == 1, "bad exitflag"                                  # optimizer.py:330
+            if plain:
+                assert exitflag == 1, "bad exitflag"                              # optimizer.py:330
+            flags[k] = exitflag
             temp = np.zeros((model.nvar, model.N))
             for i in range(model.N):
                 key = "x{0:1d}".format(i + 1)
                 temp[:, i] = output[key] if key in output else output["x{0:02d}".format(i + 1)]
+            if self.guess_mode == 1 and exitflag == 1:
+                problem["x0"] = np.concatenate((temp[:, 1:], temp[:, -1:]), axis=1).T.copy()       # the solution shifted by one stage
             pred_u = temp[0:2, :]
             if not self.configuration.noised:
                 u[:, k] = pred_u[:, 0]
@@ -538,6 +576,7 @@ class ForcesproOptimizer(Optimizer):
             x[:, k + 1] = np.transpose(model.eq(np.concatenate((u[:, k], x[:, k]))))
             solve_time[k] = info.solvetime
         x = np.delete(x, -1, axis=1)
+        self.exitflags = flags
         return x.T, u.T, solve_time
 
 

@@ -741,6 +741,58 @@ class BatchedMPCSolver:
                                                            _abi.as_dp(traj), _abi.as_dp(ctrl), _abi.as_ip(fl)))
         return traj, ctrl, fl
 
+    def forces_closed_loop_obst(self, init_state, path, orient, vdes, steps, lb, ub, hl, hu, obst_track=None, obst_offset=0.0, predict=False, guess_mode=0,
+                                r_sum=None, clearance=None, init_acc=None, hessian_mode=0, noise_mode=0, sigma=0.0, seed=0):
+        """forces_closed_loop past per-ego obstacles that move, with a guess that may follow the plan (mpc_forces_closed_loop_batch_obst).
+        obst_track [B,Lt,3] (or [B,3]: one standing pose per ego) = (x, y, heading) of ego b's obstacle at step i, Lt = 1 or >= steps; None: the
+        handle's obstacle in every stage.  predict: stage j of step k sees pose min(k + j, Lt - 1) instead of min(k, Lt - 1).  guess_mode 1: the
+        guess of the next solve is the solution shifted by one stage after exitflag 1, left alone otherwise.  r_sum: sum of the circle radii
+        (None: sqrt(hl[1]), the bound of the squared circle distances).  clearance: None = with a track.
+        -> (traj [B,steps,5], ctrl [B,steps,2], exitflag [B,steps], clearance [B,steps] | None): clearance[b, i] = min over the nine circle pairs of
+        distance - r_sum of traj[b, i] against the pose at step i."""
+        init_state = _abi.f64(init_state)
+        if init_state.ndim == 1:
+            init_state = init_state[None]
+        B = init_state.shape[0]
+        path = _abi.f64(path).reshape(B, -1, 2)
+        Lp = path.shape[1]
+        orient = _abi.f64(orient).reshape(B, Lp)
+        vdes = _abi.f64(np.broadcast_to(np.asarray(vdes, dtype=np.float64), (B,)))
+        acc = None if init_acc is None else _abi.f64(np.broadcast_to(np.asarray(init_acc, dtype=np.float64), (B,)))
+        steps = int(steps)
+        Lt = 0
+        if obst_track is not None:
+            obst_track = _abi.f64(obst_track)
+            if obst_track.ndim == 2:
+                obst_track = obst_track[:, None, :]
+            if obst_track.ndim != 3 or obst_track.shape[0] != B or obst_track.shape[2] != 3:
+                raise MpcError(_abi.MPC_ERR_INVALID, f"obst_track must be [B = {B}, Lt, 3]")
+            obst_track = _abi.f64(obst_track)
+            Lt = obst_track.shape[1]
+        if clearance is None:
+            clearance = obst_track is not None
+        if r_sum is None:
+            r_sum = float(np.sqrt(np.asarray(hl, dtype=np.float64).ravel()[1]))
+        traj, ctrl, fl = np.empty((B, steps, 5)), np.empty((B, steps, 2)), np.empty((B, steps), np.int32)
+        cl = np.empty((B, steps)) if clearance else None
+        self._check(self._lib.mpc_forces_closed_loop_batch_obst(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(acc), _abi.as_dp(path), _abi.as_dp(orient),
+                                                                _abi.as_dp(vdes), _abi.as_dp(_big(lb, 7)), _abi.as_dp(_big(ub, 7)), _abi.as_dp(_big(hl, 10)),
+                                                                _abi.as_dp(_big(hu, 10)), int(hessian_mode), int(guess_mode), Lt, _abi.as_dp(obst_track),
+                                                                float(obst_offset), 1 if predict else 0, float(r_sum), int(noise_mode), float(sigma),
+                                                                int(seed) & (2 ** 64 - 1), _abi.as_dp(traj), _abi.as_dp(ctrl), _abi.as_ip(fl), _abi.as_dp(cl)))
+        return traj, ctrl, fl, cl
+
+    def forces_closed_loop_obst_device(self, B, steps, Lp, d_init_state, d_path, d_orient, d_vdes, lb, ub, hl, hu, d_traj, d_ctrl, d_step_flag=0, d_init_acc=0,
+                                       hessian_mode=0, guess_mode=0, Lt=0, d_obst_track=0, obst_offset=0.0, predict=False, r_sum=0.0, d_clearance=0,
+                                       noise_mode=0, sigma=0.0, seed=0, stream=0):
+        """mpc_forces_closed_loop_batch_obst_dev: device pointers (ints; 0 = absent) for the rows, lb / ub / hl / hu small host arrays.  Enqueues the
+        whole loop on `stream`; nothing is synchronised."""
+        self._check(self._lib.mpc_forces_closed_loop_batch_obst_dev(self._h, int(B), int(steps), int(Lp), _vp(d_init_state), _vp(d_init_acc), _vp(d_path), _vp(d_orient),
+                                                                    _vp(d_vdes), _abi.as_dp(_big(lb, 7)), _abi.as_dp(_big(ub, 7)), _abi.as_dp(_big(hl, 10)),
+                                                                    _abi.as_dp(_big(hu, 10)), int(hessian_mode), int(guess_mode), int(Lt), _vp(d_obst_track),
+                                                                    float(obst_offset), 1 if predict else 0, float(r_sum), int(noise_mode), float(sigma),
+                                                                    int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl), _vp(d_step_flag), _vp(d_clearance), _vp(stream)))
+
     def set_option(self, name, value=None):
         """run-time switch of the handle (include/mpcgpu.h: mpc_set_option); value None restores the default.  The
         environment (MPCGPU_<NAME>) is only read when the handle is created."""
