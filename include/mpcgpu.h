@@ -442,7 +442,7 @@ int mpc_forces_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, con
                                const double* lb, const double* ub, const double* hl, const double* hu, int32_t hessian_mode,
                                double* d_x_out, int32_t* d_exitflag, int32_t* d_it, double* d_res, void* stream);
 
-/* Run-time switches of a handle (19).  They are read from the environment once, at mpc_create (MPCGPU_<NAME IN CAPITALS>), and changed afterwards
+/* Run-time switches of a handle (20).  They are read from the environment once, at mpc_create (MPCGPU_<NAME IN CAPITALS>), and changed afterwards
  * only through this call; value NULL restores the default.  Unknown name -> MPC_ERR_INVALID.
  *   what is solved
  *     "friction_lb"      the lower bound lbg[0] = 0 of the reference's stage-0 friction row sqrt((a_0^2 + v_0^2 tan(delta_0)/2.578)^2)
@@ -466,7 +466,12 @@ int mpc_forces_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, con
  *     "hybrid_live"      live instances per tile of 64 at which a tile changes over (a smaller last tile: the same fraction; -1, default: from the
  *                        machine's size; 64: k_solve_wg alone)
  *     "pipe_help"        1 / 0: the Riccati workers of the pipeline take / do not take one published stage item while their tile is with the stage
- *                        workers; -1 (default): where a round has more than three stage items per stage worker (N = 50, B = 8192)
+ *                        workers; -1 (default): where a round has more than three stage items per stage worker (N = 50, B = 8192).  Only the
+ *                        kernels with the reference's bound structure compiled in have that variant ("bound_mask"): ignored elsewhere
+ *     "pipe_early"       stages before the end of a tile's forward Riccati sweep at which its stage items go into the pipeline's ready queue (the
+ *                        stage workers then have the loads that do not read the step in flight when the sweep ends): 0 behind the sweep, n stages
+ *                        (clamped to the horizon); -1 (default): 18 in converged mode, 0 with a fixed iteration count.  Never with helping
+ *                        Riccati workers ("pipe_help").  Same bits at every value
  *     "bound_mask"       0: every bound side looked up at run time (variant 0 of the loop kernels); default 1: the kernels with the bound structure
  *                        of the reference's NLPs compiled in (optimizer.py:421-491) whenever the bounds handed to mpc_set_bounds have it
  *     "big_wg"           1: 512-thread stage workgroups (what horizons above 63 use) also for short horizons

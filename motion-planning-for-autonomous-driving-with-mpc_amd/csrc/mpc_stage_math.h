@@ -1131,8 +1131,11 @@ MPC_HD void phase_load_scalars(const PRef& P, Ctx<NX>& c) {
 // loads between its two sweeps and reads the record once the forward sweep is through (phase_preload_rec)
 // KEEPC (k_solve_wg, from a workgroup's second round on its instances): what does not change from round to round -- the reference of the next
 // stage, r_0, and whether any instance of the workgroup keeps its friction row at all -- is the caller's business (LDS / a register): no loads
-template <int NX, bool MB = false, uint32_t VM = 0xFFu, bool REC = true, bool KEEPC = false>
+// STEP (tile-major only): also read the rows the forward Riccati sweep writes -- the step, P.DZ; false: the EARLY batch, everything else -- a stage
+// worker of k_pipeline issues it while the forward sweep of its tile is still running and reads the step behind it (phase_preload_step)
+template <int NX, bool MB = false, uint32_t VM = 0xFFu, bool REC = true, bool KEEPC = false, bool STEP = true>
 MPC_HD void phase_preload(const PRef& P, Ctx<NX>& c, PreTmp<NX>& tmp, const bool fric_maybe = true) {
+    static_assert(STEP || !MB, "the mailbox path takes its step from the LDS record (REC)");
     using D = Dim<NX>;
     constexpr int NZ = D::NZ;
     if (!c.valid) return;
@@ -1142,7 +1145,7 @@ MPC_HD void phase_preload(const PRef& P, Ctx<NX>& c, PreTmp<NX>& tmp, const bool
     ws_load_rows<NZ>(MPC_ROWS(MPC_KX(Z, NZ, 0, e)), c.z);
     // (MB: step and cost-to-go come from the LDS record the sweeps of this workgroup left them in -- see Rec)
     if (MB) { if (REC) { rec_load<2>(c.rec + Rec<NX>::DU, c.dz); rec_load<NX>(c.rec + Rec<NX>::DX, c.dz + 2); } }
-    else ws_load_rows<NZ>(MPC_ROWS(MPC_K(P.DZ, NZ, 0, e)), c.dz);
+    else if (STEP) ws_load_rows<NZ>(MPC_ROWS(MPC_K(P.DZ, NZ, 0, e)), c.dz);
 #pragma unroll
     for (int i = 0; i < NZ; i += 2) {
         // multipliers of bounds that exist nowhere are never read (a_0 has per-instance bounds: stage 0 always loads its pair);
@@ -1163,7 +1166,7 @@ MPC_HD void phase_preload(const PRef& P, Ctx<NX>& c, PreTmp<NX>& tmp, const bool
     if (k < N) {
         if (!KEEPC) ws_load_rows<NX>(MPC_ROWS(MPC_K(P.REF, NX, 1, e)), c.rn);           // (constant: read where the start kernel put it, MB or not)
         ws_load_rows<NX>(MPC_ROWS(MPC_KX(Z, NZ, 1, 2 + e)), c.xn);
-        if (MB) { if (REC) rec_load<NX>(c.rec + Rec<NX>::SIZE + Rec<NX>::DX, c.dxn); } else ws_load_rows<NX>(MPC_ROWS(MPC_K(P.DZ, NZ, 1, 2 + e)), c.dxn);
+        if (MB) { if (REC) rec_load<NX>(c.rec + Rec<NX>::SIZE + Rec<NX>::DX, c.dxn); } else if (STEP) ws_load_rows<NX>(MPC_ROWS(MPC_K(P.DZ, NZ, 1, 2 + e)), c.dxn);
     } else {
 #pragma unroll
         for (int i = 0; i < NX; ++i) { if (!KEEPC) c.rn[i] = 0.0; c.xn[i] = 0.0; c.dxn[i] = 0.0; }
@@ -1209,6 +1212,17 @@ MPC_HD void phase_preload_rec(const PRef& P, Ctx<NX>& c, PreTmp<NX>& tmp) {
     rec_load<NX>(c.rec + Rec<NX>::DX, c.dz + 2);
     if (c.k < P.N) rec_load<NX>(c.rec + Rec<NX>::SIZE + Rec<NX>::DX, c.dxn);
     rec_load<D::NPK>(c.rec + Rec<NX>::PK, tmp.pk);
+}
+
+// the part of phase_preload<.., STEP = false> left out: the step of this stage and the state step of the next one, the only rows of a stage
+// item's loads that the forward sweep writes (the last stage keeps the zeros the early batch gave its dxn)
+template <int NX>
+MPC_HD void phase_preload_step(const PRef& P, Ctx<NX>& c) {
+    using D = Dim<NX>;
+    constexpr int NZ = D::NZ;
+    if (!c.valid) return;
+    ws_load_rows<NZ>(MPC_ROWS(MPC_K(P.DZ, NZ, 0, e)), c.dz);
+    if (c.k < P.N) ws_load_rows<NX>(MPC_ROWS(MPC_K(P.DZ, NZ, 1, 2 + e)), c.dxn);
 }
 
 // arithmetic on the loaded arrays only: slack steps ds = J dx + (d - s), multiplier steps dlam = -(P dx + p) - lam
