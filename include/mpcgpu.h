@@ -169,6 +169,26 @@ int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const d
                            double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt,
                            double* d_f, double* d_g, double* d_lam_g, double* d_lam_x, void* stream);
 
+/* Obstacle centres per STAGE: an obstacle that moves over the horizon.  mpc_solve_batch_stages[_dev] takes the arguments of
+ * mpc_solve_batch[_dev]_ex, mpc_eval_nlp_batch_stages[_dev] those of mpc_eval_nlp_batch[_dev], with one difference: obst is REQUIRED and is
+ * [B, N+1, 6] -- row (b, k) holds the six circle centres (order of mpc_problem_desc::obstacle) that the nine circle rows of stage k of instance
+ * b are measured against.  obst NULL -> MPC_ERR_INVALID.  The outputs x_out .. lam_x are NULL-able as in _ex and mean the same: f, g, lam_g, lam_x
+ * belong to the NLP with the per-stage centres.  The solve runs the kernels of a solve with obst [B, 6] (second chance, chunks, every horizon,
+ * nx 5 and 6): with all N+1 rows of an instance equal it returns the bits of mpc_solve_batch[_dev]_ex with that row.  A device buffer should
+ * start on a 16-byte boundary (one that does not is read in 8-byte halves).  The first per-stage call of a handle grows its workspace by
+ * 6 N rows per instance, once; a handle that never makes one keeps the workspace it had.
+ * Derivatives of a per-stage solve are not provided: it takes no sensitivity snapshot and, like every solve, ends the life of an earlier one --
+ * any mpc_sens_* call after it returns MPC_ERR_STATE.                                                                                     */
+int mpc_solve_batch_stages(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst,
+                           double* x_out, int32_t* status, int32_t* iters, double* kkt,
+                           double* f, double* g, double* lam_g, double* lam_x);
+int mpc_solve_batch_stages_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst,
+                               double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt,
+                               double* d_f, double* d_g, double* d_lam_g, double* d_lam_x, void* stream);
+int mpc_eval_nlp_batch_stages(mpc_handle* h, int32_t B, const double* x, const double* p, const double* obst, double* f, double* g);
+int mpc_eval_nlp_batch_stages_dev(mpc_handle* h, int32_t B, const double* d_x, const double* d_p, const double* d_obst,
+                                  double* d_f, double* d_g, void* stream);
+
 /* Parametric sensitivities of the returned optimum (sIPOPT's step).  p = [U_ref (N nu) | X_ref ((N+1) nx)], n_p = n_w.
  * mpc_solve_batch[_dev]_ex plus: lam_p [B, n_p] (NULL: not computed), CasADi's d/dp [f + lam_g' g + lam_x' x] at the returned x (X_ref column 0
  * -lam_g[pin rows], column k+1 -2 Q (x_k - xref_{k+1}), U_ref 0); n_dir >= 0 forward seeds dp [B, n_dir, n_p] -> dw [B, n_dir, n_w] = (dw/dp) dp
@@ -278,7 +298,7 @@ int mpc_last_loop_replayed(const mpc_handle* h);
  * approximation_circles, configuration.py:69-93 -- obst_offset = disc_distance / 4 of the obstacle rectangle).  The obstacle's SIZE stays the
  * handle's: the radius sits in the lower bound of the circle rows given to mpc_set_bounds, one obstacle size per handle.
  * A frozen obstacle gives no guarantee between steps: the plan of step i-1 kept its distance from the obstacle at step i-1.  A caller who needs a
- * margin inflates the radius by the obstacle's travel per step.
+ * margin inflates the radius by the obstacle's travel per step, or lets every stage see the obstacle where it will be: mpc_closed_loop_batch_pred.
  * clearance [B, L] or NULL: clearance[b, i] = min over the three constrained circle pairs (ego circle j, obstacle circle j) of distance - r_sum for
  * the state BEFORE step i (traj[b, i]) against the obstacle at step i; r_sum = the lower bound of the handle's circle rows.
  * Noise modes, nx = 5 / 6, step_status, mpc_last_loop_replayed and option "loop_async" as in mpc_closed_loop_batch_ex.                     */
@@ -290,6 +310,23 @@ int mpc_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t 
                                    const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
                                    int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status,
                                    double* d_clearance, void* stream);
+/* The loop past per-ego obstacles with the obstacle PREDICTED over each solve's horizon.  The arguments of mpc_closed_loop_batch_obst[_dev] plus
+ * `predict`: 0 is that loop, bit for bit; 1: stage k of the solve of step i sees track row min(i + k, Lt - 1) -- stage 0 is pinned to the measured
+ * state at time i and stage k's state is the state at time i + k, so every stage keeps its distance from where the obstacle will be then; rows
+ * past the track repeat its last pose (Lt = 1: the obstacle stands still, predict changes nothing but the kernels).  Each solve is an
+ * mpc_solve_batch_stages_dev.  With noise_mode 0 the plant is the model's own forward-Euler step: the state before step i is stage 1 of the solve
+ * of step i - 1, which held it clear of track row i -- clearance[b, i] >= 0 up to the solver's tolerance wherever that solve converged, the
+ * guarantee the frozen loop lacks.  clearance keeps its meaning (the state before step i against the pose at step i); noise modes, step_status,
+ * option "loop_async" (the whole loop enqueued without a host synchronisation) and mpc_last_loop_replayed as in mpc_closed_loop_batch_obst.
+ * predict outside {0, 1}, or predict 1 with Lt <= 0 or a NULL track -> MPC_ERR_INVALID.  mpc_closed_loop_batch_lin takes no `predict`.      */
+int mpc_closed_loop_batch_pred(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
+                               const double* orient, const double* vdes, int32_t Lt, const double* obst_track, double obst_offset,
+                               int32_t predict, int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl,
+                               int32_t* step_status, double* clearance);
+int mpc_closed_loop_batch_pred_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                   const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
+                                   int32_t predict, int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl,
+                                   int32_t* d_step_status, double* d_clearance, void* stream);
 /* The same loop as a chain of optima, linearised: besides traj / ctrl / step_status / clearance, the per-step feedback gains of the first
  * control of every solve,
  *   kgain [B,L,2,5] = d u*_0 / d s_i  (s_i = traj[b,i], the measured state)      wgain [B,L,2,7] = d u*_0 / d wt  (wt = [Q_0..Q_4 | R_0, R_1])

@@ -72,6 +72,10 @@ PROTOTYPES = {
     "mpc_eval_nlp_batch_dev": [_vp, _i32] + [_vp] * 6,
     "mpc_solve_batch_ex": [_vp, _i32] + _rows + [_dp] * 4,
     "mpc_solve_batch_dev_ex": [_vp, _i32] + [_vp] * 12,
+    "mpc_solve_batch_stages": [_vp, _i32] + _rows + [_dp] * 4,
+    "mpc_solve_batch_stages_dev": [_vp, _i32] + [_vp] * 12,
+    "mpc_eval_nlp_batch_stages": [_vp, _i32] + [_dp] * 5,
+    "mpc_eval_nlp_batch_stages_dev": [_vp, _i32] + [_vp] * 6,
     "mpc_solve_batch_sens": [_vp, _i32] + _rows + [_dp] * 5 + [_i32, _dp, _dp],
     "mpc_solve_batch_sens_dev": [_vp, _i32] + [_vp] * 12 + [_i32, _vp, _vp, _vp],
     "mpc_sens_adjoint": [_vp, _i32, _dp, _dp],
@@ -90,6 +94,8 @@ PROTOTYPES = {
     "mpc_closed_loop_batch_dev_ex": [_vp, _i32, _i32, _i32] + [_vp] * 4 + _loop_tail + [_vp] * 4,
     "mpc_closed_loop_batch_obst": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _dp, _f64] + _loop_tail + [_dp, _dp, _ip, _dp],
     "mpc_closed_loop_batch_obst_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64] + _loop_tail + [_vp] * 5,
+    "mpc_closed_loop_batch_pred": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _dp, _f64, _i32] + _loop_tail + [_dp, _dp, _ip, _dp],
+    "mpc_closed_loop_batch_pred_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64, _i32] + _loop_tail + [_vp] * 5,
     "mpc_closed_loop_batch_lin": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _dp, _f64] + _loop_tail + [_dp, _dp, _ip, _dp] + [_dp] * 3,
     "mpc_closed_loop_batch_lin_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64] + _loop_tail + [_vp] * 8,
     "mpc_loop_tangent": [_vp, _i32, _i32, _i32] + [_dp] * 5 + [_i32] + [_dp] * 5,

@@ -144,7 +144,7 @@ struct LoopObstArgs {
     int32_t B, L, Lt, nx;            // instances, loop steps, poses per track (1: the obstacle stands still; >= L: pose i at step i), states per row of `state`
     const double* track;             // [B,Lt,3] pose of ego b's obstacle: x, y, heading
     double offset;                   // front / rear circle centres: +- offset along the heading (disc_distance / 4 of the obstacle rectangle)
-    double* obst;                    // [B,6]  circle centres of the next solve (order of mpc_problem_desc::obstacle)
+    double* obst;                    // [B,6]  circle centres of the next solve (order of mpc_problem_desc::obstacle); loop_obst_stage: [B,N+1,6]
     const double* state;             // [B,nx] current plant state (LoopArgs::state)
     double* clearance;               // [B,L]  loop_clearance of the state before step i against the obstacle at step i, or null
     double r_sum;                    // sum of the two circle radii: the lower bound of the handle's circle rows
@@ -172,6 +172,18 @@ MPC_HD void loop_obst_instance(const Params& P, const LoopObstArgs& A, int b, in
     loop_obstacle_centres(A.track + ((size_t)b * A.Lt + row) * 3, A.offset, c6);
     for (int q = 0; q < 6; ++q) A.obst[(size_t)b * 6 + q] = c6[q];
     if (A.clearance) A.clearance[(size_t)b * A.L + i] = loop_clearance(P, A.state + (size_t)b * A.nx, c6, A.r_sum);
+}
+// The predicted loop (mpc_closed_loop_batch_pred, predict 1): stage k of the solve of step i is the state at time i + k, so it sees the
+// obstacle where the track puts it then -- row min(i + k, Lt - 1), the last pose held beyond the track (the rule of the FORCES-mode loop).
+// A.obst is [B, N+1, 6] here; one call per (ego, stage) writes row (b, k).  The stage-0 call also writes clearance[b, i]: the state
+// before step i against the pose at step i, as loop_obst_instance does.
+MPC_HD void loop_obst_stage(const Params& P, const LoopObstArgs& A, int N, int b, int k, int i) {
+    const int at = i + k, row = at < A.Lt - 1 ? at : A.Lt - 1;
+    double c6[6];
+    loop_obstacle_centres(A.track + ((size_t)b * A.Lt + row) * 3, A.offset, c6);
+    double* o = A.obst + ((size_t)b * (N + 1) + k) * 6;
+    for (int q = 0; q < 6; ++q) o[q] = c6[q];
+    if (k == 0 && A.clearance) A.clearance[(size_t)b * A.L + i] = loop_clearance(P, A.state + (size_t)b * A.nx, c6, A.r_sum);
 }
 
 // =========================================================================================================================

@@ -162,7 +162,9 @@ struct WsLayout {
 
 // mailbox: with the instance-major copies k_solve_wg works on (about as large as the tile-major section: a handle that can never run
 // that kernel -- long horizons, a fixed iteration count, hybrid switched off -- does without them and fits twice the rows below 4 GiB)
-inline WsLayout ws_layout(int N, int nx, size_t Bp, bool mailbox = true) {
+// obst_stages: the obstacle section holds six rows per STAGE (OBST_PER_STAGE) instead of six per instance; it is the last section of a
+// tile, so a handle that never makes a per-stage call keeps every offset and the size it had
+inline WsLayout ws_layout(int N, int nx, size_t Bp, bool mailbox = true, bool obst_stages = false) {
     const size_t NS = (size_t)nx * (nx + 1) / 2, S = N + 1;
     auto ev = [](size_t r) { return (r + 1) & ~(size_t)1; };                          // MPC_EV: whole row pairs per stage
     const size_t NZ = ev(nx + 2), XS = ev(nx), NBLK = ev((nx + 5) + 10 + 2 * nx), NPK = ev(NS + nx), NKK = 2 * nx + 2;   // Dim<NX>::NBLK: sparse H (NX + 5 entries)
@@ -173,7 +175,7 @@ inline WsLayout ws_layout(int N, int nx, size_t Bp, bool mailbox = true) {
     w.SO = take(S * 4); w.NUO = take(S * 4); w.ZLO = take(S * 4); w.ZUO = take(S * 4);
     w.LAM = take(S * XS); w.REF = take(S * XS); w.DZ = take(S * NZ);
     w.PK = take(S * NPK); w.KK = take((size_t)N * NKK); w.BLK = take(S * NBLK); w.ROLL = take(S * XS);
-    w.SC = take(SC_COUNT); w.FILT = take(2 * FILTER_MAX); w.OBST = take(6);
+    w.SC = take(SC_COUNT); w.FILT = take(2 * FILTER_MAX); w.OBST = take(obst_stages ? S * 6 : 6);
     w.rows = off;
     w.irows = ev(IS_COUNT);
     w.tile_elems = w.rows * 64;
@@ -204,12 +206,12 @@ inline int pick_bx(int N, int max_threads) {
 }
 
 inline void fill_params(Params& P, const HostProblem& hp, int B, size_t Bp, int bx, double* base, int32_t* ibase,
-                        const double* dLB, const double* dUB, bool mailbox = true) {
+                        const double* dLB, const double* dUB, bool mailbox = true, bool obst_stages = false) {
     const mpc_problem_desc& d = hp.desc;
-    const WsLayout w = ws_layout(d.N, d.nx, Bp, mailbox);
+    const WsLayout w = ws_layout(d.N, d.nx, Bp, mailbox, obst_stages);
     P.B = B; P.Bp = (int32_t)Bp; P.N = d.N; P.nx = d.nx; P.bx = bx;
     P.obst_mult = d.obst_mult; P.max_iter = d.max_iter; P.fixed_iters = d.fixed_iters;
-    P.has_fl = hp.has_fl; P.has_fu = hp.has_fu; P.has_ol = hp.has_ol; P.has_ou = hp.has_ou; P.per_inst_obst = 0;
+    P.has_fl = hp.has_fl; P.has_fu = hp.has_fu; P.has_ol = hp.has_ol; P.has_ou = hp.has_ou; P.per_inst_obst = OBST_SHARED;
     P.dt = d.dt; P.wheelbase = d.wheelbase; P.friction_div = d.friction_div; P.ego_offset = d.ego_offset; P.tol = d.tol;
     for (int i = 0; i < 6; ++i) P.Q[i] = (i < d.nx) ? d.Q[i] : 0.0;
     P.R[0] = d.R[0]; P.R[1] = d.R[1];

@@ -182,7 +182,8 @@ struct PlanState {
     bool pipe_disabled = false;         // ... it stays on one launch per kernel (abandoned pipeline launches, or the XCD census failed)
     bool resc_hint = false;             // ... its last solve had stalled instances
     int32_t B = 0;                      // the call: instances
-    bool per_inst_obst = false;         // ... one obstacle row per instance
+    int32_t per_inst_obst = OBST_SHARED;    // ... its obstacle centres (ObstMode): the descriptor's, one row per instance, one per instance and stage --
+                                        // the last two plan alike: the same kernels, the same bits where every stage's row is the instance's
     bool trace = false;                 // ... per-iteration trace (mpc_solve_batch_trace)
     bool in_rescue = false;             // ... a level of the second chance (rescue_dev): no second chance of its own
     bool async_loop = false;            // ... enqueued by the closed-loop driver without host synchronisation
@@ -258,7 +259,7 @@ SolvePlan plan_solve_nx(const HostProblem& hp, const Knobs& kn, const PlanState&
     // one thread per stage with the reference's bound structure compiled in (option bound_mask, default on): same arithmetic, same bits
     const bool ref_vm_ok = ((hp.lo_mask | hp.hi_mask) & ~REF_BOUND_VM) == 0u;    // bounds on the reference's four variables only
     pl.masked = kn.bound_mask != 0 && ref_vm_ok && (hp.dense_mask & REF_DENSE_LO) == REF_DENSE_LO && ((hp.dense_mask >> 8) & REF_DENSE_HI) == REF_DENSE_HI &&
-                hp.has_ol && !hp.has_ou && d.obst_mult == 3 && !st.per_inst_obst;
+                hp.has_ol && !hp.has_ou && d.obst_mult == 3 && st.per_inst_obst == OBST_SHARED;
     pl.cap = d.fixed_iters > 0 ? d.fixed_iters : d.max_iter;
     pl.chunk = d.fixed_iters > 0 ? pl.cap : 4;
     pl.polled = d.fixed_iters <= 0 && !st.trace;
@@ -447,6 +448,8 @@ struct SolveIo {
     double *lam_g = nullptr, *lam_x = nullptr;                      // ... the multipliers of the final iterate (mpc_solve_batch[_dev]_ex)
     double* snap = nullptr;                                         // ... the snapshot of the final iterates (mpc_solve_batch_sens[_dev], mpc_sens.h)
     size_t n_w = 0, n_g = 0, snap_len = 0;                          // HostProblem::n_w(), n_g(); Sens<NX>::len(N)
+    size_t n_obst = 6;                                              // doubles of an instance's row of obst: 6, or 6 (N + 1) -- six per stage
+    int32_t obst_mode() const { return !obst ? OBST_SHARED : n_obst > 6 ? OBST_PER_STAGE : OBST_PER_INSTANCE; }
     // mpc_solve_batch_trace: per-iteration rows [rows, 8, B] on the HOST, the iterations done (a trace call is never cut into chunks)
     struct Trace { double* out = nullptr; int32_t rows = 0; int32_t* n_it = nullptr; } trace;
     // Instances off .. off + n - 1.  THE table of the members' widths in elements per instance: staging sizes and the layout of the second
@@ -454,7 +457,7 @@ struct SolveIo {
     SolveIo rows(size_t off, int32_t n) const {
         SolveIo r = *this;
         r.B = n; r.trace = Trace{};
-        skip(r.x0, off * n_w); skip(r.p, off * n_w); skip(r.obst, off * 6);
+        skip(r.x0, off * n_w); skip(r.p, off * n_w); skip(r.obst, off * n_obst);
         skip(r.x_out, off * n_w); skip(r.status, off * 1); skip(r.iters, off * 1); skip(r.kkt, off * 1);
         skip(r.lam_g, off * n_g); skip(r.lam_x, off * n_w); skip(r.snap, off * snap_len);
         return r;

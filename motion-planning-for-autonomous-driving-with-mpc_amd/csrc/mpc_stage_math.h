@@ -94,10 +94,14 @@ enum IsRow { IS_STATUS = 0, IS_ITERS, IS_NFILT, IS_HAVETH0, IS_CONV, IS_ROLL, IS
              IS_RLEV, IS_ITACC,           // second chance inside k_solve_wg: level index (| 0x100: a level of this pass has converged; | 0x200: the first attempt stopped with
                                           // status -7, else 0; bits 16-30: its iteration count), iterations of the attempts that count so far
              IS_COUNT };
+// whose obstacle centres the circle rows of a solve are measured against: the descriptor's for the whole batch, six per instance (obst [B, 6]),
+// or six per instance and stage (obst [B, N+1, 6]: an obstacle that moves over the horizon)
+enum ObstMode : int32_t { OBST_SHARED = 0, OBST_PER_INSTANCE = 1, OBST_PER_STAGE = 2 };
 struct Params {
     int32_t B, Bp, N, nx, bx;    // instances, padded instances (multiple of 64), horizon, states, instances/block
     int32_t obst_mult, max_iter, fixed_iters;
-    int32_t has_fl, has_fu, has_ol, has_ou, per_inst_obst;
+    int32_t has_fl, has_fu, has_ol, has_ou;
+    int32_t per_inst_obst;       // obstacle centres of the solve: OBST_SHARED `obst` below, OBST_PER_INSTANCE / OBST_PER_STAGE the rows of OBST
     double dt, wheelbase, friction_div, ego_offset, tol;
     double Q[6], R[2], obst[6];
     double fl, fu, ol, ou;       // relaxed slack bounds of the friction / obstacle rows
@@ -128,7 +132,7 @@ struct Params {
     double *MZ, *MZL, *MZU, *MSO, *MNUO, *MZLO, *MZUO, *MLAM, *MREF;     // the iterate, its multipliers and the reference, likewise (filled by k_solve_wg from the tile-major arrays when it takes an instance over)
     double *SC;                  // [SC_COUNT][Bp]
     double *FILT;                // [2*FILTER_MAX][Bp]
-    const double* OBST;          // [6][Bp] per-instance obstacle centres (optional)
+    const double* OBST;          // [6][Bp] per-instance obstacle centres (optional); OBST_PER_STAGE: [(N+1)*6][Bp], six rows per stage
     int32_t* ISC;                // [IS_COUNT][Bp]
     double* WS;                  // base of the double workspace (all arrays above live inside it)
     int32_t* IWS;                // base of the int32 workspace
@@ -793,10 +797,50 @@ MPC_HD double friction_eval(const Params& P, double a, double dl, double v, doub
     return fabs(y);
 }
 
-template <int NX, bool BATCH_WIDE = false>
+// The six centres the circle rows of stage thread c are measured against.  BATCH_WIDE (variant 2: one obstacle per batch) reads no mode at
+// all.  STAGES = false compiles the per-stage mode out: the kernels whose machine code is pinned (k_start, wg_restart) have a second instantiation with it
+// (k_start<NX, true>, wg_restart<NX, true>), which a per-stage solve runs.
+// Per stage: six rows per stage in the tile-major pair layout of every other per-stage array -- three 16-byte loads, one scalar offset
+// (the stage's) more than the per-instance rows.  The mode is a kernel argument: the branch is wave-uniform.
+template <int NX, bool BATCH_WIDE = false, bool STAGES = true>
 MPC_HD void load_obst(const PRef& P, Ctx<NX>& c) {
+    if (!BATCH_WIDE && STAGES && P.per_inst_obst == OBST_PER_STAGE) {
+        ws_load_rows<6>(MPC_ROWS(MPC_K(P.OBST, 6, 0, e)), c.obst);
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 6; ++i) c.obst[i] = (!BATCH_WIDE && P.per_inst_obst) ? (double)MPC_S(P.OBST, i) : P.obst[i];
+}
+
+// ---- the caller's per-stage obstacle rows [B, N+1, 6] (row-major) -> the tile-major obstacle section, what k_transpose_obst_stages does in
+//      front of every per-stage solve.  The row of an instance is 6 (N + 1) contiguous doubles; the section wants, per row PAIR, the 64
+//      instances of a tile side by side (1 KiB).  Rows 2q and 2q + 1 of an instance are neighbours on both sides, so the unit is a 16-byte
+//      pair: a workgroup takes one tile and OBST_XP_KC stages, element e of its trip is pair e % pc of instance e / pc on the way in (3 kc
+//      consecutive pairs per instance: whole 16-byte lanes, 384 contiguous bytes per instance) and instance e % 64 of pair e / 64 on the
+//      way out (1 KiB per 64 lanes), an LDS tile in between.  The elements are independent: any order of the trip gives the same rows.
+constexpr int OBST_XP_KC = 8;                    // stages per workgroup: 64 x 24 pairs = 24 KiB of LDS whatever the horizon
+constexpr int OBST_XP_LD = 3 * OBST_XP_KC + 1;   // pairs per instance row of the LDS tile (odd: the lanes of the way out fall into different banks)
+struct alignas(16) ObstPair { double lo, hi; };
+struct ObstXpose {
+    const double* obst;          // [B][S][6]
+    double* OBST;                // first row of the obstacle section in tile 0 (ws_layout(.., obst_stages = true).OBST)
+    int32_t B, S;                // instances, stages N + 1
+    uint32_t tile_elems;
+};
+MPC_HD int obst_xp_stages(const ObstXpose& A, int k0) { return A.S - k0 < OBST_XP_KC ? A.S - k0 : OBST_XP_KC; }
+MPC_HD int obst_xp_count(const ObstXpose& A, int k0) { return 64 * 3 * obst_xp_stages(A, k0); }
+MPC_HD void obst_xp_read(const ObstXpose& A, int tile, int k0, int e, ObstPair* lds) {
+    const int pc = 3 * obst_xp_stages(A, k0), l = e / pc, p = e - l * pc, b = tile * 64 + l;
+    if (b >= A.B) return;
+    const double* s = A.obst + ((size_t)b * A.S + k0) * 6 + 2 * p;
+    // (a caller's buffer that starts on an odd double -- the second chance's sub-batch may -- is read in halves)
+    lds[l * OBST_XP_LD + p] = ((uintptr_t)A.obst & 15u) == 0 ? *reinterpret_cast<const ObstPair*>(s) : ObstPair{s[0], s[1]};
+}
+MPC_HD void obst_xp_write(const ObstXpose& A, int tile, int k0, int e, const ObstPair* lds) {
+    const int p = e >> 6, l = e & 63;
+    if (tile * 64 + l >= A.B) return;
+    // rows 2q, 2q + 1 with q = 3 k0 + p: mpc_prow(2q) = 128 q
+    *reinterpret_cast<ObstPair*>(A.OBST + (size_t)tile * A.tile_elems + (size_t)(3 * k0 + p) * 128u + 2u * (uint32_t)l) = lds[l * OBST_XP_LD + p];
 }
 
 // =========================================================================================================
@@ -947,14 +991,14 @@ MPC_HD void prestart_instance(const PRef& P, int b) {
 // =========================================================================================================
 // Phase 0 (init kernel only): build the start iterate from the caller's x0 (IPOPT section 3.6)
 // =========================================================================================================
-template <int NX>
+template <int NX, bool OSTG = true>           // (OSTG: load_obst's STAGES)
 MPC_HD void phase_init_point(const PRef& P, Ctx<NX>& c, Red0& red) {
     using D = Dim<NX>;
     constexpr int NZ = D::NZ;
     red = red_neutral0();
     if (!c.valid) return;
     const int N = P.N, k = c.k;
-    load_obst(P, c);
+    load_obst<NX, false, OSTG>(P, c);
     c.fric_row = MPC_S(P.ISC, IS_FROW) != 0;
     c.a0lb = MPC_S(P.SC, SC_A0LB);
     c.a0ub = MPC_S(P.SC, SC_A0UB);

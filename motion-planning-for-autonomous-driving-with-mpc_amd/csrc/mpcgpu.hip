@@ -167,11 +167,13 @@ constexpr uint32_t REF_VM = REF_BOUND_VM | MPC_REF_FLAGS;
 // are issued first, then step_wait() -- every thread calls it; false: the launch is being abandoned -- then the step's own loads.  Until then the
 // block has stored nothing.  step_wait.there() (uniform): the step is known to be out -- no wait, its loads follow the others at once.
 // NoStepWait: all loads in one batch.
+// OSTG (INIT only): the start iterate reads per-stage obstacle rows where the solve has them (load_obst's STAGES); false in the kernels whose
+// machine code is pinned -- k_start<NX>, wg_restart<NX> --; k_start<NX, true> / wg_restart<NX, true> serve a per-stage solve.
 struct NoStepWait {
     __device__ __forceinline__ bool there() const { return true; }
     __device__ __forceinline__ bool operator()() const { return true; }
 };
-template <int NX, bool INIT, int MAXT, uint32_t VM = 0xFFu, class StepWait = NoStepWait>
+template <int NX, bool INIT, int MAXT, uint32_t VM = 0xFFu, class StepWait = NoStepWait, bool OSTG = true>
 __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, const int n_z, const int stash_rows, const uint32_t b0,
                                             const unsigned long long tile_bits, double* lds, const bool stamp = true,
                                             uint32_t* live_out = nullptr, const bool bounds_in_lds = false, const StepWait& step_wait = StepWait()) {
@@ -209,7 +211,7 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
     if (INIT) lds_barrier();
     if (INIT) {
         Red0 r0;
-        phase_init_point<NX>(P, c, r0);
+        phase_init_point<NX, OSTG>(P, c, r0);
         block_reduce(r0, bx, lds);
         phase_init_scalars<NX>(P, c, r0);
     } else {
@@ -1139,7 +1141,8 @@ template <int NX, class Src = PrestartFromWs> __device__ __forceinline__ void pr
 
 // restart of the instance of a one-instance workgroup of k_solve_wg at a level of its second chance: warm start -> tile-major Z, start-point
 // safeguard, start iterate (what k_start does for a block) -- see k_solve_wg<.., RESC>
-template <int NX>
+// (OSTG: stage_block's; false, the default, is the function variant 2 calls, code as it was -- true the one of variant 0, which a per-stage solve runs)
+template <int NX, bool OSTG = false>
 __device__ __attribute__((noinline)) void wg_restart(const PRef& Pin, const int n_mult, const int n_z, const int stash_rows, const uint32_t b0, double* lds,
                                                      uint32_t* live_out, const bool carry, const bool from_xs, const bool keep_first, const bool first_tiled) {
     const PRef P = mpc_pref(static_cast<const Params&>(Pin), false);      // (a copy in registers, its cache policy a literal again: the reference points into the caller's stack)
@@ -1190,7 +1193,7 @@ __device__ __attribute__((noinline)) void wg_restart(const PRef& Pin, const int 
     lds_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stage_block<NX, true, 256>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, false, live_out);
+    stage_block<NX, true, 256, 0xFFu, NoStepWait, OSTG>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, false, live_out);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1411,7 +1414,9 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
                 // (out of line, on a copy of the parameters: the start-point safeguard and the start iterate inlined here put the hot loop at 512
                 //  registers with scratch -- B = 256 lane following paid 1.7 % for a path it never takes)
                 const PRef Pc = P;
-                wg_restart<NX>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
+                // (per-stage obstacle rows, variant 0 only: the instantiation that reads them -- every other solve keeps the function it had)
+                if (VAR == 2 || Pc.per_inst_obst != OBST_PER_STAGE) wg_restart<NX>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
+                else wg_restart<NX, true>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
             }
             fresh = true;
             bounds_ok = false;
@@ -1857,7 +1862,8 @@ __global__ void __launch_bounds__(1024) k_prestart_par(const Params Pk) {
 #endif
 // zero_p / zero_n: the OTHER control block of the loop kernels, zeroed here for the next solve (the two blocks alternate: a solve in steady state has
 // no fill of its own anywhere on its stream)
-template <int NX>
+// OSTG: stage_block's -- false, the default, is the kernel of every solve but a per-stage one, code as it was; true that solve's
+template <int NX, bool OSTG = false>
 __global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* zero_p, const uint32_t zero_n) {
     const PRef P(Pk);
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -1925,7 +1931,7 @@ __global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start(const Params Pk, 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     MPC_STAMP(P.DBG, blockIdx.x, KS_FENCED, threadIdx.x == 0);
-    stage_block<NX, true, 256>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, true, nullptr, true);
+    stage_block<NX, true, 256, 0xFFu, NoStepWait, OSTG>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, true, nullptr, true);
 }
 
 
@@ -2028,6 +2034,16 @@ __global__ void k_transpose_obst(const double* obst /*[B][6]*/, double* OBST /*r
     if (b >= B) return;
 #pragma unroll
     for (int i = 0; i < 6; ++i) OBST[((uint32_t)b >> 6) * tile_elems + mpc_prow((uint32_t)i) + 2u * ((uint32_t)b & 63u)] = obst[(size_t)b * 6 + i];
+}
+
+// per-stage obstacle rows [B][N+1][6] -> the obstacle section of the workspace, through LDS (mpc_stage_math.h: obst_xp_read / obst_xp_write):
+// grid (tiles, ceil((N + 1) / OBST_XP_KC)); 16-byte lanes on both sides
+__global__ void __launch_bounds__(256) k_transpose_obst_stages(const ObstXpose A) {
+    __shared__ ObstPair tile[64 * OBST_XP_LD];
+    const int tl = (int)blockIdx.x, k0 = (int)blockIdx.y * OBST_XP_KC, n = obst_xp_count(A, k0);
+    for (int e = (int)threadIdx.x; e < n; e += (int)blockDim.x) obst_xp_read(A, tl, k0, e, tile);
+    __syncthreads();
+    for (int e = (int)threadIdx.x; e < n; e += (int)blockDim.x) obst_xp_write(A, tl, k0, e, tile);
 }
 
 // debug/trace helper: gather 8 per-instance scalar rows into a contiguous [8][B] buffer
@@ -2459,6 +2475,13 @@ __global__ void __launch_bounds__(128) k_loop_obst(const Params Pk, const LoopOb
     if (b < A.B) loop_obst_instance(Pk, A, b, i);
 }
 
+// ... of the predicted loop (loop_obst_stage): one thread per (ego, stage) writes row (b, k) of the solve's [B, N+1, 6] obstacle rows
+__global__ void __launch_bounds__(256) k_loop_obst_stages(const Params Pk, const LoopObstArgs A, const int N, const int i) {
+    if (A.abort_flag != nullptr && *A.abort_flag != 0u) return;       // (as k_loop_advance)
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, S = N + 1;
+    if (t < A.B * S) loop_obst_stage(Pk, A, N, t / S, t % S, i);
+}
+
 // FORCES-mode closed loop (mpc_closed_loop.h: ForcesLoopArgs), one instance per thread
 __global__ void k_floop_setup(const ForcesLoopArgs A) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2507,11 +2530,11 @@ __global__ void __launch_bounds__(1024) k_rescue_select(const int32_t* status, i
     if (t == 0) *count = base;
 }
 // rows of the selected instances -> compact sub-batch (first call), converged rows of a level -> warm start of the next
-__global__ void k_rescue_gather(const int32_t* idx, int nw, const double* x0, const double* p, const double* obst, double* xs, double* ps, double* os,
+__global__ void k_rescue_gather(const int32_t* idx, int nw, const double* x0, const double* p, const double* obst, int n_obst, double* xs, double* ps, double* os,
                                 int32_t* it_acc) {
     const int j = blockIdx.x, b = idx[j];
     for (int q = threadIdx.x; q < nw; q += blockDim.x) { xs[(size_t)j * nw + q] = x0[(size_t)b * nw + q]; ps[(size_t)j * nw + q] = p[(size_t)b * nw + q]; }
-    if (obst != nullptr && threadIdx.x < 6) os[(size_t)j * 6 + threadIdx.x] = obst[(size_t)b * 6 + threadIdx.x];
+    if (obst != nullptr) for (int q = threadIdx.x; q < n_obst; q += blockDim.x) os[(size_t)j * n_obst + q] = obst[(size_t)b * n_obst + q];      // (6, or 6 (N + 1) per stage)
     if (threadIdx.x == 0) it_acc[j] = 0;
 }
 __global__ void k_rescue_carry(int nw, const int32_t* st, const int32_t* it, const double* out, double* xs, int32_t* it_acc) {
@@ -2546,7 +2569,7 @@ __global__ void k_rescue_scatter_mult(const int32_t* idx, int nw, int ng, const 
 // mpc_stage_math.h (the CPU harness of the tests runs the same functions).
 constexpr int NLP_OUT_THREADS = 256;
 template <int NX>
-__global__ void __launch_bounds__(NLP_OUT_THREADS) k_eval_nlp(const Params P, const double* x, const double* p, const double* obst, double* f, double* g) {
+__global__ void __launch_bounds__(NLP_OUT_THREADS) k_eval_nlp(const Params P, const double* x, const double* p, const double* obst, const int obst_stages, double* f, double* g) {
     __shared__ double fpart[NLP_OUT_THREADS];
     const int S = P.N + 1, ipb = NLP_OUT_THREADS / S, t = threadIdx.x, li = t / S, k = t - li * S;
     const int b = blockIdx.x * ipb + li;
@@ -2555,7 +2578,8 @@ __global__ void __launch_bounds__(NLP_OUT_THREADS) k_eval_nlp(const Params P, co
     double fk = 0.0;
     if (valid) {
         double ob[6];
-        for (int i = 0; i < 6; ++i) ob[i] = obst ? obst[(size_t)b * 6 + i] : P.obst[i];
+        // (obst_stages: [B, N+1, 6], stage k against its own centres)
+        for (int i = 0; i < 6; ++i) ob[i] = obst ? obst[obst_stages ? ((size_t)b * S + k) * 6 + i : (size_t)b * 6 + i] : P.obst[i];
         fk = nlp_eval_stage<NX>(P, x + (size_t)b * nw, p + (size_t)b * nw, ob, k, g ? g + (size_t)b * ng : nullptr);
     }
     fpart[t] = fk;
@@ -2759,6 +2783,7 @@ struct mpc_handle {
     // device workspace
     size_t cap_Bp = 0;
     bool ws_mailbox = false;            // the workspace carries the instance-major mailbox section (SolvePlan::mailbox at allocation time)
+    bool ws_obst_stages = false;        // ... its obstacle section holds six rows per stage (from the handle's first per-stage call on)
     double* d_ws = nullptr;
     int32_t* d_iws = nullptr;
     double *d_LB = nullptr, *d_UB = nullptr;
@@ -2854,7 +2879,7 @@ struct DevTmp {
 // Params of a kernel that reads and writes caller rows of B instances, with the handle's workspace (what its last solve left) or without
 static Params rows_params(const mpc_handle* h, int32_t B, bool ws) {
     Params P;
-    fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, ws ? h->d_ws : nullptr, ws ? h->d_iws : nullptr, h->d_LB, h->d_UB, ws && h->ws_mailbox);
+    fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, ws ? h->d_ws : nullptr, ws ? h->d_iws : nullptr, h->d_LB, h->d_UB, ws && h->ws_mailbox, ws && h->ws_obst_stages);
     return P;
 }
 // the grid of the kernels that run one thread per stage, NLP_OUT_THREADS / (N + 1) instances per workgroup
@@ -2947,7 +2972,7 @@ static int stage_solve(mpc_handle* h, const SolveIo& io, const Stage (&more)[M],
 static void free_ws(mpc_handle* h) {
     if (h->d_ws) (void)hipFree(h->d_ws);
     if (h->d_iws) (void)hipFree(h->d_iws);
-    h->d_ws = nullptr; h->d_iws = nullptr; h->cap_Bp = 0; h->ws_mailbox = false;
+    h->d_ws = nullptr; h->d_iws = nullptr; h->cap_Bp = 0; h->ws_mailbox = false; h->ws_obst_stages = false;
 }
 static void free_io(mpc_handle* h) {
     void* ptrs[] = {h->d_x0, h->d_p, h->d_xout, h->d_kkt, h->d_status, h->d_iters};
@@ -3158,27 +3183,29 @@ int mpc_get_profile(const mpc_handle* h, double out[6]) {
 // how one solve is called: its stream; a level of the second chance (null: the handle's problem as it is); enqueued by the closed loop without host synchronisation
 struct SolveCall { hipStream_t stream = nullptr; const Level* level = nullptr; bool async = false; };
 // what plan_solve reads of the device, the handle and the call
-static PlanState plan_state(const mpc_handle* h, int32_t B, bool per_inst_obst, bool trace, const SolveCall& call = {}) {
+static PlanState plan_state(const mpc_handle* h, int32_t B, int32_t obst_mode, bool trace, const SolveCall& call = {}) {
     PlanState st;
     st.n_cu = h->n_cu; st.xcd_mask = h->xcd_mask;
     st.ws_mailbox = h->ws_mailbox; st.pipe_disabled = h->pipe_disabled; st.resc_hint = h->resc_hint;
-    st.B = B; st.per_inst_obst = per_inst_obst; st.trace = trace; st.in_rescue = call.level != nullptr; st.async_loop = call.async;
+    st.B = B; st.per_inst_obst = obst_mode; st.trace = trace; st.in_rescue = call.level != nullptr; st.async_loop = call.async;
     return st;
 }
 // a pipeline launch was abandoned and its work done again with one launch per kernel (pipe_disabled): the next solve tries the pipeline again, PIPE_ABORTS_MAX times at most
 static void count_abandoned_launch(mpc_handle* h) {
     if (++h->pipe_aborts < mpc_handle::PIPE_ABORTS_MAX) h->pipe_disabled = false;
 }
-// the workspace for Bp rows, with the mailbox section if `mb` (SolvePlan::mailbox)
-static int ensure_ws(mpc_handle* h, size_t Bp, bool mb) {
-    if (Bp <= h->cap_Bp && (!mb || h->ws_mailbox)) return MPC_OK;
+// the workspace for Bp rows, with the mailbox section if `mb` (SolvePlan::mailbox) and the per-stage obstacle section if `os` (a per-stage call;
+// the handle keeps it from then on)
+static int ensure_ws(mpc_handle* h, size_t Bp, bool mb, bool os) {
+    if (Bp <= h->cap_Bp && (!mb || h->ws_mailbox) && (!os || h->ws_obst_stages)) return MPC_OK;
     const size_t Bp_req = Bp;
-    Bp = std::max(Bp, h->cap_Bp);                      // (grow only: also when all that changes is the mailbox section)
+    Bp = std::max(Bp, h->cap_Bp);                      // (grow only: also when all that changes is the mailbox or the obstacle section)
+    os = os || h->ws_obst_stages;
     free_ws(h);
-    WsLayout w = ws_layout(h->hp.desc.N, h->hp.desc.nx, Bp, mb);
+    WsLayout w = ws_layout(h->hp.desc.N, h->hp.desc.nx, Bp, mb, os);
     // (a handle that grew close to the limit WITHOUT the mailbox section and now needs one: what was asked for fits -- SolvePlan::max_rows
     //  has chunked the batch for the layout with the mailbox -- the old capacity with the section added may not)
-    if (w.total * sizeof(double) >= ((size_t)1 << 32) && Bp_req < Bp) { Bp = Bp_req; w = ws_layout(h->hp.desc.N, h->hp.desc.nx, Bp, mb); }
+    if (w.total * sizeof(double) >= ((size_t)1 << 32) && Bp_req < Bp) { Bp = Bp_req; w = ws_layout(h->hp.desc.N, h->hp.desc.nx, Bp, mb, os); }
     if (w.total * sizeof(double) >= ((size_t)1 << 32)) {
         h->err = "batch too large: the workspace must stay below 4 GiB (32-bit buffer offsets); split the batch";
         return MPC_ERR_INVALID;
@@ -3187,6 +3214,7 @@ static int ensure_ws(mpc_handle* h, size_t Bp, bool mb) {
     HIP_TRY(h, hipMalloc(&h->d_iws, w.itotal * sizeof(int32_t)));
     h->cap_Bp = Bp;
     h->ws_mailbox = mb;
+    h->ws_obst_stages = os;
     return MPC_OK;
 }
 
@@ -3267,7 +3295,7 @@ template <int NX> static auto pipeline_kernel(bool help, bool masked) {      // 
 }
 // per handle: the dynamic-LDS limit belongs to the function object of the handle's device
 template <int NX> static int set_lds_limits(mpc_handle* h, size_t ric_lds) {
-    std::vector<const void*> fs = {reinterpret_cast<const void*>(&k_start<NX>), reinterpret_cast<const void*>(&k_prestart_par<NX>)};
+    std::vector<const void*> fs = {reinterpret_cast<const void*>(&k_start<NX>), reinterpret_cast<const void*>(&k_start<NX, true>), reinterpret_cast<const void*>(&k_prestart_par<NX>)};
     for (int a = 0; a < 2; ++a)
         for (int b = 0; b < 2; ++b) {
             for (int c = 0; c < 2; ++c) fs.push_back(reinterpret_cast<const void*>(stage_kernel<NX>(a, b, c)));
@@ -3369,15 +3397,20 @@ static int solve_front(Solve& s) {
     const int B = s.io.B, ntiles = pl.ntiles, G = pl.G;
     const size_t Bp = (size_t)ntiles * 64;
     hipStream_t stream = s.stream; Params& P = s.P;
-    fill_params(P, h->hp, B, Bp, pl.bx, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox);
+    fill_params(P, h->hp, B, Bp, pl.bx, h->d_ws, h->d_iws, h->d_LB, h->d_UB, h->ws_mailbox, h->ws_obst_stages);
     if (s.call.level) { P.ol = s.call.level->ol; P.tol = s.call.level->tol; }
     P.mbw_live = 0;
     P.x0 = io.x0; P.p = io.p; P.x_out = io.x_out; P.status_out = io.status; P.iters_out = io.iters; P.kkt_out = io.kkt;
-    s.w = ws_layout(d.N, d.nx, Bp, h->ws_mailbox);
+    s.w = ws_layout(d.N, d.nx, Bp, h->ws_mailbox, h->ws_obst_stages);
     const WsLayout& w = s.w;
-    if (io.obst) {
-        P.per_inst_obst = 1;
+    if (pl.poison)            // (debugging aid: NaN into every row of every tile of the workspace before the solve -- and before the obstacle rows go in)
+        hipLaunchKernelGGL(k_poison, dim3(1024), dim3(256), 0, stream, h->d_ws, (uint32_t)w.tile_elems, (uint32_t)w.ntiles, 0u, (uint32_t)w.rows * 64u);
+    P.per_inst_obst = io.obst_mode();
+    if (P.per_inst_obst == OBST_PER_INSTANCE)
         hipLaunchKernelGGL(k_transpose_obst, dim3((B + 255) / 256), dim3(256), 0, stream, io.obst, h->d_ws + w.OBST * 64, B, (uint32_t)w.tile_elems);
+    if (P.per_inst_obst == OBST_PER_STAGE) {          // (solve_dev_impl has asked ensure_ws for the section)
+        const ObstXpose X{io.obst, h->d_ws + w.OBST * 64, B, d.N + 1, (uint32_t)w.tile_elems};
+        hipLaunchKernelGGL(k_transpose_obst_stages, dim3(ntiles, (d.N + OBST_XP_KC) / OBST_XP_KC), dim3(256), 0, stream, X);
     }
     if (!h->attr_set) { const int rc = set_lds_limits<NX>(h, pl.ric_lds); if (rc) return rc; }
     for (int g = 0; g < G; ++g) {
@@ -3394,8 +3427,6 @@ static int solve_front(Solve& s) {
         HIP_TRY(h, hipEventRecord(h->ev_fork, stream));
         for (int g = 0; g < G; ++g) HIP_TRY(h, hipStreamWaitEvent(h->sub_stream[g], h->ev_fork, 0));
     }
-    if (pl.poison)            // (debugging aid: NaN into every row of every tile of the workspace before the solve)
-        hipLaunchKernelGGL(k_poison, dim3(1024), dim3(256), 0, stream, h->d_ws, (uint32_t)w.tile_elems, (uint32_t)w.ntiles, 0u, (uint32_t)w.rows * 64u);
     if (h->tile_mask_cap < (size_t)ntiles) {
         if (h->d_tile_mask) (void)hipFree(h->d_tile_mask);
         h->d_tile_mask = nullptr;
@@ -3436,7 +3467,9 @@ static int solve_front(Solve& s) {
             // (one launch for ingest, safeguard and start iterate: same blocks, same threads)
             DevTmp t_sdbg;
             if (pl.start_timing && stamp_rows(t_sdbg, q.nblk, q.st) == hipSuccess) Pg.DBG = t_sdbg.as<unsigned long long>();
-            hipLaunchKernelGGL((k_start<NX>), dim3(q.nblk), dim3(pl.threads), pl.lds_start, q.st, Pg, h->hp.n_mult, h->hp.n_z, pl.stash_rows,
+            // (a per-stage solve: the twin whose start iterate reads the stage's own obstacle rows)
+            const auto kf = P.per_inst_obst == OBST_PER_STAGE ? &k_start<NX, true> : &k_start<NX>;
+            hipLaunchKernelGGL(kf, dim3(q.nblk), dim3(pl.threads), pl.lds_start, q.st, Pg, h->hp.n_mult, h->hp.n_z, pl.stash_rows,
                                g == 0 ? zero_next : (uint32_t*)nullptr, (uint32_t)ctl_words);
             if (g == 0 && zero_next != nullptr) next_zeroed = true;
             if (Pg.DBG) (void)report_stamps(Pg.DBG, (size_t)STAMP_SLOTS * q.nblk, [&](const unsigned long long* r) { return format_start_timing(r, q.nblk); }, q.st);
@@ -3648,11 +3681,11 @@ template <int NX>
 static int solve_dev_impl(mpc_handle* h, const SolveIo& io, const SolveCall& call, SolveOutcome& out) {
     out = SolveOutcome{};
     Solve s{h, call, call.stream, io, out}; s.prof.h = h; s.prof.s = call.stream;
-    PlanState ps = plan_state(h, io.B, io.obst != nullptr, io.trace.out != nullptr, call);
+    PlanState ps = plan_state(h, io.B, io.obst_mode(), io.trace.out != nullptr, call);
     s.pl = plan_solve(h->hp, h->knobs, ps);
     // tile-major layout: the rows of a tile do not depend on the batch size, so a smaller batch lives in the first tiles of
     // a larger allocation (grow-only; the rescue path alternates between the full batch and a failed subset)
-    int rc = ensure_ws(h, (size_t)s.pl.ntiles * 64, s.pl.mailbox); if (rc) return rc;
+    int rc = ensure_ws(h, (size_t)s.pl.ntiles * 64, s.pl.mailbox, io.obst_mode() == OBST_PER_STAGE); if (rc) return rc;
     if (ps.ws_mailbox != h->ws_mailbox) { ps.ws_mailbox = h->ws_mailbox; s.pl = plan_solve(h->hp, h->knobs, ps); }
     if ((rc = solve_front<NX>(s))) return rc;
     rc = s.pl.res_path ? solve_wg_alone<NX>(s) : s.pl.pipe_path ? solve_pipeline<NX>(s) : solve_per_kernel<NX>(s);
@@ -3677,13 +3710,13 @@ static int solve_dev_any(mpc_handle* h, const SolveIo& io, const SolveCall& call
 // ---- multipliers of a solve (mpc_solve_batch_ex): read back from the workspace behind the solve, the loop kernels are not touched -------
 // Before a solve whose multipliers will be read: the workspace in place (what solve_dev_impl would allocate) and the mailbox copy of the
 // iterate NaN, so that k_mult_out tells by the primal rows which instances k_solve_wg served in THIS solve.
-static int mult_prepare(mpc_handle* h, int32_t B, hipStream_t stream) {
+static int mult_prepare(mpc_handle* h, int32_t B, bool obst_stages, hipStream_t stream) {
     const mpc_problem_desc& d = h->hp.desc;
     const size_t Bp = ((size_t)B + 63) / 64 * 64;
-    const int rc = ensure_ws(h, Bp, plan_solve(h->hp, h->knobs, plan_state(h, B, false, false)).mailbox);
+    const int rc = ensure_ws(h, Bp, plan_solve(h->hp, h->knobs, plan_state(h, B, OBST_SHARED, false)).mailbox, obst_stages);
     if (rc) return rc;
     if (h->ws_mailbox) {
-        const WsLayout w = ws_layout(d.N, d.nx, Bp, true);
+        const WsLayout w = ws_layout(d.N, d.nx, Bp, true, h->ws_obst_stages);
         HIP_TRY(h, hipMemsetAsync(h->d_ws + w.MZ, 0xFF, Bp * (size_t)(d.N + 1) * MPC_EV(d.nx + 2) * sizeof(double), stream));
     }
     return MPC_OK;
@@ -3729,7 +3762,7 @@ static int rescue_dev(mpc_handle* h, const SolveIo& io, hipStream_t stream, int&
         // the sub-batch, one allocation: [x0 | p | x_out | obst | kkt | status | iters] rows of a level, accumulated iterations -- every part
         // starts where SolveIo::rows puts the end of the one before it
         const size_t nw = io.n_w, ng = io.n_g;
-        double* buf = static_cast<double*>(scratch_get(h, SCR_RESC_BUF, ((size_t)n * (3 * nw + 6 + 1)) * 8 + (size_t)n * 3 * 4 + 64));
+        double* buf = static_cast<double*>(scratch_get(h, SCR_RESC_BUF, ((size_t)n * (3 * nw + io.n_obst + 1)) * 8 + (size_t)n * 3 * 4 + 64));
         if (!buf) { h->err = "rescue: out of device memory"; return MPC_ERR_HIP; }
         SolveIo sub = io.rows(0, n);
         sub.lam_g = sub.lam_x = nullptr;
@@ -3738,7 +3771,7 @@ static int rescue_dev(mpc_handle* h, const SolveIo& io, hipStream_t stream, int&
         sub.x0 = xs; sub.p = ps = const_cast<double*>(end().x0); sub.x_out = const_cast<double*>(end().p); sub.obst = os = end().x_out;
         sub.kkt = const_cast<double*>(end().obst); sub.status = reinterpret_cast<int32_t*>(end().kkt); sub.iters = end().status;
         int32_t* const acc = end().iters;
-        hipLaunchKernelGGL(k_rescue_gather, dim3(n), dim3(128), 0, stream, idx, (int)nw, io.x0, io.p, io.obst, xs, ps, os, acc);
+        hipLaunchKernelGGL(k_rescue_gather, dim3(n), dim3(128), 0, stream, idx, (int)nw, io.x0, io.p, io.obst, (int)io.n_obst, xs, ps, os, acc);
         if (!io.obst) sub.obst = nullptr;
         const double* fr = pass == 0 ? pass1 : pass2;
         const int nfr = pass == 0 ? 2 : 5;
@@ -3753,7 +3786,7 @@ static int rescue_dev(mpc_handle* h, const SolveIo& io, hipStream_t stream, int&
             // (... as hp holds it: relax_lo(1.0 * ol_raw) is hp.ol by set_bound_rows, the tolerance hp.desc.tol -- so mult_prepare, mult_read and
             //  sens_read, which build their Params from hp, read the last level's solve with the bound and the tolerance it ran with)
             const Level level{relax_lo(fr[q] * h->hp.ol_raw), last ? h->hp.desc.tol : std::max(h->hp.desc.tol, 1e-4)};
-            if ((sub.lam_g || sub.snap) && last) rc = mult_prepare(h, n, stream);
+            if ((sub.lam_g || sub.snap) && last) rc = mult_prepare(h, n, sub.obst_mode() == OBST_PER_STAGE, stream);
             if (rc != MPC_OK) break;
             rc = solve_dev_any(h, sub, SolveCall{stream, &level, false}, last_level);
             if (rc == MPC_OK && sub.lam_g && last) rc = mult_read(h, sub, stream);
@@ -3781,7 +3814,10 @@ static void keep_outcome(mpc_handle* h, const SolveOutcome& o) {      // what th
 static int solve_dev(mpc_handle* h, SolveIo io, hipStream_t stream) {
     const int32_t B = io.B;
     h->rescued_last = 0;
-    const SolvePlan pl = plan_solve(h->hp, h->knobs, plan_state(h, B, io.obst != nullptr, io.trace.out != nullptr));
+    SolvePlan pl = plan_solve(h->hp, h->knobs, plan_state(h, B, io.obst_mode(), io.trace.out != nullptr));
+    // (per-stage obstacle rows: the plan is the per-instance one; the workspace limit of the chunks counts the larger obstacle section)
+    if (io.obst_mode() == OBST_PER_STAGE)
+        pl.max_rows = std::min(pl.max_rows, (((size_t)1 << 32) - 1) / (ws_layout(h->hp.desc.N, h->hp.desc.nx, 64, pl.mailbox, true).total * sizeof(double)) * 64);
     // the second chance and the multipliers read the per-instance status
     if (pl.rescue || io.lam_g) { const int rs = supply_status(h, io); if (rs) return rs; }
     // The workspace is addressed with 32-bit buffer offsets (< 4 GiB): a batch beyond that is solved in chunks of whole tiles, one after
@@ -3796,7 +3832,7 @@ static int solve_dev(mpc_handle* h, SolveIo io, hipStream_t stream) {
         h->rescued_last = rescued;
         return MPC_OK;
     }
-    if (io.lam_g || io.snap) { const int rm = mult_prepare(h, B, stream); if (rm) return rm; }
+    if (io.lam_g || io.snap) { const int rm = mult_prepare(h, B, io.obst_mode() == OBST_PER_STAGE, stream); if (rm) return rm; }
     SolveOutcome out;
     int rc = solve_dev_any(h, io, SolveCall{stream}, out);
     keep_outcome(h, out);
@@ -3828,6 +3864,34 @@ static int ensure_io(mpc_handle* h, size_t B) {
     return MPC_OK;
 }
 
+// objective and constraint rows of the reference's NLP at B points (k_eval_nlp); f / g may be null; obst_stages: d_obst is [B, N+1, 6]
+static int eval_nlp_dev(mpc_handle* h, int32_t B, const double* d_x, const double* d_p, const double* d_obst, bool obst_stages, double* d_f, double* d_g,
+                        hipStream_t stream) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !d_x || !d_p) { h->err = "B > 0 and x, p are required"; return MPC_ERR_INVALID; }
+    if (!nlp_horizon_ok(h)) return MPC_ERR_INVALID;
+    if (!d_f && !d_g) return MPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    FOR_NX(h, hipLaunchKernelGGL((k_eval_nlp<NX>), nlp_out_grid(h, B), dim3(NLP_OUT_THREADS), 0, stream, rows_params(h, B, false), d_x, d_p, d_obst,
+                                 obst_stages ? 1 : 0, d_f, d_g));
+    HIP_TRY(h, hipGetLastError());
+    return MPC_OK;
+}
+static int eval_nlp_host(mpc_handle* h, int32_t B, const double* x, const double* p, const double* obst, bool obst_stages, double* f, double* g) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || !x || !p) { h->err = "B > 0 and x, p are required"; return MPC_ERR_INVALID; }
+    if (!f && !g) return MPC_OK;
+    const size_t nw = h->hp.n_w(), nB = (size_t)B, ng = h->hp.n_g(), no = obst_stages ? (size_t)6 * (h->hp.desc.N + 1) : 6;
+    return stage_host(h, {{x, nB * nw * 8, false}, {p, nB * nw * 8, false}, {obst, nB * no * 8, false}, {f, nB * 8, true}, {g, nB * ng * 8, true}},
+                      [&](void** d, hipStream_t s) { return eval_nlp_dev(h, B, (double*)d[0], (double*)d[1], (double*)d[2], obst_stages, (double*)d[3], (double*)d[4], s); });
+}
+// the rows of a per-stage solve: obst is [B, N+1, 6]
+static const char* const STAGES_NEED_OBST = "per-stage obstacle rows: obst [B, N+1, 6] is required";
+static SolveIo stages_io(const mpc_handle* h, SolveIo io) {
+    if (h) io.n_obst = (size_t)6 * (size_t)(h->hp.desc.N + 1);
+    return io;
+}
+
 // solve_dev plus the NLP's objective / rows at the returned x and the multipliers of the final iterate (io.lam_g, io.lam_x; all four
 // optional; none asked for: exactly solve_dev, nothing synchronised here)
 static int solve_ex_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, hipStream_t s) {
@@ -3840,7 +3904,7 @@ static int solve_ex_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, hip
         if (!io.lam_g || !io.lam_x) { h->err = "out of device memory"; return MPC_ERR_HIP; }
     }
     int rc = solve_dev(h, io, s);
-    if (rc == MPC_OK && (d_f || d_g)) rc = mpc_eval_nlp_batch_dev(h, io.B, io.x_out, io.p, io.obst, d_f, d_g, (void*)s);
+    if (rc == MPC_OK && (d_f || d_g)) rc = eval_nlp_dev(h, io.B, io.x_out, io.p, io.obst, io.obst_mode() == OBST_PER_STAGE, d_f, d_g, s);
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));
     return MPC_OK;
@@ -3965,23 +4029,40 @@ int mpc_solve_batch_trace(mpc_handle* h, int32_t B, const double* x0, const doub
 // objective and constraint rows of the reference's NLP at B points (k_eval_nlp); f / g may be null
 int mpc_eval_nlp_batch_dev(mpc_handle* h, int32_t B, const double* d_x, const double* d_p, const double* d_obst, double* d_f, double* d_g,
                            void* stream_) {
+    return eval_nlp_dev(h, B, d_x, d_p, d_obst, false, d_f, d_g, (hipStream_t)stream_);
+}
+int mpc_eval_nlp_batch(mpc_handle* h, int32_t B, const double* x, const double* p, const double* obst, double* f, double* g) {
+    return eval_nlp_host(h, B, x, p, obst, false, f, g);
+}
+// ... with obstacle rows per stage, obst [B, N+1, 6] (required)
+int mpc_eval_nlp_batch_stages_dev(mpc_handle* h, int32_t B, const double* d_x, const double* d_p, const double* d_obst, double* d_f, double* d_g,
+                                  void* stream_) {
     if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !d_x || !d_p) { h->err = "B > 0 and x, p are required"; return MPC_ERR_INVALID; }
-    if (!nlp_horizon_ok(h)) return MPC_ERR_INVALID;
-    if (!d_f && !d_g) return MPC_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    FOR_NX(h, hipLaunchKernelGGL((k_eval_nlp<NX>), nlp_out_grid(h, B), dim3(NLP_OUT_THREADS), 0, (hipStream_t)stream_, rows_params(h, B, false), d_x, d_p, d_obst, d_f, d_g));
-    HIP_TRY(h, hipGetLastError());
-    return MPC_OK;
+    if (!d_obst) { h->err = STAGES_NEED_OBST; return MPC_ERR_INVALID; }
+    return eval_nlp_dev(h, B, d_x, d_p, d_obst, true, d_f, d_g, (hipStream_t)stream_);
+}
+int mpc_eval_nlp_batch_stages(mpc_handle* h, int32_t B, const double* x, const double* p, const double* obst, double* f, double* g) {
+    if (!h) return MPC_ERR_INVALID;
+    if (!obst) { h->err = STAGES_NEED_OBST; return MPC_ERR_INVALID; }
+    return eval_nlp_host(h, B, x, p, obst, true, f, g);
 }
 
-int mpc_eval_nlp_batch(mpc_handle* h, int32_t B, const double* x, const double* p, const double* obst, double* f, double* g) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || !x || !p) { h->err = "B > 0 and x, p are required"; return MPC_ERR_INVALID; }
-    if (!f && !g) return MPC_OK;
-    const size_t nw = h->hp.n_w(), nB = (size_t)B, ng = h->hp.n_g();
-    return stage_host(h, {{x, nB * nw * 8, false}, {p, nB * nw * 8, false}, {obst, nB * 6 * 8, false}, {f, nB * 8, true}, {g, nB * ng * 8, true}},
-                      [&](void** d, hipStream_t s) { return mpc_eval_nlp_batch_dev(h, B, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], s); });
+// mpc_solve_batch[_dev]_ex with obstacle rows per stage, obst [B, N+1, 6] (required): no sensitivity snapshot is taken, and begin_solve has ended
+// the life of an earlier one
+int mpc_solve_batch_stages_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
+                               int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
+                               void* stream_) {
+    const SolveIo io = stages_io(h, solve_io(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_lam_g, d_lam_x));
+    const int rc = begin_solve(h, io, d_obst ? nullptr : STAGES_NEED_OBST);
+    return rc ? rc : solve_ex_dev(h, io, d_f, d_g, (hipStream_t)stream_);
+}
+int mpc_solve_batch_stages(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, double* x_out, int32_t* status,
+                           int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x) {
+    const SolveIo io = stages_io(h, solve_io(h, B, x0, p, obst, x_out, status, iters, kkt, lam_g, lam_x));
+    const int rc = begin_solve(h, io, obst ? nullptr : STAGES_NEED_OBST);
+    if (rc) return rc;
+    return stage_solve(h, io, {{f, (size_t)B * 8, true}, {g, (size_t)B * io.n_g * 8, true}},
+                       [&](const SolveIo& dio, void** m, hipStream_t s) { return solve_ex_dev(h, dio, (double*)m[0], (double*)m[1], s); });
 }
 
 int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
@@ -4100,7 +4181,8 @@ int mpc_plant_step(mpc_handle* h, int32_t B, int32_t integrator, const double* x
 }
 
 // per-ego obstacle tracks of a closed loop (mpc_closed_loop_batch_obst[_dev]); the plain loop has none
-struct LoopTrack { int32_t Lt; const double* d_track; double offset; double* d_clearance; };
+// predict (mpc_closed_loop_batch_pred): stage k of the solve of step i sees track row min(i + k, Lt - 1) instead of row i
+struct LoopTrack { int32_t Lt; const double* d_track; double offset; double* d_clearance; int32_t predict = 0; };
 
 // the closed loop of every entry point, with `track` (k_loop_obst in front of every solve, whose rows then carry the obstacle centres) or without;
 // with `lin` (mpc_closed_loop_batch_lin_dev has checked it) step by step, every solve leaving its snapshot and the gain kernels of the families asked for behind
@@ -4123,9 +4205,12 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
     int rc = ensure_io(h, (size_t)B);
     if (rc) return rc;
     double* d_obst = nullptr;
-    if (track && !(d_obst = static_cast<double*>(scratch_get(h, SCR_LOOP_OBST, (size_t)B * 6 * sizeof(double))))) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    const bool predict = track && track->predict != 0;
+    const size_t n_obst = predict ? (size_t)6 * (size_t)(d.N + 1) : 6;
+    if (track && !(d_obst = static_cast<double*>(scratch_get(h, SCR_LOOP_OBST, (size_t)B * n_obst * sizeof(double))))) { h->err = "out of device memory"; return MPC_ERR_HIP; }
     // the rows of every solve of the loop: the handle's own (begin_solve: the bounds must be set)
-    const SolveIo io = solve_io(h, B, h->d_x0, h->d_p, d_obst, h->d_xout, h->d_status, h->d_iters, h->d_kkt);
+    SolveIo io = solve_io(h, B, h->d_x0, h->d_p, d_obst, h->d_xout, h->d_status, h->d_iters, h->d_kkt);
+    if (predict) io = stages_io(h, io);
     if ((rc = begin_solve(h, io))) return rc;
     if (h->cap_state < (size_t)B) {
         if (h->d_state) (void)hipFree(h->d_state);
@@ -4152,7 +4237,10 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
         O.r_sum = h->hp.ol_raw;
         PO.ego_offset = d.ego_offset;
     }
-    const auto place_obstacles = [&](int i) { if (track) hipLaunchKernelGGL(k_loop_obst, grid, block, 0, stream, PO, O, i); };
+    const auto place_obstacles = [&](int i) {
+        if (predict) hipLaunchKernelGGL(k_loop_obst_stages, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, PO, O, d.N, i);
+        else if (track) hipLaunchKernelGGL(k_loop_obst, grid, block, 0, stream, PO, O, i);
+    };
     if (lin) {
         // Step by step: the snapshot solve synchronises.  Its launch plan does not depend on the snapshot, so traj, ctrl and step_status are those
         // of the step-by-step loop below, bit for bit.  The snapshot is never marked valid: the sens entry points refuse after this loop as after any.
@@ -4186,7 +4274,7 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
     // that needs the second chance -- is recorded on the device and looked at ONCE, at the end; then the loop is replayed
     // step by step with the host in between (the per-kernel path polls for convergence, the second chance needs the count).
     bool replay = true, loop_abandoned = false;
-    if (plan_solve(h->hp, h->knobs, plan_state(h, B, track != nullptr, false)).loop_async) {
+    if (plan_solve(h->hp, h->knobs, plan_state(h, B, io.obst_mode(), false)).loop_async) {
         HIP_TRY(h, hipMemsetAsync(h->d_fail, 0, FAIL_WORDS * sizeof(uint32_t), stream));
         A.abort_flag = O.abort_flag = h->d_fail + FAIL_LOOP_ABORT;
         hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
@@ -4239,6 +4327,39 @@ int mpc_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t 
                                    double* d_clearance, void* stream_) {
     const LoopTrack track{Lt, d_obst_track, obst_offset, d_clearance};
     return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, &track, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, stream_);
+}
+
+// the loop past per-ego obstacles with the obstacle predicted over each solve's horizon (predict 1) or frozen (predict 0: the loop above)
+static const char* const PRED_REFUSAL = "closed loop: predict is 0 (the obstacle frozen over each solve's horizon) or 1 (stage k sees track row min(i + k, Lt - 1))";
+int mpc_closed_loop_batch_pred_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                   const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
+                                   int32_t predict, int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl,
+                                   int32_t* d_step_status, double* d_clearance, void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    if (predict != 0 && predict != 1) { h->err = PRED_REFUSAL; return MPC_ERR_INVALID; }
+    if (predict && (Lt <= 0 || !d_obst_track)) { h->err = "closed loop: predict 1 needs obst_track [B, Lt, 3] with Lt >= 1"; return MPC_ERR_INVALID; }
+    const LoopTrack track{Lt, d_obst_track, obst_offset, d_clearance, predict};
+    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, &track, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, stream_);
+}
+
+int mpc_closed_loop_batch_pred(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                               const double* vdes, int32_t Lt, const double* obst_track, double obst_offset, int32_t predict, int32_t noise_mode,
+                               double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
+    if (predict != 0 && predict != 1) { h->err = PRED_REFUSAL; return MPC_ERR_INVALID; }
+    if (predict && (Lt <= 0 || !obst_track)) { h->err = "closed loop: predict 1 needs obst_track [B, Lt, 3] with Lt >= 1"; return MPC_ERR_INVALID; }
+    if (!obst_track || (Lt != 1 && Lt < L)) {
+        h->err = "closed loop: obst_track [B, Lt, 3] is required, with Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i)";
+        return MPC_ERR_INVALID;
+    }
+    const size_t nB = (size_t)B;
+    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
+                          {obst_track, nB * Lt * 3 * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true}, {step_status, nB * L * 4, true},
+                          {clearance, nB * L * 8, true}}, [&](void** d, hipStream_t s) {
+        return mpc_closed_loop_batch_pred_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], obst_offset, predict,
+                                              noise_mode, sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], (double*)d[8], s);
+    });
 }
 
 int mpc_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,

@@ -129,7 +129,8 @@ class NlpSolverHandle:
         self._stats = {}
 
     def __call__(self, x0=None, p=None, lbg=None, lbx=None, ubg=None, ubx=None, obst=None, **_unused):
-        """obst (not a CasADi keyword): circle centres [6] / [B, 6] of this solve's obstacle instead of the template's (BatchedMPCSolver.solve)"""
+        """obst (not a CasADi keyword): circle centres [6] / [B, 6] of this solve's obstacle instead of the template's, or [N+1, 6] / [B, N+1, 6]:
+        centres per stage (BatchedMPCSolver.solve)"""
         be = self._backend
         x0a = np.asarray(x0.full() if hasattr(x0, "full") else x0, dtype=np.float64)
         pa = np.asarray(p.full() if hasattr(p, "full") else p, dtype=np.float64)
@@ -141,7 +142,10 @@ class NlpSolverHandle:
         if lbg is not None or lbx is not None or ubg is not None or ubx is not None:
             be.set_bounds(lbx, ubx, lbg, ubg)
         full = isinstance(be, BatchedMPCSolver)
-        kw = {} if obst is None else dict(obst=np.asarray(obst, dtype=np.float64).reshape(x0a.shape[0], 6))
+        kw = {}
+        if obst is not None:
+            oa = np.asarray(obst, dtype=np.float64)
+            kw = dict(obst=oa.reshape(x0a.shape[0], 6) if oa.size == 6 * x0a.shape[0] else oa.reshape(x0a.shape[0], -1, 6))
         res = be.solve(x0a, pa, multipliers=True, **kw) if full else be.solve(x0a, pa, **kw)
         rescued = np.zeros(res.status.shape[0], dtype=bool)
         n_rescued = int(be.last_rescued()) if hasattr(be, "last_rescued") else 0      # the second chance behind the C-ABI (a count, not a mask)

@@ -214,7 +214,7 @@ class BatchedMPCSolver:
         return np.array([self.desc.Q[i] for i in range(5)] + [self.desc.R[0], self.desc.R[1]])
 
     def _rows_in(self, name, x, p, obst):
-        """(B, x [B, n_w], p [B, n_w], obst [B, 6] | None) as contiguous doubles; a single instance may come as vectors"""
+        """(B, x [B, n_w], p [B, n_w], obst [B, 6] | [B, N+1, 6] | None) as contiguous doubles; a single instance may come as vectors"""
         x, p = _abi.f64(x), _abi.f64(p)
         if x.ndim == 1:
             x = x[None]
@@ -223,6 +223,11 @@ class BatchedMPCSolver:
         B = x.shape[0]
         if x.shape != (B, self.n_w) or p.shape != (B, self.n_w):
             raise MpcError(_abi.MPC_ERR_INVALID, f"{name}/p must be [B, {self.n_w}]")
+        if obst is not None and np.ndim(obst) == 3:            # centres per stage (mpc_solve_batch_stages)
+            obst = _abi.f64(obst)
+            if obst.shape != (B, self.N + 1, 6):
+                raise MpcError(_abi.MPC_ERR_INVALID, f"obst per stage must be [B, {self.N + 1}, 6]")
+            return B, x, p, obst
         return B, x, p, None if obst is None else _abi.f64(obst, (B, 6))
 
     def _nlp_out(self, B):
@@ -230,22 +235,34 @@ class BatchedMPCSolver:
         return np.empty(B), np.empty((B, self.n_g)), np.empty((B, self.n_g)), np.empty((B, self.n_w))
 
     def eval_nlp(self, x, p, obst=None):
-        """objective f [B] and constraint rows g [B, n_g] of the reference's NLP at any x [B, n_w] (mpc_eval_nlp_batch)."""
+        """objective f [B] and constraint rows g [B, n_g] of the reference's NLP at any x [B, n_w] (mpc_eval_nlp_batch); obst [B, 6], or
+        [B, N+1, 6]: every stage against centres of its own (mpc_eval_nlp_batch_stages)."""
         B, x, p, obst = self._rows_in("x", x, p, obst)
         f, g = np.empty(B), np.empty((B, self.n_g))
-        self._check(self._lib.mpc_eval_nlp_batch(self._h, B, _abi.as_dp(x), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(f), _abi.as_dp(g)))
+        fn = self._lib.mpc_eval_nlp_batch_stages if obst is not None and obst.ndim == 3 else self._lib.mpc_eval_nlp_batch
+        self._check(fn(self._h, B, _abi.as_dp(x), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(f), _abi.as_dp(g)))
         return f, g
 
     def solve(self, x0, p, obst=None, *, multipliers=False, lam_p=False, dp=None) -> SolveResult:
         """B instances at once.  multipliers=True: also f, g at the returned x and the multipliers lam_g, lam_x (CasADi's convention:
         grad f + J_g' lam_g + lam_x = 0) in the result (mpc_solve_batch_ex).  lam_p=True: CasADi's lam_p; dp [B, n_dir, n_p] (or [B, n_p]):
         forward sensitivities dw = (dw*/dp) dp of the optimum (mpc_solve_batch_sens, which also keeps the final iterates for sens_adjoint).
-        p = [U_ref | X_ref], n_p = n_w."""
+        p = [U_ref | X_ref], n_p = n_w.  obst [B, 6]: obstacle centres per instance; [B, N+1, 6]: per instance and stage, an obstacle that
+        moves over the horizon (mpc_solve_batch_stages) -- no derivatives: lam_p / dp raise, and a later sens_* finds no snapshot."""
         B, x0, p, obst = self._rows_in("x0", x0, p, obst)
         out = np.empty_like(x0)
         status = np.empty(B, np.int32)
         iters = np.empty(B, np.int32)
         kkt = np.empty(B, np.float64)
+        if obst is not None and obst.ndim == 3:
+            if lam_p or dp is not None:
+                raise MpcError(_abi.MPC_ERR_INVALID, "derivatives of a solve with obstacle centres per stage are not provided (obst [B, N+1, 6])")
+            self._sens_gen += 1                              # (the library has ended the life of an earlier snapshot)
+            f, g, lam_g, lam_x = self._nlp_out(B) if multipliers else (None,) * 4
+            self._check(self._lib.mpc_solve_batch_stages(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out),
+                                                         _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt), _abi.as_dp(f), _abi.as_dp(g),
+                                                         _abi.as_dp(lam_g), _abi.as_dp(lam_x)))
+            return SolveResult(out, status, iters, kkt, f, g, lam_g, lam_x)
         if lam_p or dp is not None:
             return self._solve_sens(x0, p, obst, out, status, iters, kkt, multipliers, lam_p, dp)
         if not multipliers:
@@ -435,13 +452,19 @@ class BatchedMPCSolver:
         return [self._h, int(B), _vp(d_x0), _vp(d_p), _vp(d_obst), _vp(d_x_out), _vp(d_status), _vp(d_iters), _vp(d_kkt)]
 
     def solve_device(self, B, d_x0, d_p, d_x_out, d_status=0, d_iters=0, d_kkt=0, d_obst=0, stream=0, d_f=0, d_g=0, d_lam_g=0, d_lam_x=0,
-                     d_lam_p=0, n_dir=0, d_dp=0, d_dw=0):
+                     d_lam_p=0, n_dir=0, d_dp=0, d_dw=0, obst_stages=False):
         """device pointers (ints, e.g. torch.Tensor.data_ptr()) and a hipStream_t handle (int, 0 = default).  d_f [B], d_g / d_lam_g
         [B, n_g], d_lam_x [B, n_w]: the extra outputs of mpc_solve_batch_dev_ex (0 = not asked for).  d_lam_p [B, n_p], n_dir > 0 with
-        d_dp [B, n_dir, n_p] -> d_dw [B, n_dir, n_w]: mpc_solve_batch_sens_dev (keeps the final iterates for sens_adjoint_device)."""
+        d_dp [B, n_dir, n_p] -> d_dw [B, n_dir, n_w]: mpc_solve_batch_sens_dev (keeps the final iterates for sens_adjoint_device).
+        obst_stages=True: d_obst is [B, N+1, 6], centres per stage (mpc_solve_batch_stages_dev; no sensitivity outputs)."""
         rows = self._dev_rows(B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt)
         extra = [_vp(d_f), _vp(d_g), _vp(d_lam_g), _vp(d_lam_x)]
-        if d_lam_p or n_dir:
+        if obst_stages:
+            if d_lam_p or n_dir:
+                raise MpcError(_abi.MPC_ERR_INVALID, "derivatives of a solve with obstacle centres per stage are not provided (obst_stages)")
+            self._sens_gen += 1
+            self._check(self._lib.mpc_solve_batch_stages_dev(*rows, *extra, _vp(stream)))
+        elif d_lam_p or n_dir:
             self._sens_gen += 1
             self._sens_B = int(B)
             self._check(self._lib.mpc_solve_batch_sens_dev(*rows, *extra, _vp(d_lam_p), int(n_dir), _vp(d_dp), _vp(d_dw), _vp(stream)))
@@ -493,7 +516,7 @@ class BatchedMPCSolver:
         return out[0] if single else out
 
     def closed_loop(self, init_state, path, orient, vdes, steps, noise_mode=0, sigma=0.0, seed=0, obst_track=None, obst_offset=0.0, clearance=False,
-                    linearize=False):
+                    linearize=False, predict=False):
         """B egos through `steps` receding-horizon steps on the device (include/mpcgpu.h: mpc_closed_loop_batch_ex; the loop
         body of CasadiOptimizer.optimize, optimizer.py:596-631).  init_state [B,5], path [B,Lp,2], orient [B,Lp],
         vdes [B] -> (traj [B,steps,5], ctrl [B,steps,2], step_status [B,steps]).  noise_mode / sigma / seed: the reference's
@@ -501,6 +524,8 @@ class BatchedMPCSolver:
         obst_track [B,Lt,3] (x, y, heading; Lt = 1: standing still, Lt >= steps: row i at step i; [B,3] = Lt 1): every ego past an obstacle of
         its own, frozen over each solve's horizon (mpc_closed_loop_batch_obst); obst_offset: its front / rear circle centres along the heading.
         clearance=True (with a track): a fourth return value [B,steps], see include/mpcgpu.h.
+        predict=True (with a track): the obstacle predicted over each solve's horizon instead -- stage k of the solve of step i sees track row
+        min(i + k, Lt - 1) (mpc_closed_loop_batch_pred); not with linearize.
         linearize=True: a LoopLin instead -- the same rollout, step by step, with the gains kgain, wgain and (with a track) ogain of every step
         (mpc_closed_loop_batch_lin), what loop_tangent / loop_adjoint sweep over."""
         init_state = _abi.f64(init_state)
@@ -516,6 +541,8 @@ class BatchedMPCSolver:
         ctrl = np.empty((B, steps, 2))
         st = np.empty((B, steps), np.int32)
         tail = (int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), _abi.as_dp(traj), _abi.as_dp(ctrl), _abi.as_ip(st))
+        if predict and (obst_track is None or linearize):
+            raise MpcError(_abi.MPC_ERR_INVALID, "predict needs obst_track, and the linearised loop has no predicted form")
         if obst_track is None:
             if clearance:
                 raise MpcError(_abi.MPC_ERR_INVALID, "clearance needs obst_track")
@@ -541,17 +568,25 @@ class BatchedMPCSolver:
                                                             _abi.as_dp(vdes), track.shape[1], _abi.as_dp(track), float(obst_offset), *tail, _abi.as_dp(cl),
                                                             _abi.as_dp(kg), _abi.as_dp(wg), _abi.as_dp(og)))
             return LoopLin(traj, ctrl, st, kg, wg, og, cl, track.shape[1])
+        if predict:
+            self._check(self._lib.mpc_closed_loop_batch_pred(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient),
+                                                             _abi.as_dp(vdes), track.shape[1], _abi.as_dp(track), float(obst_offset), int(predict), *tail,
+                                                             _abi.as_dp(cl)))
+            return (traj, ctrl, st, cl) if clearance else (traj, ctrl, st)
         self._check(self._lib.mpc_closed_loop_batch_obst(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient),
                                                          _abi.as_dp(vdes), track.shape[1], _abi.as_dp(track), float(obst_offset), *tail, _abi.as_dp(cl)))
         return (traj, ctrl, st, cl) if clearance else (traj, ctrl, st)
 
     def closed_loop_device(self, B, d_init_state, d_path, d_orient, d_vdes, steps, Lp, d_traj, d_ctrl, d_step_status=0, noise_mode=0, sigma=0.0,
-                           seed=0, stream=0, d_obst_track=0, Lt=0, obst_offset=0.0, d_clearance=0):
+                           seed=0, stream=0, d_obst_track=0, Lt=0, obst_offset=0.0, d_clearance=0, predict=0):
         """device-pointer form (ints): the whole loop is enqueued on `stream`; see mpc_closed_loop_batch_dev_ex, and with d_obst_track [B,Lt,3]
-        (d_clearance [B,steps] or 0) mpc_closed_loop_batch_obst_dev"""
+        (d_clearance [B,steps] or 0) mpc_closed_loop_batch_obst_dev; predict != 0: mpc_closed_loop_batch_pred_dev with that value"""
         head = (self._h, int(B), int(steps), int(Lp), _vp(d_init_state), _vp(d_path), _vp(d_orient), _vp(d_vdes))
         tail = (int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl), _vp(d_step_status))
-        if d_obst_track or Lt:
+        if predict:
+            self._check(self._lib.mpc_closed_loop_batch_pred_dev(*head, int(Lt), _vp(d_obst_track), float(obst_offset), int(predict), *tail, _vp(d_clearance),
+                                                                 _vp(stream)))
+        elif d_obst_track or Lt:
             self._check(self._lib.mpc_closed_loop_batch_obst_dev(*head, int(Lt), _vp(d_obst_track), float(obst_offset), *tail, _vp(d_clearance), _vp(stream)))
         else:
             self._check(self._lib.mpc_closed_loop_batch_dev_ex(*head, *tail, _vp(stream)))
