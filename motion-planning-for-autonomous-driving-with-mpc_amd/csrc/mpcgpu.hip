@@ -2718,6 +2718,13 @@ __global__ void __launch_bounds__(SENS_THREADS) k_loop_adjoint(const Params P, c
     loop_adjoint_lane(P, A, b, seed_traj, seed_ctrl, grad_init, grad_wt, grad_track);
 }
 
+// The last update of either integrator is a fused multiply-add written out: left to the compiler's contraction, every component was fused but the
+// heading, whose addition the two branches share after tail merging (a product rounded, then a sum) -- one unit in the last place away from the
+// closed loop's own Euler step, so that a host loop over mpc_plant_step did not replay it.  The loop (loop_advance_instance, k_loop_advance -- code
+// shared with the host harness, where fma() would not be the hardware's) still writes x + h * f and is fused by contraction;
+// tests/test_gpu_descriptor.py holds it to this kernel bit for bit and fails if the compiler stops doing so.  The RK4 branch is NOT bit for bit the
+// FORCES loop's step (forces_loop_advance_instance): its stage sums and half steps contract differently in the two kernels (tried, last bits
+// differ); the loops' tests compare those at 1e-9
 template <int NX>
 __global__ void k_plant_step(const Params Pk, const double* x, const double* u, double* xn, int B, int integrator) {
     const PRef P(Pk);
@@ -2732,7 +2739,7 @@ __global__ void k_plant_step(const Params Pk, const double* x, const double* u, 
     if (integrator == 0) {
         ode_eval<NX>(P, xs, us, f, s, c, td);
 #pragma unroll
-        for (int i = 0; i < NX; ++i) xn[(size_t)b * NX + i] = xs[i] + h * f[i];
+        for (int i = 0; i < NX; ++i) xn[(size_t)b * NX + i] = fma(h, f[i], xs[i]);
     } else {
         double k1[NX], k2[NX], k3[NX], k4[NX], tmp[NX];
         ode_eval<NX>(P, xs, us, k1, s, c, td);
@@ -2746,7 +2753,7 @@ __global__ void k_plant_step(const Params Pk, const double* x, const double* u, 
         for (int i = 0; i < NX; ++i) tmp[i] = xs[i] + h * k3[i];
         ode_eval<NX>(P, tmp, us, k4, s, c, td);
 #pragma unroll
-        for (int i = 0; i < NX; ++i) xn[(size_t)b * NX + i] = xs[i] + h / 6.0 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+        for (int i = 0; i < NX; ++i) xn[(size_t)b * NX + i] = fma(h / 6.0, k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i], xs[i]);
     }
 }
 

@@ -56,7 +56,9 @@ def rk4_with_jacobian(z, dt=0.1, l=WHEELBASE_ODE):
     return c, J
 
 
-def stage_functions(z, p, terminal=False, weights=WEIGHTS_MODEL_C, dt=0.1):
+def stage_functions(z, p, terminal=False, weights=WEIGHTS_MODEL_C, dt=0.1, wheelbase=WHEELBASE_ODE, friction_div=WHEELBASE_FRICTION,
+                    ego_offset=EGO_OFFSET):
+    """wheelbase: l of the ODE; friction_div: the divisor of psi_dot in h[0]; ego_offset: front / rear circle centres along the heading"""
     z = np.asarray(z, dtype=np.float64)
     p = np.asarray(p, dtype=np.float64)
     Q, R, P = weights["Q"], weights["R"], weights["P"]
@@ -68,23 +70,23 @@ def stage_functions(z, p, terminal=False, weights=WEIGHTS_MODEL_C, dt=0.1):
     if not terminal:
         f += R[0] * z[0] ** 2 + R[1] * z[1] ** 2
         gf[0], gf[1] = 2 * R[0] * z[0], 2 * R[1] * z[1]
-    c, jc = (None, None) if terminal else rk4_with_jacobian(z, dt)
+    c, jc = (None, None) if terminal else rk4_with_jacobian(z, dt, wheelbase)
     h = np.zeros(10)
     jh = np.zeros((10, 7))
     td = np.tan(z[4])
-    q = z[5] * z[5] * td / WHEELBASE_FRICTION                    # v * psi_dot
+    q = z[5] * z[5] * td / friction_div                    # v * psi_dot
     h[0] = z[1] ** 2 + q ** 2
     jh[0, 1] = 2 * z[1]
-    jh[0, 4] = 2 * q * z[5] * z[5] / np.cos(z[4]) ** 2 / WHEELBASE_FRICTION
-    jh[0, 5] = 2 * q * 2 * z[5] * td / WHEELBASE_FRICTION
+    jh[0, 4] = 2 * q * z[5] * z[5] / np.cos(z[4]) ** 2 / friction_div
+    jh[0, 5] = 2 * q * 2 * z[5] * td / friction_div
     cs, sn = np.cos(z[6]), np.sin(z[6])
     for e, sg in enumerate((0.0, 1.0, -1.0)):                     # centre, front, rear circle (configuration.py:69-93)
-        ex, ey = z[2] + sg * EGO_OFFSET * cs, z[3] + sg * EGO_OFFSET * sn
+        ex, ey = z[2] + sg * ego_offset * cs, z[3] + sg * ego_offset * sn
         for j in range(3):
             ox, oy = p[4 + 2 * j], p[5 + 2 * j]
             row = 1 + 3 * e + j
             h[row] = (ex - ox) ** 2 + (ey - oy) ** 2
             jh[row, 2] = 2 * (ex - ox)
             jh[row, 3] = 2 * (ey - oy)
-            jh[row, 6] = 2 * (ex - ox) * (-sg * EGO_OFFSET * sn) + 2 * (ey - oy) * (sg * EGO_OFFSET * cs)
+            jh[row, 6] = 2 * (ex - ox) * (-sg * ego_offset * sn) + 2 * (ey - oy) * (sg * ego_offset * cs)
     return dict(f=f, grad_f=gf, c=c, jac_c=jc, h=h, jac_h=jh)

@@ -44,12 +44,14 @@ IPM_TOL = 1e-4          # residuals (dual, primal, equality); the accuracy an SQ
 IPM_TOL_MU = 1e-6       # complementarity gap
 
 
-def build_qp(zbar, params, xinit, lb, ub, hl, hu, weights=FM.WEIGHTS_MODEL_C, dt=0.1):
+def build_qp(zbar, params, xinit, lb, ub, hl, hu, weights=FM.WEIGHTS_MODEL_C, dt=0.1, wheelbase=FM.WHEELBASE_ODE, friction_div=FM.WHEELBASE_FRICTION,
+             ego_offset=FM.EGO_OFFSET):
     """zbar (N,7), params (N,10), xinit (5) -> list of per-stage dicts: g (7), C (5,7), c (5), G (m,7), d (m)  [G dz <= d]"""
     N = zbar.shape[0]
+    model = dict(weights=weights, dt=dt, wheelbase=wheelbase, friction_div=friction_div, ego_offset=ego_offset)
     st = []
     for k in range(N):
-        r = FM.stage_functions(zbar[k], params[k], terminal=(k == N - 1), weights=weights, dt=dt)
+        r = FM.stage_functions(zbar[k], params[k], terminal=(k == N - 1), **model)
         rows, rhs = [], []
         for i in range(7):
             if k == 0 and i >= 2:
@@ -71,7 +73,7 @@ def build_qp(zbar, params, xinit, lb, ub, hl, hu, weights=FM.WEIGHTS_MODEL_C, dt
                 rhs.append(r["h"][j] - hl[j])
         c, C = (None, None)
         if k < N - 1:
-            rr = FM.stage_functions(zbar[k], params[k], terminal=False, weights=weights, dt=dt)
+            rr = FM.stage_functions(zbar[k], params[k], terminal=False, **model)
             c, C = rr["c"], rr["jac_c"]
         st.append(dict(g=r["grad_f"], C=C, c=c, G=np.array(rows), d=np.array(rhs)))
     return st
@@ -163,7 +165,8 @@ def solve_qp(st, zbar, xinit, Hd, max_it=IPM_MAX_IT, tol=IPM_TOL, tol_mu=IPM_TOL
     return x.reshape(N, 7), it, conv, kkt
 
 
-def sqp_step(zbar, params, xinit, lb, ub, hl, hu, weights=FM.WEIGHTS_MODEL_C, dt=0.1, mode=0):
-    st = build_qp(zbar, params, xinit, lb, ub, hl, hu, weights, dt)
+def sqp_step(zbar, params, xinit, lb, ub, hl, hu, weights=FM.WEIGHTS_MODEL_C, dt=0.1, mode=0, wheelbase=FM.WHEELBASE_ODE,
+             friction_div=FM.WHEELBASE_FRICTION, ego_offset=FM.EGO_OFFSET):
+    st = build_qp(zbar, params, xinit, lb, ub, hl, hu, weights, dt, wheelbase, friction_div, ego_offset)
     dz, it, conv, kkt = solve_qp(st, zbar, xinit, hessian_diag(weights, zbar.shape[0], mode))
     return zbar + dz, it, conv, kkt

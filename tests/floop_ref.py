@@ -2,12 +2,10 @@
 closed loop past per-ego obstacles (include/mpcgpu.h, mpc_forces_closed_loop_batch_obst) over any `solve(zbar, params, xinit) -> (z_out, exitflag)`
 callable -- the bookkeeping (parameter rows, guess, plant, noise, clearance) restated in numpy, independent of csrc/mpc_closed_loop.h --, the scenes
 and the ego families of the tests, and the emulated solver (the kernel's own QP code on the CPU, tests/emu)."""
-import ctypes as C
-
 import numpy as np
 
 import forces_families as FF
-from helpers import abi, emu_lib, pkg
+from helpers import emu_forces_solve, pkg
 from oracle import forces_model_numpy as FM
 
 nz = __import__("importlib").import_module(pkg.__name__ + ".noise")
@@ -88,9 +86,10 @@ def rk4(x, u, dt=DT, l=WHEELBASE):
 
 
 def host_loop(solve, init_state, path, orient, vdes, L, N, track=None, offset=OBST_OFFSET, predict=0, guess_mode=0, obstacle=None, steps=None,
-              init_acc=None, sigma=0.0, seed=None, r_sum=R_SUM, ego_offset=EGO_OFFSET, log=None):
+              init_acc=None, sigma=0.0, seed=None, r_sum=R_SUM, ego_offset=EGO_OFFSET, log=None, dt=DT, wheelbase=WHEELBASE):
     """the loop of B egos: dict(traj [B,S,5], ctrl [B,S,2], flag [B,S], clearance [B,S] | None) over the first S = `steps` (default L) steps of a run
-    of L.  seed: the applied-input noise of noise mode 2.  log: a list that receives (zbar, params, xinit) of every solve."""
+    of L.  seed: the applied-input noise of noise mode 2.  log: a list that receives (zbar, params, xinit) of every solve.  dt, wheelbase: the plant's
+    (RK4), ego_offset / r_sum: the clearance's."""
     init_state = np.asarray(init_state, dtype=np.float64)
     B = init_state.shape[0]
     S = L if steps is None else steps
@@ -114,26 +113,15 @@ def host_loop(solve, init_state, path, orient, vdes, L, N, track=None, offset=OB
             u += np.array([nz.applied_noise(seed, b, k, sigma) for b in range(B)])
         traj[:, k], ctrl[:, k], flag[:, k] = x, u, fl
         zbar = next_guess(zbar, z_out, fl, guess_mode)
-        x = rk4(x, u)
+        x = rk4(x, u, dt, wheelbase)
     return dict(traj=traj, ctrl=ctrl, flag=flag, clearance=cl)
 
 
 def emu_solver(N, hessian_mode=0):
     """solve(zbar, params, xinit) on the emulated kernel (tests/emu: forces_qp_instance, instance after instance)"""
-    dp = abi.as_dp
-
-    def big(a):
-        return np.ascontiguousarray(np.where(np.isfinite(a), a, np.sign(a) * 1e308))
-
     def solve(zbar, params, xinit):
-        zbar, params, xinit = (np.ascontiguousarray(a, dtype=np.float64) for a in (zbar, params, xinit))
-        B = zbar.shape[0]
-        zo, it, st, kk = np.zeros_like(zbar), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
-        rc = emu_lib().emu_forces_solve(B, N, C.c_double(DT), C.c_double(WHEELBASE), C.c_double(FRICTION_DIV), C.c_double(EGO_OFFSET),
-                                        dp(np.array(WEIGHTS["Q"], float)), dp(np.array(WEIGHTS["R"], float)), dp(np.array(WEIGHTS["P"], float)),
-                                        dp(big(LB)), dp(big(UB)), dp(big(HL)), dp(big(HU)), hessian_mode, dp(zbar), dp(params), dp(xinit), dp(zo),
-                                        abi.as_ip(it), abi.as_ip(st), dp(kk))
-        assert rc == 0
+        zo, _, st, _ = emu_forces_solve(zbar, params, xinit, WEIGHTS, LB, UB, HL, HU, hessian_mode, dt=DT, wheelbase=WHEELBASE, friction_div=FRICTION_DIV,
+                                        ego_offset=EGO_OFFSET)
         return zo, st
     return solve
 
@@ -147,14 +135,14 @@ def backend_solver(be):
 
 
 # ---- scenes (one ego) and families (B egos) --------------------------------------------------------------------------------------------------
-def ego_inputs(B, N, v0, y0=None):
+def ego_inputs(B, N, v0, y0=None, dt=DT):
     """init_state [B,5] on the path (v0 dt i, 0), path [B,Lp,2], orient [B,Lp], vdes [B]"""
     L, Lp = run_length(N)
     init = np.tile([0.0, 0.0, 0.0, v0, 0.0], (B, 1))
     if y0 is not None:
         init[:, 1] = y0
     path = np.zeros((B, Lp, 2))
-    path[:, :, 0] = v0 * DT * np.arange(Lp)
+    path[:, :, 0] = v0 * dt * np.arange(Lp)
     return init, path, np.zeros((B, Lp)), np.full(B, float(v0))
 
 
@@ -183,14 +171,14 @@ def run_scene(solve, sc, guess_mode, predict, steps=STEPS, **kw):
                      guess_mode=guess_mode, steps=steps, **kw)
 
 
-def overtake_family(B, N, seed=7):
+def overtake_family(B, N, seed=7, dt=DT):
     """B egos at 10 m/s, each past its own obstacle: speed U(3.5, 4.5) m/s, lateral U(-2.7, -2.3), start U(14, 17)"""
     rng = np.random.default_rng(seed)
     L, _ = run_length(N)
     speed, lat, start = rng.uniform(3.5, 4.5, B), rng.uniform(-2.7, -2.3, B), rng.uniform(14.0, 17.0, B)
     i = np.arange(L)
-    track = np.stack([start[:, None] + speed[:, None] * DT * i, np.repeat(lat[:, None], L, axis=1), np.zeros((B, L))], axis=2)
-    return ego_inputs(B, N, 10.0) + (np.ascontiguousarray(track),)
+    track = np.stack([start[:, None] + speed[:, None] * dt * i, np.repeat(lat[:, None], L, axis=1), np.zeros((B, L))], axis=2)
+    return ego_inputs(B, N, 10.0, dt=dt) + (np.ascontiguousarray(track),)
 
 
 def parked_family(B, N, seed=7):

@@ -108,7 +108,7 @@ def emu_lib():
     return _emu
 
 
-def emu_desc(cfg, fixed_iters=0, max_iter=100):
+def emu_desc(cfg, fixed_iters=0, max_iter=100, tol=1e-8, obst_mult=3):
     d = abi.MpcProblemDesc()
     emu_lib().emu_default_desc(C.byref(d), cfg.N, cfg.nx)
     for i, q in enumerate(cfg.Qdiag):
@@ -117,12 +117,12 @@ def emu_desc(cfg, fixed_iters=0, max_iter=100):
     oc = cfg.obstacle_centers.ravel()
     for i in range(6):
         d.obstacle[i] = oc[i]
-    d.dt, d.ego_offset = cfg.dt, cfg.ego_offset
-    d.fixed_iters, d.max_iter = fixed_iters, max_iter
+    d.dt, d.ego_offset, d.wheelbase, d.friction_div = cfg.dt, cfg.ego_offset, cfg.wheelbase, cfg.friction_div
+    d.fixed_iters, d.max_iter, d.tol, d.obst_mult = fixed_iters, max_iter, tol, obst_mult
     return d
 
 
-def emu_solve(cfg, x0, p, bx=0, bounds=None, obst=None, fixed_iters=0, want_rc=False):
+def emu_solve(cfg, x0, p, bx=0, bounds=None, obst=None, fixed_iters=0, want_rc=False, tol=1e-8, obst_mult=3):
     x0 = np.ascontiguousarray(x0, dtype=np.float64)
     p = np.ascontiguousarray(p, dtype=np.float64)
     if bounds is None:
@@ -133,7 +133,7 @@ def emu_solve(cfg, x0, p, bx=0, bounds=None, obst=None, fixed_iters=0, want_rc=F
     st, it, kkt = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
     tr = np.zeros((101, 8, B))
     nit = np.zeros(1, np.int32)
-    d = emu_desc(cfg, fixed_iters)
+    d = emu_desc(cfg, fixed_iters, tol=tol, obst_mult=obst_mult)
     if obst is not None:
         obst = np.ascontiguousarray(obst, dtype=np.float64)
     fn = emu_lib().emu_solve_batch
@@ -197,6 +197,22 @@ def straight_path(L, x0, y0, psi, v_des, dt=0.1):
     return path, np.full(L, psi)
 
 
+def emu_forces_solve(zbar, params, xinit, weights, lb, ub, hl, hu, mode=0, dt=0.1, wheelbase=2.5789128, friction_div=2.578, ego_offset=0.75):
+    """the FORCES-mode SQP step of the kernels (csrc/mpc_forces_qp.h) stepped on the CPU by tests/emu, with every model scalar an argument:
+    zbar [B,N,7], params [B,N,10], xinit [B,5] -> (z [B,N,7], iterations [B], status [B], kkt [B])"""
+    zbar, params, xinit = (np.ascontiguousarray(a, dtype=np.float64) for a in (zbar, params, xinit))
+    B, N = zbar.shape[:2]
+    big = lambda a: np.ascontiguousarray(np.where(np.isfinite(a), a, np.sign(a) * 1e308), dtype=np.float64)     # noqa: E731
+    zo, it, st, kk = np.zeros_like(zbar), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
+    dp = abi.as_dp
+    rc = emu_lib().emu_forces_solve(B, N, C.c_double(dt), C.c_double(wheelbase), C.c_double(friction_div), C.c_double(ego_offset),
+                                    dp(np.array(weights["Q"], float)), dp(np.array(weights["R"], float)), dp(np.array(weights["P"], float)),
+                                    dp(big(np.asarray(lb, float))), dp(big(np.asarray(ub, float))), dp(big(np.asarray(hl, float))),
+                                    dp(big(np.asarray(hu, float))), int(mode), dp(zbar), dp(params), dp(xinit), dp(zo), abi.as_ip(it), abi.as_ip(st), dp(kk))
+    assert rc == 0
+    return zo, it, st, kk
+
+
 class EmuForcesBackend:
     """TEST ONLY stand-in for BatchedMPCSolver in FORCES mode: the kernels' own QP code stepped on the CPU by the emulation
     harness (tests/emu) and the oracle's RK4 plant step.  The product never constructs this."""
@@ -214,18 +230,10 @@ class EmuForcesBackend:
 
     def forces_solve(self, x0, xinit, par, lb, ub, hl, hu, hessian_mode=0):
         self.calls += 1
-        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, self.N, 7)
+        x0 = np.asarray(x0, dtype=np.float64).reshape(-1, self.N, 7)
         B = x0.shape[0]
-        xinit = np.ascontiguousarray(xinit, dtype=np.float64).reshape(B, 5)
-        par = np.ascontiguousarray(par, dtype=np.float64).reshape(B, self.N, 10)
-        big = lambda a: np.ascontiguousarray(np.where(np.isfinite(a), a, np.sign(a) * 1e308), dtype=np.float64)     # noqa: E731
-        zo, it, st, kk = np.zeros_like(x0), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
-        dp = abi.as_dp
-        rc = emu_lib().emu_forces_solve(B, self.N, C.c_double(0.1), C.c_double(2.5789128), C.c_double(self.friction_div), C.c_double(self.ego_offset),
-                                        dp(np.array(self.w["Q"], float)), dp(np.array(self.w["R"], float)), dp(np.array(self.w["P"], float)),
-                                        dp(big(np.asarray(lb, float))), dp(big(np.asarray(ub, float))), dp(big(np.asarray(hl, float))), dp(big(np.asarray(hu, float))), int(hessian_mode),
-                                        dp(x0), dp(par), dp(xinit), dp(zo), abi.as_ip(it), abi.as_ip(st), dp(kk))
-        assert rc == 0
+        zo, it, st, kk = emu_forces_solve(x0, np.asarray(par, dtype=np.float64).reshape(B, self.N, 10), np.asarray(xinit, dtype=np.float64).reshape(B, 5), self.w,
+                                          lb, ub, hl, hu, hessian_mode, friction_div=self.friction_div, ego_offset=self.ego_offset)
         return zo, st, it, kk
 
 

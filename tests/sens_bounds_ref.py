@@ -109,3 +109,12 @@ def lam_bounds(cfg, lam_g, lam_x):
     out[2 * nw + OL] = -np.minimum(lo, 0.0).sum()
     out[2 * nw + OU] = -np.maximum(lo, 0.0).sum()
     return out
+
+
+# ---- away from the default descriptor (tests/descriptor_families.py: D5, D6) -----------------------------------------------------------------
+# This reference against the CPU harness (tests/sensx: sensboundx_solve) at the point, worst max|dw - want| / max(max|want|, 0.1) over the rows the
+# GPU test compares and the ten directions of tests/test_sens_bounds_cpu.py, measured by
+# tests/test_descriptor_cpu.py::test_sensitivity_harness_against_the_reference.  D5 "outlier" is instance 12 alone (see tests/sens_ref.py), "rest"
+# every other row (instance 16: 8.5e-6, the others 3e-7 and below).  Bounds: min(10 x the figure, the 1e-4 of TOL_DW above).
+DESC_HARNESS_WORST = {"D5": dict(rest=8.6e-6, outlier=2.1e-5), "D6": dict(rest=4.11e-6)}
+DESC_TOL = {k: {q: min(10 * v, 1e-4) for q, v in d.items()} for k, d in DESC_HARNESS_WORST.items()}

@@ -88,3 +88,15 @@ def lam_obst(cfg, centres, w, lam_g):
         _, J, _ = nlp.obstacle_rows(X[k])
         out[2 * j: 2 * j + 2] -= (lam_g[r] + lam_g[r + 1] + lam_g[r + 2]) * J[j, :2]
     return out
+
+
+# ---- away from the default descriptor (tests/descriptor_families.py: D5, D6) -----------------------------------------------------------------
+# This reference against the CPU harness (tests/sensx: sensobstx_solve) at the point, worst max|dw - ref| / max(1, max|ref|) over the rows the GPU
+# test compares, every instance with an obstacle row of its own (obst_rows of tests/test_sens_obst_cpu.py), measured by
+# tests/test_descriptor_cpu.py::test_sensitivity_harness_against_the_reference.  D6: instance 28 is left out of the comparison -- there the reference
+# is 9.7e-5 from the harness (every other row: 1.4e-6 and below), ten times the 1e-5 the family is held to (TOL_DW of tests/test_gpu_sens_obst.py):
+# no referee on that row.  D5 (no circle row active): the reference is exactly 0, the figure is max|dw| of the harness, what the barrier's z / gap of far
+# rows leaves; its bound is inherited, the TOL_DW tests/test_gpu_sens_obst.py holds its lane-following case to (ten times a residue of 1e-12 is no bound).
+DESC_HARNESS_WORST = {"D5": dict(rest=2.7e-12), "D6": dict(rest=1.4e-6)}
+DESC_TOL = {"D5": dict(rest=1e-5), "D6": dict(rest=min(10 * 1.4e-6, 1e-5))}
+DESC_LEFT_OUT = {"D5": (), "D6": (28,)}

@@ -73,3 +73,11 @@ def lam_weights(cfg, w, p):
         out[:5] += e[:5] * e[:5]
         out[5:] += U[k] * U[k]
     return out
+
+
+# ---- away from the default descriptor (tests/descriptor_families.py: D5, D6) -----------------------------------------------------------------
+# This reference against the CPU harness (tests/sensx: sensweightx_solve) at the point, worst max|dw - want| / max|want| over the rows the GPU test
+# compares and the eight directions, measured by tests/test_descriptor_cpu.py::test_sensitivity_harness_against_the_reference.  D5 "outlier" is
+# instance 12 alone (see tests/sens_ref.py), "rest" every other row.  Bounds: min(10 x the figure, the 1e-4 of TOL_DW above).
+DESC_HARNESS_WORST = {"D5": dict(rest=8.1e-7, outlier=1.73e-5), "D6": dict(rest=3.55e-6)}
+DESC_TOL = {k: {q: min(10 * v, 1e-4) for q, v in d.items()} for k, d in DESC_HARNESS_WORST.items()}
