@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mpcgpu.h"
@@ -130,9 +131,13 @@ inline int set_bound_rows(HostProblem& hp, const double* lbx, const double* ubx,
     hp.bounds_set = true;
     return MPC_OK;
 }
-inline int set_bounds(HostProblem& hp, const double* lbx, const double* ubx, const double* lbg, const double* ubg, std::string& err) {
+inline int set_bounds(HostProblem& hp_live, const double* lbx, const double* ubx, const double* lbg, const double* ubg, std::string& err) {
+    // A refused call leaves the problem as it was: the rows are parsed into a copy.  (Until tests/test_gpu_bound_structures.py asked, a refusal
+    // left LB / UB half rewritten and the masks recomputed from them on the host, beside the previous call's bounds on the device.)
+    HostProblem hp = hp_live;
     const int rc = set_bound_rows(hp, lbx, ubx, lbg, ubg, err);
-    hp.lo_mask = hp.hi_mask = 0;                // (also after an error: LB / UB may have changed)
+    if (rc) return rc;
+    hp.lo_mask = hp.hi_mask = 0;
     hp.dense_mask = 0xFFFFu;
     for (size_t q = 0; q < hp.LB.size(); ++q) {
         const int i = (int)(q % (size_t)hp.NZ()), k = (int)(q / (size_t)hp.NZ());
@@ -143,7 +148,8 @@ inline int set_bounds(HostProblem& hp, const double* lbx, const double* ubx, con
             if (!(hp.UB[q] < 1e300)) hp.dense_mask &= ~(0x100u << i);
         }
     }
-    return rc;
+    hp_live = std::move(hp);
+    return MPC_OK;
 }
 
 // ---- workspace: one allocation of doubles + one of int32, tile-major [tile of 64 instances][row][64 lanes] --------
@@ -205,6 +211,11 @@ inline int pick_bx(int N, int max_threads) {
     return bx;
 }
 
+// nx = 6 with a costless, unbounded progress state: the Riccati sweeps may skip it (Params::dec_s)
+inline int dec_s_of(const HostProblem& hp) {
+    return (hp.desc.nx == 6 && hp.desc.Q[5] == 0.0 && !((hp.lo_mask | hp.hi_mask) & (1u << 7))) ? 1 : 0;
+}
+
 inline void fill_params(Params& P, const HostProblem& hp, int B, size_t Bp, int bx, double* base, int32_t* ibase,
                         const double* dLB, const double* dUB, bool mailbox = true, bool obst_stages = false) {
     const mpc_problem_desc& d = hp.desc;
@@ -222,7 +233,7 @@ inline void fill_params(Params& P, const HostProblem& hp, int B, size_t Bp, int 
     P.dec_s = 0;                      // set after the masks below
     P.tile_mask = nullptr;
     P.lo_mask = hp.lo_mask; P.hi_mask = hp.hi_mask; P.dense_mask = hp.dense_mask;
-    P.dec_s = (d.nx == 6 && d.Q[5] == 0.0 && !((P.lo_mask | P.hi_mask) & (1u << 7))) ? 1 : 0;
+    P.dec_s = dec_s_of(hp);
     P.x0 = nullptr; P.p = nullptr; P.LB = dLB; P.UB = dUB;
     // every array pointer addresses its first row inside tile 0
     P.Z = base + w.Z * 64; P.ZL = base + w.ZL * 64; P.ZU = base + w.ZU * 64;

@@ -70,6 +70,11 @@ constexpr double EPS10 = 10.0 * 2.220446049250313e-16;
 // costs the collision-avoidance family iterations (mean 25.6 against 24.5, and most of its instances that wander to the iteration limit:
 // profiles/r04_ca_lottery.txt).  Instances with such a row are symmetrised every stage, like the ones that ever needed an inertia correction.
 constexpr double ILL_WEIGHT = 1e4;
+// A bound on a state the reference's NLP leaves free -- x, y, the heading, the progress state: bits 2, 3, 6, 7 of (u, x) -- does the same once it
+// is active (a box on the terminal y, N = 30 / 50: k_solve_wg alone needed an iteration more than every other path and the oracle on 4 - 14 % of
+// the rows and ended up to 5e-6 from them; tests/test_gpu_bound_structures.py).  The bounds of the steering angle and the speed do not: their
+// states sit one stage behind an input.
+constexpr uint32_t ILL_STATE_VM = 0xCCu;
 
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef __attribute__((address_space(3))) const double* mpc_lds_cptr;
@@ -90,7 +95,7 @@ enum ScRow {
     SC_COUNT
 };
 enum IsRow { IS_STATUS = 0, IS_ITERS, IS_NFILT, IS_HAVETH0, IS_CONV, IS_ROLL, IS_FROW,
-             IS_ILL,                      // a circle row of the instance carries a large weight z / s (set by the stage phases of k_solve_wg, sticky): its MFMA sweeps keep the cost-to-go symmetric
+             IS_ILL,                      // a circle row (or a bound of a state in ILL_STATE_VM) of the instance carries a large weight z / s (set by the stage phases of k_solve_wg, sticky): its MFMA sweeps keep the cost-to-go symmetric
              IS_RLEV, IS_ITACC,           // second chance inside k_solve_wg: level index (| 0x100: a level of this pass has converged; | 0x200: the first attempt stopped with
                                           // status -7, else 0; bits 16-30: its iteration count), iterations of the attempts that count so far
              IS_COUNT };
@@ -634,7 +639,7 @@ struct Ctx {
     bool fric_row;   // stage-0 friction row kept as a row (false: presolved into the bounds a0lb/a0ub of a_0)
     double a0lb, a0ub;
     bool conv;       // fixed-iteration (benchmark) mode: tolerance already reached, steps are accepted as they come
-    bool ill;        // a circle row of this stage has a weight z / s above ILL_WEIGHT at the new iterate (phase_ineq_assemble)
+    bool ill;        // a circle row, or a bound of a state in ILL_STATE_VM, of this stage has a weight z / s above ILL_WEIGHT at the new iterate (phase_ineq_assemble)
     mpc_lds_cptr bnd;                        // LDS copy of the bounds table [LB (N+1)*NZ | UB (N+1)*NZ] (device)
     int bnd_ub;
     mpc_lds_ptr rec;                         // k_solve_wg (the MB instantiations of the phases): the LDS record of this (instance, stage)
@@ -1643,6 +1648,9 @@ MPC_HD void phase_ineq_assemble(const PRef& P, Ctx<NX>& c, OUT& xo, KktPart& kp,
             if (MPC_HAS_LO(lb)) side_kkt(zi - lb, REUSE ? c.igl[i] : mpc_rcp(zi - lb), c.zl[i], 1.0, 1, sg, gbb, rz, kp.cmin, kp.cmax, kp.sz, kp.gp);
             if (MPC_HAS_HI(ub)) side_kkt(ub - zi, REUSE ? c.igu[i] : mpc_rcp(ub - zi), c.zu[i], -1.0, 1, sg, gbb, rz, kp.cmin, kp.cmax, kp.sz, kp.gp);
         }
+        // (a heavy bound on x, y, the heading or the progress state -- none in the reference's NLP -- weighs on the cost-to-go as a heavy circle row does)
+        // (discarded where the compiled-in mask holds none of these states: variant 2 keeps its machine code)
+        if constexpr ((VM & ILL_STATE_VM) != 0u) { if (((ILL_STATE_VM >> i) & 1u) && sg > ILL_WEIGHT) c.ill = true; }
         xo.put(3 * i + IR::SG, sg); xo.put(3 * i + IR::GBB, gbb); xo.put(3 * i + IR::RZ, rz);
     }
     double orx[3] = {0.0, 0.0, 0.0}, ogxa[3] = {0.0, 0.0, 0.0}, ogxb[3] = {0.0, 0.0, 0.0}, oH[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};

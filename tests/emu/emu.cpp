@@ -41,7 +41,8 @@ extern "C" void emu_default_desc(mpc_problem_desc* d, int32_t N, int32_t nx) { d
 // the launch plan of one solve (mpc_solve_plan.h) for a handle with these options (set as mpc_set_option would) and this state:
 // state = [n_cu, xcd_mask, ws_mailbox (-1: as a handle's first solve finds it), pipe_disabled, resc_hint, B, per_inst_obst, trace, in_rescue,
 // async_loop]; out = [path (0 one launch per kernel, 1 pipeline, 2 k_solve_wg alone), bx, hyb_bx, hand, Riccati workers per XCD, pipe_help,
-// max_rows, mailbox, rescue, XCDs, tiles per XCD, k_solve_wg workgroups, tiles, masked, wg_resc, groups, loop_async, xcd_mask]
+// max_rows, mailbox, rescue, XCDs, tiles per XCD, k_solve_wg workgroups, tiles, masked, wg_resc, groups, loop_async, xcd_mask, rows of the
+// stage workgroups' LDS stash, dec_s, has_fl, has_fu, has_ol, has_ou, lo_mask, hi_mask, dense_mask, 256-thread stage workgroups]
 extern "C" int emu_solve_plan(const mpc_problem_desc* desc, const double* lbx, const double* ubx, const double* lbg, const double* ubg,
                               const char* const* opt_names, const char* const* opt_values, int32_t n_opts, const int64_t* state, int64_t* out) {
     HostProblem hp;
@@ -61,9 +62,28 @@ extern "C" int emu_solve_plan(const mpc_problem_desc* desc, const double* lbx, c
     if (state[2] < 0) st.ws_mailbox = plan_solve(hp, kn, st).mailbox;      // (ensure_ws before the first solve)
     const SolvePlan pl = plan_solve(hp, kn, st);
     const int64_t v[] = {pl.res_path ? 2 : pl.pipe_path ? 1 : 0, pl.bx, pl.hyb_bx, pl.hand, pl.n_ric, pl.pipe_help, (int64_t)pl.max_rows, pl.mailbox,
-                         pl.rescue, pl.n_xcd, pl.tiles_x, pl.wg_grid, pl.ntiles, pl.masked, pl.wg_resc, pl.G, pl.loop_async, pl.xcd_mask};
+                         pl.rescue, pl.n_xcd, pl.tiles_x, pl.wg_grid, pl.ntiles, pl.masked, pl.wg_resc, pl.G, pl.loop_async, pl.xcd_mask,
+                         pl.stash_rows, dec_s_of(hp), hp.has_fl, hp.has_fu, hp.has_ol, hp.has_ou, hp.lo_mask, hp.hi_mask, hp.dense_mask, pl.small_wg};
     for (size_t i = 0; i < sizeof v / sizeof v[0]; ++i) out[i] = v[i];
     return MPC_OK;
+}
+
+// set_bounds (mpc_host_common.h) twice on one problem, as a handle's mpc_set_bounds calls arrive: the first lists must be accepted; returns what
+// the second call returned.  same[0] = 1 where the problem is, field for field, what the first call left (LB, UB, the has_* flags and their
+// levels, the raw levels, n_mult, n_z, the three masks, bounds_set)
+extern "C" int emu_set_bounds_twice(const mpc_problem_desc* desc, const double* const* first, const double* const* second, int32_t* same) {
+    HostProblem hp;
+    hp.desc = *desc;
+    std::string err;
+    if (validate_desc(hp.desc, err) || set_bounds(hp, first[0], first[1], first[2], first[3], err)) return MPC_ERR_INVALID;
+    const HostProblem was = hp;
+    const int rc = set_bounds(hp, second[0], second[1], second[2], second[3], err);
+    const auto eq = [](const std::vector<double>& a, const std::vector<double>& b) { return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0); };
+    same[0] = eq(hp.LB, was.LB) && eq(hp.UB, was.UB) && hp.has_fl == was.has_fl && hp.has_fu == was.has_fu && hp.has_ol == was.has_ol && hp.has_ou == was.has_ou &&
+              hp.fl == was.fl && hp.fu == was.fu && hp.ol == was.ol && hp.ou == was.ou && hp.ol_raw == was.ol_raw && hp.fl_raw == was.fl_raw &&
+              hp.n_mult == was.n_mult && hp.n_z == was.n_z && hp.lo_mask == was.lo_mask && hp.hi_mask == was.hi_mask && hp.dense_mask == was.dense_mask &&
+              hp.bounds_set == was.bounds_set && !(rc && err.empty());
+    return rc;
 }
 
 // what solve_dev does behind a launch (mpc_solve_plan.h: after_solve): in = [pl.rescue, failed, resc_ran, resc_in_kernel, rescued_in_kernel];

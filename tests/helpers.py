@@ -243,9 +243,12 @@ class EmuForcesBackend:
 # kernels does not rest on the sibling IPM implementations.  Multipliers are recovered by sign-constrained least squares on the
 # rows / bounds that are active at w.
 # ------------------------------------------------------------------------------------------------------------
-def kkt_certificate(nlp, w, p, active_tol=1e-4):
+def kkt_certificate(nlp, w, p, active_tol=1e-4, bounds=None):
+    """bounds: (lbg, ubg, lbx, ubx) in place of the reference's (nlp.bounds()); the result then names the active sides as well, "active":
+    [("g" | "x", index, "lo" | "hi")] (equality rows left out)"""
     from scipy.optimize import lsq_linear
-    lbg, ubg, lbx, ubx = nlp.bounds()
+    lbg, ubg, lbx, ubx = nlp.bounds() if bounds is None else bounds
+    active = []
     w, p = np.asarray(w, float), np.asarray(p, float)
     g, J, grad = nlp.g(w, p), nlp.jac(w, p), nlp.grad(w, p)
     feas = max(0.0, float((lbg - g).max()), float((g - ubg).max()), float((lbx - w).max()), float((w - ubx).max()))
@@ -258,20 +261,20 @@ def kkt_certificate(nlp, w, p, active_tol=1e-4):
             cols.append(J[i]); lo.append(-np.inf); hi.append(np.inf)
             continue
         sc = max(1.0, abs(g[i]))
-        if np.isfinite(lbg[i]) and i != 0 and g[i] - lbg[i] <= active_tol * sc:      # (row 0: |y| >= 0 is implied, never active)
-            cols.append(-J[i]); lo.append(0.0); hi.append(np.inf)
+        if np.isfinite(lbg[i]) and (i != 0 or lbg[0] > 0.0) and g[i] - lbg[i] <= active_tol * sc:      # (row 0: |y| >= 0 is implied, never active)
+            cols.append(-J[i]); lo.append(0.0); hi.append(np.inf); active.append(("g", i, "lo"))
         if np.isfinite(ubg[i]) and ubg[i] - g[i] <= active_tol * sc:
-            cols.append(J[i]); lo.append(0.0); hi.append(np.inf)
+            cols.append(J[i]); lo.append(0.0); hi.append(np.inf); active.append(("g", i, "hi"))
     for i in range(nlp.n_w):
         e = np.zeros(nlp.n_w)
         e[i] = 1.0
         sc = max(1.0, abs(w[i]))
         if np.isfinite(lbx[i]) and w[i] - lbx[i] <= active_tol * sc:
-            cols.append(-e); lo.append(0.0); hi.append(np.inf)
+            cols.append(-e); lo.append(0.0); hi.append(np.inf); active.append(("x", i, "lo"))
         if np.isfinite(ubx[i]) and ubx[i] - w[i] <= active_tol * sc:
-            cols.append(e); lo.append(0.0); hi.append(np.inf)
+            cols.append(e); lo.append(0.0); hi.append(np.inf); active.append(("x", i, "hi"))
     A = np.array(cols).T
     r = lsq_linear(A, -grad, bounds=(np.array(lo), np.array(hi)), method="bvls" if A.shape[1] < 400 else "trf", tol=1e-14, lsq_solver="exact")
     res = A @ r.x + grad
     return dict(stationarity=float(np.abs(res).max()) / max(1.0, float(np.abs(grad).max())), feasibility=feas,
-                n_active=int(sum(1 for q in lo if q == 0.0)), grad_norm=float(np.abs(grad).max()))
+                n_active=int(sum(1 for q in lo if q == 0.0)), grad_norm=float(np.abs(grad).max()), **({} if bounds is None else dict(active=active)))

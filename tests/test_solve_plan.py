@@ -17,7 +17,8 @@ from oracle.nlp_numpy import WEIGHTS_ZAM_LF, BicycleNLP, NLPConfig, synthetic_ba
 N_CU, XCD_MASK = 256, 0xFF
 PATHS = {0: "kernels", 1: "pipe", 2: "wg"}          # one launch per kernel and iteration | k_pipeline (+ k_solve_wg) | k_solve_wg alone
 OUT = ("path", "bx", "hyb_bx", "hand", "n_ric", "help", "chunk", "mailbox", "rescue", "n_xcd", "tiles_x", "wg_grid", "ntiles", "masked",
-       "wg_resc", "groups", "loop_async", "xcd_mask")
+       "wg_resc", "groups", "loop_async", "xcd_mask", "stash_rows", "dec_s", "has_fl", "has_fu", "has_ol", "has_ou", "lo_mask", "hi_mask", "dense_mask",
+       "small_wg")
 
 LF30 = "zamlf_n30_nx6"
 CFGS = {LF30: FAMILIES[LF30][0], "usalf_n50_nx5": FAMILIES["usalf_n50_nx5"][0], "ca": CA_CFG,
@@ -94,8 +95,10 @@ def bounds_of(fam):
     return [np.ascontiguousarray(a, dtype=np.float64) for a in BicycleNLP(CFGS[fam]).bounds()]
 
 
-def plan(fam, B, opts, n_cu=N_CU, xcd_mask=XCD_MASK, ws_mailbox=-1, pipe_disabled=0, resc_hint=0, trace=0, in_rescue=0, async_loop=0):
-    """emu_solve_plan for a handle of family `fam` with options `opts` (fixed_iters: the descriptor's); ws_mailbox -1 = a handle's first solve"""
+def plan(fam, B, opts, n_cu=N_CU, xcd_mask=XCD_MASK, ws_mailbox=-1, pipe_disabled=0, resc_hint=0, trace=0, in_rescue=0, async_loop=0, bounds=None,
+         obst_mult=3):
+    """emu_solve_plan for a handle of family `fam` (a name of CFGS, or an NLPConfig) with options `opts` (fixed_iters: the descriptor's);
+    ws_mailbox -1 = a handle's first solve; bounds: (lbg, ubg, lbx, ubx) in place of the family's reference bounds"""
     L = emu_lib()
     if not getattr(L, "_plan_ready", False):
         L.emu_solve_plan.argtypes = [C.POINTER(abi.MpcProblemDesc)] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_char_p)] * 2 + \
@@ -103,8 +106,9 @@ def plan(fam, B, opts, n_cu=N_CU, xcd_mask=XCD_MASK, ws_mailbox=-1, pipe_disable
         L.emu_solve_plan.restype = C.c_int
         L._plan_ready = True
     opts = dict(opts)
-    d = emu_desc(CFGS[fam], fixed_iters=int(opts.pop("fixed_iters", 0)))
-    lbg, ubg, lbx, ubx = bounds_of(fam)
+    cfg = CFGS[fam] if isinstance(fam, str) else fam
+    d = emu_desc(cfg, fixed_iters=int(opts.pop("fixed_iters", 0)), obst_mult=obst_mult)
+    lbg, ubg, lbx, ubx = [np.ascontiguousarray(a, dtype=np.float64) for a in (BicycleNLP(cfg).bounds() if bounds is None else bounds)]
     names = (C.c_char_p * max(1, len(opts)))(*[k.encode() for k in opts])
     values = (C.c_char_p * max(1, len(opts)))(*[str(v).encode() for v in opts.values()])
     state = np.array([n_cu, xcd_mask, ws_mailbox, pipe_disabled, resc_hint, B, 0, trace, in_rescue, async_loop], np.int64)
