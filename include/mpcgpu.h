@@ -327,6 +327,35 @@ int mpc_closed_loop_batch_pred_dev(mpc_handle* h, int32_t B, int32_t L, int32_t 
                                    const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
                                    int32_t predict, int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl,
                                    int32_t* d_step_status, double* d_clearance, void* stream);
+/* The loop through TRAFFIC: M >= 1 obstacles, and every stage of every solve avoids the one nearest to it.  The arguments of
+ * mpc_closed_loop_batch_pred[_dev] with (Lt, obst_track, obst_offset, predict) replaced by (M, Lt, per_ego, tracks, offsets, pairing).
+ * per_ego 0: tracks [M, Lt, 3], offsets [M], shared by all egos (one scene, many egos); per_ego 1: tracks [B, M, Lt, 3], offsets [B, M].  Lt = 1 or
+ * Lt >= L as above.  A pose whose x is not finite (NaN) means that the obstacle is ABSENT at that row: CommonRoad obstacles live for part of a scenario.
+ * Before the solve of step i, stage k of ego b gets the circle centres of an obstacle at track row r = min(i + k, Lt - 1), picked against the
+ * predicted ego pose of that stage -- at step 0 the measured state, from step 1 on stage k of the shifted last plan (the solve's warm start):
+ *   pairing 0  (the reference's pairs, on one obstacle): the present obstacle m with the smallest min_j |E_j - O_{m,j}| (ego circle j against
+ *              obstacle circle j; lowest m on a tie) gives all three centres;  chosen[b, i, k, 0..2] = m
+ *   pairing 1  (each ego circle against its nearest circle): slot j is the circle O_{m,c} nearest to ego circle j over all present m and c (ties:
+ *              lowest m, then lowest c), so front-against-rear contacts count too;  chosen[b, i, k, j] = m
+ * No obstacle present at r: the descriptor's centres, chosen = -1.  This is the standard nearest-obstacle formulation, not an exact multi-obstacle
+ * NLP: two obstacles equally close to one ego circle at one stage constrain it only once.  The solves are mpc_solve_batch_stages_dev's, unchanged;
+ * with M = 1 and pairing 0 traj, ctrl and step_status are bit for bit those of mpc_closed_loop_batch_pred with predict 1 on that track.  One radius
+ * per handle, as in every loop: the lower bound of the circle rows holds for all obstacles.
+ * clearance [B, L] or NULL: clearance[b, i] = min over the obstacles present at row min(i, Lt - 1) and over ALL nine circle pairs of distance - r_sum
+ * for the state before step i, +inf when none is present; nearest [B, L] (int32) or NULL: the obstacle that attains it, or -1; chosen
+ * [B, L, N+1, 3] (int32) or NULL.  MPC_ERR_INVALID with a message: M < 1; Lt neither 1 nor >= L; NULL tracks or offsets; an offset that is not
+ * finite (the device-pointer form copies the offsets back once, before it enqueues anything); pairing or per_ego outside {0, 1}.  Noise modes,
+ * step_status, option "loop_async" and mpc_last_loop_replayed as in mpc_closed_loop_batch_obst; like every loop it ends the life of the
+ * sensitivity snapshot.                                                                                                                          */
+int mpc_closed_loop_batch_traffic(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
+                                  const double* orient, const double* vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* tracks,
+                                  const double* offsets, int32_t pairing, int32_t noise_mode, double sigma, uint64_t seed, double* traj,
+                                  double* ctrl, int32_t* step_status, double* clearance, int32_t* nearest, int32_t* chosen);
+int mpc_closed_loop_batch_traffic_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                      const double* d_orient, const double* d_vdes, int32_t M, int32_t Lt, int32_t per_ego,
+                                      const double* d_tracks, const double* d_offsets, int32_t pairing, int32_t noise_mode, double sigma,
+                                      uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status, double* d_clearance,
+                                      int32_t* d_nearest, int32_t* d_chosen, void* stream);
 /* The same loop as a chain of optima, linearised: besides traj / ctrl / step_status / clearance, the per-step feedback gains of the first
  * control of every solve,
  *   kgain [B,L,2,5] = d u*_0 / d s_i  (s_i = traj[b,i], the measured state)      wgain [B,L,2,7] = d u*_0 / d wt  (wt = [Q_0..Q_4 | R_0, R_1])

@@ -96,6 +96,8 @@ PROTOTYPES = {
     "mpc_closed_loop_batch_obst_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64] + _loop_tail + [_vp] * 5,
     "mpc_closed_loop_batch_pred": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _dp, _f64, _i32] + _loop_tail + [_dp, _dp, _ip, _dp],
     "mpc_closed_loop_batch_pred_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64, _i32] + _loop_tail + [_vp] * 5,
+    "mpc_closed_loop_batch_traffic": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _i32, _i32, _dp, _dp, _i32] + _loop_tail + [_dp, _dp, _ip, _dp, _ip, _ip],
+    "mpc_closed_loop_batch_traffic_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _vp, _vp, _i32] + _loop_tail + [_vp] * 7,
     "mpc_closed_loop_batch_lin": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _dp, _f64] + _loop_tail + [_dp, _dp, _ip, _dp] + [_dp] * 3,
     "mpc_closed_loop_batch_lin_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64] + _loop_tail + [_vp] * 8,
     "mpc_loop_tangent": [_vp, _i32, _i32, _i32] + [_dp] * 5 + [_i32] + [_dp] * 5,

@@ -187,6 +187,129 @@ MPC_HD void loop_obst_stage(const Params& P, const LoopObstArgs& A, int N, int b
 }
 
 // =========================================================================================================================
+// The loop through traffic (mpc_closed_loop_batch_traffic): M obstacle tracks, and before every solve each stage of each ego is given the
+// circle centres of the obstacle that threatens it at that stage's time.  The NLP keeps its three circle rows per stage: this is the
+// standard NEAREST-OBSTACLE formulation, not an exact multi-obstacle NLP.  Its limit: two obstacles equally close to one ego circle at one
+// stage constrain it only once -- the stage sees one of them (the lowest index) and the plan may cut into the other until a later solve,
+// whose selection then turns to it.
+//   * time row of stage k of step i: min(i + k, Lt - 1), the rule of loop_obst_stage; an obstacle whose x at that row is not finite is
+//     ABSENT there (CommonRoad obstacles live for part of a scenario)
+//   * predicted ego pose of stage k: at step 0 the measured state (the warm start of step 0 is the tiled initial state, in the reference's
+//     transposed layout); from step 1 on stage k of the warm start that loop_advance_instance has just written, the shifted last plan
+//   * pairing 0, the reference's pairs on ONE obstacle: score(m) = min_j |E_j - O_{m,j}|, the present obstacle with the smallest score
+//     (lowest index on a tie) gives all three centres of the row
+//   * pairing 1, each ego circle against its nearest circle: slot j of the row is the circle O_{m,c} nearest to ego circle j over all present
+//     m and c (ties: lowest m, then lowest c); the NLP's row j measures ego circle j against slot j, so front-against-rear contacts count
+//   * nothing present: the descriptor's centres, chosen = -1
+// One call per (ego, stage); no call reads what another one writes.  The stage-0 call also writes clearance[b, i] and nearest[b, i]: the state
+// before step i against ALL nine pairs of every obstacle present at row min(i, Lt - 1), +inf / -1 when there is none.
+// =========================================================================================================================
+struct LoopTrafficArgs {
+    int32_t B, L, Lt, nx, N, M;      // instances, loop steps, poses per track (1 or >= L), states per row of `state`, horizon, obstacles
+    int32_t per_ego, pairing;        // 0: tracks [M,Lt,3], offsets [M] shared by all egos; 1: [B,M,Lt,3], [B,M].  pairing as above
+    const double* tracks;            // poses x, y, heading; x not finite: absent at that row
+    const double* offsets;           // front / rear circle centres of obstacle m: +- offset along its heading
+    double desc_obst[6];             // the descriptor's centres: the row of a stage that sees no obstacle
+    double ego_offset;               // ego circle centres: +- ego_offset along the ego's heading
+    double* obst;                    // [B,N+1,6] circle centres of the next solve
+    const double* state;             // [B,nx]   current plant state (LoopArgs::state)
+    const double* x0;                // [B,n_w]  warm start of the next solve (LoopArgs::x0)
+    double* clearance;               // [B,L] or null
+    int32_t* nearest;                // [B,L] or null
+    int32_t* chosen;                 // [B,L,N+1,3] or null
+    double r_sum;                    // sum of the two circle radii: the lower bound of the handle's circle rows
+    const uint32_t* abort_flag;      // as LoopArgs::abort_flag
+};
+MPC_HD bool loop_traffic_present(const double* row) { return fabs(row[0]) <= 1.7976931348623157e308; }       // (false for NaN and +-inf)
+MPC_HD const double* loop_traffic_pose(const LoopTrafficArgs& A, int b, int m, int row) {
+    return A.tracks + (((size_t)(A.per_ego ? b : 0) * A.M + m) * A.Lt + row) * 3;
+}
+MPC_HD double loop_traffic_offset(const LoopTrafficArgs& A, int b, int m) { return A.offsets[(size_t)(A.per_ego ? b : 0) * A.M + m]; }
+// the three ego circle centres of a pose: the centre, then +- ego_offset along psi
+MPC_HD void loop_traffic_ego(double x, double y, double psi, double ego_offset, double* e6) {
+    const double cs = cos(psi), sn = sin(psi);
+    e6[0] = x;                   e6[1] = y;
+    e6[2] = x + ego_offset * cs; e6[3] = y + ego_offset * sn;
+    e6[4] = x - ego_offset * cs; e6[5] = y - ego_offset * sn;
+}
+MPC_HD double loop_traffic_dist(const double* e, const double* o) {
+    const double dx = e[0] - o[0], dy = e[1] - o[1];
+    return sqrt(dx * dx + dy * dy);
+}
+// Most obstacles of a scene are far from a given stage, and the centres of one cost a sine and a cosine.  Every circle of the ego lies within
+// ego_offset of its pose, every circle of obstacle m within |offset_m| of its pose, so every pair distance lies within reach_m = ego_offset +
+// |offset_m| of the distance d_m of the two poses.  loop_traffic_bound: the smallest d_m + reach_m over the obstacles present at `row` -- no winner
+// of any selection is farther than that; loop_traffic_near: false for an obstacle all of whose pairs are farther (by more than rounding), which
+// therefore wins nothing and ties with nothing.  The selection looks at the others only: the same result as looking at all.
+MPC_HD double loop_traffic_bound(const LoopTrafficArgs& A, int b, int row, const double* xy) {
+    double bound = INFINITY;
+    for (int m = 0; m < A.M; ++m) {
+        const double* pose = loop_traffic_pose(A, b, m, row);
+        if (!loop_traffic_present(pose)) continue;
+        const double hi = loop_traffic_dist(xy, pose) + A.ego_offset + fabs(loop_traffic_offset(A, b, m));
+        if (hi < bound) bound = hi;
+    }
+    return bound;
+}
+MPC_HD bool loop_traffic_near(const LoopTrafficArgs& A, int b, int m, const double* pose, const double* xy, double bound) {
+    const double lo = loop_traffic_dist(xy, pose) - A.ego_offset - fabs(loop_traffic_offset(A, b, m));
+    return !(lo > bound * (1.0 + 1e-12) + 1e-12);
+}
+MPC_HD void loop_traffic_stage(const LoopTrafficArgs& A, int b, int k, int i) {
+    const int N = A.N, S = N + 1, nw = 2 * N + A.nx * S;
+    const int at = i + k, row = at < A.Lt - 1 ? at : A.Lt - 1;
+    const double* st = A.state + (size_t)b * A.nx;
+    const double* pl = (i == 0) ? st : A.x0 + (size_t)b * nw + 2 * N + A.nx * k;
+    double e6[6], c6[6], out[6], best[3];
+    int32_t pick[3] = {-1, -1, -1};
+    loop_traffic_ego(pl[0], pl[1], pl[4], A.ego_offset, e6);
+    for (int q = 0; q < 6; ++q) out[q] = A.desc_obst[q];
+    double bound = loop_traffic_bound(A, b, row, pl);
+    for (int m = 0; m < A.M; ++m) {
+        const double* pose = loop_traffic_pose(A, b, m, row);
+        if (!loop_traffic_present(pose) || !loop_traffic_near(A, b, m, pose, pl, bound)) continue;
+        loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
+        if (A.pairing == 0) {
+            double score = loop_traffic_dist(e6, c6);
+            for (int j = 1; j < 3; ++j) score = fmin(score, loop_traffic_dist(e6 + 2 * j, c6 + 2 * j));
+            if (pick[0] < 0 || score < best[0]) {
+                best[0] = score;
+                pick[0] = pick[1] = pick[2] = m;
+                for (int q = 0; q < 6; ++q) out[q] = c6[q];
+            }
+        } else {
+            for (int j = 0; j < 3; ++j)
+                for (int c = 0; c < 3; ++c) {
+                    const double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c);
+                    if (pick[j] < 0 || dist < best[j]) { best[j] = dist; pick[j] = m; out[2 * j] = c6[2 * c]; out[2 * j + 1] = c6[2 * c + 1]; }
+                }
+        }
+    }
+    double* o = A.obst + ((size_t)b * S + k) * 6;
+    for (int q = 0; q < 6; ++q) o[q] = out[q];
+    if (A.chosen)
+        for (int j = 0; j < 3; ++j) A.chosen[(((size_t)b * A.L + i) * S + k) * 3 + j] = pick[j];
+    if (k != 0 || (!A.clearance && !A.nearest)) return;
+    // the state before step i against every circle of every obstacle present at the step's own row
+    double cl = INFINITY;
+    int32_t near = -1;
+    loop_traffic_ego(st[0], st[1], st[4], A.ego_offset, e6);
+    bound = loop_traffic_bound(A, b, row, st);
+    for (int m = 0; m < A.M; ++m) {
+        const double* pose = loop_traffic_pose(A, b, m, row);
+        if (!loop_traffic_present(pose) || !loop_traffic_near(A, b, m, pose, st, bound)) continue;
+        loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
+        for (int j = 0; j < 3; ++j)
+            for (int c = 0; c < 3; ++c) {
+                const double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c);
+                if (near < 0 || dist < cl) { cl = dist; near = m; }
+            }
+    }
+    if (A.clearance) A.clearance[(size_t)b * A.L + i] = near < 0 ? INFINITY : cl - A.r_sum;
+    if (A.nearest) A.nearest[(size_t)b * A.L + i] = near;
+}
+
+// =========================================================================================================================
 // The FORCES-mode loop (ForcesproOptimizer.optimize, MPC_Planner/optimizer.py:246-366) around `solver.solve(problem)`:
 //   * the guess problem["x0"] is the tiled initial point and is NEVER refreshed                              :264-274
 //   * run-time parameters of step k: the next N path points / orientations (replenished with the last one), the desired

@@ -2482,6 +2482,14 @@ __global__ void __launch_bounds__(256) k_loop_obst_stages(const Params Pk, const
     if (t < A.B * S) loop_obst_stage(Pk, A, N, t / S, t % S, i);
 }
 
+// ... of the loop through traffic (loop_traffic_stage): the same grid, thread (b, k) picks among the M obstacles the one that threatens stage k of
+// ego b at its time and writes row (b, k); the stage varies fastest across lanes, so neighbouring lanes read neighbouring rows of a track
+__global__ void __launch_bounds__(256) k_loop_traffic(const LoopTrafficArgs A, const int i) {
+    if (A.abort_flag != nullptr && *A.abort_flag != 0u) return;       // (as k_loop_advance)
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, S = A.N + 1;
+    if (t < A.B * S) loop_traffic_stage(A, t / S, t % S, i);
+}
+
 // FORCES-mode closed loop (mpc_closed_loop.h: ForcesLoopArgs), one instance per thread
 __global__ void k_floop_setup(const ForcesLoopArgs A) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -4189,7 +4197,9 @@ int mpc_plant_step(mpc_handle* h, int32_t B, int32_t integrator, const double* x
 
 // per-ego obstacle tracks of a closed loop (mpc_closed_loop_batch_obst[_dev]); the plain loop has none
 // predict (mpc_closed_loop_batch_pred): stage k of the solve of step i sees track row min(i + k, Lt - 1) instead of row i
-struct LoopTrack { int32_t Lt; const double* d_track; double offset; double* d_clearance; int32_t predict = 0; };
+// traffic (mpc_closed_loop_batch_traffic): M >= 1 tracks [M, Lt, 3] (per_ego: [B, M, Lt, 3]) with an offset each; every stage sees the nearest one
+struct LoopTrack { int32_t Lt; const double* d_track; double offset; double* d_clearance; int32_t predict = 0;
+                   int32_t M = 0, per_ego = 0, pairing = 0; const double* d_offsets = nullptr; int32_t* d_nearest = nullptr; int32_t* d_chosen = nullptr; };
 
 // the closed loop of every entry point, with `track` (k_loop_obst in front of every solve, whose rows then carry the obstacle centres) or without;
 // with `lin` (mpc_closed_loop_batch_lin_dev has checked it) step by step, every solve leaving its snapshot and the gain kernels of the families asked for behind
@@ -4212,7 +4222,8 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
     int rc = ensure_io(h, (size_t)B);
     if (rc) return rc;
     double* d_obst = nullptr;
-    const bool predict = track && track->predict != 0;
+    const bool traffic = track && track->M > 0;                       // (centres per stage, as the predicted loop)
+    const bool predict = track && (track->predict != 0 || traffic);
     const size_t n_obst = predict ? (size_t)6 * (size_t)(d.N + 1) : 6;
     if (track && !(d_obst = static_cast<double*>(scratch_get(h, SCR_LOOP_OBST, (size_t)B * n_obst * sizeof(double))))) { h->err = "out of device memory"; return MPC_ERR_HIP; }
     // the rows of every solve of the loop: the handle's own (begin_solve: the bounds must be set)
@@ -4244,8 +4255,16 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
         O.r_sum = h->hp.ol_raw;
         PO.ego_offset = d.ego_offset;
     }
+    LoopTrafficArgs T{};
+    if (traffic) {
+        T.B = B; T.L = L; T.Lt = track->Lt; T.nx = d.nx; T.N = d.N; T.M = track->M; T.per_ego = track->per_ego; T.pairing = track->pairing;
+        T.tracks = track->d_track; T.offsets = track->d_offsets; T.ego_offset = d.ego_offset; T.obst = d_obst; T.state = h->d_state; T.x0 = h->d_x0;
+        T.clearance = track->d_clearance; T.nearest = track->d_nearest; T.chosen = track->d_chosen; T.r_sum = h->hp.ol_raw;
+        for (int q = 0; q < 6; ++q) T.desc_obst[q] = d.obstacle[q];
+    }
     const auto place_obstacles = [&](int i) {
-        if (predict) hipLaunchKernelGGL(k_loop_obst_stages, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, PO, O, d.N, i);
+        if (traffic) { T.abort_flag = O.abort_flag; hipLaunchKernelGGL(k_loop_traffic, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, T, i); }
+        else if (predict) hipLaunchKernelGGL(k_loop_obst_stages, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, PO, O, d.N, i);
         else if (track) hipLaunchKernelGGL(k_loop_obst, grid, block, 0, stream, PO, O, i);
     };
     if (lin) {
@@ -4384,6 +4403,56 @@ int mpc_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, 
                           {clearance, nB * L * 8, true}}, [&](void** d, hipStream_t s) {
         return mpc_closed_loop_batch_obst_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], obst_offset, noise_mode,
                                               sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], (double*)d[8], s);
+    });
+}
+
+// the loop through traffic: every stage of every solve sees the nearest of M obstacles (k_loop_traffic in front of every solve, which reads centres per stage)
+static const char* bad_traffic(int32_t L, int32_t M, int32_t Lt, int32_t per_ego, const void* tracks, const void* offsets, int32_t pairing) {
+    if (M < 1) return "traffic loop: M >= 1 obstacle tracks are required";
+    if (Lt != 1 && Lt < L) return "traffic loop: Lt = 1 (the obstacles stand still) or Lt >= L (row i: the obstacles at step i)";
+    if (!tracks) return "traffic loop: tracks [M, Lt, 3] (per_ego: [B, M, Lt, 3]) are required";
+    if (!offsets) return "traffic loop: offsets [M] (per_ego: [B, M]) are required";
+    if (pairing != 0 && pairing != 1) return "traffic loop: pairing is 0 (the reference's pairs on the nearest obstacle) or 1 (each ego circle against its nearest circle)";
+    if (per_ego != 0 && per_ego != 1) return "traffic loop: per_ego is 0 (tracks shared by all egos) or 1 (tracks per ego)";
+    return nullptr;
+}
+static const char* const TRAFFIC_OFFSET_REFUSAL = "traffic loop: every offset must be finite";
+int mpc_closed_loop_batch_traffic_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                      const double* d_orient, const double* d_vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* d_tracks,
+                                      const double* d_offsets, int32_t pairing, int32_t noise_mode, double sigma, uint64_t seed, double* d_traj,
+                                      double* d_ctrl, int32_t* d_step_status, double* d_clearance, int32_t* d_nearest, int32_t* d_chosen, void* stream_) {
+    if (!h) return MPC_ERR_INVALID;
+    if (const char* bad = bad_traffic(L, M, Lt, per_ego, d_tracks, d_offsets, pairing)) { h->err = bad; return MPC_ERR_INVALID; }
+    if (B <= 0) { h->err = "closed loop: B > 0 is required"; return MPC_ERR_INVALID; }
+    // the offsets live on the device: one small copy behind what the stream already holds, before anything of the loop is enqueued
+    HIP_TRY(h, hipSetDevice(h->device));
+    std::vector<double> off((size_t)(per_ego ? B : 1) * (size_t)M);
+    HIP_TRY(h, hipMemcpyAsync(off.data(), d_offsets, off.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream_));
+    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream_));
+    for (double v : off)
+        if (!std::isfinite(v)) { h->err = TRAFFIC_OFFSET_REFUSAL; return MPC_ERR_INVALID; }
+    LoopTrack track{Lt, d_tracks, 0.0, d_clearance, 0};
+    track.M = M; track.per_ego = per_ego; track.pairing = pairing; track.d_offsets = d_offsets; track.d_nearest = d_nearest; track.d_chosen = d_chosen;
+    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, &track, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, stream_);
+}
+
+int mpc_closed_loop_batch_traffic(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                                  const double* vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* tracks, const double* offsets, int32_t pairing,
+                                  int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance,
+                                  int32_t* nearest, int32_t* chosen) {
+    if (!h) return MPC_ERR_INVALID;
+    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
+    if (const char* bad = bad_traffic(L, M, Lt, per_ego, tracks, offsets, pairing)) { h->err = bad; return MPC_ERR_INVALID; }
+    const size_t nB = (size_t)B, nT = (per_ego ? nB : 1) * (size_t)M;
+    for (size_t q = 0; q < nT; ++q)
+        if (!std::isfinite(offsets[q])) { h->err = TRAFFIC_OFFSET_REFUSAL; return MPC_ERR_INVALID; }
+    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
+                          {tracks, nT * Lt * 3 * 8, false}, {offsets, nT * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true},
+                          {step_status, nB * L * 4, true}, {clearance, nB * L * 8, true}, {nearest, nB * L * 4, true},
+                          {chosen, nB * L * (size_t)(h->hp.desc.N + 1) * 3 * 4, true}}, [&](void** d, hipStream_t s) {
+        return mpc_closed_loop_batch_traffic_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], M, Lt, per_ego, (double*)d[4], (double*)d[5],
+                                                 pairing, noise_mode, sigma, seed, (double*)d[6], (double*)d[7], (int32_t*)d[8], (double*)d[9], (int32_t*)d[10],
+                                                 (int32_t*)d[11], s);
     });
 }
 

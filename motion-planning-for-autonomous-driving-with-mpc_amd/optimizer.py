@@ -88,6 +88,37 @@ def compute_centers_of_approximation_circles(x_position, y_position, v_length, v
     return center, center_fw, center_rw
 
 
+def nearest_obstacle_centres(poses, tracks, offsets, rows, ego_offset, pairing, default):
+    """The selection of the loop through traffic (csrc/mpc_closed_loop.h, loop_traffic_stage; include/mpcgpu.h, mpc_closed_loop_batch_traffic) for one
+    ego, in numpy: poses [K, 3] = predicted (x, y, psi) of the K stages, tracks [M, Lt, 3] (NaN x: absent), offsets [M], rows [K] = the track row every
+    stage sees, default [6] = the centres of a stage that sees no obstacle -> (centres [K, 6], chosen [K, 3]; -1: none).
+    pairing 0: the present obstacle with the smallest min_j |E_j - O_{m,j}| gives all three centres; 1: slot j is the circle nearest to ego circle j
+    over all present obstacles and circles.  Ties go to the lowest obstacle, then the lowest circle."""
+    def circles(x, y, th, off):
+        return np.array([[x, y], [x + off * np.cos(th), y + off * np.sin(th)], [x - off * np.cos(th), y - off * np.sin(th)]])
+    K = len(poses)
+    out, chosen = np.tile(np.asarray(default, dtype=np.float64), (K, 1)).reshape(K, 3, 2), np.full((K, 3), -1, dtype=np.int32)
+    for k in range(K):
+        E = circles(poses[k][0], poses[k][1], poses[k][2], ego_offset)
+        best = np.full(3, np.inf)
+        for m in range(len(tracks)):
+            x, y, th = tracks[m][rows[k]]
+            if not np.isfinite(x):
+                continue
+            O = circles(x, y, th, offsets[m])
+            if pairing == 0:
+                score = min(np.hypot(*(E[j] - O[j])) for j in range(3))
+                if chosen[k, 0] < 0 or score < best[0]:
+                    best[0], chosen[k], out[k] = score, m, O
+            else:
+                for j in range(3):
+                    for c in range(3):
+                        dist = np.hypot(*(E[j] - O[c]))
+                        if chosen[k, j] < 0 or dist < best[j]:
+                            best[j], chosen[k, j], out[k, j] = dist, m, O[c]
+    return out.reshape(K, 6), chosen
+
+
 class VehicleDynamics:
     """configuration.py:342-368 (kinematic single track); l = a + b of parameters_vehicle2."""
     l = 2.5789128
@@ -202,6 +233,21 @@ class Optimizer(object):
         self.obstacle_track = None if track is None else np.asarray(track, dtype=np.float64).reshape(-1, 3)
         _, disc_distance = compute_approximating_circle_radius(so["length"], so["width"])
         self.obstacle_offset = (disc_distance / 2) / 2
+        # optional (not in the reference): traffic.  obstacle_tracks [M, L, 3] = the pose of M obstacles at every loop step (NaN x: absent at that step),
+        # obstacle_sizes [M, 2] = their lengths and widths; obstacle_pairing 0 / 1 (nearest_obstacle_centres).  Every stage of every solve avoids the
+        # obstacle nearest to it (mpc_closed_loop_batch_traffic).  The circle centres of obstacle m lie +- disc_distance / 4 of ITS rectangle along its
+        # heading; a handle has ONE radius, so the lower bound of the circle rows (lbg) is that of the LARGEST obstacle, held against all of them.
+        tracks = getattr(configuration, "obstacle_tracks", None)
+        self.obstacle_tracks = None
+        if tracks is not None:
+            self.obstacle_tracks = np.asarray(tracks, dtype=np.float64)
+            sizes = np.asarray(configuration.obstacle_sizes, dtype=np.float64).reshape(-1, 2)
+            if self.obstacle_tracks.ndim != 3 or self.obstacle_tracks.shape[2] != 3 or len(sizes) != len(self.obstacle_tracks):
+                raise ValueError("obstacle_tracks must be [M, L, 3] with obstacle_sizes [M, 2]")
+            self.obstacle_offsets = np.array([compute_approximating_circle_radius(l, w)[1] / 4 for l, w in sizes])
+            self.radius_obstacle = max(compute_approximating_circle_radius(l, w)[0] for l, w in sizes)
+            self.obstacle_pairing = int(getattr(configuration, "obstacle_pairing", 0))
+        self.nearest = self.chosen = None           # optimize() through traffic: the nearest obstacle of every step (device loop), the obstacle behind every slot
         self.clearance = None           # optimize() with a track, device loop: distance - r_sum of every step (include/mpcgpu.h, mpc_closed_loop_batch_obst)
 
     def obstacle_centers_at(self, step):
@@ -227,7 +273,12 @@ class Optimizer(object):
 
 
 class CasadiOptimizer(Optimizer):
-    """optimizer.py:369-702 with the NLP solved on the GPU."""
+    """optimizer.py:369-702 with the NLP solved on the GPU.
+
+    Not in the reference: a configuration with `obstacle_tracks` [M, L, 3] (NaN x: absent at that step) and `obstacle_sizes` [M, 2] is driven through
+    traffic -- every stage of every solve avoids the obstacle nearest to it (BatchedMPCSolver.closed_loop_traffic; `obstacle_pairing` 0 / 1), on the
+    device and, with the same selection in numpy, in the step-by-step host loop.  The circle offsets are each obstacle's own (disc_distance / 4 of
+    its rectangle).  A handle has ONE radius: the lower bound of the circle rows (lbg) is that of the largest obstacle, held against all of them."""
 
     num_states = 5
     num_controls = 2
@@ -296,7 +347,13 @@ class CasadiOptimizer(Optimizer):
             backend.set_bounds(lbx, ubx, lbg, ubg)
             init_state = np.array([self.init_position[0], self.init_position[1], 0.0, self.init_velocity, self.init_orientation])
             loop_kw = dict(noise_mode=1 if noised else 0, sigma=sigma if noised else 0.0, seed=0 if seed is None else int(seed))
-            if self.obstacle_track is None:
+            if self.obstacle_tracks is not None:
+                # through traffic: every stage of every solve sees the obstacle nearest to it (mpc_closed_loop_batch_traffic)
+                traj, ctrl, st, cl, near, chosen = backend.closed_loop_traffic(init_state, self.resampled_path_points, self.orientation, self.desired_velocity,
+                                                                                self.iter_length, self.traffic_rows(), self.obstacle_offsets,
+                                                                                pairing=self.obstacle_pairing, **loop_kw)
+                self.clearance, self.nearest, self.chosen = cl[0], near[0], chosen[0]
+            elif self.obstacle_track is None:
                 traj, ctrl, st = backend.closed_loop(init_state, self.resampled_path_points, self.orientation, self.desired_velocity, self.iter_length, **loop_kw)
             else:
                 # every solve sees the obstacle where it is at its step, frozen over the horizon (mpc_closed_loop_batch_obst)
@@ -313,13 +370,19 @@ class CasadiOptimizer(Optimizer):
         x_now = np.array([self.init_position[0], self.init_position[1], 0.0, self.init_velocity, self.init_orientation], dtype=float)
         plan_u, plan_x = np.zeros((num_controls, N)), np.tile(x_now[:, None], (1, N + 1))
         window = np.tile(x_now, (N + 1, 1))                       # step 0 tracks the initial state itself
-        applied, visited, seconds = [], [x_now.copy()], []
+        applied, visited, seconds, chosen_log = [], [x_now.copy()], [], []
         for step in range(self.iter_length):
             p_vec = np.concatenate((np.zeros(num_controls * N), window.ravel()))[:, None]           # [U_ref = 0 | X_ref], optimizer.py:552
             w0 = self.warm_start(plan_u, plan_x, first=(step == 0))
             tic = time.time()
             sol, f = self.solver()
             obst_kw = {} if self.obstacle_track is None else dict(obst=self.obstacle_centers_at(step))      # (the obstacle where it is at this step)
+            if self.obstacle_tracks is not None:
+                # through traffic, the host twin of k_loop_traffic: stage k against the obstacles at time step + k, seen from the measured state at step 0
+                # and from the shifted last plan afterwards
+                centres, picked = self.traffic_centres(step, np.tile(x_now[[0, 1, 4]], (N + 1, 1)) if step == 0 else plan_x[[0, 1, 4]].T)
+                obst_kw = dict(obst=centres)
+                chosen_log.append(picked)
             w = sol(x0=w0, p=p_vec, lbg=lbg, lbx=lbx, ubg=ubg, ubx=ubx, **obst_kw)["x"].full().ravel()
             seconds.append(time.time() - tic)
             plan_u = w[:num_controls * N].reshape(N, num_controls).T
@@ -334,8 +397,26 @@ class CasadiOptimizer(Optimizer):
             plan_u, plan_x = self.shift(plan_u), self.shift(plan_x)
             window, _ = self.desired_command_and_trajectory(step, x_now, N)
             visited.append(x_now.copy())
+        self.chosen = np.array(chosen_log) if chosen_log else None
         # (what the reference returns: the states the solver was called AT -- the last propagated one is dropped, optimizer.py:639-641)
         return np.array(visited[:-1]), np.array(applied), np.array(seconds)
+
+    def ego_offset(self):
+        """front / rear circle centres of the ego: +- disc_distance / 4 of its rectangle along its heading (what solver() hands the backend)"""
+        return compute_approximating_circle_radius(self.configuration.p.l, self.configuration.p.w)[1] / 4
+
+    def traffic_rows(self):
+        """obstacle_tracks as the loop takes them: [M, Lt, 3] with Lt = 1 or Lt >= iter_length (a shorter track holds its last pose)"""
+        tr = self.obstacle_tracks
+        if tr.shape[1] == 1 or tr.shape[1] >= self.iter_length:
+            return tr
+        return tr[:, np.minimum(np.arange(self.iter_length), tr.shape[1] - 1)]
+
+    def traffic_centres(self, step, poses):
+        """(centres [N+1, 6], chosen [N+1, 3]) of the solve of loop step `step` for the predicted ego poses [N+1, 3] (x, y, psi) of its stages"""
+        tr = self.traffic_rows()
+        return nearest_obstacle_centres(poses, tr, self.obstacle_offsets, np.minimum(step + np.arange(len(poses)), tr.shape[1] - 1), self.ego_offset(),
+                                        self.obstacle_pairing, np.array(self.obstacle_circles_centers_tuple, dtype=np.float64).ravel())
 
     @staticmethod
     def shift(plan):
@@ -585,4 +666,4 @@ class ForcesproOptimizer(Optimizer):
 
 
 __all__ = ["CasadiOptimizer", "ForcesproOptimizer", "ForcesSolverHandle", "ForcesModel", "ForcesInfo", "Optimizer", "NlpSolverHandle", "DMLike", "VehicleDynamics", "ca", "np",
-           "find_closest_point", "compute_approximating_circle_radius", "compute_centers_of_approximation_circles"]
+           "find_closest_point", "nearest_obstacle_centres", "compute_approximating_circle_radius", "compute_centers_of_approximation_circles"]

@@ -366,8 +366,17 @@ class Configuration(object):
         c.use_case = self.settings["scenario_settings"]["use_case"]
         # optional (not in the reference): scenario_settings.dynamic_obstacle_id names a moving obstacle of the scenario to plan around -- its pose at
         # every loop step goes to the optimizer (the solve of a step sees it where it is at that step), its rectangle is the obstacle's size
+        # "all" or a list of ids: traffic -- every obstacle named (static ones too; "all": every obstacle of the scenario) goes to the optimizer as
+        # obstacle_tracks [M, L, 3] (NaN outside an obstacle's lifetime) with obstacle_sizes [M, 2], and every stage of every solve avoids the nearest
         dyn_id = self.settings["scenario_settings"].get("dynamic_obstacle_id")
-        if c.use_case == "collision_avoidance" and dyn_id is not None:
+        if c.use_case == "collision_avoidance" and (isinstance(dyn_id, (list, tuple)) or (isinstance(dyn_id, str) and dyn_id.strip().lower() == "all")):
+            c.obstacle_tracks, lengths, widths = obstacle_tracks(self.scenario, None if isinstance(dyn_id, str) else dyn_id, c.iter_length)
+            c.obstacle_sizes = np.stack([lengths, widths], axis=1)
+            first = int(np.argmax(np.isfinite(c.obstacle_tracks[:, :, 0]).any(axis=1)))
+            at = int(np.argmax(np.isfinite(c.obstacle_tracks[first, :, 0])))
+            c.static_obstacle = {"position_x": c.obstacle_tracks[first, at, 0], "position_y": c.obstacle_tracks[first, at, 1], "length": lengths[first],
+                                 "width": widths[first], "orientation": c.obstacle_tracks[first, at, 2]}
+        elif c.use_case == "collision_avoidance" and dyn_id is not None:
             c.obstacle_track, length, width = obstacle_track(self.scenario, dyn_id, c.iter_length)
             c.static_obstacle = {"position_x": c.obstacle_track[0, 0], "position_y": c.obstacle_track[0, 1], "length": length, "width": width,
                                  "orientation": c.obstacle_track[0, 2]}
@@ -415,6 +424,32 @@ def obstacle_track(scenario, obstacle_id, steps):
     return track, o.length, o.width
 
 
+def obstacle_tracks(scenario, ids, steps):
+    """(poses [M, steps, 3] (x, y, orientation), lengths [M], widths [M]) of the obstacles `ids` (None: all, static ones first, in the scenario's order)
+    at time steps 0 .. steps-1 -- the tracks of BatchedMPCSolver.closed_loop_traffic.  A static obstacle repeats its pose.  A moving obstacle has NaN
+    poses outside its lifetime (before its first and after its last recorded state: it is ABSENT there); a time step missing in between holds the one
+    before."""
+    steps = int(steps)
+    known = [(o.obstacle_id, o, True) for o in scenario.obstacles] + [(o.obstacle_id, o, False) for o in scenario.dynamic_obstacles]
+    if ids is None:
+        picked = known
+    else:
+        by_id = {i: q for q in known for i in (q[0],)}
+        missing = [int(i) for i in ids if int(i) not in by_id]
+        if missing:
+            raise KeyError("no obstacle {} in the scenario".format(missing))
+        picked = [by_id[int(i)] for i in ids]
+    poses = np.full((len(picked), steps, 3), np.nan)
+    for m, (_, o, static) in enumerate(picked):
+        if static:
+            poses[m] = [o.position[0], o.position[1], o.orientation]
+            continue
+        times = sorted(o.states)
+        for i in range(times[0], min(times[-1] + 1, steps)):
+            poses[m, i] = o.states[max(t for t in times if t <= i)]
+    return poses, np.array([q[1].length for q in picked], dtype=np.float64), np.array([q[1].width for q in picked], dtype=np.float64)
+
+
 def road_corridor(scenario, lanelet_ids, include_oncoming=True):
     """(left, right) boundary polylines, in driving direction, of the road along a lanelet sequence (a route): for every lanelet
     of the sequence the RIGHT bound of its rightmost neighbour of the same driving direction and, on the other side, the LEFT
@@ -452,6 +487,6 @@ def init_values(scenario, planning_problem_id=None):
     return pp.initial_position, pp.initial_velocity, pp.initial_acceleration, pp.initial_orientation
 
 
-__all__ = ["read_scenario", "Configuration", "init_values", "plan_route", "obstacle_rectangles", "obstacle_track", "road_corridor", "clip_reference_path", "find_closest_point",
+__all__ = ["read_scenario", "Configuration", "init_values", "plan_route", "obstacle_rectangles", "obstacle_track", "obstacle_tracks", "road_corridor", "clip_reference_path", "find_closest_point",
            "chaikins_corner_cutting", "resample_polyline", "compute_polyline_length", "compute_orientation_from_polyline",
            "parameters_vehicle2"]

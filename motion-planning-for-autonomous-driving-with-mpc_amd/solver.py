@@ -591,6 +591,47 @@ class BatchedMPCSolver:
         else:
             self._check(self._lib.mpc_closed_loop_batch_dev_ex(*head, *tail, _vp(stream)))
 
+    def closed_loop_traffic(self, init_state, path, orient, vdes, steps, tracks, offsets, pairing=0, noise_mode=0, sigma=0.0, seed=0):
+        """B egos through traffic (mpc_closed_loop_batch_traffic): before every solve each stage of each ego gets the circle centres of the obstacle
+        nearest to it at that stage's time -- the nearest-obstacle formulation; two obstacles equally close to one ego circle at one stage constrain
+        it only once.  tracks [M,Lt,3] (x, y, heading; NaN x: absent at that row) with offsets [M]: one scene shared by all egos; tracks [B,M,Lt,3]
+        with offsets [B,M]: a scene per ego.  Lt = 1 or Lt >= steps.  pairing 0: the reference's pairs on the nearest obstacle; 1: each ego circle
+        against its nearest obstacle circle.  A handle has one radius: the lower bound of its circle rows holds for every obstacle.
+        -> (traj [B,steps,5], ctrl [B,steps,2], step_status [B,steps], clearance [B,steps] over all nine pairs of every present obstacle (+inf: none),
+        nearest [B,steps] (the obstacle that attains it, -1: none), chosen [B,steps,N+1,3] (the obstacle behind every slot of every stage))"""
+        init_state = _abi.f64(init_state)
+        if init_state.ndim == 1:
+            init_state = init_state[None]
+        B = init_state.shape[0]
+        path = _abi.f64(path).reshape(B, -1, 2)
+        Lp = path.shape[1]
+        orient = _abi.f64(orient).reshape(B, Lp)
+        vdes = _abi.f64(np.broadcast_to(np.asarray(vdes, dtype=np.float64), (B,)))
+        steps = int(steps)
+        tracks, offsets = _abi.f64(tracks), _abi.f64(offsets)
+        if tracks.ndim not in (3, 4) or tracks.shape[-1] != 3 or (tracks.ndim == 4 and tracks.shape[0] != B) or offsets.shape != tracks.shape[:-2]:
+            raise MpcError(_abi.MPC_ERR_INVALID, "tracks must be [M, Lt, 3] with offsets [M], or [B, M, Lt, 3] with offsets [B, M]")
+        M, Lt = tracks.shape[-3], tracks.shape[-2]
+        traj, ctrl, st = np.empty((B, steps, 5)), np.empty((B, steps, 2)), np.empty((B, steps), np.int32)
+        cl, near, chosen = np.empty((B, steps)), np.empty((B, steps), np.int32), np.empty((B, steps, self.N + 1, 3), np.int32)
+        self._sens_gen += 1                                  # (like every loop: the library has ended the life of an earlier snapshot)
+        self._check(self._lib.mpc_closed_loop_batch_traffic(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient), _abi.as_dp(vdes),
+                                                            M, Lt, int(tracks.ndim == 4), _abi.as_dp(tracks), _abi.as_dp(offsets), int(pairing), int(noise_mode),
+                                                            float(sigma), int(seed) & (2 ** 64 - 1), _abi.as_dp(traj), _abi.as_dp(ctrl), _abi.as_ip(st),
+                                                            _abi.as_dp(cl), _abi.as_ip(near), _abi.as_ip(chosen)))
+        return traj, ctrl, st, cl, near, chosen
+
+    def closed_loop_traffic_device(self, B, d_init_state, d_path, d_orient, d_vdes, steps, Lp, M, Lt, per_ego, d_tracks, d_offsets, d_traj, d_ctrl,
+                                   d_step_status=0, pairing=0, noise_mode=0, sigma=0.0, seed=0, d_clearance=0, d_nearest=0, d_chosen=0, stream=0):
+        """device-pointer form (ints; 0 = absent) of closed_loop_traffic (mpc_closed_loop_batch_traffic_dev): d_tracks [M,Lt,3] / [B,M,Lt,3], d_offsets [M] /
+        [B,M] by per_ego, d_nearest [B,steps] and d_chosen [B,steps,N+1,3] int32.  The offsets are copied back once and checked, then the whole loop is
+        enqueued on `stream`."""
+        self._sens_gen += 1
+        self._check(self._lib.mpc_closed_loop_batch_traffic_dev(self._h, int(B), int(steps), int(Lp), _vp(d_init_state), _vp(d_path), _vp(d_orient), _vp(d_vdes),
+                                                                int(M), int(Lt), int(per_ego), _vp(d_tracks), _vp(d_offsets), int(pairing), int(noise_mode),
+                                                                float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl), _vp(d_step_status),
+                                                                _vp(d_clearance), _vp(d_nearest), _vp(d_chosen), _vp(stream)))
+
     def closed_loop_lin_device(self, B, d_init_state, d_path, d_orient, d_vdes, steps, Lp, d_traj, d_ctrl, d_step_status=0, noise_mode=0, sigma=0.0,
                                seed=0, stream=0, d_obst_track=0, Lt=0, obst_offset=0.0, d_clearance=0, d_kgain=0, d_wgain=0, d_ogain=0):
         """device-pointer form of closed_loop(..., linearize=True) (mpc_closed_loop_batch_lin_dev): d_kgain [B,steps,2,5], d_wgain [B,steps,2,7],
