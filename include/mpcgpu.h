@@ -356,6 +356,45 @@ int mpc_closed_loop_batch_traffic_dev(mpc_handle* h, int32_t B, int32_t L, int32
                                       const double* d_tracks, const double* d_offsets, int32_t pairing, int32_t noise_mode, double sigma,
                                       uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status, double* d_clearance,
                                       int32_t* d_nearest, int32_t* d_chosen, void* stream);
+/* The loop stepped FROM OUTSIDE: a session.  Every loop above is closed over its own model -- the plant is the NLP's forward-Euler step, the obstacles
+ * come from tracks that already hold the future.  A simulator or a vehicle owns the plant and reports a measured state every step; perception reports
+ * where the obstacles are NOW and how fast they move.  One session per handle; it owns device buffers of its own (the rows of its solves, the loop's work
+ * buffers, the record, copies of path / orient / vdes / offsets), released by mpc_session_end and mpc_destroy, so between two steps every other entry
+ * point of the handle may run -- solves, sens calls, other loops, mpc_set_weights, mpc_set_bounds: the next step uses the new weights and bounds.
+ *   mpc_session_begin   the arguments of mpc_closed_loop_batch_traffic that do not change over a loop; L >= N still fixes the frozen tail of the reference
+ *                       window, Lp >= L.  M = 0: lane following (plain solves, offsets NULL); M > 0: offsets [M] (per_ego: [B, M]), finite.  Everything is
+ *                       copied and the set-up has run when the call returns (both forms synchronise).  The record is filled with NaN / 0.
+ *   mpc_session_step    step i = mpc_session_steps_done(h), in stream order:
+ *       ingest      measured [B, 5] or NULL (the model's own Euler prediction: the loops above; required NULL at step 0, where init_state is the
+ *                   measurement) replaces the first five entries of the state and of row 0 of X_ref; a row whose x is not finite is a DROPPED
+ *                   measurement, that ego keeps the prediction; with nx = 6 the progress state stays the model's; the warm start stays the shifted last plan
+ *       obstacles   (M > 0) obs [M, 5] (per_ego: [B, M, 5]) = (x, y, heading, vx, vy) now; x not finite: absent; a velocity that is not finite counts
+ *                   as 0.  Stage k sees obstacle m at (x + (k dt) vx, y + (k dt) vy, heading), constant-velocity prediction, and the selection is
+ *                   mpc_closed_loop_batch_traffic's (both pairings, ties, the descriptor's centres when nothing is present; the ego pose is the state at
+ *                   step 0, stage k of the warm start afterwards).  clearance [B], nearest [B], chosen [B, N+1, 3], any of them NULL: this step's, as
+ *                   defined there, against the observed poses (M = 0: they must be NULL)
+ *       solve       mpc_solve_batch_dev (M > 0: mpc_solve_batch_stages_dev) on the session's rows, second chance included, synchronous
+ *       advance     the step is recorded (traj[b, i] = the state the solve started from, ctrl, step_status), the model's Euler step is the prediction
+ *                   for step i + 1, the next warm start and reference window are written; no noise
+ *       emit        u [B, 2] (required) the applied control, plan [B, n_w] the solution, status [B]; complete when the stream is synchronised
+ *   mpc_session_record  copies out what has been recorded so far (rows of steps not yet taken: NaN / 0); any argument may be NULL
+ *   mpc_session_steps_done  the index of the next step, -1 when no session is open
+ * With measured NULL at every step the record is bit for bit that of the loop it opens (M = 0: mpc_closed_loop_batch_ex; standing obstacles, vx = vy = 0:
+ * mpc_closed_loop_batch_traffic with Lt = 1, clearance / nearest / chosen included).  A step ends the life of a sensitivity snapshot, as any solve does.
+ * MPC_ERR_STATE: step / record / end without an open session, begin while one is open, step L + 1, bounds not set.  MPC_ERR_INVALID: M < 0; M > 0 with
+ * NULL or non-finite offsets; obs NULL with M > 0; measured at step 0; u NULL; pairing or per_ego outside {0, 1}; the shape rules of the loops.       */
+int mpc_session_begin(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                      const double* vdes, int32_t M, int32_t per_ego, const double* offsets, int32_t pairing);
+int mpc_session_begin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path, const double* d_orient,
+                          const double* d_vdes, int32_t M, int32_t per_ego, const double* d_offsets, int32_t pairing, void* stream);
+int mpc_session_step(mpc_handle* h, const double* measured, const double* obs, double* u, double* plan, int32_t* status, double* clearance,
+                     int32_t* nearest, int32_t* chosen);
+int mpc_session_step_dev(mpc_handle* h, const double* d_measured, const double* d_obs, double* d_u, double* d_plan, int32_t* d_status,
+                         double* d_clearance, int32_t* d_nearest, int32_t* d_chosen, void* stream);
+int mpc_session_record(mpc_handle* h, double* traj, double* ctrl, int32_t* step_status);
+int mpc_session_record_dev(mpc_handle* h, double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream);
+int mpc_session_steps_done(const mpc_handle* h);
+int mpc_session_end(mpc_handle* h);
 /* The same loop as a chain of optima, linearised: besides traj / ctrl / step_status / clearance, the per-step feedback gains of the first
  * control of every solve,
  *   kgain [B,L,2,5] = d u*_0 / d s_i  (s_i = traj[b,i], the measured state)      wgain [B,L,2,7] = d u*_0 / d wt  (wt = [Q_0..Q_4 | R_0, R_1])

@@ -15,7 +15,7 @@ The directory name contains hyphens (it is fixed by the build contract); import 
 at the repository root.
 """
 from ._abi import MpcLibraryError, load_library  # noqa: F401
-from .solver import BatchedMPCSolver, BoundSens, LoopLin, MpcError, ObstSens, SolveResult, WeightSens, rescue_failed  # noqa: F401
+from .solver import BatchedMPCSolver, BoundSens, LoopLin, LoopSession, MpcError, ObstSens, SolveResult, WeightSens, rescue_failed  # noqa: F401
 from . import mpc_planner, noise, optimizer, scenario, sharding  # noqa: E402,F401
 from .optimizer import CasadiOptimizer, ForcesproOptimizer  # noqa: E402,F401
 from .mpc_planner import MPCPlanner  # noqa: E402,F401

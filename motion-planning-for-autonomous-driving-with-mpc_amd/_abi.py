@@ -98,6 +98,14 @@ PROTOTYPES = {
     "mpc_closed_loop_batch_pred_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64, _i32] + _loop_tail + [_vp] * 5,
     "mpc_closed_loop_batch_traffic": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _i32, _i32, _dp, _dp, _i32] + _loop_tail + [_dp, _dp, _ip, _dp, _ip, _ip],
     "mpc_closed_loop_batch_traffic_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _vp, _vp, _i32] + _loop_tail + [_vp] * 7,
+    "mpc_session_begin": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _i32, _dp, _i32],
+    "mpc_session_begin_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _i32, _vp, _i32, _vp],
+    "mpc_session_step": [_vp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip],
+    "mpc_session_step_dev": [_vp] + [_vp] * 8 + [_vp],
+    "mpc_session_record": [_vp, _dp, _dp, _ip],
+    "mpc_session_record_dev": [_vp] + [_vp] * 3 + [_vp],
+    "mpc_session_steps_done": [_vp],
+    "mpc_session_end": [_vp],
     "mpc_closed_loop_batch_lin": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _dp, _f64] + _loop_tail + [_dp, _dp, _ip, _dp] + [_dp] * 3,
     "mpc_closed_loop_batch_lin_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64] + _loop_tail + [_vp] * 8,
     "mpc_loop_tangent": [_vp, _i32, _i32, _i32] + [_dp] * 5 + [_i32] + [_dp] * 5,

@@ -241,10 +241,18 @@ MPC_HD double loop_traffic_dist(const double* e, const double* o) {
 // |offset_m| of the distance d_m of the two poses.  loop_traffic_bound: the smallest d_m + reach_m over the obstacles present at `row` -- no winner
 // of any selection is farther than that; loop_traffic_near: false for an obstacle all of whose pairs are farther (by more than rounding), which
 // therefore wins nothing and ties with nothing.  The selection looks at the others only: the same result as looking at all.
-MPC_HD double loop_traffic_bound(const LoopTrafficArgs& A, int b, int row, const double* xy) {
-    double bound = INFINITY;
+// `Pose`: where obstacle m is for the stage being placed, pose(m, tmp3) -> (x, y, heading) -- a row of a track (TrafficTrackPose, the loops) or an
+// observed pose moved on at constant velocity (SessionObsPose, the stepping session), which is all the two differ in.
+struct TrafficTrackPose {
+    const LoopTrafficArgs& A;
+    int b, row;
+    MPC_HD const double* operator()(int m, double*) const { return loop_traffic_pose(A, b, m, row); }
+};
+template <class Pose>
+MPC_HD double loop_traffic_bound(const LoopTrafficArgs& A, int b, const Pose& at, const double* xy) {
+    double bound = INFINITY, tmp[3];
     for (int m = 0; m < A.M; ++m) {
-        const double* pose = loop_traffic_pose(A, b, m, row);
+        const double* pose = at(m, tmp);
         if (!loop_traffic_present(pose)) continue;
         const double hi = loop_traffic_dist(xy, pose) + A.ego_offset + fabs(loop_traffic_offset(A, b, m));
         if (hi < bound) bound = hi;
@@ -255,18 +263,19 @@ MPC_HD bool loop_traffic_near(const LoopTrafficArgs& A, int b, int m, const doub
     const double lo = loop_traffic_dist(xy, pose) - A.ego_offset - fabs(loop_traffic_offset(A, b, m));
     return !(lo > bound * (1.0 + 1e-12) + 1e-12);
 }
-MPC_HD void loop_traffic_stage(const LoopTrafficArgs& A, int b, int k, int i) {
+// row (b, k) of the solve of step i, and from the stage-0 call column `col` of clearance / nearest and block `col` of chosen (the loops: col = i)
+template <class Pose>
+MPC_HD void loop_traffic_place(const LoopTrafficArgs& A, int b, int k, int i, int col, const Pose& at) {
     const int N = A.N, S = N + 1, nw = 2 * N + A.nx * S;
-    const int at = i + k, row = at < A.Lt - 1 ? at : A.Lt - 1;
     const double* st = A.state + (size_t)b * A.nx;
     const double* pl = (i == 0) ? st : A.x0 + (size_t)b * nw + 2 * N + A.nx * k;
-    double e6[6], c6[6], out[6], best[3];
+    double e6[6], c6[6], out[6], best[3], tmp[3];
     int32_t pick[3] = {-1, -1, -1};
     loop_traffic_ego(pl[0], pl[1], pl[4], A.ego_offset, e6);
     for (int q = 0; q < 6; ++q) out[q] = A.desc_obst[q];
-    double bound = loop_traffic_bound(A, b, row, pl);
+    double bound = loop_traffic_bound(A, b, at, pl);
     for (int m = 0; m < A.M; ++m) {
-        const double* pose = loop_traffic_pose(A, b, m, row);
+        const double* pose = at(m, tmp);
         if (!loop_traffic_present(pose) || !loop_traffic_near(A, b, m, pose, pl, bound)) continue;
         loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
         if (A.pairing == 0) {
@@ -288,15 +297,15 @@ MPC_HD void loop_traffic_stage(const LoopTrafficArgs& A, int b, int k, int i) {
     double* o = A.obst + ((size_t)b * S + k) * 6;
     for (int q = 0; q < 6; ++q) o[q] = out[q];
     if (A.chosen)
-        for (int j = 0; j < 3; ++j) A.chosen[(((size_t)b * A.L + i) * S + k) * 3 + j] = pick[j];
+        for (int j = 0; j < 3; ++j) A.chosen[(((size_t)b * A.L + col) * S + k) * 3 + j] = pick[j];
     if (k != 0 || (!A.clearance && !A.nearest)) return;
     // the state before step i against every circle of every obstacle present at the step's own row
     double cl = INFINITY;
     int32_t near = -1;
     loop_traffic_ego(st[0], st[1], st[4], A.ego_offset, e6);
-    bound = loop_traffic_bound(A, b, row, st);
+    bound = loop_traffic_bound(A, b, at, st);
     for (int m = 0; m < A.M; ++m) {
-        const double* pose = loop_traffic_pose(A, b, m, row);
+        const double* pose = at(m, tmp);
         if (!loop_traffic_present(pose) || !loop_traffic_near(A, b, m, pose, st, bound)) continue;
         loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
         for (int j = 0; j < 3; ++j)
@@ -305,8 +314,55 @@ MPC_HD void loop_traffic_stage(const LoopTrafficArgs& A, int b, int k, int i) {
                 if (near < 0 || dist < cl) { cl = dist; near = m; }
             }
     }
-    if (A.clearance) A.clearance[(size_t)b * A.L + i] = near < 0 ? INFINITY : cl - A.r_sum;
-    if (A.nearest) A.nearest[(size_t)b * A.L + i] = near;
+    if (A.clearance) A.clearance[(size_t)b * A.L + col] = near < 0 ? INFINITY : cl - A.r_sum;
+    if (A.nearest) A.nearest[(size_t)b * A.L + col] = near;
+}
+MPC_HD void loop_traffic_stage(const LoopTrafficArgs& A, int b, int k, int i) {
+    const int at = i + k, row = at < A.Lt - 1 ? at : A.Lt - 1;
+    loop_traffic_place(A, b, k, i, i, TrafficTrackPose{A, b, row});
+}
+
+// =========================================================================================================================
+// The stepping session (mpc_session_begin / _step): the loop opened at step granularity for a caller that owns the plant and the perception.
+// Around the unchanged solve and loop_advance_instance it adds two pieces:
+//   * ingest: the measured state (x, y, delta, v, psi) of ego b replaces the model's prediction in `state` and in row 0 of X_ref; a row whose x is
+//     not finite is a dropped measurement (the prediction stays); the progress state of nx = 6 stays the model's; the warm start is left alone
+//   * obstacles: obs [M, 5] (per_ego: [B, M, 5]) = (x, y, heading, vx, vy) NOW; stage k sees obstacle m moved on at constant velocity,
+//     (x + (k dt) vx, y + (k dt) vy, heading) -- computed in the thread -- and the selection is loop_traffic_place's.  x not finite: absent; a
+//     velocity that is not finite counts as 0.  T.L = 1: clearance / nearest [B] and chosen [B, N+1, 3] are this step's
+// =========================================================================================================================
+struct SessionIngestArgs {
+    int32_t B, N, nx;
+    const double* measured;          // [B,5]
+    double* state;                   // [B,nx] LoopArgs::state
+    double* p;                       // [B,n_w] LoopArgs::p
+};
+MPC_HD void session_ingest_instance(const SessionIngestArgs& A, int b) {
+    const double* m = A.measured + (size_t)b * 5;
+    if (!loop_traffic_present(m)) return;
+    double* xr = A.p + (size_t)b * (2 * A.N + A.nx * (A.N + 1)) + 2 * A.N;
+    for (int c = 0; c < 5; ++c) { A.state[(size_t)b * A.nx + c] = m[c]; xr[c] = m[c]; }
+}
+struct SessionTrafficArgs {
+    LoopTrafficArgs T;               // tracks / Lt unused; L = 1
+    const double* obs;               // [M,5] or [B,M,5]
+    double dt;
+    int32_t step;                    // 0: the ego pose of every stage is the state; later: the stages of the warm start
+};
+struct SessionObsPose {
+    const SessionTrafficArgs& A;
+    int b;
+    double ahead;                    // k dt
+    MPC_HD const double* operator()(int m, double* tmp) const {
+        const double* o = A.obs + ((size_t)(A.T.per_ego ? b : 0) * A.T.M + m) * 5;
+        tmp[0] = o[0] + ahead * (loop_traffic_present(o + 3) ? o[3] : 0.0);
+        tmp[1] = o[1] + ahead * (loop_traffic_present(o + 4) ? o[4] : 0.0);
+        tmp[2] = o[2];
+        return tmp;
+    }
+};
+MPC_HD void session_traffic_stage(const SessionTrafficArgs& A, int b, int k) {
+    loop_traffic_place(A.T, b, k, A.step, 0, SessionObsPose{A, b, (double)k * A.dt});
 }
 
 // =========================================================================================================================

@@ -2490,6 +2490,28 @@ __global__ void __launch_bounds__(256) k_loop_traffic(const LoopTrafficArgs A, c
     if (t < A.B * S) loop_traffic_stage(A, t / S, t % S, i);
 }
 
+// The stepping session (mpc_closed_loop.h: SessionIngestArgs, SessionTrafficArgs).  Before solve i >= 1: one ego per thread takes its measured state
+__global__ void __launch_bounds__(128) k_session_ingest(const SessionIngestArgs A) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < A.B) session_ingest_instance(A, b);
+}
+// ... then the grid of k_loop_traffic: thread (b, k) places the obstacle rows of stage k from the observed poses, moved on k dt at their velocities
+__global__ void __launch_bounds__(256) k_session_traffic(const SessionTrafficArgs A) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, S = A.T.N + 1;
+    if (t < A.T.B * S) session_traffic_stage(A, t / S, t % S);
+}
+// behind k_loop_advance(i): the step's applied control (as recorded), the solution and its status into the caller's rows; plan / status may be null
+__global__ void __launch_bounds__(256) k_session_emit(const LoopArgs A, const int i, double* u, double* plan, int32_t* status) {
+    const int nw = 2 * A.N + A.nx * (A.N + 1);
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)A.B * nw) return;
+    const size_t b = t / nw;
+    const int q = (int)(t - b * nw);
+    if (plan) plan[t] = A.x_out[t];
+    if (q < 2) u[b * 2 + q] = A.ctrl[(b * A.L + i) * 2 + q];
+    if (q == 0 && status) status[b] = A.status[b];
+}
+
 // FORCES-mode closed loop (mpc_closed_loop.h: ForcesLoopArgs), one instance per thread
 __global__ void k_floop_setup(const ForcesLoopArgs A) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2789,6 +2811,16 @@ enum Scratch : int {
     N_SCRATCH
 };
 
+// The stepping session of a handle (mpc_session_*): ONE device allocation of its own, carved into the rows of its solves, the loop's work buffers, the
+// record and the copies of what mpc_session_begin was given -- nothing of the handle's I/O rows or scratch slots, so any other call may run between two steps
+struct LoopSession {
+    void* base = nullptr;               // null: no session is open
+    int32_t step = 0, M = 0, per_ego = 0, pairing = 0;
+    LoopArgs A{};                       // B, L, Lp and the rows (init_state: null once mpc_session_begin has returned)
+    double *xout = nullptr, *kkt = nullptr, *obst = nullptr, *offsets = nullptr;       // obst [B,N+1,6], offsets: null with M = 0
+    int32_t *status = nullptr, *iters = nullptr;
+};
+
 // d_fail / h_fail: instances that did not converge, counted by k_egest (one launch per kernel) or by every solve of an asynchronous closed loop over its steps (else: PH_FAIL); that loop's sticky abort word
 enum FailWord { FAIL_COUNT, FAIL_LOOP_ABORT, FAIL_WORDS };
 struct mpc_handle {
@@ -2853,6 +2885,7 @@ struct mpc_handle {
     std::vector<double> raw_bounds[4];  // lbx, ubx, lbg, ubg as mpc_set_bounds was given them (mpc_get_bounds)
     void* scratch[N_SCRATCH] = {};
     size_t scratch_cap[N_SCRATCH] = {};
+    LoopSession session;                // mpc_session_begin .. mpc_session_end
 };
 
 // error text of the last failed mpc_create on this thread (a handle does not exist yet to carry it)
@@ -3074,6 +3107,7 @@ int mpc_destroy(mpc_handle* h) {
     if (h->d_tile_mask) (void)hipFree(h->d_tile_mask);
     if (h->d_state) (void)hipFree(h->d_state);
     for (void* sp : h->scratch) if (sp) (void)hipFree(sp);
+    if (h->session.base) (void)hipFree(h->session.base);
     if (h->h_counter) (void)hipHostFree(h->h_counter);
     if (h->d_fail) (void)hipFree(h->d_fail);
     if (h->h_fail) (void)hipHostFree(h->h_fail);
@@ -4454,6 +4488,171 @@ int mpc_closed_loop_batch_traffic(mpc_handle* h, int32_t B, int32_t L, int32_t L
                                                  pairing, noise_mode, sigma, seed, (double*)d[6], (double*)d[7], (int32_t*)d[8], (double*)d[9], (int32_t*)d[10],
                                                  (int32_t*)d[11], s);
     });
+}
+
+// ---- the stepping session (include/mpcgpu.h, mpc_session_*): the loop above opened at step granularity ------------------------------------------
+static const char* const NO_SESSION = "session: no session is open on this handle (mpc_session_begin)";
+static const char* bad_session_begin(const mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const void* init_state, const void* path, const void* orient,
+                                     const void* vdes, int32_t M, int32_t per_ego, const void* offsets, int32_t pairing) {
+    if (B <= 0 || L <= 0 || Lp < L || L < h->hp.desc.N || !init_state || !path || !orient || !vdes)
+        return "session: B > 0, L >= N, Lp >= L and all of init_state, path, orient, vdes are required";
+    if (M < 0) return "session: M >= 0 obstacles (0: lane following)";
+    if (M > 0 && !offsets) return "session: offsets [M] (per_ego: [B, M]) are required with M > 0";
+    if (pairing != 0 && pairing != 1) return "session: pairing is 0 (the reference's pairs on the nearest obstacle) or 1 (each ego circle against its nearest circle)";
+    if (per_ego != 0 && per_ego != 1) return "session: per_ego is 0 (obstacles shared by all egos) or 1 (obstacles per ego)";
+    return nullptr;
+}
+static int session_refused(mpc_handle* h, bool want_open) {
+    if (!h) return MPC_ERR_INVALID;
+    if (want_open && !h->session.base) { h->err = NO_SESSION; return MPC_ERR_STATE; }
+    if (!want_open && h->session.base) { h->err = "session: a session is open on this handle (mpc_session_end)"; return MPC_ERR_STATE; }
+    return MPC_OK;
+}
+
+int mpc_session_begin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path, const double* d_orient,
+                          const double* d_vdes, int32_t M, int32_t per_ego, const double* d_offsets, int32_t pairing, void* stream_) {
+    if (const int rc = session_refused(h, false)) return rc;
+    if (!nlp_horizon_ok(h)) return MPC_ERR_INVALID;
+    if (const char* bad = bad_session_begin(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, M, per_ego, d_offsets, pairing)) { h->err = bad; return MPC_ERR_INVALID; }
+    if (!h->hp.bounds_set) { h->err = "mpc_set_bounds has not been called"; return MPC_ERR_STATE; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t stream = (hipStream_t)stream_;
+    const mpc_problem_desc& d = h->hp.desc;
+    const size_t nB = (size_t)B, nx = (size_t)d.nx, nw = h->hp.n_w(), nS = (size_t)d.N + 1, nO = M > 0 ? (per_ego ? nB : 1) * (size_t)M : 0;
+    if (M > 0) {
+        std::vector<double> off(nO);
+        HIP_TRY(h, hipMemcpyAsync(off.data(), d_offsets, nO * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(h, hipStreamSynchronize(stream));
+        for (double v : off)
+            if (!std::isfinite(v)) { h->err = "session: every offset must be finite"; return MPC_ERR_INVALID; }
+    }
+    // one allocation, every piece on a 256-byte boundary
+    size_t total = 0;
+    const auto take = [&](size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; };
+    const size_t o_state = take(nB * nx * 8), o_x0 = take(nB * nw * 8), o_p = take(nB * nw * 8), o_xout = take(nB * nw * 8), o_kkt = take(nB * 8),
+                 o_status = take(nB * 4), o_iters = take(nB * 4), o_obst = take(M > 0 ? nB * nS * 6 * 8 : 0), o_traj = take(nB * L * 5 * 8),
+                 o_ctrl = take(nB * L * 2 * 8), o_sst = take(nB * L * 4), o_path = take(nB * Lp * 2 * 8), o_orient = take(nB * Lp * 8), o_vdes = take(nB * 8),
+                 o_off = take(nO * 8);
+    void* base = nullptr;
+    if (hipMalloc(&base, total) != hipSuccess) { h->err = "session: out of device memory"; return MPC_ERR_HIP; }
+    char* c = static_cast<char*>(base);
+    const auto dbl = [&](size_t at) { return reinterpret_cast<double*>(c + at); };
+    LoopSession S;
+    S.base = base; S.M = M; S.per_ego = per_ego; S.pairing = pairing;
+    S.xout = dbl(o_xout); S.kkt = dbl(o_kkt); S.obst = M > 0 ? dbl(o_obst) : nullptr; S.offsets = M > 0 ? dbl(o_off) : nullptr;
+    S.status = reinterpret_cast<int32_t*>(c + o_status); S.iters = reinterpret_cast<int32_t*>(c + o_iters);
+    LoopArgs& A = S.A;
+    A.B = B; A.N = d.N; A.L = L; A.Lp = Lp; A.nx = d.nx;
+    A.init_state = d_init_state; A.path = dbl(o_path); A.orient = dbl(o_orient); A.vdes = dbl(o_vdes);
+    A.state = dbl(o_state); A.x0 = dbl(o_x0); A.p = dbl(o_p); A.x_out = S.xout; A.status = S.status;
+    A.traj = dbl(o_traj); A.ctrl = dbl(o_ctrl); A.step_status = reinterpret_cast<int32_t*>(c + o_sst);
+    // the caller's arrays are read here and never again: everything below has run when the call returns
+    hipError_t e = hipMemcpyAsync(dbl(o_path), d_path, nB * Lp * 2 * 8, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbl(o_orient), d_orient, nB * Lp * 8, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbl(o_vdes), d_vdes, nB * 8, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && M > 0) e = hipMemcpyAsync(S.offsets, d_offsets, nO * 8, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(A.traj, 0xFF, nB * L * 5 * 8, stream);              // (all bits set: NaN)
+    if (e == hipSuccess) e = hipMemsetAsync(A.ctrl, 0xFF, nB * L * 2 * 8, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(A.step_status, 0, nB * L * 4, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_loop_setup, dim3((B + 127) / 128), dim3(128), 0, stream, A);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        (void)hipFree(base);
+        h->err = std::string("session: setting up failed: ") + hipGetErrorString(e);
+        return MPC_ERR_HIP;
+    }
+    A.init_state = nullptr;
+    h->session = S;
+    return MPC_OK;
+}
+
+int mpc_session_begin(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                      const double* vdes, int32_t M, int32_t per_ego, const double* offsets, int32_t pairing) {
+    if (const int rc = session_refused(h, false)) return rc;
+    if (const char* bad = bad_session_begin(h, B, L, Lp, init_state, path, orient, vdes, M, per_ego, offsets, pairing)) { h->err = bad; return MPC_ERR_INVALID; }
+    const size_t nB = (size_t)B, nO = M > 0 ? (per_ego ? nB : 1) * (size_t)M : 0;
+    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
+                          {M > 0 ? offsets : nullptr, nO * 8, false}}, [&](void** d, hipStream_t s) {
+        return mpc_session_begin_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], M, per_ego, (double*)d[4], pairing, s);
+    });
+}
+
+int mpc_session_step_dev(mpc_handle* h, const double* d_measured, const double* d_obs, double* d_u, double* d_plan, int32_t* d_status, double* d_clearance,
+                         int32_t* d_nearest, int32_t* d_chosen, void* stream_) {
+    if (const int rc = session_refused(h, true)) return rc;
+    LoopSession& S = h->session;
+    const LoopArgs& A = S.A;
+    if (S.step >= A.L) { h->err = "session: all L steps have been taken (mpc_session_end, then mpc_session_begin)"; return MPC_ERR_STATE; }
+    if (!d_u) { h->err = "session: u [B, 2] is required"; return MPC_ERR_INVALID; }
+    if (d_measured && S.step == 0) { h->err = "session: step 0 takes no measured state (init_state of mpc_session_begin is the measurement)"; return MPC_ERR_INVALID; }
+    if (S.M > 0 && !d_obs) { h->err = "session: obs [M, 5] (per_ego: [B, M, 5]) is required, the session has M > 0 obstacles"; return MPC_ERR_INVALID; }
+    if (S.M == 0 && (d_clearance || d_nearest || d_chosen)) { h->err = "session: clearance, nearest and chosen need obstacles (M > 0)"; return MPC_ERR_INVALID; }
+    const mpc_problem_desc& d = h->hp.desc;
+    const int32_t B = A.B, i = S.step;
+    SolveIo io = solve_io(h, B, A.x0, A.p, S.obst, S.xout, S.status, S.iters, S.kkt);
+    if (S.M > 0) io = stages_io(h, io);
+    if (const int rc = begin_solve(h, io)) return rc;
+    const hipStream_t stream = (hipStream_t)stream_;
+    if (d_measured) hipLaunchKernelGGL(k_session_ingest, dim3((B + 127) / 128), dim3(128), 0, stream, SessionIngestArgs{B, d.N, d.nx, d_measured, A.state, A.p});
+    if (S.M > 0) {
+        SessionTrafficArgs T{};
+        T.T.B = B; T.T.L = 1; T.T.nx = d.nx; T.T.N = d.N; T.T.M = S.M; T.T.per_ego = S.per_ego; T.T.pairing = S.pairing;
+        T.T.offsets = S.offsets; T.T.ego_offset = d.ego_offset; T.T.obst = S.obst; T.T.state = A.state; T.T.x0 = A.x0;
+        T.T.clearance = d_clearance; T.T.nearest = d_nearest; T.T.chosen = d_chosen; T.T.r_sum = h->hp.ol_raw;
+        for (int q = 0; q < 6; ++q) T.T.desc_obst[q] = d.obstacle[q];
+        T.obs = d_obs; T.dt = d.dt; T.step = i;
+        hipLaunchKernelGGL(k_session_traffic, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, T);
+    }
+    if (const int rc = solve_dev(h, io, stream)) return rc;
+    hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, plant_params(h), A, i);
+    hipLaunchKernelGGL(k_session_emit, dim3((unsigned)(((size_t)B * io.n_w + 255) / 256)), dim3(256), 0, stream, A, i, d_u, d_plan, d_status);
+    HIP_TRY(h, hipGetLastError());
+    ++S.step;
+    return MPC_OK;
+}
+
+int mpc_session_step(mpc_handle* h, const double* measured, const double* obs, double* u, double* plan, int32_t* status, double* clearance,
+                     int32_t* nearest, int32_t* chosen) {
+    if (const int rc = session_refused(h, true)) return rc;
+    const LoopSession& S = h->session;
+    const size_t nB = (size_t)S.A.B, nO = (S.per_ego ? nB : 1) * (size_t)S.M, nS = (size_t)S.A.N + 1;
+    return stage_host(h, {{measured, nB * 5 * 8, false}, {S.M > 0 ? obs : nullptr, nO * 5 * 8, false}, {u, nB * 2 * 8, true}, {plan, nB * h->hp.n_w() * 8, true},
+                          {status, nB * 4, true}, {clearance, nB * 8, true}, {nearest, nB * 4, true}, {chosen, nB * nS * 3 * 4, true}},
+                      [&](void** d, hipStream_t s) {
+        return mpc_session_step_dev(h, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (int32_t*)d[4], (double*)d[5], (int32_t*)d[6], (int32_t*)d[7], s);
+    });
+}
+
+int mpc_session_record_dev(mpc_handle* h, double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream_) {
+    if (const int rc = session_refused(h, true)) return rc;
+    const LoopArgs& A = h->session.A;
+    const size_t n = (size_t)A.B * A.L;
+    const hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (d_traj) HIP_TRY(h, hipMemcpyAsync(d_traj, A.traj, n * 5 * 8, hipMemcpyDeviceToDevice, stream));
+    if (d_ctrl) HIP_TRY(h, hipMemcpyAsync(d_ctrl, A.ctrl, n * 2 * 8, hipMemcpyDeviceToDevice, stream));
+    if (d_step_status) HIP_TRY(h, hipMemcpyAsync(d_step_status, A.step_status, n * 4, hipMemcpyDeviceToDevice, stream));
+    return MPC_OK;
+}
+
+int mpc_session_record(mpc_handle* h, double* traj, double* ctrl, int32_t* step_status) {
+    if (const int rc = session_refused(h, true)) return rc;
+    const size_t n = (size_t)h->session.A.B * h->session.A.L;
+    return stage_host(h, {{traj, n * 5 * 8, true}, {ctrl, n * 2 * 8, true}, {step_status, n * 4, true}},
+                      [&](void** d, hipStream_t s) { return mpc_session_record_dev(h, (double*)d[0], (double*)d[1], (int32_t*)d[2], s); });
+}
+
+int mpc_session_steps_done(const mpc_handle* h) { return h && h->session.base ? h->session.step : -1; }
+
+int mpc_session_end(mpc_handle* h) {
+    if (const int rc = session_refused(h, true)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipFree(h->session.base));               // (waits for whatever still runs on the session's rows)
+    h->session = LoopSession{};
+    return MPC_OK;
 }
 
 // the loop with per-step gains: Lt = 0 with a null track is the plain loop (ogain must then be null); no gain asked for: the loop it wraps

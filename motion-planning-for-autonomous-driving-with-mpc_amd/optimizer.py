@@ -237,13 +237,16 @@ class Optimizer(object):
         # obstacle_sizes [M, 2] = their lengths and widths; obstacle_pairing 0 / 1 (nearest_obstacle_centres).  Every stage of every solve avoids the
         # obstacle nearest to it (mpc_closed_loop_batch_traffic).  The circle centres of obstacle m lie +- disc_distance / 4 of ITS rectangle along its
         # heading; a handle has ONE radius, so the lower bound of the circle rows (lbg) is that of the LARGEST obstacle, held against all of them.
+        # `obstacle_sizes` without tracks: what open_session() needs -- its caller observes the obstacles step by step and has no tracks to give.
         tracks = getattr(configuration, "obstacle_tracks", None)
-        self.obstacle_tracks = None
-        if tracks is not None:
-            self.obstacle_tracks = np.asarray(tracks, dtype=np.float64)
-            sizes = np.asarray(configuration.obstacle_sizes, dtype=np.float64).reshape(-1, 2)
-            if self.obstacle_tracks.ndim != 3 or self.obstacle_tracks.shape[2] != 3 or len(sizes) != len(self.obstacle_tracks):
-                raise ValueError("obstacle_tracks must be [M, L, 3] with obstacle_sizes [M, 2]")
+        sizes = getattr(configuration, "obstacle_sizes", None)
+        self.obstacle_tracks = self.obstacle_offsets = None
+        if tracks is not None or sizes is not None:
+            sizes = np.asarray(sizes, dtype=np.float64).reshape(-1, 2)
+            if tracks is not None:
+                self.obstacle_tracks = np.asarray(tracks, dtype=np.float64)
+                if self.obstacle_tracks.ndim != 3 or self.obstacle_tracks.shape[2] != 3 or len(sizes) != len(self.obstacle_tracks):
+                    raise ValueError("obstacle_tracks must be [M, L, 3] with obstacle_sizes [M, 2]")
             self.obstacle_offsets = np.array([compute_approximating_circle_radius(l, w)[1] / 4 for l, w in sizes])
             self.radius_obstacle = max(compute_approximating_circle_radius(l, w)[0] for l, w in sizes)
             self.obstacle_pairing = int(getattr(configuration, "obstacle_pairing", 0))
@@ -400,6 +403,20 @@ class CasadiOptimizer(Optimizer):
         self.chosen = np.array(chosen_log) if chosen_log else None
         # (what the reference returns: the states the solver was called AT -- the last propagated one is dropped, optimizer.py:639-641)
         return np.array(visited[:-1]), np.array(applied), np.array(seconds)
+
+    def open_session(self):
+        """The loop of optimize() stepped from outside (BatchedMPCSolver.session), built from the configuration as optimize() builds its device loop:
+        the bounds of inequal_constraints() (the radius of the largest obstacle), the initial state, the path, its orientation, the desired velocity,
+        and with `obstacle_sizes` [M, 2] the obstacles' offsets and `obstacle_pairing` -- no tracks are needed (nor handed over when the configuration has
+        some): the caller observes the obstacles.  Without `obstacle_sizes` the session is lane following (M = 0) past the static obstacle.  A simulator loop is `with o.open_session() as sess: u = sess.step(measured, obstacles)`, one ego: u [1, 2],
+        measured [5] (None at step 0), obstacles [M, 5] = (x, y, heading, vx, vy) now."""
+        lbg, ubg, lbx, ubx = self.inequal_constraints()
+        backend = self.solver()[0]._backend
+        backend.set_bounds(lbx, ubx, lbg, ubg)
+        init_state = np.array([self.init_position[0], self.init_position[1], 0.0, self.init_velocity, self.init_orientation])
+        traffic = self.obstacle_offsets is not None
+        return backend.session(init_state, self.resampled_path_points, self.orientation, self.desired_velocity, self.iter_length,
+                               offsets=self.obstacle_offsets if traffic else None, per_ego=0, pairing=self.obstacle_pairing if traffic else 0)
 
     def ego_offset(self):
         """front / rear circle centres of the ego: +- disc_distance / 4 of its rectangle along its heading (what solver() hands the backend)"""

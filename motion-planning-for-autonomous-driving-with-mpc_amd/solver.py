@@ -632,6 +632,12 @@ class BatchedMPCSolver:
                                                                 float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl), _vp(d_step_status),
                                                                 _vp(d_clearance), _vp(d_nearest), _vp(d_chosen), _vp(stream)))
 
+    def session(self, init_state, path, orient, vdes, steps, offsets=None, per_ego=None, pairing=0):
+        """the loop stepped from outside (mpc_session_begin): a LoopSession, `with solver.session(...) as sess: u = sess.step(measured, obstacles)`.
+        The arguments of closed_loop_traffic that do not change over a loop; offsets None: lane following (M = 0), [M]: obstacles shared by all egos,
+        [B, M]: per ego (per_ego overrides what the shape says, e.g. B = 1).  One session per solver; everything is copied."""
+        return LoopSession(self, init_state, path, orient, vdes, steps, offsets, per_ego, pairing)
+
     def closed_loop_lin_device(self, B, d_init_state, d_path, d_orient, d_vdes, steps, Lp, d_traj, d_ctrl, d_step_status=0, noise_mode=0, sigma=0.0,
                                seed=0, stream=0, d_obst_track=0, Lt=0, obst_offset=0.0, d_clearance=0, d_kgain=0, d_wgain=0, d_ogain=0):
         """device-pointer form of closed_loop(..., linearize=True) (mpc_closed_loop_batch_lin_dev): d_kgain [B,steps,2,5], d_wgain [B,steps,2,7],
@@ -913,6 +919,94 @@ class BatchedMPCSolver:
         self._check(self._lib.mpc_get_pipeline_profile(self._h, _abi.as_dp(out)))
         return dict(ms=out[0], ran=bool(out[1]), rounds=int(out[2]), riccati_wait_ms=out[3], stage_wait_ms=out[4],
                     stage_busy_ms=out[5], items=int(out[6]), stage_workers=int(out[7]), riccati_workers=int(round((out[7] % 1) * 1000)))
+
+
+class LoopSession:
+    """The closed loop stepped from outside (include/mpcgpu.h, mpc_session_*): the caller owns the plant and the perception.
+
+        with solver.session(init_state, path, orient, vdes, steps, offsets) as sess:
+            u = sess.step(obstacles=obs0)                       # step 0: init_state is the measurement
+            while sess.steps_done < steps:
+                u = sess.step(measured, obstacles)              # measured [B, 5] (NaN x: dropped), obstacles [M, 5] / [B, M, 5]
+            traj, ctrl, status = sess.record()
+
+    Between two steps the solver may be used for anything else; set_weights / set_bounds take effect at the next step."""
+
+    OUTPUTS = ("plan", "status", "clearance", "nearest", "chosen")
+
+    def __init__(self, solver, init_state, path, orient, vdes, steps, offsets=None, per_ego=None, pairing=0):
+        self._s = solver
+        init_state = _abi.f64(init_state)
+        if init_state.ndim == 1:
+            init_state = init_state[None]
+        B = init_state.shape[0]
+        path = _abi.f64(path).reshape(B, -1, 2)
+        Lp = path.shape[1]
+        orient = _abi.f64(orient).reshape(B, Lp)
+        vdes = _abi.f64(np.broadcast_to(np.asarray(vdes, dtype=np.float64), (B,)))
+        self.B, self.steps, self.M, self.per_ego = B, int(steps), 0, 0
+        if offsets is not None:
+            offsets = _abi.f64(offsets)
+            self.per_ego = int(offsets.ndim == 2) if per_ego is None else int(per_ego)
+            if offsets.ndim not in (1, 2) or (self.per_ego == 1 and offsets.shape[0] != B):
+                raise MpcError(_abi.MPC_ERR_INVALID, "offsets must be [M], or [B, M] for obstacles per ego")
+            self.M = offsets.shape[-1]
+            offsets = offsets.reshape(-1)
+        self._open = False
+        solver._check(solver._lib.mpc_session_begin(solver._h, B, self.steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient), _abi.as_dp(vdes),
+                                                    self.M, self.per_ego, _abi.as_dp(offsets), int(pairing)))
+        self._open = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._open:
+            self._open = False
+            self._s._check(self._s._lib.mpc_session_end(self._s._h))
+
+    @property
+    def steps_done(self):
+        """the index of the next step (mpc_session_steps_done)"""
+        return int(self._s._lib.mpc_session_steps_done(self._s._h))
+
+    def step(self, measured=None, obstacles=None, outputs=()):
+        """one step (mpc_session_step) -> u [B, 2], the control to apply; with outputs, a tuple of names out of OUTPUTS, -> (u, *those arrays):
+        plan [B, n_w] the solution, status [B], and with obstacles this step's clearance [B], nearest [B], chosen [B, N+1, 3].
+        measured [B, 5]: the plant's state now (None: the model's own prediction; None at step 0); obstacles [M, 5] or [B, M, 5]: (x, y, heading, vx, vy)
+        now, NaN x: absent"""
+        s, B = self._s, self.B
+        unknown = [o for o in outputs if o not in self.OUTPUTS]
+        if unknown:
+            raise MpcError(_abi.MPC_ERR_INVALID, f"outputs: {unknown} not in {self.OUTPUTS}")
+        if measured is not None:
+            measured = _abi.f64(measured, (B, 5))
+        if obstacles is not None:
+            obstacles = _abi.f64(obstacles, ((B,) if self.per_ego else ()) + (self.M, 5))
+        out = dict(plan=np.empty((B, s.n_w)), status=np.empty(B, np.int32), clearance=np.empty(B), nearest=np.empty(B, np.int32),
+                   chosen=np.empty((B, s.N + 1, 3), np.int32))
+        out = {k: (v if k in outputs else None) for k, v in out.items()}
+        u = np.empty((B, 2))
+        s._sens_gen += 1                                     # (a step is a solve: the library has ended the life of an earlier snapshot)
+        s._check(s._lib.mpc_session_step(s._h, _abi.as_dp(measured), _abi.as_dp(obstacles), _abi.as_dp(u), _abi.as_dp(out["plan"]), _abi.as_ip(out["status"]),
+                                         _abi.as_dp(out["clearance"]), _abi.as_ip(out["nearest"]), _abi.as_ip(out["chosen"])))
+        return (u, *[out[o] for o in outputs]) if outputs else u
+
+    def step_device(self, d_u, d_measured=0, d_obs=0, d_plan=0, d_status=0, d_clearance=0, d_nearest=0, d_chosen=0, stream=0):
+        """device-pointer form (ints; 0 = absent) of step (mpc_session_step_dev): enqueued on `stream`, the solve synchronises it"""
+        s = self._s
+        s._sens_gen += 1
+        s._check(s._lib.mpc_session_step_dev(s._h, _vp(d_measured), _vp(d_obs), _vp(d_u), _vp(d_plan), _vp(d_status), _vp(d_clearance), _vp(d_nearest),
+                                             _vp(d_chosen), _vp(stream)))
+
+    def record(self):
+        """(traj [B, steps, 5], ctrl [B, steps, 2], step_status [B, steps]) as recorded so far (mpc_session_record); steps not yet taken: NaN / 0"""
+        traj, ctrl, st = np.empty((self.B, self.steps, 5)), np.empty((self.B, self.steps, 2)), np.empty((self.B, self.steps), np.int32)
+        self._s._check(self._s._lib.mpc_session_record(self._s._h, _abi.as_dp(traj), _abi.as_dp(ctrl), _abi.as_ip(st)))
+        return traj, ctrl, st
 
 
 def rescue_failed(backend, x0, p, result, bounds, fractions=RESCUE_FRACTIONS):
