@@ -16,6 +16,10 @@
 namespace mpc {
 
 constexpr double BOUND_RELAX = 1e-8;   // IPOPT bound_relax_factor
+// widths of public arrays (include/mpcgpu.h): the cost weights wt = [Q_0 .. Q_4 | R_0, R_1] (mpc_sens.h); the states of traj and the numbers
+// of a pose x, y, heading (mpc_loop_lin.h)
+constexpr int SENS_NWT = 7, SENS_NWQ = 5;
+constexpr int LOOP_NS = 5, LOOP_NPOSE = 3;
 
 struct HostProblem {
     mpc_problem_desc desc{};

@@ -18,8 +18,6 @@
 
 namespace mpc {
 
-constexpr int LOOP_NS = 5, LOOP_NPOSE = 3;        // states of traj; numbers of a pose (x, y, heading)
-
 // the step a gain kernel works for: gain [B, L, 2, COLS] receives rows (b, i); track / Lt / offset: LoopObstArgs' (the obstacle family only)
 struct LoopGainArgs {
     int32_t L, i, Lt;

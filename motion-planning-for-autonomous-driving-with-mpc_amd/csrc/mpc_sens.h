@@ -746,8 +746,7 @@ MPC_HD void sens_lam_obst(const Params& P, const double* snap, double* lo) {
 // of the adjoint identity is 1e-10).  So the solve is sens_solve_circ's, with every circle shift t = 0 and SENS_WT_REFINE step of refinement
 // (the obstacle right-hand side starts from 6e-5 and needs two): the identity then holds to 5e-16.
 // x_k, u_k: the snapshot's Z; xref: the instance's p row pr (the p of the solve; the snapshot does not hold it).
-constexpr int SENS_NWT = 7, SENS_NWQ = 5;
-constexpr int SENS_WT_REFINE = 1;
+constexpr int SENS_WT_REFINE = 1;      // (SENS_NWT, SENS_NWQ: mpc_host_common.h)
 
 // forward direction: dwt [7] -> dw [n_w].  D: the stage data of sens_obst_setup; nrow, om, work: scratch of sens_solve_circ
 template <int NX>

@@ -465,4 +465,53 @@ struct SolveIo {
     template <class T> static void skip(T*& q, size_t elems) { if (q) q += elems; }
 };
 
+// ---- the arrays of one closed loop of B egos over L steps as the host loop chain of mpcgpu.hip passes them on, under the same rules as SolveIo.
+//      A new per-loop buffer is a member here, a row of each_array and a line at the entry point that accepts it.  (An aggregate: what every loop
+//      has comes first, in the order of the entry points' arguments, so that they can write LoopIo{B, L, Lp, ...}.)
+struct LoopIo {
+    int32_t B = 0, L = 0, Lp = 0;                                   // egos, steps, path points per ego
+    const double *init_state = nullptr, *path = nullptr, *orient = nullptr, *vdes = nullptr;
+    int32_t noise_mode = 0;
+    double sigma = 0.0;
+    uint64_t seed = 0;
+    double *traj = nullptr, *ctrl = nullptr;                        // written: the states before every step, the applied controls, ...
+    int32_t* step_status = nullptr;                                 // ... how every step's solve ended
+    double *kgain = nullptr, *wgain = nullptr, *ogain = nullptr;    // ... with mpc_closed_loop_batch_lin: the per-step gains (mpc_loop_lin.h)
+    // one obstacle track per ego (obst / pred / lin, the FORCES-mode obstacle loop).  tracked: the loop places obstacles in front of every solve --
+    // an entry point that takes a track says so, and Lt = 0 with a null track is then refused like any other missing track
+    bool tracked = false;
+    int32_t Lt = 0, predict = 0;
+    const double* track = nullptr;                                  // (through traffic: the M tracks)
+    double offset = 0.0;
+    double* clearance = nullptr;
+    // traffic: M >= 1 tracks shared by all egos, or per ego, with an offset each
+    int32_t M = 0, per_ego = 0, pairing = 0;
+    const double* offsets = nullptr;
+    int32_t *nearest = nullptr, *chosen = nullptr;
+
+    // THE table of the arrays, under a horizon of N stages: f(member, written by the loop, its bytes -- 0 where it is null) for each of the N_ARRAYS.
+    // nB egos, nL = nB L steps, nT tracks, nS = N + 1 stages of a solve.  Staging sizes (stage_loop of mpcgpu.hip) come from here and nowhere else.
+    static constexpr size_t N_ARRAYS = 15;
+    template <class F>
+    void each_array(int32_t N, F&& f) {
+        const size_t nB = (size_t)B, nL = nB * (size_t)L, nT = M > 0 ? (per_ego ? nB : 1) * (size_t)M : nB, nS = (size_t)N + 1;
+        const auto a = [&](auto*& m, bool out, size_t elems) { f(m, out, m ? elems * sizeof(*m) : 0); };
+        a(init_state, false, nB * 5); a(path, false, nB * Lp * 2); a(orient, false, nB * Lp); a(vdes, false, nB);
+        a(track, false, nT * Lt * 3); a(offsets, false, nT);
+        a(traj, true, nL * 5); a(ctrl, true, nL * 2); a(step_status, true, nL);
+        a(clearance, true, nL); a(nearest, true, nL); a(chosen, true, nL * nS * 3);
+        a(kgain, true, nL * 2 * LOOP_NS); a(wgain, true, nL * 2 * SENS_NWT); a(ogain, true, nL * 2 * LOOP_NPOSE);
+    }
+};
+
+// What every closed loop of the NLP refuses, whichever entry point it came through, host-pointer or device form (null: nothing)
+inline const char* loop_refusal(const LoopIo& io, int32_t N) {
+    if (io.B <= 0 || io.L <= 0 || io.Lp < io.L || io.L < N || !io.init_state || !io.path || !io.orient || !io.vdes || !io.traj || !io.ctrl)
+        return "closed loop: B > 0, L >= N, Lp >= L and all of init_state, path, orient, vdes, traj, ctrl are required";
+    if (io.noise_mode < 0 || io.noise_mode > 2 || (io.noise_mode != 0 && !(io.sigma >= 0.0))) return "closed loop: noise_mode in {0, 1, 2}, sigma >= 0";
+    if (io.tracked && (!io.track || (io.Lt != 1 && io.Lt < io.L) || !std::isfinite(io.offset)))
+        return "closed loop: obst_track [B, Lt, 3] is required, with Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i), and a finite obst_offset";
+    return nullptr;
+}
+
 }  // namespace mpc

@@ -2804,8 +2804,8 @@ enum Scratch : int {
     SCR_SENS_F,                         // sens_family_launch: the factors of the KKT matrices
     SCR_SENS_OBST,                      // sens_family_launch: the stage data and the solves' vectors of a family with CIRC (sens_obst_setup, sens_solve_circ)
     SCR_FQ_WS, SCR_FQ_FLAG, SCR_FQ_IT, SCR_FQ_RES,                         // mpc_forces_solve_batch_dev: workspace, outputs not asked for
-    SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves
-    SCR_FT_STATE, SCR_FT_ZBAR, SCR_FT_PARAMS, SCR_FT_ZOUT, SCR_FT_FLAG,    // mpc_forces_closed_loop_batch_obst_dev: the rows of its solves
+    SCR_FL_STATE, SCR_FL_ZBAR, SCR_FL_PARAMS, SCR_FL_ZOUT, SCR_FL_FLAG,    // mpc_forces_closed_loop_batch_dev: the rows of its solves (forces_loop_begin: five slots in this order)
+    SCR_FT_STATE, SCR_FT_ZBAR, SCR_FT_PARAMS, SCR_FT_ZOUT, SCR_FT_FLAG,    // mpc_forces_closed_loop_batch_obst_dev: the rows of its solves (the same five)
     SCR_LOOP_OBST,                      // closed_loop_dev: the obstacle rows of a loop with per-ego obstacle tracks (k_loop_obst)
     SCR_LOOP_SEED, SCR_LOOP_GRAD,       // closed_loop_dev with gains: the unit seeds and the gradient rows of k_loop_gain
     N_SCRATCH
@@ -3013,6 +3013,20 @@ static int stage_solve(mpc_handle* h, const SolveIo& io, const Stage (&more)[M],
 #define X(m, out) dio.m = static_cast<decltype(dio.m)>(*d++);
         IO_HOST_ROWS(X)
 #undef X
+        return dev(dio, d, s);
+    });
+}
+// The host-pointer form of a closed loop: the arrays of `io` (sizes: LoopIo::each_array under the handle's horizon) and the buffers `more` staged,
+// `dev` run with the arrays on the device, the device twins of `more` and the stream.
+static const Stage NO_MORE[1] = {{nullptr, 0, false}};
+template <size_t M, class Dev>
+static int stage_loop(mpc_handle* h, const LoopIo& io, const Stage (&more)[M], Dev&& dev) {
+    Stage st[LoopIo::N_ARRAYS + M], *q = st;
+    LoopIo dio = io;
+    dio.each_array(h->hp.desc.N, [&](auto*& m, bool out, size_t bytes) { *q++ = Stage{m, bytes, out}; });
+    std::copy(more, more + M, q);
+    return stage_host(h, st, [&](void** d, hipStream_t s) {
+        dio.each_array(h->hp.desc.N, [&](auto*& m, bool, size_t) { m = static_cast<std::remove_reference_t<decltype(m)>>(*d++); });
         return dev(dio, d, s);
     });
 }
@@ -4041,9 +4055,6 @@ static int solve_sens_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, d
     HIP_TRY(h, hipStreamSynchronize(s));
     return MPC_OK;
 }
-// the per-step gains of mpc_closed_loop_batch_lin[_dev] (mpc_loop_lin.h), each [B, L, 2, .] or null; the plain loops have none
-struct LoopLin { double *kgain, *wgain, *ogain; };
-
 // one family's gains of loop step A.i, between the step's solve (which left the snapshot) and k_loop_advance: k_loop_gain<NX, Fam>
 template <template <int> class Fam>
 static void loop_gain_launch(mpc_handle* h, int32_t B, const double* snap, double* F, double* W, double* seed, double* grad, const LoopGainArgs& A, hipStream_t s) {
@@ -4052,6 +4063,14 @@ static void loop_gain_launch(mpc_handle* h, int32_t B, const double* snap, doubl
 }
 
 static const char* bad_dirs(int32_t n_dir, const double* dp, const double* dw) { return n_dir < 0 || (n_dir > 0 && (!dp || !dw)) ? "n_dir >= 0, and dp, dw are required when n_dir > 0" : nullptr; }
+
+// the model scalars and the weights of the FORCES formulation, from the descriptor (ForcesArgs of k_forces_stage, ForcesQpArgs of k_forces_qp)
+template <class Args>
+static void forces_model(const mpc_problem_desc& d, Args& A) {
+    A.dt = d.dt; A.l = d.wheelbase; A.wb = d.friction_div; A.rho = d.ego_offset;
+    for (int i = 0; i < 5; ++i) { A.Q[i] = d.Q[i]; A.Pt[i] = d.P[i]; }
+    A.R[0] = d.R[0]; A.R[1] = d.R[1];
+}
 
 extern "C" {
 
@@ -4229,37 +4248,60 @@ int mpc_plant_step(mpc_handle* h, int32_t B, int32_t integrator, const double* x
                       [&](void** d, hipStream_t s) { return mpc_plant_step_dev(h, B, integrator, (double*)d[0], (double*)d[1], (double*)d[2], s); });
 }
 
-// per-ego obstacle tracks of a closed loop (mpc_closed_loop_batch_obst[_dev]); the plain loop has none
+// ---- the closed loops of the NLP.  A loop travels as one LoopIo (mpc_solve_plan.h): an entry point fills it from its arguments and makes the checks that
+//      are its own (loop_entry); the device forms then run closed_loop_dev, the host-pointer forms stage the arrays and run it on their twins -----------
+// `io` past one obstacle track per ego.  optional (the loops that run with and without: Lt = 0 with a null track is none): else a track is required
 // predict (mpc_closed_loop_batch_pred): stage k of the solve of step i sees track row min(i + k, Lt - 1) instead of row i
-// traffic (mpc_closed_loop_batch_traffic): M >= 1 tracks [M, Lt, 3] (per_ego: [B, M, Lt, 3]) with an offset each; every stage sees the nearest one
-struct LoopTrack { int32_t Lt; const double* d_track; double offset; double* d_clearance; int32_t predict = 0;
-                   int32_t M = 0, per_ego = 0, pairing = 0; const double* d_offsets = nullptr; int32_t* d_nearest = nullptr; int32_t* d_chosen = nullptr; };
-
-// the closed loop of every entry point, with `track` (k_loop_obst in front of every solve, whose rows then carry the obstacle centres) or without;
-// with `lin` (mpc_closed_loop_batch_lin_dev has checked it) step by step, every solve leaving its snapshot and the gain kernels of the families asked for behind
-// it (null: exactly the loop without)
-static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
-                           const double* d_orient, const double* d_vdes, const LoopTrack* track, int32_t noise_mode, double sigma, uint64_t seed,
-                           double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream_, const LoopLin* lin = nullptr) {
-    if (!h) return MPC_ERR_INVALID;
+static LoopIo with_track(LoopIo io, int32_t Lt, const double* track, double offset, double* clearance, int32_t predict = 0, bool optional = false) {
+    io.tracked = !optional || Lt != 0 || track; io.Lt = Lt; io.track = track; io.offset = offset; io.clearance = clearance; io.predict = predict;
+    return io;
+}
+// LoopArgs of a loop's bookkeeping kernels: the arrays of `lo`, the plant state and the rows of the loop's solves
+static LoopArgs loop_args(const mpc_handle* h, const LoopIo& lo, double* state, double* x0, double* p, const double* x_out, const int32_t* status) {
+    LoopArgs A{};
+    A.B = lo.B; A.N = h->hp.desc.N; A.L = lo.L; A.Lp = lo.Lp; A.nx = h->hp.desc.nx;
+    A.init_state = lo.init_state; A.path = lo.path; A.orient = lo.orient; A.vdes = lo.vdes;
+    A.state = state; A.x0 = x0; A.p = p; A.x_out = x_out; A.status = status;
+    A.traj = lo.traj; A.ctrl = lo.ctrl; A.step_status = lo.step_status;
+    A.noise_mode = lo.noise_mode; A.sigma = lo.sigma; A.seed_lo = (uint32_t)lo.seed; A.seed_hi = (uint32_t)(lo.seed >> 32);
+    return A;
+}
+// LoopTrafficArgs of k_loop_traffic / k_session_traffic: the traffic group of `lo`, the solves' obstacle rows, the state and warm start of `A`
+static LoopTrafficArgs loop_traffic_args(const mpc_handle* h, const LoopIo& lo, double* obst, const LoopArgs& A) {
     const mpc_problem_desc& d = h->hp.desc;
-    if (B <= 0 || L <= 0 || Lp < L || L < d.N || !d_init_state || !d_path || !d_orient || !d_vdes || !d_traj || !d_ctrl) {
-        h->err = "closed loop: B > 0, L >= N, Lp >= L and all of init_state, path, orient, vdes, traj, ctrl are required";
-        return MPC_ERR_INVALID;
-    }
-    if (noise_mode < 0 || noise_mode > 2 || (noise_mode != 0 && !(sigma >= 0.0))) { h->err = "closed loop: noise_mode in {0, 1, 2}, sigma >= 0"; return MPC_ERR_INVALID; }
-    if (track && (!track->d_track || (track->Lt != 1 && track->Lt < L) || !std::isfinite(track->offset))) {
-        h->err = "closed loop: obst_track [B, Lt, 3] is required, with Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i), and a finite obst_offset";
-        return MPC_ERR_INVALID;
-    }
+    LoopTrafficArgs T{};
+    T.B = lo.B; T.L = lo.L; T.Lt = lo.Lt; T.nx = d.nx; T.N = d.N; T.M = lo.M; T.per_ego = lo.per_ego; T.pairing = lo.pairing;
+    T.tracks = lo.track; T.offsets = lo.offsets; T.ego_offset = d.ego_offset; T.obst = obst; T.state = A.state; T.x0 = A.x0;
+    T.clearance = lo.clearance; T.nearest = lo.nearest; T.chosen = lo.chosen; T.r_sum = h->hp.ol_raw;
+    for (int q = 0; q < 6; ++q) T.desc_obst[q] = d.obstacle[q];
+    return T;
+}
+// the offsets of a loop through traffic live on the device: one small copy behind what the stream already holds, before anything of the loop is
+// enqueued; a value that is not finite is refused with `refusal`
+static int offsets_finite(mpc_handle* h, const LoopIo& lo, hipStream_t stream, const char* refusal) {
+    std::vector<double> off((size_t)(lo.per_ego ? lo.B : 1) * (size_t)lo.M);
+    HIP_TRY(h, hipMemcpyAsync(off.data(), lo.offsets, off.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    for (double v : off)
+        if (!std::isfinite(v)) { h->err = refusal; return MPC_ERR_INVALID; }
+    return MPC_OK;
+}
+
+// The closed loop of every entry point.  tracked: k_loop_obst (predict: k_loop_obst_stages, M > 0: k_loop_traffic) in front of every solve, whose rows
+// then carry the obstacle centres.  With a gain array (mpc_closed_loop_batch_lin_dev has checked them) step by step, every solve leaving its snapshot
+// and the gain kernels of the families asked for behind it; without: exactly the loop without.
+static int closed_loop_dev(mpc_handle* h, const LoopIo& lo, hipStream_t stream) {
+    const mpc_problem_desc& d = h->hp.desc;
+    if (const char* bad = loop_refusal(lo, d.N)) { h->err = bad; return MPC_ERR_INVALID; }
+    const int32_t B = lo.B, L = lo.L;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = ensure_io(h, (size_t)B);
     if (rc) return rc;
     double* d_obst = nullptr;
-    const bool traffic = track && track->M > 0;                       // (centres per stage, as the predicted loop)
-    const bool predict = track && (track->predict != 0 || traffic);
+    const bool traffic = lo.M > 0;                                    // (centres per stage, as the predicted loop)
+    const bool predict = lo.predict != 0 || traffic;
     const size_t n_obst = predict ? (size_t)6 * (size_t)(d.N + 1) : 6;
-    if (track && !(d_obst = static_cast<double*>(scratch_get(h, SCR_LOOP_OBST, (size_t)B * n_obst * sizeof(double))))) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    if (lo.tracked && !(d_obst = static_cast<double*>(scratch_get(h, SCR_LOOP_OBST, (size_t)B * n_obst * sizeof(double))))) { h->err = "out of device memory"; return MPC_ERR_HIP; }
     // the rows of every solve of the loop: the handle's own (begin_solve: the bounds must be set)
     SolveIo io = solve_io(h, B, h->d_x0, h->d_p, d_obst, h->d_xout, h->d_status, h->d_iters, h->d_kkt);
     if (predict) io = stages_io(h, io);
@@ -4270,38 +4312,36 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
         HIP_TRY(h, hipMalloc(&h->d_state, (size_t)B * 6 * sizeof(double)));
         h->cap_state = (size_t)B;
     }
-    hipStream_t stream = (hipStream_t)stream_;
-    LoopArgs A{};
-    A.B = B; A.N = d.N; A.L = L; A.Lp = Lp; A.nx = d.nx;
-    A.init_state = d_init_state; A.path = d_path; A.orient = d_orient; A.vdes = d_vdes;
-    A.state = h->d_state; A.x0 = h->d_x0; A.p = h->d_p; A.x_out = h->d_xout; A.status = h->d_status;
-    A.traj = d_traj; A.ctrl = d_ctrl; A.step_status = d_step_status;
-    A.noise_mode = noise_mode; A.sigma = sigma; A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32);
+    LoopArgs A = loop_args(h, lo, h->d_state, h->d_x0, h->d_p, h->d_xout, h->d_status);
     const Params P = plant_params(h);
     const dim3 grid((B + 127) / 128), block(128);
     // before solve i, with a track: ego b's row of the solve's obstacle centres (stream order keeps it until solve i, its second chance and any
     // restart have read it), and the clearance of its state
     LoopObstArgs O{};
     Params PO = P;
-    if (track) {
-        O.B = B; O.L = L; O.Lt = track->Lt; O.nx = d.nx;
-        O.track = track->d_track; O.offset = track->offset; O.obst = d_obst; O.state = h->d_state; O.clearance = track->d_clearance;
+    if (lo.tracked) {
+        O.B = B; O.L = L; O.Lt = lo.Lt; O.nx = d.nx;
+        O.track = lo.track; O.offset = lo.offset; O.obst = d_obst; O.state = h->d_state; O.clearance = lo.clearance;
         O.r_sum = h->hp.ol_raw;
         PO.ego_offset = d.ego_offset;
     }
-    LoopTrafficArgs T{};
-    if (traffic) {
-        T.B = B; T.L = L; T.Lt = track->Lt; T.nx = d.nx; T.N = d.N; T.M = track->M; T.per_ego = track->per_ego; T.pairing = track->pairing;
-        T.tracks = track->d_track; T.offsets = track->d_offsets; T.ego_offset = d.ego_offset; T.obst = d_obst; T.state = h->d_state; T.x0 = h->d_x0;
-        T.clearance = track->d_clearance; T.nearest = track->d_nearest; T.chosen = track->d_chosen; T.r_sum = h->hp.ol_raw;
-        for (int q = 0; q < 6; ++q) T.desc_obst[q] = d.obstacle[q];
-    }
+    LoopTrafficArgs T = traffic ? loop_traffic_args(h, lo, d_obst, A) : LoopTrafficArgs{};
     const auto place_obstacles = [&](int i) {
         if (traffic) { T.abort_flag = O.abort_flag; hipLaunchKernelGGL(k_loop_traffic, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, T, i); }
         else if (predict) hipLaunchKernelGGL(k_loop_obst_stages, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, PO, O, d.N, i);
-        else if (track) hipLaunchKernelGGL(k_loop_obst, grid, block, 0, stream, PO, O, i);
+        else if (lo.tracked) hipLaunchKernelGGL(k_loop_obst, grid, block, 0, stream, PO, O, i);
     };
-    if (lin) {
+    // One attempt at the loop: k_loop_setup, then for every step the obstacle rows, `solve` (false: the attempt ends there, with nothing more enqueued)
+    // and k_loop_advance
+    const auto run_steps = [&](auto&& solve) {
+        hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
+        for (int i = 0; i < L; ++i) {
+            place_obstacles(i);
+            if (!solve(i)) return;
+            hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
+        }
+    };
+    if (lo.kgain || lo.wgain || lo.ogain) {
         // Step by step: the snapshot solve synchronises.  Its launch plan does not depend on the snapshot, so traj, ctrl and step_status are those
         // of the step-by-step loop below, bit for bit.  The snapshot is never marked valid: the sens entry points refuse after this loop as after any.
         const size_t nB = (size_t)B, nw = io.n_w;
@@ -4310,22 +4350,20 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
         SolveIo sio = io;
         sio.snap = static_cast<double*>(scratch_get(h, SCR_SENS_SNAP, nB * io.snap_len * 8));
         double* F = static_cast<double*>(scratch_get(h, SCR_SENS_F, nB * (size_t)(d.N + 1) * (size_t)sens_fs(h) * 8));
-        double* W = (lin->wgain || lin->ogain) ? static_cast<double*>(scratch_get(h, SCR_SENS_OBST, nB * wlen * 8)) : nullptr;
+        double* W = (lo.wgain || lo.ogain) ? static_cast<double*>(scratch_get(h, SCR_SENS_OBST, nB * wlen * 8)) : nullptr;
         double* sd = static_cast<double*>(scratch_get(h, SCR_LOOP_SEED, nB * nw * 8));
         double* gr = static_cast<double*>(scratch_get(h, SCR_LOOP_GRAD, nB * nw * 8));          // (n_w: the longest row, the p family's)
-        if (!sio.snap || !F || ((lin->wgain || lin->ogain) && !W) || !sd || !gr) { h->err = "closed loop with gains: out of device memory"; return MPC_ERR_HIP; }
+        if (!sio.snap || !F || ((lo.wgain || lo.ogain) && !W) || !sd || !gr) { h->err = "closed loop with gains: out of device memory"; return MPC_ERR_HIP; }
         h->loop_replayed = 1;
-        hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
-        for (int i = 0; i < L; ++i) {
-            place_obstacles(i);
-            rc = solve_dev(h, sio, stream);
-            if (rc) return rc;
-            LoopGainArgs G{L, i, track ? track->Lt : 0, track ? track->d_track : nullptr, track ? track->offset : 0.0, nullptr};
-            if ((G.gain = lin->kgain)) loop_gain_launch<SensFamP>(h, B, sio.snap, F, W, sd, gr, G, stream);
-            if ((G.gain = lin->wgain)) loop_gain_launch<SensFamWeights>(h, B, sio.snap, F, W, sd, gr, G, stream);
-            if ((G.gain = lin->ogain)) loop_gain_launch<SensFamObst>(h, B, sio.snap, F, W, sd, gr, G, stream);
-            hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
-        }
+        run_steps([&](int i) {
+            if ((rc = solve_dev(h, sio, stream))) return false;
+            LoopGainArgs G{L, i, lo.tracked ? lo.Lt : 0, lo.tracked ? lo.track : nullptr, lo.tracked ? lo.offset : 0.0, nullptr};
+            if ((G.gain = lo.kgain)) loop_gain_launch<SensFamP>(h, B, sio.snap, F, W, sd, gr, G, stream);
+            if ((G.gain = lo.wgain)) loop_gain_launch<SensFamWeights>(h, B, sio.snap, F, W, sd, gr, G, stream);
+            if ((G.gain = lo.ogain)) loop_gain_launch<SensFamObst>(h, B, sio.snap, F, W, sd, gr, G, stream);
+            return true;
+        });
+        if (rc) return rc;
         HIP_TRY(h, hipGetLastError());
         return MPC_OK;
     }
@@ -4337,16 +4375,13 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
     if (plan_solve(h->hp, h->knobs, plan_state(h, B, io.obst_mode(), false)).loop_async) {
         HIP_TRY(h, hipMemsetAsync(h->d_fail, 0, FAIL_WORDS * sizeof(uint32_t), stream));
         A.abort_flag = O.abort_flag = h->d_fail + FAIL_LOOP_ABORT;
-        hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
         bool all_async = true;
         SolveOutcome out;
-        for (int i = 0; i < L && all_async; ++i) {
-            place_obstacles(i);
-            rc = solve_dev_any(h, io, SolveCall{stream, nullptr, true}, out);
-            if (rc) return rc;
-            all_async = out.async_ok;            // (a batch shape the pipeline does not take: the solve has run synchronously -- start over)
-            if (all_async) hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
-        }
+        run_steps([&](int) {
+            if ((rc = solve_dev_any(h, io, SolveCall{stream, nullptr, true}, out))) return false;
+            return all_async = out.async_ok;     // (a batch shape the pipeline does not take: the solve has run synchronously -- start over)
+        });
+        if (rc) return rc;
         keep_outcome(h, out);
         if (all_async) {
             HIP_TRY(h, hipMemcpyAsync(h->h_fail, h->d_fail, FAIL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -4362,144 +4397,156 @@ static int closed_loop_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, cons
     h->loop_replayed = replay ? 1 : 0;
     if (replay) {
         A.abort_flag = O.abort_flag = nullptr;
-        hipLaunchKernelGGL(k_loop_setup, grid, block, 0, stream, A);
-        for (int i = 0; i < L; ++i) {
-            place_obstacles(i);
-            rc = solve_dev(h, io, stream);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, P, A, i);
-        }
+        run_steps([&](int) { return !(rc = solve_dev(h, io, stream)); });
+        if (rc) return rc;
     }
     if (loop_abandoned) count_abandoned_launch(h);
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
+// An entry point of these loops, in either form.  `own`: what the entry point refuses about its own arguments (null: it has none).  host: the arrays of
+// `io` are the caller's host arrays -- the common refusals before anything is staged, then `dev` on the device twins and the handle's stream
+using LoopCheck = const char* (*)(const mpc_handle*, const LoopIo&);
+static int loop_entry(mpc_handle* h, const LoopIo& io, LoopCheck own, bool host, void* stream, int (*dev)(mpc_handle*, const LoopIo&, hipStream_t) = closed_loop_dev) {
+    if (!h) return MPC_ERR_INVALID;
+    const char* bad = own ? own(h, io) : nullptr;
+    if (!bad && host) bad = loop_refusal(io, h->hp.desc.N);
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    if (!host) return dev(h, io, (hipStream_t)stream);
+    return stage_loop(h, io, NO_MORE, [&](const LoopIo& dio, void**, hipStream_t s) { return dev(h, dio, s); });
+}
 
 int mpc_closed_loop_batch_dev_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
                                  const double* d_orient, const double* d_vdes, int32_t noise_mode, double sigma, uint64_t seed,
                                  double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream_) {
-    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, nullptr, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, stream_);
+    return loop_entry(h, LoopIo{B, L, Lp, d_init_state, d_path, d_orient, d_vdes, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status}, nullptr, false, stream_);
 }
+int mpc_closed_loop_batch_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
+                             const double* orient, const double* vdes, int32_t noise_mode, double sigma, uint64_t seed, double* traj,
+                             double* ctrl, int32_t* step_status) {
+    return loop_entry(h, LoopIo{B, L, Lp, init_state, path, orient, vdes, noise_mode, sigma, seed, traj, ctrl, step_status}, nullptr, true, nullptr);
+}
+int mpc_closed_loop_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                              const double* d_orient, const double* d_vdes, double* d_traj, double* d_ctrl, int32_t* d_step_status,
+                              void* stream_) {
+    return mpc_closed_loop_batch_dev_ex(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, 0, 0.0, 0, d_traj, d_ctrl, d_step_status, stream_);
+}
+int mpc_closed_loop_batch(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
+                          const double* orient, const double* vdes, double* traj, double* ctrl, int32_t* step_status) {
+    return mpc_closed_loop_batch_ex(h, B, L, Lp, init_state, path, orient, vdes, 0, 0.0, 0, traj, ctrl, step_status);
+}
+int mpc_last_loop_replayed(const mpc_handle* h) { return h ? h->loop_replayed : MPC_ERR_INVALID; }
 
 int mpc_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
                                    const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
                                    int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status,
                                    double* d_clearance, void* stream_) {
-    const LoopTrack track{Lt, d_obst_track, obst_offset, d_clearance};
-    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, &track, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, stream_);
+    const LoopIo io{B, L, Lp, d_init_state, d_path, d_orient, d_vdes, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status};
+    return loop_entry(h, with_track(io, Lt, d_obst_track, obst_offset, d_clearance), nullptr, false, stream_);
+}
+int mpc_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                               const double* vdes, int32_t Lt, const double* obst_track, double obst_offset, int32_t noise_mode, double sigma,
+                               uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance) {
+    const LoopIo io{B, L, Lp, init_state, path, orient, vdes, noise_mode, sigma, seed, traj, ctrl, step_status};
+    return loop_entry(h, with_track(io, Lt, obst_track, obst_offset, clearance), nullptr, true, nullptr);
 }
 
 // the loop past per-ego obstacles with the obstacle predicted over each solve's horizon (predict 1) or frozen (predict 0: the loop above)
-static const char* const PRED_REFUSAL = "closed loop: predict is 0 (the obstacle frozen over each solve's horizon) or 1 (stage k sees track row min(i + k, Lt - 1))";
+static const char* bad_pred(const mpc_handle*, const LoopIo& io) {
+    if (io.predict != 0 && io.predict != 1) return "closed loop: predict is 0 (the obstacle frozen over each solve's horizon) or 1 (stage k sees track row min(i + k, Lt - 1))";
+    if (io.predict && (io.Lt <= 0 || !io.track)) return "closed loop: predict 1 needs obst_track [B, Lt, 3] with Lt >= 1";
+    return nullptr;
+}
 int mpc_closed_loop_batch_pred_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
                                    const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
                                    int32_t predict, int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl,
                                    int32_t* d_step_status, double* d_clearance, void* stream_) {
-    if (!h) return MPC_ERR_INVALID;
-    if (predict != 0 && predict != 1) { h->err = PRED_REFUSAL; return MPC_ERR_INVALID; }
-    if (predict && (Lt <= 0 || !d_obst_track)) { h->err = "closed loop: predict 1 needs obst_track [B, Lt, 3] with Lt >= 1"; return MPC_ERR_INVALID; }
-    const LoopTrack track{Lt, d_obst_track, obst_offset, d_clearance, predict};
-    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, &track, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, stream_);
+    const LoopIo io{B, L, Lp, d_init_state, d_path, d_orient, d_vdes, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status};
+    return loop_entry(h, with_track(io, Lt, d_obst_track, obst_offset, d_clearance, predict), bad_pred, false, stream_);
 }
-
 int mpc_closed_loop_batch_pred(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
                                const double* vdes, int32_t Lt, const double* obst_track, double obst_offset, int32_t predict, int32_t noise_mode,
                                double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
-    if (predict != 0 && predict != 1) { h->err = PRED_REFUSAL; return MPC_ERR_INVALID; }
-    if (predict && (Lt <= 0 || !obst_track)) { h->err = "closed loop: predict 1 needs obst_track [B, Lt, 3] with Lt >= 1"; return MPC_ERR_INVALID; }
-    if (!obst_track || (Lt != 1 && Lt < L)) {
-        h->err = "closed loop: obst_track [B, Lt, 3] is required, with Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i)";
-        return MPC_ERR_INVALID;
-    }
-    const size_t nB = (size_t)B;
-    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
-                          {obst_track, nB * Lt * 3 * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true}, {step_status, nB * L * 4, true},
-                          {clearance, nB * L * 8, true}}, [&](void** d, hipStream_t s) {
-        return mpc_closed_loop_batch_pred_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], obst_offset, predict,
-                                              noise_mode, sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], (double*)d[8], s);
-    });
+    const LoopIo io{B, L, Lp, init_state, path, orient, vdes, noise_mode, sigma, seed, traj, ctrl, step_status};
+    return loop_entry(h, with_track(io, Lt, obst_track, obst_offset, clearance, predict), bad_pred, true, nullptr);
 }
 
-int mpc_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
-                               const double* vdes, int32_t Lt, const double* obst_track, double obst_offset, int32_t noise_mode, double sigma,
-                               uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
-    if (!obst_track || (Lt != 1 && Lt < L)) {
-        h->err = "closed loop: obst_track [B, Lt, 3] is required, with Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i)";
-        return MPC_ERR_INVALID;
-    }
-    const size_t nB = (size_t)B;
-    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
-                          {obst_track, nB * Lt * 3 * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true}, {step_status, nB * L * 4, true},
-                          {clearance, nB * L * 8, true}}, [&](void** d, hipStream_t s) {
-        return mpc_closed_loop_batch_obst_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], obst_offset, noise_mode,
-                                              sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], (double*)d[8], s);
-    });
+// the loop through traffic: every stage of every solve sees the nearest of M obstacles (k_loop_traffic in front of every solve, which reads centres per
+// stage): M >= 1 tracks [M, Lt, 3] (per_ego: [B, M, Lt, 3]) with an offset each
+static LoopIo with_traffic(LoopIo io, int32_t M, int32_t Lt, int32_t per_ego, const double* tracks, const double* offsets, int32_t pairing,
+                           double* clearance, int32_t* nearest, int32_t* chosen) {
+    io = with_track(io, Lt, tracks, 0.0, clearance);
+    io.M = M; io.per_ego = per_ego; io.pairing = pairing; io.offsets = offsets; io.nearest = nearest; io.chosen = chosen;
+    return io;
 }
-
-// the loop through traffic: every stage of every solve sees the nearest of M obstacles (k_loop_traffic in front of every solve, which reads centres per stage)
-static const char* bad_traffic(int32_t L, int32_t M, int32_t Lt, int32_t per_ego, const void* tracks, const void* offsets, int32_t pairing) {
-    if (M < 1) return "traffic loop: M >= 1 obstacle tracks are required";
-    if (Lt != 1 && Lt < L) return "traffic loop: Lt = 1 (the obstacles stand still) or Lt >= L (row i: the obstacles at step i)";
-    if (!tracks) return "traffic loop: tracks [M, Lt, 3] (per_ego: [B, M, Lt, 3]) are required";
-    if (!offsets) return "traffic loop: offsets [M] (per_ego: [B, M]) are required";
-    if (pairing != 0 && pairing != 1) return "traffic loop: pairing is 0 (the reference's pairs on the nearest obstacle) or 1 (each ego circle against its nearest circle)";
-    if (per_ego != 0 && per_ego != 1) return "traffic loop: per_ego is 0 (tracks shared by all egos) or 1 (tracks per ego)";
+static const char* bad_traffic(const mpc_handle*, const LoopIo& io) {
+    if (io.M < 1) return "traffic loop: M >= 1 obstacle tracks are required";
+    if (io.Lt != 1 && io.Lt < io.L) return "traffic loop: Lt = 1 (the obstacles stand still) or Lt >= L (row i: the obstacles at step i)";
+    if (!io.track) return "traffic loop: tracks [M, Lt, 3] (per_ego: [B, M, Lt, 3]) are required";
+    if (!io.offsets) return "traffic loop: offsets [M] (per_ego: [B, M]) are required";
+    if (io.pairing != 0 && io.pairing != 1) return "traffic loop: pairing is 0 (the reference's pairs on the nearest obstacle) or 1 (each ego circle against its nearest circle)";
+    if (io.per_ego != 0 && io.per_ego != 1) return "traffic loop: per_ego is 0 (tracks shared by all egos) or 1 (tracks per ego)";
     return nullptr;
 }
-static const char* const TRAFFIC_OFFSET_REFUSAL = "traffic loop: every offset must be finite";
+static int traffic_loop_dev(mpc_handle* h, const LoopIo& io, hipStream_t stream) {
+    if (io.B <= 0) { h->err = "closed loop: B > 0 is required"; return MPC_ERR_INVALID; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (const int rc = offsets_finite(h, io, stream, "traffic loop: every offset must be finite")) return rc;
+    return closed_loop_dev(h, io, stream);
+}
 int mpc_closed_loop_batch_traffic_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
                                       const double* d_orient, const double* d_vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* d_tracks,
                                       const double* d_offsets, int32_t pairing, int32_t noise_mode, double sigma, uint64_t seed, double* d_traj,
                                       double* d_ctrl, int32_t* d_step_status, double* d_clearance, int32_t* d_nearest, int32_t* d_chosen, void* stream_) {
-    if (!h) return MPC_ERR_INVALID;
-    if (const char* bad = bad_traffic(L, M, Lt, per_ego, d_tracks, d_offsets, pairing)) { h->err = bad; return MPC_ERR_INVALID; }
-    if (B <= 0) { h->err = "closed loop: B > 0 is required"; return MPC_ERR_INVALID; }
-    // the offsets live on the device: one small copy behind what the stream already holds, before anything of the loop is enqueued
-    HIP_TRY(h, hipSetDevice(h->device));
-    std::vector<double> off((size_t)(per_ego ? B : 1) * (size_t)M);
-    HIP_TRY(h, hipMemcpyAsync(off.data(), d_offsets, off.size() * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream_));
-    HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream_));
-    for (double v : off)
-        if (!std::isfinite(v)) { h->err = TRAFFIC_OFFSET_REFUSAL; return MPC_ERR_INVALID; }
-    LoopTrack track{Lt, d_tracks, 0.0, d_clearance, 0};
-    track.M = M; track.per_ego = per_ego; track.pairing = pairing; track.d_offsets = d_offsets; track.d_nearest = d_nearest; track.d_chosen = d_chosen;
-    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, &track, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, stream_);
+    const LoopIo io{B, L, Lp, d_init_state, d_path, d_orient, d_vdes, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status};
+    return loop_entry(h, with_traffic(io, M, Lt, per_ego, d_tracks, d_offsets, pairing, d_clearance, d_nearest, d_chosen), bad_traffic, false, stream_, traffic_loop_dev);
 }
-
 int mpc_closed_loop_batch_traffic(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
                                   const double* vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* tracks, const double* offsets, int32_t pairing,
                                   int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance,
                                   int32_t* nearest, int32_t* chosen) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
-    if (const char* bad = bad_traffic(L, M, Lt, per_ego, tracks, offsets, pairing)) { h->err = bad; return MPC_ERR_INVALID; }
-    const size_t nB = (size_t)B, nT = (per_ego ? nB : 1) * (size_t)M;
-    for (size_t q = 0; q < nT; ++q)
-        if (!std::isfinite(offsets[q])) { h->err = TRAFFIC_OFFSET_REFUSAL; return MPC_ERR_INVALID; }
-    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
-                          {tracks, nT * Lt * 3 * 8, false}, {offsets, nT * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true},
-                          {step_status, nB * L * 4, true}, {clearance, nB * L * 8, true}, {nearest, nB * L * 4, true},
-                          {chosen, nB * L * (size_t)(h->hp.desc.N + 1) * 3 * 4, true}}, [&](void** d, hipStream_t s) {
-        return mpc_closed_loop_batch_traffic_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], M, Lt, per_ego, (double*)d[4], (double*)d[5],
-                                                 pairing, noise_mode, sigma, seed, (double*)d[6], (double*)d[7], (int32_t*)d[8], (double*)d[9], (int32_t*)d[10],
-                                                 (int32_t*)d[11], s);
-    });
+    const LoopIo io{B, L, Lp, init_state, path, orient, vdes, noise_mode, sigma, seed, traj, ctrl, step_status};
+    return loop_entry(h, with_traffic(io, M, Lt, per_ego, tracks, offsets, pairing, clearance, nearest, chosen), bad_traffic, true, nullptr, traffic_loop_dev);
+}
+
+// the loop with per-step gains: Lt = 0 with a null track is the plain loop (ogain must then be null); no gain asked for: the loop it wraps
+static const char* bad_lin(const mpc_handle* h, const LoopIo& io) {
+    if (h->hp.desc.fixed_iters > 0) return "closed loop with gains: the sensitivities need solves to convergence (fixed_iters = 0)";
+    if (!io.tracked && io.ogain) return "closed loop with gains: ogain needs obst_track";
+    if (!io.tracked && io.clearance) return "closed loop with gains: clearance needs obst_track";
+    return nullptr;
+}
+int mpc_closed_loop_batch_lin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                  const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
+                                  int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status,
+                                  double* d_clearance, double* d_kgain, double* d_wgain, double* d_ogain, void* stream_) {
+    const LoopIo io{B, L, Lp, d_init_state, d_path, d_orient, d_vdes, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status, d_kgain, d_wgain, d_ogain};
+    return loop_entry(h, with_track(io, Lt, d_obst_track, obst_offset, d_clearance, 0, true), bad_lin, false, stream_);
+}
+int mpc_closed_loop_batch_lin(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                              const double* vdes, int32_t Lt, const double* obst_track, double obst_offset, int32_t noise_mode, double sigma,
+                              uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance, double* kgain, double* wgain,
+                              double* ogain) {
+    const LoopIo io{B, L, Lp, init_state, path, orient, vdes, noise_mode, sigma, seed, traj, ctrl, step_status, kgain, wgain, ogain};
+    return loop_entry(h, with_track(io, Lt, obst_track, obst_offset, clearance, 0, true), bad_lin, true, nullptr);
 }
 
 // ---- the stepping session (include/mpcgpu.h, mpc_session_*): the loop above opened at step granularity ------------------------------------------
 static const char* const NO_SESSION = "session: no session is open on this handle (mpc_session_begin)";
-static const char* bad_session_begin(const mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const void* init_state, const void* path, const void* orient,
-                                     const void* vdes, int32_t M, int32_t per_ego, const void* offsets, int32_t pairing) {
-    if (B <= 0 || L <= 0 || Lp < L || L < h->hp.desc.N || !init_state || !path || !orient || !vdes)
+// what mpc_session_begin[_dev] is given, none of which changes over the loop (offsets: read with M > 0 only)
+static LoopIo session_io(int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient, const double* vdes, int32_t M,
+                         int32_t per_ego, const double* offsets, int32_t pairing) {
+    LoopIo io{B, L, Lp, init_state, path, orient, vdes};
+    io.M = M; io.per_ego = per_ego; io.pairing = pairing; io.offsets = M > 0 ? offsets : nullptr;
+    return io;
+}
+static const char* bad_session_begin(const mpc_handle* h, const LoopIo& io) {
+    if (io.B <= 0 || io.L <= 0 || io.Lp < io.L || io.L < h->hp.desc.N || !io.init_state || !io.path || !io.orient || !io.vdes)
         return "session: B > 0, L >= N, Lp >= L and all of init_state, path, orient, vdes are required";
-    if (M < 0) return "session: M >= 0 obstacles (0: lane following)";
-    if (M > 0 && !offsets) return "session: offsets [M] (per_ego: [B, M]) are required with M > 0";
-    if (pairing != 0 && pairing != 1) return "session: pairing is 0 (the reference's pairs on the nearest obstacle) or 1 (each ego circle against its nearest circle)";
-    if (per_ego != 0 && per_ego != 1) return "session: per_ego is 0 (obstacles shared by all egos) or 1 (obstacles per ego)";
+    if (io.M < 0) return "session: M >= 0 obstacles (0: lane following)";
+    if (io.M > 0 && !io.offsets) return "session: offsets [M] (per_ego: [B, M]) are required with M > 0";
+    if (io.pairing != 0 && io.pairing != 1) return "session: pairing is 0 (the reference's pairs on the nearest obstacle) or 1 (each ego circle against its nearest circle)";
+    if (io.per_ego != 0 && io.per_ego != 1) return "session: per_ego is 0 (obstacles shared by all egos) or 1 (obstacles per ego)";
     return nullptr;
 }
 static int session_refused(mpc_handle* h, bool want_open) {
@@ -4509,23 +4556,17 @@ static int session_refused(mpc_handle* h, bool want_open) {
     return MPC_OK;
 }
 
-int mpc_session_begin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path, const double* d_orient,
-                          const double* d_vdes, int32_t M, int32_t per_ego, const double* d_offsets, int32_t pairing, void* stream_) {
+static int session_begin_dev(mpc_handle* h, const LoopIo& in, hipStream_t stream) {
     if (const int rc = session_refused(h, false)) return rc;
     if (!nlp_horizon_ok(h)) return MPC_ERR_INVALID;
-    if (const char* bad = bad_session_begin(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, M, per_ego, d_offsets, pairing)) { h->err = bad; return MPC_ERR_INVALID; }
+    if (const char* bad = bad_session_begin(h, in)) { h->err = bad; return MPC_ERR_INVALID; }
     if (!h->hp.bounds_set) { h->err = "mpc_set_bounds has not been called"; return MPC_ERR_STATE; }
     HIP_TRY(h, hipSetDevice(h->device));
-    const hipStream_t stream = (hipStream_t)stream_;
     const mpc_problem_desc& d = h->hp.desc;
-    const size_t nB = (size_t)B, nx = (size_t)d.nx, nw = h->hp.n_w(), nS = (size_t)d.N + 1, nO = M > 0 ? (per_ego ? nB : 1) * (size_t)M : 0;
-    if (M > 0) {
-        std::vector<double> off(nO);
-        HIP_TRY(h, hipMemcpyAsync(off.data(), d_offsets, nO * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(h, hipStreamSynchronize(stream));
-        for (double v : off)
-            if (!std::isfinite(v)) { h->err = "session: every offset must be finite"; return MPC_ERR_INVALID; }
-    }
+    const int32_t B = in.B, L = in.L, Lp = in.Lp, M = in.M;
+    const size_t nB = (size_t)B, nx = (size_t)d.nx, nw = h->hp.n_w(), nS = (size_t)d.N + 1, nO = M > 0 ? (in.per_ego ? nB : 1) * (size_t)M : 0;
+    if (M > 0)
+        if (const int rc = offsets_finite(h, in, stream, "session: every offset must be finite")) return rc;
     // one allocation, every piece on a 256-byte boundary
     size_t total = 0;
     const auto take = [&](size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; };
@@ -4538,19 +4579,17 @@ int mpc_session_begin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const
     char* c = static_cast<char*>(base);
     const auto dbl = [&](size_t at) { return reinterpret_cast<double*>(c + at); };
     LoopSession S;
-    S.base = base; S.M = M; S.per_ego = per_ego; S.pairing = pairing;
+    S.base = base; S.M = M; S.per_ego = in.per_ego; S.pairing = in.pairing;
     S.xout = dbl(o_xout); S.kkt = dbl(o_kkt); S.obst = M > 0 ? dbl(o_obst) : nullptr; S.offsets = M > 0 ? dbl(o_off) : nullptr;
     S.status = reinterpret_cast<int32_t*>(c + o_status); S.iters = reinterpret_cast<int32_t*>(c + o_iters);
-    LoopArgs& A = S.A;
-    A.B = B; A.N = d.N; A.L = L; A.Lp = Lp; A.nx = d.nx;
-    A.init_state = d_init_state; A.path = dbl(o_path); A.orient = dbl(o_orient); A.vdes = dbl(o_vdes);
-    A.state = dbl(o_state); A.x0 = dbl(o_x0); A.p = dbl(o_p); A.x_out = S.xout; A.status = S.status;
-    A.traj = dbl(o_traj); A.ctrl = dbl(o_ctrl); A.step_status = reinterpret_cast<int32_t*>(c + o_sst);
+    // the session's loop: the caller's init_state, its own copies of the other inputs and its own record
+    const LoopIo own{B, L, Lp, in.init_state, dbl(o_path), dbl(o_orient), dbl(o_vdes), 0, 0.0, 0, dbl(o_traj), dbl(o_ctrl), reinterpret_cast<int32_t*>(c + o_sst)};
+    LoopArgs& A = S.A = loop_args(h, own, dbl(o_state), dbl(o_x0), dbl(o_p), S.xout, S.status);
     // the caller's arrays are read here and never again: everything below has run when the call returns
-    hipError_t e = hipMemcpyAsync(dbl(o_path), d_path, nB * Lp * 2 * 8, hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbl(o_orient), d_orient, nB * Lp * 8, hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dbl(o_vdes), d_vdes, nB * 8, hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess && M > 0) e = hipMemcpyAsync(S.offsets, d_offsets, nO * 8, hipMemcpyDeviceToDevice, stream);
+    hipError_t e = hipMemcpyAsync(dbl(o_path), in.path, nB * Lp * 2 * 8, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbl(o_orient), in.orient, nB * Lp * 8, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dbl(o_vdes), in.vdes, nB * 8, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && M > 0) e = hipMemcpyAsync(S.offsets, in.offsets, nO * 8, hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess) e = hipMemsetAsync(A.traj, 0xFF, nB * L * 5 * 8, stream);              // (all bits set: NaN)
     if (e == hipSuccess) e = hipMemsetAsync(A.ctrl, 0xFF, nB * L * 2 * 8, stream);
     if (e == hipSuccess) e = hipMemsetAsync(A.step_status, 0, nB * L * 4, stream);
@@ -4572,12 +4611,13 @@ int mpc_session_begin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const
 int mpc_session_begin(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
                       const double* vdes, int32_t M, int32_t per_ego, const double* offsets, int32_t pairing) {
     if (const int rc = session_refused(h, false)) return rc;
-    if (const char* bad = bad_session_begin(h, B, L, Lp, init_state, path, orient, vdes, M, per_ego, offsets, pairing)) { h->err = bad; return MPC_ERR_INVALID; }
-    const size_t nB = (size_t)B, nO = M > 0 ? (per_ego ? nB : 1) * (size_t)M : 0;
-    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
-                          {M > 0 ? offsets : nullptr, nO * 8, false}}, [&](void** d, hipStream_t s) {
-        return mpc_session_begin_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], M, per_ego, (double*)d[4], pairing, s);
-    });
+    const LoopIo io = session_io(B, L, Lp, init_state, path, orient, vdes, M, per_ego, offsets, pairing);
+    if (const char* bad = bad_session_begin(h, io)) { h->err = bad; return MPC_ERR_INVALID; }
+    return stage_loop(h, io, NO_MORE, [&](const LoopIo& dio, void**, hipStream_t s) { return session_begin_dev(h, dio, s); });
+}
+int mpc_session_begin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path, const double* d_orient,
+                          const double* d_vdes, int32_t M, int32_t per_ego, const double* d_offsets, int32_t pairing, void* stream_) {
+    return session_begin_dev(h, session_io(B, L, Lp, d_init_state, d_path, d_orient, d_vdes, M, per_ego, d_offsets, pairing), (hipStream_t)stream_);
 }
 
 int mpc_session_step_dev(mpc_handle* h, const double* d_measured, const double* d_obs, double* d_u, double* d_plan, int32_t* d_status, double* d_clearance,
@@ -4598,12 +4638,10 @@ int mpc_session_step_dev(mpc_handle* h, const double* d_measured, const double* 
     const hipStream_t stream = (hipStream_t)stream_;
     if (d_measured) hipLaunchKernelGGL(k_session_ingest, dim3((B + 127) / 128), dim3(128), 0, stream, SessionIngestArgs{B, d.N, d.nx, d_measured, A.state, A.p});
     if (S.M > 0) {
-        SessionTrafficArgs T{};
-        T.T.B = B; T.T.L = 1; T.T.nx = d.nx; T.T.N = d.N; T.T.M = S.M; T.T.per_ego = S.per_ego; T.T.pairing = S.pairing;
-        T.T.offsets = S.offsets; T.T.ego_offset = d.ego_offset; T.T.obst = S.obst; T.T.state = A.state; T.T.x0 = A.x0;
-        T.T.clearance = d_clearance; T.T.nearest = d_nearest; T.T.chosen = d_chosen; T.T.r_sum = h->hp.ol_raw;
-        for (int q = 0; q < 6; ++q) T.T.desc_obst[q] = d.obstacle[q];
-        T.obs = d_obs; T.dt = d.dt; T.step = i;
+        LoopIo one;                     // this step as a loop of one step through the observed traffic (no tracks)
+        one.B = B; one.L = 1; one.M = S.M; one.per_ego = S.per_ego; one.pairing = S.pairing; one.offsets = S.offsets;
+        one.clearance = d_clearance; one.nearest = d_nearest; one.chosen = d_chosen;
+        const SessionTrafficArgs T{loop_traffic_args(h, one, S.obst, A), d_obs, d.dt, i};
         hipLaunchKernelGGL(k_session_traffic, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, T);
     }
     if (const int rc = solve_dev(h, io, stream)) return rc;
@@ -4653,42 +4691,6 @@ int mpc_session_end(mpc_handle* h) {
     HIP_TRY(h, hipFree(h->session.base));               // (waits for whatever still runs on the session's rows)
     h->session = LoopSession{};
     return MPC_OK;
-}
-
-// the loop with per-step gains: Lt = 0 with a null track is the plain loop (ogain must then be null); no gain asked for: the loop it wraps
-int mpc_closed_loop_batch_lin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
-                                  const double* d_orient, const double* d_vdes, int32_t Lt, const double* d_obst_track, double obst_offset,
-                                  int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status,
-                                  double* d_clearance, double* d_kgain, double* d_wgain, double* d_ogain, void* stream_) {
-    if (!h) return MPC_ERR_INVALID;
-    if (h->hp.desc.fixed_iters > 0) { h->err = "closed loop with gains: the sensitivities need solves to convergence (fixed_iters = 0)"; return MPC_ERR_INVALID; }
-    const bool has_track = Lt != 0 || d_obst_track != nullptr;
-    if (!has_track && d_ogain) { h->err = "closed loop with gains: ogain needs obst_track"; return MPC_ERR_INVALID; }
-    if (!has_track && d_clearance) { h->err = "closed loop with gains: clearance needs obst_track"; return MPC_ERR_INVALID; }
-    const LoopTrack track{Lt, d_obst_track, obst_offset, d_clearance};
-    const LoopLin lin{d_kgain, d_wgain, d_ogain};
-    return closed_loop_dev(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, has_track ? &track : nullptr, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status,
-                           stream_, (d_kgain || d_wgain || d_ogain) ? &lin : nullptr);
-}
-
-int mpc_closed_loop_batch_lin(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
-                              const double* vdes, int32_t Lt, const double* obst_track, double obst_offset, int32_t noise_mode, double sigma,
-                              uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance, double* kgain, double* wgain,
-                              double* ogain) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
-    if ((Lt != 0 || obst_track) && (!obst_track || (Lt != 1 && Lt < L))) {
-        h->err = "closed loop: obst_track [B, Lt, 3] needs Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i); Lt = 0 with a null track: no obstacle tracks";
-        return MPC_ERR_INVALID;
-    }
-    const size_t nB = (size_t)B, nL = nB * (size_t)L;
-    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
-                          {obst_track, nB * (size_t)Lt * 3 * 8, false}, {traj, nL * 5 * 8, true}, {ctrl, nL * 2 * 8, true}, {step_status, nL * 4, true},
-                          {clearance, nL * 8, true}, {kgain, nL * 2 * LOOP_NS * 8, true}, {wgain, nL * 2 * SENS_NWT * 8, true}, {ogain, nL * 2 * LOOP_NPOSE * 8, true}},
-                      [&](void** d, hipStream_t s) {
-        return mpc_closed_loop_batch_lin_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], Lt, (double*)d[4], obst_offset, noise_mode,
-                                             sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], (double*)d[8], (double*)d[9], (double*)d[10], (double*)d[11], s);
-    });
 }
 
 // The sweeps over a recorded loop: stateless -- they read their arguments and the handle's dt and wheelbase, and may follow any call.
@@ -4758,31 +4760,6 @@ int mpc_loop_adjoint(mpc_handle* h, int32_t B, int32_t L, const double* traj, co
                                     (double*)d[7], (double*)d[8], s);
     });
 }
-
-int mpc_closed_loop_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
-                              const double* d_orient, const double* d_vdes, double* d_traj, double* d_ctrl, int32_t* d_step_status,
-                              void* stream_) {
-    return mpc_closed_loop_batch_dev_ex(h, B, L, Lp, d_init_state, d_path, d_orient, d_vdes, 0, 0.0, 0, d_traj, d_ctrl, d_step_status, stream_);
-}
-
-int mpc_closed_loop_batch_ex(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
-                             const double* orient, const double* vdes, int32_t noise_mode, double sigma, uint64_t seed, double* traj,
-                             double* ctrl, int32_t* step_status) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "closed loop: null or empty argument"; return MPC_ERR_INVALID; }
-    const size_t nB = (size_t)B;
-    return stage_host(h, {{init_state, nB * 5 * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false}, {vdes, nB * 8, false},
-                          {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true}, {step_status, nB * L * 4, true}}, [&](void** d, hipStream_t s) {
-        return mpc_closed_loop_batch_dev_ex(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], noise_mode, sigma, seed, (double*)d[4],
-                                            (double*)d[5], (int32_t*)d[6], s);
-    });
-}
-
-int mpc_closed_loop_batch(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
-                          const double* orient, const double* vdes, double* traj, double* ctrl, int32_t* step_status) {
-    return mpc_closed_loop_batch_ex(h, B, L, Lp, init_state, path, orient, vdes, 0, 0.0, 0, traj, ctrl, step_status);
-}
-int mpc_last_loop_replayed(const mpc_handle* h) { return h ? h->loop_replayed : MPC_ERR_INVALID; }
 
 int mpc_metrics_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lo, const double* d_traj, const double* d_ref_path, const double* d_origin_path,
                           double r_sum, int32_t all_pairs, double* d_deviation, double* d_rmsd, double* d_clearance, void* stream_) {
@@ -4873,9 +4850,7 @@ int mpc_forces_stage_eval(mpc_handle* h, int32_t B, int32_t terminal, const doub
                           {terminal ? nullptr : jac_c, nB * 35 * 8, true}, {hval, nB * 10 * 8, true}, {jac_h, nB * 70 * 8, true}}, [&](void** dv, hipStream_t s) {
         ForcesArgs A{};
         A.B = B; A.terminal = terminal ? 1 : 0;
-        A.dt = d.dt; A.l = d.wheelbase; A.wb = d.friction_div; A.rho = d.ego_offset;
-        for (int i = 0; i < 5; ++i) { A.Q[i] = d.Q[i]; A.Pt[i] = d.P[i]; }
-        A.R[0] = d.R[0]; A.R[1] = d.R[1];
+        forces_model(d, A);
         A.z = (double*)dv[0]; A.p = (double*)dv[1]; A.f = (double*)dv[2]; A.grad_f = (double*)dv[3]; A.c = (double*)dv[4]; A.jac_c = (double*)dv[5];
         A.h = (double*)dv[6]; A.jac_h = (double*)dv[7];
         hipLaunchKernelGGL(k_forces_stage, dim3((B + 127) / 128), dim3(128), 0, s, A);
@@ -4905,10 +4880,8 @@ int mpc_forces_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, con
     if (!dws || !dflag || !dit || !dres) { h->err = "forces solve: out of device memory"; return MPC_ERR_HIP; }
     ForcesQpArgs A{};
     A.B = B; A.Bp = (int32_t)Bp; A.N = N; A.max_it = 60;
-    A.dt = d.dt; A.l = d.wheelbase; A.wb = d.friction_div; A.rho = d.ego_offset;
+    forces_model(d, A);
     A.tol = 1e-4; A.tol_mu = 1e-6;
-    for (int i = 0; i < 5; ++i) { A.Q[i] = d.Q[i]; A.Pt[i] = d.P[i]; }
-    A.R[0] = d.R[0]; A.R[1] = d.R[1];
     forces_hessian_diag(hessian_mode, A.Q, A.R, A.Pt, A.hd, A.hdN);
     for (int i = 0; i < 7; ++i) { A.lb[i] = lb[i]; A.ub[i] = ub[i]; }
     for (int i = 0; i < 10; ++i) { A.hl[i] = hl[i]; A.hu[i] = hu[i]; }
@@ -4942,138 +4915,134 @@ int mpc_forces_solve_batch(mpc_handle* h, int32_t B, const double* x0, const dou
     });
 }
 
-int mpc_forces_closed_loop_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_init_acc,
-                                     const double* d_path, const double* d_orient, const double* d_vdes, const double* lb, const double* ub,
-                                     const double* hl, const double* hu, int32_t hessian_mode, int32_t noise_mode, double sigma, uint64_t seed,
-                                     double* d_traj, double* d_ctrl, int32_t* d_step_flag, void* stream_) {
+// ---- the FORCES-mode loops: the arrays travel as a LoopIo (the obstacle loop: its single-track group), what only these loops take as a ForcesIn ----
+struct ForcesIn {
+    const double *init_acc, *lb, *ub, *hl, *hu;         // init_acc [B]: on the device or the host as the arrays of the LoopIo beside it
+    int32_t hessian_mode, guess_mode = 0;               // guess_mode, r_sum: the obstacle loop only (ForcesTurnArgs)
+    double r_sum = 0.0;
+};
+using ForcesCheck = const char* (*)(const mpc_handle*, const LoopIo&, const ForcesIn&);
+// An entry point of these loops, in either form: what both loops refuse, then `own` (null: the entry point has no objection of its own); host: the
+// arrays of `io` and init_acc staged; `dev` on the device arrays
+static int forces_entry(mpc_handle* h, const LoopIo& io, const ForcesIn& in, ForcesCheck own, bool host, void* stream,
+                        int (*dev)(mpc_handle*, const LoopIo&, const ForcesIn&, hipStream_t)) {
     if (!h) return MPC_ERR_INVALID;
-    const mpc_problem_desc& d = h->hp.desc;
-    if (B <= 0 || L <= 0 || Lp <= 0 || L < d.N || !d_init_state || !d_path || !d_orient || !d_vdes || !d_traj || !d_ctrl || !lb || !ub || !hl || !hu) {
-        h->err = "forces closed loop: B, L, Lp > 0, L >= N and init_state, path, orient, vdes, traj, ctrl, lb, ub, hl, hu are required";
-        return MPC_ERR_INVALID;
-    }
-    if (!(noise_mode == 0 || noise_mode == 2) || (noise_mode && !(sigma >= 0.0))) { h->err = "forces closed loop: noise_mode 0 or 2, sigma >= 0"; return MPC_ERR_INVALID; }
-    if (d.nx != 5) { h->err = "the FORCES formulation has 5 states"; return MPC_ERR_INVALID; }
+    const char* bad = nullptr;
+    if (io.B <= 0 || io.L <= 0 || io.Lp <= 0 || io.L < h->hp.desc.N || !io.init_state || !io.path || !io.orient || !io.vdes || !io.traj || !io.ctrl || !in.lb || !in.ub ||
+        !in.hl || !in.hu)
+        bad = "forces closed loop: B, L, Lp > 0, L >= N and init_state, path, orient, vdes, traj, ctrl, lb, ub, hl, hu are required";
+    else if (!(io.noise_mode == 0 || io.noise_mode == 2) || (io.noise_mode && !(io.sigma >= 0.0))) bad = "forces closed loop: noise_mode 0 or 2, sigma >= 0";
+    else if (h->hp.desc.nx != 5) bad = "the FORCES formulation has 5 states";
+    else if (own) bad = own(h, io, in);
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    if (!host) return dev(h, io, in, (hipStream_t)stream);
+    return stage_loop(h, io, {{in.init_acc, (size_t)io.B * sizeof(double), false}}, [&](const LoopIo& dio, void** m, hipStream_t s) {
+        ForcesIn din = in;
+        din.init_acc = static_cast<const double*>(m[0]);
+        return dev(h, dio, din, s);
+    });
+}
+// What the two loops share in front of their launches: the rows of the loop's solves in the scratch slots first .. first + 4 (state, zbar, params,
+// z_out, exitflag: SCR_FL_* or SCR_FT_*) and the arguments of the loop's kernels
+static int forces_loop_begin(mpc_handle* h, const LoopIo& io, const ForcesIn& in, Scratch first, ForcesLoopArgs& A) {
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t nB = (size_t)B, N = (size_t)d.N;
-    double* st = static_cast<double*>(scratch_get(h, SCR_FL_STATE, nB * 5 * 8));
-    double* zb = static_cast<double*>(scratch_get(h, SCR_FL_ZBAR, nB * N * 7 * 8));
-    double* par = static_cast<double*>(scratch_get(h, SCR_FL_PARAMS, nB * N * 10 * 8));
-    double* zo = static_cast<double*>(scratch_get(h, SCR_FL_ZOUT, nB * N * 7 * 8));
-    int32_t* fl = static_cast<int32_t*>(scratch_get(h, SCR_FL_FLAG, nB * 4));
-    if (!st || !zb || !par || !zo || !fl) { h->err = "forces closed loop: out of device memory"; return MPC_ERR_HIP; }
-    hipStream_t s = (hipStream_t)stream_;
-    ForcesLoopArgs A{};
-    A.B = B; A.N = d.N; A.L = L; A.Lp = Lp;
-    A.init_state = d_init_state; A.init_acc = d_init_acc; A.path = d_path; A.orient = d_orient; A.vdes = d_vdes;
+    const mpc_problem_desc& d = h->hp.desc;
+    const size_t nB = (size_t)io.B, N = (size_t)d.N;
+    const auto row = [&](int k, size_t bytes) { return scratch_get(h, (Scratch)(first + k), bytes); };
+    A = ForcesLoopArgs{};
+    A.state = static_cast<double*>(row(0, nB * 5 * 8));
+    A.zbar = static_cast<double*>(row(1, nB * N * 7 * 8));
+    A.params = static_cast<double*>(row(2, nB * N * 10 * 8));
+    A.z_out = static_cast<double*>(row(3, nB * N * 7 * 8));
+    A.exitflag = static_cast<int32_t*>(row(4, nB * 4));
+    if (!A.state || !A.zbar || !A.params || !A.z_out || !A.exitflag) { h->err = "forces closed loop: out of device memory"; return MPC_ERR_HIP; }
+    A.B = io.B; A.N = d.N; A.L = io.L; A.Lp = io.Lp;
+    A.init_state = io.init_state; A.init_acc = in.init_acc; A.path = io.path; A.orient = io.orient; A.vdes = io.vdes;
     for (int i = 0; i < 6; ++i) A.obstacle[i] = d.obstacle[i];
-    A.state = st; A.zbar = zb; A.params = par; A.z_out = zo; A.exitflag = fl;
-    A.traj = d_traj; A.ctrl = d_ctrl; A.step_flag = d_step_flag;
+    A.traj = io.traj; A.ctrl = io.ctrl; A.step_flag = io.step_status;
     A.dt = d.dt; A.wheelbase = d.wheelbase;
-    A.noise_mode = noise_mode; A.sigma = sigma; A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32);
-    const dim3 grid((B + 127) / 128), block(128);
+    A.noise_mode = io.noise_mode; A.sigma = io.sigma; A.seed_lo = (uint32_t)io.seed; A.seed_hi = (uint32_t)(io.seed >> 32);
+    return MPC_OK;
+}
+// the solve of one step of either loop on the rows of A (which its kernels read: hence const there)
+static int forces_loop_solve(mpc_handle* h, const ForcesLoopArgs& A, const ForcesIn& in, hipStream_t s) {
+    return mpc_forces_solve_batch_dev(h, A.B, A.zbar, A.state, A.params, in.lb, in.ub, in.hl, in.hu, in.hessian_mode, const_cast<double*>(A.z_out),
+                                      const_cast<int32_t*>(A.exitflag), nullptr, nullptr, (void*)s);
+}
+
+static int forces_loop_dev(mpc_handle* h, const LoopIo& io, const ForcesIn& in, hipStream_t s) {
+    ForcesLoopArgs A;
+    if (const int rc = forces_loop_begin(h, io, in, SCR_FL_STATE, A)) return rc;
+    const dim3 grid((io.B + 127) / 128), block(128);
     hipLaunchKernelGGL(k_floop_setup, grid, block, 0, s, A);
-    for (int k = 0; k < L; ++k) {                       // nothing comes back to the host between the steps
+    for (int k = 0; k < io.L; ++k) {                    // nothing comes back to the host between the steps
         hipLaunchKernelGGL(k_floop_params, grid, block, 0, s, A, k);
-        const int rc = mpc_forces_solve_batch_dev(h, B, zb, st, par, lb, ub, hl, hu, hessian_mode, zo, fl, nullptr, nullptr, (void*)s);
-        if (rc) return rc;
+        if (const int rc = forces_loop_solve(h, A, in, s)) return rc;
         hipLaunchKernelGGL(k_floop_advance, grid, block, 0, s, A, k);
     }
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
-
+int mpc_forces_closed_loop_batch_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_init_acc,
+                                     const double* d_path, const double* d_orient, const double* d_vdes, const double* lb, const double* ub,
+                                     const double* hl, const double* hu, int32_t hessian_mode, int32_t noise_mode, double sigma, uint64_t seed,
+                                     double* d_traj, double* d_ctrl, int32_t* d_step_flag, void* stream_) {
+    return forces_entry(h, LoopIo{B, L, Lp, d_init_state, d_path, d_orient, d_vdes, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_flag},
+                        ForcesIn{d_init_acc, lb, ub, hl, hu, hessian_mode}, nullptr, false, stream_, forces_loop_dev);
+}
 int mpc_forces_closed_loop_batch(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* init_acc, const double* path,
                                  const double* orient, const double* vdes, const double* lb, const double* ub, const double* hl, const double* hu,
                                  int32_t hessian_mode, int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_flag) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "forces closed loop: null or empty argument"; return MPC_ERR_INVALID; }
-    const size_t nB = (size_t)B;
-    return stage_host(h, {{init_state, nB * 5 * 8, false}, {init_acc, nB * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false},
-                          {vdes, nB * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true}, {step_flag, nB * L * 4, true}}, [&](void** d, hipStream_t s) {
-        return mpc_forces_closed_loop_batch_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], lb, ub, hl, hu,
-                                                hessian_mode, noise_mode, sigma, seed, (double*)d[5], (double*)d[6], (int32_t*)d[7], s);
-    });
+    return forces_entry(h, LoopIo{B, L, Lp, init_state, path, orient, vdes, noise_mode, sigma, seed, traj, ctrl, step_flag},
+                        ForcesIn{init_acc, lb, ub, hl, hu, hessian_mode}, nullptr, true, nullptr, forces_loop_dev);
 }
 
-// what both forms of mpc_forces_closed_loop_batch_obst refuse about the guess and the track (null: nothing)
-static const char* forces_loop_obst_refusal(int32_t L, int32_t guess_mode, int32_t Lt, const double* track, double obst_offset, int32_t predict,
-                                            double r_sum, const double* clearance) {
-    if (!(guess_mode == 0 || guess_mode == 1) || !(predict == 0 || predict == 1)) return "forces closed loop: guess_mode 0 or 1, predict 0 or 1";
-    if (Lt == 0 && !track) {
-        if (predict) return "forces closed loop: predict needs obst_track (Lt = 0 with a null track: the descriptor's obstacle in every stage)";
-        if (clearance) return "forces closed loop: clearance needs obst_track (Lt = 0 with a null track: the descriptor's obstacle in every stage)";
-        return nullptr;
+// the loop past per-ego obstacles that move: what both of its forms refuse about the guess and the track (null: nothing)
+static const char* bad_forces_turn(const mpc_handle* h, const LoopIo& io, const ForcesIn& in) {
+    if (!(in.guess_mode == 0 || in.guess_mode == 1) || !(io.predict == 0 || io.predict == 1)) return "forces closed loop: guess_mode 0 or 1, predict 0 or 1";
+    if (!io.tracked) {
+        if (io.predict) return "forces closed loop: predict needs obst_track (Lt = 0 with a null track: the descriptor's obstacle in every stage)";
+        if (io.clearance) return "forces closed loop: clearance needs obst_track (Lt = 0 with a null track: the descriptor's obstacle in every stage)";
+    } else {
+        if (!io.track || (io.Lt != 1 && io.Lt < io.L) || !std::isfinite(io.offset))
+            return "forces closed loop: obst_track [B, Lt, 3] needs Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i) and a finite "
+                   "obst_offset; Lt = 0 with a null track: no obstacle tracks";
+        if (io.clearance && !std::isfinite(in.r_sum)) return "forces closed loop: clearance needs a finite r_sum";
     }
-    if (!track || (Lt != 1 && Lt < L) || !std::isfinite(obst_offset))
-        return "forces closed loop: obst_track [B, Lt, 3] needs Lt = 1 (the obstacle stands still) or Lt >= L (row i: the obstacle at step i) and a finite "
-               "obst_offset; Lt = 0 with a null track: no obstacle tracks";
-    if (clearance && !std::isfinite(r_sum)) return "forces closed loop: clearance needs a finite r_sum";
+    if ((size_t)io.B * (size_t)h->hp.desc.N >= ((size_t)1 << 27)) return "forces closed loop: batch too large for one call";       // (one thread per stage row, int indices)
     return nullptr;
 }
-
-int mpc_forces_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_init_acc,
-                                          const double* d_path, const double* d_orient, const double* d_vdes, const double* lb, const double* ub,
-                                          const double* hl, const double* hu, int32_t hessian_mode, int32_t guess_mode, int32_t Lt,
-                                          const double* d_obst_track, double obst_offset, int32_t predict, double r_sum, int32_t noise_mode, double sigma,
-                                          uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_flag, double* d_clearance, void* stream_) {
-    if (!h) return MPC_ERR_INVALID;
-    const mpc_problem_desc& d = h->hp.desc;
-    if (B <= 0 || L <= 0 || Lp <= 0 || L < d.N || !d_init_state || !d_path || !d_orient || !d_vdes || !d_traj || !d_ctrl || !lb || !ub || !hl || !hu) {
-        h->err = "forces closed loop: B, L, Lp > 0, L >= N and init_state, path, orient, vdes, traj, ctrl, lb, ub, hl, hu are required";
-        return MPC_ERR_INVALID;
-    }
-    if (!(noise_mode == 0 || noise_mode == 2) || (noise_mode && !(sigma >= 0.0))) { h->err = "forces closed loop: noise_mode 0 or 2, sigma >= 0"; return MPC_ERR_INVALID; }
-    if (d.nx != 5) { h->err = "the FORCES formulation has 5 states"; return MPC_ERR_INVALID; }
-    if (const char* why = forces_loop_obst_refusal(L, guess_mode, Lt, d_obst_track, obst_offset, predict, r_sum, d_clearance)) { h->err = why; return MPC_ERR_INVALID; }
-    const size_t nB = (size_t)B, N = (size_t)d.N;
-    if (nB * N >= ((size_t)1 << 27)) { h->err = "forces closed loop: batch too large for one call"; return MPC_ERR_INVALID; }      // (one thread per stage row, int indices)
-    HIP_TRY(h, hipSetDevice(h->device));
-    double* st = static_cast<double*>(scratch_get(h, SCR_FT_STATE, nB * 5 * 8));
-    double* zb = static_cast<double*>(scratch_get(h, SCR_FT_ZBAR, nB * N * 7 * 8));
-    double* par = static_cast<double*>(scratch_get(h, SCR_FT_PARAMS, nB * N * 10 * 8));
-    double* zo = static_cast<double*>(scratch_get(h, SCR_FT_ZOUT, nB * N * 7 * 8));
-    int32_t* fl = static_cast<int32_t*>(scratch_get(h, SCR_FT_FLAG, nB * 4));
-    if (!st || !zb || !par || !zo || !fl) { h->err = "forces closed loop: out of device memory"; return MPC_ERR_HIP; }
-    hipStream_t s = (hipStream_t)stream_;
+static int forces_turn_dev(mpc_handle* h, const LoopIo& io, const ForcesIn& in, hipStream_t s) {
     ForcesTurnArgs A{};
-    ForcesLoopArgs& F = A.F;
-    F.B = B; F.N = d.N; F.L = L; F.Lp = Lp;
-    F.init_state = d_init_state; F.init_acc = d_init_acc; F.path = d_path; F.orient = d_orient; F.vdes = d_vdes;
-    for (int i = 0; i < 6; ++i) F.obstacle[i] = d.obstacle[i];
-    F.state = st; F.zbar = zb; F.params = par; F.z_out = zo; F.exitflag = fl;
-    F.traj = d_traj; F.ctrl = d_ctrl; F.step_flag = d_step_flag;
-    F.dt = d.dt; F.wheelbase = d.wheelbase;
-    F.noise_mode = noise_mode; F.sigma = sigma; F.seed_lo = (uint32_t)seed; F.seed_hi = (uint32_t)(seed >> 32);
-    A.guess_mode = guess_mode; A.Lt = Lt; A.predict = predict; A.track = d_obst_track; A.offset = obst_offset;
-    A.clearance = d_clearance; A.r_sum = r_sum; A.ego_offset = d.ego_offset;
-    const dim3 block(256), grid((unsigned)((nB * N + 255) / 256));
+    if (const int rc = forces_loop_begin(h, io, in, SCR_FT_STATE, A.F)) return rc;
+    A.guess_mode = in.guess_mode; A.Lt = io.Lt; A.predict = io.predict; A.track = io.track; A.offset = io.offset;
+    A.clearance = io.clearance; A.r_sum = in.r_sum; A.ego_offset = h->hp.desc.ego_offset;
+    const dim3 block(256), grid((unsigned)(((size_t)io.B * (size_t)h->hp.desc.N + 255) / 256));
     hipLaunchKernelGGL(k_floop_turn_setup, grid, block, 0, s, A);
-    for (int k = 0; k < L; ++k) {                       // nothing comes back to the host between the steps
-        const int rc = mpc_forces_solve_batch_dev(h, B, zb, st, par, lb, ub, hl, hu, hessian_mode, zo, fl, nullptr, nullptr, (void*)s);
-        if (rc) return rc;
+    for (int k = 0; k < io.L; ++k) {                    // nothing comes back to the host between the steps
+        if (const int rc = forces_loop_solve(h, A.F, in, s)) return rc;
         hipLaunchKernelGGL(k_floop_turn, grid, block, 0, s, A, k);
     }
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
-
+int mpc_forces_closed_loop_batch_obst_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_init_acc,
+                                          const double* d_path, const double* d_orient, const double* d_vdes, const double* lb, const double* ub,
+                                          const double* hl, const double* hu, int32_t hessian_mode, int32_t guess_mode, int32_t Lt,
+                                          const double* d_obst_track, double obst_offset, int32_t predict, double r_sum, int32_t noise_mode, double sigma,
+                                          uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_flag, double* d_clearance, void* stream_) {
+    const LoopIo io{B, L, Lp, d_init_state, d_path, d_orient, d_vdes, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_flag};
+    return forces_entry(h, with_track(io, Lt, d_obst_track, obst_offset, d_clearance, predict, true), ForcesIn{d_init_acc, lb, ub, hl, hu, hessian_mode, guess_mode, r_sum},
+                        bad_forces_turn, false, stream_, forces_turn_dev);
+}
 int mpc_forces_closed_loop_batch_obst(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* init_acc, const double* path,
                                       const double* orient, const double* vdes, const double* lb, const double* ub, const double* hl, const double* hu,
                                       int32_t hessian_mode, int32_t guess_mode, int32_t Lt, const double* obst_track, double obst_offset, int32_t predict,
                                       double r_sum, int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl, int32_t* step_flag,
                                       double* clearance) {
-    if (!h) return MPC_ERR_INVALID;
-    if (B <= 0 || L <= 0 || Lp <= 0 || !init_state || !path || !orient || !vdes || !traj || !ctrl) { h->err = "forces closed loop: null or empty argument"; return MPC_ERR_INVALID; }
-    if (const char* why = forces_loop_obst_refusal(L, guess_mode, Lt, obst_track, obst_offset, predict, r_sum, clearance)) { h->err = why; return MPC_ERR_INVALID; }
-    const size_t nB = (size_t)B;
-    return stage_host(h, {{init_state, nB * 5 * 8, false}, {init_acc, nB * 8, false}, {path, nB * Lp * 2 * 8, false}, {orient, nB * Lp * 8, false},
-                          {vdes, nB * 8, false}, {obst_track, nB * (size_t)Lt * 3 * 8, false}, {traj, nB * L * 5 * 8, true}, {ctrl, nB * L * 2 * 8, true},
-                          {step_flag, nB * L * 4, true}, {clearance, nB * L * 8, true}}, [&](void** d, hipStream_t s) {
-        return mpc_forces_closed_loop_batch_obst_dev(h, B, L, Lp, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (double*)d[4], lb, ub, hl, hu,
-                                                     hessian_mode, guess_mode, Lt, (double*)d[5], obst_offset, predict, r_sum, noise_mode, sigma, seed,
-                                                     (double*)d[6], (double*)d[7], (int32_t*)d[8], (double*)d[9], s);
-    });
+    const LoopIo io{B, L, Lp, init_state, path, orient, vdes, noise_mode, sigma, seed, traj, ctrl, step_flag};
+    return forces_entry(h, with_track(io, Lt, obst_track, obst_offset, clearance, predict, true), ForcesIn{init_acc, lb, ub, hl, hu, hessian_mode, guess_mode, r_sum},
+                        bad_forces_turn, true, nullptr, forces_turn_dev);
 }
 
 }  // extern "C"

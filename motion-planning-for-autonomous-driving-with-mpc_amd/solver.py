@@ -28,6 +28,20 @@ def _big(a, n):
     return _abi.f64(np.where(np.isfinite(a), a, np.sign(a) * 1e308))
 
 
+def _loop_in(init_state, path, orient, vdes):
+    """what every closed loop starts from, as contiguous arrays: init_state [B,5] (or [5]: one ego), path [B,Lp,2], orient [B,Lp], vdes [B] (or a
+    scalar) -> (init_state, path, orient, vdes, B, Lp)"""
+    init_state = _abi.f64(init_state)
+    if init_state.ndim == 1:
+        init_state = init_state[None]
+    B = init_state.shape[0]
+    path = _abi.f64(path).reshape(B, -1, 2)
+    Lp = path.shape[1]
+    orient = _abi.f64(orient).reshape(B, Lp)
+    vdes = _abi.f64(np.broadcast_to(np.asarray(vdes, dtype=np.float64), (B,)))
+    return init_state, path, orient, vdes, B, Lp
+
+
 def _vp(d_ptr):
     """a device pointer or stream handle given as an int (0: absent)"""
     return C.c_void_p(d_ptr or None)
@@ -528,14 +542,7 @@ class BatchedMPCSolver:
         min(i + k, Lt - 1) (mpc_closed_loop_batch_pred); not with linearize.
         linearize=True: a LoopLin instead -- the same rollout, step by step, with the gains kgain, wgain and (with a track) ogain of every step
         (mpc_closed_loop_batch_lin), what loop_tangent / loop_adjoint sweep over."""
-        init_state = _abi.f64(init_state)
-        if init_state.ndim == 1:
-            init_state = init_state[None]
-        B = init_state.shape[0]
-        path = _abi.f64(path).reshape(B, -1, 2)
-        Lp = path.shape[1]
-        orient = _abi.f64(orient).reshape(B, Lp)
-        vdes = _abi.f64(np.broadcast_to(np.asarray(vdes, dtype=np.float64), (B,)))
+        init_state, path, orient, vdes, B, Lp = _loop_in(init_state, path, orient, vdes)
         steps = int(steps)
         traj = np.empty((B, steps, 5))
         ctrl = np.empty((B, steps, 2))
@@ -599,14 +606,7 @@ class BatchedMPCSolver:
         against its nearest obstacle circle.  A handle has one radius: the lower bound of its circle rows holds for every obstacle.
         -> (traj [B,steps,5], ctrl [B,steps,2], step_status [B,steps], clearance [B,steps] over all nine pairs of every present obstacle (+inf: none),
         nearest [B,steps] (the obstacle that attains it, -1: none), chosen [B,steps,N+1,3] (the obstacle behind every slot of every stage))"""
-        init_state = _abi.f64(init_state)
-        if init_state.ndim == 1:
-            init_state = init_state[None]
-        B = init_state.shape[0]
-        path = _abi.f64(path).reshape(B, -1, 2)
-        Lp = path.shape[1]
-        orient = _abi.f64(orient).reshape(B, Lp)
-        vdes = _abi.f64(np.broadcast_to(np.asarray(vdes, dtype=np.float64), (B,)))
+        init_state, path, orient, vdes, B, Lp = _loop_in(init_state, path, orient, vdes)
         steps = int(steps)
         tracks, offsets = _abi.f64(tracks), _abi.f64(offsets)
         if tracks.ndim not in (3, 4) or tracks.shape[-1] != 3 or (tracks.ndim == 4 and tracks.shape[0] != B) or offsets.shape != tracks.shape[:-2]:
@@ -806,14 +806,7 @@ class BatchedMPCSolver:
         """B egos through `steps` steps of ForcesproOptimizer.optimize (optimizer.py:246-366) on the device
         (mpc_forces_closed_loop_batch): init_state [B,5], path [B,Lp,2], orient [B,Lp], vdes [B] -> (traj [B,steps,5],
         ctrl [B,steps,2], exitflag [B,steps])."""
-        init_state = _abi.f64(init_state)
-        if init_state.ndim == 1:
-            init_state = init_state[None]
-        B = init_state.shape[0]
-        path = _abi.f64(path).reshape(B, -1, 2)
-        Lp = path.shape[1]
-        orient = _abi.f64(orient).reshape(B, Lp)
-        vdes = _abi.f64(np.broadcast_to(np.asarray(vdes, dtype=np.float64), (B,)))
+        init_state, path, orient, vdes, B, Lp = _loop_in(init_state, path, orient, vdes)
         acc = None if init_acc is None else _abi.f64(np.broadcast_to(np.asarray(init_acc, dtype=np.float64), (B,)))
         steps = int(steps)
         traj, ctrl, fl = np.empty((B, steps, 5)), np.empty((B, steps, 2)), np.empty((B, steps), np.int32)
@@ -832,14 +825,7 @@ class BatchedMPCSolver:
         (None: sqrt(hl[1]), the bound of the squared circle distances).  clearance: None = with a track.
         -> (traj [B,steps,5], ctrl [B,steps,2], exitflag [B,steps], clearance [B,steps] | None): clearance[b, i] = min over the nine circle pairs of
         distance - r_sum of traj[b, i] against the pose at step i."""
-        init_state = _abi.f64(init_state)
-        if init_state.ndim == 1:
-            init_state = init_state[None]
-        B = init_state.shape[0]
-        path = _abi.f64(path).reshape(B, -1, 2)
-        Lp = path.shape[1]
-        orient = _abi.f64(orient).reshape(B, Lp)
-        vdes = _abi.f64(np.broadcast_to(np.asarray(vdes, dtype=np.float64), (B,)))
+        init_state, path, orient, vdes, B, Lp = _loop_in(init_state, path, orient, vdes)
         acc = None if init_acc is None else _abi.f64(np.broadcast_to(np.asarray(init_acc, dtype=np.float64), (B,)))
         steps = int(steps)
         Lt = 0
@@ -936,14 +922,7 @@ class LoopSession:
 
     def __init__(self, solver, init_state, path, orient, vdes, steps, offsets=None, per_ego=None, pairing=0):
         self._s = solver
-        init_state = _abi.f64(init_state)
-        if init_state.ndim == 1:
-            init_state = init_state[None]
-        B = init_state.shape[0]
-        path = _abi.f64(path).reshape(B, -1, 2)
-        Lp = path.shape[1]
-        orient = _abi.f64(orient).reshape(B, Lp)
-        vdes = _abi.f64(np.broadcast_to(np.asarray(vdes, dtype=np.float64), (B,)))
+        init_state, path, orient, vdes, B, Lp = _loop_in(init_state, path, orient, vdes)
         self.B, self.steps, self.M, self.per_ego = B, int(steps), 0, 0
         if offsets is not None:
             offsets = _abi.f64(offsets)

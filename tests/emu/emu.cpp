@@ -184,3 +184,37 @@ extern "C" int emu_solve_io_rows(int32_t N, int32_t nx, int64_t snap_len, int32_
     out[8] = r.lam_g ? r.lam_g - io.lam_g : -1; out[9] = r.lam_x ? r.lam_x - io.lam_x : -1; out[10] = r.snap ? r.snap - io.snap : -1;
     return 0;
 }
+
+// A LoopIo (mpc_solve_plan.h) from the harness: dims = [B, L, Lp, Lt, M, per_ego, noise_mode, tracked]; the fifteen array members in the order
+// init_state, path, orient, vdes, track, offsets, traj, ctrl, step_status, clearance, nearest, chosen, kgain, wgain, ogain point `at[i]` bytes into
+// `base` (negative: null).  Nothing is dereferenced.
+static LoopIo emu_loop_io(const int32_t* dims, double sigma, double offset, char* base, const int64_t* at) {
+    const auto ptr = [&](int i) { return at[i] < 0 ? nullptr : base + at[i]; };
+    LoopIo io;
+    io.B = dims[0]; io.L = dims[1]; io.Lp = dims[2]; io.Lt = dims[3]; io.M = dims[4]; io.per_ego = dims[5]; io.noise_mode = dims[6]; io.tracked = dims[7] != 0;
+    io.sigma = sigma; io.offset = offset;
+    io.init_state = (const double*)ptr(0); io.path = (const double*)ptr(1); io.orient = (const double*)ptr(2); io.vdes = (const double*)ptr(3);
+    io.track = (const double*)ptr(4); io.offsets = (const double*)ptr(5); io.traj = (double*)ptr(6); io.ctrl = (double*)ptr(7);
+    io.step_status = (int32_t*)ptr(8); io.clearance = (double*)ptr(9); io.nearest = (int32_t*)ptr(10); io.chosen = (int32_t*)ptr(11);
+    io.kgain = (double*)ptr(12); io.wgain = (double*)ptr(13); io.ogain = (double*)ptr(14);
+    return io;
+}
+// LoopIo::each_array under a horizon of N stages, in the order it visits the arrays: where[i] = the offset in `base` of the i-th member visited (-1:
+// null), bytes[i] = its size, written[i] = the loop writes it.  Returns the number of arrays visited, negative if that is not LoopIo::N_ARRAYS.
+extern "C" int emu_loop_io_arrays(const int32_t* dims, int32_t N, char* base, const int64_t* at, int64_t* where, int64_t* bytes, int32_t* written) {
+    LoopIo io = emu_loop_io(dims, 0.0, 0.0, base, at);
+    int n = 0;
+    io.each_array(N, [&](auto*& m, bool out, size_t b) {
+        where[n] = m ? (const char*)m - base : -1;
+        bytes[n] = (int64_t)b;
+        written[n++] = out;
+    });
+    return n == (int)LoopIo::N_ARRAYS ? n : -n;
+}
+// loop_refusal (mpc_solve_plan.h): the text into out (cap bytes), its length returned; 0: nothing is refused
+extern "C" int emu_loop_refusal(const int32_t* dims, double sigma, double offset, char* base, const int64_t* at, int32_t N, char* out, int32_t cap) {
+    const char* bad = loop_refusal(emu_loop_io(dims, sigma, offset, base, at), N);
+    if (!bad) return 0;
+    snprintf(out, (size_t)cap, "%s", bad);
+    return (int)strlen(bad);
+}
