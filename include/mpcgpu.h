@@ -189,6 +189,24 @@ int mpc_eval_nlp_batch_stages(mpc_handle* h, int32_t B, const double* x, const d
 int mpc_eval_nlp_batch_stages_dev(mpc_handle* h, int32_t B, const double* d_x, const double* d_p, const double* d_obst,
                                   double* d_f, double* d_g, void* stream);
 
+/* A radius per obstacle: mpc_solve_batch_sized[_dev] takes the arguments of mpc_solve_batch_stages[_dev] plus rsum [B, N+1, 3] directly behind
+ * obst.  rsum[b, k, j] is the lower bound of the three copies of circle row j of stage k of instance b -- ego circle j against slot j of
+ * obst[b, k] -- in place of the one lower bound of mpc_set_bounds; it is relaxed as that one is.  The upper side of the circle rows and every
+ * other bound stay the handle's: a handle whose circle rows have a finite upper bound or no lower bound -> MPC_ERR_BOUNDS with a message.  obst
+ * or rsum NULL -> MPC_ERR_INVALID.  The host form also refuses an entry of rsum that is not finite or is negative; the device form does not
+ * read the buffer back: a non-finite entry ends that instance with status -6 and touches no other.  x_out .. lam_x mean what they mean in
+ * _stages; g is the literal distance, so f and g are mpc_eval_nlp_batch_stages' bits at the returned x, and lam_g follows the same sign rule.
+ * Every level of the second chance scales each row's bound by the level's fraction; the last level is the problem itself.  fixed_iters, chunks,
+ * nx 5 / 6 and every horizon behave as in _stages.  With every entry of rsum equal to the circle lower bound given to mpc_set_bounds the call
+ * returns the bits of mpc_solve_batch_stages[_dev].  The first sized call of a handle grows its workspace once (10 rows per stage and instance
+ * in place of 6).  No sensitivity snapshot, as for _stages: any mpc_sens_* call after it returns MPC_ERR_STATE.                              */
+int mpc_solve_batch_sized(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, const double* rsum,
+                          double* x_out, int32_t* status, int32_t* iters, double* kkt,
+                          double* f, double* g, double* lam_g, double* lam_x);
+int mpc_solve_batch_sized_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, const double* d_rsum,
+                              double* d_x_out, int32_t* d_status, int32_t* d_iters, double* d_kkt,
+                              double* d_f, double* d_g, double* d_lam_g, double* d_lam_x, void* stream);
+
 /* Parametric sensitivities of the returned optimum (sIPOPT's step).  p = [U_ref (N nu) | X_ref ((N+1) nx)], n_p = n_w.
  * mpc_solve_batch[_dev]_ex plus: lam_p [B, n_p] (NULL: not computed), CasADi's d/dp [f + lam_g' g + lam_x' x] at the returned x (X_ref column 0
  * -lam_g[pin rows], column k+1 -2 Q (x_k - xref_{k+1}), U_ref 0); n_dir >= 0 forward seeds dp [B, n_dir, n_p] -> dw [B, n_dir, n_w] = (dw/dp) dp
@@ -340,7 +358,7 @@ int mpc_closed_loop_batch_pred_dev(mpc_handle* h, int32_t B, int32_t L, int32_t 
  * No obstacle present at r: the descriptor's centres, chosen = -1.  This is the standard nearest-obstacle formulation, not an exact multi-obstacle
  * NLP: two obstacles equally close to one ego circle at one stage constrain it only once.  The solves are mpc_solve_batch_stages_dev's, unchanged;
  * with M = 1 and pairing 0 traj, ctrl and step_status are bit for bit those of mpc_closed_loop_batch_pred with predict 1 on that track.  One radius
- * per handle, as in every loop: the lower bound of the circle rows holds for all obstacles.
+ * per handle, as in every loop but mpc_closed_loop_batch_traffic_sized: the lower bound of the circle rows holds for all obstacles.
  * clearance [B, L] or NULL: clearance[b, i] = min over the obstacles present at row min(i, Lt - 1) and over ALL nine circle pairs of distance - r_sum
  * for the state before step i, +inf when none is present; nearest [B, L] (int32) or NULL: the obstacle that attains it, or -1; chosen
  * [B, L, N+1, 3] (int32) or NULL.  MPC_ERR_INVALID with a message: M < 1; Lt neither 1 nor >= L; NULL tracks or offsets; an offset that is not
@@ -356,6 +374,25 @@ int mpc_closed_loop_batch_traffic_dev(mpc_handle* h, int32_t B, int32_t L, int32
                                       const double* d_tracks, const double* d_offsets, int32_t pairing, int32_t noise_mode, double sigma,
                                       uint64_t seed, double* d_traj, double* d_ctrl, int32_t* d_step_status, double* d_clearance,
                                       int32_t* d_nearest, int32_t* d_chosen, void* stream);
+/* Traffic of mixed sizes: mpc_closed_loop_batch_traffic_sized[_dev] takes the arguments of mpc_closed_loop_batch_traffic[_dev] plus rsums behind
+ * offsets, in the same shape ([M], per_ego: [B, M]): rsums[m] is the radius sum of ego and obstacle m, checked as the offsets are -- finite -- and
+ * >= 0 (MPC_ERR_INVALID with a message; NULL likewise).  The selection is by CLEARANCE, not by distance: with delta_m = rsums[m] - r_sum (the
+ * handle's circle lower bound) pairing 0 compares min_j |E_j - O_{m,j}| - delta_m, pairing 1 |E_j - O_{m,c}| - delta_m; ties as above.  The slot's
+ * row of the next solve gets the winner's centres and the winner's rsums[m]; no obstacle present: the descriptor's centres, the handle's radius,
+ * chosen = -1.  Every solve is an mpc_solve_batch_sized_dev (its refusal of the handle's bound structure: MPC_ERR_BOUNDS).  clearance[b, i] = min
+ * over the present obstacles and all nine pairs of distance - rsums[m]; nearest the obstacle that attains it.  Noise modes, "loop_async", replay
+ * and step_status as in the traffic loop.  With every rsums[m] equal to the handle's bound traj, ctrl, step_status, clearance, nearest and chosen
+ * are the bits of mpc_closed_loop_batch_traffic.                                                                                                  */
+int mpc_closed_loop_batch_traffic_sized(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path,
+                                        const double* orient, const double* vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* tracks,
+                                        const double* offsets, const double* rsums, int32_t pairing, int32_t noise_mode, double sigma,
+                                        uint64_t seed, double* traj, double* ctrl, int32_t* step_status, double* clearance, int32_t* nearest,
+                                        int32_t* chosen);
+int mpc_closed_loop_batch_traffic_sized_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                            const double* d_orient, const double* d_vdes, int32_t M, int32_t Lt, int32_t per_ego,
+                                            const double* d_tracks, const double* d_offsets, const double* d_rsums, int32_t pairing,
+                                            int32_t noise_mode, double sigma, uint64_t seed, double* d_traj, double* d_ctrl,
+                                            int32_t* d_step_status, double* d_clearance, int32_t* d_nearest, int32_t* d_chosen, void* stream);
 /* The loop stepped FROM OUTSIDE: a session.  Every loop above is closed over its own model -- the plant is the NLP's forward-Euler step, the obstacles
  * come from tracks that already hold the future.  A simulator or a vehicle owns the plant and reports a measured state every step; perception reports
  * where the obstacles are NOW and how fast they move.  One session per handle; it owns device buffers of its own (the rows of its solves, the loop's work

@@ -76,6 +76,8 @@ PROTOTYPES = {
     "mpc_solve_batch_stages_dev": [_vp, _i32] + [_vp] * 12,
     "mpc_eval_nlp_batch_stages": [_vp, _i32] + [_dp] * 5,
     "mpc_eval_nlp_batch_stages_dev": [_vp, _i32] + [_vp] * 6,
+    "mpc_solve_batch_sized": [_vp, _i32] + _rows[:3] + [_dp] + _rows[3:] + [_dp] * 4,          # _stages with rsum behind obst
+    "mpc_solve_batch_sized_dev": [_vp, _i32] + [_vp] * 13,
     "mpc_solve_batch_sens": [_vp, _i32] + _rows + [_dp] * 5 + [_i32, _dp, _dp],
     "mpc_solve_batch_sens_dev": [_vp, _i32] + [_vp] * 12 + [_i32, _vp, _vp, _vp],
     "mpc_sens_adjoint": [_vp, _i32, _dp, _dp],
@@ -98,6 +100,8 @@ PROTOTYPES = {
     "mpc_closed_loop_batch_pred_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _vp, _f64, _i32] + _loop_tail + [_vp] * 5,
     "mpc_closed_loop_batch_traffic": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _i32, _i32, _dp, _dp, _i32] + _loop_tail + [_dp, _dp, _ip, _dp, _ip, _ip],
     "mpc_closed_loop_batch_traffic_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _vp, _vp, _i32] + _loop_tail + [_vp] * 7,
+    "mpc_closed_loop_batch_traffic_sized": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _i32, _i32, _dp, _dp, _dp, _i32] + _loop_tail + [_dp, _dp, _ip, _dp, _ip, _ip],
+    "mpc_closed_loop_batch_traffic_sized_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _i32, _i32, _vp, _vp, _vp, _i32] + _loop_tail + [_vp] * 7,
     "mpc_session_begin": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _i32, _dp, _i32],
     "mpc_session_begin_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _i32, _vp, _i32, _vp],
     "mpc_session_step": [_vp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip],

@@ -322,6 +322,100 @@ MPC_HD void loop_traffic_stage(const LoopTrafficArgs& A, int b, int k, int i) {
     loop_traffic_place(A, b, k, i, i, TrafficTrackPose{A, b, row});
 }
 
+// ---- traffic of mixed sizes (mpc_closed_loop_batch_traffic_sized): obstacle m has a radius sum of its own, rsums[m], and every solve is a sized
+//      one.  The selection is by CLEARANCE: with delta_m = rsums[m] - r_sum (the handle's) every key above is a distance less delta_m -- pairing 0
+//      compares min_j |E_j - O_{m,j}| - delta_m, pairing 1 |E_j - O_{m,c}| - delta_m; ties as above.  The row of the solve is written PACKED, as
+//      sized_pack leaves it (mpc_stage_math.h: six centres, the three slots' radius sums, a pad): the winner's centres with the winner's rsums[m];
+//      nothing present: the descriptor's centres with the handle's radius.  clearance: the smallest key over all nine pairs of every present
+//      obstacle, less r_sum -- the smallest distance - rsums[m].  The cull stays exact: the keys of obstacle m lie within reach_m of d_m - delta_m.
+//      delta_m = 0.0 changes no bit: with every rsums[m] = r_sum the centres, chosen, clearance and nearest are loop_traffic_place's.
+//      (A copy of loop_traffic_place's text with the keys shifted -- keep the two in step; k_loop_traffic and k_session_traffic keep their code.)
+struct LoopTrafficSizedArgs {
+    LoopTrafficArgs T;               // T.obst: the packed rows [B, N+1, OBST_SIZED_ROWS]
+    const double* rsums;             // [M] or [B, M], like T.offsets
+};
+MPC_HD double loop_traffic_delta(const LoopTrafficSizedArgs& S, int b, int m) { return S.rsums[(size_t)(S.T.per_ego ? b : 0) * S.T.M + m] - S.T.r_sum; }
+template <class Pose>
+MPC_HD double loop_traffic_bound_sized(const LoopTrafficSizedArgs& S, int b, const Pose& at, const double* xy) {
+    const LoopTrafficArgs& A = S.T;
+    double bound = INFINITY, tmp[3];
+    for (int m = 0; m < A.M; ++m) {
+        const double* pose = at(m, tmp);
+        if (!loop_traffic_present(pose)) continue;
+        const double hi = loop_traffic_dist(xy, pose) + A.ego_offset + fabs(loop_traffic_offset(A, b, m)) - loop_traffic_delta(S, b, m);
+        if (hi < bound) bound = hi;
+    }
+    return bound;
+}
+MPC_HD bool loop_traffic_near_sized(const LoopTrafficSizedArgs& S, int b, int m, const double* pose, const double* xy, double bound) {
+    const LoopTrafficArgs& A = S.T;
+    const double lo = loop_traffic_dist(xy, pose) - A.ego_offset - fabs(loop_traffic_offset(A, b, m)) - loop_traffic_delta(S, b, m);
+    return !(lo > bound + fabs(bound) * 1e-12 + 1e-12);          // (a key may be negative here: the margin is on its size)
+}
+template <class Pose>
+MPC_HD void loop_traffic_place_sized(const LoopTrafficSizedArgs& S, int b, int k, int i, int col, const Pose& at) {
+    const LoopTrafficArgs& A = S.T;
+    const int N = A.N, St = N + 1, nw = 2 * N + A.nx * St;
+    const double* st = A.state + (size_t)b * A.nx;
+    const double* pl = (i == 0) ? st : A.x0 + (size_t)b * nw + 2 * N + A.nx * k;
+    double e6[6], c6[6], out[6], rad[3] = {A.r_sum, A.r_sum, A.r_sum}, best[3], tmp[3];
+    int32_t pick[3] = {-1, -1, -1};
+    loop_traffic_ego(pl[0], pl[1], pl[4], A.ego_offset, e6);
+    for (int q = 0; q < 6; ++q) out[q] = A.desc_obst[q];
+    double bound = loop_traffic_bound_sized(S, b, at, pl);
+    for (int m = 0; m < A.M; ++m) {
+        const double* pose = at(m, tmp);
+        if (!loop_traffic_present(pose) || !loop_traffic_near_sized(S, b, m, pose, pl, bound)) continue;
+        loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
+        const double dm = loop_traffic_delta(S, b, m), rm = S.rsums[(size_t)(A.per_ego ? b : 0) * A.M + m];
+        if (A.pairing == 0) {
+            double score = loop_traffic_dist(e6, c6);
+            for (int j = 1; j < 3; ++j) score = fmin(score, loop_traffic_dist(e6 + 2 * j, c6 + 2 * j));
+            score -= dm;
+            if (pick[0] < 0 || score < best[0]) {
+                best[0] = score;
+                pick[0] = pick[1] = pick[2] = m;
+                rad[0] = rad[1] = rad[2] = rm;
+                for (int q = 0; q < 6; ++q) out[q] = c6[q];
+            }
+        } else {
+            for (int j = 0; j < 3; ++j)
+                for (int c = 0; c < 3; ++c) {
+                    const double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c) - dm;
+                    if (pick[j] < 0 || dist < best[j]) { best[j] = dist; pick[j] = m; rad[j] = rm; out[2 * j] = c6[2 * c]; out[2 * j + 1] = c6[2 * c + 1]; }
+                }
+        }
+    }
+    double* o = A.obst + ((size_t)b * St + k) * OBST_SIZED_ROWS;
+    for (int q = 0; q < 6; ++q) o[q] = out[q];
+    for (int j = 0; j < 3; ++j) o[OBST_SIZED_OD + j] = rad[j];
+    o[OBST_SIZED_SCALE] = 0.0;
+    if (A.chosen)
+        for (int j = 0; j < 3; ++j) A.chosen[(((size_t)b * A.L + col) * St + k) * 3 + j] = pick[j];
+    if (k != 0 || (!A.clearance && !A.nearest)) return;
+    double cl = INFINITY;
+    int32_t near = -1;
+    loop_traffic_ego(st[0], st[1], st[4], A.ego_offset, e6);
+    bound = loop_traffic_bound_sized(S, b, at, st);
+    for (int m = 0; m < A.M; ++m) {
+        const double* pose = at(m, tmp);
+        if (!loop_traffic_present(pose) || !loop_traffic_near_sized(S, b, m, pose, st, bound)) continue;
+        loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
+        const double dm = loop_traffic_delta(S, b, m);
+        for (int j = 0; j < 3; ++j)
+            for (int c = 0; c < 3; ++c) {
+                const double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c) - dm;
+                if (near < 0 || dist < cl) { cl = dist; near = m; }
+            }
+    }
+    if (A.clearance) A.clearance[(size_t)b * A.L + col] = near < 0 ? INFINITY : cl - A.r_sum;
+    if (A.nearest) A.nearest[(size_t)b * A.L + col] = near;
+}
+MPC_HD void loop_traffic_stage_sized(const LoopTrafficSizedArgs& S, int b, int k, int i) {
+    const int at = i + k, row = at < S.T.Lt - 1 ? at : S.T.Lt - 1;
+    loop_traffic_place_sized(S, b, k, i, i, TrafficTrackPose{S.T, b, row});
+}
+
 // =========================================================================================================================
 // The stepping session (mpc_session_begin / _step): the loop opened at step granularity for a caller that owns the plant and the perception.
 // Around the unchanged solve and loop_advance_instance it adds two pieces:

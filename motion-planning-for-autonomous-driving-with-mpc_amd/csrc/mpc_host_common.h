@@ -173,8 +173,9 @@ struct WsLayout {
 // mailbox: with the instance-major copies k_solve_wg works on (about as large as the tile-major section: a handle that can never run
 // that kernel -- long horizons, a fixed iteration count, hybrid switched off -- does without them and fits twice the rows below 4 GiB)
 // obst_stages: the obstacle section holds six rows per STAGE (OBST_PER_STAGE) instead of six per instance; it is the last section of a
-// tile, so a handle that never makes a per-stage call keeps every offset and the size it had
-inline WsLayout ws_layout(int N, int nx, size_t Bp, bool mailbox = true, bool obst_stages = false) {
+// tile, so a handle that never makes a per-stage call keeps every offset and the size it had; 2: OBST_SIZED_ROWS per stage (a sized solve:
+// centres, offsets, scale -- a per-stage solve finds its six rows per stage in the same section)
+inline WsLayout ws_layout(int N, int nx, size_t Bp, bool mailbox = true, int obst_stages = 0) {
     const size_t NS = (size_t)nx * (nx + 1) / 2, S = N + 1;
     auto ev = [](size_t r) { return (r + 1) & ~(size_t)1; };                          // MPC_EV: whole row pairs per stage
     const size_t NZ = ev(nx + 2), XS = ev(nx), NBLK = ev((nx + 5) + 10 + 2 * nx), NPK = ev(NS + nx), NKK = 2 * nx + 2;   // Dim<NX>::NBLK: sparse H (NX + 5 entries)
@@ -185,7 +186,7 @@ inline WsLayout ws_layout(int N, int nx, size_t Bp, bool mailbox = true, bool ob
     w.SO = take(S * 4); w.NUO = take(S * 4); w.ZLO = take(S * 4); w.ZUO = take(S * 4);
     w.LAM = take(S * XS); w.REF = take(S * XS); w.DZ = take(S * NZ);
     w.PK = take(S * NPK); w.KK = take((size_t)N * NKK); w.BLK = take(S * NBLK); w.ROLL = take(S * XS);
-    w.SC = take(SC_COUNT); w.FILT = take(2 * FILTER_MAX); w.OBST = take(obst_stages ? S * 6 : 6);
+    w.SC = take(SC_COUNT); w.FILT = take(2 * FILTER_MAX); w.OBST = take(obst_stages == 2 ? S * OBST_SIZED_ROWS : obst_stages ? S * 6 : 6);
     w.rows = off;
     w.irows = ev(IS_COUNT);
     w.tile_elems = w.rows * 64;
@@ -221,7 +222,7 @@ inline int dec_s_of(const HostProblem& hp) {
 }
 
 inline void fill_params(Params& P, const HostProblem& hp, int B, size_t Bp, int bx, double* base, int32_t* ibase,
-                        const double* dLB, const double* dUB, bool mailbox = true, bool obst_stages = false) {
+                        const double* dLB, const double* dUB, bool mailbox = true, int obst_stages = 0) {
     const mpc_problem_desc& d = hp.desc;
     const WsLayout w = ws_layout(d.N, d.nx, Bp, mailbox, obst_stages);
     P.B = B; P.Bp = (int32_t)Bp; P.N = d.N; P.nx = d.nx; P.bx = bx;

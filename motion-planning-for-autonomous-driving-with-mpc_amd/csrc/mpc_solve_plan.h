@@ -183,7 +183,8 @@ struct PlanState {
     bool resc_hint = false;             // ... its last solve had stalled instances
     int32_t B = 0;                      // the call: instances
     int32_t per_inst_obst = OBST_SHARED;    // ... its obstacle centres (ObstMode): the descriptor's, one row per instance, one per instance and stage --
-                                        // the last two plan alike: the same kernels, the same bits where every stage's row is the instance's
+                                        // the last two plan alike: the same kernels, the same bits where every stage's row is the instance's;
+                                        // OBST_PER_STAGE_SIZED plans like them too and runs its own instantiations (SolvePlan::sized)
     bool trace = false;                 // ... per-iteration trace (mpc_solve_batch_trace)
     bool in_rescue = false;             // ... a level of the second chance (rescue_dev): no second chance of its own
     bool async_loop = false;            // ... enqueued by the closed-loop driver without host synchronisation
@@ -194,6 +195,8 @@ struct SolvePlan {
     int S, bx, threads, nblk, ntiles, G, stash_rows;
     size_t lds_bytes, lds_init, ric_lds;
     bool masked;                        // the kernels with the reference's bound structure compiled in (variant 2)
+    bool sized;                         // the kernels with a lower bound per circle row compiled in (VM_SIZED: k_start_sized, variant 4 of k_pipeline / k_solve_wg,
+                                        // k_stage<.., SIZED_VM>) -- a sized solve and nothing else; never together with `masked`
     int cap, chunk;                     // iterations at most, launches between two convergence polls
     bool polled;
     // the front of the solve: k_start (ingest, safeguard and start iterate in one launch) or k_ingest + k_prestart_par + k_stage<INIT>
@@ -260,6 +263,7 @@ SolvePlan plan_solve_nx(const HostProblem& hp, const Knobs& kn, const PlanState&
     const bool ref_vm_ok = ((hp.lo_mask | hp.hi_mask) & ~REF_BOUND_VM) == 0u;    // bounds on the reference's four variables only
     pl.masked = kn.bound_mask != 0 && ref_vm_ok && (hp.dense_mask & REF_DENSE_LO) == REF_DENSE_LO && ((hp.dense_mask >> 8) & REF_DENSE_HI) == REF_DENSE_HI &&
                 hp.has_ol && !hp.has_ou && d.obst_mult == 3 && st.per_inst_obst == OBST_SHARED;
+    pl.sized = st.per_inst_obst == OBST_PER_STAGE_SIZED;
     pl.cap = d.fixed_iters > 0 ? d.fixed_iters : d.max_iter;
     pl.chunk = d.fixed_iters > 0 ? pl.cap : 4;
     pl.polled = d.fixed_iters <= 0 && !st.trace;
@@ -413,7 +417,7 @@ inline SolvePlan plan_solve(const HostProblem& hp, const Knobs& kn, const PlanSt
 
 // ---- after the launch: what one solve reports back, and what its caller (solve_dev of mpcgpu.hip) does about the instances that stalled -------
 // a level of the second chance (rescue_dev): the lower bound of the circle rows and the tolerance this solve runs with, in place of the problem's
-struct Level { double ol, tol; };
+struct Level { double ol, tol; double frac = 1.0; };      // (frac: the level's fraction, what a sized solve scales its rows' offsets by)
 struct SolveOutcome {
     bool async_ok = false;              // the solve was enqueued without host synchronisation: nothing below but `mode` is known
     int mode = 0;                       // 0: one launch per kernel and iteration, 1: single-launch pipeline (+ k_solve_wg behind it), 2: k_solve_wg alone
@@ -449,7 +453,9 @@ struct SolveIo {
     double* snap = nullptr;                                         // ... the snapshot of the final iterates (mpc_solve_batch_sens[_dev], mpc_sens.h)
     size_t n_w = 0, n_g = 0, snap_len = 0;                          // HostProblem::n_w(), n_g(); Sens<NX>::len(N)
     size_t n_obst = 6;                                              // doubles of an instance's row of obst: 6, or 6 (N + 1) -- six per stage
-    int32_t obst_mode() const { return !obst ? OBST_SHARED : n_obst > 6 ? OBST_PER_STAGE : OBST_PER_INSTANCE; }
+    bool sized = false;                                             // obst holds the packed rows of a sized solve: n_obst = OBST_SIZED_ROWS (N + 1), sized_pack
+    int32_t obst_mode() const { return !obst ? OBST_SHARED : sized ? OBST_PER_STAGE_SIZED : n_obst > 6 ? OBST_PER_STAGE : OBST_PER_INSTANCE; }
+    int obst_section() const { return obst_mode() == OBST_PER_STAGE_SIZED ? 2 : obst_mode() == OBST_PER_STAGE ? 1 : 0; }      // ws_layout's obst_stages
     // mpc_solve_batch_trace: per-iteration rows [rows, 8, B] on the HOST, the iterations done (a trace call is never cut into chunks)
     struct Trace { double* out = nullptr; int32_t rows = 0; int32_t* n_it = nullptr; } trace;
     // Instances off .. off + n - 1.  THE table of the members' widths in elements per instance: staging sizes and the layout of the second
@@ -488,6 +494,9 @@ struct LoopIo {
     int32_t M = 0, per_ego = 0, pairing = 0;
     const double* offsets = nullptr;
     int32_t *nearest = nullptr, *chosen = nullptr;
+    // traffic of mixed sizes (mpc_closed_loop_batch_traffic_sized): a radius sum per obstacle, shaped like offsets, on the DEVICE -- not a row of
+    // each_array: the host form stages it beside the table's arrays (stage_loop's `more`); null: the traffic loop with the handle's radius
+    const double* rsums = nullptr;
 
     // THE table of the arrays, under a horizon of N stages: f(member, written by the loop, its bytes -- 0 where it is null) for each of the N_ARRAYS.
     // nB egos, nL = nB L steps, nT tracks, nS = N + 1 stages of a solve.  Staging sizes (stage_loop of mpcgpu.hip) come from here and nowhere else.

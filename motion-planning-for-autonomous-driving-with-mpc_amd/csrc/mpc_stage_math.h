@@ -100,8 +100,10 @@ enum IsRow { IS_STATUS = 0, IS_ITERS, IS_NFILT, IS_HAVETH0, IS_CONV, IS_ROLL, IS
                                           // status -7, else 0; bits 16-30: its iteration count), iterations of the attempts that count so far
              IS_COUNT };
 // whose obstacle centres the circle rows of a solve are measured against: the descriptor's for the whole batch, six per instance (obst [B, 6]),
-// or six per instance and stage (obst [B, N+1, 6]: an obstacle that moves over the horizon)
-enum ObstMode : int32_t { OBST_SHARED = 0, OBST_PER_INSTANCE = 1, OBST_PER_STAGE = 2 };
+// or six per instance and stage (obst [B, N+1, 6]: an obstacle that moves over the horizon); OBST_PER_STAGE_SIZED: per instance and stage as well,
+// and every circle row of a stage with a lower bound of its own (mpc_solve_batch_sized: rsum [B, N+1, 3]) -- see OBST_SIZED_ROWS
+enum ObstMode : int32_t { OBST_SHARED = 0, OBST_PER_INSTANCE = 1, OBST_PER_STAGE = 2, OBST_PER_STAGE_SIZED = 3 };
+MPC_HD constexpr bool obst_mode_staged(int32_t m) { return m == OBST_PER_STAGE || m == OBST_PER_STAGE_SIZED; }
 struct Params {
     int32_t B, Bp, N, nx, bx;    // instances, padded instances (multiple of 64), horizon, states, instances/block
     int32_t obst_mult, max_iter, fixed_iters;
@@ -687,6 +689,21 @@ MPC_HD void emit_result(const PRef& P, const Ctx<NX>& c, const int status, const
 //             presence test of that side (the acceleration has an upper bound only -- and a per-instance lower one at stage 0, from the
 //             presolved friction row: its lower side keeps the run-time test)
 constexpr uint32_t VM_OSPEC = 0x100u;
+//   VM_SIZED  a lower bound per circle row (OBST_PER_STAGE_SIZED): the stage's obstacle rows carry, behind the six centres, the three offsets
+//             od = (the row's own relaxed bound) - P.ol and a scale (OBST_SIZED_ROWS); wherever a phase takes a circle row's VALUE it takes
+//             dist - od, so that slack, barrier, fraction-to-boundary and KKT error see the row's own bound through the shared P.ol.  Derivatives
+//             are the distance's.  od = 0.0 changes no bit: with every bound the handle's, the instantiation computes what its per-stage sibling does.
+constexpr uint32_t VM_SIZED = 0x200u;
+// The three offsets of a stage thread live in a context of their own type, CtxSized, which the VM_SIZED instantiations of the kernels declare in
+// place of Ctx (CtxOf) and whose phases see through their Ctx reference: Ctx itself, and with it every other kernel's code, is what it was (a member
+// added to Ctx, used or not, changed the machine code of kernels that never read it: k_stage, k_pipeline<NX, 0>, k_solve_wg<6, 2>).
+template <int NX>
+struct CtxSized : Ctx<NX> { double od[3]; };
+template <int NX, bool SIZED> struct CtxPick { typedef Ctx<NX> type; };
+template <int NX> struct CtxPick<NX, true> { typedef CtxSized<NX> type; };
+template <int NX, uint32_t VM> using CtxOf = typename CtxPick<NX, (VM & VM_SIZED) != 0u>::type;
+#define MPC_OD_REF(c_) (static_cast<CtxSized<NX>&>(c_).od)
+#define MPC_OD(j) ((VM & VM_SIZED) ? static_cast<const CtxSized<NX>&>(c).od[j] : 0.0)
 MPC_HD constexpr uint32_t vm_dense(uint32_t lo, uint32_t hi) { return (lo << 16) | (hi << 24); }
 #define MPC_HAS_OL ((VM & VM_OSPEC) ? true : (P.has_ol != 0))
 #define MPC_HAS_OU ((VM & VM_OSPEC) ? false : (P.has_ou != 0))
@@ -807,8 +824,22 @@ MPC_HD double friction_eval(const Params& P, double a, double dl, double v, doub
 // (k_start<NX, true>, wg_restart<NX, true>), which a per-stage solve runs.
 // Per stage: six rows per stage in the tile-major pair layout of every other per-stage array -- three 16-byte loads, one scalar offset
 // (the stage's) more than the per-instance rows.  The mode is a kernel argument: the branch is wave-uniform.
-template <int NX, bool BATCH_WIDE = false, bool STAGES = true>
+// SIZED (the VM_SIZED instantiations, which only a sized solve runs: no look at the mode): OBST_SIZED_ROWS rows per stage -- the six centres in the
+// three 16-byte loads of the per-stage mode, then (od_0, od_1) and (od_2, scale): two loads more.  The scale is 1.0 but at a level of the second
+// chance, which scales every row's offset by its fraction (x 1.0 changes no bit).  The three products stay in CtxSized: the line search evaluates the
+// rows at every trial point, and a re-read there would put two loads behind the kernel's own stores in every trial.
+constexpr int OBST_SIZED_ROWS = 10, OBST_SIZED_OD = 6, OBST_SIZED_SCALE = 9;
+template <int NX, bool BATCH_WIDE = false, bool STAGES = true, bool SIZED = false>
 MPC_HD void load_obst(const PRef& P, Ctx<NX>& c) {
+    if constexpr (SIZED) {
+        double r[OBST_SIZED_ROWS];
+        ws_load_rows<OBST_SIZED_ROWS>(MPC_ROWS(MPC_K(P.OBST, OBST_SIZED_ROWS, 0, e)), r);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) c.obst[i] = r[i];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) MPC_OD_REF(c)[j] = r[OBST_SIZED_OD + j] * r[OBST_SIZED_SCALE];
+        return;
+    }
     if (!BATCH_WIDE && STAGES && P.per_inst_obst == OBST_PER_STAGE) {
         ws_load_rows<6>(MPC_ROWS(MPC_K(P.OBST, 6, 0, e)), c.obst);
         return;
@@ -846,6 +877,48 @@ MPC_HD void obst_xp_write(const ObstXpose& A, int tile, int k0, int e, const Obs
     if (tile * 64 + l >= A.B) return;
     // rows 2q, 2q + 1 with q = 3 k0 + p: mpc_prow(2q) = 128 q
     *reinterpret_cast<ObstPair*>(A.OBST + (size_t)tile * A.tile_elems + (size_t)(3 * k0 + p) * 128u + 2u * (uint32_t)l) = lds[l * OBST_XP_LD + p];
+}
+
+// ---- the sized sibling (k_transpose_obst_sized, in front of every sized solve).  The rows come packed, [B, N+1, OBST_SIZED_ROWS] row-major: a
+//      stage's six centres, its three radius sums and a pad (sized_pack below, what the entry points make of obst and rsum -- one row per
+//      instance for the chunks and the second chance's gather to cut and copy).  Same trip, five pairs per stage instead of three; pairs 3 and 4
+//      of a stage are converted on the way in: (rsum_0, rsum_1) -> (od_0, od_1), (rsum_2, pad) -> (od_2, scale), with
+//          od = relax_lo(rsum) - relax_lo(ol_raw) = (rsum - ol_raw) - relax (max(1, |rsum|) - max(1, |ol_raw|)),
+//      written so that rsum == ol_raw gives 0.0 whatever the compiler contracts, and a non-finite rsum a NaN (that row ends with status -6).
+constexpr int OBST_XS_KC = 4;                    // stages per workgroup: 64 x 21 pairs = 21 KiB of LDS
+constexpr int OBST_XS_PP = OBST_SIZED_ROWS / 2;  // pairs per stage
+constexpr int OBST_XS_LD = OBST_XS_PP * OBST_XS_KC + 1;
+struct ObstXposeSized {
+    const double* rows;          // [B][S][OBST_SIZED_ROWS]
+    double* OBST;                // first row of the obstacle section in tile 0 (ws_layout(.., obst_sized = true).OBST)
+    int32_t B, S;
+    uint32_t tile_elems;
+    double ol_raw, relax, scale; // the handle's circle lower bound as set, BOUND_RELAX, the level's fraction (1.0: the problem itself)
+};
+MPC_HD double sized_od(const ObstXposeSized& A, double rsum) { return (rsum - A.ol_raw) - A.relax * (fmax(1.0, fabs(rsum)) - fmax(1.0, fabs(A.ol_raw))); }
+MPC_HD int obst_xs_stages(const ObstXposeSized& A, int k0) { return A.S - k0 < OBST_XS_KC ? A.S - k0 : OBST_XS_KC; }
+MPC_HD int obst_xs_count(const ObstXposeSized& A, int k0) { return 64 * OBST_XS_PP * obst_xs_stages(A, k0); }
+MPC_HD void obst_xs_read(const ObstXposeSized& A, int tile, int k0, int e, ObstPair* lds) {
+    const int pc = OBST_XS_PP * obst_xs_stages(A, k0), l = e / pc, p = e - l * pc, b = tile * 64 + l;
+    if (b >= A.B) return;
+    const double* s = A.rows + ((size_t)b * A.S + k0) * OBST_SIZED_ROWS + 2 * p;
+    ObstPair v = ((uintptr_t)A.rows & 15u) == 0 ? *reinterpret_cast<const ObstPair*>(s) : ObstPair{s[0], s[1]};
+    const int q = p % OBST_XS_PP;
+    if (q == 3) v = ObstPair{sized_od(A, v.lo), sized_od(A, v.hi)};
+    if (q == 4) v = ObstPair{sized_od(A, v.lo), A.scale};
+    lds[l * OBST_XS_LD + p] = v;
+}
+MPC_HD void obst_xs_write(const ObstXposeSized& A, int tile, int k0, int e, const ObstPair* lds) {
+    const int p = e >> 6, l = e & 63;
+    if (tile * 64 + l >= A.B) return;
+    *reinterpret_cast<ObstPair*>(A.OBST + (size_t)tile * A.tile_elems + (size_t)(OBST_XS_PP * k0 + p) * 128u + 2u * (uint32_t)l) = lds[l * OBST_XS_LD + p];
+}
+// obst [B, S, 6] and rsum [B, S, 3] -> rows [B, S, OBST_SIZED_ROWS]; element e = b S + k
+MPC_HD void sized_pack(const double* obst, const double* rsum, double* rows, size_t e) {
+    double* r = rows + e * OBST_SIZED_ROWS;
+    for (int i = 0; i < 6; ++i) r[i] = obst[e * 6 + i];
+    for (int j = 0; j < 3; ++j) r[OBST_SIZED_OD + j] = rsum[e * 3 + j];
+    r[OBST_SIZED_SCALE] = 0.0;
 }
 
 // =========================================================================================================
@@ -996,14 +1069,14 @@ MPC_HD void prestart_instance(const PRef& P, int b) {
 // =========================================================================================================
 // Phase 0 (init kernel only): build the start iterate from the caller's x0 (IPOPT section 3.6)
 // =========================================================================================================
-template <int NX, bool OSTG = true>           // (OSTG: load_obst's STAGES)
+template <int NX, bool OSTG = true, bool SIZED = false>           // (OSTG, SIZED: load_obst's STAGES, SIZED)
 MPC_HD void phase_init_point(const PRef& P, Ctx<NX>& c, Red0& red) {
     using D = Dim<NX>;
     constexpr int NZ = D::NZ;
     red = red_neutral0();
     if (!c.valid) return;
     const int N = P.N, k = c.k;
-    load_obst<NX, false, OSTG>(P, c);
+    load_obst<NX, false, OSTG, SIZED>(P, c);
     c.fric_row = MPC_S(P.ISC, IS_FROW) != 0;
     c.a0lb = MPC_S(P.SC, SC_A0LB);
     c.a0ub = MPC_S(P.SC, SC_A0UB);
@@ -1067,6 +1140,10 @@ MPC_HD void phase_init_point(const PRef& P, Ctx<NX>& c, Red0& red) {
     mpc_sincos(c.z[2 + 4], sps, cps);
     double dist[3];
     obstacle_eval(P, c.obst, c.z[2], c.z[3], sps, cps, dist, nullptr, nullptr, false);
+    if constexpr (SIZED) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) dist[j] -= MPC_OD_REF(c)[j];
+    }
     const double ol = P.has_ol ? P.ol : -INFINITY, ou = P.has_ou ? P.ou : INFINITY;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -1189,7 +1266,7 @@ MPC_HD void phase_preload(const PRef& P, Ctx<NX>& c, PreTmp<NX>& tmp, const bool
     constexpr int NZ = D::NZ;
     if (!c.valid) return;
     const int N = P.N, k = c.k;
-    load_obst<NX, (VM & 0x100u) != 0u>(P, c);
+    load_obst<NX, (VM & 0x100u) != 0u, true, (VM & VM_SIZED) != 0u>(P, c);
     // (rows come in pairs, one 16-byte load per pair: see mpc_prow)
     ws_load_rows<NZ>(MPC_ROWS(MPC_KX(Z, NZ, 0, e)), c.z);
     // (MB: step and cost-to-go come from the LDS record the sweeps of this workgroup left them in -- see Rec)
@@ -1275,7 +1352,7 @@ MPC_HD void phase_preload_step(const PRef& P, Ctx<NX>& c) {
 }
 
 // arithmetic on the loaded arrays only: slack steps ds = J dx + (d - s), multiplier steps dlam = -(P dx + p) - lam
-template <int NX>
+template <int NX, uint32_t VM = 0xFFu>          // (VM: VM_SIZED alone is read)
 MPC_HD void phase_premath(const PRef& P, Ctx<NX>& c, const PreTmp<NX>& tmp) {
     using D = Dim<NX>;
     if (!c.valid) return;
@@ -1287,7 +1364,7 @@ MPC_HD void phase_premath(const PRef& P, Ctx<NX>& c, const PreTmp<NX>& tmp) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             double J[3];
-            const double dist = circle_eval(P, c.obst, j, c.z[2], c.z[3], tg.sps, tg.cps, J, nullptr, true);
+            const double dist = circle_eval(P, c.obst, j, c.z[2], c.z[3], tg.sps, tg.cps, J, nullptr, true) - MPC_OD(j);
             double ds = dist - c.so[j];
 #pragma unroll
             for (int a = 0; a < 3; ++a) ds += J[a] * c.dz[2 + oi[a]];
@@ -1431,7 +1508,7 @@ MPC_HD void phase_trial_eval(const PRef& P, Ctx<NX>& c, Red2& red) {
     {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const double dist = circle_eval(P, c.obst, j, zt[2], zt[3], tg.sps, tg.cps, nullptr, nullptr, false);
+            const double dist = circle_eval(P, c.obst, j, zt[2], zt[3], tg.sps, tg.cps, nullptr, nullptr, false) - MPC_OD(j);
             const double s = c.so[j] + al * c.dso[j];
             theta += m * fabs(dist - s);
             if (MPC_HAS_OL) { const double gap = s - P.ol; if (gap <= 0) bad = 1.0; else gp *= powi_small(gap, m); }
@@ -1657,7 +1734,7 @@ MPC_HD void phase_ineq_assemble(const PRef& P, Ctx<NX>& c, OUT& xo, KktPart& kp,
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         double J[3], Ho[6];
-        const double dist = circle_eval(P, c.obst, j, c.z[2], c.z[3], tg.sps, tg.cps, J, Ho, true);
+        const double dist = circle_eval(P, c.obst, j, c.z[2], c.z[3], tg.sps, tg.cps, J, Ho, true) - MPC_OD(j);
         const double s = c.so[j], nu = c.nuo[j];
         double sg = 0.0, gbb = 0.0, rs = -nu;
         if (MPC_HAS_OL) side_kkt(s - P.ol, REUSE ? c.iglo[j] : mpc_rcp(s - P.ol), c.zlo[j], 1.0, m, sg, gbb, rs, kp.cmin, kp.cmax, kp.sz, kp.gp);
@@ -1665,6 +1742,10 @@ MPC_HD void phase_ineq_assemble(const PRef& P, Ctx<NX>& c, OUT& xo, KktPart& kp,
         if (m * sg > ILL_WEIGHT) c.ill = true;
         kp.dual = fmax(kp.dual, fabs(rs));
         const double res = dist - s;
+        // (a sized row whose own bound is not finite: fmax drops a NaN from the residual norms and the row's multiplier is still zero, so nothing
+        //  the termination test reads would show it before the sweeps choke on the Hessian -- status -7; into the stationarity residual, whose
+        //  non-finite entries end the instance with status -6)
+        if constexpr ((VM & VM_SIZED) != 0u) { if (!isfinite(res)) orx[0] = res; }
         kp.theta += m * fabs(res);
         kp.prim = fmax(kp.prim, fabs(res));
         kp.smult += m * fabs(nu);

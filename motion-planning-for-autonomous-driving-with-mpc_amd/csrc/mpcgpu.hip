@@ -160,6 +160,10 @@ __device__ __forceinline__ void stash_xfer(Ctx<NX>& c, double* st, int T, int t,
 #define MPC_REF_FLAGS (VM_OSPEC | vm_dense(REF_DENSE_LO, REF_DENSE_HI))
 #endif
 constexpr uint32_t REF_VM = REF_BOUND_VM | MPC_REF_FLAGS;
+// the phases' mask of variant VAR of k_pipeline / k_solve_wg: 0 bounds looked up at run time, 2 the reference's structure, 4 variant 0 with a lower
+// bound per circle row (VM_SIZED: the kernels of mpc_solve_batch_sized, instantiations of their own -- no kernel of another solve reads a flag for it)
+constexpr uint32_t SIZED_VM = 0xFFu | VM_SIZED;
+constexpr uint32_t var_vm(int var) { return var == 2 ? REF_VM : var == 4 ? SIZED_VM : 0xFFu; }
 // One stage workgroup's share of an iteration: the bx instance columns starting at b0.  `tile_bits` is the activity mask
 // of b0's tile (bit l: instance l was iterating when the last Riccati sweep started); a block without such an instance
 // leaves before touching HBM.  Called once per launch by k_stage and once per work item by k_pipeline.
@@ -179,7 +183,7 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
                                             uint32_t* live_out = nullptr, const bool bounds_in_lds = false, const StepWait& step_wait = StepWait()) {
     constexpr bool EARLY = !std::is_same<StepWait, NoStepWait>::value;
     static_assert(!(EARLY && INIT), "the start iterate reads no step");
-    Ctx<NX> c;
+    CtxOf<NX, VM> c;      // (Ctx<NX> but in the VM_SIZED instantiations)
     constexpr bool STASH = MAXT <= 256 && MPC_STAGE_STASH;
     const bool has_ou = (VM & VM_OSPEC) ? false : (P.has_ou != 0);     // (what the stash parks)
     const int bx = P.bx, t = threadIdx.x;
@@ -211,7 +215,7 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
     if (INIT) lds_barrier();
     if (INIT) {
         Red0 r0;
-        phase_init_point<NX, OSTG>(P, c, r0);
+        phase_init_point<NX, OSTG, (VM & VM_SIZED) != 0u>(P, c, r0);
         block_reduce(r0, bx, lds);
         phase_init_scalars<NX>(P, c, r0);
     } else {
@@ -227,10 +231,10 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
                 if (!step_wait()) return;
                 phase_preload_step<NX>(P, c);
             }
-            phase_premath<NX>(P, c, tmp);
+            phase_premath<NX, VM>(P, c, tmp);
         } else {
             phase_preload<NX, false, VM>(P, c, tmp);           // every array load of the kernel is in flight before the first wait
-            phase_premath<NX>(P, c, tmp);
+            phase_premath<NX, VM>(P, c, tmp);
             MPC_STAMP(P.DBG, blockIdx.x, SB_ISSUED, t == 0 && stamp);
         }
         // (launches that write the caller's rows themselves: an instance the Riccati sweep has just given up leaves here -- its iterate is in c.z)
@@ -321,7 +325,7 @@ template <int NX, uint32_t VM, class Mid>
 __device__ __forceinline__ void wg_stage(const PRef& P, const int ib0, const int ib1, double* lds_bnd, const mpc_lds_ptr rec_base, const int n_mult, const int n_z, const bool stamp,
                                          uint32_t* live_out, WgIo& io, Mid&& mid) {
     const int bx = P.bx, t = threadIdx.x;
-    Ctx<NX> c;
+    CtxOf<NX, VM> c;      // (Ctx<NX> but in the VM_SIZED instantiations)
     PreTmp<NX> tmp;
     c.k = t / bx;
     c.bl = t & (bx - 1);
@@ -353,7 +357,7 @@ __device__ __forceinline__ void wg_stage(const PRef& P, const int ib0, const int
     MPC_STAMP(P.DBG, blockIdx.x, SB_ENTER, t == 0 && stamp);
     if (((io.fail >> (t & (bx - 1))) & 1u) && c.valid) { c.status = -7; c.active = false; }      // (what the sweep has written to the status row)
     phase_preload_rec<NX>(P, c, tmp);
-    phase_premath<NX>(P, c, tmp);
+    phase_premath<NX, VM>(P, c, tmp);
     MPC_STAMP(P.DBG, blockIdx.x, SB_ISSUED, t == 0 && stamp);
     if (!__any(c.active ? 1 : 0)) return;
     MPC_STAMP(P.DBG, blockIdx.x, SB_LOADED, t == 0 && stamp);
@@ -1026,7 +1030,7 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
                     const uint32_t item = lds_uniform(sh_word[1]);
                     const unsigned long long bits = ((unsigned long long)lds_uniform(sh_word[3]) << 32) | lds_uniform(sh_word[2]);
                     if (item != PIPE_EXIT) {
-                        stage_block<NX, false, 256, VAR == 2 ? REF_VM : 0xFFu>(P, n_mult, n_z, stash_rows, pipe_item_tile(item) * 64u + pipe_item_q(item) * (uint32_t)P.bx, bits, lds, false, nullptr, false);
+                        stage_block<NX, false, 256, var_vm(VAR)>(P, n_mult, n_z, stash_rows, pipe_item_tile(item) * 64u + pipe_item_q(item) * (uint32_t)P.bx, bits, lds, false, nullptr, false);
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         lds_barrier();
                         if (t == 0) {
@@ -1081,9 +1085,9 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
         MPC_STAMP(P.DBG, blockIdx.x, PW_BCAST, t == 0 && n_pass == 5u);
         const uint32_t tile = pipe_item_tile(item);
         if constexpr (HELP)
-            stage_block<NX, false, 256, VAR == 2 ? REF_VM : 0xFFu>(P, n_mult, n_z, stash_rows, tile * 64u + pipe_item_q(item) * (uint32_t)P.bx, bits, lds, n_pass == 5u, nullptr, have_bounds);
+            stage_block<NX, false, 256, var_vm(VAR)>(P, n_mult, n_z, stash_rows, tile * 64u + pipe_item_q(item) * (uint32_t)P.bx, bits, lds, n_pass == 5u, nullptr, have_bounds);
         else
-            stage_block<NX, false, 256, VAR == 2 ? REF_VM : 0xFFu>(P, n_mult, n_z, stash_rows, tile * 64u + pipe_item_q(item) * (uint32_t)P.bx, bits, lds, n_pass == 5u, nullptr, have_bounds,
+            stage_block<NX, false, 256, var_vm(VAR)>(P, n_mult, n_z, stash_rows, tile * 64u + pipe_item_q(item) * (uint32_t)P.bx, bits, lds, n_pass == 5u, nullptr, have_bounds,
                                                                    PipeStepWait{step_ready + tile, abort_w, &sh_word[0], pipe_item_round(item), tile, kpub < 0});
         // (an item whose instance columns have all finished leaves stage_block before the copy)
         have_bounds = have_bounds || ((bits >> ((pipe_item_q(item) * (uint32_t)P.bx) & 63u)) & ((P.bx >= 64) ? ~0ull : ((1ull << P.bx) - 1ull))) != 0ull;
@@ -1142,6 +1146,7 @@ template <int NX, class Src = PrestartFromWs> __device__ __forceinline__ void pr
 // restart of the instance of a one-instance workgroup of k_solve_wg at a level of its second chance: warm start -> tile-major Z, start-point
 // safeguard, start iterate (what k_start does for a block) -- see k_solve_wg<.., RESC>
 // (OSTG: stage_block's; false, the default, is the function variant 2 calls, code as it was -- true the one of variant 0, which a per-stage solve runs)
+// KEEP IN STEP with wg_restart_sized below, a copy of this text: a change here is made there too.
 template <int NX, bool OSTG = false>
 __device__ __attribute__((noinline)) void wg_restart(const PRef& Pin, const int n_mult, const int n_z, const int stash_rows, const uint32_t b0, double* lds,
                                                      uint32_t* live_out, const bool carry, const bool from_xs, const bool keep_first, const bool first_tiled) {
@@ -1194,6 +1199,67 @@ __device__ __attribute__((noinline)) void wg_restart(const PRef& Pin, const int 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     stage_block<NX, true, 256, 0xFFu, NoStepWait, OSTG>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, false, live_out);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+// ... of a sized solve (variant 4): wg_restart<NX, true> with the start iterate's phases instantiated for SIZED_VM.  A copy of its text, on purpose:
+// with the two sharing their body through a function, wg_restart<NX> and its callers k_solve_wg<.., RESC> came out of the compiler with other
+// machine code than before (tools/kernel_hashes.py), and a build of those is trusted only once the GPU suite has passed on it.
+// KEEP IN STEP with wg_restart above: all that differs is the name and the last stage_block's mask and OSTG.
+template <int NX>
+__device__ __attribute__((noinline)) void wg_restart_sized(const PRef& Pin, const int n_mult, const int n_z, const int stash_rows, const uint32_t b0, double* lds,
+                                                           uint32_t* live_out, const bool carry, const bool from_xs, const bool keep_first, const bool first_tiled) {
+    const PRef P = mpc_pref(static_cast<const Params&>(Pin), false);      // (a copy in registers, its cache policy a literal again: the reference points into the caller's stack)
+    using D = Dim<NX>;
+    const int t = threadIdx.x, N = P.N, bx = P.bx;
+    struct { int b, k, mb, bl; } c;
+    c.k = t / bx;
+    c.bl = t & (bx - 1);
+    c.mb = (int)blockIdx.x * bx;
+    c.b = (int)b0 + c.bl;
+    const bool valid = (c.k <= N) && (c.b < P.B);
+    if (valid) {
+        constexpr int NZ = D::NZ;
+        double v[MPC_EV(NZ)];
+        static_assert(2 * MPC_EV(NZ) <= D::NPK, "two iterates fit the cost-to-go rows of a stage");
+        // (first level: the iterate the first attempt stopped at is kept -- behind the warm start in the same scratch rows --, with its KKT
+        //  error; should every level fail, the caller gets that row back, as from rescue_dev: wg_restore_first)
+        if (keep_first) {
+            // (an instance that came out of the pipeline stalled has never been taken over: its iterate is still tile-major)
+            if (first_tiled) ws_load_rows<NZ>(MPC_ROWS(MPC_K(P.Z, NZ, 0, e)), v);
+            else ws_load_rows<NZ>(MPC_ROWS(MPC_KI(P.MZ, NZ, 0, e)), v);
+            ws_store_rows<NZ>(MPC_ROWS(MPC_K(P.PK, D::NPK, 0, MPC_EV(NZ) + e)), v);
+            if (c.k == 0) MPC_S(P.SC, SC_E0S) = (double)MPC_S(P.SC, SC_E0);
+        }
+        // (the scratch of the warm start: the tile-major rows of the cost-to-go, which this kernel does not use)
+        if (carry) {
+            ws_load_rows<NZ>(MPC_ROWS(MPC_KI(P.MZ, NZ, 0, e)), v);
+            ws_store_rows<NZ>(MPC_ROWS(MPC_K(P.PK, D::NPK, 0, e)), v);
+        }
+        if (from_xs) {
+            if (!carry) ws_load_rows<NZ>(MPC_ROWS(MPC_K(P.PK, D::NPK, 0, e)), v);
+        } else {
+            const size_t nw = (size_t)2 * N + (size_t)NX * (N + 1);
+            const double* xr = P.x0 + (size_t)c.b * nw;
+            v[0] = (c.k < N) ? MPC_GP(xr, 2 * c.k) : 0.0;
+            v[1] = (c.k < N) ? MPC_GP(xr, 2 * c.k + 1) : 0.0;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) v[2 + i] = MPC_GP(xr, 2 * N + NX * c.k + i);
+        }
+        ws_store_rows<NZ>(MPC_ROWS(MPC_K(P.Z, NZ, 0, e)), v);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    prestart_par_block<NX>(P, b0, lds);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stage_block<NX, true, 256, SIZED_VM, NoStepWait, true>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, false, live_out);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1414,6 +1480,12 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
                 // (out of line, on a copy of the parameters: the start-point safeguard and the start iterate inlined here put the hot loop at 512
                 //  registers with scratch -- B = 256 lane following paid 1.7 % for a path it never takes)
                 const PRef Pc = P;
+                if constexpr (VAR == 4) {
+                    // (a sized solve: the level scales every row's offset by its fraction -- the scale row of the instance's stages, which this
+                    //  workgroup alone reads; the restart's first wait for its stores is in front of every load of it)
+                    if (valid) MPC_K(P.OBST,OBST_SIZED_ROWS, 0, OBST_SIZED_SCALE) = resc_fraction(q);
+                    wg_restart_sized<NX>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
+                } else
                 // (per-stage obstacle rows, variant 0 only: the instantiation that reads them -- every other solve keeps the function it had)
                 if (VAR == 2 || Pc.per_inst_obst != OBST_PER_STAGE) wg_restart<NX>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
                 else wg_restart<NX, true>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
@@ -1523,7 +1595,7 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
         MfmaLane<NX> m;
         mfma_lane_setup<NX>(m, lw, P.dt);
         // ---- KKT solves of the live instances (two: interleaved in one instruction stream), then the stage phases (wg_stage)
-        constexpr uint32_t SVM = VAR == 2 ? REF_VM : 0xFFu;
+        constexpr uint32_t SVM = var_vm(VAR);
         {
             auto inst_of = [&](int g, MfmaInst& in, double& x0) {
                 in.inst = (uint32_t)(g ? ib1 : ib0);
@@ -1619,6 +1691,7 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
     }
 #endif
 }
+// (KEEP IN STEP: k_solve_wg_sized below repeats this kernel's epilogue.)
 // Params::fin_ctl: the launch is the last of its solve -- the workgroup that leaves LAST copies the solve's statistics block (abort word, rounds,
 // counters of both loop kernels, instances that did not converge: the PH_WORDS words at fin_ctl) into the handle's pinned host block (fin_host),
 // so that the host reads it when the stream has drained: no copy command, no kernel of its own behind the loop.  fin_ctl[PH_FIN_TICKET] counts the
@@ -1638,6 +1711,31 @@ __global__ void __launch_bounds__(256) k_solve_wg(const Params Pk, const int n_m
             //  read them with agent-scope loads; the caller's rows become visible with the end of the kernel)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             tk = __hip_atomic_fetch_add(ctl + PH_FIN_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // counted as gone
+        }
+        tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk);
+        if (tk == gridDim.x - 1u && threadIdx.x < PH_WORDS) {
+            const uint32_t v = __hip_atomic_load(ctl + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(kp->fin_host + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+#endif
+}
+// k_solve_wg of a sized solve: variant 4 of the body (var_vm), the same epilogue (KEEP IN STEP with k_solve_wg above).  A kernel of its own name, not k_solve_wg<NX, 4, RESC>: the
+// kernels that call wg_restart find their LDS through a table the compiler indexes by kernel, in the order of the kernels' names -- a further
+// k_solve_wg<5, ..> renumbered k_solve_wg<6, ..> and changed a literal in their code; this name sorts behind them all.
+template <int NX, bool RESC = false>
+__global__ void __launch_bounds__(256) k_solve_wg_sized(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* stats, const uint32_t* skip_if,
+                                                        const WgRescue resc, unsigned long long* wtrace, const int32_t* list, const uint32_t* list_n) {
+    solve_wg_body<NX, 4, RESC>(Pk, n_mult, n_z, stash_rows, stats, skip_if, resc, wtrace, list, list_n);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (threadIdx.x < 64) {
+        const mpc_kernarg_params kp = wg_kernarg();
+        uint32_t* const ctl = kp->fin_ctl;
+        if (ctl == nullptr) return;
+        uint32_t tk = 0u;
+        if (threadIdx.x == 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            tk = __hip_atomic_fetch_add(ctl + PH_FIN_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk);
         if (tk == gridDim.x - 1u && threadIdx.x < PH_WORDS) {
@@ -1863,6 +1961,7 @@ __global__ void __launch_bounds__(1024) k_prestart_par(const Params Pk) {
 // zero_p / zero_n: the OTHER control block of the loop kernels, zeroed here for the next solve (the two blocks alternate: a solve in steady state has
 // no fill of its own anywhere on its stream)
 // OSTG: stage_block's -- false, the default, is the kernel of every solve but a per-stage one, code as it was; true that solve's
+// KEEP IN STEP with k_start_sized below, a copy of this text: a change here is made there too.
 template <int NX, bool OSTG = false>
 __global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* zero_p, const uint32_t zero_n) {
     const PRef P(Pk);
@@ -1932,6 +2031,78 @@ __global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start(const Params Pk, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     MPC_STAMP(P.DBG, blockIdx.x, KS_FENCED, threadIdx.x == 0);
     stage_block<NX, true, 256, 0xFFu, NoStepWait, OSTG>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, true, nullptr, true);
+}
+// ... of a sized solve: k_start<NX, true> with the start iterate's phases instantiated for SIZED_VM -- a copy of its text, for wg_restart_sized's reason.
+// KEEP IN STEP with k_start above: all that differs is the name and the last stage_block's mask and OSTG.
+template <int NX>
+__global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start_sized(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* zero_p, const uint32_t zero_n) {
+    const PRef P(Pk);
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    if (zero_p != nullptr && blockIdx.x == 0)
+        for (uint32_t q = threadIdx.x; q < zero_n; q += blockDim.x) zero_p[q] = 0u;
+    uint32_t blk = blockIdx.x;
+    if ((gridDim.x & 7u) == 0u) blk = (blk & 7u) * (gridDim.x >> 3) + (blk >> 3);
+    const uint32_t b0 = (blk + (uint32_t)P.tile0 * (64u / (uint32_t)P.bx)) * (uint32_t)P.bx;
+    MPC_STAMP(P.DBG, blockIdx.x, KS_BEGIN, threadIdx.x == 0);
+    {
+        // ---- the caller's rows of this block (x0, the X_ref part of p: row-major [B][n_w]) -> LDS -> the tile-major Z / REF rows of the
+        //      workspace: what k_ingest does for a whole batch, here for the block's own bx instances (consecutive rows: coalesced reads)
+        constexpr int NZ = NX + 2;
+        const int N = P.N, nw = 2 * N + NX * (N + 1), bx = P.bx, t = threadIdx.x;
+        // LDS: [the safeguard's tables and scan rows (prestart_par_block) | the block's rows of x0 | of the X_ref part of p]: the safeguard reads the
+        // guess and the reference from the last two, so it does not wait for the stores below
+        const size_t pre_doubles = prestart_doubles(NX, N + 1, bx);
+        // (the safeguard's region starts where stage_block keeps its bounds table -- behind the reduction scratch -- and begins with that table: the
+        //  start iterate finds it in place)
+        double* const pre = lds + (blockDim.x >> 6) * 10 * bx;
+        double* rx = pre + ((pre_doubles + 1) & ~(size_t)1);     // [bx][nw]
+        double* rp = rx + bx * nw;                               // [bx][nw - 2N]   (the U_ref part of p is not used by the NLP, optimizer.py:507-511)
+        const int nrow = ((int)b0 + bx <= P.B) ? bx : (P.B > (int)b0 ? P.B - (int)b0 : 0);
+        const int npx = nw - 2 * N;
+        // (every load of a thread requested before its first LDS write: batched_fill; the rows of p one per trip element -- no division)
+        batched_fill<8>(nrow * nw, t, (int)blockDim.x, [&](int q) { return MPC_GP(P.x0, (size_t)b0 * nw + q); }, [&](int q, double v) { rx[q] = v; });
+        for (int r0 = 0; r0 < nrow; r0 += 8) {
+            for (int c0 = 0; c0 < npx; c0 += (int)blockDim.x) {
+                const int col = c0 + t;
+                double v[8];
+#pragma unroll
+                for (int r = 0; r < 8; ++r) v[r] = (r0 + r < nrow && col < npx) ? (double)MPC_GP(P.p, ((size_t)b0 + r0 + r) * nw + 2 * N + col) : 0.0;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) if (r0 + r < nrow && col < npx) rp[(r0 + r) * npx + col] = v[r];
+            }
+        }
+        __syncthreads();
+        MPC_STAMP(P.DBG, blockIdx.x, KS_ROWS, threadIdx.x == 0);
+        struct { int b, k; } c;
+        c.k = t / bx;
+        const int bl = t & (bx - 1);
+        c.b = (int)b0 + bl;
+        if (c.k <= N && c.b < P.B) {
+            double z[NZ], r[NX];
+            const double* xr = rx + bl * nw;
+            z[0] = (c.k < N) ? xr[2 * c.k] : 0.0;
+            z[1] = (c.k < N) ? xr[2 * c.k + 1] : 0.0;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) { z[2 + i] = xr[2 * N + NX * c.k + i]; r[i] = rp[bl * npx + NX * c.k + i]; }
+            ws_store_rows<NZ>(MPC_ROWS(MPC_K(P.Z, NZ, 0, e)), z);
+            ws_store_rows<NX>(MPC_ROWS(MPC_K(P.REF, NX, 0, e)), r);
+        }
+        struct FromLds {
+            const double *rx, *rp;
+            int nw, npx, N;
+            __device__ __forceinline__ double z(int bl, int k, int i) const { return i < 2 ? (k < N ? rx[bl * nw + 2 * k + i] : 0.0) : rx[bl * nw + 2 * N + NX * k + (i - 2)]; }
+            __device__ __forceinline__ double ref0(int bl, int i) const { return rp[bl * npx + i]; }
+        } src{rx, rp, nw, npx, N};
+        MPC_STAMP(P.DBG, blockIdx.x, KS_STORED, threadIdx.x == 0);
+        prestart_par_block<NX, FromLds>(P, b0, pre, src);
+    }
+    MPC_STAMP(P.DBG, blockIdx.x, KS_SAFE, threadIdx.x == 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    MPC_STAMP(P.DBG, blockIdx.x, KS_FENCED, threadIdx.x == 0);
+    stage_block<NX, true, 256, SIZED_VM, NoStepWait, true>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, true, nullptr, true);
 }
 
 
@@ -2044,6 +2215,19 @@ __global__ void __launch_bounds__(256) k_transpose_obst_stages(const ObstXpose A
     for (int e = (int)threadIdx.x; e < n; e += (int)blockDim.x) obst_xp_read(A, tl, k0, e, tile);
     __syncthreads();
     for (int e = (int)threadIdx.x; e < n; e += (int)blockDim.x) obst_xp_write(A, tl, k0, e, tile);
+}
+// the sized sibling: packed rows [B, N+1, OBST_SIZED_ROWS] -> centres, offsets and scale of every stage; grid (tiles, ceil((N + 1) / OBST_XS_KC))
+__global__ void __launch_bounds__(256) k_transpose_obst_sized(const ObstXposeSized A) {
+    __shared__ ObstPair tile[64 * OBST_XS_LD];
+    const int tl = (int)blockIdx.x, k0 = (int)blockIdx.y * OBST_XS_KC, n = obst_xs_count(A, k0);
+    for (int e = (int)threadIdx.x; e < n; e += (int)blockDim.x) obst_xs_read(A, tl, k0, e, tile);
+    __syncthreads();
+    for (int e = (int)threadIdx.x; e < n; e += (int)blockDim.x) obst_xs_write(A, tl, k0, e, tile);
+}
+// obst [B, N+1, 6], rsum [B, N+1, 3] -> the packed rows; one thread per (instance, stage)
+__global__ void __launch_bounds__(256) k_sized_pack(const double* obst, const double* rsum, double* rows, const size_t n) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) sized_pack(obst, rsum, rows, e);
 }
 
 // debug/trace helper: gather 8 per-instance scalar rows into a contiguous [8][B] buffer
@@ -2489,6 +2673,12 @@ __global__ void __launch_bounds__(256) k_loop_traffic(const LoopTrafficArgs A, c
     const int t = blockIdx.x * blockDim.x + threadIdx.x, S = A.N + 1;
     if (t < A.B * S) loop_traffic_stage(A, t / S, t % S, i);
 }
+// ... through traffic of mixed sizes (loop_traffic_stage_sized): the same grid; the selection by clearance, the row written packed for the sized solve
+__global__ void __launch_bounds__(256) k_loop_traffic_sized(const LoopTrafficSizedArgs A, const int i) {
+    if (A.T.abort_flag != nullptr && *A.T.abort_flag != 0u) return;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, S = A.T.N + 1;
+    if (t < A.T.B * S) loop_traffic_stage_sized(A, t / S, t % S, i);
+}
 
 // The stepping session (mpc_closed_loop.h: SessionIngestArgs, SessionTrafficArgs).  Before solve i >= 1: one ego per thread takes its measured state
 __global__ void __launch_bounds__(128) k_session_ingest(const SessionIngestArgs A) {
@@ -2808,6 +2998,7 @@ enum Scratch : int {
     SCR_FT_STATE, SCR_FT_ZBAR, SCR_FT_PARAMS, SCR_FT_ZOUT, SCR_FT_FLAG,    // mpc_forces_closed_loop_batch_obst_dev: the rows of its solves (the same five)
     SCR_LOOP_OBST,                      // closed_loop_dev: the obstacle rows of a loop with per-ego obstacle tracks (k_loop_obst)
     SCR_LOOP_SEED, SCR_LOOP_GRAD,       // closed_loop_dev with gains: the unit seeds and the gradient rows of k_loop_gain
+    SCR_SIZED_ROWS,                     // solve_sized_dev: the packed rows (centres and radius sums of every stage) of a sized solve
     N_SCRATCH
 };
 
@@ -2830,7 +3021,7 @@ struct mpc_handle {
     // device workspace
     size_t cap_Bp = 0;
     bool ws_mailbox = false;            // the workspace carries the instance-major mailbox section (SolvePlan::mailbox at allocation time)
-    bool ws_obst_stages = false;        // ... its obstacle section holds six rows per stage (from the handle's first per-stage call on)
+    int ws_obst_stages = 0;             // ... its obstacle section holds six rows per stage (1, from the handle's first per-stage call on; 2: OBST_SIZED_ROWS, from its first sized call on)
     double* d_ws = nullptr;
     int32_t* d_iws = nullptr;
     double *d_LB = nullptr, *d_UB = nullptr;
@@ -2927,7 +3118,7 @@ struct DevTmp {
 // Params of a kernel that reads and writes caller rows of B instances, with the handle's workspace (what its last solve left) or without
 static Params rows_params(const mpc_handle* h, int32_t B, bool ws) {
     Params P;
-    fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, ws ? h->d_ws : nullptr, ws ? h->d_iws : nullptr, h->d_LB, h->d_UB, ws && h->ws_mailbox, ws && h->ws_obst_stages);
+    fill_params(P, h->hp, B, ((size_t)B + 63) / 64 * 64, 1, ws ? h->d_ws : nullptr, ws ? h->d_iws : nullptr, h->d_LB, h->d_UB, ws && h->ws_mailbox, ws ? h->ws_obst_stages : 0);
     return P;
 }
 // the grid of the kernels that run one thread per stage, NLP_OUT_THREADS / (N + 1) instances per workgroup
@@ -3034,7 +3225,7 @@ static int stage_loop(mpc_handle* h, const LoopIo& io, const Stage (&more)[M], D
 static void free_ws(mpc_handle* h) {
     if (h->d_ws) (void)hipFree(h->d_ws);
     if (h->d_iws) (void)hipFree(h->d_iws);
-    h->d_ws = nullptr; h->d_iws = nullptr; h->cap_Bp = 0; h->ws_mailbox = false; h->ws_obst_stages = false;
+    h->d_ws = nullptr; h->d_iws = nullptr; h->cap_Bp = 0; h->ws_mailbox = false; h->ws_obst_stages = 0;
 }
 static void free_io(mpc_handle* h) {
     void* ptrs[] = {h->d_x0, h->d_p, h->d_xout, h->d_kkt, h->d_status, h->d_iters};
@@ -3259,11 +3450,11 @@ static void count_abandoned_launch(mpc_handle* h) {
 }
 // the workspace for Bp rows, with the mailbox section if `mb` (SolvePlan::mailbox) and the per-stage obstacle section if `os` (a per-stage call;
 // the handle keeps it from then on)
-static int ensure_ws(mpc_handle* h, size_t Bp, bool mb, bool os) {
-    if (Bp <= h->cap_Bp && (!mb || h->ws_mailbox) && (!os || h->ws_obst_stages)) return MPC_OK;
+static int ensure_ws(mpc_handle* h, size_t Bp, bool mb, int os) {
+    if (Bp <= h->cap_Bp && (!mb || h->ws_mailbox) && os <= h->ws_obst_stages) return MPC_OK;
     const size_t Bp_req = Bp;
     Bp = std::max(Bp, h->cap_Bp);                      // (grow only: also when all that changes is the mailbox or the obstacle section)
-    os = os || h->ws_obst_stages;
+    os = std::max(os, h->ws_obst_stages);
     free_ws(h);
     WsLayout w = ws_layout(h->hp.desc.N, h->hp.desc.nx, Bp, mb, os);
     // (a handle that grew close to the limit WITHOUT the mailbox section and now needs one: what was asked for fits -- SolvePlan::max_rows
@@ -3345,16 +3536,38 @@ static hipError_t wait_stream(mpc_handle* h, hipStream_t stream) {
 //      returns (the abort word of the pipeline, the convergence poll, the restart after an abandoned launch)
 // the kernel instantiation of a launch, picked in one place per family; set_lds_limits enumerates the same functions' arguments
 // (masked / VAR 2: the reference's bound structure compiled in, else looked up at run time)
-template <int NX> static auto stage_kernel(bool small_wg, bool init, bool masked) {
-    if (small_wg) return init ? &k_stage<NX, true, 256> : masked ? &k_stage<NX, false, 256, REF_VM> : &k_stage<NX, false, 256>;
-    return init ? &k_stage<NX, true, 512> : masked ? &k_stage<NX, false, 512, REF_VM> : &k_stage<NX, false, 512>;
+// (sized: SolvePlan::sized -- the instantiations with a lower bound per circle row, never together with masked; named in one place, SizedK, which
+//  the pickers reach last: the compiler lays functions out in the order it first meets them, and the kernels of the other solves stay where they were)
+template <int NX> struct SizedK {
+    static auto stage(bool small_wg, bool init) {
+        if (small_wg) return init ? &k_stage<NX, true, 256, SIZED_VM> : &k_stage<NX, false, 256, SIZED_VM>;
+        return init ? &k_stage<NX, true, 512, SIZED_VM> : &k_stage<NX, false, 512, SIZED_VM>;
+    }
+    static auto wg(bool resc) { return resc ? &k_solve_wg_sized<NX, true> : &k_solve_wg_sized<NX>; }
+    static auto pipeline() { return &k_pipeline<NX, 4>; }
+    static auto start() { return &k_start_sized<NX>; }
+};
+template <int NX> static auto stage_kernel(bool small_wg, bool init, bool masked, bool sized = false) {
+    if (!sized) {
+        if (small_wg) return init ? &k_stage<NX, true, 256> : masked ? &k_stage<NX, false, 256, REF_VM> : &k_stage<NX, false, 256>;
+        return init ? &k_stage<NX, true, 512> : masked ? &k_stage<NX, false, 512, REF_VM> : &k_stage<NX, false, 512>;
+    }
+    return SizedK<NX>::stage(small_wg, init);
 }
-template <int NX> static auto wg_kernel(bool masked, bool resc) {
-    if (resc) return masked ? &k_solve_wg<NX, 2, true> : &k_solve_wg<NX, 0, true>;
-    return masked ? &k_solve_wg<NX, 2> : &k_solve_wg<NX, 0>;
+template <int NX> static auto wg_kernel(bool masked, bool resc, bool sized = false) {
+    if (!sized) {
+        if (resc) return masked ? &k_solve_wg<NX, 2, true> : &k_solve_wg<NX, 0, true>;
+        return masked ? &k_solve_wg<NX, 2> : &k_solve_wg<NX, 0>;
+    }
+    return SizedK<NX>::wg(resc);
 }
-template <int NX> static auto pipeline_kernel(bool help, bool masked) {      // (helping Riccati workers: in the masked variant only, SolvePlan::pipe_help)
-    return help ? &k_pipeline<NX, 2, true> : masked ? &k_pipeline<NX, 2> : &k_pipeline<NX, 0>;
+template <int NX> static auto pipeline_kernel(bool help, bool masked, bool sized = false) {      // (helping Riccati workers: in the masked variant only, SolvePlan::pipe_help)
+    if (!sized) return help ? &k_pipeline<NX, 2, true> : masked ? &k_pipeline<NX, 2> : &k_pipeline<NX, 0>;
+    return SizedK<NX>::pipeline();
+}
+template <int NX> static auto start_kernel(int32_t obst_mode) {      // (a per-stage solve: the twin whose start iterate reads the stage's own obstacle rows; a sized one: its rows' offsets too)
+    if (obst_mode != OBST_PER_STAGE_SIZED) return obst_mode == OBST_PER_STAGE ? &k_start<NX, true> : &k_start<NX>;
+    return SizedK<NX>::start();
 }
 // per handle: the dynamic-LDS limit belongs to the function object of the handle's device
 template <int NX> static int set_lds_limits(mpc_handle* h, size_t ric_lds) {
@@ -3365,6 +3578,12 @@ template <int NX> static int set_lds_limits(mpc_handle* h, size_t ric_lds) {
             fs.push_back(reinterpret_cast<const void*>(wg_kernel<NX>(a, b)));
             fs.push_back(reinterpret_cast<const void*>(pipeline_kernel<NX>(a, b)));
         }
+    for (int a = 0; a < 2; ++a) {
+        for (int b = 0; b < 2; ++b) fs.push_back(reinterpret_cast<const void*>(stage_kernel<NX>(a, b, false, true)));
+        fs.push_back(reinterpret_cast<const void*>(wg_kernel<NX>(false, a, true)));
+    }
+    fs.push_back(reinterpret_cast<const void*>(pipeline_kernel<NX>(false, false, true)));
+    fs.push_back(reinterpret_cast<const void*>(start_kernel<NX>(OBST_PER_STAGE_SIZED)));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_riccati<NX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ric_lds));
     for (const void* kf : fs) HIP_TRY(h, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
     h->attr_set = true;
@@ -3398,7 +3617,7 @@ template <class F> static hipError_t report_stamps(const unsigned long long* d_r
 template <int NX> static void launch_stage(const Solve& s, const Group& q, bool init) {
     Params Pg = s.P;
     Pg.tile0 = q.tile0;
-    const auto kf = stage_kernel<NX>(s.pl.small_wg, init, s.pl.masked);
+    const auto kf = stage_kernel<NX>(s.pl.small_wg, init, s.pl.masked, s.pl.sized);
     hipLaunchKernelGGL(kf, dim3(q.nblk), dim3(s.pl.threads), init ? s.pl.lds_init : s.pl.lds_bytes, q.st, Pg, s.h->hp.n_mult, s.h->hp.n_z, s.pl.stash_rows);
 }
 // k_solve_wg: alone over every instance, or behind the pipeline (skip_if: its abort word) over the instances on the hand-over lists (list, list_n)
@@ -3419,7 +3638,7 @@ template <int NX> static void launch_wg(Solve& s, const uint32_t* skip_if, const
         s.out.resc_in_kernel = list == nullptr;
     }
     // (one wavefront per workgroup -- S * hyb_bx <= 64: checked where the path is chosen; its statistics and the lists' counters: words of the control block)
-    const auto kf = wg_kernel<NX>(pl.masked, pl.wg_resc);
+    const auto kf = wg_kernel<NX>(pl.masked, pl.wg_resc, pl.sized);
     hipLaunchKernelGGL(kf, dim3(pl.wg_grid), dim3(64), pl.wg_lds, s.stream, Pw, h->hp.n_mult, h->hp.n_z, pl.stash_rows, s.ctl + PIPE_WG, skip_if, rs, s.t_wtrace.as<unsigned long long>(), list,
                        list != nullptr ? (const uint32_t*)(s.ctl + PIPE_HO) : nullptr);
 }
@@ -3474,6 +3693,10 @@ static int solve_front(Solve& s) {
     if (P.per_inst_obst == OBST_PER_STAGE) {          // (solve_dev_impl has asked ensure_ws for the section)
         const ObstXpose X{io.obst, h->d_ws + w.OBST * 64, B, d.N + 1, (uint32_t)w.tile_elems};
         hipLaunchKernelGGL(k_transpose_obst_stages, dim3(ntiles, (d.N + OBST_XP_KC) / OBST_XP_KC), dim3(256), 0, stream, X);
+    }
+    if (P.per_inst_obst == OBST_PER_STAGE_SIZED) {    // (io.obst: the packed rows; a level of the second chance scales the rows' offsets by its fraction)
+        const ObstXposeSized X{io.obst, h->d_ws + w.OBST * 64, B, d.N + 1, (uint32_t)w.tile_elems, h->hp.ol_raw, BOUND_RELAX, s.call.level ? s.call.level->frac : 1.0};
+        hipLaunchKernelGGL(k_transpose_obst_sized, dim3(ntiles, (d.N + OBST_XS_KC) / OBST_XS_KC), dim3(256), 0, stream, X);
     }
     if (!h->attr_set) { const int rc = set_lds_limits<NX>(h, pl.ric_lds); if (rc) return rc; }
     for (int g = 0; g < G; ++g) {
@@ -3530,8 +3753,7 @@ static int solve_front(Solve& s) {
             // (one launch for ingest, safeguard and start iterate: same blocks, same threads)
             DevTmp t_sdbg;
             if (pl.start_timing && stamp_rows(t_sdbg, q.nblk, q.st) == hipSuccess) Pg.DBG = t_sdbg.as<unsigned long long>();
-            // (a per-stage solve: the twin whose start iterate reads the stage's own obstacle rows)
-            const auto kf = P.per_inst_obst == OBST_PER_STAGE ? &k_start<NX, true> : &k_start<NX>;
+            const auto kf = start_kernel<NX>(P.per_inst_obst);
             hipLaunchKernelGGL(kf, dim3(q.nblk), dim3(pl.threads), pl.lds_start, q.st, Pg, h->hp.n_mult, h->hp.n_z, pl.stash_rows,
                                g == 0 ? zero_next : (uint32_t*)nullptr, (uint32_t)ctl_words);
             if (g == 0 && zero_next != nullptr) next_zeroed = true;
@@ -3587,7 +3809,7 @@ template <int NX> static int solve_pipeline(Solve& s) {
     P.DBG = t_pdbg.as<unsigned long long>();
     s.prof.next(3, stream);
     P.mbw_live = pl.mbw_live;
-    const auto kf = pipeline_kernel<NX>(pl.pipe_help, pl.masked);
+    const auto kf = pipeline_kernel<NX>(pl.pipe_help, pl.masked, pl.sized);
     hipLaunchKernelGGL(kf, dim3(h->n_cu), dim3(pl.threads), std::max(pl.lds_bytes, pl.ric_lds), stream, P, A, h->hp.n_mult, h->hp.n_z, pl.stash_rows);
     if (pl.hand > 0) {
         if (!h->prof_span) s.prof.next(5, stream);          // (span mode: the pipeline's span stays open over k_solve_wg)
@@ -3748,7 +3970,7 @@ static int solve_dev_impl(mpc_handle* h, const SolveIo& io, const SolveCall& cal
     s.pl = plan_solve(h->hp, h->knobs, ps);
     // tile-major layout: the rows of a tile do not depend on the batch size, so a smaller batch lives in the first tiles of
     // a larger allocation (grow-only; the rescue path alternates between the full batch and a failed subset)
-    int rc = ensure_ws(h, (size_t)s.pl.ntiles * 64, s.pl.mailbox, io.obst_mode() == OBST_PER_STAGE); if (rc) return rc;
+    int rc = ensure_ws(h, (size_t)s.pl.ntiles * 64, s.pl.mailbox, io.obst_section()); if (rc) return rc;
     if (ps.ws_mailbox != h->ws_mailbox) { ps.ws_mailbox = h->ws_mailbox; s.pl = plan_solve(h->hp, h->knobs, ps); }
     if ((rc = solve_front<NX>(s))) return rc;
     rc = s.pl.res_path ? solve_wg_alone<NX>(s) : s.pl.pipe_path ? solve_pipeline<NX>(s) : solve_per_kernel<NX>(s);
@@ -3773,7 +3995,7 @@ static int solve_dev_any(mpc_handle* h, const SolveIo& io, const SolveCall& call
 // ---- multipliers of a solve (mpc_solve_batch_ex): read back from the workspace behind the solve, the loop kernels are not touched -------
 // Before a solve whose multipliers will be read: the workspace in place (what solve_dev_impl would allocate) and the mailbox copy of the
 // iterate NaN, so that k_mult_out tells by the primal rows which instances k_solve_wg served in THIS solve.
-static int mult_prepare(mpc_handle* h, int32_t B, bool obst_stages, hipStream_t stream) {
+static int mult_prepare(mpc_handle* h, int32_t B, int obst_stages, hipStream_t stream) {
     const mpc_problem_desc& d = h->hp.desc;
     const size_t Bp = ((size_t)B + 63) / 64 * 64;
     const int rc = ensure_ws(h, Bp, plan_solve(h->hp, h->knobs, plan_state(h, B, OBST_SHARED, false)).mailbox, obst_stages);
@@ -3848,8 +4070,8 @@ static int rescue_dev(mpc_handle* h, const SolveIo& io, hipStream_t stream, int&
             const bool last = q + 1 == nfr;             // (the original problem; the levels before it only produce warm starts)
             // (... as hp holds it: relax_lo(1.0 * ol_raw) is hp.ol by set_bound_rows, the tolerance hp.desc.tol -- so mult_prepare, mult_read and
             //  sens_read, which build their Params from hp, read the last level's solve with the bound and the tolerance it ran with)
-            const Level level{relax_lo(fr[q] * h->hp.ol_raw), last ? h->hp.desc.tol : std::max(h->hp.desc.tol, 1e-4)};
-            if ((sub.lam_g || sub.snap) && last) rc = mult_prepare(h, n, sub.obst_mode() == OBST_PER_STAGE, stream);
+            const Level level{relax_lo(fr[q] * h->hp.ol_raw), last ? h->hp.desc.tol : std::max(h->hp.desc.tol, 1e-4), fr[q]};
+            if ((sub.lam_g || sub.snap) && last) rc = mult_prepare(h, n, sub.obst_section(), stream);
             if (rc != MPC_OK) break;
             rc = solve_dev_any(h, sub, SolveCall{stream, &level, false}, last_level);
             if (rc == MPC_OK && sub.lam_g && last) rc = mult_read(h, sub, stream);
@@ -3879,8 +4101,8 @@ static int solve_dev(mpc_handle* h, SolveIo io, hipStream_t stream) {
     h->rescued_last = 0;
     SolvePlan pl = plan_solve(h->hp, h->knobs, plan_state(h, B, io.obst_mode(), io.trace.out != nullptr));
     // (per-stage obstacle rows: the plan is the per-instance one; the workspace limit of the chunks counts the larger obstacle section)
-    if (io.obst_mode() == OBST_PER_STAGE)
-        pl.max_rows = std::min(pl.max_rows, (((size_t)1 << 32) - 1) / (ws_layout(h->hp.desc.N, h->hp.desc.nx, 64, pl.mailbox, true).total * sizeof(double)) * 64);
+    if (io.obst_section() || h->ws_obst_stages)       // (the section the workspace will have: the call's, or a larger one the handle has grown already)
+        pl.max_rows = std::min(pl.max_rows, (((size_t)1 << 32) - 1) / (ws_layout(h->hp.desc.N, h->hp.desc.nx, 64, pl.mailbox, std::max(io.obst_section(), h->ws_obst_stages)).total * sizeof(double)) * 64);
     // the second chance and the multipliers read the per-instance status
     if (pl.rescue || io.lam_g) { const int rs = supply_status(h, io); if (rs) return rs; }
     // The workspace is addressed with 32-bit buffer offsets (< 4 GiB): a batch beyond that is solved in chunks of whole tiles, one after
@@ -3895,7 +4117,7 @@ static int solve_dev(mpc_handle* h, SolveIo io, hipStream_t stream) {
         h->rescued_last = rescued;
         return MPC_OK;
     }
-    if (io.lam_g || io.snap) { const int rm = mult_prepare(h, B, io.obst_mode() == OBST_PER_STAGE, stream); if (rm) return rm; }
+    if (io.lam_g || io.snap) { const int rm = mult_prepare(h, B, io.obst_section(), stream); if (rm) return rm; }
     SolveOutcome out;
     int rc = solve_dev_any(h, io, SolveCall{stream}, out);
     keep_outcome(h, out);
@@ -3971,6 +4193,36 @@ static int solve_ex_dev(mpc_handle* h, SolveIo io, double* d_f, double* d_g, hip
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));
     return MPC_OK;
+}
+
+// ---- a solve with a lower bound per circle row (mpc_solve_batch_sized[_dev]) -----------------------------------------------------------
+// what its entry points start with: begin_solve, the two row arguments, and the handle's bound structure -- a row of its own replaces the
+// lower side of a row that has one and no upper side, the structure the reference sets; for any other a sized row has no meaning
+static int begin_sized(mpc_handle* h, const SolveIo& io, const double* rsum) {
+    const int rc = begin_solve(h, io, io.obst && rsum ? nullptr : "sized solve: obst [B, N+1, 6] and rsum [B, N+1, 3] are required");
+    if (rc) return rc;
+    if (!h->hp.has_ol || h->hp.has_ou) {
+        h->err = "sized solve: the circle rows of the handle need a lower bound and no finite upper bound (mpc_set_bounds)";
+        return MPC_ERR_BOUNDS;
+    }
+    return MPC_OK;
+}
+// io as of a per-stage solve (obst [B, N+1, 6]); d_rsum [B, N+1, 3].  The two are packed into one row per instance (sized_pack), which the chain
+// treats as it treats the obstacle rows of any solve: chunks cut it, the second chance's gather copies it.  f / g are the NLP's own -- the literal
+// distances -- at the returned x: mpc_eval_nlp_batch_stages' bits.
+static int solve_sized_dev(mpc_handle* h, SolveIo io, const double* d_rsum, double* d_f, double* d_g, hipStream_t s) {
+    const size_t S = (size_t)h->hp.desc.N + 1, ne = (size_t)io.B * S;
+    double* rows = static_cast<double*>(scratch_get(h, SCR_SIZED_ROWS, ne * OBST_SIZED_ROWS * 8));
+    if (!rows) { h->err = "out of device memory"; return MPC_ERR_HIP; }
+    const double* d_obst = io.obst;
+    hipLaunchKernelGGL(k_sized_pack, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, d_obst, d_rsum, rows, ne);
+    io.obst = rows; io.n_obst = S * OBST_SIZED_ROWS; io.sized = true;
+    int rc = solve_ex_dev(h, io, nullptr, nullptr, s);
+    if (rc == MPC_OK && (d_f || d_g)) {
+        rc = eval_nlp_dev(h, io.B, io.x_out, io.p, d_obst, true, d_f, d_g, s);
+        if (rc == MPC_OK) HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    return rc;
 }
 
 // ---- parametric sensitivities -----------------------------------------------------------------------------------
@@ -4131,6 +4383,26 @@ int mpc_solve_batch_stages(mpc_handle* h, int32_t B, const double* x0, const dou
     if (rc) return rc;
     return stage_solve(h, io, {{f, (size_t)B * 8, true}, {g, (size_t)B * io.n_g * 8, true}},
                        [&](const SolveIo& dio, void** m, hipStream_t s) { return solve_ex_dev(h, dio, (double*)m[0], (double*)m[1], s); });
+}
+
+// mpc_solve_batch_stages[_dev] with a lower bound per circle row, rsum [B, N+1, 3] (required) behind obst.  No snapshot either.
+int mpc_solve_batch_sized_dev(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, const double* d_rsum, double* d_x_out,
+                              int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_f, double* d_g, double* d_lam_g, double* d_lam_x,
+                              void* stream_) {
+    const SolveIo io = stages_io(h, solve_io(h, B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt, d_lam_g, d_lam_x));
+    const int rc = begin_sized(h, io, d_rsum);
+    return rc ? rc : solve_sized_dev(h, io, d_rsum, d_f, d_g, (hipStream_t)stream_);
+}
+int mpc_solve_batch_sized(mpc_handle* h, int32_t B, const double* x0, const double* p, const double* obst, const double* rsum, double* x_out,
+                          int32_t* status, int32_t* iters, double* kkt, double* f, double* g, double* lam_g, double* lam_x) {
+    const SolveIo io = stages_io(h, solve_io(h, B, x0, p, obst, x_out, status, iters, kkt, lam_g, lam_x));
+    int rc = begin_sized(h, io, rsum);
+    if (rc) return rc;
+    const size_t nr = (size_t)B * 3 * (size_t)(h->hp.desc.N + 1);
+    for (size_t i = 0; i < nr; ++i)
+        if (!(std::isfinite(rsum[i]) && rsum[i] >= 0.0)) { h->err = "sized solve: every entry of rsum must be finite and >= 0"; return MPC_ERR_INVALID; }
+    return stage_solve(h, io, {{f, (size_t)B * 8, true}, {g, (size_t)B * io.n_g * 8, true}, {rsum, nr * 8, false}},
+                       [&](const SolveIo& dio, void** m, hipStream_t s) { return solve_sized_dev(h, dio, (const double*)m[2], (double*)m[0], (double*)m[1], s); });
 }
 
 int mpc_solve_batch_dev_ex(mpc_handle* h, int32_t B, const double* d_x0, const double* d_p, const double* d_obst, double* d_x_out,
@@ -4300,12 +4572,14 @@ static int closed_loop_dev(mpc_handle* h, const LoopIo& lo, hipStream_t stream) 
     double* d_obst = nullptr;
     const bool traffic = lo.M > 0;                                    // (centres per stage, as the predicted loop)
     const bool predict = lo.predict != 0 || traffic;
-    const size_t n_obst = predict ? (size_t)6 * (size_t)(d.N + 1) : 6;
+    const bool sized = traffic && lo.rsums != nullptr;                // (every solve a sized one; the rows packed by k_loop_traffic_sized)
+    const size_t n_obst = sized ? (size_t)OBST_SIZED_ROWS * (size_t)(d.N + 1) : predict ? (size_t)6 * (size_t)(d.N + 1) : 6;
     if (lo.tracked && !(d_obst = static_cast<double*>(scratch_get(h, SCR_LOOP_OBST, (size_t)B * n_obst * sizeof(double))))) { h->err = "out of device memory"; return MPC_ERR_HIP; }
     // the rows of every solve of the loop: the handle's own (begin_solve: the bounds must be set)
     SolveIo io = solve_io(h, B, h->d_x0, h->d_p, d_obst, h->d_xout, h->d_status, h->d_iters, h->d_kkt);
     if (predict) io = stages_io(h, io);
-    if ((rc = begin_solve(h, io))) return rc;
+    if (sized) { io.n_obst = n_obst; io.sized = true; }
+    if ((rc = sized ? begin_sized(h, io, lo.rsums) : begin_solve(h, io))) return rc;
     if (h->cap_state < (size_t)B) {
         if (h->d_state) (void)hipFree(h->d_state);
         h->d_state = nullptr;
@@ -4326,8 +4600,10 @@ static int closed_loop_dev(mpc_handle* h, const LoopIo& lo, hipStream_t stream) 
         PO.ego_offset = d.ego_offset;
     }
     LoopTrafficArgs T = traffic ? loop_traffic_args(h, lo, d_obst, A) : LoopTrafficArgs{};
+    LoopTrafficSizedArgs TS{T, lo.rsums};
     const auto place_obstacles = [&](int i) {
-        if (traffic) { T.abort_flag = O.abort_flag; hipLaunchKernelGGL(k_loop_traffic, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, T, i); }
+        if (sized) { TS.T.abort_flag = O.abort_flag; hipLaunchKernelGGL(k_loop_traffic_sized, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, TS, i); }
+        else if (traffic) { T.abort_flag = O.abort_flag; hipLaunchKernelGGL(k_loop_traffic, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, T, i); }
         else if (predict) hipLaunchKernelGGL(k_loop_obst_stages, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, PO, O, d.N, i);
         else if (lo.tracked) hipLaunchKernelGGL(k_loop_obst, grid, block, 0, stream, PO, O, i);
     };
@@ -4507,6 +4783,48 @@ int mpc_closed_loop_batch_traffic(mpc_handle* h, int32_t B, int32_t L, int32_t L
                                   int32_t* nearest, int32_t* chosen) {
     const LoopIo io{B, L, Lp, init_state, path, orient, vdes, noise_mode, sigma, seed, traj, ctrl, step_status};
     return loop_entry(h, with_traffic(io, M, Lt, per_ego, tracks, offsets, pairing, clearance, nearest, chosen), bad_traffic, true, nullptr, traffic_loop_dev);
+}
+
+// ... of mixed sizes: rsums [M] (per_ego: [B, M]) behind offsets, the radius sum of ego and obstacle m; checked as the offsets are, and >= 0
+static const char* bad_traffic_sized(const mpc_handle* h, const LoopIo& io) {
+    if (const char* bad = bad_traffic(h, io)) return bad;
+    return io.rsums ? nullptr : "sized traffic loop: rsums [M] (per_ego: [B, M]) are required";
+}
+static int traffic_sized_loop_dev(mpc_handle* h, const LoopIo& io, hipStream_t stream) {
+    if (io.B <= 0) { h->err = "closed loop: B > 0 is required"; return MPC_ERR_INVALID; }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (const int rc = offsets_finite(h, io, stream, "traffic loop: every offset must be finite")) return rc;
+    std::vector<double> rs((size_t)(io.per_ego ? io.B : 1) * (size_t)io.M);
+    HIP_TRY(h, hipMemcpyAsync(rs.data(), io.rsums, rs.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    for (double v : rs)
+        if (!(std::isfinite(v) && v >= 0.0)) { h->err = "sized traffic loop: every entry of rsums must be finite and >= 0"; return MPC_ERR_INVALID; }
+    return closed_loop_dev(h, io, stream);
+}
+int mpc_closed_loop_batch_traffic_sized_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                            const double* d_orient, const double* d_vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* d_tracks,
+                                            const double* d_offsets, const double* d_rsums, int32_t pairing, int32_t noise_mode, double sigma, uint64_t seed,
+                                            double* d_traj, double* d_ctrl, int32_t* d_step_status, double* d_clearance, int32_t* d_nearest, int32_t* d_chosen,
+                                            void* stream_) {
+    LoopIo io = with_traffic(LoopIo{B, L, Lp, d_init_state, d_path, d_orient, d_vdes, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status}, M, Lt, per_ego,
+                             d_tracks, d_offsets, pairing, d_clearance, d_nearest, d_chosen);
+    io.rsums = d_rsums;
+    return loop_entry(h, io, bad_traffic_sized, false, stream_, traffic_sized_loop_dev);
+}
+int mpc_closed_loop_batch_traffic_sized(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                                        const double* vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* tracks, const double* offsets,
+                                        const double* rsums, int32_t pairing, int32_t noise_mode, double sigma, uint64_t seed, double* traj, double* ctrl,
+                                        int32_t* step_status, double* clearance, int32_t* nearest, int32_t* chosen) {
+    if (!h) return MPC_ERR_INVALID;
+    LoopIo io = with_traffic(LoopIo{B, L, Lp, init_state, path, orient, vdes, noise_mode, sigma, seed, traj, ctrl, step_status}, M, Lt, per_ego, tracks, offsets,
+                             pairing, clearance, nearest, chosen);
+    io.rsums = rsums;
+    const char* bad = bad_traffic_sized(h, io);
+    if (!bad) bad = loop_refusal(io, h->hp.desc.N);
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    const size_t nr = (size_t)(per_ego ? B : 1) * (size_t)M;
+    const Stage more[1] = {{rsums, nr * sizeof(double), false}};
+    return stage_loop(h, io, more, [&](LoopIo dio, void** m, hipStream_t s) { dio.rsums = static_cast<const double*>(m[0]); return traffic_sized_loop_dev(h, dio, s); });
 }
 
 // the loop with per-step gains: Lt = 0 with a null track is the plain loop (ogain must then be null); no gain asked for: the loop it wraps

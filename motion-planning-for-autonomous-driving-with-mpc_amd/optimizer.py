@@ -88,16 +88,25 @@ def compute_centers_of_approximation_circles(x_position, y_position, v_length, v
     return center, center_fw, center_rw
 
 
-def nearest_obstacle_centres(poses, tracks, offsets, rows, ego_offset, pairing, default):
+def nearest_obstacle_centres(poses, tracks, offsets, rows, ego_offset, pairing, default, rsums=None, r_default=None):
     """The selection of the loop through traffic (csrc/mpc_closed_loop.h, loop_traffic_stage; include/mpcgpu.h, mpc_closed_loop_batch_traffic) for one
     ego, in numpy: poses [K, 3] = predicted (x, y, psi) of the K stages, tracks [M, Lt, 3] (NaN x: absent), offsets [M], rows [K] = the track row every
     stage sees, default [6] = the centres of a stage that sees no obstacle -> (centres [K, 6], chosen [K, 3]; -1: none).
     pairing 0: the present obstacle with the smallest min_j |E_j - O_{m,j}| gives all three centres; 1: slot j is the circle nearest to ego circle j
-    over all present obstacles and circles.  Ties go to the lowest obstacle, then the lowest circle."""
+    over all present obstacles and circles.  Ties go to the lowest obstacle, then the lowest circle.
+    rsums [M] (optional; with r_default, the handle's radius sum): obstacles of their own sizes -- the selection is by CLEARANCE, every distance
+    above less delta_m = rsums[m] - r_default, and a third value comes back: radii [K, 3], the winner's rsums[m] per slot (r_default where
+    nothing is present) -- obst [K, 6] and rsum [K, 3] of one instance of BatchedMPCSolver.solve(..., rsum=).  With every rsums[m] equal to
+    r_default the centres and `chosen` are those of the call without it."""
     def circles(x, y, th, off):
         return np.array([[x, y], [x + off * np.cos(th), y + off * np.sin(th)], [x - off * np.cos(th), y - off * np.sin(th)]])
     K = len(poses)
     out, chosen = np.tile(np.asarray(default, dtype=np.float64), (K, 1)).reshape(K, 3, 2), np.full((K, 3), -1, dtype=np.int32)
+    sized = rsums is not None
+    if sized and r_default is None:
+        raise ValueError("nearest_obstacle_centres: rsums needs r_default, the radius sum of a stage that sees no obstacle")
+    delta = np.asarray(rsums, dtype=np.float64) - r_default if sized else np.zeros(len(tracks))
+    radii = np.full((K, 3), r_default if sized else np.nan)
     for k in range(K):
         E = circles(poses[k][0], poses[k][1], poses[k][2], ego_offset)
         best = np.full(3, np.inf)
@@ -107,16 +116,20 @@ def nearest_obstacle_centres(poses, tracks, offsets, rows, ego_offset, pairing, 
                 continue
             O = circles(x, y, th, offsets[m])
             if pairing == 0:
-                score = min(np.hypot(*(E[j] - O[j])) for j in range(3))
+                score = min(np.hypot(*(E[j] - O[j])) for j in range(3)) - delta[m]
                 if chosen[k, 0] < 0 or score < best[0]:
                     best[0], chosen[k], out[k] = score, m, O
+                    if sized:
+                        radii[k] = rsums[m]
             else:
                 for j in range(3):
                     for c in range(3):
-                        dist = np.hypot(*(E[j] - O[c]))
+                        dist = np.hypot(*(E[j] - O[c])) - delta[m]
                         if chosen[k, j] < 0 or dist < best[j]:
                             best[j], chosen[k, j], out[k, j] = dist, m, O[c]
-    return out.reshape(K, 6), chosen
+                            if sized:
+                                radii[k, j] = rsums[m]
+    return (out.reshape(K, 6), chosen, radii) if sized else (out.reshape(K, 6), chosen)
 
 
 class VehicleDynamics:
@@ -159,9 +172,9 @@ class NlpSolverHandle:
         self._backend = backend
         self._stats = {}
 
-    def __call__(self, x0=None, p=None, lbg=None, lbx=None, ubg=None, ubx=None, obst=None, **_unused):
+    def __call__(self, x0=None, p=None, lbg=None, lbx=None, ubg=None, ubx=None, obst=None, rsum=None, **_unused):
         """obst (not a CasADi keyword): circle centres [6] / [B, 6] of this solve's obstacle instead of the template's, or [N+1, 6] / [B, N+1, 6]:
-        centres per stage (BatchedMPCSolver.solve)"""
+        centres per stage (BatchedMPCSolver.solve); rsum (with centres per stage): [N+1, 3] / [B, N+1, 3], a radius sum per circle row"""
         be = self._backend
         x0a = np.asarray(x0.full() if hasattr(x0, "full") else x0, dtype=np.float64)
         pa = np.asarray(p.full() if hasattr(p, "full") else p, dtype=np.float64)
@@ -177,6 +190,8 @@ class NlpSolverHandle:
         if obst is not None:
             oa = np.asarray(obst, dtype=np.float64)
             kw = dict(obst=oa.reshape(x0a.shape[0], 6) if oa.size == 6 * x0a.shape[0] else oa.reshape(x0a.shape[0], -1, 6))
+            if rsum is not None:
+                kw["rsum"] = np.asarray(rsum, dtype=np.float64).reshape(x0a.shape[0], -1, 3)
         res = be.solve(x0a, pa, multipliers=True, **kw) if full else be.solve(x0a, pa, **kw)
         rescued = np.zeros(res.status.shape[0], dtype=bool)
         n_rescued = int(be.last_rescued()) if hasattr(be, "last_rescued") else 0      # the second chance behind the C-ABI (a count, not a mask)
@@ -236,7 +251,7 @@ class Optimizer(object):
         # optional (not in the reference): traffic.  obstacle_tracks [M, L, 3] = the pose of M obstacles at every loop step (NaN x: absent at that step),
         # obstacle_sizes [M, 2] = their lengths and widths; obstacle_pairing 0 / 1 (nearest_obstacle_centres).  Every stage of every solve avoids the
         # obstacle nearest to it (mpc_closed_loop_batch_traffic).  The circle centres of obstacle m lie +- disc_distance / 4 of ITS rectangle along its
-        # heading; a handle has ONE radius, so the lower bound of the circle rows (lbg) is that of the LARGEST obstacle, held against all of them.
+        # heading; by default ONE radius: the lower bound of the circle rows (lbg) is that of the LARGEST obstacle, held against all of them (obstacle_radii below).
         # `obstacle_sizes` without tracks: what open_session() needs -- its caller observes the obstacles step by step and has no tracks to give.
         tracks = getattr(configuration, "obstacle_tracks", None)
         sizes = getattr(configuration, "obstacle_sizes", None)
@@ -249,6 +264,15 @@ class Optimizer(object):
                     raise ValueError("obstacle_tracks must be [M, L, 3] with obstacle_sizes [M, 2]")
             self.obstacle_offsets = np.array([compute_approximating_circle_radius(l, w)[1] / 4 for l, w in sizes])
             self.radius_obstacle = max(compute_approximating_circle_radius(l, w)[0] for l, w in sizes)
+            # obstacle_radii (opt-in): "largest", the default -- the one radius above; "own" -- every obstacle with the radius of ITS rectangle: the
+            # loops select by clearance and every solve is a sized one (mpc_closed_loop_batch_traffic_sized, BatchedMPCSolver.solve(rsum=)); lbg keeps
+            # the largest radius, which a stage that sees no obstacle is held to
+            self.obstacle_radii = str(getattr(configuration, "obstacle_radii", "largest"))
+            if self.obstacle_radii not in ("largest", "own"):
+                raise ValueError('obstacle_radii is "largest" or "own"')
+            self.obstacle_rsums = None
+            if self.obstacle_radii == "own":
+                self.obstacle_rsums = np.array([compute_approximating_circle_radius(l, w)[0] for l, w in sizes]) + self.radius_ego
             self.obstacle_pairing = int(getattr(configuration, "obstacle_pairing", 0))
         self.nearest = self.chosen = None           # optimize() through traffic: the nearest obstacle of every step (device loop), the obstacle behind every slot
         self.clearance = None           # optimize() with a track, device loop: distance - r_sum of every step (include/mpcgpu.h, mpc_closed_loop_batch_obst)
@@ -281,7 +305,8 @@ class CasadiOptimizer(Optimizer):
     Not in the reference: a configuration with `obstacle_tracks` [M, L, 3] (NaN x: absent at that step) and `obstacle_sizes` [M, 2] is driven through
     traffic -- every stage of every solve avoids the obstacle nearest to it (BatchedMPCSolver.closed_loop_traffic; `obstacle_pairing` 0 / 1), on the
     device and, with the same selection in numpy, in the step-by-step host loop.  The circle offsets are each obstacle's own (disc_distance / 4 of
-    its rectangle).  A handle has ONE radius: the lower bound of the circle rows (lbg) is that of the largest obstacle, held against all of them."""
+    its rectangle).  By default one radius: the lower bound of the circle rows (lbg) is that of the largest obstacle, held against all of them;
+    `obstacle_radii = "own"` plans around every obstacle at its own size (mpc_closed_loop_batch_traffic_sized)."""
 
     num_states = 5
     num_controls = 2
@@ -354,7 +379,8 @@ class CasadiOptimizer(Optimizer):
                 # through traffic: every stage of every solve sees the obstacle nearest to it (mpc_closed_loop_batch_traffic)
                 traj, ctrl, st, cl, near, chosen = backend.closed_loop_traffic(init_state, self.resampled_path_points, self.orientation, self.desired_velocity,
                                                                                 self.iter_length, self.traffic_rows(), self.obstacle_offsets,
-                                                                                pairing=self.obstacle_pairing, **loop_kw)
+                                                                                pairing=self.obstacle_pairing,
+                                                                                **({} if self.obstacle_rsums is None else dict(rsums=self.obstacle_rsums)), **loop_kw)
                 self.clearance, self.nearest, self.chosen = cl[0], near[0], chosen[0]
             elif self.obstacle_track is None:
                 traj, ctrl, st = backend.closed_loop(init_state, self.resampled_path_points, self.orientation, self.desired_velocity, self.iter_length, **loop_kw)
@@ -383,8 +409,9 @@ class CasadiOptimizer(Optimizer):
             if self.obstacle_tracks is not None:
                 # through traffic, the host twin of k_loop_traffic: stage k against the obstacles at time step + k, seen from the measured state at step 0
                 # and from the shifted last plan afterwards
-                centres, picked = self.traffic_centres(step, np.tile(x_now[[0, 1, 4]], (N + 1, 1)) if step == 0 else plan_x[[0, 1, 4]].T)
-                obst_kw = dict(obst=centres)
+                placed = self.traffic_centres(step, np.tile(x_now[[0, 1, 4]], (N + 1, 1)) if step == 0 else plan_x[[0, 1, 4]].T)
+                centres, picked = placed[0], placed[1]
+                obst_kw = dict(obst=centres) if len(placed) == 2 else dict(obst=centres, rsum=placed[2])
                 chosen_log.append(picked)
             w = sol(x0=w0, p=p_vec, lbg=lbg, lbx=lbx, ubg=ubg, ubx=ubx, **obst_kw)["x"].full().ravel()
             seconds.append(time.time() - tic)
@@ -430,10 +457,12 @@ class CasadiOptimizer(Optimizer):
         return tr[:, np.minimum(np.arange(self.iter_length), tr.shape[1] - 1)]
 
     def traffic_centres(self, step, poses):
-        """(centres [N+1, 6], chosen [N+1, 3]) of the solve of loop step `step` for the predicted ego poses [N+1, 3] (x, y, psi) of its stages"""
+        """(centres [N+1, 6], chosen [N+1, 3]) of the solve of loop step `step` for the predicted ego poses [N+1, 3] (x, y, psi) of its stages; with
+        obstacle_radii = "own" the selection is by clearance and the slots' radius sums [N+1, 3] come third"""
         tr = self.traffic_rows()
+        own = {} if self.obstacle_rsums is None else dict(rsums=self.obstacle_rsums, r_default=self.radius_obstacle + self.radius_ego)
         return nearest_obstacle_centres(poses, tr, self.obstacle_offsets, np.minimum(step + np.arange(len(poses)), tr.shape[1] - 1), self.ego_offset(),
-                                        self.obstacle_pairing, np.array(self.obstacle_circles_centers_tuple, dtype=np.float64).ravel())
+                                        self.obstacle_pairing, np.array(self.obstacle_circles_centers_tuple, dtype=np.float64).ravel(), **own)
 
     @staticmethod
     def shift(plan):

@@ -257,22 +257,35 @@ class BatchedMPCSolver:
         self._check(fn(self._h, B, _abi.as_dp(x), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(f), _abi.as_dp(g)))
         return f, g
 
-    def solve(self, x0, p, obst=None, *, multipliers=False, lam_p=False, dp=None) -> SolveResult:
+    def solve(self, x0, p, obst=None, *, multipliers=False, lam_p=False, dp=None, rsum=None) -> SolveResult:
         """B instances at once.  multipliers=True: also f, g at the returned x and the multipliers lam_g, lam_x (CasADi's convention:
         grad f + J_g' lam_g + lam_x = 0) in the result (mpc_solve_batch_ex).  lam_p=True: CasADi's lam_p; dp [B, n_dir, n_p] (or [B, n_p]):
         forward sensitivities dw = (dw*/dp) dp of the optimum (mpc_solve_batch_sens, which also keeps the final iterates for sens_adjoint).
         p = [U_ref | X_ref], n_p = n_w.  obst [B, 6]: obstacle centres per instance; [B, N+1, 6]: per instance and stage, an obstacle that
-        moves over the horizon (mpc_solve_batch_stages) -- no derivatives: lam_p / dp raise, and a later sens_* finds no snapshot."""
+        moves over the horizon (mpc_solve_batch_stages) -- no derivatives: lam_p / dp raise, and a later sens_* finds no snapshot.
+        rsum [B, N+1, 3] (with obst [B, N+1, 6]): a lower bound per circle row, rsum[b, k, j] for ego circle j against slot j of obst[b, k]
+        (mpc_solve_batch_sized); None is the call without it."""
         B, x0, p, obst = self._rows_in("x0", x0, p, obst)
         out = np.empty_like(x0)
         status = np.empty(B, np.int32)
         iters = np.empty(B, np.int32)
         kkt = np.empty(B, np.float64)
+        if rsum is not None:
+            if obst is None or obst.ndim != 3:
+                raise MpcError(_abi.MPC_ERR_INVALID, "rsum goes with obstacle centres per stage (obst [B, N+1, 6])")
+            rsum = _abi.f64(rsum)
+            if rsum.shape != (B, self.N + 1, 3):
+                raise MpcError(_abi.MPC_ERR_INVALID, f"rsum must be [B, {self.N + 1}, 3]")
         if obst is not None and obst.ndim == 3:
             if lam_p or dp is not None:
                 raise MpcError(_abi.MPC_ERR_INVALID, "derivatives of a solve with obstacle centres per stage are not provided (obst [B, N+1, 6])")
             self._sens_gen += 1                              # (the library has ended the life of an earlier snapshot)
             f, g, lam_g, lam_x = self._nlp_out(B) if multipliers else (None,) * 4
+            if rsum is not None:
+                self._check(self._lib.mpc_solve_batch_sized(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(rsum),
+                                                            _abi.as_dp(out), _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt), _abi.as_dp(f),
+                                                            _abi.as_dp(g), _abi.as_dp(lam_g), _abi.as_dp(lam_x)))
+                return SolveResult(out, status, iters, kkt, f, g, lam_g, lam_x)
             self._check(self._lib.mpc_solve_batch_stages(self._h, B, _abi.as_dp(x0), _abi.as_dp(p), _abi.as_dp(obst), _abi.as_dp(out),
                                                          _abi.as_ip(status), _abi.as_ip(iters), _abi.as_dp(kkt), _abi.as_dp(f), _abi.as_dp(g),
                                                          _abi.as_dp(lam_g), _abi.as_dp(lam_x)))
@@ -466,17 +479,23 @@ class BatchedMPCSolver:
         return [self._h, int(B), _vp(d_x0), _vp(d_p), _vp(d_obst), _vp(d_x_out), _vp(d_status), _vp(d_iters), _vp(d_kkt)]
 
     def solve_device(self, B, d_x0, d_p, d_x_out, d_status=0, d_iters=0, d_kkt=0, d_obst=0, stream=0, d_f=0, d_g=0, d_lam_g=0, d_lam_x=0,
-                     d_lam_p=0, n_dir=0, d_dp=0, d_dw=0, obst_stages=False):
+                     d_lam_p=0, n_dir=0, d_dp=0, d_dw=0, obst_stages=False, d_rsum=0):
         """device pointers (ints, e.g. torch.Tensor.data_ptr()) and a hipStream_t handle (int, 0 = default).  d_f [B], d_g / d_lam_g
         [B, n_g], d_lam_x [B, n_w]: the extra outputs of mpc_solve_batch_dev_ex (0 = not asked for).  d_lam_p [B, n_p], n_dir > 0 with
         d_dp [B, n_dir, n_p] -> d_dw [B, n_dir, n_w]: mpc_solve_batch_sens_dev (keeps the final iterates for sens_adjoint_device).
-        obst_stages=True: d_obst is [B, N+1, 6], centres per stage (mpc_solve_batch_stages_dev; no sensitivity outputs)."""
+        obst_stages=True: d_obst is [B, N+1, 6], centres per stage (mpc_solve_batch_stages_dev; no sensitivity outputs).
+        d_rsum (with obst_stages): [B, N+1, 3], a lower bound per circle row (mpc_solve_batch_sized_dev); 0 is the call without it."""
         rows = self._dev_rows(B, d_x0, d_p, d_obst, d_x_out, d_status, d_iters, d_kkt)
         extra = [_vp(d_f), _vp(d_g), _vp(d_lam_g), _vp(d_lam_x)]
+        if d_rsum and not obst_stages:
+            raise MpcError(_abi.MPC_ERR_INVALID, "d_rsum goes with obstacle centres per stage (obst_stages)")
         if obst_stages:
             if d_lam_p or n_dir:
                 raise MpcError(_abi.MPC_ERR_INVALID, "derivatives of a solve with obstacle centres per stage are not provided (obst_stages)")
             self._sens_gen += 1
+            if d_rsum:
+                self._check(self._lib.mpc_solve_batch_sized_dev(*rows[:5], _vp(d_rsum), *rows[5:], *extra, _vp(stream)))
+                return
             self._check(self._lib.mpc_solve_batch_stages_dev(*rows, *extra, _vp(stream)))
         elif d_lam_p or n_dir:
             self._sens_gen += 1
@@ -598,14 +617,17 @@ class BatchedMPCSolver:
         else:
             self._check(self._lib.mpc_closed_loop_batch_dev_ex(*head, *tail, _vp(stream)))
 
-    def closed_loop_traffic(self, init_state, path, orient, vdes, steps, tracks, offsets, pairing=0, noise_mode=0, sigma=0.0, seed=0):
+    def closed_loop_traffic(self, init_state, path, orient, vdes, steps, tracks, offsets, pairing=0, noise_mode=0, sigma=0.0, seed=0, rsums=None):
         """B egos through traffic (mpc_closed_loop_batch_traffic): before every solve each stage of each ego gets the circle centres of the obstacle
         nearest to it at that stage's time -- the nearest-obstacle formulation; two obstacles equally close to one ego circle at one stage constrain
         it only once.  tracks [M,Lt,3] (x, y, heading; NaN x: absent at that row) with offsets [M]: one scene shared by all egos; tracks [B,M,Lt,3]
         with offsets [B,M]: a scene per ego.  Lt = 1 or Lt >= steps.  pairing 0: the reference's pairs on the nearest obstacle; 1: each ego circle
         against its nearest obstacle circle.  A handle has one radius: the lower bound of its circle rows holds for every obstacle.
         -> (traj [B,steps,5], ctrl [B,steps,2], step_status [B,steps], clearance [B,steps] over all nine pairs of every present obstacle (+inf: none),
-        nearest [B,steps] (the obstacle that attains it, -1: none), chosen [B,steps,N+1,3] (the obstacle behind every slot of every stage))"""
+        nearest [B,steps] (the obstacle that attains it, -1: none), chosen [B,steps,N+1,3] (the obstacle behind every slot of every stage))
+        rsums (shaped like offsets; None: the call without it): traffic of mixed sizes (mpc_closed_loop_batch_traffic_sized) -- rsums[m] is the radius
+        sum of ego and obstacle m, the selection is by clearance (distance less rsums[m] - the handle's radius), every slot of every solve carries
+        its winner's radius, and clearance is the smallest distance - rsums[m]."""
         init_state, path, orient, vdes, B, Lp = _loop_in(init_state, path, orient, vdes)
         steps = int(steps)
         tracks, offsets = _abi.f64(tracks), _abi.f64(offsets)
@@ -615,6 +637,15 @@ class BatchedMPCSolver:
         traj, ctrl, st = np.empty((B, steps, 5)), np.empty((B, steps, 2)), np.empty((B, steps), np.int32)
         cl, near, chosen = np.empty((B, steps)), np.empty((B, steps), np.int32), np.empty((B, steps, self.N + 1, 3), np.int32)
         self._sens_gen += 1                                  # (like every loop: the library has ended the life of an earlier snapshot)
+        if rsums is not None:
+            rsums = _abi.f64(rsums)
+            if rsums.shape != offsets.shape:
+                raise MpcError(_abi.MPC_ERR_INVALID, "rsums must have the shape of offsets")
+            self._check(self._lib.mpc_closed_loop_batch_traffic_sized(
+                self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient), _abi.as_dp(vdes), M, Lt, int(tracks.ndim == 4),
+                _abi.as_dp(tracks), _abi.as_dp(offsets), _abi.as_dp(rsums), int(pairing), int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1),
+                _abi.as_dp(traj), _abi.as_dp(ctrl), _abi.as_ip(st), _abi.as_dp(cl), _abi.as_ip(near), _abi.as_ip(chosen)))
+            return traj, ctrl, st, cl, near, chosen
         self._check(self._lib.mpc_closed_loop_batch_traffic(self._h, B, steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient), _abi.as_dp(vdes),
                                                             M, Lt, int(tracks.ndim == 4), _abi.as_dp(tracks), _abi.as_dp(offsets), int(pairing), int(noise_mode),
                                                             float(sigma), int(seed) & (2 ** 64 - 1), _abi.as_dp(traj), _abi.as_dp(ctrl), _abi.as_ip(st),
@@ -622,11 +653,17 @@ class BatchedMPCSolver:
         return traj, ctrl, st, cl, near, chosen
 
     def closed_loop_traffic_device(self, B, d_init_state, d_path, d_orient, d_vdes, steps, Lp, M, Lt, per_ego, d_tracks, d_offsets, d_traj, d_ctrl,
-                                   d_step_status=0, pairing=0, noise_mode=0, sigma=0.0, seed=0, d_clearance=0, d_nearest=0, d_chosen=0, stream=0):
+                                   d_step_status=0, pairing=0, noise_mode=0, sigma=0.0, seed=0, d_clearance=0, d_nearest=0, d_chosen=0, stream=0, d_rsums=0):
         """device-pointer form (ints; 0 = absent) of closed_loop_traffic (mpc_closed_loop_batch_traffic_dev): d_tracks [M,Lt,3] / [B,M,Lt,3], d_offsets [M] /
         [B,M] by per_ego, d_nearest [B,steps] and d_chosen [B,steps,N+1,3] int32.  The offsets are copied back once and checked, then the whole loop is
-        enqueued on `stream`."""
+        enqueued on `stream`.  d_rsums (shaped like d_offsets; 0: the call without it): mpc_closed_loop_batch_traffic_sized_dev."""
         self._sens_gen += 1
+        if d_rsums:
+            self._check(self._lib.mpc_closed_loop_batch_traffic_sized_dev(
+                self._h, int(B), int(steps), int(Lp), _vp(d_init_state), _vp(d_path), _vp(d_orient), _vp(d_vdes), int(M), int(Lt), int(per_ego), _vp(d_tracks),
+                _vp(d_offsets), _vp(d_rsums), int(pairing), int(noise_mode), float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl),
+                _vp(d_step_status), _vp(d_clearance), _vp(d_nearest), _vp(d_chosen), _vp(stream)))
+            return
         self._check(self._lib.mpc_closed_loop_batch_traffic_dev(self._h, int(B), int(steps), int(Lp), _vp(d_init_state), _vp(d_path), _vp(d_orient), _vp(d_vdes),
                                                                 int(M), int(Lt), int(per_ego), _vp(d_tracks), _vp(d_offsets), int(pairing), int(noise_mode),
                                                                 float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl), _vp(d_step_status),

@@ -25,12 +25,32 @@ def hashes(lib):
     co = code_object(lib)
     dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co], check=True, capture_output=True, text=True).stdout
     out, cur, h, pcrel = {}, None, None, 0
+
+    class Tail:
+        """sha256 of the lines fed to it, but for a run of `s_nop 0` at the very end: the fill between a function's last instruction (s_endpgm, the
+        return) and the next function's alignment boundary.  Its length depends on where the function lies -- a device function in front of
+        the first kernel is followed by up to 63 of them, as many as its own address leaves to the next 256 bytes -- and it is never executed."""
+        def __init__(self):
+            self.h, self.held = hashlib.sha256(), []
+
+        def update(self, b):
+            if b.startswith(b"s_nop 0") or b == b"...":            # ("...": the disassembler's mark for a run of zero bytes behind the fill)
+                self.held.append(b)
+                return
+            for q in self.held:
+                self.h.update(q)
+            self.held = []
+            self.h.update(b)
+
+        def hexdigest(self):
+            return self.h.hexdigest()
+
     for line in dis.split("\n"):
         m = re.match(r"^[0-9a-f]* ?<(\S+)>:$", line.strip())
         if m:
             if cur is not None:
                 out[cur] = h.hexdigest()[:16]
-            cur, h = m.group(1), hashlib.sha256()
+            cur, h = m.group(1), Tail()
             continue
         if cur is not None and line.strip():
             # (pc-relative addresses of other symbols -- a callee, a table in .rodata --: `s_getpc_b64` followed by `s_add_u32 / s_addc_u32 ..., literal`;
