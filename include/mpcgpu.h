@@ -614,6 +614,8 @@ int mpc_forces_solve_batch_dev(mpc_handle* h, int32_t B, const double* d_x0, con
  *                        stage workers then have the loads that do not read the step in flight when the sweep ends): 0 behind the sweep, n stages
  *                        (clamped to the horizon); -1 (default): 18 in converged mode, 0 with a fixed iteration count.  Never with helping
  *                        Riccati workers ("pipe_help").  Same bits at every value
+ *     "red_transpose"    default 1: the stage items of the pipeline reduce their ten-field record over the stages of an instance by a transpose
+ *                        through LDS (one lane per field and instance folds the column); 0: by the lane butterfly.  Same bits either way
  *     "bound_mask"       0: every bound side looked up at run time (variant 0 of the loop kernels); default 1: the kernels with the bound structure
  *                        of the reference's NLPs compiled in (optimizer.py:421-491) whenever the bounds handed to mpc_set_bounds have it
  *     "big_wg"           1: 512-thread stage workgroups (what horizons above 63 use) also for short horizons

@@ -18,6 +18,7 @@ struct Knobs {
     int pipeline, hybrid, hybrid_bx, hybrid_live, pipe_help, pipe_test_abort, pipe_xcd_mask, pipe_early;
     int rescue, rescue_wg, rescue_alone, loop_async, sync_spin, max_batch, friction_lb, bound_mask, big_wg, groups, poison;
     int timing;                         // profiling aids, a sum of TIMING_* (below): shader-clock stamps printed to stderr; each synchronises
+    int red_transpose;                  // k_pipeline's stage items reduce their ten-field record by a transpose through LDS (1, the default) or by the lane butterfly (0): the same bits
     Knobs();
 };
 // how a value given as text is read (value NULL always restores the default)
@@ -40,6 +41,7 @@ inline constexpr KnobDef KNOBS[] = {
     {"bound_mask", &Knobs::bound_mask, 1, KnobParse::INT},      {"big_wg", &Knobs::big_wg, 0, KnobParse::FLAG},
     {"groups", &Knobs::groups, 0, KnobParse::INT},              {"poison", &Knobs::poison, 0, KnobParse::FLAG},
     {"timing", &Knobs::timing, 0, KnobParse::INT},               {"pipe_early", &Knobs::pipe_early, -1, KnobParse::INT},
+    {"red_transpose", &Knobs::red_transpose, 1, KnobParse::ON},
 };
 inline Knobs::Knobs() { for (const KnobDef& e : KNOBS) this->*e.field = e.dflt; }
 inline const KnobDef* find_knob(const char* name) {

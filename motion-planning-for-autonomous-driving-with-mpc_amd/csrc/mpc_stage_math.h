@@ -156,6 +156,9 @@ struct Params {
     // final (emit_result) -- the loop kernels are then the last to touch the batch, no output transpose (k_egest) behind them; fail_count (optional)
     // += instances that end with status 0 / -7 (the host decides from it whether a second chance is due)
     int32_t emit;
+    // k_pipeline: the stage items' reduction behind the evaluation in its transposed form (block_reduce_t; option red_transpose) -- the same bits
+    // either way.  (In the four bytes between `emit` and the pointer behind it: no offset of the kernel-argument segment moves.)
+    int32_t red_t;
     uint32_t* fail_count;
     // k_solve_wg as the last kernel of a solve: the workgroup that leaves last copies the head of the solve's control block (fin_ctl) into the
     // handle's pinned host block (fin_host) -- see its epilogue; null: nobody does

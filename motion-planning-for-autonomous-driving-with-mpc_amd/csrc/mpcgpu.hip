@@ -40,6 +40,7 @@
 #include "mpc_riccati_mfma.h"
 #include "mpc_sens.h"
 #include "mpc_loop_lin.h"
+#include "mpc_red_fold.h"
 
 using namespace mpc;
 
@@ -132,6 +133,83 @@ __device__ __forceinline__ void block_reduce(R& r, int bx, double* lds) {
     }
 }
 
+// ---- the same reduction TRANSPOSED, for the stage items of k_pipeline (256 threads, bx = 8: eight stages of every column per wavefront) ----
+// In the butterfly every lane of a column performs the whole tree and every wavefront the whole pass through LDS, although one result per
+// (instance, field) exists.  Here every thread writes its NQ doubles to a scratch [row][column][stage] -- stage fastest --, ONE lane per
+// (field, column) reads the leaves of its column and folds them in red_fold's order (mpc_red_fold.h: the order of the butterfly's stage-0
+// lane, so every result keeps its bits), and every thread reads the NQ results of its column back as broadcast reads.  Two barriers, as before.
+//   * rows: the fields sorted by operator (red_row), so that the folding lanes of a WAVEFRONT share one operator -- wavefront 0 folds the
+//     sums, 1 the minima, 2 the maxima (at most eight fields of a kind: 64 lanes / bx) -- and no lane waits for another operator's pass;
+//   * padding threads (stages beyond the horizon) write their neutral leaf like every other thread: the folding lanes read 8 nw leaves
+//     without a test;
+//   * column stride RED_CS = 34 doubles (272 bytes, so every column starts 16-byte aligned and two neighbouring stages are one 16-byte
+//     read): folding lane (row, col) starts at word 68 (8 row + col) = 4 (8 row + col) (mod 64) and reads four words -- sixteen lanes with
+//     consecutive columns cover the 64 banks exactly once, as many lanes as a 16-byte read serves per pass; with a stride of 32 doubles
+//     every lane would start on bank 0.
+// scr: red_t_doubles(NQ, bx) doubles (the leaves, then the NQ bx results), 16-byte aligned, that no thread of the workgroup touches between the barrier in front of this call
+// and the next one behind it.
+constexpr int RED_CS = 34;
+constexpr int red_t_doubles(int nq, int bx) { return nq * bx * (RED_CS + 1); }
+template <typename R> constexpr int red_count(int kind) {
+    int n = 0;
+    for (int q = 0; q < (int)(sizeof(R) / sizeof(double)); ++q) n += red_kind((const R*)nullptr, q) == kind ? 1 : 0;
+    return n;
+}
+template <typename R> constexpr int red_base(int kind) { return kind == RED_SUM ? 0 : kind == RED_MIN ? red_count<R>(RED_SUM) : red_count<R>(RED_SUM) + red_count<R>(RED_MIN); }
+template <typename R> constexpr int red_row(int q) {
+    const int kind = red_kind((const R*)nullptr, q);
+    int n = red_base<R>(kind);
+    for (int i = 0; i < q; ++i) n += red_kind((const R*)nullptr, i) == kind ? 1 : 0;
+    return n;
+}
+typedef double mpc_d2 __attribute__((ext_vector_type(2)));
+template <int KIND>
+__device__ __forceinline__ double red_fold_column(const double* col, const int nw) {
+    double x[32];
+#pragma unroll
+    for (int s = 0; s < 32; s += 2) { const mpc_d2 v = *reinterpret_cast<const mpc_d2*>(col + s); x[s] = v.x; x[s + 1] = v.y; }
+    // red_fold_field<KIND, 8>(nw, ..) with its loop over the wavefronts unrolled (x[] stays in registers: every index a literal)
+    auto leaf = [&](const int s) { return x[s]; };
+    double acc = red_tree_field<KIND, 8>(0, leaf);
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+        if (w < nw) acc = red_op<KIND>(acc, red_tree_field<KIND, 8>(8 * w, leaf));
+    return acc;
+}
+// bx = 8, blockDim.x = 64 nw with nw = 3 or 4 (the caller checks)
+template <typename R>
+__device__ __forceinline__ void block_reduce_t(R& r, double* scr) {
+    constexpr int NQ = sizeof(R) / sizeof(double), BX = 8;
+    static_assert(red_count<R>(RED_SUM) <= 8 && red_count<R>(RED_MIN) <= 8 && red_count<R>(RED_MAX) <= 8, "the fields of one operator fit one wavefront");
+    static_assert(RED_SUM == 0 && RED_MIN == 1 && RED_MAX == 2, "wavefront w folds operator w");
+    const int t = threadIdx.x, nw = blockDim.x >> 6, lane = t & 63, bl = t & (BX - 1);
+    const int wave = lds_uniform(t >> 6);
+    double* v = reinterpret_cast<double*>(&r);
+    double* res = scr + NQ * BX * RED_CS;
+    {
+        double* mine = scr + bl * RED_CS + (t >> 3);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) mine[red_row<R>(q) * BX * RED_CS] = v[q];
+    }
+    lds_barrier();
+    if (wave < 3) {
+        const int cnt = wave == RED_SUM ? red_count<R>(RED_SUM) : wave == RED_MIN ? red_count<R>(RED_MIN) : red_count<R>(RED_MAX);
+        const int base = wave == RED_SUM ? red_base<R>(RED_SUM) : wave == RED_MIN ? red_base<R>(RED_MIN) : red_base<R>(RED_MAX);
+        if (lane < cnt * BX) {
+            const int slot = base * BX + lane;                         // (row, column) = (base + lane / 8, lane % 8)
+            const double* col = scr + slot * RED_CS;
+            double out;
+            if (wave == RED_SUM) out = red_fold_column<RED_SUM>(col, nw);
+            else if (wave == RED_MIN) out = red_fold_column<RED_MIN>(col, nw);
+            else out = red_fold_column<RED_MAX>(col, nw);
+            res[slot] = out;
+        }
+    }
+    lds_barrier();
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) v[q] = res[red_row<R>(q) * BX + bl];
+}
+
 // multiplier state that is not touched by the line search is parked in LDS while the search runs (registers of the
 // 256-thread variant are capped at 256 so that two workgroups share a CU): Stash<NX>::rows (mpc_solve_plan.h) rows of blockDim doubles
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
@@ -177,7 +255,11 @@ struct NoStepWait {
     __device__ __forceinline__ bool there() const { return true; }
     __device__ __forceinline__ bool operator()() const { return true; }
 };
-template <int NX, bool INIT, int MAXT, uint32_t VM = 0xFFu, class StepWait = NoStepWait, bool OSTG = true>
+// RT: the reduction behind the evaluation (Red3, ten fields) may take the transposed form (block_reduce_t) -- chosen per kernel family: the stage
+// workers of k_pipeline; every other kernel keeps the butterfly and its machine code.  Params::red_t (option red_transpose) then decides at run
+// time, so that one build holds both forms (tests/test_gpu_red_transpose.py compares them).  Red0 .. Red2 stay on the butterfly: with one to
+// four fields it is as short as the fold of one column.
+template <int NX, bool INIT, int MAXT, uint32_t VM = 0xFFu, class StepWait = NoStepWait, bool OSTG = true, bool RT = false>
 __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, const int n_z, const int stash_rows, const uint32_t b0,
                                             const unsigned long long tile_bits, double* lds, const bool stamp = true,
                                             uint32_t* live_out = nullptr, const bool bounds_in_lds = false, const StepWait& step_wait = StepWait()) {
@@ -287,7 +369,16 @@ __device__ __forceinline__ void stage_block(const PRef& P, const int n_mult, con
     Red3 r3;
     phase_eval_assemble<NX, !INIT, false, VM>(P, c, r3);
     MPC_STAMP(P.DBG, blockIdx.x, SB_EVAL, t == 0 && stamp);
-    block_reduce(r3, bx, lds);
+    if constexpr (RT && !INIT) {
+        // scratch of the transposed form: the rows of the stash region behind the neighbour exchange's 2 NX -- every thread has taken its
+        // multipliers back from there before the exchange's barrier, and nothing writes them before the next item's line search
+        const int T = blockDim.x;
+        const bool fits = bx == 8 && T >= 192 && T <= 256 && (stash_rows - 2 * NX) * T >= red_t_doubles(sizeof(Red3) / sizeof(double), 8);
+        if (P.red_t != 0 && fits) block_reduce_t(r3, lds_x + 2 * NX * T);
+        else block_reduce(r3, bx, lds);
+    } else {
+        block_reduce(r3, bx, lds);
+    }
     MPC_STAMP(P.DBG, blockIdx.x, SB_RED3, t == 0 && stamp);
     phase_finish<NX, false>(P, c, r3, n_mult, n_z);
     MPC_STAMP(P.DBG, blockIdx.x, SB_END, t == 0 && stamp);
@@ -1087,7 +1178,7 @@ __global__ void __launch_bounds__(256) k_pipeline(const Params Pk, const PipeArg
         if constexpr (HELP)
             stage_block<NX, false, 256, var_vm(VAR)>(P, n_mult, n_z, stash_rows, tile * 64u + pipe_item_q(item) * (uint32_t)P.bx, bits, lds, n_pass == 5u, nullptr, have_bounds);
         else
-            stage_block<NX, false, 256, var_vm(VAR)>(P, n_mult, n_z, stash_rows, tile * 64u + pipe_item_q(item) * (uint32_t)P.bx, bits, lds, n_pass == 5u, nullptr, have_bounds,
+            stage_block<NX, false, 256, var_vm(VAR), PipeStepWait, true, true>(P, n_mult, n_z, stash_rows, tile * 64u + pipe_item_q(item) * (uint32_t)P.bx, bits, lds, n_pass == 5u, nullptr, have_bounds,
                                                                    PipeStepWait{step_ready + tile, abort_w, &sh_word[0], pipe_item_round(item), tile, kpub < 0});
         // (an item whose instance columns have all finished leaves stage_block before the copy)
         have_bounds = have_bounds || ((bits >> ((pipe_item_q(item) * (uint32_t)P.bx) & 63u)) & ((P.bx >= 64) ? ~0ull : ((1ull << P.bx) - 1ull))) != 0ull;
@@ -3809,6 +3900,7 @@ template <int NX> static int solve_pipeline(Solve& s) {
     P.DBG = t_pdbg.as<unsigned long long>();
     s.prof.next(3, stream);
     P.mbw_live = pl.mbw_live;
+    P.red_t = h->knobs.red_transpose;
     const auto kf = pipeline_kernel<NX>(pl.pipe_help, pl.masked, pl.sized);
     hipLaunchKernelGGL(kf, dim3(h->n_cu), dim3(pl.threads), std::max(pl.lds_bytes, pl.ric_lds), stream, P, A, h->hp.n_mult, h->hp.n_z, pl.stash_rows);
     if (pl.hand > 0) {
