@@ -248,54 +248,81 @@ struct TrafficTrackPose {
     int b, row;
     MPC_HD const double* operator()(int m, double*) const { return loop_traffic_pose(A, b, m, row); }
 };
-template <class Pose>
-MPC_HD double loop_traffic_bound(const LoopTrafficArgs& A, int b, const Pose& at, const double* xy) {
+// `Keys`: what the selection compares.  TrafficDistance (the loop through traffic, the stepping session): a key is a distance.  TrafficClearance
+// (traffic of mixed sizes, below): a key is a distance less delta_m, and the row is written packed.  Everything of the second kind stands behind
+// `if constexpr (Keys::SIZED)`: the first kind's arithmetic has no `- 0.0` in it for a compiler to fold or not.
+struct TrafficDistance {
+    static constexpr bool SIZED = false;
+    const LoopTrafficArgs& A;
+    MPC_HD double delta(int, int) const { return 0.0; }
+    MPC_HD double rsum(int, int) const { return A.r_sum; }
+    MPC_HD double margin(double bound) const { return bound * (1.0 + 1e-12) + 1e-12; }
+};
+template <class Keys, class Pose>
+MPC_HD double loop_traffic_bound(const Keys& K, int b, const Pose& at, const double* xy) {
+    const LoopTrafficArgs& A = K.A;
     double bound = INFINITY, tmp[3];
     for (int m = 0; m < A.M; ++m) {
         const double* pose = at(m, tmp);
         if (!loop_traffic_present(pose)) continue;
-        const double hi = loop_traffic_dist(xy, pose) + A.ego_offset + fabs(loop_traffic_offset(A, b, m));
+        double hi = loop_traffic_dist(xy, pose) + A.ego_offset + fabs(loop_traffic_offset(A, b, m));
+        if constexpr (Keys::SIZED) hi -= K.delta(b, m);
         if (hi < bound) bound = hi;
     }
     return bound;
 }
-MPC_HD bool loop_traffic_near(const LoopTrafficArgs& A, int b, int m, const double* pose, const double* xy, double bound) {
-    const double lo = loop_traffic_dist(xy, pose) - A.ego_offset - fabs(loop_traffic_offset(A, b, m));
-    return !(lo > bound * (1.0 + 1e-12) + 1e-12);
+template <class Keys>
+MPC_HD bool loop_traffic_near(const Keys& K, int b, int m, const double* pose, const double* xy, double bound) {
+    const LoopTrafficArgs& A = K.A;
+    double lo = loop_traffic_dist(xy, pose) - A.ego_offset - fabs(loop_traffic_offset(A, b, m));
+    if constexpr (Keys::SIZED) lo -= K.delta(b, m);
+    return !(lo > K.margin(bound));
 }
 // row (b, k) of the solve of step i, and from the stage-0 call column `col` of clearance / nearest and block `col` of chosen (the loops: col = i)
-template <class Pose>
-MPC_HD void loop_traffic_place(const LoopTrafficArgs& A, int b, int k, int i, int col, const Pose& at) {
+template <class Keys, class Pose>
+MPC_HD void loop_traffic_place(const Keys& K, int b, int k, int i, int col, const Pose& at) {
+    const LoopTrafficArgs& A = K.A;
     const int N = A.N, S = N + 1, nw = 2 * N + A.nx * S;
     const double* st = A.state + (size_t)b * A.nx;
     const double* pl = (i == 0) ? st : A.x0 + (size_t)b * nw + 2 * N + A.nx * k;
-    double e6[6], c6[6], out[6], best[3], tmp[3];
+    double e6[6], c6[6], out[6], rad[3] = {A.r_sum, A.r_sum, A.r_sum}, best[3], tmp[3];
     int32_t pick[3] = {-1, -1, -1};
     loop_traffic_ego(pl[0], pl[1], pl[4], A.ego_offset, e6);
     for (int q = 0; q < 6; ++q) out[q] = A.desc_obst[q];
-    double bound = loop_traffic_bound(A, b, at, pl);
+    double bound = loop_traffic_bound(K, b, at, pl);
     for (int m = 0; m < A.M; ++m) {
         const double* pose = at(m, tmp);
-        if (!loop_traffic_present(pose) || !loop_traffic_near(A, b, m, pose, pl, bound)) continue;
+        if (!loop_traffic_present(pose) || !loop_traffic_near(K, b, m, pose, pl, bound)) continue;
         loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
+        const double dm = K.delta(b, m), rm = K.rsum(b, m);
         if (A.pairing == 0) {
             double score = loop_traffic_dist(e6, c6);
             for (int j = 1; j < 3; ++j) score = fmin(score, loop_traffic_dist(e6 + 2 * j, c6 + 2 * j));
+            if constexpr (Keys::SIZED) score -= dm;
             if (pick[0] < 0 || score < best[0]) {
                 best[0] = score;
                 pick[0] = pick[1] = pick[2] = m;
+                if constexpr (Keys::SIZED) rad[0] = rad[1] = rad[2] = rm;
                 for (int q = 0; q < 6; ++q) out[q] = c6[q];
             }
         } else {
             for (int j = 0; j < 3; ++j)
                 for (int c = 0; c < 3; ++c) {
-                    const double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c);
-                    if (pick[j] < 0 || dist < best[j]) { best[j] = dist; pick[j] = m; out[2 * j] = c6[2 * c]; out[2 * j + 1] = c6[2 * c + 1]; }
+                    double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c);
+                    if constexpr (Keys::SIZED) dist -= dm;
+                    if (pick[j] < 0 || dist < best[j]) {
+                        best[j] = dist; pick[j] = m; out[2 * j] = c6[2 * c]; out[2 * j + 1] = c6[2 * c + 1];
+                        if constexpr (Keys::SIZED) rad[j] = rm;
+                    }
                 }
         }
     }
-    double* o = A.obst + ((size_t)b * S + k) * 6;
+    double* o = A.obst + ((size_t)b * S + k) * (Keys::SIZED ? OBST_SIZED_ROWS : 6);
     for (int q = 0; q < 6; ++q) o[q] = out[q];
+    if constexpr (Keys::SIZED) {
+        for (int j = 0; j < 3; ++j) o[OBST_SIZED_OD + j] = rad[j];
+        o[OBST_SIZED_SCALE] = 0.0;
+    }
     if (A.chosen)
         for (int j = 0; j < 3; ++j) A.chosen[(((size_t)b * A.L + col) * S + k) * 3 + j] = pick[j];
     if (k != 0 || (!A.clearance && !A.nearest)) return;
@@ -303,14 +330,16 @@ MPC_HD void loop_traffic_place(const LoopTrafficArgs& A, int b, int k, int i, in
     double cl = INFINITY;
     int32_t near = -1;
     loop_traffic_ego(st[0], st[1], st[4], A.ego_offset, e6);
-    bound = loop_traffic_bound(A, b, at, st);
+    bound = loop_traffic_bound(K, b, at, st);
     for (int m = 0; m < A.M; ++m) {
         const double* pose = at(m, tmp);
-        if (!loop_traffic_present(pose) || !loop_traffic_near(A, b, m, pose, st, bound)) continue;
+        if (!loop_traffic_present(pose) || !loop_traffic_near(K, b, m, pose, st, bound)) continue;
         loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
+        const double dm = K.delta(b, m);
         for (int j = 0; j < 3; ++j)
             for (int c = 0; c < 3; ++c) {
-                const double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c);
+                double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c);
+                if constexpr (Keys::SIZED) dist -= dm;
                 if (near < 0 || dist < cl) { cl = dist; near = m; }
             }
     }
@@ -319,7 +348,7 @@ MPC_HD void loop_traffic_place(const LoopTrafficArgs& A, int b, int k, int i, in
 }
 MPC_HD void loop_traffic_stage(const LoopTrafficArgs& A, int b, int k, int i) {
     const int at = i + k, row = at < A.Lt - 1 ? at : A.Lt - 1;
-    loop_traffic_place(A, b, k, i, i, TrafficTrackPose{A, b, row});
+    loop_traffic_place(TrafficDistance{A}, b, k, i, i, TrafficTrackPose{A, b, row});
 }
 
 // ---- traffic of mixed sizes (mpc_closed_loop_batch_traffic_sized): obstacle m has a radius sum of its own, rsums[m], and every solve is a sized
@@ -328,92 +357,23 @@ MPC_HD void loop_traffic_stage(const LoopTrafficArgs& A, int b, int k, int i) {
 //      sized_pack leaves it (mpc_stage_math.h: six centres, the three slots' radius sums, a pad): the winner's centres with the winner's rsums[m];
 //      nothing present: the descriptor's centres with the handle's radius.  clearance: the smallest key over all nine pairs of every present
 //      obstacle, less r_sum -- the smallest distance - rsums[m].  The cull stays exact: the keys of obstacle m lie within reach_m of d_m - delta_m.
-//      delta_m = 0.0 changes no bit: with every rsums[m] = r_sum the centres, chosen, clearance and nearest are loop_traffic_place's.
-//      (A copy of loop_traffic_place's text with the keys shifted -- keep the two in step; k_loop_traffic and k_session_traffic keep their code.)
+//      delta_m = 0.0 changes no bit: with every rsums[m] = r_sum the centres, chosen, clearance and nearest are TrafficDistance's.
+//      (loop_traffic_place<TrafficClearance, ..>: the one text above with its SIZED parts in.)
 struct LoopTrafficSizedArgs {
     LoopTrafficArgs T;               // T.obst: the packed rows [B, N+1, OBST_SIZED_ROWS]
     const double* rsums;             // [M] or [B, M], like T.offsets
 };
-MPC_HD double loop_traffic_delta(const LoopTrafficSizedArgs& S, int b, int m) { return S.rsums[(size_t)(S.T.per_ego ? b : 0) * S.T.M + m] - S.T.r_sum; }
-template <class Pose>
-MPC_HD double loop_traffic_bound_sized(const LoopTrafficSizedArgs& S, int b, const Pose& at, const double* xy) {
-    const LoopTrafficArgs& A = S.T;
-    double bound = INFINITY, tmp[3];
-    for (int m = 0; m < A.M; ++m) {
-        const double* pose = at(m, tmp);
-        if (!loop_traffic_present(pose)) continue;
-        const double hi = loop_traffic_dist(xy, pose) + A.ego_offset + fabs(loop_traffic_offset(A, b, m)) - loop_traffic_delta(S, b, m);
-        if (hi < bound) bound = hi;
-    }
-    return bound;
-}
-MPC_HD bool loop_traffic_near_sized(const LoopTrafficSizedArgs& S, int b, int m, const double* pose, const double* xy, double bound) {
-    const LoopTrafficArgs& A = S.T;
-    const double lo = loop_traffic_dist(xy, pose) - A.ego_offset - fabs(loop_traffic_offset(A, b, m)) - loop_traffic_delta(S, b, m);
-    return !(lo > bound + fabs(bound) * 1e-12 + 1e-12);          // (a key may be negative here: the margin is on its size)
-}
-template <class Pose>
-MPC_HD void loop_traffic_place_sized(const LoopTrafficSizedArgs& S, int b, int k, int i, int col, const Pose& at) {
-    const LoopTrafficArgs& A = S.T;
-    const int N = A.N, St = N + 1, nw = 2 * N + A.nx * St;
-    const double* st = A.state + (size_t)b * A.nx;
-    const double* pl = (i == 0) ? st : A.x0 + (size_t)b * nw + 2 * N + A.nx * k;
-    double e6[6], c6[6], out[6], rad[3] = {A.r_sum, A.r_sum, A.r_sum}, best[3], tmp[3];
-    int32_t pick[3] = {-1, -1, -1};
-    loop_traffic_ego(pl[0], pl[1], pl[4], A.ego_offset, e6);
-    for (int q = 0; q < 6; ++q) out[q] = A.desc_obst[q];
-    double bound = loop_traffic_bound_sized(S, b, at, pl);
-    for (int m = 0; m < A.M; ++m) {
-        const double* pose = at(m, tmp);
-        if (!loop_traffic_present(pose) || !loop_traffic_near_sized(S, b, m, pose, pl, bound)) continue;
-        loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
-        const double dm = loop_traffic_delta(S, b, m), rm = S.rsums[(size_t)(A.per_ego ? b : 0) * A.M + m];
-        if (A.pairing == 0) {
-            double score = loop_traffic_dist(e6, c6);
-            for (int j = 1; j < 3; ++j) score = fmin(score, loop_traffic_dist(e6 + 2 * j, c6 + 2 * j));
-            score -= dm;
-            if (pick[0] < 0 || score < best[0]) {
-                best[0] = score;
-                pick[0] = pick[1] = pick[2] = m;
-                rad[0] = rad[1] = rad[2] = rm;
-                for (int q = 0; q < 6; ++q) out[q] = c6[q];
-            }
-        } else {
-            for (int j = 0; j < 3; ++j)
-                for (int c = 0; c < 3; ++c) {
-                    const double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c) - dm;
-                    if (pick[j] < 0 || dist < best[j]) { best[j] = dist; pick[j] = m; rad[j] = rm; out[2 * j] = c6[2 * c]; out[2 * j + 1] = c6[2 * c + 1]; }
-                }
-        }
-    }
-    double* o = A.obst + ((size_t)b * St + k) * OBST_SIZED_ROWS;
-    for (int q = 0; q < 6; ++q) o[q] = out[q];
-    for (int j = 0; j < 3; ++j) o[OBST_SIZED_OD + j] = rad[j];
-    o[OBST_SIZED_SCALE] = 0.0;
-    if (A.chosen)
-        for (int j = 0; j < 3; ++j) A.chosen[(((size_t)b * A.L + col) * St + k) * 3 + j] = pick[j];
-    if (k != 0 || (!A.clearance && !A.nearest)) return;
-    double cl = INFINITY;
-    int32_t near = -1;
-    loop_traffic_ego(st[0], st[1], st[4], A.ego_offset, e6);
-    bound = loop_traffic_bound_sized(S, b, at, st);
-    for (int m = 0; m < A.M; ++m) {
-        const double* pose = at(m, tmp);
-        if (!loop_traffic_present(pose) || !loop_traffic_near_sized(S, b, m, pose, st, bound)) continue;
-        loop_obstacle_centres(pose, loop_traffic_offset(A, b, m), c6);
-        const double dm = loop_traffic_delta(S, b, m);
-        for (int j = 0; j < 3; ++j)
-            for (int c = 0; c < 3; ++c) {
-                const double dist = loop_traffic_dist(e6 + 2 * j, c6 + 2 * c) - dm;
-                if (near < 0 || dist < cl) { cl = dist; near = m; }
-            }
-    }
-    if (A.clearance) A.clearance[(size_t)b * A.L + col] = near < 0 ? INFINITY : cl - A.r_sum;
-    if (A.nearest) A.nearest[(size_t)b * A.L + col] = near;
-}
+struct TrafficClearance {
+    static constexpr bool SIZED = true;
+    const LoopTrafficArgs& A;
+    const double* rsums;
+    MPC_HD double rsum(int b, int m) const { return rsums[(size_t)(A.per_ego ? b : 0) * A.M + m]; }
+    MPC_HD double delta(int b, int m) const { return rsum(b, m) - A.r_sum; }
+    MPC_HD double margin(double bound) const { return bound + fabs(bound) * 1e-12 + 1e-12; }         // (a key may be negative here: the margin is on its size)
+};
 MPC_HD void loop_traffic_stage_sized(const LoopTrafficSizedArgs& S, int b, int k, int i) {
     const int at = i + k, row = at < S.T.Lt - 1 ? at : S.T.Lt - 1;
-    loop_traffic_place_sized(S, b, k, i, i, TrafficTrackPose{S.T, b, row});
+    loop_traffic_place(TrafficClearance{S.T, S.rsums}, b, k, i, i, TrafficTrackPose{S.T, b, row});
 }
 
 // =========================================================================================================================
@@ -456,7 +416,7 @@ struct SessionObsPose {
     }
 };
 MPC_HD void session_traffic_stage(const SessionTrafficArgs& A, int b, int k) {
-    loop_traffic_place(A.T, b, k, A.step, 0, SessionObsPose{A, b, (double)k * A.dt});
+    loop_traffic_place(TrafficDistance{A.T}, b, k, A.step, 0, SessionObsPose{A, b, (double)k * A.dt});
 }
 
 // =========================================================================================================================

@@ -197,7 +197,7 @@ struct SolvePlan {
     int S, bx, threads, nblk, ntiles, G, stash_rows;
     size_t lds_bytes, lds_init, ric_lds;
     bool masked;                        // the kernels with the reference's bound structure compiled in (variant 2)
-    bool sized;                         // the kernels with a lower bound per circle row compiled in (VM_SIZED: k_start_sized, variant 4 of k_pipeline / k_solve_wg,
+    bool sized;                         // the kernels with a lower bound per circle row compiled in (VM_SIZED: k_start<.., SIZED_VM>, variant 4 of k_pipeline / k_solve_wg,
                                         // k_stage<.., SIZED_VM>) -- a sized solve and nothing else; never together with `masked`
     int cap, chunk;                     // iterations at most, launches between two convergence polls
     bool polled;

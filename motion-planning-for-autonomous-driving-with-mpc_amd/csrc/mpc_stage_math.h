@@ -824,7 +824,7 @@ MPC_HD double friction_eval(const Params& P, double a, double dl, double v, doub
 
 // The six centres the circle rows of stage thread c are measured against.  BATCH_WIDE (variant 2: one obstacle per batch) reads no mode at
 // all.  STAGES = false compiles the per-stage mode out: the kernels whose machine code is pinned (k_start, wg_restart) have a second instantiation with it
-// (k_start<NX, true>, wg_restart<NX, true>), which a per-stage solve runs.
+// (k_start<NX, true>, wg_restart<NX, true>), which a per-stage solve runs, and a third for a sized solve (k_start / wg_restart<NX, true, SIZED_VM>).
 // Per stage: six rows per stage in the tile-major pair layout of every other per-stage array -- three 16-byte loads, one scalar offset
 // (the stage's) more than the per-instance rows.  The mode is a kernel argument: the branch is wave-uniform.
 // SIZED (the VM_SIZED instantiations, which only a sized solve runs: no look at the mode): OBST_SIZED_ROWS rows per stage -- the six centres in the

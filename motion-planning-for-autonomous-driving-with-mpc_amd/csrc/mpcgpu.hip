@@ -239,7 +239,8 @@ __device__ __forceinline__ void stash_xfer(Ctx<NX>& c, double* st, int T, int t,
 #endif
 constexpr uint32_t REF_VM = REF_BOUND_VM | MPC_REF_FLAGS;
 // the phases' mask of variant VAR of k_pipeline / k_solve_wg: 0 bounds looked up at run time, 2 the reference's structure, 4 variant 0 with a lower
-// bound per circle row (VM_SIZED: the kernels of mpc_solve_batch_sized, instantiations of their own -- no kernel of another solve reads a flag for it)
+// bound per circle row (VM_SIZED: the kernels of mpc_solve_batch_sized, instantiations of their own -- no kernel of another solve reads a flag for it:
+// k_start / wg_restart<NX, true, SIZED_VM>, k_stage<.., SIZED_VM>, variant 4 of k_pipeline, and k_solve_wg_sized, variant 4 under a name of its own)
 constexpr uint32_t SIZED_VM = 0xFFu | VM_SIZED;
 constexpr uint32_t var_vm(int var) { return var == 2 ? REF_VM : var == 4 ? SIZED_VM : 0xFFu; }
 // One stage workgroup's share of an iteration: the bx instance columns starting at b0.  `tile_bits` is the activity mask
@@ -1237,8 +1238,9 @@ template <int NX, class Src = PrestartFromWs> __device__ __forceinline__ void pr
 // restart of the instance of a one-instance workgroup of k_solve_wg at a level of its second chance: warm start -> tile-major Z, start-point
 // safeguard, start iterate (what k_start does for a block) -- see k_solve_wg<.., RESC>
 // (OSTG: stage_block's; false, the default, is the function variant 2 calls, code as it was -- true the one of variant 0, which a per-stage solve runs)
-// KEEP IN STEP with wg_restart_sized below, a copy of this text: a change here is made there too.
-template <int NX, bool OSTG = false>
+// (VM: the mask of the start iterate's phases; a sized solve, variant 4, calls wg_restart<NX, true, SIZED_VM>.  A template parameter on this one
+//  function leaves the machine code of every instantiation as it was; a body shared through a called helper did not -- DESIGN.md)
+template <int NX, bool OSTG = false, uint32_t VM = 0xFFu>
 __device__ __attribute__((noinline)) void wg_restart(const PRef& Pin, const int n_mult, const int n_z, const int stash_rows, const uint32_t b0, double* lds,
                                                      uint32_t* live_out, const bool carry, const bool from_xs, const bool keep_first, const bool first_tiled) {
     const PRef P = mpc_pref(static_cast<const Params&>(Pin), false);      // (a copy in registers, its cache policy a literal again: the reference points into the caller's stack)
@@ -1289,68 +1291,7 @@ __device__ __attribute__((noinline)) void wg_restart(const PRef& Pin, const int 
     lds_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stage_block<NX, true, 256, 0xFFu, NoStepWait, OSTG>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, false, live_out);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    lds_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-// ... of a sized solve (variant 4): wg_restart<NX, true> with the start iterate's phases instantiated for SIZED_VM.  A copy of its text, on purpose:
-// with the two sharing their body through a function, wg_restart<NX> and its callers k_solve_wg<.., RESC> came out of the compiler with other
-// machine code than before (tools/kernel_hashes.py), and a build of those is trusted only once the GPU suite has passed on it.
-// KEEP IN STEP with wg_restart above: all that differs is the name and the last stage_block's mask and OSTG.
-template <int NX>
-__device__ __attribute__((noinline)) void wg_restart_sized(const PRef& Pin, const int n_mult, const int n_z, const int stash_rows, const uint32_t b0, double* lds,
-                                                           uint32_t* live_out, const bool carry, const bool from_xs, const bool keep_first, const bool first_tiled) {
-    const PRef P = mpc_pref(static_cast<const Params&>(Pin), false);      // (a copy in registers, its cache policy a literal again: the reference points into the caller's stack)
-    using D = Dim<NX>;
-    const int t = threadIdx.x, N = P.N, bx = P.bx;
-    struct { int b, k, mb, bl; } c;
-    c.k = t / bx;
-    c.bl = t & (bx - 1);
-    c.mb = (int)blockIdx.x * bx;
-    c.b = (int)b0 + c.bl;
-    const bool valid = (c.k <= N) && (c.b < P.B);
-    if (valid) {
-        constexpr int NZ = D::NZ;
-        double v[MPC_EV(NZ)];
-        static_assert(2 * MPC_EV(NZ) <= D::NPK, "two iterates fit the cost-to-go rows of a stage");
-        // (first level: the iterate the first attempt stopped at is kept -- behind the warm start in the same scratch rows --, with its KKT
-        //  error; should every level fail, the caller gets that row back, as from rescue_dev: wg_restore_first)
-        if (keep_first) {
-            // (an instance that came out of the pipeline stalled has never been taken over: its iterate is still tile-major)
-            if (first_tiled) ws_load_rows<NZ>(MPC_ROWS(MPC_K(P.Z, NZ, 0, e)), v);
-            else ws_load_rows<NZ>(MPC_ROWS(MPC_KI(P.MZ, NZ, 0, e)), v);
-            ws_store_rows<NZ>(MPC_ROWS(MPC_K(P.PK, D::NPK, 0, MPC_EV(NZ) + e)), v);
-            if (c.k == 0) MPC_S(P.SC, SC_E0S) = (double)MPC_S(P.SC, SC_E0);
-        }
-        // (the scratch of the warm start: the tile-major rows of the cost-to-go, which this kernel does not use)
-        if (carry) {
-            ws_load_rows<NZ>(MPC_ROWS(MPC_KI(P.MZ, NZ, 0, e)), v);
-            ws_store_rows<NZ>(MPC_ROWS(MPC_K(P.PK, D::NPK, 0, e)), v);
-        }
-        if (from_xs) {
-            if (!carry) ws_load_rows<NZ>(MPC_ROWS(MPC_K(P.PK, D::NPK, 0, e)), v);
-        } else {
-            const size_t nw = (size_t)2 * N + (size_t)NX * (N + 1);
-            const double* xr = P.x0 + (size_t)c.b * nw;
-            v[0] = (c.k < N) ? MPC_GP(xr, 2 * c.k) : 0.0;
-            v[1] = (c.k < N) ? MPC_GP(xr, 2 * c.k + 1) : 0.0;
-#pragma unroll
-            for (int i = 0; i < NX; ++i) v[2 + i] = MPC_GP(xr, 2 * N + NX * c.k + i);
-        }
-        ws_store_rows<NZ>(MPC_ROWS(MPC_K(P.Z, NZ, 0, e)), v);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    lds_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    prestart_par_block<NX>(P, b0, lds);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    lds_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stage_block<NX, true, 256, SIZED_VM, NoStepWait, true>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, false, live_out);
+    stage_block<NX, true, 256, VM, NoStepWait, OSTG>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, false, live_out);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1416,6 +1357,31 @@ __device__ __forceinline__ EmitDst wg_emit_dst() {
 #else
 inline EmitDst wg_emit_dst() { return EmitDst{}; }
 #endif
+// the end of k_solve_wg and k_solve_wg_sized.  Params::fin_ctl: the launch is the last of its solve -- the workgroup that leaves LAST copies the
+// solve's statistics block (abort word, rounds, counters of both loop kernels, instances that did not converge: the PH_WORDS words at fin_ctl) into
+// the handle's pinned host block (fin_host), so that the host reads it when the stream has drained: no copy command, no kernel of its own behind
+// the loop.  fin_ctl[PH_FIN_TICKET] counts the workgroups that have left.
+__device__ __forceinline__ void wg_hand_out_stats() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (threadIdx.x < 64) {           // (one wavefront per workgroup)
+        const mpc_kernarg_params kp = wg_kernarg();
+        uint32_t* const ctl = kp->fin_ctl;
+        if (ctl == nullptr) return;
+        uint32_t tk = 0u;
+        if (threadIdx.x == 0) {
+            // (this workgroup's counters are agent-scope atomics: performed once acknowledged -- no cache write-back needed for the last workgroup to
+            //  read them with agent-scope loads; the caller's rows become visible with the end of the kernel)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            tk = __hip_atomic_fetch_add(ctl + PH_FIN_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // counted as gone
+        }
+        tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk);
+        if (tk == gridDim.x - 1u && threadIdx.x < PH_WORDS) {
+            const uint32_t v = __hip_atomic_load(ctl + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(kp->fin_host + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+#endif
+}
 template <int NX, int VAR, bool RESC>
 __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* stats, const uint32_t* skip_if,
                                               const WgRescue& resc, unsigned long long* wtrace, const int32_t* list, const uint32_t* list_n) {
@@ -1575,7 +1541,7 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
                     // (a sized solve: the level scales every row's offset by its fraction -- the scale row of the instance's stages, which this
                     //  workgroup alone reads; the restart's first wait for its stores is in front of every load of it)
                     if (valid) MPC_K(P.OBST,OBST_SIZED_ROWS, 0, OBST_SIZED_SCALE) = resc_fraction(q);
-                    wg_restart_sized<NX>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
+                    wg_restart<NX, true, SIZED_VM>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
                 } else
                 // (per-stage obstacle rows, variant 0 only: the instantiation that reads them -- every other solve keeps the function it had)
                 if (VAR == 2 || Pc.per_inst_obst != OBST_PER_STAGE) wg_restart<NX>(Pc, n_mult, n_z, stash_rows, (uint32_t)ib0, lds, &sh_mask, carry != 0, from_xs, q == 1, rounds == 0u);
@@ -1782,59 +1748,20 @@ __device__ __forceinline__ void solve_wg_body(const Params& Pk, const int n_mult
     }
 #endif
 }
-// (KEEP IN STEP: k_solve_wg_sized below repeats this kernel's epilogue.)
-// Params::fin_ctl: the launch is the last of its solve -- the workgroup that leaves LAST copies the solve's statistics block (abort word, rounds,
-// counters of both loop kernels, instances that did not converge: the PH_WORDS words at fin_ctl) into the handle's pinned host block (fin_host),
-// so that the host reads it when the stream has drained: no copy command, no kernel of its own behind the loop.  fin_ctl[PH_FIN_TICKET] counts the
-// workgroups that have left.
 template <int NX, int VAR, bool RESC = false>
 __global__ void __launch_bounds__(256) k_solve_wg(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* stats, const uint32_t* skip_if,
                                                                    const WgRescue resc, unsigned long long* wtrace, const int32_t* list, const uint32_t* list_n) {
     solve_wg_body<NX, VAR, RESC>(Pk, n_mult, n_z, stash_rows, stats, skip_if, resc, wtrace, list, list_n);
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (threadIdx.x < 64) {           // (one wavefront per workgroup)
-        const mpc_kernarg_params kp = wg_kernarg();
-        uint32_t* const ctl = kp->fin_ctl;
-        if (ctl == nullptr) return;
-        uint32_t tk = 0u;
-        if (threadIdx.x == 0) {
-            // (this workgroup's counters are agent-scope atomics: performed once acknowledged -- no cache write-back needed for the last workgroup to
-            //  read them with agent-scope loads; the caller's rows become visible with the end of the kernel)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            tk = __hip_atomic_fetch_add(ctl + PH_FIN_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // counted as gone
-        }
-        tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk);
-        if (tk == gridDim.x - 1u && threadIdx.x < PH_WORDS) {
-            const uint32_t v = __hip_atomic_load(ctl + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(kp->fin_host + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-#endif
+    wg_hand_out_stats();
 }
-// k_solve_wg of a sized solve: variant 4 of the body (var_vm), the same epilogue (KEEP IN STEP with k_solve_wg above).  A kernel of its own name, not k_solve_wg<NX, 4, RESC>: the
+// k_solve_wg of a sized solve: variant 4 of the body (var_vm).  A kernel of its own name, not k_solve_wg<NX, 4, RESC>: the
 // kernels that call wg_restart find their LDS through a table the compiler indexes by kernel, in the order of the kernels' names -- a further
 // k_solve_wg<5, ..> renumbered k_solve_wg<6, ..> and changed a literal in their code; this name sorts behind them all.
 template <int NX, bool RESC = false>
 __global__ void __launch_bounds__(256) k_solve_wg_sized(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* stats, const uint32_t* skip_if,
                                                         const WgRescue resc, unsigned long long* wtrace, const int32_t* list, const uint32_t* list_n) {
     solve_wg_body<NX, 4, RESC>(Pk, n_mult, n_z, stash_rows, stats, skip_if, resc, wtrace, list, list_n);
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (threadIdx.x < 64) {
-        const mpc_kernarg_params kp = wg_kernarg();
-        uint32_t* const ctl = kp->fin_ctl;
-        if (ctl == nullptr) return;
-        uint32_t tk = 0u;
-        if (threadIdx.x == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            tk = __hip_atomic_fetch_add(ctl + PH_FIN_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk);
-        if (tk == gridDim.x - 1u && threadIdx.x < PH_WORDS) {
-            const uint32_t v = __hip_atomic_load(ctl + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(kp->fin_host + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-#endif
+    wg_hand_out_stats();
 }
 
 // Start-point safeguard with one thread per (instance, stage), the layout of the stage kernel (bx instance columns per workgroup).  The two
@@ -2052,8 +1979,9 @@ __global__ void __launch_bounds__(1024) k_prestart_par(const Params Pk) {
 // zero_p / zero_n: the OTHER control block of the loop kernels, zeroed here for the next solve (the two blocks alternate: a solve in steady state has
 // no fill of its own anywhere on its stream)
 // OSTG: stage_block's -- false, the default, is the kernel of every solve but a per-stage one, code as it was; true that solve's
-// KEEP IN STEP with k_start_sized below, a copy of this text: a change here is made there too.
-template <int NX, bool OSTG = false>
+// VM: the mask of the start iterate's phases -- a sized solve starts with k_start<NX, true, SIZED_VM> (a template parameter, as on wg_restart; the
+// text stays in the kernel, since called from two thin kernels it came out as other machine code)
+template <int NX, bool OSTG = false, uint32_t VM = 0xFFu>
 __global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* zero_p, const uint32_t zero_n) {
     const PRef P(Pk);
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -2121,79 +2049,7 @@ __global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start(const Params Pk, 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     MPC_STAMP(P.DBG, blockIdx.x, KS_FENCED, threadIdx.x == 0);
-    stage_block<NX, true, 256, 0xFFu, NoStepWait, OSTG>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, true, nullptr, true);
-}
-// ... of a sized solve: k_start<NX, true> with the start iterate's phases instantiated for SIZED_VM -- a copy of its text, for wg_restart_sized's reason.
-// KEEP IN STEP with k_start above: all that differs is the name and the last stage_block's mask and OSTG.
-template <int NX>
-__global__ void __launch_bounds__(256, MPC_KSTART_OCC) k_start_sized(const Params Pk, const int n_mult, const int n_z, const int stash_rows, uint32_t* zero_p, const uint32_t zero_n) {
-    const PRef P(Pk);
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    if (zero_p != nullptr && blockIdx.x == 0)
-        for (uint32_t q = threadIdx.x; q < zero_n; q += blockDim.x) zero_p[q] = 0u;
-    uint32_t blk = blockIdx.x;
-    if ((gridDim.x & 7u) == 0u) blk = (blk & 7u) * (gridDim.x >> 3) + (blk >> 3);
-    const uint32_t b0 = (blk + (uint32_t)P.tile0 * (64u / (uint32_t)P.bx)) * (uint32_t)P.bx;
-    MPC_STAMP(P.DBG, blockIdx.x, KS_BEGIN, threadIdx.x == 0);
-    {
-        // ---- the caller's rows of this block (x0, the X_ref part of p: row-major [B][n_w]) -> LDS -> the tile-major Z / REF rows of the
-        //      workspace: what k_ingest does for a whole batch, here for the block's own bx instances (consecutive rows: coalesced reads)
-        constexpr int NZ = NX + 2;
-        const int N = P.N, nw = 2 * N + NX * (N + 1), bx = P.bx, t = threadIdx.x;
-        // LDS: [the safeguard's tables and scan rows (prestart_par_block) | the block's rows of x0 | of the X_ref part of p]: the safeguard reads the
-        // guess and the reference from the last two, so it does not wait for the stores below
-        const size_t pre_doubles = prestart_doubles(NX, N + 1, bx);
-        // (the safeguard's region starts where stage_block keeps its bounds table -- behind the reduction scratch -- and begins with that table: the
-        //  start iterate finds it in place)
-        double* const pre = lds + (blockDim.x >> 6) * 10 * bx;
-        double* rx = pre + ((pre_doubles + 1) & ~(size_t)1);     // [bx][nw]
-        double* rp = rx + bx * nw;                               // [bx][nw - 2N]   (the U_ref part of p is not used by the NLP, optimizer.py:507-511)
-        const int nrow = ((int)b0 + bx <= P.B) ? bx : (P.B > (int)b0 ? P.B - (int)b0 : 0);
-        const int npx = nw - 2 * N;
-        // (every load of a thread requested before its first LDS write: batched_fill; the rows of p one per trip element -- no division)
-        batched_fill<8>(nrow * nw, t, (int)blockDim.x, [&](int q) { return MPC_GP(P.x0, (size_t)b0 * nw + q); }, [&](int q, double v) { rx[q] = v; });
-        for (int r0 = 0; r0 < nrow; r0 += 8) {
-            for (int c0 = 0; c0 < npx; c0 += (int)blockDim.x) {
-                const int col = c0 + t;
-                double v[8];
-#pragma unroll
-                for (int r = 0; r < 8; ++r) v[r] = (r0 + r < nrow && col < npx) ? (double)MPC_GP(P.p, ((size_t)b0 + r0 + r) * nw + 2 * N + col) : 0.0;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) if (r0 + r < nrow && col < npx) rp[(r0 + r) * npx + col] = v[r];
-            }
-        }
-        __syncthreads();
-        MPC_STAMP(P.DBG, blockIdx.x, KS_ROWS, threadIdx.x == 0);
-        struct { int b, k; } c;
-        c.k = t / bx;
-        const int bl = t & (bx - 1);
-        c.b = (int)b0 + bl;
-        if (c.k <= N && c.b < P.B) {
-            double z[NZ], r[NX];
-            const double* xr = rx + bl * nw;
-            z[0] = (c.k < N) ? xr[2 * c.k] : 0.0;
-            z[1] = (c.k < N) ? xr[2 * c.k + 1] : 0.0;
-#pragma unroll
-            for (int i = 0; i < NX; ++i) { z[2 + i] = xr[2 * N + NX * c.k + i]; r[i] = rp[bl * npx + NX * c.k + i]; }
-            ws_store_rows<NZ>(MPC_ROWS(MPC_K(P.Z, NZ, 0, e)), z);
-            ws_store_rows<NX>(MPC_ROWS(MPC_K(P.REF, NX, 0, e)), r);
-        }
-        struct FromLds {
-            const double *rx, *rp;
-            int nw, npx, N;
-            __device__ __forceinline__ double z(int bl, int k, int i) const { return i < 2 ? (k < N ? rx[bl * nw + 2 * k + i] : 0.0) : rx[bl * nw + 2 * N + NX * k + (i - 2)]; }
-            __device__ __forceinline__ double ref0(int bl, int i) const { return rp[bl * npx + i]; }
-        } src{rx, rp, nw, npx, N};
-        MPC_STAMP(P.DBG, blockIdx.x, KS_STORED, threadIdx.x == 0);
-        prestart_par_block<NX, FromLds>(P, b0, pre, src);
-    }
-    MPC_STAMP(P.DBG, blockIdx.x, KS_SAFE, threadIdx.x == 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    MPC_STAMP(P.DBG, blockIdx.x, KS_FENCED, threadIdx.x == 0);
-    stage_block<NX, true, 256, SIZED_VM, NoStepWait, true>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, true, nullptr, true);
+    stage_block<NX, true, 256, VM, NoStepWait, OSTG>(P, n_mult, n_z, stash_rows, b0, ~0ull, lds, true, nullptr, true);
 }
 
 
@@ -3636,7 +3492,7 @@ template <int NX> struct SizedK {
     }
     static auto wg(bool resc) { return resc ? &k_solve_wg_sized<NX, true> : &k_solve_wg_sized<NX>; }
     static auto pipeline() { return &k_pipeline<NX, 4>; }
-    static auto start() { return &k_start_sized<NX>; }
+    static auto start() { return &k_start<NX, true, SIZED_VM>; }
 };
 template <int NX> static auto stage_kernel(bool small_wg, bool init, bool masked, bool sized = false) {
     if (!sized) {
@@ -4860,6 +4716,13 @@ static int traffic_loop_dev(mpc_handle* h, const LoopIo& io, hipStream_t stream)
     if (io.B <= 0) { h->err = "closed loop: B > 0 is required"; return MPC_ERR_INVALID; }
     HIP_TRY(h, hipSetDevice(h->device));
     if (const int rc = offsets_finite(h, io, stream, "traffic loop: every offset must be finite")) return rc;
+    if (io.rsums) {                     // (of mixed sizes: checked as the offsets are, and >= 0)
+        std::vector<double> rs((size_t)(io.per_ego ? io.B : 1) * (size_t)io.M);
+        HIP_TRY(h, hipMemcpyAsync(rs.data(), io.rsums, rs.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(h, hipStreamSynchronize(stream));
+        for (double v : rs)
+            if (!(std::isfinite(v) && v >= 0.0)) { h->err = "sized traffic loop: every entry of rsums must be finite and >= 0"; return MPC_ERR_INVALID; }
+    }
     return closed_loop_dev(h, io, stream);
 }
 int mpc_closed_loop_batch_traffic_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
@@ -4877,21 +4740,10 @@ int mpc_closed_loop_batch_traffic(mpc_handle* h, int32_t B, int32_t L, int32_t L
     return loop_entry(h, with_traffic(io, M, Lt, per_ego, tracks, offsets, pairing, clearance, nearest, chosen), bad_traffic, true, nullptr, traffic_loop_dev);
 }
 
-// ... of mixed sizes: rsums [M] (per_ego: [B, M]) behind offsets, the radius sum of ego and obstacle m; checked as the offsets are, and >= 0
+// ... of mixed sizes: rsums [M] (per_ego: [B, M]) behind offsets, the radius sum of ego and obstacle m (traffic_loop_dev checks its entries)
 static const char* bad_traffic_sized(const mpc_handle* h, const LoopIo& io) {
     if (const char* bad = bad_traffic(h, io)) return bad;
     return io.rsums ? nullptr : "sized traffic loop: rsums [M] (per_ego: [B, M]) are required";
-}
-static int traffic_sized_loop_dev(mpc_handle* h, const LoopIo& io, hipStream_t stream) {
-    if (io.B <= 0) { h->err = "closed loop: B > 0 is required"; return MPC_ERR_INVALID; }
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (const int rc = offsets_finite(h, io, stream, "traffic loop: every offset must be finite")) return rc;
-    std::vector<double> rs((size_t)(io.per_ego ? io.B : 1) * (size_t)io.M);
-    HIP_TRY(h, hipMemcpyAsync(rs.data(), io.rsums, rs.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(h, hipStreamSynchronize(stream));
-    for (double v : rs)
-        if (!(std::isfinite(v) && v >= 0.0)) { h->err = "sized traffic loop: every entry of rsums must be finite and >= 0"; return MPC_ERR_INVALID; }
-    return closed_loop_dev(h, io, stream);
 }
 int mpc_closed_loop_batch_traffic_sized_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
                                             const double* d_orient, const double* d_vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* d_tracks,
@@ -4901,7 +4753,7 @@ int mpc_closed_loop_batch_traffic_sized_dev(mpc_handle* h, int32_t B, int32_t L,
     LoopIo io = with_traffic(LoopIo{B, L, Lp, d_init_state, d_path, d_orient, d_vdes, noise_mode, sigma, seed, d_traj, d_ctrl, d_step_status}, M, Lt, per_ego,
                              d_tracks, d_offsets, pairing, d_clearance, d_nearest, d_chosen);
     io.rsums = d_rsums;
-    return loop_entry(h, io, bad_traffic_sized, false, stream_, traffic_sized_loop_dev);
+    return loop_entry(h, io, bad_traffic_sized, false, stream_, traffic_loop_dev);
 }
 int mpc_closed_loop_batch_traffic_sized(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
                                         const double* vdes, int32_t M, int32_t Lt, int32_t per_ego, const double* tracks, const double* offsets,
@@ -4916,7 +4768,7 @@ int mpc_closed_loop_batch_traffic_sized(mpc_handle* h, int32_t B, int32_t L, int
     if (bad) { h->err = bad; return MPC_ERR_INVALID; }
     const size_t nr = (size_t)(per_ego ? B : 1) * (size_t)M;
     const Stage more[1] = {{rsums, nr * sizeof(double), false}};
-    return stage_loop(h, io, more, [&](LoopIo dio, void** m, hipStream_t s) { dio.rsums = static_cast<const double*>(m[0]); return traffic_sized_loop_dev(h, dio, s); });
+    return stage_loop(h, io, more, [&](LoopIo dio, void** m, hipStream_t s) { dio.rsums = static_cast<const double*>(m[0]); return traffic_loop_dev(h, dio, s); });
 }
 
 // the loop with per-step gains: Lt = 0 with a null track is the plain loop (ogain must then be null); no gain asked for: the loop it wraps
