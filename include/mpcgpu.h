@@ -419,7 +419,31 @@ int mpc_closed_loop_batch_traffic_sized_dev(mpc_handle* h, int32_t B, int32_t L,
  * With measured NULL at every step the record is bit for bit that of the loop it opens (M = 0: mpc_closed_loop_batch_ex; standing obstacles, vx = vy = 0:
  * mpc_closed_loop_batch_traffic with Lt = 1, clearance / nearest / chosen included).  A step ends the life of a sensitivity snapshot, as any solve does.
  * MPC_ERR_STATE: step / record / end without an open session, begin while one is open, step L + 1, bounds not set.  MPC_ERR_INVALID: M < 0; M > 0 with
- * NULL or non-finite offsets; obs NULL with M > 0; measured at step 0; u NULL; pairing or per_ego outside {0, 1}; the shape rules of the loops.       */
+ * NULL or non-finite offsets; obs NULL with M > 0; measured at step 0; u NULL; pairing or per_ego outside {0, 1}; the shape rules of the loops.
+ *
+ * Two things the caller may know better than the session, each an entry point of its own; the four above keep their arguments and their bits.
+ *   mpc_session_begin_sized   a radius per obstacle: the arguments of mpc_session_begin plus rsums behind offsets, in the same shape ([M], per_ego:
+ *                       [B, M]); rsums[m] is the radius sum of ego and obstacle m, copied as the offsets are and checked once, here, as
+ *                       mpc_closed_loop_batch_traffic_sized checks it: finite and >= 0 (the device form copies it back once, next to the offsets).
+ *                       Every step of such a session is a sized solve (mpc_solve_batch_sized_dev's, second chance included) and the selection is by
+ *                       CLEARANCE, as in mpc_closed_loop_batch_traffic_sized: a slot's row carries the winner's centres and the winner's rsums[m];
+ *                       nothing present: the descriptor's centres with the handle's radius, chosen = -1.  clearance is the smallest distance -
+ *                       rsums[m], nearest the obstacle that attains it.  With every rsums[m] equal to the handle's bound every output of every step has
+ *                       the bits of a plain session; with standing obstacles and measured NULL the record, clearance, nearest and chosen are those of
+ *                       mpc_closed_loop_batch_traffic_sized with Lt = 1.  MPC_ERR_INVALID with "rsums" in the message: M < 1, rsums NULL, an entry that
+ *                       is not finite or negative.  MPC_ERR_BOUNDS: the circle rows of the handle have no lower bound or a finite upper one -- checked
+ *                       here, and again at every step (mpc_set_bounds may run between two steps): that step returns the code, is not counted, and the
+ *                       session stays open.
+ *   mpc_session_step_pred     poses predicted by the caller: the arguments of mpc_session_step with obs replaced by pred [M, N+1, 3] (per_ego:
+ *                       [B, M, N+1, 3]) = (x, y, heading) of obstacle m as stage k is to see it, its pose k dt from now -- a trajectory from a
+ *                       prediction module instead of a velocity: a vehicle that turns, cuts in or brakes to a stop.  The rows are taken as they stand.
+ *                       An x that is not finite: absent AT THAT STAGE, so an obstacle may enter or leave within the horizon.  Row 0 is the pose now:
+ *                       clearance and nearest are taken against it.  Everything else -- ingest, the ego pose of the selection, both pairings, ties,
+ *                       solve, advance, emit, the record -- is mpc_session_step's; it works in a plain and in a sized session, and the two step forms
+ *                       may alternate freely within one.  With measured NULL and pred[m, k] = tracks[m, min(i + k, Lt - 1)] at step i the record,
+ *                       clearance, nearest and chosen are bit for bit those of mpc_closed_loop_batch_traffic (a sized session:
+ *                       mpc_closed_loop_batch_traffic_sized) on those tracks.  The device form reads d_pred in stream order and copies nothing back.
+ *                       MPC_ERR_INVALID: a session with M = 0; pred NULL; u NULL; measured at step 0.  MPC_ERR_STATE as mpc_session_step.                 */
 int mpc_session_begin(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
                       const double* vdes, int32_t M, int32_t per_ego, const double* offsets, int32_t pairing);
 int mpc_session_begin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path, const double* d_orient,
@@ -428,6 +452,15 @@ int mpc_session_step(mpc_handle* h, const double* measured, const double* obs, d
                      int32_t* nearest, int32_t* chosen);
 int mpc_session_step_dev(mpc_handle* h, const double* d_measured, const double* d_obs, double* d_u, double* d_plan, int32_t* d_status,
                          double* d_clearance, int32_t* d_nearest, int32_t* d_chosen, void* stream);
+int mpc_session_begin_sized(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                            const double* vdes, int32_t M, int32_t per_ego, const double* offsets, const double* rsums, int32_t pairing);
+int mpc_session_begin_sized_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path,
+                                const double* d_orient, const double* d_vdes, int32_t M, int32_t per_ego, const double* d_offsets,
+                                const double* d_rsums, int32_t pairing, void* stream);
+int mpc_session_step_pred(mpc_handle* h, const double* measured, const double* pred, double* u, double* plan, int32_t* status, double* clearance,
+                          int32_t* nearest, int32_t* chosen);
+int mpc_session_step_pred_dev(mpc_handle* h, const double* d_measured, const double* d_pred, double* d_u, double* d_plan, int32_t* d_status,
+                              double* d_clearance, int32_t* d_nearest, int32_t* d_chosen, void* stream);
 int mpc_session_record(mpc_handle* h, double* traj, double* ctrl, int32_t* step_status);
 int mpc_session_record_dev(mpc_handle* h, double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream);
 int mpc_session_steps_done(const mpc_handle* h);

@@ -106,6 +106,10 @@ PROTOTYPES = {
     "mpc_session_begin_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _i32, _vp, _i32, _vp],
     "mpc_session_step": [_vp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip],
     "mpc_session_step_dev": [_vp] + [_vp] * 8 + [_vp],
+    "mpc_session_begin_sized": [_vp, _i32, _i32, _i32] + [_dp] * 4 + [_i32, _i32, _dp, _dp, _i32],                  # rsums behind offsets
+    "mpc_session_begin_sized_dev": [_vp, _i32, _i32, _i32] + [_vp] * 4 + [_i32, _i32, _vp, _vp, _i32, _vp],
+    "mpc_session_step_pred": [_vp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip],                                         # pred in the place of obs
+    "mpc_session_step_pred_dev": [_vp] + [_vp] * 8 + [_vp],
     "mpc_session_record": [_vp, _dp, _dp, _ip],
     "mpc_session_record_dev": [_vp] + [_vp] * 3 + [_vp],
     "mpc_session_steps_done": [_vp],

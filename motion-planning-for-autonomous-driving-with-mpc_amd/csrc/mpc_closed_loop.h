@@ -418,6 +418,44 @@ struct SessionObsPose {
 MPC_HD void session_traffic_stage(const SessionTrafficArgs& A, int b, int k) {
     loop_traffic_place(TrafficDistance{A.T}, b, k, A.step, 0, SessionObsPose{A, b, (double)k * A.dt});
 }
+// ---- the rest of the square Keys x Pose (mpc_session_begin_sized, mpc_session_step_pred): loop_traffic_place has two axes, and the session above is
+//      one corner of it.
+//        Pose \ Keys          TrafficDistance (a plain session)        TrafficClearance (a sized session: rsums at begin)
+//        TrafficTrackPose     loop_traffic_stage                       loop_traffic_stage_sized            (the loops)
+//        SessionObsPose       session_traffic_stage                    session_traffic_stage_sized
+//        SessionPredPose      session_pred_stage                       session_pred_stage_sized
+//      SessionPredPose: the caller predicts.  pred [M, N+1, 3] (per_ego: [B, M, N+1, 3]) = (x, y, heading) of obstacle m as stage k is to see it, its
+//      pose k dt from now; the thread takes row (b or 0, m, k) as it stands -- no arithmetic, so with pred[m, k] = track[m, min(i + k, Lt - 1)] a
+//      stage computes what loop_traffic_stage[_sized] computes at step i, bit for bit.  x not finite: absent AT THAT STAGE (an obstacle may enter or
+//      leave within the horizon).  Row 0 is the pose now: the stage-0 call takes clearance / nearest against it.  The sized forms select by clearance
+//      and write the packed rows of a sized solve, T.obst [B, N+1, OBST_SIZED_ROWS]; rsums [M] / [B, M] like T.offsets.
+struct SessionTrafficSizedArgs {
+    SessionTrafficArgs S;
+    const double* rsums;
+};
+MPC_HD void session_traffic_stage_sized(const SessionTrafficSizedArgs& A, int b, int k) {
+    loop_traffic_place(TrafficClearance{A.S.T, A.rsums}, b, k, A.S.step, 0, SessionObsPose{A.S, b, (double)k * A.S.dt});
+}
+struct SessionPredArgs {
+    LoopTrafficArgs T;               // tracks / Lt unused; L = 1
+    const double* pred;              // [M,N+1,3] or [B,M,N+1,3]
+    int32_t step;                    // as SessionTrafficArgs::step
+};
+struct SessionPredPose {
+    const SessionPredArgs& A;
+    int b, k;
+    MPC_HD const double* operator()(int m, double*) const { return A.pred + (((size_t)(A.T.per_ego ? b : 0) * A.T.M + m) * (A.T.N + 1) + k) * 3; }
+};
+MPC_HD void session_pred_stage(const SessionPredArgs& A, int b, int k) {
+    loop_traffic_place(TrafficDistance{A.T}, b, k, A.step, 0, SessionPredPose{A, b, k});
+}
+struct SessionPredSizedArgs {
+    SessionPredArgs S;
+    const double* rsums;
+};
+MPC_HD void session_pred_stage_sized(const SessionPredSizedArgs& A, int b, int k) {
+    loop_traffic_place(TrafficClearance{A.S.T, A.rsums}, b, k, A.S.step, 0, SessionPredPose{A.S, b, k});
+}
 
 // =========================================================================================================================
 // The FORCES-mode loop (ForcesproOptimizer.optimize, MPC_Planner/optimizer.py:246-366) around `solver.solve(problem)`:

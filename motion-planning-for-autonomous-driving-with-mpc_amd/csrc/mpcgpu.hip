@@ -2637,6 +2637,20 @@ __global__ void __launch_bounds__(256) k_session_traffic(const SessionTrafficArg
     const int t = blockIdx.x * blockDim.x + threadIdx.x, S = A.T.N + 1;
     if (t < A.T.B * S) session_traffic_stage(A, t / S, t % S);
 }
+// ... the other corners of Keys x Pose (mpc_closed_loop.h), each a kernel of its own in the same grid: observed poses in a sized session (the selection
+// by clearance, the rows written packed for the sized solve), poses predicted by the caller in a plain session, and in a sized one
+__global__ void __launch_bounds__(256) k_session_traffic_sized(const SessionTrafficSizedArgs A) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, S = A.S.T.N + 1;
+    if (t < A.S.T.B * S) session_traffic_stage_sized(A, t / S, t % S);
+}
+__global__ void __launch_bounds__(256) k_session_pred(const SessionPredArgs A) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, S = A.T.N + 1;
+    if (t < A.T.B * S) session_pred_stage(A, t / S, t % S);
+}
+__global__ void __launch_bounds__(256) k_session_pred_sized(const SessionPredSizedArgs A) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, S = A.S.T.N + 1;
+    if (t < A.S.T.B * S) session_pred_stage_sized(A, t / S, t % S);
+}
 // behind k_loop_advance(i): the step's applied control (as recorded), the solution and its status into the caller's rows; plan / status may be null
 __global__ void __launch_bounds__(256) k_session_emit(const LoopArgs A, const int i, double* u, double* plan, int32_t* status) {
     const int nw = 2 * A.N + A.nx * (A.N + 1);
@@ -2956,6 +2970,8 @@ struct LoopSession {
     int32_t step = 0, M = 0, per_ego = 0, pairing = 0;
     LoopArgs A{};                       // B, L, Lp and the rows (init_state: null once mpc_session_begin has returned)
     double *xout = nullptr, *kkt = nullptr, *obst = nullptr, *offsets = nullptr;       // obst [B,N+1,6], offsets: null with M = 0
+    bool sized = false;                 // mpc_session_begin_sized: every step a sized solve, obst [B,N+1,OBST_SIZED_ROWS] packed by the placement kernel
+    double* rsums = nullptr;            // ... its copy of the radius sums, shaped like offsets; null in a plain session
     int32_t *status = nullptr, *iters = nullptr;
 };
 
@@ -4818,24 +4834,40 @@ static int session_refused(mpc_handle* h, bool want_open) {
     return MPC_OK;
 }
 
-static int session_begin_dev(mpc_handle* h, const LoopIo& in, hipStream_t stream) {
+// what the sized session adds to the checks of a session: at begin, and again at every step (mpc_set_bounds may have run in between)
+static const char* const SIZED_SESSION_BOUNDS = "sized session: the circle rows of the handle need a lower bound and no finite upper bound (mpc_set_bounds)";
+static const char* bad_session_sized(const LoopIo& io) {
+    return io.M >= 1 && io.rsums ? nullptr : "sized session: M >= 1 obstacles and rsums [M] (per_ego: [B, M]) are required";
+}
+// sized: mpc_session_begin_sized[_dev] -- in.rsums on the device, shaped like in.offsets
+static int session_begin_dev(mpc_handle* h, const LoopIo& in, hipStream_t stream, bool sized = false) {
     if (const int rc = session_refused(h, false)) return rc;
     if (!nlp_horizon_ok(h)) return MPC_ERR_INVALID;
     if (const char* bad = bad_session_begin(h, in)) { h->err = bad; return MPC_ERR_INVALID; }
+    if (sized)
+        if (const char* bad = bad_session_sized(in)) { h->err = bad; return MPC_ERR_INVALID; }
     if (!h->hp.bounds_set) { h->err = "mpc_set_bounds has not been called"; return MPC_ERR_STATE; }
+    if (sized && (!h->hp.has_ol || h->hp.has_ou)) { h->err = SIZED_SESSION_BOUNDS; return MPC_ERR_BOUNDS; }
     HIP_TRY(h, hipSetDevice(h->device));
     const mpc_problem_desc& d = h->hp.desc;
     const int32_t B = in.B, L = in.L, Lp = in.Lp, M = in.M;
     const size_t nB = (size_t)B, nx = (size_t)d.nx, nw = h->hp.n_w(), nS = (size_t)d.N + 1, nO = M > 0 ? (in.per_ego ? nB : 1) * (size_t)M : 0;
     if (M > 0)
         if (const int rc = offsets_finite(h, in, stream, "session: every offset must be finite")) return rc;
+    if (sized) {                        // (checked once, here, as the sized traffic loop checks them: one small copy back next to the offsets')
+        std::vector<double> rs(nO);
+        HIP_TRY(h, hipMemcpyAsync(rs.data(), in.rsums, nO * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(h, hipStreamSynchronize(stream));
+        for (double v : rs)
+            if (!(std::isfinite(v) && v >= 0.0)) { h->err = "sized session: every entry of rsums must be finite and >= 0"; return MPC_ERR_INVALID; }
+    }
     // one allocation, every piece on a 256-byte boundary
     size_t total = 0;
     const auto take = [&](size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; };
     const size_t o_state = take(nB * nx * 8), o_x0 = take(nB * nw * 8), o_p = take(nB * nw * 8), o_xout = take(nB * nw * 8), o_kkt = take(nB * 8),
-                 o_status = take(nB * 4), o_iters = take(nB * 4), o_obst = take(M > 0 ? nB * nS * 6 * 8 : 0), o_traj = take(nB * L * 5 * 8),
+                 o_status = take(nB * 4), o_iters = take(nB * 4), o_obst = take(M > 0 ? nB * nS * (sized ? (size_t)OBST_SIZED_ROWS : 6) * 8 : 0), o_traj = take(nB * L * 5 * 8),
                  o_ctrl = take(nB * L * 2 * 8), o_sst = take(nB * L * 4), o_path = take(nB * Lp * 2 * 8), o_orient = take(nB * Lp * 8), o_vdes = take(nB * 8),
-                 o_off = take(nO * 8);
+                 o_off = take(nO * 8), o_rsums = take(sized ? nO * 8 : 0);
     void* base = nullptr;
     if (hipMalloc(&base, total) != hipSuccess) { h->err = "session: out of device memory"; return MPC_ERR_HIP; }
     char* c = static_cast<char*>(base);
@@ -4844,6 +4876,7 @@ static int session_begin_dev(mpc_handle* h, const LoopIo& in, hipStream_t stream
     S.base = base; S.M = M; S.per_ego = in.per_ego; S.pairing = in.pairing;
     S.xout = dbl(o_xout); S.kkt = dbl(o_kkt); S.obst = M > 0 ? dbl(o_obst) : nullptr; S.offsets = M > 0 ? dbl(o_off) : nullptr;
     S.status = reinterpret_cast<int32_t*>(c + o_status); S.iters = reinterpret_cast<int32_t*>(c + o_iters);
+    S.sized = sized; S.rsums = sized ? dbl(o_rsums) : nullptr;
     // the session's loop: the caller's init_state, its own copies of the other inputs and its own record
     const LoopIo own{B, L, Lp, in.init_state, dbl(o_path), dbl(o_orient), dbl(o_vdes), 0, 0.0, 0, dbl(o_traj), dbl(o_ctrl), reinterpret_cast<int32_t*>(c + o_sst)};
     LoopArgs& A = S.A = loop_args(h, own, dbl(o_state), dbl(o_x0), dbl(o_p), S.xout, S.status);
@@ -4852,6 +4885,7 @@ static int session_begin_dev(mpc_handle* h, const LoopIo& in, hipStream_t stream
     if (e == hipSuccess) e = hipMemcpyAsync(dbl(o_orient), in.orient, nB * Lp * 8, hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dbl(o_vdes), in.vdes, nB * 8, hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess && M > 0) e = hipMemcpyAsync(S.offsets, in.offsets, nO * 8, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess && sized) e = hipMemcpyAsync(S.rsums, in.rsums, nO * 8, hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess) e = hipMemsetAsync(A.traj, 0xFF, nB * L * 5 * 8, stream);              // (all bits set: NaN)
     if (e == hipSuccess) e = hipMemsetAsync(A.ctrl, 0xFF, nB * L * 2 * 8, stream);
     if (e == hipSuccess) e = hipMemsetAsync(A.step_status, 0, nB * L * 4, stream);
@@ -4882,29 +4916,61 @@ int mpc_session_begin_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const
     return session_begin_dev(h, session_io(B, L, Lp, d_init_state, d_path, d_orient, d_vdes, M, per_ego, d_offsets, pairing), (hipStream_t)stream_);
 }
 
-int mpc_session_step_dev(mpc_handle* h, const double* d_measured, const double* d_obs, double* d_u, double* d_plan, int32_t* d_status, double* d_clearance,
-                         int32_t* d_nearest, int32_t* d_chosen, void* stream_) {
+// ... with a radius sum per obstacle: rsums behind offsets, staged beside the table's arrays as the sized traffic loop stages its own
+int mpc_session_begin_sized(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* init_state, const double* path, const double* orient,
+                            const double* vdes, int32_t M, int32_t per_ego, const double* offsets, const double* rsums, int32_t pairing) {
+    if (const int rc = session_refused(h, false)) return rc;
+    LoopIo io = session_io(B, L, Lp, init_state, path, orient, vdes, M, per_ego, offsets, pairing);
+    io.rsums = rsums;
+    const char* bad = bad_session_begin(h, io);
+    if (!bad) bad = bad_session_sized(io);
+    if (bad) { h->err = bad; return MPC_ERR_INVALID; }
+    const Stage more[1] = {{rsums, (size_t)(per_ego ? B : 1) * (size_t)M * sizeof(double), false}};
+    return stage_loop(h, io, more, [&](LoopIo dio, void** m, hipStream_t s) { dio.rsums = static_cast<const double*>(m[0]); return session_begin_dev(h, dio, s, true); });
+}
+int mpc_session_begin_sized_dev(mpc_handle* h, int32_t B, int32_t L, int32_t Lp, const double* d_init_state, const double* d_path, const double* d_orient,
+                                const double* d_vdes, int32_t M, int32_t per_ego, const double* d_offsets, const double* d_rsums, int32_t pairing, void* stream_) {
+    LoopIo io = session_io(B, L, Lp, d_init_state, d_path, d_orient, d_vdes, M, per_ego, d_offsets, pairing);
+    io.rsums = d_rsums;
+    return session_begin_dev(h, io, (hipStream_t)stream_, true);
+}
+
+// One step of either form.  predicted false: d_poses is obs [M, 5] (mpc_session_step_dev); true: pred [M, N+1, 3] (mpc_session_step_pred_dev).  The two
+// differ in the placement kernel launched in front of the solve -- and a sized session differs from a plain one in that kernel and in the solve's rows
+static int session_step_dev(mpc_handle* h, const double* d_measured, const double* d_poses, bool predicted, double* d_u, double* d_plan, int32_t* d_status,
+                            double* d_clearance, int32_t* d_nearest, int32_t* d_chosen, void* stream_) {
     if (const int rc = session_refused(h, true)) return rc;
     LoopSession& S = h->session;
     const LoopArgs& A = S.A;
     if (S.step >= A.L) { h->err = "session: all L steps have been taken (mpc_session_end, then mpc_session_begin)"; return MPC_ERR_STATE; }
     if (!d_u) { h->err = "session: u [B, 2] is required"; return MPC_ERR_INVALID; }
     if (d_measured && S.step == 0) { h->err = "session: step 0 takes no measured state (init_state of mpc_session_begin is the measurement)"; return MPC_ERR_INVALID; }
-    if (S.M > 0 && !d_obs) { h->err = "session: obs [M, 5] (per_ego: [B, M, 5]) is required, the session has M > 0 obstacles"; return MPC_ERR_INVALID; }
+    if (predicted && S.M == 0) { h->err = "session: predicted poses need obstacles, the session has M = 0 (mpc_session_step)"; return MPC_ERR_INVALID; }
+    if (predicted && !d_poses) { h->err = "session: pred [M, N+1, 3] (per_ego: [B, M, N+1, 3]) is required"; return MPC_ERR_INVALID; }
+    if (S.M > 0 && !d_poses) { h->err = "session: obs [M, 5] (per_ego: [B, M, 5]) is required, the session has M > 0 obstacles"; return MPC_ERR_INVALID; }
     if (S.M == 0 && (d_clearance || d_nearest || d_chosen)) { h->err = "session: clearance, nearest and chosen need obstacles (M > 0)"; return MPC_ERR_INVALID; }
     const mpc_problem_desc& d = h->hp.desc;
     const int32_t B = A.B, i = S.step;
     SolveIo io = solve_io(h, B, A.x0, A.p, S.obst, S.xout, S.status, S.iters, S.kkt);
     if (S.M > 0) io = stages_io(h, io);
-    if (const int rc = begin_solve(h, io)) return rc;
+    if (S.sized) { io.n_obst = (size_t)OBST_SIZED_ROWS * (size_t)(d.N + 1); io.sized = true; }
+    if (const int rc = S.sized ? begin_sized(h, io, S.rsums) : begin_solve(h, io)) return rc;
     const hipStream_t stream = (hipStream_t)stream_;
     if (d_measured) hipLaunchKernelGGL(k_session_ingest, dim3((B + 127) / 128), dim3(128), 0, stream, SessionIngestArgs{B, d.N, d.nx, d_measured, A.state, A.p});
     if (S.M > 0) {
-        LoopIo one;                     // this step as a loop of one step through the observed traffic (no tracks)
+        LoopIo one;                     // this step as a loop of one step through the observed or predicted traffic (no tracks)
         one.B = B; one.L = 1; one.M = S.M; one.per_ego = S.per_ego; one.pairing = S.pairing; one.offsets = S.offsets;
         one.clearance = d_clearance; one.nearest = d_nearest; one.chosen = d_chosen;
-        const SessionTrafficArgs T{loop_traffic_args(h, one, S.obst, A), d_obs, d.dt, i};
-        hipLaunchKernelGGL(k_session_traffic, dim3((B * (d.N + 1) + 255) / 256), dim3(256), 0, stream, T);
+        const dim3 grid((B * (d.N + 1) + 255) / 256), block(256);
+        if (!predicted) {
+            const SessionTrafficArgs T{loop_traffic_args(h, one, S.obst, A), d_poses, d.dt, i};
+            if (S.sized) hipLaunchKernelGGL(k_session_traffic_sized, grid, block, 0, stream, SessionTrafficSizedArgs{T, S.rsums});
+            else hipLaunchKernelGGL(k_session_traffic, grid, block, 0, stream, T);
+        } else {
+            const SessionPredArgs T{loop_traffic_args(h, one, S.obst, A), d_poses, i};
+            if (S.sized) hipLaunchKernelGGL(k_session_pred_sized, grid, block, 0, stream, SessionPredSizedArgs{T, S.rsums});
+            else hipLaunchKernelGGL(k_session_pred, grid, block, 0, stream, T);
+        }
     }
     if (const int rc = solve_dev(h, io, stream)) return rc;
     hipLaunchKernelGGL(k_loop_advance, dim3(B), dim3(128), 0, stream, plant_params(h), A, i);
@@ -4913,17 +4979,35 @@ int mpc_session_step_dev(mpc_handle* h, const double* d_measured, const double* 
     ++S.step;
     return MPC_OK;
 }
+int mpc_session_step_dev(mpc_handle* h, const double* d_measured, const double* d_obs, double* d_u, double* d_plan, int32_t* d_status, double* d_clearance,
+                         int32_t* d_nearest, int32_t* d_chosen, void* stream_) {
+    return session_step_dev(h, d_measured, d_obs, false, d_u, d_plan, d_status, d_clearance, d_nearest, d_chosen, stream_);
+}
+int mpc_session_step_pred_dev(mpc_handle* h, const double* d_measured, const double* d_pred, double* d_u, double* d_plan, int32_t* d_status,
+                              double* d_clearance, int32_t* d_nearest, int32_t* d_chosen, void* stream_) {
+    return session_step_dev(h, d_measured, d_pred, true, d_u, d_plan, d_status, d_clearance, d_nearest, d_chosen, stream_);
+}
 
-int mpc_session_step(mpc_handle* h, const double* measured, const double* obs, double* u, double* plan, int32_t* status, double* clearance,
-                     int32_t* nearest, int32_t* chosen) {
+// the host-pointer form of a step: `poses` is obs (5 doubles per obstacle) or pred (3 (N + 1) per obstacle)
+static int session_step_host(mpc_handle* h, const double* measured, const double* poses, bool predicted, double* u, double* plan, int32_t* status,
+                             double* clearance, int32_t* nearest, int32_t* chosen) {
     if (const int rc = session_refused(h, true)) return rc;
     const LoopSession& S = h->session;
     const size_t nB = (size_t)S.A.B, nO = (S.per_ego ? nB : 1) * (size_t)S.M, nS = (size_t)S.A.N + 1;
-    return stage_host(h, {{measured, nB * 5 * 8, false}, {S.M > 0 ? obs : nullptr, nO * 5 * 8, false}, {u, nB * 2 * 8, true}, {plan, nB * h->hp.n_w() * 8, true},
-                          {status, nB * 4, true}, {clearance, nB * 8, true}, {nearest, nB * 4, true}, {chosen, nB * nS * 3 * 4, true}},
+    return stage_host(h, {{measured, nB * 5 * 8, false}, {S.M > 0 ? poses : nullptr, nO * (predicted ? nS * 3 : 5) * 8, false}, {u, nB * 2 * 8, true},
+                          {plan, nB * h->hp.n_w() * 8, true}, {status, nB * 4, true}, {clearance, nB * 8, true}, {nearest, nB * 4, true},
+                          {chosen, nB * nS * 3 * 4, true}},
                       [&](void** d, hipStream_t s) {
-        return mpc_session_step_dev(h, (double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3], (int32_t*)d[4], (double*)d[5], (int32_t*)d[6], (int32_t*)d[7], s);
+        return session_step_dev(h, (double*)d[0], (double*)d[1], predicted, (double*)d[2], (double*)d[3], (int32_t*)d[4], (double*)d[5], (int32_t*)d[6], (int32_t*)d[7], s);
     });
+}
+int mpc_session_step(mpc_handle* h, const double* measured, const double* obs, double* u, double* plan, int32_t* status, double* clearance,
+                     int32_t* nearest, int32_t* chosen) {
+    return session_step_host(h, measured, obs, false, u, plan, status, clearance, nearest, chosen);
+}
+int mpc_session_step_pred(mpc_handle* h, const double* measured, const double* pred, double* u, double* plan, int32_t* status, double* clearance,
+                          int32_t* nearest, int32_t* chosen) {
+    return session_step_host(h, measured, pred, true, u, plan, status, clearance, nearest, chosen);
 }
 
 int mpc_session_record_dev(mpc_handle* h, double* d_traj, double* d_ctrl, int32_t* d_step_status, void* stream_) {

@@ -433,17 +433,19 @@ class CasadiOptimizer(Optimizer):
 
     def open_session(self):
         """The loop of optimize() stepped from outside (BatchedMPCSolver.session), built from the configuration as optimize() builds its device loop:
-        the bounds of inequal_constraints() (the radius of the largest obstacle), the initial state, the path, its orientation, the desired velocity,
+        the bounds of inequal_constraints() (the radius of the largest obstacle; with obstacle_radii = "own" every obstacle's own radius sum is handed
+        over besides, and the session is a sized one, as optimize()'s loop is), the initial state, the path, its orientation, the desired velocity,
         and with `obstacle_sizes` [M, 2] the obstacles' offsets and `obstacle_pairing` -- no tracks are needed (nor handed over when the configuration has
         some): the caller observes the obstacles.  Without `obstacle_sizes` the session is lane following (M = 0) past the static obstacle.  A simulator loop is `with o.open_session() as sess: u = sess.step(measured, obstacles)`, one ego: u [1, 2],
-        measured [5] (None at step 0), obstacles [M, 5] = (x, y, heading, vx, vy) now."""
+        measured [5] (None at step 0), obstacles [M, 5] = (x, y, heading, vx, vy) now -- or predicted=[M, N+1, 3], the poses a prediction module gives for the stages."""
         lbg, ubg, lbx, ubx = self.inequal_constraints()
         backend = self.solver()[0]._backend
         backend.set_bounds(lbx, ubx, lbg, ubg)
         init_state = np.array([self.init_position[0], self.init_position[1], 0.0, self.init_velocity, self.init_orientation])
         traffic = self.obstacle_offsets is not None
         return backend.session(init_state, self.resampled_path_points, self.orientation, self.desired_velocity, self.iter_length,
-                               offsets=self.obstacle_offsets if traffic else None, per_ego=0, pairing=self.obstacle_pairing if traffic else 0)
+                               offsets=self.obstacle_offsets if traffic else None, per_ego=0, pairing=self.obstacle_pairing if traffic else 0,
+                               **({} if not traffic or self.obstacle_rsums is None else dict(rsums=self.obstacle_rsums)))
 
     def ego_offset(self):
         """front / rear circle centres of the ego: +- disc_distance / 4 of its rectangle along its heading (what solver() hands the backend)"""

@@ -669,11 +669,13 @@ class BatchedMPCSolver:
                                                                 float(sigma), int(seed) & (2 ** 64 - 1), _vp(d_traj), _vp(d_ctrl), _vp(d_step_status),
                                                                 _vp(d_clearance), _vp(d_nearest), _vp(d_chosen), _vp(stream)))
 
-    def session(self, init_state, path, orient, vdes, steps, offsets=None, per_ego=None, pairing=0):
+    def session(self, init_state, path, orient, vdes, steps, offsets=None, per_ego=None, pairing=0, rsums=None):
         """the loop stepped from outside (mpc_session_begin): a LoopSession, `with solver.session(...) as sess: u = sess.step(measured, obstacles)`.
         The arguments of closed_loop_traffic that do not change over a loop; offsets None: lane following (M = 0), [M]: obstacles shared by all egos,
-        [B, M]: per ego (per_ego overrides what the shape says, e.g. B = 1).  One session per solver; everything is copied."""
-        return LoopSession(self, init_state, path, orient, vdes, steps, offsets, per_ego, pairing)
+        [B, M]: per ego (per_ego overrides what the shape says, e.g. B = 1).  One session per solver; everything is copied.
+        rsums (shaped like offsets; None: the call without it): a sized session (mpc_session_begin_sized) -- rsums[m] is the radius sum of ego and
+        obstacle m, the selection is by clearance and every step is a sized solve, as in closed_loop_traffic(rsums=)."""
+        return LoopSession(self, init_state, path, orient, vdes, steps, offsets, per_ego, pairing, rsums)
 
     def closed_loop_lin_device(self, B, d_init_state, d_path, d_orient, d_vdes, steps, Lp, d_traj, d_ctrl, d_step_status=0, noise_mode=0, sigma=0.0,
                                seed=0, stream=0, d_obst_track=0, Lt=0, obst_offset=0.0, d_clearance=0, d_kgain=0, d_wgain=0, d_ogain=0):
@@ -953,11 +955,13 @@ class LoopSession:
                 u = sess.step(measured, obstacles)              # measured [B, 5] (NaN x: dropped), obstacles [M, 5] / [B, M, 5]
             traj, ctrl, status = sess.record()
 
-    Between two steps the solver may be used for anything else; set_weights / set_bounds take effect at the next step."""
+    A caller with a prediction module hands over trajectories instead of velocities, sess.step(measured, predicted=pred) with pred [M, N+1, 3] /
+    [B, M, N+1, 3] (mpc_session_step_pred); the two kinds of step may alternate.  rsums (shaped like offsets): a radius sum per obstacle
+    (mpc_session_begin_sized).  Between two steps the solver may be used for anything else; set_weights / set_bounds take effect at the next step."""
 
     OUTPUTS = ("plan", "status", "clearance", "nearest", "chosen")
 
-    def __init__(self, solver, init_state, path, orient, vdes, steps, offsets=None, per_ego=None, pairing=0):
+    def __init__(self, solver, init_state, path, orient, vdes, steps, offsets=None, per_ego=None, pairing=0, rsums=None):
         self._s = solver
         init_state, path, orient, vdes, B, Lp = _loop_in(init_state, path, orient, vdes)
         self.B, self.steps, self.M, self.per_ego = B, int(steps), 0, 0
@@ -967,10 +971,21 @@ class LoopSession:
             if offsets.ndim not in (1, 2) or (self.per_ego == 1 and offsets.shape[0] != B):
                 raise MpcError(_abi.MPC_ERR_INVALID, "offsets must be [M], or [B, M] for obstacles per ego")
             self.M = offsets.shape[-1]
+        if rsums is not None:
+            rsums = _abi.f64(rsums)
+            if offsets is None or rsums.shape != offsets.shape:
+                raise MpcError(_abi.MPC_ERR_INVALID, "rsums must have the shape of offsets")
+            rsums = rsums.reshape(-1)
+        if offsets is not None:
             offsets = offsets.reshape(-1)
+        self.sized = rsums is not None
         self._open = False
-        solver._check(solver._lib.mpc_session_begin(solver._h, B, self.steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient), _abi.as_dp(vdes),
-                                                    self.M, self.per_ego, _abi.as_dp(offsets), int(pairing)))
+        head = (solver._h, B, self.steps, Lp, _abi.as_dp(init_state), _abi.as_dp(path), _abi.as_dp(orient), _abi.as_dp(vdes), self.M, self.per_ego,
+                _abi.as_dp(offsets))
+        if rsums is None:
+            solver._check(solver._lib.mpc_session_begin(*head, int(pairing)))
+        else:
+            solver._check(solver._lib.mpc_session_begin_sized(*head, _abi.as_dp(rsums), int(pairing)))
         self._open = True
 
     def __enter__(self):
@@ -989,12 +1004,15 @@ class LoopSession:
         """the index of the next step (mpc_session_steps_done)"""
         return int(self._s._lib.mpc_session_steps_done(self._s._h))
 
-    def step(self, measured=None, obstacles=None, outputs=()):
+    def step(self, measured=None, obstacles=None, predicted=None, outputs=()):
         """one step (mpc_session_step) -> u [B, 2], the control to apply; with outputs, a tuple of names out of OUTPUTS, -> (u, *those arrays):
         plan [B, n_w] the solution, status [B], and with obstacles this step's clearance [B], nearest [B], chosen [B, N+1, 3].
         measured [B, 5]: the plant's state now (None: the model's own prediction; None at step 0); obstacles [M, 5] or [B, M, 5]: (x, y, heading, vx, vy)
-        now, NaN x: absent"""
+        now, NaN x: absent.  predicted [M, N+1, 3] or [B, M, N+1, 3] in the place of obstacles (mpc_session_step_pred): (x, y, heading) of obstacle m
+        as stage k is to see it, row 0 its pose now, NaN x: absent at that stage"""
         s, B = self._s, self.B
+        if obstacles is not None and predicted is not None:
+            raise MpcError(_abi.MPC_ERR_INVALID, "a step takes obstacles (observed poses and velocities) or predicted (poses per stage), not both")
         unknown = [o for o in outputs if o not in self.OUTPUTS]
         if unknown:
             raise MpcError(_abi.MPC_ERR_INVALID, f"outputs: {unknown} not in {self.OUTPUTS}")
@@ -1002,21 +1020,33 @@ class LoopSession:
             measured = _abi.f64(measured, (B, 5))
         if obstacles is not None:
             obstacles = _abi.f64(obstacles, ((B,) if self.per_ego else ()) + (self.M, 5))
+        if predicted is not None:
+            predicted = _abi.f64(predicted, ((B,) if self.per_ego else ()) + (self.M, s.N + 1, 3))
         out = dict(plan=np.empty((B, s.n_w)), status=np.empty(B, np.int32), clearance=np.empty(B), nearest=np.empty(B, np.int32),
                    chosen=np.empty((B, s.N + 1, 3), np.int32))
         out = {k: (v if k in outputs else None) for k, v in out.items()}
         u = np.empty((B, 2))
         s._sens_gen += 1                                     # (a step is a solve: the library has ended the life of an earlier snapshot)
-        s._check(s._lib.mpc_session_step(s._h, _abi.as_dp(measured), _abi.as_dp(obstacles), _abi.as_dp(u), _abi.as_dp(out["plan"]), _abi.as_ip(out["status"]),
-                                         _abi.as_dp(out["clearance"]), _abi.as_ip(out["nearest"]), _abi.as_ip(out["chosen"])))
+        tail = (_abi.as_dp(u), _abi.as_dp(out["plan"]), _abi.as_ip(out["status"]), _abi.as_dp(out["clearance"]), _abi.as_ip(out["nearest"]),
+                _abi.as_ip(out["chosen"]))
+        if predicted is None:
+            s._check(s._lib.mpc_session_step(s._h, _abi.as_dp(measured), _abi.as_dp(obstacles), *tail))
+        else:
+            s._check(s._lib.mpc_session_step_pred(s._h, _abi.as_dp(measured), _abi.as_dp(predicted), *tail))
         return (u, *[out[o] for o in outputs]) if outputs else u
 
-    def step_device(self, d_u, d_measured=0, d_obs=0, d_plan=0, d_status=0, d_clearance=0, d_nearest=0, d_chosen=0, stream=0):
-        """device-pointer form (ints; 0 = absent) of step (mpc_session_step_dev): enqueued on `stream`, the solve synchronises it"""
+    def step_device(self, d_u, d_measured=0, d_obs=0, d_plan=0, d_status=0, d_clearance=0, d_nearest=0, d_chosen=0, stream=0, d_pred=0):
+        """device-pointer form (ints; 0 = absent) of step (mpc_session_step_dev): enqueued on `stream`, the solve synchronises it.  d_pred in the
+        place of d_obs: mpc_session_step_pred_dev"""
         s = self._s
+        if d_obs and d_pred:
+            raise MpcError(_abi.MPC_ERR_INVALID, "a step takes d_obs or d_pred, not both")
         s._sens_gen += 1
-        s._check(s._lib.mpc_session_step_dev(s._h, _vp(d_measured), _vp(d_obs), _vp(d_u), _vp(d_plan), _vp(d_status), _vp(d_clearance), _vp(d_nearest),
-                                             _vp(d_chosen), _vp(stream)))
+        tail = (_vp(d_u), _vp(d_plan), _vp(d_status), _vp(d_clearance), _vp(d_nearest), _vp(d_chosen), _vp(stream))
+        if d_pred:
+            s._check(s._lib.mpc_session_step_pred_dev(s._h, _vp(d_measured), _vp(d_pred), *tail))
+        else:
+            s._check(s._lib.mpc_session_step_dev(s._h, _vp(d_measured), _vp(d_obs), *tail))
 
     def record(self):
         """(traj [B, steps, 5], ctrl [B, steps, 2], step_status [B, steps]) as recorded so far (mpc_session_record); steps not yet taken: NaN / 0"""
